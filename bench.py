@@ -11,8 +11,10 @@ Workload (BASELINE.json configs[2], the configuration the metric is quoted on):
             on each rank's row shard -> per-rank [256, 5] (score, global row) -> RCCL all-gather
             -> host merge (N > 1) -> results in host memory.  The corpus is fixed at 1M rows
             and split row-wise over the N ranks (strong scaling).
-  embed:    (reported under "embed") encoder forward of bge-base-shaped chunks -> chunks/s.
+  embed:    (reported under "embed", --full only) encoder forward of bge-base-shaped chunks -> chunks/s.
 Inputs are resident in HBM before the timed region.  One JSON line is printed by rank 0.
+A plain run times the retrieve steps only; --full adds the measured peaks, the CPU baselines and parity check
+against the oracle, the served legs and the embed leg.  --dump-outputs DIR writes the last timed step's results.
 """
 from __future__ import annotations
 
@@ -214,7 +216,20 @@ def main():
                     help="where the G*k -> k merge runs for N > 1 (north star: host)")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo = rehearsal on a one-GPU box (collective on host copies); the driver uses nccl (RCCL)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: measured peaks, CPU baselines and the parity check "
+                         "against the oracle, the served legs, the embed leg (each can still be dropped with its --no-* "
+                         "option). Without it only the retrieve steps are timed.")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's results (scores.npy float32 [batch, k], "
+                         "rows.npy float64 [batch, k], global corpus rows) into DIR")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.hnsw_baseline > 0 and not args.full:
+        ap.error("--hnsw-baseline is part of --full")
+    if not args.full:
+        args.no_cpu_baseline = args.no_served = args.no_peaks = args.no_embed = True
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -336,6 +351,10 @@ def main():
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in events.values()])) if events else float("nan")
     gpu_s = final["s"].clone().numpy()
     gpu_r = final["r"].clone().numpy()
+    if rank == 0 and args.dump_outputs:   # every rank holds the same merged results; one copy is enough
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), gpu_s.astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "rows.npy"), gpu_r.astype(np.float64))
 
     result = None
     if rank == 0:

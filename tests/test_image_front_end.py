@@ -12,12 +12,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 GOLD = os.path.join(ROOT, "tests", "golden")
 
 from oracle import clip_oracle as C  # noqa: E402
-from make_resize_golden import SIZES, formula_image  # noqa: E402  (pure numpy helpers)
+from make_resize_golden import SIZES, formula_image, load_expected  # noqa: E402  (pure numpy helpers)
 
 
 @pytest.fixture(scope="module")
 def expected():
-    return np.load(os.path.join(GOLD, "resize_expected.npz"))
+    return load_expected(GOLD)
 
 
 def page_region():

@@ -13,7 +13,7 @@ prof() {   # prof <subdir> <rocprofv3 args...> -- <command...>
     find "$OUT/$sub" -name "*.db" -delete 2>/dev/null
     echo "[profile_round] $sub: $(find "$OUT/$sub" -name '*.csv' | wc -l) csv files"
 }
-timeout -k 10 600 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "[profile_round] bench rc=$? $(cut -c1-160 "$OUT/bench.json")"
+timeout -k 10 600 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "[profile_round] bench rc=$? $(cut -c1-160 "$OUT/bench.json")"
 prof stats --kernel-trace --stats --output-format csv -d "$OUT/stats" -o s -- $BENCH
 prof pmc_fetch --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o c -- $BENCH --steps 10 --warmup 2
 prof pmc_write --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o c -- $BENCH --steps 10 --warmup 2
