@@ -84,6 +84,22 @@ int mmrag_cosine_topk_lists(const void *q, const void *corpus, int B, int64_t n,
 int mmrag_cosine_topk_select(int B, int64_t n, int k, int64_t row_offset, const void *workspace,
                              float *out_scores, int64_t *out_rows, void *stream);
 
+/* Deep exact top-k: the same search for any k in 1..MMRAG_MAX_K_DEEP (Chroma's n_results has no cap of 20).
+ * Same arguments, layout, ordering, padding and error codes as mmrag_cosine_topk; scores are bit-identical to
+ * it (the same GEMM), and its first 20 results are those of mmrag_cosine_topk(k = 20).  A bound from a strided
+ * sample, a threshold-filter scan into per-query candidate buffers and a per-query radix select, all
+ * stream-ordered on `stream`; a query whose survivors overflow its buffer is re-run alone, exactly.
+ * It SYNCHRONISES `stream` once (to read the per-query survivor counts; not at all when n is small enough that
+ * nothing can overflow), so it cannot be captured into a graph.
+ *   workspace  dev, >= mmrag_cosine_topk_deep_workspace_bytes(B, n, k) bytes, 16-byte aligned
+ *              (0 outside k = 1..MMRAG_MAX_K_DEEP; grows with n: it holds one query x n candidates) */
+#define MMRAG_MAX_K_DEEP 4096
+size_t mmrag_cosine_topk_deep_workspace_bytes(int B, int64_t n, int k);
+int mmrag_cosine_topk_deep(const void *q, const void *corpus, int B, int64_t n, int d, int64_t ld,
+                           int dtype, int k, int64_t row_offset, const uint32_t *alive_bits,
+                           float *out_scores, int64_t *out_rows, void *workspace,
+                           size_t workspace_bytes, void *stream);
+
 /* Merge G shards' local top-k (layout [G, B, k_in], as produced by an all-gather of
  * mmrag_cosine_topk outputs) into the global top-k [B, k].  Device version (one tiny
  * kernel) and host version (north star: "final host merge"); identical ordering rule.

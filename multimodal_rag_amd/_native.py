@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(_PKG, "lib", "libmmrag.so")
 
 F32, F16, BF16 = 0, 1, 2
 MAX_K = 20
+MAX_K_DEEP = 4096   # mmrag_cosine_topk_deep
 _TORCH2DT = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 _DT2TORCH = {v: k for k, v in _TORCH2DT.items()}
 
@@ -51,6 +52,13 @@ def _declare(lib):
                                                         c_int, c_void_p, c_void_p, c_size_t, c_void_p, ctypes.c_uint]
     lib.mmrag_cosine_topk_select.restype = c_int
     lib.mmrag_cosine_topk_select.argtypes = [c_int, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.mmrag_cosine_topk_deep_workspace_bytes.restype = c_size_t
+    lib.mmrag_cosine_topk_deep_workspace_bytes.argtypes = [c_int, c_int64, c_int]
+    lib.mmrag_cosine_topk_deep.restype = c_int
+    lib.mmrag_cosine_topk_deep.argtypes = lib.mmrag_cosine_topk.argtypes
+    # debug form of mmrag_cosine_topk_deep (csrc/search_deep.hip, not in include/mmrag.h): switches + candidate capacity
+    lib.mmrag_internal_cosine_topk_deep_ex.restype = c_int
+    lib.mmrag_internal_cosine_topk_deep_ex.argtypes = lib.mmrag_cosine_topk.argtypes + [ctypes.c_uint, c_int64]
     lib.mmrag_merge_topk.restype = c_int
     lib.mmrag_merge_topk.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.mmrag_merge_topk_host.restype = c_int
@@ -220,6 +228,43 @@ def cosine_topk(q: torch.Tensor, corpus: torch.Tensor, n: int, d: int, k: int, r
                                  workspace.numel() * workspace.element_size(), _stream_ptr(q.device))
     _check(st, "mmrag_cosine_topk")
     return out_s, out_r
+
+
+# debug switch of the deep search (tests only): no bound passes, every live row is a candidate of the main pass
+DEEP_DBG_NO_BOUND = 1
+
+
+def cosine_topk_deep(q: torch.Tensor, corpus: torch.Tensor, n: int, d: int, k: int, row_offset: int = 0,
+                     alive_bits: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                     dbg: int = 0, cap: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact cosine top-k for any k in 1..MAX_K_DEEP (include/mmrag.h mmrag_cosine_topk_deep): the same arguments and
+    results as cosine_topk, scores bit-identical to it.  Synchronises the current stream once (the survivor counts).
+    `dbg` / `cap` (tests only): DEEP_DBG_NO_BOUND, and a candidate capacity smaller than the library's."""
+    _dev_check(q, corpus, alive_bits)
+    if q.dim() != 2 or corpus.dim() != 2 or not q.is_contiguous() or not corpus.is_contiguous():
+        raise MMRagNativeError("cosine_topk_deep: q and corpus must be contiguous 2-D tensors")
+    if q.dtype != corpus.dtype or q.shape[1] != corpus.shape[1]:
+        raise MMRagNativeError("cosine_topk_deep: q and corpus must share dtype and padded width")
+    if n > corpus.shape[0]:
+        raise MMRagNativeError(f"cosine_topk_deep: n={n} exceeds corpus capacity {corpus.shape[0]}")
+    B, ld = q.shape
+    L = lib()
+    need = cosine_topk_deep_workspace_bytes(B, n, k)
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
+    out_s = torch.empty((B, k), dtype=torch.float32, device=q.device)
+    out_r = torch.empty((B, k), dtype=torch.int64, device=q.device)
+    with torch.cuda.device(q.device):
+        st = L.mmrag_internal_cosine_topk_deep_ex(
+            q.data_ptr(), corpus.data_ptr(), B, n, d, ld, _TORCH2DT[q.dtype], k, row_offset,
+            alive_bits.data_ptr() if alive_bits is not None else None, out_s.data_ptr(), out_r.data_ptr(),
+            workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr(q.device), dbg, cap)
+    _check(st, "mmrag_cosine_topk_deep")
+    return out_s, out_r
+
+
+def cosine_topk_deep_workspace_bytes(B: int, n: int, k: int) -> int:
+    return int(lib().mmrag_cosine_topk_deep_workspace_bytes(B, n, k))
 
 
 def device_info() -> dict:

@@ -24,6 +24,8 @@
 //     the epilogue;
 //   * every lane list is written once at kernel end; a second tiny kernel merges the
 //     gridDim.x * WM * 2 lists per query into the final [B, k] (ties -> lower row).
+//   * K = 0 is the filter mode of the deep top-k (search_deep.hip): no lists; the epilogue appends
+//     every score >= thr0[q] to a per-query buffer, one returning atomic per lane per tile.
 #include "search_shared.h"
 
 #include <stdlib.h>
@@ -70,6 +72,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void cosine_topk_kernel(const KPar
     const int q0 = by * QROWS;
     const int my_tiles = (p.n_tiles - bx + walkers - 1) / walkers;
     const int n_items = my_tiles * nk;
+    // corpus tile of walk position i: tile0 + bx + i * walkers (filter mode: times tile_stride, a strided sample).
+    // Written out at each use: a helper lambda changes the register allocation of the list kernels.
 
     // ---- DMA descriptors ------------------------------------------------------------------
     const long long q_rows_left = (long long)p.B - q0;
@@ -95,7 +99,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void cosine_topk_kernel(const KPar
 
     int is_tile = 0, is_k = 0;  // issue cursor: (index among my tiles, k slab)
     auto issue = [&](int stage_idx) {
-        const long long tile = (long long)p.tile0 + bx + (long long)is_tile * walkers;
+        const long long tile = K == 0 ? (long long)p.tile0 + (long long)(bx + is_tile * walkers) * p.tile_stride
+                                      : (long long)p.tile0 + bx + (long long)is_tile * walkers;
         const long long row0 = tile * TM;
         const long long rows_left = p.n - row0;
         const unsigned c_bytes = (unsigned)((rows_left < TM ? rows_left : (long long)TM) * (long long)RB);
@@ -130,7 +135,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void cosine_topk_kernel(const KPar
     // ---- accumulators, lists ---------------------------------------------------------------
     f32x16_t acc[RM];
     auto init_acc = [&](int tile_idx) {
-        const long long tile = (long long)p.tile0 + bx + (long long)tile_idx * walkers;
+        const long long tile = K == 0 ? (long long)p.tile0 + (long long)(bx + tile_idx * walkers) * p.tile_stride
+                                      : (long long)p.tile0 + bx + (long long)tile_idx * walkers;
         const long long row0 = tile * TM + (long long)wm * (RM * 32);
         const bool ragged = row0 + RM * 32 > p.n;
         if (!ragged && p.alive_bits == nullptr) {
@@ -154,13 +160,14 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void cosine_topk_kernel(const KPar
         }
     };
 
-    TopList<K> best;
+    TopList<(K > 0 ? K : 1)> best;
     best.init();
     float thr = NEG_INF;
     if (q0 + wn * 32 + r32 >= p.B)
         thr = INFINITY;  // padding query slot: its all-zero scores must never open the insertion path
     else if (p.thr0 != nullptr)
         thr = p.thr0[q0 + wn * 32 + r32];
+    if constexpr (K == 0) thr = fmaxf(thr, -__FLT_MAX__);  // masked rows (-inf) never pass the filter
 
     // ---- fragment addresses (bytes inside a stage) ------------------------------------------
     const int sw = (r32 >> 1) & 7;
@@ -251,9 +258,47 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void cosine_topk_kernel(const KPar
         if (++ks == nk) {
             // ---- epilogue: lane-local top-K over this wave's 32*RM rows of the tile ----------
             ks = 0;
-            const long long tile = (long long)p.tile0 + bx + (long long)tile_idx * walkers;
+            const long long tile = K == 0 ? (long long)p.tile0 + (long long)(bx + tile_idx * walkers) * p.tile_stride
+                                          : (long long)p.tile0 + bx + (long long)tile_idx * walkers;
             const int row_base = (int)(tile * TM) + wm * (RM * 32) + 4 * h;
-            if constexpr (K > 5) {
+            if constexpr (K == 0) {
+                // filter mode: count this lane's survivors, reserve their slots with one returning atomic, append.
+                // The counter keeps the true count; slots at or past deep_cap are not written.
+                int n_pass = 0;
+#pragma unroll
+                for (int b = 0; b < RM; ++b)
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) n_pass += acc[b][j] >= thr ? 1 : 0;
+                if (__builtin_amdgcn_ballot_w64(n_pass > 0) != 0ull) {
+                    const int qg = q0 + wn * 32 + r32;  // n_pass > 0 only for real queries (padding: thr = +inf)
+                    unsigned at = 0;
+                    if (n_pass > 0) at = atomicAdd(p.deep_cnt + qg, (unsigned)n_pass);
+                    float *bs = p.cand_s + (size_t)qg * p.deep_cap;
+                    int *br = p.cand_r + (size_t)qg * p.deep_cap;
+                    const unsigned cap = (unsigned)p.deep_cap;
+#pragma unroll
+                    for (int b = 0; b < RM; ++b) {
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            const float m4 = fmaxf(fmaxf(acc[b][4 * g], acc[b][4 * g + 1]),
+                                                   fmaxf(acc[b][4 * g + 2], acc[b][4 * g + 3]));
+                            if (__builtin_amdgcn_ballot_w64(m4 >= thr) != 0ull) {
+#pragma unroll
+                                for (int i = 0; i < 4; ++i) {
+                                    const float s = acc[b][4 * g + i];
+                                    if (s >= thr) {
+                                        if (at < cap) {
+                                            bs[at] = s;
+                                            br[at] = row_base + b * 32 + i + 8 * g;
+                                        }
+                                        ++at;
+                                    }
+                                }
+                            }
+                        }
+                    }
+                }
+            } else if constexpr (K > 5) {
                 // deep lists: one (not unrolled) insertion body per 4-row group keeps the code small
                 // (a K=20 insertion is ~100 instructions; 128 unrolled copies would not fit the I-cache)
 #pragma unroll
@@ -310,19 +355,21 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void cosine_topk_kernel(const KPar
                     }
                 }
             }
-            // k-th best of the union of the two half-wave lists of this query: a lower bound
-            // on the final k-th score, shared by both lanes
-            float u = fmaxf(best.v[K - 1], __shfl_xor(best.v[K - 1], 32));
+            if constexpr (K > 0) {
+                // k-th best of the union of the two half-wave lists of this query: a lower bound
+                // on the final k-th score, shared by both lanes
+                float u = fmaxf(best.v[K - 1], __shfl_xor(best.v[K - 1], 32));
 #pragma unroll
-            for (int i = 0; i + 1 < K; ++i) u = fmaxf(u, fminf(best.v[i], __shfl_xor(best.v[K - 2 - i], 32)));
-            thr = fmaxf(thr, u);
+                for (int i = 0; i + 1 < K; ++i) u = fmaxf(u, fminf(best.v[i], __shfl_xor(best.v[K - 2 - i], 32)));
+                thr = fmaxf(thr, u);
+            }
             ++tile_idx;
             if (tile_idx < my_tiles) init_acc(tile_idx);
         }
     }
 
     // ---- merge the workgroup's WM*2 lists per query through LDS, write ONE list per query -------
-    {
+    if constexpr (K > 0) {
         constexpr int NL = WM * 2;  // lists per query inside this workgroup
         static_assert(QROWS * NL * K * 8 <= NSTAGE * STAGE, "list merge scratch must fit in the ring");
         __builtin_amdgcn_s_barrier();  // every wave is done reading the ring
@@ -590,6 +637,25 @@ int dispatch_main(const Plan &pl, const KParams &p, hipStream_t s) {
     } else {
         dispatch_deep<DT, 20>(pl, p, grid, s);
     }
+    return MMRAG_OK;
+}
+
+// filter mode (K = 0) for search_deep.hip: the list search's WN plan and wave shapes (16 waves at WN = 8, as depth 5;
+// 8 for fp32, whose bf16 split does not fit 128 registers without spilling)
+template <int DT>
+void launch_filter(int WN, const KParams &p, dim3 grid, hipStream_t s) {
+    if (WN == 2) launch_main<DT, 2, 0, 3>(p, grid, s);
+    else if (WN == 4) launch_main<DT, 4, 0, 3>(p, grid, s);
+    else if constexpr (DT == MMRAG_F32) launch_main<DT, 8, 0, 2, 8>(p, grid, s);
+    else launch_main<DT, 8, 0, 2, 16>(p, grid, s);
+}
+
+int deep_filter_launch(int dtype, int WN, const KParams &p, int grid_x, int grid_y, hipStream_t s) {
+    const dim3 grid(grid_x, grid_y);
+    if (dtype == MMRAG_F32) launch_filter<MMRAG_F32>(WN, p, grid, s);
+    else if (dtype == MMRAG_F16) launch_filter<MMRAG_F16>(WN, p, grid, s);
+    else launch_filter<MMRAG_BF16>(WN, p, grid, s);
+    MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
 }
 

@@ -99,6 +99,10 @@ struct KParams {
     unsigned *tickets;    // [query groups]: next dynamically handed-out tile, counted from TICKET0
     int p_static;         // tile positions every workgroup walks by the static rule (tile = bx + pos * walkers); the
                           // tiles from p_static * walkers on are handed out by ticket.  Huge = no dynamic hand-out
+    // ---- filter mode of the slab-ring kernel (search_deep.hip: K = 0) ----
+    int tile_stride;      // tile of walk position i is tile0 + i * tile_stride (strided sample of the collection)
+    unsigned *deep_cnt;   // [B]: survivors per query, the TRUE count (appends past deep_cap are dropped)
+    int deep_cap;         // candidate slots per query in cand_s / cand_r ([B, deep_cap])
 };
 constexpr unsigned TICKET0 = 0xff800000u;   // the exchange block is filled with the bit pattern of -inf
 
@@ -152,6 +156,12 @@ int qs_seed_thresholds(int K, const float *best, int walkers, int n_queries, flo
 constexpr int QSW_DEFAULT_MFMA = 16;   // the shape list depth 5 runs on (A/B in DESIGN.md section 7)
 bool qsw_supported(int dtype, unsigned row_bytes, int K, int mfma);
 int qsw_launch(int dtype, int K, int mfma, const KParams &p, int grid_x, int grid_y, hipStream_t s);
+
+// ---- filter mode of the slab-ring kernel (search.hip), for the deep top-k of search_deep.hip ---------------------------
+// Same GEMM, MFMA sequence and WN plan as a list search of B queries; the epilogue appends every score >= thr0[q]
+// (inclusive; thr0 = null: every live row) as (score, local row) to query q's slots of cand_s / cand_r and counts it in
+// deep_cnt[q].  Walks p.n_tiles tiles: tile0 + (bx + i * walkers) * tile_stride.
+int deep_filter_launch(int dtype, int WN, const KParams &p, int grid_x, int grid_y, hipStream_t s);
 
 
 }  // namespace mmrag_impl

@@ -186,6 +186,7 @@ class VectorIndex:
         self._row_of: Dict[str, int] = {}
         self._lock = threading.RLock()
         self._search_ws: Optional[torch.Tensor] = None    # candidate-list workspace of the search kernels, reused
+        self._deep_ws: Optional[torch.Tensor] = None      # workspace of the deep search (n_results > 20), reused
         from .config import settings
 
         self.f32_exact = bool(settings.MMRAG_F32_EXACT_SEARCH)   # float32 collections only (see config.py)
@@ -386,10 +387,28 @@ class VectorIndex:
             return _native.cosine_topk(q, self._matrix, self._n, self.dim, n_results, alive_bits=bits,
                                        workspace=self._search_ws if torch.cuda.current_stream(self.device) == torch.cuda.default_stream(self.device) else None,
                                        packed_out=True)
+        if n_results <= _native.MAX_K_DEEP:
+            # deeper than the kernel's lists (get_similar_documents asks for n_results + 1): the threshold-filter scan
+            # and per-query select of csrc/search_deep.hip, any batch, one call (it synchronises the stream once)
+            step = 64 if self.f32_exact and self.dtype == torch.float32 else q.shape[0]   # as above: exact float32
+            parts = []
+            for i in range(0, q.shape[0], step):
+                qi = q[i:i + step]
+                need = _native.cosine_topk_deep_workspace_bytes(qi.shape[0], self._n, n_results)
+                ws = None
+                if torch.cuda.current_stream(self.device) == torch.cuda.default_stream(self.device):
+                    if self._deep_ws is None or self._deep_ws.numel() < need:
+                        self._deep_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+                    ws = self._deep_ws
+                parts.append(_native.cosine_topk_deep(qi, self._matrix, self._n, self.dim, n_results, alive_bits=bits,
+                                                      workspace=ws))
+            if len(parts) == 1:
+                return parts[0]
+            return torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)
         if q.shape[0] != 1:
-            raise ValueError(f"n_results > {_native.MAX_K} is supported for single queries only")
-        # deeper than the kernel's lists (get_similar_documents asks for n_results + 1): further passes with the rows
-        # already returned masked out -- still exact, still ordered
+            raise ValueError(f"n_results > {_native.MAX_K_DEEP} is supported for single queries only")
+        # deeper than the deep search (MAX_K_DEEP): further passes with the rows already returned masked out -- still
+        # exact, still ordered
         if bits is None:
             bits = self._alive_dev
         bits = bits.clone()
@@ -413,7 +432,9 @@ class VectorIndex:
     def search(self, query_embeddings, n_results: int, where: Optional[Dict[str, Any]] = None):
         """Raw device search: (scores [B, k] float32 desc, rows [B, k] int64, -1 = none).
 
-        The kernel selects up to MAX_K = 20 per pass (api.py:163 caps top_k at 20)."""
+        Any batch size for n_results up to MAX_K_DEEP = 4096: up to MAX_K = 20 in the kernel's register lists (one
+        scan), above that the deep search (bound, filter scan, select; one stream synchronisation).  Deeper than 4096:
+        single queries only, in passes of 20 with the rows already returned masked out."""
         with self._lock:
             return self._launch_search(query_embeddings, n_results, where)
 
