@@ -131,6 +131,18 @@ def _declare(lib):
     lib.mmrag_pool_normalize_f16.restype = c_int
     lib.mmrag_pool_normalize_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                              c_void_p]
+    # test-only entry points (not in include/mmrag.h): single kernels of the folded-LayerNorm and fp32 forwards
+    lib.mmrag_internal_linear_f16_norms.restype = c_int
+    lib.mmrag_internal_linear_f16_norms.argtypes = [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                                    c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_void_p]
+    lib.mmrag_internal_attention_f32.restype = c_int
+    lib.mmrag_internal_attention_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
+    lib.mmrag_internal_layernorm_f32.restype = c_int
+    lib.mmrag_internal_layernorm_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p]
+    lib.mmrag_internal_pool_norm_f32.restype = c_int
+    lib.mmrag_internal_pool_norm_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                                 c_void_p]
 
 
 def lib():
@@ -521,6 +533,64 @@ def pool_normalize_f16(x: torch.Tensor, cu_seqlens: torch.Tensor, pool: int, nor
         st = lib().mmrag_pool_normalize_f16(x.data_ptr(), cu_seqlens.data_ptr(), _ptr(sel), out.data_ptr(), B, H, pool,
                                             int(normalize), _stream_ptr(x.device))
     _check(st, "mmrag_pool_normalize_f16")
+    return out
+
+
+def linear_f16_norms(x: torch.Tensor, wt: torch.Tensor, bias: Optional[torch.Tensor] = None, act: int = ACT_NONE,
+                     resid: Optional[torch.Tensor] = None, ln_gamma: Optional[torch.Tensor] = None,
+                     ln_beta: Optional[torch.Tensor] = None, ln_eps: float = 1e-12,
+                     ln_stats_out: Optional[torch.Tensor] = None, res_stats: Optional[torch.Tensor] = None,
+                     res_gamma: Optional[torch.Tensor] = None, res_beta: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(tests) one GEMM of the single-query forward (M <= 64): out = act(LN(x) @ wt.T + bias) (+ LN'(resid)), where LN
+    is applied when ln_gamma is given (its per-row (mean, rstd) go to ln_stats_out, float32 [M, 2]) and LN' when
+    res_stats (float32 [M, 2]) is given"""
+    _dev_check(x, wt, bias, resid, ln_gamma, ln_beta, ln_stats_out, res_stats, res_gamma, res_beta)
+    M, K = x.shape
+    Nf = wt.shape[0]
+    out = torch.empty((M, Nf), dtype=torch.float16, device=x.device)
+    with torch.cuda.device(x.device):
+        st = lib().mmrag_internal_linear_f16_norms(x.data_ptr(), M, K, wt.data_ptr(), Nf, _ptr(bias), act, _ptr(resid),
+                                                   out.data_ptr(), _ptr(ln_gamma), _ptr(ln_beta), ln_eps,
+                                                   _ptr(ln_stats_out), _ptr(res_stats), _ptr(res_gamma), _ptr(res_beta),
+                                                   _stream_ptr(x.device))
+    _check(st, "mmrag_internal_linear_f16_norms")
+    return out
+
+
+def attention_f32(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_len: int, n_heads: int) -> torch.Tensor:
+    """(tests) the fp32 forward's attention on its own: qkv float32 [T, 3H] -> ctx float32 [T, H]"""
+    _dev_check(qkv, cu_seqlens)
+    T, H3 = qkv.shape
+    ctx = torch.empty((T, H3 // 3), dtype=torch.float32, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        st = lib().mmrag_internal_attention_f32(qkv.data_ptr(), cu_seqlens.data_ptr(), ctx.data_ptr(),
+                                                cu_seqlens.numel() - 1, max_len, H3 // 3, n_heads,
+                                                _stream_ptr(qkv.device))
+    _check(st, "mmrag_internal_attention_f32")
+    return ctx
+
+
+def layernorm_f32(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float) -> torch.Tensor:
+    """(tests) the fp32 forward's LayerNorm on its own"""
+    _dev_check(x, gamma, beta)
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        st = lib().mmrag_internal_layernorm_f32(x.data_ptr(), out.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                                x.shape[0], x.shape[1], eps, _stream_ptr(x.device))
+    _check(st, "mmrag_internal_layernorm_f32")
+    return out
+
+
+def pool_norm_f32(x: torch.Tensor, cu_seqlens: torch.Tensor, pool: int, normalize: bool = True,
+                  sel: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(tests) the fp32 forward's pooling + L2 normalisation on its own"""
+    _dev_check(x, cu_seqlens, sel)
+    B, H = cu_seqlens.numel() - 1, x.shape[1]
+    out = torch.empty((B, H), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        st = lib().mmrag_internal_pool_norm_f32(x.data_ptr(), cu_seqlens.data_ptr(), _ptr(sel), out.data_ptr(), B, H,
+                                                pool, int(normalize), _stream_ptr(x.device))
+    _check(st, "mmrag_internal_pool_norm_f32")
     return out
 
 

@@ -1264,7 +1264,7 @@ template <int NWC, int STEPS, bool LN_IN = false>
 __global__ __launch_bounds__(64 * NWC) void linear_small16_kernel(const LinearParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ float part[NWC][4][64];  // [wave][register][lane]
-    __shared__ float2 rowsum[NWC][16];  // LN_IN: (sum, sum of squares) of each wave's share of the 16 token rows
+    __shared__ float2 rowsum[NWC][16];  // LN_IN: (sum, sum of squared deviations) of each wave's share of the 16 token rows
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int r16 = lane & 15, kq = lane >> 4;
@@ -1295,29 +1295,39 @@ __global__ __launch_bounds__(64 * NWC) void linear_small16_kernel(const LinearPa
         if constexpr (LN_IN) {
             // the workgroup's waves hold the 16 token rows between them (wave = K share, lane group kq = 8 of every 32):
             // row sums over the lane's values, over the four lane groups, over the waves (LDS), then normalise in place,
-            // rounding to fp16 as the LayerNorm pass would have stored the row
-            float s1 = 0.f, s2 = 0.f;
+            // rounding to fp16 as the LayerNorm pass would have stored the row.  Two passes like ln_row: the mean, then
+            // the squared deviations from it (E[x^2] - mean^2 in fp32 loses the variance of rows whose mean is large
+            // against their spread: 1e-2 relative error on rstd at a mean of 300 sigma)
+            float s1 = 0.f;
+#pragma unroll
+            for (int s_ = 0; s_ < STEPS; ++s_)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) s1 += (float)b[s_][e];
+            s1 += __shfl_xor(s1, 16);
+            s1 += __shfl_xor(s1, 32);
+            // (no barrier before this write: the previous token block read rowsum before its partials barrier)
+            if (kq == 0) rowsum[wave][r16].x = s1;
+            __syncthreads();
+            float t1 = 0.f;
+#pragma unroll
+            for (int w = 0; w < NWC; ++w) t1 += rowsum[w][r16].x;
+            const float inv_k = 1.0f / (float)p.K, mean = t1 * inv_k;
+            float s2 = 0.f;
 #pragma unroll
             for (int s_ = 0; s_ < STEPS; ++s_)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    const float v = (float)b[s_][e];
-                    s1 += v;
-                    s2 = fmaf(v, v, s2);
+                    const float dx = (float)b[s_][e] - mean;
+                    s2 = fmaf(dx, dx, s2);
                 }
-            s1 += __shfl_xor(s1, 16), s2 += __shfl_xor(s2, 16);
-            s1 += __shfl_xor(s1, 32), s2 += __shfl_xor(s2, 32);
-            if (t0 > 0) __syncthreads();   // rowsum of the previous token block has been read
-            if (kq == 0) rowsum[wave][r16] = make_float2(s1, s2);
+            s2 += __shfl_xor(s2, 16);
+            s2 += __shfl_xor(s2, 32);
+            if (kq == 0) rowsum[wave][r16].y = s2;   // (.x is still being read: a different word)
             __syncthreads();
-            float t1 = 0.f, t2 = 0.f;
+            float t2 = 0.f;
 #pragma unroll
-            for (int w = 0; w < NWC; ++w) {
-                const float2 v = rowsum[w][r16];
-                t1 += v.x, t2 += v.y;
-            }
-            const float inv_k = 1.0f / (float)p.K, mean = t1 * inv_k;
-            const float rstd = rsqrtf(fmaxf(fmaf(t2, inv_k, -mean * mean), 0.f) + p.ln_eps);
+            for (int w = 0; w < NWC; ++w) t2 += rowsum[w][r16].y;
+            const float rstd = rsqrtf(t2 * inv_k + p.ln_eps);
             if (blockIdx.x == 0 && wave == 0 && kq == 0 && t0 + r16 < p.M && p.ln_stats_out != nullptr)
                 p.ln_stats_out[t0 + r16] = make_float2(mean, rstd);
 #pragma unroll
@@ -1498,6 +1508,33 @@ int mmrag_linear_f16(const void *x, int64_t M, int K, const void *wt, int N, con
                         ((uintptr_t)resid % 8) == 0 && ((uintptr_t)bias % 16) == 0,
                     "linear: misaligned pointer");
     launch_linear(x, (int)M, K, wt, N, bias, act, resid, out, (hipStream_t)stream);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    return MMRAG_OK;
+}
+
+// (tests only, not in mmrag.h) one GEMM of the single-query forward as encoder_body launches it: input rows normalised
+// on load (ln_gamma / ln_beta, their (mean, rstd) to ln_stats_out) and / or an un-normalised residual normalised with
+// res_stats / res_gamma / res_beta before the add
+int mmrag_internal_linear_f16_norms(const void *x, int64_t M, int K, const void *wt, int N, const float *bias, int act,
+                                    const void *resid, void *out, const float *ln_gamma, const float *ln_beta,
+                                    float ln_eps, float *ln_stats_out, const float *res_stats, const float *res_gamma,
+                                    const float *res_beta, void *stream) {
+    MMRAG_CHECK_ARG(x && wt && out, "linear_norms: null pointer");
+    MMRAG_CHECK_ARG(M > 0 && M <= 64 && N > 0 && N % 4 == 0, "linear_norms: bad shape M=%lld N=%d", (long long)M, N);
+    MMRAG_CHECK_ARG(act >= 0 && act <= 2, "linear_norms: bad activation %d", act);
+    MMRAG_CHECK_ARG((ln_gamma == nullptr) == (ln_beta == nullptr), "linear_norms: ln_gamma / ln_beta both or neither");
+    MMRAG_CHECK_ARG(res_stats == nullptr || (resid && res_gamma && res_beta), "linear_norms: res_stats needs resid, res_gamma, res_beta");
+    MMRAG_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)wt % 16) == 0 && ((uintptr_t)out % 8) == 0 &&
+                        ((uintptr_t)resid % 8) == 0 && ((uintptr_t)bias % 16) == 0 && ((uintptr_t)ln_gamma % 16) == 0 &&
+                        ((uintptr_t)ln_beta % 16) == 0 && ((uintptr_t)ln_stats_out % 8) == 0 &&
+                        ((uintptr_t)res_stats % 8) == 0 && ((uintptr_t)res_gamma % 16) == 0 &&
+                        ((uintptr_t)res_beta % 16) == 0,
+                    "linear_norms: misaligned pointer");
+    SmallNorms n;
+    n.ln_gamma = ln_gamma, n.ln_beta = ln_beta, n.ln_eps = ln_eps, n.ln_stats_out = (float2 *)ln_stats_out;
+    n.res_stats = (const float2 *)res_stats, n.res_gamma = res_gamma, n.res_beta = res_beta;
+    const int st = launch_linear(x, (int)M, K, wt, N, bias, act, resid, out, (hipStream_t)stream, &n);
+    if (st != MMRAG_OK) return st;
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
 }

@@ -376,6 +376,14 @@ int launch_linear_f32(const float *x, int64_t M, int K, const float *wt, int N, 
     return MMRAG_OK;
 }
 
+void launch_attention_f32(const float *qkv, const int32_t *cu, float *ctx, int B, int max_len, int H, int dh,
+                          hipStream_t s) {
+    const dim3 grid((unsigned)((max_len + 127) / 128), (unsigned)(H / dh), (unsigned)B);
+    const float scale = 1.0f / sqrtf((float)dh);
+    if (dh == 32) attention_f32_kernel<32><<<grid, 256, 0, s>>>(qkv, cu, ctx, H, scale);
+    else attention_f32_kernel<64><<<grid, 256, 0, s>>>(qkv, cu, ctx, H, scale);
+}
+
 }  // namespace
 
 }  // namespace mmrag_impl
@@ -392,6 +400,41 @@ size_t mmrag_encoder_f32_workspace_bytes(const mmrag_encoder_desc *d, int64_t T,
     if (!d || T <= 0 || B <= 0) return 0;
     const size_t H = (size_t)d->hidden, I = (size_t)d->intermediate, Tz = (size_t)T;
     return 2 * align256f(Tz * H * 4) + align256f(Tz * 3 * H * 4) + align256f(Tz * H * 4) + align256f(Tz * I * 4) + 256;
+}
+
+// (tests only, not in mmrag.h) the fp32 forward's attention, LayerNorm and pooling kernels launched on their own
+int mmrag_internal_attention_f32(const float *qkv, const int32_t *cu_seqlens, float *ctx, int B, int max_len, int H,
+                                 int n_heads, void *stream) {
+    MMRAG_CHECK_ARG(qkv && cu_seqlens && ctx, "attention_f32: null pointer");
+    MMRAG_CHECK_ARG(B > 0 && max_len > 0 && n_heads > 0 && H % n_heads == 0, "attention_f32: bad shape");
+    const int dh = H / n_heads;
+    MMRAG_CHECK_ARG(dh == 32 || dh == 64, "attention_f32: head dim %d unsupported (32 or 64)", dh);
+    MMRAG_CHECK_ARG(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)ctx % 16) == 0, "attention_f32: misaligned pointer");
+    launch_attention_f32(qkv, cu_seqlens, ctx, B, max_len, H, dh, (hipStream_t)stream);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    return MMRAG_OK;
+}
+
+int mmrag_internal_layernorm_f32(const float *x, float *out, const float *gamma, const float *beta, int64_t T, int H,
+                                 float eps, void *stream) {
+    MMRAG_CHECK_ARG(x && out && gamma && beta, "layernorm_f32: null pointer");
+    MMRAG_CHECK_ARG(T > 0 && T < INT_MAX && H > 0 && H % 4 == 0 && H <= 1024, "layernorm_f32: bad shape T=%lld H=%d",
+                    (long long)T, H);
+    MMRAG_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)gamma % 16) == 0 &&
+                        ((uintptr_t)beta % 16) == 0, "layernorm_f32: pointers must be 16-byte aligned");
+    layernorm_f32_kernel<<<(unsigned)((T + 3) / 4), 256, 0, (hipStream_t)stream>>>(x, out, gamma, beta, (int)T, H, eps);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    return MMRAG_OK;
+}
+
+int mmrag_internal_pool_norm_f32(const float *x, const int32_t *cu_seqlens, const int32_t *sel, float *out, int B, int H,
+                                 int pool, int normalize, void *stream) {
+    MMRAG_CHECK_ARG(x && cu_seqlens && out, "pool_norm_f32: null pointer");
+    MMRAG_CHECK_ARG(B > 0 && H > 0 && H <= 1024, "pool_norm_f32: bad shape B=%d H=%d", B, H);
+    MMRAG_CHECK_ARG(pool >= 0 && pool <= 2 && (pool != 2 || sel), "pool_norm_f32: bad mode %d", pool);
+    pool_norm_f32_kernel<<<(unsigned)B, 256, 0, (hipStream_t)stream>>>(x, cu_seqlens, sel, out, H, pool, normalize);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    return MMRAG_OK;
 }
 
 #define RUN(call) do { if ((st = (call)) != MMRAG_OK) return st; } while (0)
@@ -427,12 +470,9 @@ int mmrag_encoder_forward_f32(const mmrag_encoder_desc *d, const void *const *w,
                                                  (int)T, H, d->vocab, d->max_pos, d->ln_eps);
     MMRAG_CHECK_HIP(hipGetLastError());
     const void *const *lw = w + 5;
-    const float scale = 1.0f / sqrtf((float)DH);
-    const dim3 agrid((unsigned)((max_len + 127) / 128), (unsigned)d->n_heads, (unsigned)B);
     for (int l = 0; l < d->n_layers; ++l, lw += 12) {
         RUN(launch_linear_f32(x, T, H, (const float *)lw[0], 3 * H, (const float *)lw[1], MMRAG_ACT_NONE, nullptr, qkv, s));
-        if (DH == 32) attention_f32_kernel<32><<<agrid, 256, 0, s>>>(qkv, cu_seqlens, ctx, H, scale);
-        else attention_f32_kernel<64><<<agrid, 256, 0, s>>>(qkv, cu_seqlens, ctx, H, scale);
+        launch_attention_f32(qkv, cu_seqlens, ctx, B, max_len, H, DH, s);
         MMRAG_CHECK_HIP(hipGetLastError());
         RUN(launch_linear_f32(ctx, T, H, (const float *)lw[2], H, (const float *)lw[3], MMRAG_ACT_NONE, x, y, s));
         layernorm_f32_kernel<<<row_grid, 256, 0, s>>>(y, x, (const float *)lw[4], (const float *)lw[5], (int)T, H, d->ln_eps);

@@ -271,12 +271,15 @@ def test_single_query_forward_vs_oracle(N, shape, lens, pool):
 
 @pytest.mark.parametrize("hidden,heads,inter,lens", [(384, 12, 1536, [9]), (384, 12, 1536, [17, 5, 30]), (768, 12, 3072, [64]),
                                                       (768, 12, 3072, [3, 40]), (1024, 16, 2048, [33])])
-def test_single_query_forward_without_layernorm_launches(N, hidden, heads, inter, lens):
+def test_single_query_forward_without_layernorm_launches(N, monkeypatch, hidden, heads, inter, lens):
     """T <= 64 (the online /query shape) runs BERT with the LayerNorms folded into the neighbouring GEMMs
     (csrc/encoder.hip "the single-query path without LayerNorm launches").  Same embeddings as the forward WITH the
     LayerNorm launches (developer switch 512), which the oracle / transformers goldens pin; non-trivial gamma / beta;
-    one to three sequences, token blocks of 16 both full and ragged."""
+    one to three sequences, token blocks of 16 both full and ragged.  No HIP graphs: a single sequence would otherwise
+    replay the graph captured under the first switch setting and compare that forward with itself."""
     import ctypes
+
+    monkeypatch.setenv("MMRAG_ENCODER_GRAPHS", "0")
 
     from multimodal_rag_amd.encoder import DeviceEncoder, EncoderConfig, random_bert_weights
 
@@ -304,3 +307,49 @@ def test_single_query_forward_without_layernorm_launches(N, hidden, heads, inter
     assert np.array_equal(got, again)
     assert np.abs(np.linalg.norm(got, axis=1) - 1).max() < 1e-3
     assert np.abs(got - ref).max() <= 1e-3, float(np.abs(got - ref).max())
+
+
+@pytest.mark.parametrize("shape", [E.MINILM_L6, E.BGE_BASE], ids=["minilm", "bge"])
+@pytest.mark.parametrize("lens", [[9], [17, 5, 30], [64]])
+@pytest.mark.parametrize("std", [0.05, 0.012, 0.008])
+def test_single_query_forward_folded_layernorm_large_beta(N, monkeypatch, record_property, shape, lens, std):
+    """Every LayerNorm whose output the single-query forward folds (embeddings, attention.output and all but the last
+    layer's output.LayerNorm) gets beta + 100, so the un-normalised rows the folded GEMMs normalise on load, and whose
+    (mean, rstd) a later GEMM's residual add reuses, sit far from 0.  How far depends on the matrices: with std 0.05
+    their outputs swamp the offset (row means within ~1 row std); std 0.012 gives means of 6-16 row stds, std 0.008
+    13-34.  The folded forward against the forward with LayerNorm launches (DBG_ENCODER_LN_PASSES; no HIP graphs,
+    which would replay the first setting) and both against the float32 oracle, under the bounds above.  (With std
+    0.002, means of ~100 row stds, the fp16 residual stream alone puts BOTH forwards ~1e-2 from the oracle: these
+    bounds cannot hold there for either, and the op tests in test_encoder_ops_gpu.py pin the kernel instead.)"""
+    import ctypes
+
+    from multimodal_rag_amd.encoder import DeviceEncoder, EncoderConfig
+
+    monkeypatch.setenv("MMRAG_ENCODER_GRAPHS", "0")
+    w = E.make_bert_weights(shape, seed=31, std=std)
+    last = f"encoder.layer.{shape.n_layers - 1}.output.LayerNorm.bias"
+    for k in w:
+        if k.endswith("LayerNorm.bias") and k != last:
+            w[k] = w[k] + np.float32(100.0)
+    cfg = EncoderConfig("q", shape.n_layers, shape.hidden, shape.n_heads, shape.intermediate, shape.vocab,
+                        shape.max_pos, max_seq_length=shape.max_pos, pool="mean", ln_eps=shape.ln_eps)
+    enc = DeviceEncoder(cfg, w, "cuda:0")
+    g = np.random.default_rng(32)
+    seqs = [g.integers(1000, shape.vocab, n).tolist() for n in lens]
+    want = E.bert_encode(dataclasses.replace(shape, pool="mean"), E.round_weights_fp16(w), seqs)
+    L = N.lib()
+    L.mmrag_internal_set_debug.argtypes = [ctypes.c_uint]
+    try:
+        L.mmrag_internal_set_debug(512)          # DBG_ENCODER_LN_PASSES
+        passes = enc.encode_ids(seqs).cpu().numpy()
+        L.mmrag_internal_set_debug(0)
+        got = enc.encode_ids(seqs).cpu().numpy()
+    finally:
+        L.mmrag_internal_set_debug(0)
+    d_passes = float(np.abs(got - passes).max())
+    errs = {k: (float(np.abs(v - want).max()), float((v * want).sum(1).min())) for k, v in (("folded", got), ("passes", passes))}
+    record_property("folded vs passes", d_passes)
+    record_property("vs oracle (max err, min cos)", errs)
+    assert d_passes <= 1e-3, d_passes
+    for k, (err, cos) in errs.items():
+        assert err <= 4e-3 and cos >= 0.9999, (k, err, cos)
