@@ -150,7 +150,7 @@ int mmrag_copy_to_host_async(void *dst_host, const void *src_dev, size_t bytes, 
 #define MMRAG_ACT_GELU 1       /* erf GELU (BERT) */
 #define MMRAG_ACT_QUICK_GELU 2 /* x * sigmoid(1.702 x) (CLIP) */
 
-#define MMRAG_ARCH_BERT 0  /* post-LN blocks, learned absolute positions, token-type 0, embedding LN */
+#define MMRAG_ARCH_BERT 0  /* post-LN blocks, learned absolute positions, token-type 0 (pairs: per token), embedding LN */
 #define MMRAG_ARCH_PRELN 1 /* pre-LN blocks (CLIP towers), final LN, bias-free projection */
 
 #define MMRAG_POOL_MEAN 0  /* masked mean over the sequence's tokens (all-MiniLM-L6-v2) */
@@ -200,6 +200,35 @@ int mmrag_encoder_forward_f32(const mmrag_encoder_desc *desc, const void *const 
 int mmrag_linear_f32(const float *x, int64_t M, int K, const float *wt, int N, const float *bias, int act,
                      const float *resid, float *out, void *stream);
 
+/* Cross-encoder re-ranking.  Fills in the reference's placeholder EmbeddingManager.rerank_results
+ * (app/utils/embedder.py:834-859: "Re-ranking not implemented yet", truncation to top_k), whose docstring names a
+ * cross-encoder: each (query, passage) pair is ONE packed sequence [CLS] a [SEP] b [SEP] scored by a
+ * BertForSequenceClassification (e.g. cross-encoder/ms-marco-MiniLM-L-6-v2).
+ * Embedding with segment ids -> the same encoder blocks as mmrag_encoder_forward / _f32 -> the [CLS] row ->
+ * pooler tanh(W_p h + b_p) -> classifier W_c pooled + b_c, in float32 (one launch).
+ *   desc        arch must be MMRAG_ARCH_BERT; desc.pool and desc.normalize are IGNORED (the head reads [CLS], raw)
+ *   w           the weight table of mmrag_encoder_forward (fp16 mode) / mmrag_encoder_forward_f32 (fp32 mode), except
+ *               w[2] = the whole token-type table [type_vocab >= 2, H] (rows 0 and 1 are read; type ids are clamped
+ *               to 0..1, as ids are clamped to the vocabulary), and after the layers, at w[5 + 12 L ...]:
+ *               pooler_w [H, H], pooler_b [H], cls_w [n_labels, H], cls_b [n_labels], all float32 in both modes
+ *   n_labels    1..16
+ *   ids, type_ids, pos_ids   dev [T] int32, packed as for the encoder (segment id 0 up to and including the first
+ *               [SEP], 1 after it)
+ *   out_logits  dev [B, n_labels] float32 (no sigmoid / softmax)
+ *   workspace   >= mmrag_cross_encoder_workspace_bytes(desc, T, B) (fp32: the _f32 query), 16-byte aligned
+ * Bad arguments return MMRAG_EINVAL, a short workspace MMRAG_EWORKSPACE.  Logits of a sequence do not depend on the
+ * other sequences of the batch beyond the encoder's own GEMM tiling; identical calls give identical bits. */
+size_t mmrag_cross_encoder_workspace_bytes(const mmrag_encoder_desc *desc, int64_t T, int B);
+int mmrag_cross_encoder_forward(const mmrag_encoder_desc *desc, const void *const *w, int n_labels, const int32_t *ids,
+                                const int32_t *type_ids, const int32_t *pos_ids, const int32_t *cu_seqlens, int64_t T,
+                                int B, int max_len, float *out_logits, void *workspace, size_t workspace_bytes,
+                                void *stream);
+size_t mmrag_cross_encoder_f32_workspace_bytes(const mmrag_encoder_desc *desc, int64_t T, int B);
+int mmrag_cross_encoder_forward_f32(const mmrag_encoder_desc *desc, const void *const *w, int n_labels,
+                                    const int32_t *ids, const int32_t *type_ids, const int32_t *pos_ids,
+                                    const int32_t *cu_seqlens, int64_t T, int B, int max_len, float *out_logits,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+
 /* Vision tower (CLIP ViT-B/32 shape; BASELINE config 4 -- no reference behaviour):
  * patchify (+ fused uint8 -> normalised fp16 preprocessing) -> patch-embedding GEMM -> class token +
  * positions -> pre-LN -> the same pre-LN blocks / final LN / projection / L2 normalise as the text tower.
@@ -226,6 +255,16 @@ void *mmrag_wordpiece_create(const uint32_t *cps, const int64_t *offsets, int n_
 void mmrag_wordpiece_destroy(void *tokenizer);
 int mmrag_wordpiece_encode_batch(const void *tokenizer, const uint32_t *cps, const int64_t *offsets, int n,
                                  int max_length, int32_t *ids, int32_t *lens, int n_threads);
+
+/* Pair encoding for the cross-encoder (what CrossEncoder.predict's fast tokenizer does with (query, passage) pairs):
+ * row i = [CLS] a_i [SEP] b_i [SEP] with type_ids 0 through the first [SEP] and 1 after it.  Over budget
+ * max_length - 3 the pieces are cut by the fast tokenizer's LongestFirst rule: when the shorter side fits in half the
+ * budget the longer side gets the rest; otherwise each side gets budget / 2 and an odd token goes to the longer side
+ * (to b on equal lengths).  A text equal to the previous pair's text (the query of a batch) is tokenised once.
+ *   ids, type_ids [n, max_length] int32 (entries past lens[i] untouched), lens [n]; max_length >= 3 */
+int mmrag_wordpiece_encode_pairs(const void *tokenizer, const uint32_t *cps_a, const int64_t *offsets_a,
+                                 const uint32_t *cps_b, const int64_t *offsets_b, int n, int max_length, int32_t *ids,
+                                 int32_t *type_ids, int32_t *lens, int n_threads);
 
 /* CLIP byte-level BPE (the text tower's tokenizer, BASELINE config 4; the reference only names CLIP in config.py:106).
  * Host code, multi-threaded; equals multimodal_rag_amd/tokenizer.py:ClipBpeTokenizer, which tests pin to

@@ -143,6 +143,28 @@ def _declare(lib):
     lib.mmrag_internal_pool_norm_f32.restype = c_int
     lib.mmrag_internal_pool_norm_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                                  c_void_p]
+    # cross-encoder (include/mmrag.h) and its test-only exports
+    lib.mmrag_cross_encoder_workspace_bytes.restype = c_size_t
+    lib.mmrag_cross_encoder_workspace_bytes.argtypes = [c_void_p, c_int64, c_int]
+    lib.mmrag_cross_encoder_f32_workspace_bytes.restype = c_size_t
+    lib.mmrag_cross_encoder_f32_workspace_bytes.argtypes = [c_void_p, c_int64, c_int]
+    lib.mmrag_cross_encoder_forward.restype = c_int
+    lib.mmrag_cross_encoder_forward.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_int64, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.mmrag_cross_encoder_forward_f32.restype = c_int
+    lib.mmrag_cross_encoder_forward_f32.argtypes = lib.mmrag_cross_encoder_forward.argtypes
+    lib.mmrag_wordpiece_encode_pairs.restype = c_int
+    lib.mmrag_wordpiece_encode_pairs.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                                 c_void_p, c_void_p, c_int]
+    lib.mmrag_internal_embed_types_ln_f16.restype = c_int
+    lib.mmrag_internal_embed_types_ln_f16.argtypes = [c_void_p] * 9 + [c_int64, c_int, c_int, c_int, c_int, c_float,
+                                                                       c_void_p]
+    lib.mmrag_internal_embed_types_ln_f32.restype = c_int
+    lib.mmrag_internal_embed_types_ln_f32.argtypes = lib.mmrag_internal_embed_types_ln_f16.argtypes
+    lib.mmrag_internal_cls_head_f32.restype = c_int
+    lib.mmrag_internal_cls_head_f32.argtypes = [c_void_p] * 6 + [c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]
+    lib.mmrag_internal_cls_head_workspace_bytes.restype = c_size_t
+    lib.mmrag_internal_cls_head_workspace_bytes.argtypes = [c_int, c_int, c_int]
 
 
 def lib():
@@ -635,6 +657,66 @@ def encoder_forward(desc: EncoderDesc, weight_ptrs, ids: torch.Tensor, pos_ids: 
                                          workspace.data_ptr(), workspace.numel() * workspace.element_size(),
                                          _stream_ptr(ids.device))
     _check(st, "mmrag_encoder_forward")
+    return out
+
+
+def cross_encoder_workspace_bytes(desc: EncoderDesc, T: int, B: int, f32: bool = False) -> int:
+    fn = lib().mmrag_cross_encoder_f32_workspace_bytes if f32 else lib().mmrag_cross_encoder_workspace_bytes
+    return int(fn(ctypes.byref(desc), T, B))
+
+
+def cross_encoder_forward(desc: EncoderDesc, weight_ptrs, n_labels: int, ids: torch.Tensor, type_ids: torch.Tensor,
+                          pos_ids: torch.Tensor, cu_seqlens: torch.Tensor, max_len: int,
+                          workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                          f32: bool = False) -> torch.Tensor:
+    """One cross-encoder pass over packed (query, passage) sequences -> logits [B, n_labels] float32.  `weight_ptrs`
+    in the order include/mmrag.h documents for mmrag_cross_encoder_forward (see reranker.DeviceCrossEncoder)."""
+    _dev_check(ids, type_ids, pos_ids, cu_seqlens, workspace, out)
+    T, B = ids.numel(), cu_seqlens.numel() - 1
+    need = cross_encoder_workspace_bytes(desc, T, B, f32)
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=ids.device)
+    if out is None:
+        out = torch.empty((B, n_labels), dtype=torch.float32, device=ids.device)
+    fn = lib().mmrag_cross_encoder_forward_f32 if f32 else lib().mmrag_cross_encoder_forward
+    with torch.cuda.device(ids.device):
+        st = fn(ctypes.byref(desc), weight_ptrs, n_labels, ids.data_ptr(), type_ids.data_ptr(), pos_ids.data_ptr(),
+                cu_seqlens.data_ptr(), T, B, max_len, out.data_ptr(), workspace.data_ptr(),
+                workspace.numel() * workspace.element_size(), _stream_ptr(ids.device))
+    _check(st, "mmrag_cross_encoder_forward")
+    return out
+
+
+def embed_types_ln(ids, type_ids, pos_ids, tok, pos, type_tab, gamma, beta, eps: float) -> torch.Tensor:
+    """(tests) the cross-encoder's embedding kernel on its own: LN(tok[ids] + pos[pos_ids] + type_tab[type_ids]); fp16
+    tables -> fp16 rows, fp32 tables -> fp32 rows"""
+    _dev_check(ids, type_ids, pos_ids, tok, pos, type_tab, gamma, beta)
+    T, H = ids.numel(), tok.shape[1]
+    f32 = tok.dtype == torch.float32
+    out = torch.empty((T, H), dtype=tok.dtype, device=tok.device)
+    fn = lib().mmrag_internal_embed_types_ln_f32 if f32 else lib().mmrag_internal_embed_types_ln_f16
+    with torch.cuda.device(tok.device):
+        st = fn(ids.data_ptr(), type_ids.data_ptr(), pos_ids.data_ptr(), tok.data_ptr(), pos.data_ptr(),
+                type_tab.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), T, H, tok.shape[0], pos.shape[0],
+                type_tab.shape[0], eps, _stream_ptr(tok.device))
+    _check(st, "mmrag_internal_embed_types_ln")
+    return out
+
+
+def cls_head_f32(cls: torch.Tensor, wp, bp, wc, bc) -> torch.Tensor:
+    """(tests) the classification head on its own: W_c tanh(W_p cls + b_p) + b_c, all float32"""
+    _dev_check(cls, wp, bp, wc, bc)
+    B, H = cls.shape
+    NL = wc.shape[0]
+    ws = torch.empty(int(lib().mmrag_internal_cls_head_workspace_bytes(B, H, NL)) + 256, dtype=torch.uint8,
+                     device=cls.device)
+    off = (-ws.data_ptr()) % 256
+    out = torch.empty((B, NL), dtype=torch.float32, device=cls.device)
+    with torch.cuda.device(cls.device):
+        st = lib().mmrag_internal_cls_head_f32(cls.data_ptr(), wp.data_ptr(), bp.data_ptr(), wc.data_ptr(), bc.data_ptr(),
+                                               out.data_ptr(), B, H, NL, ws.data_ptr() + off, ws.numel() - off,
+                                               _stream_ptr(cls.device))
+    _check(st, "mmrag_internal_cls_head_f32")
     return out
 
 

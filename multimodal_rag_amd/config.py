@@ -61,6 +61,11 @@ class Settings:
     # cleanup().  Off by default, as in the reference's current code: its chromadb.Client(Settings(persist_directory=...))
     # lacks is_persistent=True, i.e. the reference's collection is in-memory too
     MMRAG_PERSIST: bool = field(default_factory=lambda: _b("MMRAG_PERSIST", "false"))
+    # cross-encoder re-ranking (rerank_results, POST /query with "rerank": true): a local BertForSequenceClassification
+    # directory (config.json + model.safetensors + vocab.txt, e.g. cross-encoder/ms-marco-MiniLM-L-6-v2); empty = the
+    # reference's placeholder (truncation only).  /query re-ranks max(top_k, MMRAG_RERANK_CANDIDATES) search hits
+    MMRAG_RERANKER_DIR: str = field(default_factory=lambda: os.getenv("MMRAG_RERANKER_DIR", ""))
+    MMRAG_RERANK_CANDIDATES: int = field(default_factory=lambda: int(os.getenv("MMRAG_RERANK_CANDIDATES", "20")))
     # CLIP engines only: embed image items from their pixels (vision tower) instead of their summary text
     MMRAG_EMBED_IMAGE_PIXELS: bool = field(default_factory=lambda: _b("MMRAG_EMBED_IMAGE_PIXELS", "true"))
 

@@ -166,6 +166,32 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int *__restrict__ i
     }
 }
 
+// out[t] = LN(tok[ids[t]] + pos[pos_ids[t]] + type[type_ids[t]])   (BERT sequence pairs: segment 0 / 1 per token)
+// The same row arithmetic as embed_ln_kernel with the type row picked per token; ids, positions and type ids are
+// clamped into their tables.  Workgroup 0 also zeroes `zero[0 .. n_zero)` (the head's arrival counters, used later in
+// the same stream).
+__global__ __launch_bounds__(256) void embed_types_ln_kernel(const int *__restrict__ ids, const int *__restrict__ type_ids,
+                                                              const int *__restrict__ pos_ids,
+                                                              const _Float16 *__restrict__ tok,
+                                                              const _Float16 *__restrict__ pos,
+                                                              const _Float16 *__restrict__ type_tab,
+                                                              const float *__restrict__ g, const float *__restrict__ b,
+                                                              _Float16 *__restrict__ out, int T, int H, int vocab,
+                                                              int max_pos, int type_vocab, float eps, int *zero,
+                                                              int n_zero) {
+    if (blockIdx.x == 0)
+        for (int i = threadIdx.x; i < n_zero; i += 256) zero[i] = 0;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= T) return;
+    int id = ids[row], ps = pos_ids[row], ty = type_ids[row];
+    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+    ps = ps < 0 ? 0 : (ps >= max_pos ? max_pos - 1 : ps);
+    ty = ty < 0 ? 0 : (ty >= type_vocab ? type_vocab - 1 : ty);
+    ln_row<2>(tok + (size_t)id * H, out + (size_t)row * H, g, b, H, eps, lane, pos + (size_t)ps * H,
+              type_tab + (size_t)ty * H);
+}
+
 // ---------------------------------------------------------------------------------------------
 // linear: out[M, N] = act(x[M, K] . wt[N, K]^T + bias[N]) (+ resid[M, N])
 // MFMA orientation: D[feature][token]: features in the accumulator registers (MFMA A = weight
@@ -1801,6 +1827,76 @@ int mmrag_vit_forward(const mmrag_encoder_desc *d, const void *const *w, const v
         (const float *)w[4], (_Float16 *)b.x, (int)T, d->hidden, S, d->ln_eps);
     MMRAG_CHECK_HIP(hipGetLastError());
     return encoder_body(d, w + 5, b, cu_seqlens, nullptr, T, B, S, out, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// cross-encoder (sequence-pair classifier): embed with segment ids, the unchanged encoder body pooled at [CLS] without
+// normalisation into a float32 workspace buffer, then the classification head (cross_head.hip)
+// ---------------------------------------------------------------------------------------------
+#define MMRAG_CROSS_TYPE_VOCAB 2   // rows of w[2] the forward reads (BERT's type_vocab_size; pairs use types 0 and 1)
+
+int mmrag_internal_embed_types_ln_f16(const int32_t *ids, const int32_t *type_ids, const int32_t *pos_ids,
+                                      const void *tok, const void *pos, const void *type_tab, const float *gamma,
+                                      const float *beta, void *out, int64_t T, int H, int vocab, int max_pos,
+                                      int type_vocab, float eps, void *stream) {
+    MMRAG_CHECK_ARG(ids && type_ids && pos_ids && tok && pos && type_tab && gamma && beta && out, "embed_types_ln: null pointer");
+    MMRAG_CHECK_ARG(T > 0 && T < INT_MAX && H > 0 && H % 8 == 0 && H <= 1024 && vocab > 0 && max_pos > 0 && type_vocab > 0,
+                    "embed_types_ln: bad shape T=%lld H=%d", (long long)T, H);
+    embed_types_ln_kernel<<<(unsigned)((T + 3) / 4), 256, 0, (hipStream_t)stream>>>(
+        ids, type_ids, pos_ids, (const _Float16 *)tok, (const _Float16 *)pos, (const _Float16 *)type_tab, gamma, beta,
+        (_Float16 *)out, (int)T, H, vocab, max_pos, type_vocab, eps, nullptr, 0);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    return MMRAG_OK;
+}
+
+static size_t cross_tail_bytes(int64_t T, int B, int H) {
+    (void)T;
+    return align256((size_t)B * H * 4) + cls_head_workspace_bytes(B, H, 16);
+}
+
+size_t mmrag_cross_encoder_workspace_bytes(const mmrag_encoder_desc *d, int64_t T, int B) {
+    if (!d || T <= 0 || B <= 0 || d->hidden <= 0) return 0;
+    return mmrag_encoder_workspace_bytes(d, T, B) + cross_tail_bytes(T, B, d->hidden);
+}
+
+int mmrag_cross_encoder_forward(const mmrag_encoder_desc *d, const void *const *w, int n_labels, const int32_t *ids,
+                                const int32_t *type_ids, const int32_t *pos_ids, const int32_t *cu_seqlens, int64_t T,
+                                int B, int max_len, float *out_logits, void *workspace, size_t workspace_bytes,
+                                void *stream) {
+    MMRAG_CHECK_ARG(d && w && ids && type_ids && pos_ids && cu_seqlens && out_logits, "cross_encoder_forward: null pointer");
+    MMRAG_CHECK_ARG(T > 0 && T < INT_MAX && B > 0 && max_len > 0, "cross_encoder_forward: bad shape T=%lld B=%d",
+                    (long long)T, B);
+    MMRAG_CHECK_ARG(d->arch == MMRAG_ARCH_BERT, "cross_encoder_forward: BERT family only (arch %d)", d->arch);
+    MMRAG_CHECK_ARG(n_labels >= 1 && n_labels <= 16, "cross_encoder_forward: n_labels = %d (1..16)", n_labels);
+    MMRAG_CHECK_ARG(d->n_layers > 0 && d->vocab > 0 && d->max_pos > 0 && d->n_heads > 0 && d->hidden % d->n_heads == 0,
+                    "cross_encoder_forward: bad encoder shape");
+    MMRAG_CHECK_ARG(d->hidden / d->n_heads == 32 || d->hidden / d->n_heads == 64,
+                    "cross_encoder_forward: head dimension %d (32 and 64 are built)", d->hidden / d->n_heads);
+    mmrag_encoder_desc dc = *d;   // pool / normalize of the caller's desc are ignored
+    dc.pool = MMRAG_POOL_FIRST, dc.normalize = 0, dc.out_dim = d->hidden;
+    int st;
+    RUN(check_desc(&dc));
+    const size_t body = mmrag_encoder_workspace_bytes(&dc, T, B), need = body + cross_tail_bytes(T, B, dc.hidden);
+    if (!workspace || workspace_bytes < need) {
+        set_error("cross_encoder_forward: workspace %zu bytes < required %zu", workspace_bytes, need);
+        return MMRAG_EWORKSPACE;
+    }
+    EncBuffers b;
+    RUN(carve(&dc, T, B, workspace, body, &b));
+    // the tail: carve() aligned the workspace start up to 256 bytes inside its own 256-byte slack
+    char *tail = (char *)(((uintptr_t)workspace + 255) / 256 * 256) + (body - 256);
+    float *cls = (float *)tail;
+    void *head_ws = tail + align256((size_t)B * dc.hidden * 4);
+    const int H = dc.hidden;
+    embed_types_ln_kernel<<<(unsigned)((T + 3) / 4), 256, 0, (hipStream_t)stream>>>(
+        ids, type_ids, pos_ids, (const _Float16 *)w[0], (const _Float16 *)w[1], (const _Float16 *)w[2],
+        (const float *)w[3], (const float *)w[4], (_Float16 *)b.x, (int)T, H, dc.vocab, dc.max_pos,
+        MMRAG_CROSS_TYPE_VOCAB, dc.ln_eps, cls_head_counter_ptr(head_ws, B, H, n_labels), cls_head_counters(B));
+    MMRAG_CHECK_HIP(hipGetLastError());
+    RUN(encoder_body(&dc, w + 5, b, cu_seqlens, nullptr, T, B, max_len, cls, stream));
+    const void *const *hw = w + 5 + 12 * dc.n_layers;
+    return launch_cls_head_f32(cls, (const float *)hw[0], (const float *)hw[1], (const float *)hw[2],
+                               (const float *)hw[3], out_logits, B, H, n_labels, head_ws, (hipStream_t)stream);
 }
 #undef RUN
 

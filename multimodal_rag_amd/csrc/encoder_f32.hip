@@ -92,6 +92,29 @@ __global__ __launch_bounds__(256) void embed_ln_f32_kernel(const int *__restrict
     ln_row_f32(tok + (size_t)id * H, pos + (size_t)ps * H, type0, out + (size_t)row * H, g, b, H, eps, threadIdx.x & 63);
 }
 
+// the same with a segment id per token: out[t] = LN(tok[ids[t]] + pos[pos_ids[t]] + type[type_ids[t]]) (cross-encoder
+// pairs); type ids are clamped like ids.  Workgroup 0 also zeroes zero[0 .. n_zero) (the head's arrival counters).
+__global__ __launch_bounds__(256) void embed_types_ln_f32_kernel(const int *__restrict__ ids,
+                                                                 const int *__restrict__ type_ids,
+                                                                 const int *__restrict__ pos_ids,
+                                                                 const float *__restrict__ tok, const float *__restrict__ pos,
+                                                                 const float *__restrict__ type_tab,
+                                                                 const float *__restrict__ g, const float *__restrict__ b,
+                                                                 float *__restrict__ out, int T, int H, int vocab,
+                                                                 int max_pos, int type_vocab, float eps, int *zero,
+                                                                 int n_zero) {
+    if (blockIdx.x == 0)
+        for (int i = threadIdx.x; i < n_zero; i += 256) zero[i] = 0;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= T) return;
+    int id = ids[row], ps = pos_ids[row], ty = type_ids[row];
+    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+    ps = ps < 0 ? 0 : (ps >= max_pos ? max_pos - 1 : ps);
+    ty = ty < 0 ? 0 : (ty >= type_vocab ? type_vocab - 1 : ty);
+    ln_row_f32(tok + (size_t)id * H, pos + (size_t)ps * H, type_tab + (size_t)ty * H, out + (size_t)row * H, g, b, H, eps,
+               threadIdx.x & 63);
+}
+
 // ---- out = act(x . Wt^T + bias) (+ resid), all float32.  128 tokens x 128 features per workgroup, 4 waves of 64 x 64
 // (2 x 2 MFMA tiles of 32 x 32), K in 128-byte slabs (32 floats) through a two-stage LDS-DMA ring, XOR-swizzled like
 // every slab tile of this library.  v_mfma_f32_32x32x2_f32 takes ONE float per lane and operand: lane (r, h) feeds
@@ -439,37 +462,38 @@ int mmrag_internal_pool_norm_f32(const float *x, const int32_t *cu_seqlens, cons
 
 #define RUN(call) do { if ((st = (call)) != MMRAG_OK) return st; } while (0)
 
-int mmrag_encoder_forward_f32(const mmrag_encoder_desc *d, const void *const *w, const int32_t *ids,
-                              const int32_t *pos_ids, const int32_t *cu_seqlens, const int32_t *sel, int64_t T, int B,
-                              int max_len, float *out, void *workspace, size_t workspace_bytes, void *stream) {
-    MMRAG_CHECK_ARG(d && w && ids && pos_ids && cu_seqlens && out, "encoder_forward_f32: null pointer");
-    MMRAG_CHECK_ARG(T > 0 && T < INT_MAX && B > 0 && max_len > 0, "encoder_forward_f32: bad shape T=%lld B=%d", (long long)T, B);
-    MMRAG_CHECK_ARG(d->arch == MMRAG_ARCH_BERT, "encoder_forward_f32: the float32 mode covers the BERT family only");
+struct F32Buffers {
+    float *x, *y, *qkv, *ctx, *hm;
+};
+
+static int check_f32_desc(const mmrag_encoder_desc *d, const char *what) {
+    MMRAG_CHECK_ARG(d->arch == MMRAG_ARCH_BERT, "%s: the float32 mode covers the BERT family only", what);
     MMRAG_CHECK_ARG(d->hidden % 64 == 0 && d->intermediate % 64 == 0 && d->hidden <= 1024,
-                    "encoder_forward_f32: hidden/intermediate must be multiples of 64 (hidden <= 1024)");
-    MMRAG_CHECK_ARG(d->n_heads > 0 && d->hidden % d->n_heads == 0, "encoder_forward_f32: bad head count");
-    const int H = d->hidden, I = d->intermediate, DH = H / d->n_heads;
-    MMRAG_CHECK_ARG(DH == 32 || DH == 64, "encoder_forward_f32: head dimension %d (32 and 64 are built)", DH);
-    MMRAG_CHECK_ARG(d->pool >= 0 && d->pool <= 2 && (d->pool != 2 || sel), "encoder_forward_f32: bad pool mode");
-    MMRAG_CHECK_ARG(!d->causal, "encoder_forward_f32: causal attention is not built (BERT is bidirectional)");
-    const size_t need = mmrag_encoder_f32_workspace_bytes(d, T, B);
-    if (!workspace || workspace_bytes < need) {
-        set_error("encoder_forward_f32: workspace %zu bytes < required %zu", workspace_bytes, need);
-        return MMRAG_EWORKSPACE;
-    }
-    const size_t Tz = (size_t)T;
+                    "%s: hidden/intermediate must be multiples of 64 (hidden <= 1024)", what);
+    MMRAG_CHECK_ARG(d->n_heads > 0 && d->hidden % d->n_heads == 0, "%s: bad head count", what);
+    const int DH = d->hidden / d->n_heads;
+    MMRAG_CHECK_ARG(DH == 32 || DH == 64, "%s: head dimension %d (32 and 64 are built)", what, DH);
+    MMRAG_CHECK_ARG(!d->causal, "%s: causal attention is not built (BERT is bidirectional)", what);
+    return MMRAG_OK;
+}
+
+static F32Buffers carve_f32(const mmrag_encoder_desc *d, int64_t T, void *workspace) {
+    const size_t Tz = (size_t)T, H = (size_t)d->hidden, I = (size_t)d->intermediate;
     char *pw = (char *)(((uintptr_t)workspace + 255) / 256 * 256);
     auto take = [&](size_t bytes) { char *r = pw; pw += align256f(bytes); return (float *)r; };
-    float *x = take(Tz * H * 4), *y = take(Tz * H * 4), *qkv = take(Tz * 3 * H * 4), *ctx = take(Tz * H * 4);
-    float *hm = take(Tz * (size_t)I * 4);
-    hipStream_t s = (hipStream_t)stream;
+    F32Buffers b;
+    b.x = take(Tz * H * 4), b.y = take(Tz * H * 4), b.qkv = take(Tz * 3 * H * 4), b.ctx = take(Tz * H * 4);
+    b.hm = take(Tz * I * 4);
+    return b;
+}
+
+// the transformer blocks over the embedded rows in b.x; the last layer's output ends in b.x
+static int f32_layers(const mmrag_encoder_desc *d, const void *const *lw, const F32Buffers &b, const int32_t *cu_seqlens,
+                      int64_t T, int B, int max_len, hipStream_t s) {
+    const int H = d->hidden, I = d->intermediate, DH = H / d->n_heads;
+    float *x = b.x, *y = b.y, *qkv = b.qkv, *ctx = b.ctx, *hm = b.hm;
     const unsigned row_grid = (unsigned)((T + 3) / 4);
     int st;
-    embed_ln_f32_kernel<<<row_grid, 256, 0, s>>>(ids, pos_ids, (const float *)w[0], (const float *)w[1],
-                                                 (const float *)w[2], (const float *)w[3], (const float *)w[4], x,
-                                                 (int)T, H, d->vocab, d->max_pos, d->ln_eps);
-    MMRAG_CHECK_HIP(hipGetLastError());
-    const void *const *lw = w + 5;
     for (int l = 0; l < d->n_layers; ++l, lw += 12) {
         RUN(launch_linear_f32(x, T, H, (const float *)lw[0], 3 * H, (const float *)lw[1], MMRAG_ACT_NONE, nullptr, qkv, s));
         launch_attention_f32(qkv, cu_seqlens, ctx, B, max_len, H, DH, s);
@@ -481,9 +505,91 @@ int mmrag_encoder_forward_f32(const mmrag_encoder_desc *d, const void *const *w,
         layernorm_f32_kernel<<<row_grid, 256, 0, s>>>(y, x, (const float *)lw[10], (const float *)lw[11], (int)T, H, d->ln_eps);
         MMRAG_CHECK_HIP(hipGetLastError());
     }
-    pool_norm_f32_kernel<<<(unsigned)B, 256, 0, s>>>(x, cu_seqlens, sel, out, H, d->pool, d->normalize);
+    return MMRAG_OK;
+}
+
+int mmrag_encoder_forward_f32(const mmrag_encoder_desc *d, const void *const *w, const int32_t *ids,
+                              const int32_t *pos_ids, const int32_t *cu_seqlens, const int32_t *sel, int64_t T, int B,
+                              int max_len, float *out, void *workspace, size_t workspace_bytes, void *stream) {
+    MMRAG_CHECK_ARG(d && w && ids && pos_ids && cu_seqlens && out, "encoder_forward_f32: null pointer");
+    MMRAG_CHECK_ARG(T > 0 && T < INT_MAX && B > 0 && max_len > 0, "encoder_forward_f32: bad shape T=%lld B=%d", (long long)T, B);
+    int st;
+    RUN(check_f32_desc(d, "encoder_forward_f32"));
+    MMRAG_CHECK_ARG(d->pool >= 0 && d->pool <= 2 && (d->pool != 2 || sel), "encoder_forward_f32: bad pool mode");
+    const size_t need = mmrag_encoder_f32_workspace_bytes(d, T, B);
+    if (!workspace || workspace_bytes < need) {
+        set_error("encoder_forward_f32: workspace %zu bytes < required %zu", workspace_bytes, need);
+        return MMRAG_EWORKSPACE;
+    }
+    const F32Buffers b = carve_f32(d, T, workspace);
+    hipStream_t s = (hipStream_t)stream;
+    embed_ln_f32_kernel<<<(unsigned)((T + 3) / 4), 256, 0, s>>>(ids, pos_ids, (const float *)w[0], (const float *)w[1],
+                                                                (const float *)w[2], (const float *)w[3],
+                                                                (const float *)w[4], b.x, (int)T, d->hidden, d->vocab,
+                                                                d->max_pos, d->ln_eps);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    RUN(f32_layers(d, w + 5, b, cu_seqlens, T, B, max_len, s));
+    pool_norm_f32_kernel<<<(unsigned)B, 256, 0, s>>>(b.x, cu_seqlens, sel, out, d->hidden, d->pool, d->normalize);
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
+}
+
+// ---- cross-encoder, float32 (mmrag.h): embed with segment ids, the same layers, [CLS] rows, the classification head --
+static size_t cross_f32_tail_bytes(int B, int H) { return align256f((size_t)B * H * 4) + cls_head_workspace_bytes(B, H, 16); }
+
+size_t mmrag_cross_encoder_f32_workspace_bytes(const mmrag_encoder_desc *d, int64_t T, int B) {
+    if (!d || T <= 0 || B <= 0 || d->hidden <= 0) return 0;
+    return mmrag_encoder_f32_workspace_bytes(d, T, B) + cross_f32_tail_bytes(B, d->hidden);
+}
+
+int mmrag_internal_embed_types_ln_f32(const int32_t *ids, const int32_t *type_ids, const int32_t *pos_ids,
+                                      const float *tok, const float *pos, const float *type_tab, const float *gamma,
+                                      const float *beta, float *out, int64_t T, int H, int vocab, int max_pos,
+                                      int type_vocab, float eps, void *stream) {
+    MMRAG_CHECK_ARG(ids && type_ids && pos_ids && tok && pos && type_tab && gamma && beta && out,
+                    "embed_types_ln_f32: null pointer");
+    MMRAG_CHECK_ARG(T > 0 && T < INT_MAX && H > 0 && H % 4 == 0 && H <= 1024 && vocab > 0 && max_pos > 0 && type_vocab > 0,
+                    "embed_types_ln_f32: bad shape T=%lld H=%d", (long long)T, H);
+    embed_types_ln_f32_kernel<<<(unsigned)((T + 3) / 4), 256, 0, (hipStream_t)stream>>>(
+        ids, type_ids, pos_ids, tok, pos, type_tab, gamma, beta, out, (int)T, H, vocab, max_pos, type_vocab, eps, nullptr, 0);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    return MMRAG_OK;
+}
+
+int mmrag_cross_encoder_forward_f32(const mmrag_encoder_desc *d, const void *const *w, int n_labels, const int32_t *ids,
+                                    const int32_t *type_ids, const int32_t *pos_ids, const int32_t *cu_seqlens,
+                                    int64_t T, int B, int max_len, float *out_logits, void *workspace,
+                                    size_t workspace_bytes, void *stream) {
+    MMRAG_CHECK_ARG(d && w && ids && type_ids && pos_ids && cu_seqlens && out_logits,
+                    "cross_encoder_forward_f32: null pointer");
+    MMRAG_CHECK_ARG(T > 0 && T < INT_MAX && B > 0 && max_len > 0, "cross_encoder_forward_f32: bad shape T=%lld B=%d",
+                    (long long)T, B);
+    MMRAG_CHECK_ARG(n_labels >= 1 && n_labels <= 16, "cross_encoder_forward_f32: n_labels = %d (1..16)", n_labels);
+    MMRAG_CHECK_ARG(d->n_layers > 0 && d->vocab > 0 && d->max_pos > 0, "cross_encoder_forward_f32: bad encoder shape");
+    int st;
+    RUN(check_f32_desc(d, "cross_encoder_forward_f32"));
+    const size_t body = mmrag_encoder_f32_workspace_bytes(d, T, B), need = body + cross_f32_tail_bytes(B, d->hidden);
+    if (!workspace || workspace_bytes < need) {
+        set_error("cross_encoder_forward_f32: workspace %zu bytes < required %zu", workspace_bytes, need);
+        return MMRAG_EWORKSPACE;
+    }
+    const F32Buffers b = carve_f32(d, T, workspace);
+    const int H = d->hidden;
+    char *tail = (char *)(((uintptr_t)workspace + 255) / 256 * 256) + (body - 256);
+    float *cls = (float *)tail;
+    void *head_ws = tail + align256f((size_t)B * H * 4);
+    hipStream_t s = (hipStream_t)stream;
+    embed_types_ln_f32_kernel<<<(unsigned)((T + 3) / 4), 256, 0, s>>>(
+        ids, type_ids, pos_ids, (const float *)w[0], (const float *)w[1], (const float *)w[2], (const float *)w[3],
+        (const float *)w[4], b.x, (int)T, H, d->vocab, d->max_pos, 2, d->ln_eps, cls_head_counter_ptr(head_ws, B, H, n_labels),
+        cls_head_counters(B));
+    MMRAG_CHECK_HIP(hipGetLastError());
+    RUN(f32_layers(d, w + 5, b, cu_seqlens, T, B, max_len, s));
+    pool_norm_f32_kernel<<<(unsigned)B, 256, 0, s>>>(b.x, cu_seqlens, nullptr, cls, H, MMRAG_POOL_FIRST, 0);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    const void *const *hw = w + 5 + 12 * d->n_layers;
+    return launch_cls_head_f32(cls, (const float *)hw[0], (const float *)hw[1], (const float *)hw[2],
+                               (const float *)hw[3], out_logits, B, H, n_labels, head_ws, s);
 }
 #undef RUN
 

@@ -46,3 +46,12 @@ constexpr unsigned DBG_ATTENTION_STREAMED = 4096u;   // attention: the double-bu
 constexpr unsigned DBG_LINEAR_TILE64 = 1024u, DBG_LINEAR_TILE128 = 2048u;   // mid-size M: force 64x64 / 128x128 tiles (A/B)   // BERT single-query forward with LayerNorm launches (A/B, tests)   // M <= 64: the 32-feature workgroups for every K (A/B)   // timing only: every tile reads the first token tile
 
 }  // namespace mmrag
+
+// the cross-encoder's classification head (cross_head.hip), shared by the fp16 and fp32 forwards
+namespace mmrag_impl {
+size_t cls_head_workspace_bytes(int B, int H, int NL);
+int cls_head_counters(int B);
+int *cls_head_counter_ptr(void *ws, int B, int H, int NL);
+int launch_cls_head_f32(const float *cls, const float *wp, const float *bp, const float *wc, const float *bc, float *out,
+                        int B, int H, int NL, void *ws, hipStream_t s);
+}  // namespace mmrag_impl

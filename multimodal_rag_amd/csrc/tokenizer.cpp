@@ -8,6 +8,7 @@
 // per slice of the batch.  Unicode data comes from unicode_tables.inc, generated from the same
 // interpreter's unicodedata that tokenizer.py uses; tests/test_tokenizer.py fuzzes the two against
 // each other.
+#include <limits.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -222,12 +223,9 @@ void wordpiece(const Vocab &v, const u32s &word, std::vector<int32_t> &ids) {
     }
 }
 
-void encode_one(const Vocab &v, const uint32_t *text, size_t n, int max_length, int32_t *out, int32_t *out_len) {
-    std::vector<int32_t> ids;
-    ids.reserve((size_t)max_length + 8);
-    ids.push_back(v.cls);
+// the WordPiece ids of `text` appended to `ids`, stopping once ids holds `stop` entries (it may hold a few more)
+void pieces(const Vocab &v, const uint32_t *text, size_t n, int stop, std::vector<int32_t> &ids) {
     u32s word, low, norm, tmp, piece;
-    const int stop = max_length - 1;
     auto flush_piece = [&]() {
         if (!piece.empty()) {
             wordpiece(v, piece, ids);
@@ -279,11 +277,34 @@ void encode_one(const Vocab &v, const uint32_t *text, size_t n, int max_length, 
         }
     }
     if (more) flush_word();
+}
+
+void encode_one(const Vocab &v, const uint32_t *text, size_t n, int max_length, int32_t *out, int32_t *out_len) {
+    std::vector<int32_t> ids;
+    ids.reserve((size_t)max_length + 8);
+    ids.push_back(v.cls);
+    const int stop = max_length - 1;
+    pieces(v, text, n, stop, ids);
     int len = (int)ids.size();
     if (len > stop) len = stop;
     for (int i = 0; i < len; ++i) out[i] = ids[i];
     out[len] = v.sep;
     *out_len = len + 1;
+}
+
+// lengths kept of a pair of piece lists under `budget` tokens: the fast tokenizer's TruncationStrategy::LongestFirst
+void longest_first(int la, int lb, int budget, int *ka, int *kb) {
+    if (la + lb <= budget) {
+        *ka = la, *kb = lb;
+    } else if (la <= lb && la <= budget / 2) {
+        *ka = la, *kb = budget - la;
+    } else if (lb < la && lb <= budget / 2) {
+        *ka = budget - lb, *kb = lb;
+    } else {
+        const int h = budget / 2;
+        *ka = la > lb ? budget - h : h;
+        *kb = budget - *ka;
+    }
 }
 
 }  // namespace
@@ -342,6 +363,65 @@ int mmrag_wordpiece_encode_batch(const void *tk, const uint32_t *cps, const int6
         for (int i = lo; i < hi; ++i)
             encode_one(v, cps + offsets[i], (size_t)(offsets[i + 1] - offsets[i]), max_length,
                        ids + (size_t)i * max_length, lens + i);
+    };
+    if (n_threads == 1) {
+        work(0, n);
+        return MMRAG_OK;
+    }
+    std::vector<std::thread> th;
+    const int per = (n + n_threads - 1) / n_threads;
+    for (int t = 0; t < n_threads; ++t) {
+        const int lo = t * per, hi = std::min(n, lo + per);
+        if (lo < hi) th.emplace_back(work, lo, hi);
+    }
+    for (auto &t : th) t.join();
+    return MMRAG_OK;
+}
+
+// pairs i = (a_i, b_i): [CLS] a [SEP] b [SEP], type ids 0 through the first [SEP], 1 after it; LongestFirst truncation
+// of the pieces to max_length - 3.  Each side is tokenised in full (the rule compares the untruncated lengths); a text
+// equal to the previous pair's text on the same side is not tokenised again (the query of a rerank batch).
+int mmrag_wordpiece_encode_pairs(const void *tk, const uint32_t *cps_a, const int64_t *offsets_a, const uint32_t *cps_b,
+                                 const int64_t *offsets_b, int n, int max_length, int32_t *ids, int32_t *type_ids,
+                                 int32_t *lens, int n_threads) {
+    MMRAG_CHECK_ARG(tk && offsets_a && offsets_b && ids && type_ids && lens, "wordpiece_encode_pairs: null pointer");
+    MMRAG_CHECK_ARG(n >= 0 && max_length >= 3, "wordpiece_encode_pairs: bad shape n=%d max_length=%d", n, max_length);
+    MMRAG_CHECK_ARG(n == 0 || ((cps_a || offsets_a[n] == offsets_a[0]) && (cps_b || offsets_b[n] == offsets_b[0])),
+                    "wordpiece_encode_pairs: null text");
+    const Vocab &v = *(const Vocab *)tk;
+    if (n_threads < 1) n_threads = 1;
+    if (n_threads > n) n_threads = n > 0 ? n : 1;
+    if (n > 0) {   // as mmrag_wordpiece_encode_batch: a thread per ~16 k code points
+        const int64_t by_work = 1 + (offsets_a[n] - offsets_a[0] + offsets_b[n] - offsets_b[0]) / 16384;
+        if (n_threads > by_work) n_threads = (int)by_work;
+    }
+    const int budget = max_length - 3;
+    auto same_as_prev = [](const uint32_t *cps, const int64_t *off, int i) {
+        const int64_t n0 = off[i] - off[i - 1], n1 = off[i + 1] - off[i];
+        return n0 == n1 && std::equal(cps + off[i - 1], cps + off[i], cps + off[i]);
+    };
+    auto work = [&](int lo, int hi) {
+        std::vector<int32_t> pa, pb;
+        for (int i = lo; i < hi; ++i) {
+            if (i == lo || !same_as_prev(cps_a, offsets_a, i)) {
+                pa.clear();
+                pieces(v, cps_a + offsets_a[i], (size_t)(offsets_a[i + 1] - offsets_a[i]), INT_MAX, pa);
+            }
+            if (i == lo || !same_as_prev(cps_b, offsets_b, i)) {
+                pb.clear();
+                pieces(v, cps_b + offsets_b[i], (size_t)(offsets_b[i + 1] - offsets_b[i]), INT_MAX, pb);
+            }
+            int ka, kb;
+            longest_first((int)pa.size(), (int)pb.size(), budget, &ka, &kb);
+            int32_t *o = ids + (size_t)i * max_length, *ty = type_ids + (size_t)i * max_length;
+            int at = 0;
+            o[at] = v.cls, ty[at++] = 0;
+            for (int j = 0; j < ka; ++j) o[at] = pa[j], ty[at++] = 0;
+            o[at] = v.sep, ty[at++] = 0;
+            for (int j = 0; j < kb; ++j) o[at] = pb[j], ty[at++] = 1;
+            o[at] = v.sep, ty[at++] = 1;
+            lens[i] = at;
+        }
     };
     if (n_threads == 1) {
         work(0, n);

@@ -22,6 +22,7 @@ from __future__ import annotations
 import asyncio
 import hashlib
 import logging
+import threading
 import time
 from typing import Any, Dict, List, Optional, Sequence
 
@@ -69,6 +70,8 @@ class EmbeddingManager:
         self._dispatcher = None
         self._encode_lock = asyncio.Lock()       # one encoder pass at a time from this event loop
         self._sleep = asyncio.sleep              # (tests swap the back-off sleep out)
+        self._reranker = None                    # cross-encoder (MMRAG_RERANKER_DIR), loaded on first use
+        self._reranker_lock = threading.Lock()
 
     # ------------------------------------------------------------------ lifecycle -----------
     async def initialize(self):
@@ -360,13 +363,41 @@ class EmbeddingManager:
             logger.error("Failed to find similar documents: %s", e)
             raise
 
+    def has_reranker(self) -> bool:
+        """True when rerank_results re-scores (a cross-encoder is configured: MMRAG_RERANKER_DIR, or one was set)"""
+        return self._reranker is not None or bool(settings.MMRAG_RERANKER_DIR)
+
+    def _get_reranker(self):
+        """the cross-encoder of MMRAG_RERANKER_DIR, loaded once on the embedder's device"""
+        with self._reranker_lock:
+            if self._reranker is None:
+                from .reranker import DeviceCrossEncoder
+
+                device = getattr(self._engine, "device", None) or "cuda:0"
+                self._reranker = DeviceCrossEncoder.from_local_dir(settings.MMRAG_RERANKER_DIR, device)
+            return self._reranker
+
     async def rerank_results(self, query_text: str, results: Dict[str, Any],
                              top_k: Optional[int] = None) -> Dict[str, Any]:
-        """embedder.py:834-859: the reference's placeholder -- no re-ranking, only truncation to top_k."""
-        logger.warning("Re-ranking not implemented yet")
-        if top_k and top_k < len(results["ids"]):
-            return {key: results[key][:top_k] for key in RESULT_KEYS}
-        return results
+        """embedder.py:834-859.  Without a cross-encoder (MMRAG_RERANKER_DIR empty): the reference's placeholder -- no
+        re-ranking, only truncation to top_k.  With one: every (query_text, document) pair is scored (a None document
+        as ""), the results are reordered by descending score (stable: ties keep the search order), truncated to top_k
+        and carry their scores in `rerank_scores` (a multi-label model's first logit column is the score)."""
+        if not self.has_reranker():
+            logger.warning("Re-ranking not implemented yet")
+            if top_k and top_k < len(results["ids"]):
+                return {key: results[key][:top_k] for key in RESULT_KEYS}
+            return results
+        reranker = self._reranker if self._reranker is not None else await asyncio.to_thread(self._get_reranker)
+        docs = [d if d is not None else "" for d in results["documents"]]
+        scores = await asyncio.to_thread(reranker.predict, [(query_text, d) for d in docs]) if docs else []
+        scores = [float(x) for x in np.asarray(scores, np.float64).reshape(len(docs), -1)[:, 0]] if docs else []
+        order = sorted(range(len(docs)), key=lambda i: -scores[i])
+        if top_k:
+            order = order[:top_k]
+        out = {key: [results[key][i] for i in order] for key in RESULT_KEYS}
+        out["rerank_scores"] = [scores[i] for i in order]
+        return out
 
     # ------------------------------------------------------------------ maintenance ---------
     async def delete_document(self, doc_id: str):

@@ -33,6 +33,9 @@ class QueryRequest(BaseModel):  # api.py:161-164
     query: str = Field(..., min_length=1, max_length=2000)
     top_k: int = Field(5, ge=1, le=20)
     use_multimodal: bool = Field(False)
+    # not in the reference: re-score max(top_k, MMRAG_RERANK_CANDIDATES) hits with the cross-encoder of
+    # MMRAG_RERANKER_DIR and answer from the best top_k (each source then carries its `rerank_score`)
+    rerank: bool = Field(False)
 
 
 class QueryResponse(BaseModel):  # api.py:167-170
@@ -119,9 +122,15 @@ class Pipeline:
         return {"doc_id": doc_id, "filename": filename, "doc_type": tree.get("doc_type", "unknown"),
                 "chunks_processed": stored}
 
-    async def answer(self, question: str, top_k: int, multimodal: bool) -> Optional[dict]:
-        """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved"""
-        hits = await self.embedder.query(question, n_results=top_k)
+    async def answer(self, question: str, top_k: int, multimodal: bool, rerank: bool = False) -> Optional[dict]:
+        """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
+        max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the cross-encoder's best top_k"""
+        if rerank:
+            hits = await self.embedder.query(question, n_results=max(top_k, settings.MMRAG_RERANK_CANDIDATES))
+            if hits["ids"]:
+                hits = await self.embedder.rerank_results(question, hits, top_k=top_k)
+        else:
+            hits = await self.embedder.query(question, n_results=top_k)
         if not hits["ids"]:
             return None
         raw = await self.retriever.retrieve_raw_documents(hits["ids"])
@@ -138,6 +147,9 @@ class Pipeline:
         ranked = [{"rank": at, "doc_id": found, "relevance_score": round(float(1.0 - min(dist, 1.0)), 3),   # api.py:390
                    "type": meta.get("type", "unknown")}
                   for at, (found, dist, meta) in enumerate(zip(hits["ids"], hits["distances"], hits["metadatas"]), 1)]
+        if rerank:
+            for src, score in zip(ranked, hits["rerank_scores"]):
+                src["rerank_score"] = score
         return {"answer": text, "sources": ranked}
 
     async def health(self) -> dict:
@@ -223,7 +235,13 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
     @_as_http_500
     async def query_documents(request: QueryRequest):  # api.py:325-413
         t0 = time.time()
-        out = await pipe.answer(request.query, request.top_k, request.use_multimodal)
+        if request.rerank and not (hasattr(pipe.embedder, "has_reranker") and pipe.embedder.has_reranker()):
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                detail="Re-ranking is not configured: set MMRAG_RERANKER_DIR to a local cross-encoder")
+        if request.rerank:
+            out = await pipe.answer(request.query, request.top_k, request.use_multimodal, rerank=True)
+        else:
+            out = await pipe.answer(request.query, request.top_k, request.use_multimodal)
         if out is None:
             out = {"answer": NO_DOCS_ANSWER, "sources": []}
         return {**out, "processing_time": time.time() - t0}

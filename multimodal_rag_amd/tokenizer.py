@@ -103,6 +103,40 @@ class WordPieceTokenizer:
                 break
         return ids[: max_length - 1] + [self.sep]
 
+    def pieces(self, text: str) -> List[int]:
+        """every WordPiece id of `text` (no special tokens, no truncation)"""
+        ids: List[int] = []
+        for w in basic_tokenize(text, self.lower):
+            ids.extend(self._wordpiece(w))
+        return ids
+
+    def encode_pair(self, a: str, b: str, max_length: int):
+        """(ids, type_ids) of the pair [CLS] a [SEP] b [SEP] -- what CrossEncoder's fast tokenizer produces for a
+        (query, passage) pair: type 0 through the first [SEP], 1 after it; pieces cut to max_length - 3 by
+        `longest_first`."""
+        if max_length < 3:
+            raise ValueError("max_length must be >= 3 for a pair")
+        pa, pb = self.pieces(a), self.pieces(b)
+        ka, kb = longest_first(len(pa), len(pb), max_length - 3)
+        ids = [self.cls] + pa[:ka] + [self.sep] + pb[:kb] + [self.sep]
+        return ids, [0] * (ka + 2) + [1] * (kb + 1)
+
+
+def longest_first(la: int, lb: int, budget: int):
+    """Lengths kept of two piece lists under `budget`: the fast (`tokenizers`) TruncationStrategy::LongestFirst.  When
+    the shorter side fits in half the budget the longer side gets the rest; otherwise each side gets budget // 2 and the
+    odd token goes to the longer side (to the second side on equal lengths).  (The slow BertTokenizer removes one token
+    at a time and splits differently.)"""
+    if la + lb <= budget:
+        return la, lb
+    if la <= lb and la <= budget // 2:
+        return la, budget - la
+    if lb < la and lb <= budget // 2:
+        return budget - lb, lb
+    h = budget // 2
+    ka = budget - h if la > lb else h
+    return ka, budget - ka
+
 
 def _utf32(strings):
     """(codepoints uint32 [total], offsets int64 [n+1]) of a list of str (lone surrogates pass through)."""
@@ -163,6 +197,28 @@ class NativeWordPieceTokenizer:
         if st:
             raise RuntimeError(self._lib.mmrag_last_error().decode())
         return ids, lens
+
+    def encode_pairs_arrays(self, firsts: List[str], seconds: List[str], max_length: int):
+        """(ids [n, max_length] int32, type_ids [n, max_length] int32, lens [n] int32) of the pairs (firsts[i],
+        seconds[i]) as `WordPieceTokenizer.encode_pair` lays them out; entries past lens[i] are unspecified.  A text
+        equal to the previous pair's (the query of a rerank batch) is tokenised once."""
+        np = self._np
+        if len(firsts) != len(seconds):
+            raise ValueError("firsts and seconds differ in length")
+        if max_length < 3:
+            raise ValueError("max_length must be >= 3 for a pair")
+        n = len(firsts)
+        ca, oa = _utf32(firsts)
+        cb, ob = _utf32(seconds)
+        ids = np.empty((n, max_length), np.int32)
+        types = np.empty((n, max_length), np.int32)
+        lens = np.empty(n, np.int32)
+        st = self._lib.mmrag_wordpiece_encode_pairs(self._h, ca.ctypes.data, oa.ctypes.data, cb.ctypes.data,
+                                                    ob.ctypes.data, n, max_length, ids.ctypes.data, types.ctypes.data,
+                                                    lens.ctypes.data, min(16, self.n_threads))
+        if st:
+            raise RuntimeError(self._lib.mmrag_last_error().decode())
+        return ids, types, lens
 
     def encode_batch(self, texts: List[str], max_length: int) -> List[List[int]]:
         np = self._np
