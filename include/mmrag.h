@@ -266,6 +266,58 @@ int mmrag_wordpiece_encode_pairs(const void *tokenizer, const uint32_t *cps_a, c
                                  const uint32_t *cps_b, const int64_t *offsets_b, int n, int max_length, int32_t *ids,
                                  int32_t *type_ids, int32_t *lens, int n_threads);
 
+/* ---------------------------------------------------------------------------------------
+ * Lexical retrieval (BM25).  The full-text leg the reference's Chroma store keeps beside its vector index
+ * (an FTS5 table over every document); fused with the dense leg by VectorIndex.hybrid_query.
+ *
+ * Analyzer + lexicon (HOST, multi-threaded): BERT's text cleaning, whitespace split and CJK spacing; each word
+ * str.lower() then its canonical decomposition KEEPING the combining marks; split at punctuation, which is dropped.
+ * No stemming, no stop words.  The lexicon maps term strings to int32 ids in first-seen order.
+ *   analyze_batch  text i = cps[offsets[i] .. offsets[i+1]); out_offsets [n+1]; pairs of text i are
+ *                  (term_ids, tfs)[out_offsets[i] .. out_offsets[i+1]); dl [n] = its token count (unknown terms
+ *                  included).  MMRAG_LEX_DOCUMENTS adds unseen terms and sorts each text's pairs by term id;
+ *                  MMRAG_LEX_QUERIES adds nothing, drops unknown terms and keeps the order of first occurrence.
+ *                  More than `capacity` pairs: MMRAG_EWORKSPACE with out_offsets filled in (call again with
+ *                  capacity >= out_offsets[n]; adding terms twice is harmless). */
+#define MMRAG_LEX_DOCUMENTS 0
+#define MMRAG_LEX_QUERIES 1
+void *mmrag_lexicon_create(void);
+void mmrag_lexicon_destroy(void *lexicon);
+int64_t mmrag_lexicon_size(const void *lexicon);
+int mmrag_lexicon_analyze_batch(void *lexicon, const uint32_t *cps, const int64_t *offsets, int n, int mode,
+                                int64_t *out_offsets, int32_t *term_ids, int32_t *tfs, int32_t *dl, int64_t capacity,
+                                int n_threads);
+
+/* Device index (all pointers dev).  Forward log: row r's postings are (fwd_term, fwd_tf)[fwd_off[r] .. fwd_off[r+1]),
+ * sorted by term id (as MMRAG_LEX_DOCUMENTS produces them).  df [n_terms] counts the LIVE rows holding each term.
+ *   df_update   df[t] += sign for every posting of rows[0 .. n_rows) (rows NULL: rows row0 .. row0 + n_rows); sign +-1.
+ *               Integer atomics: the result does not depend on their order.
+ *   csr_build   the term-major inverted index of rows [0, n): post_row / post_tf [term_off[t] .. term_off[t+1]) hold
+ *               term t's postings sorted by row (dead rows included: the alive bits filter them).  term_off [n_terms+1],
+ *               post_* [fwd_off[n]].  Counting sort (histogram, scan, scatter) then a per-term sort by row.
+ *   bm25_topk   for query b with terms q_terms[q_off[b] .. q_off[b+1]) (distinct, in order of first occurrence):
+ *                 score(d) = sum_t idf_t * tf (k1 + 1) / (tf + k1 (1 - b + b dl_d / avgdl)),
+ *                 idf_t = ln(1 + (N - df_t + 0.5) / (df_t + 0.5)),  N = n_live,  avgdl = sum_dl / N,
+ *               float32, the terms added in query order.  Rows with a score > 0 (at least one query term), set in
+ *               alive_bits (NULL = every row) compete; out [B, k] score desc, ties to the lower row, (-inf, -1) padded.
+ *               k 1..MMRAG_MAX_K_DEEP.  Synchronises `stream` once to read the per-query match counts (a query
+ *               whose matches overflow its candidate buffer is re-run alone into a buffer of n slots).
+ *   rows_dot    out[i] = <q[qi[i]], corpus[rows[i]]> over the first d columns, float32 (the cosine of a row the dense
+ *               leg did not return). */
+int mmrag_lexical_df_update(const int64_t *fwd_off, const int32_t *fwd_term, const int64_t *rows, int64_t row0,
+                            int64_t n_rows, int sign, int32_t *df, void *stream);
+size_t mmrag_lexical_csr_build_workspace_bytes(int64_t n, int n_terms);
+int mmrag_lexical_csr_build(const int64_t *fwd_off, const int32_t *fwd_term, const int32_t *fwd_tf, int64_t n,
+                            int64_t n_postings, int n_terms, int64_t *term_off, int32_t *post_row, int32_t *post_tf,
+                            void *workspace, size_t workspace_bytes, void *stream);
+size_t mmrag_bm25_topk_workspace_bytes(int B, int64_t n, int k);
+int mmrag_bm25_topk(const int64_t *term_off, const int32_t *post_row, const int32_t *post_tf, const int32_t *dl,
+                    const int32_t *df, int n_terms, int64_t n, const int32_t *q_off, const int32_t *q_terms, int B,
+                    int64_t n_live, int64_t sum_dl, float k1, float b, int k, const uint32_t *alive_bits,
+                    float *out_scores, int64_t *out_rows, void *workspace, size_t workspace_bytes, void *stream);
+int mmrag_rows_dot(const void *q, const void *corpus, int64_t ld, int dtype, int d, const int32_t *qi,
+                   const int64_t *rows, int64_t m, float *out, void *stream);
+
 /* CLIP byte-level BPE (the text tower's tokenizer, BASELINE config 4; the reference only names CLIP in config.py:106).
  * Host code, multi-threaded; equals multimodal_rag_amd/tokenizer.py:ClipBpeTokenizer, which tests pin to
  * transformers.CLIPTokenizer.  The caller passes text already NFC-normalised, whitespace-collapsed and lower-cased.

@@ -165,6 +165,9 @@ def _declare(lib):
     lib.mmrag_internal_cls_head_f32.argtypes = [c_void_p] * 6 + [c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]
     lib.mmrag_internal_cls_head_workspace_bytes.restype = c_size_t
     lib.mmrag_internal_cls_head_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    from .lexical import declare as declare_lexical   # BM25 analyzer, device index and search (csrc/lexical.hip)
+
+    declare_lexical(lib)
 
 
 def lib():

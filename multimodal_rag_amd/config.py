@@ -66,6 +66,14 @@ class Settings:
     # reference's placeholder (truncation only).  /query re-ranks max(top_k, MMRAG_RERANK_CANDIDATES) search hits
     MMRAG_RERANKER_DIR: str = field(default_factory=lambda: os.getenv("MMRAG_RERANKER_DIR", ""))
     MMRAG_RERANK_CANDIDATES: int = field(default_factory=lambda: int(os.getenv("MMRAG_RERANK_CANDIDATES", "20")))
+    # BM25 lexical leg (VectorIndex.lexical_query / hybrid_query, csrc/lexical.hip): term-frequency saturation k1 and
+    # length normalisation b of the score, the same for every query
+    MMRAG_BM25_K1: float = field(default_factory=lambda: float(os.getenv("MMRAG_BM25_K1", "1.2")))
+    MMRAG_BM25_B: float = field(default_factory=lambda: float(os.getenv("MMRAG_BM25_B", "0.75")))
+    # hybrid retrieval: each leg returns max(n_results, MMRAG_HYBRID_CANDIDATES) hits (at most 4096), fused by
+    # reciprocal rank with sum 1 / (MMRAG_HYBRID_RRF_K + rank)
+    MMRAG_HYBRID_CANDIDATES: int = field(default_factory=lambda: int(os.getenv("MMRAG_HYBRID_CANDIDATES", "50")))
+    MMRAG_HYBRID_RRF_K: int = field(default_factory=lambda: int(os.getenv("MMRAG_HYBRID_RRF_K", "60")))
     # CLIP engines only: embed image items from their pixels (vision tower) instead of their summary text
     MMRAG_EMBED_IMAGE_PIXELS: bool = field(default_factory=lambda: _b("MMRAG_EMBED_IMAGE_PIXELS", "true"))
 

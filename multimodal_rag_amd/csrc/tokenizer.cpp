@@ -101,8 +101,8 @@ inline uint32_t ccc_of(uint32_t cp) {
     return m ? m[1] : 0;
 }
 
-// unicodedata.normalize("NFD", w) with the Mn characters dropped afterwards
-void nfd_strip_mn(const u32s &w, u32s &out, u32s &tmp) {
+// unicodedata.normalize("NFD", w), with the Mn characters dropped afterwards when strip_mn is set
+void nfd(const u32s &w, u32s &out, u32s &tmp, bool strip_mn) {
     tmp.clear();
     for (uint32_t c : w) {
         if (c < 0xC0) {
@@ -134,8 +134,10 @@ void nfd_strip_mn(const u32s &w, u32s &out, u32s &tmp) {
     }
     out.clear();
     for (uint32_t c : tmp)
-        if (!(c >= 0x300 && in_ranges(RANGES_MN, c))) out.push_back(c);
+        if (!strip_mn || !(c >= 0x300 && in_ranges(RANGES_MN, c))) out.push_back(c);
 }
+
+void nfd_strip_mn(const u32s &w, u32s &out, u32s &tmp) { nfd(w, out, tmp, true); }
 
 struct Vocab {
     // open-addressing table over (codepoint string -> id); `first` = whole entries, `cont` = entries that
@@ -307,6 +309,116 @@ void longest_first(int la, int lb, int budget, int *ka, int *kb) {
     }
 }
 
+// fn(lo, hi) over [0, n) on up to n_threads threads, one contiguous slice each
+template <class F>
+void parallel_slices(int n, int n_threads, F fn) {
+    if (n_threads > n) n_threads = n > 0 ? n : 1;
+    if (n_threads <= 1) {
+        fn(0, n);
+        return;
+    }
+    std::vector<std::thread> th;
+    const int per = (n + n_threads - 1) / n_threads;
+    for (int t = 0; t < n_threads; ++t) {
+        const int lo = t * per, hi = std::min(n, lo + per);
+        if (lo < hi) th.emplace_back(fn, lo, hi);
+    }
+    for (auto &t : th) t.join();
+}
+
+// ---- BM25 word analyzer and lexicon ------------------------------------------------------------------------------
+// The terms of one text: BERT's cleaning, whitespace split and CJK spacing (as `pieces`), then per word str.lower()
+// and the canonical decomposition WITH its combining marks ("học" != "hoc"), split at punctuation, which is dropped.
+// Term i of the text is pool[ends[i-1] .. ends[i]) (ends[-1] = 0).
+struct Analyzed {
+    u32s pool;
+    std::vector<uint32_t> ends;
+    std::vector<int32_t> ids;   // term ids in token order (-1: not in the lexicon)
+};
+
+void analyze_text(const uint32_t *text, size_t n, Analyzed &a) {
+    a.pool.clear();
+    a.ends.clear();
+    u32s word, low, norm, tmp;
+    auto flush_word = [&]() {
+        if (word.empty()) return;
+        lower_word(word, low);
+        nfd(low, norm, tmp, false);
+        size_t start = a.pool.size();
+        for (uint32_t c : norm) {
+            if (is_punct(c)) {
+                if (a.pool.size() > start) a.ends.push_back((uint32_t)a.pool.size());
+                start = a.pool.size();
+            } else {
+                a.pool.push_back(c);
+            }
+        }
+        if (a.pool.size() > start) a.ends.push_back((uint32_t)a.pool.size());
+        word.clear();
+    };
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t c = text[i];
+        if (c == 0 || c == 0xFFFD) continue;
+        const bool ws = c == ' ' || c == '\t' || c == '\n' || c == '\r';
+        if (!ws && (c < 0x20 || (c >= 0x7F && in_ranges(RANGES_CTRL, c)))) continue;  // Cc / Cf
+        if (ws || (c >= 0xA0 && in_ranges(RANGES_ZS, c)) || c == 0x2028 || c == 0x2029 || c == 0x1C || c == 0x1D ||
+            c == 0x1E || c == 0x1F || c == 0x85) {
+            flush_word();
+        } else if (is_cjk(c)) {
+            flush_word();
+            word.push_back(c);
+            flush_word();
+        } else {
+            word.push_back(c);
+        }
+    }
+    flush_word();
+}
+
+// term string -> int32 id in first-seen order: a growable open-addressing table over one code-point pool
+struct Lexicon {
+    struct Slot {
+        uint64_t hash;
+        uint64_t off;
+        uint32_t len;
+        int32_t id;
+    };
+    u32s pool;
+    std::vector<Slot> slots;
+    size_t mask;
+    int32_t n = 0;
+    Lexicon() : slots(1024, Slot{0, 0, 0, -1}), mask(1023) {}
+
+    int32_t find(const uint32_t *p, size_t len) const {
+        const uint64_t h = Vocab::Table::hash_of(p, len);
+        for (size_t i = h & mask; slots[i].hash; i = (i + 1) & mask)
+            if (slots[i].hash == h && slots[i].len == len && !memcmp(&pool[slots[i].off], p, len * 4)) return slots[i].id;
+        return -1;
+    }
+    int32_t insert(const uint32_t *p, size_t len) {
+        const int32_t got = find(p, len);
+        if (got >= 0) return got;
+        if ((size_t)(n + 1) * 2 > slots.size()) {
+            std::vector<Slot> old;
+            old.swap(slots);
+            slots.assign(old.size() * 2, Slot{0, 0, 0, -1});
+            mask = slots.size() - 1;
+            for (const Slot &s : old) {
+                if (!s.hash) continue;
+                size_t i = s.hash & mask;
+                while (slots[i].hash) i = (i + 1) & mask;
+                slots[i] = s;
+            }
+        }
+        const uint64_t h = Vocab::Table::hash_of(p, len);
+        size_t i = h & mask;
+        while (slots[i].hash) i = (i + 1) & mask;
+        slots[i] = Slot{h, (uint64_t)pool.size(), (uint32_t)len, n};
+        pool.insert(pool.end(), p, p + len);
+        return n++;
+    }
+};
+
 }  // namespace
 
 using namespace mmrag;
@@ -434,6 +546,92 @@ int mmrag_wordpiece_encode_pairs(const void *tk, const uint32_t *cps_a, const in
         if (lo < hi) th.emplace_back(work, lo, hi);
     }
     for (auto &t : th) t.join();
+    return MMRAG_OK;
+}
+
+void *mmrag_lexicon_create(void) { return new Lexicon(); }
+
+void mmrag_lexicon_destroy(void *lexicon) { delete (Lexicon *)lexicon; }
+
+int64_t mmrag_lexicon_size(const void *lexicon) { return lexicon ? ((const Lexicon *)lexicon)->n : -1; }
+
+// Analysis on n_threads threads (a thread per ~16 k code points, as mmrag_wordpiece_encode_batch); only the insertion
+// of unseen terms runs on one thread, in text order, so ids are first-seen whatever the thread count.
+int mmrag_lexicon_analyze_batch(void *lexicon, const uint32_t *cps, const int64_t *offsets, int n, int mode,
+                                int64_t *out_offsets, int32_t *term_ids, int32_t *tfs, int32_t *dl, int64_t capacity,
+                                int n_threads) {
+    MMRAG_CHECK_ARG(lexicon && offsets && out_offsets && dl, "lexicon_analyze_batch: null pointer");
+    MMRAG_CHECK_ARG(n >= 0, "lexicon_analyze_batch: n=%d", n);
+    MMRAG_CHECK_ARG(mode == MMRAG_LEX_DOCUMENTS || mode == MMRAG_LEX_QUERIES, "lexicon_analyze_batch: bad mode %d", mode);
+    MMRAG_CHECK_ARG(n == 0 || cps || offsets[n] == offsets[0], "lexicon_analyze_batch: null text");
+    MMRAG_CHECK_ARG(capacity >= 0 && (capacity == 0 || (term_ids && tfs)), "lexicon_analyze_batch: null output");
+    Lexicon &lx = *(Lexicon *)lexicon;
+    if (n_threads < 1) n_threads = 1;
+    if (n > 0) {
+        const int64_t by_work = 1 + (offsets[n] - offsets[0]) / 16384;
+        if (n_threads > by_work) n_threads = (int)by_work;
+    }
+    std::vector<Analyzed> docs((size_t)n);
+    // 1. split and normalise; look every term up (read-only: no insertion runs meanwhile)
+    parallel_slices(n, n_threads, [&](int lo, int hi) {
+        for (int i = lo; i < hi; ++i) {
+            Analyzed &a = docs[i];
+            analyze_text(cps + offsets[i], (size_t)(offsets[i + 1] - offsets[i]), a);
+            a.ids.resize(a.ends.size());
+            for (size_t t = 0, b = 0; t < a.ends.size(); b = a.ends[t++]) a.ids[t] = lx.find(&a.pool[b], a.ends[t] - b);
+        }
+    });
+    // 2. documents: unseen terms get ids in text order
+    if (mode == MMRAG_LEX_DOCUMENTS) {
+        for (Analyzed &a : docs)
+            for (size_t t = 0, b = 0; t < a.ends.size(); b = a.ends[t++])
+                if (a.ids[t] < 0) a.ids[t] = lx.insert(&a.pool[b], a.ends[t] - b);
+    }
+    // 3. (term id, tf) pairs: documents sorted by id, queries in order of first occurrence; unknown terms dropped
+    std::vector<std::vector<std::pair<int32_t, int32_t>>> pairs((size_t)n);
+    parallel_slices(n, n_threads, [&](int lo, int hi) {
+        std::vector<int32_t> sorted;
+        for (int i = lo; i < hi; ++i) {
+            const Analyzed &a = docs[i];
+            auto &out = pairs[i];
+            dl[i] = (int32_t)a.ids.size();
+            sorted.clear();
+            for (int32_t id : a.ids)
+                if (id >= 0) sorted.push_back(id);
+            std::sort(sorted.begin(), sorted.end());
+            for (size_t j = 0; j < sorted.size();) {
+                size_t e = j;
+                while (e < sorted.size() && sorted[e] == sorted[j]) ++e;
+                out.emplace_back(sorted[j], (int32_t)(e - j));
+                j = e;
+            }
+            if (mode == MMRAG_LEX_QUERIES) {
+                // first-occurrence order: rank each distinct id by the position it first appears at
+                std::vector<std::pair<size_t, std::pair<int32_t, int32_t>>> first;
+                for (const auto &p : out) {
+                    const size_t at = (size_t)(std::find(a.ids.begin(), a.ids.end(), p.first) - a.ids.begin());
+                    first.emplace_back(at, p);
+                }
+                std::sort(first.begin(), first.end());
+                for (size_t j = 0; j < out.size(); ++j) out[j] = first[j].second;
+            }
+        }
+    });
+    out_offsets[0] = 0;
+    for (int i = 0; i < n; ++i) out_offsets[i + 1] = out_offsets[i] + (int64_t)pairs[i].size();
+    if (out_offsets[n] > capacity) {
+        set_error("lexicon_analyze_batch: %lld pairs > capacity %lld", (long long)out_offsets[n], (long long)capacity);
+        return MMRAG_EWORKSPACE;
+    }
+    parallel_slices(n, n_threads, [&](int lo, int hi) {
+        for (int i = lo; i < hi; ++i) {
+            int64_t at = out_offsets[i];
+            for (const auto &p : pairs[i]) {
+                term_ids[at] = p.first;
+                tfs[at++] = p.second;
+            }
+        }
+    });
     return MMRAG_OK;
 }
 

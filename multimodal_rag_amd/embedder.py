@@ -37,6 +37,7 @@ logger = logging.getLogger(__name__)
 
 ITEM_KINDS = ("text", "table", "image")           # the kinds embed_and_store counts (embedder.py:477-479)
 RESULT_KEYS = ("ids", "distances", "metadatas", "documents")
+HYBRID_KEYS = RESULT_KEYS + ("hybrid_scores", "lexical_scores")
 _HOSTROWS = load_hostrows()
 _COLLECTION_NOTE = {"description": "Multi-modal RAG embeddings"}
 
@@ -317,6 +318,39 @@ class EmbeddingManager:
             hit = (await self._engine_call("Query", self._answer, [query_text], n_results, filter_dict))[0]
         except Exception as e:
             logger.error("Query failed: %s", e, exc_info=True)
+            raise
+        self.stats["total_queries"] += 1
+        return hit
+
+    def supports_hybrid(self) -> bool:
+        """True when the collection can answer hybrid_query (a single-GPU VectorIndex; not the sharded serving path)"""
+        return self.collection is None or hasattr(self.collection, "hybrid_query")
+
+    def _answer_hybrid(self, text: str, n_results: int, filter_dict: Optional[Dict]) -> Dict[str, Any]:
+        """blocking, one worker thread: cached or fresh embedding, then ONE collection.hybrid_query"""
+        rows, todo, keys = self._lookup([text])
+        if todo:
+            self._encode_into([text], rows, todo, keys)
+        matrix = self._stack(rows, len(todo))
+        res = self.collection.hybrid_query(matrix, [text], n_results=n_results, where=filter_dict,
+                                           include=self._INCLUDE)
+        return {key: res[key][0] for key in HYBRID_KEYS}
+
+    async def hybrid_query(self, query_text: str, n_results: int = 5,
+                           filter_dict: Optional[Dict] = None) -> Dict[str, Any]:
+        """Dense + BM25 retrieval fused by reciprocal rank (VectorIndex.hybrid_query): one result dict with `ids`,
+        `distances`, `metadatas`, `documents`, `hybrid_scores` and `lexical_scores`, in hybrid-score order (distances
+        are therefore not ascending).  Same empty-query error, embedding cache and query count as query(); it calls
+        the collection directly (no dynamic batching)."""
+        await self._ready()
+        if not query_text or not query_text.strip():
+            raise ValueError("Query text cannot be empty")
+        if not hasattr(self.collection, "hybrid_query"):
+            raise ValueError("hybrid retrieval needs a single-GPU collection (VectorIndex)")
+        try:
+            hit = await self._engine_call("Hybrid query", self._answer_hybrid, query_text, n_results, filter_dict)
+        except Exception as e:
+            logger.error("Hybrid query failed: %s", e, exc_info=True)
             raise
         self.stats["total_queries"] += 1
         return hit

@@ -187,6 +187,7 @@ class VectorIndex:
         self._lock = threading.RLock()
         self._search_ws: Optional[torch.Tensor] = None    # candidate-list workspace of the search kernels, reused
         self._deep_ws: Optional[torch.Tensor] = None      # workspace of the deep search (n_results > 20), reused
+        self._lex = None   # lexical.LexicalIndex once enable_lexical() ran (lazily: first lexical / hybrid query)
         from .config import settings
 
         self.f32_exact = bool(settings.MMRAG_F32_EXACT_SEARCH)   # float32 collections only (see config.py)
@@ -316,6 +317,8 @@ class VectorIndex:
                 self._metadatas.append(metadatas[i])
             self._meta_index.append([metadatas[i] for i in keep])
             self._set_alive(self._n, self._n + len(keep))
+            if self._lex is not None:
+                self._lex.append([documents[i] for i in keep])
             self._n += len(keep)
             self._grown(len(keep))
 
@@ -332,6 +335,8 @@ class VectorIndex:
             self._metadatas.extend(metadatas if metadatas is not None else [{} for _ in range(m)])
             self._meta_index.append(self._metadatas[self._n: self._n + m])
             self._set_alive(self._n, self._n + m)
+            if self._lex is not None:
+                self._lex.append(self._documents[self._n: self._n + m])
             self._n += m
             self._grown(m)
 
@@ -584,6 +589,8 @@ class VectorIndex:
             # text there.  The alive bitmap and _row_of are what say "dead"; compact() drops the entries for good.
             self._clear_alive(rows)
             self._n_dead += int(rows.size)
+            if self._lex is not None:
+                self._lex.delete_rows(rows)
             if self._n_dead >= self.COMPACT_MIN_DEAD and self._n_dead > self.COMPACT_DEAD_FRACTION * self._n:
                 self.compact()
             return sorted(gone)
@@ -612,6 +619,8 @@ class VectorIndex:
             self._alive_dev = torch.zeros(self._n_words(cap), dtype=torch.int32, device=self.device)
             if self._n:
                 self._set_alive(0, self._n)
+            if self._lex is not None:
+                self._lex.compact(keep)
 
     def reset(self):
         with self._lock:
@@ -621,3 +630,112 @@ class VectorIndex:
             self._meta_index = MetaIndex()
             self._alive_host[:] = 0
             self._alive_dev.zero_()
+            if self._lex is not None:
+                self._lex.reset()
+
+    # ------------------------------------------------------------------ lexical / hybrid ----
+    def enable_lexical(self):
+        """Build the BM25 state (lexical.LexicalIndex) from the stored documents in row order; from then on add,
+        add_rows_device, delete, compact and reset keep it current.  Until then they do no lexical work.  Runs by
+        itself on the first lexical_query / hybrid_query."""
+        with self._lock:
+            if self._lex is None:
+                from .lexical import LexicalIndex
+
+                lex = LexicalIndex(self.device)
+                lex.append(self._documents[: self._n])
+                if self._n_dead:
+                    lex.delete_rows(np.nonzero(self._is_dead(np.arange(self._n, dtype=np.int64)))[0])
+                self._lex = lex
+            return self._lex
+
+    @property
+    def lexical_enabled(self) -> bool:
+        return self._lex is not None
+
+    def _lexical_search(self, query_texts: Sequence[str], n_results: int, where):
+        """enqueue the BM25 search (caller holds the lock): device (scores, rows), -1 padded"""
+        if isinstance(query_texts, str):
+            raise ValueError("query_texts must be a list of strings")
+        if n_results < 1 or n_results > _native.MAX_K_DEEP:
+            raise ValueError(f"n_results must be in 1..{_native.MAX_K_DEEP} for lexical search")
+        lex = self.enable_lexical()
+        return lex.topk(list(query_texts), n_results, self._where_bits(where))
+
+    def lexical_query(self, query_texts: Sequence[str], n_results: int = 10, where: Optional[Dict[str, Any]] = None,
+                      include: Sequence[str] = ("metadatas", "documents")) -> Dict[str, Any]:
+        """BM25 search (csrc/lexical.hip): Chroma-shaped lists of lists `ids`, `documents`, `metadatas` and
+        `lexical_scores` (descending; ties to the lower row).  Only rows holding at least one query term are returned,
+        so a list may be shorter than n_results.  Statistics (N, avgdl, df) are over the live rows; `where` restricts
+        the results only."""
+        with self._lock:
+            scores, rows = self._lexical_search(query_texts, n_results, where)
+            ids_t, docs_t, metas_t = self._ids, self._documents, self._metadatas
+        scores_h, rows_h = scores.cpu(), rows.cpu()
+        out: Dict[str, Any] = {"ids": [], "documents": [] if "documents" in include else None,
+                               "metadatas": [] if "metadatas" in include else None, "lexical_scores": []}
+        for srow, rrow in zip(scores_h.tolist(), rows_h.tolist()):
+            hit = [r for r in rrow if r >= 0]
+            out["ids"].append([ids_t[r] for r in hit])
+            out["lexical_scores"].append(srow[: len(hit)])
+            if out["documents"] is not None:
+                out["documents"].append([docs_t[r] for r in hit])
+            if out["metadatas"] is not None:
+                out["metadatas"].append([dict(metas_t[r]) for r in hit])
+        return out
+
+    def hybrid_query(self, query_embeddings, query_texts: Sequence[str], n_results: int = 10,
+                     where: Optional[Dict[str, Any]] = None,
+                     include: Sequence[str] = ("metadatas", "documents", "distances"),
+                     check_norm: bool = True) -> Dict[str, Any]:
+        """Dense + lexical retrieval fused by reciprocal rank (lexical.rrf_fuse).  Each leg takes
+        C = max(n_results, MMRAG_HYBRID_CANDIDATES) hits (at most 4096) under the same `where`; a row scores
+        sum 1 / (MMRAG_HYBRID_RRF_K + rank) over the legs that returned it.  Returns `ids`, `documents`, `metadatas`,
+        `distances`, `hybrid_scores` and `lexical_scores` (0.0 for rows the lexical leg did not return), ordered by
+        hybrid score -- so `distances` (1 - cos, the dense leg's own value where it returned the row, else computed on
+        the device from the stored row) are NOT ascending."""
+        from .config import settings
+        from .lexical import rows_dot, rrf_fuse
+
+        texts = list(query_texts)
+        if n_results < 1:
+            raise ValueError("n_results must be >= 1")
+        C = min(max(n_results, settings.MMRAG_HYBRID_CANDIDATES), _native.MAX_K_DEEP)
+        with self._lock:
+            q = self._pack_queries(query_embeddings, check_norm)
+            if q.shape[0] != len(texts):
+                raise ValueError(f"{q.shape[0]} query embeddings for {len(texts)} query texts")
+            d_scores, d_rows = self._launch_search(query_embeddings, C, where, check_norm)
+            l_scores, l_rows = self._lexical_search(texts, C, where)
+            ids_t, docs_t, metas_t = self._ids, self._documents, self._metadatas
+            d_s, d_r = d_scores.cpu(), d_rows.cpu()
+            l_s, l_r = l_scores.cpu().tolist(), l_rows.cpu().tolist()
+            dist_dense = (1.0 - d_s).tolist()                    # float32 arithmetic, as query() does
+            fused, need = [], []
+            for b in range(len(texts)):
+                drow = [r for r in d_r[b].tolist() if r >= 0]
+                lrow = [r for r in l_r[b] if r >= 0]
+                top = rrf_fuse(drow, lrow, settings.MMRAG_HYBRID_RRF_K)[:n_results]
+                dpos = {r: i for i, r in enumerate(drow)}
+                fused.append((top, dpos, {r: l_s[b][i] for i, r in enumerate(lrow)}))
+                need.extend((b, r) for r, _ in top if r not in dpos)
+            if need:
+                dots = rows_dot(q, self._matrix, self.dim, torch.tensor([b for b, _ in need], device=self.device),
+                                torch.tensor([r for _, r in need], device=self.device))
+                extra = dict(zip(need, (1.0 - dots.cpu()).tolist()))
+            else:
+                extra = {}
+        out: Dict[str, Any] = {"ids": [], "distances": [], "hybrid_scores": [], "lexical_scores": [],
+                               "documents": [] if "documents" in include else None,
+                               "metadatas": [] if "metadatas" in include else None}
+        for b, (top, dpos, lex) in enumerate(fused):
+            rows = [r for r, _ in top]
+            out["ids"].append([ids_t[r] for r in rows])
+            out["hybrid_scores"].append([s for _, s in top])
+            out["lexical_scores"].append([lex.get(r, 0.0) for r in rows])
+            out["distances"].append([dist_dense[b][dpos[r]] if r in dpos else extra[(b, r)] for r in rows])
+            if out["documents"] is not None:
+                out["documents"].append([docs_t[r] for r in rows])
+            if out["metadatas"] is not None:
+                out["metadatas"].append([dict(metas_t[r]) for r in rows])
+        return out

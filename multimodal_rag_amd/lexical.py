@@ -1,0 +1,356 @@
+"""BM25 lexical retrieval on the device, and reciprocal-rank fusion with the dense leg.
+
+The reference's Chroma store keeps every document in a full-text index beside its vector index; this module is that
+leg for `VectorIndex`.  Analysis is host code (csrc/tokenizer.cpp, with `analyze` below as its
+pure-Python twin); postings, statistics and scoring live on the device (csrc/lexical.hip).
+
+Scoring contract (the tests pin it against tests/bm25_ref.py):
+  score(q, d) = sum over the distinct known terms t of q, in order of first occurrence, of
+                idf_t * tf (k1 + 1) / (tf + k1 (1 - b + b dl / avgdl)),   idf_t = ln(1 + (N - df_t + 0.5) / (df_t + 0.5))
+  with N, avgdl = sum(dl) / N and df over the LIVE rows (a `where` filter restricts results, not statistics), float32 on
+  the device.  Rows with score > 0, alive and passing `where`, ordered by score, ties to the lower row.
+"""
+from __future__ import annotations
+
+import os
+import unicodedata
+from ctypes import c_float, c_int, c_int64, c_size_t, c_void_p
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _native
+from .tokenizer import _is_cjk, _is_punct, _utf32
+
+LEX_DOCUMENTS, LEX_QUERIES = 0, 1   # mmrag_lexicon_analyze_batch modes (include/mmrag.h)
+
+
+def analyze(text: Optional[str]) -> List[str]:
+    """The BM25 terms of `text` (pure Python; csrc/tokenizer.cpp analyze_text is the native twin): BERT's cleaning,
+    CJK spacing and whitespace split, then per word str.lower() and NFD keeping the combining marks, split at
+    punctuation, which is dropped.  No stemming, no stop words.  None is empty."""
+    if not text:
+        return []
+    out = []
+    for ch in text:
+        cp = ord(ch)
+        if cp == 0 or cp == 0xFFFD or (unicodedata.category(ch) in ("Cc", "Cf") and ch not in "\t\n\r"):
+            continue
+        if _is_cjk(cp):
+            out.append(f" {ch} ")
+        elif ch in " \t\n\r" or unicodedata.category(ch) == "Zs":
+            out.append(" ")
+        else:
+            out.append(ch)
+    terms: List[str] = []
+    for w in "".join(out).split():
+        cur = ""
+        for ch in unicodedata.normalize("NFD", w.lower()):
+            if _is_punct(ch):
+                if cur:
+                    terms.append(cur)
+                cur = ""
+            else:
+                cur += ch
+        if cur:
+            terms.append(cur)
+    return terms
+
+
+def rrf_fuse(dense_rows: Sequence[int], lexical_rows: Sequence[int], k: int = 60) -> List[Tuple[int, float]]:
+    """Reciprocal-rank fusion of one query's two ranked row lists: every row of either list with score
+    sum 1 / (k + rank) over the lists it is in (ranks 1-based, the dense term added first), ordered by score
+    descending, ties to the better dense rank (absent = worst), then to the lower row."""
+    dense_rank = {int(r): i + 1 for i, r in enumerate(dense_rows)}
+    score: Dict[int, float] = {r: 1.0 / (k + rank) for r, rank in dense_rank.items()}
+    for i, r in enumerate(lexical_rows):
+        r = int(r)
+        score[r] = score.get(r, 0.0) + 1.0 / (k + i + 1)
+    worst = len(dense_rank) + 1
+    order = sorted(score, key=lambda r: (-score[r], dense_rank.get(r, worst), r))
+    return [(r, score[r]) for r in order]
+
+
+class Lexicon:
+    """term string -> int32 id in first-seen order (libmmrag.so's native lexicon).  Host only: works without a GPU."""
+
+    def __init__(self, n_threads: int = 0):
+        self._lib = _native.lib()
+        self._h = self._lib.mmrag_lexicon_create()
+        self.n_threads = n_threads or min(16, os.cpu_count() or 1)
+
+    def __len__(self) -> int:
+        return int(self._lib.mmrag_lexicon_size(self._h))
+
+    def analyze_batch(self, texts: Sequence[Optional[str]], mode: int):
+        """(offsets int64 [n+1], term_ids int32, tfs int32, dl int32 [n]) of `texts`; pairs of text i at
+        offsets[i] .. offsets[i+1].  LEX_DOCUMENTS adds unseen terms (pairs sorted by id); LEX_QUERIES drops unknown
+        terms (pairs in order of first occurrence)."""
+        cps, offs = _utf32([t or "" for t in texts])
+        n = len(texts)
+        out_off = np.zeros(n + 1, np.int64)
+        dl = np.zeros(n, np.int32)
+        cap = int(cps.size) + 1
+        while True:
+            ids = np.empty(cap, np.int32)
+            tfs = np.empty(cap, np.int32)
+            st = self._lib.mmrag_lexicon_analyze_batch(self._h, cps.ctypes.data, offs.ctypes.data, n, mode,
+                                                       out_off.ctypes.data, ids.ctypes.data, tfs.ctypes.data,
+                                                       dl.ctypes.data, cap, self.n_threads)
+            if st == 2 and int(out_off[n]) > cap:      # MMRAG_EWORKSPACE: more pairs than code points (rare)
+                cap = int(out_off[n])
+                continue
+            _native._check(st, "mmrag_lexicon_analyze_batch")
+            total = int(out_off[n])
+            return out_off, ids[:total], tfs[:total], dl
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.mmrag_lexicon_destroy(h)
+
+
+def _grow(t: torch.Tensor, need: int) -> torch.Tensor:
+    if t.numel() >= need:
+        return t
+    out = torch.zeros(max(need, 2 * t.numel()), dtype=t.dtype, device=t.device)
+    out[: t.numel()].copy_(t)
+    return out
+
+
+class LexicalIndex:
+    """The device lexical state of one `VectorIndex` (its owner holds the lock around every call).
+
+    Forward log (row-major postings, grown like the matrix) and per-row dl on the device; df per term kept by integer
+    kernels; N and sum(dl) as host integers.  The term-major CSR is rebuilt on the device (counting sort) by the first
+    search after adds; deletes only update df, N and sum(dl) -- the alive bits filter dead rows."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.reset()
+
+    def reset(self):
+        dev = self.device
+        self.n = 0
+        self.n_live = 0
+        self.sum_dl = 0
+        self._off_host = np.zeros(1, np.int64)
+        self._dl_host = np.zeros(0, np.int32)
+        self._fwd_off = torch.zeros(257, dtype=torch.int64, device=dev)
+        self._fwd_term = torch.zeros(4096, dtype=torch.int32, device=dev)
+        self._fwd_tf = torch.zeros(4096, dtype=torch.int32, device=dev)
+        self._dl = torch.zeros(256, dtype=torch.int32, device=dev)
+        self._df = torch.zeros(1024, dtype=torch.int32, device=dev)
+        self._csr = None                  # (term_off, post_row, post_tf) of rows [0, _csr_n), n_terms = _csr_terms
+        self._csr_n = self._csr_terms = -1
+        self._csr_ws = None
+        self._search_ws = None
+        self.csr_builds = 0               # how many times the CSR was rebuilt (tests, tools)
+        self.lexicon = Lexicon()
+        self._max_term = -1               # largest term id appended (synthetic postings bypass the lexicon)
+
+    @property
+    def n_terms(self) -> int:
+        return max(len(self.lexicon), self._max_term + 1)
+
+    @property
+    def n_postings(self) -> int:
+        return int(self._off_host[-1])
+
+    def _stream(self) -> int:
+        return _native._stream_ptr(self.device)
+
+    def append(self, documents: Sequence[Optional[str]]):
+        """analyse and append rows n .. n + len(documents), all alive"""
+        m = len(documents)
+        if m == 0:
+            return
+        off, ids, tfs, dl = self.lexicon.analyze_batch(documents, LEX_DOCUMENTS)
+        self.append_postings(off, ids, tfs, dl)
+
+    def append_postings(self, off: np.ndarray, ids: np.ndarray, tfs: np.ndarray, dl: np.ndarray):
+        """append already analysed rows (offsets [m+1] from 0, term ids sorted within each row, distinct): the form
+        `Lexicon.analyze_batch(..., LEX_DOCUMENTS)` returns; tools feed synthetic corpora through it"""
+        m = int(dl.size)
+        p0 = self.n_postings
+        if ids.size:
+            self._max_term = max(self._max_term, int(ids.max()))
+        new_off = p0 + np.asarray(off, np.int64)
+        self._fwd_off = _grow(self._fwd_off, self.n + m + 1)
+        self._fwd_term = _grow(self._fwd_term, p0 + int(ids.size))
+        self._fwd_tf = _grow(self._fwd_tf, p0 + int(ids.size))
+        self._dl = _grow(self._dl, self.n + m)
+        self._df = _grow(self._df, max(self.n_terms, 1))
+        self._fwd_off[self.n: self.n + m + 1].copy_(torch.from_numpy(new_off))
+        if ids.size:
+            self._fwd_term[p0: p0 + ids.size].copy_(torch.from_numpy(np.ascontiguousarray(ids, np.int32)))
+            self._fwd_tf[p0: p0 + ids.size].copy_(torch.from_numpy(np.ascontiguousarray(tfs, np.int32)))
+        self._dl[self.n: self.n + m].copy_(torch.from_numpy(np.ascontiguousarray(dl, np.int32)))
+        self._off_host = np.concatenate([self._off_host[:-1], new_off])
+        self._dl_host = np.concatenate([self._dl_host, np.asarray(dl, np.int32)])
+        with torch.cuda.device(self.device):
+            _native._check(_native.lib().mmrag_lexical_df_update(self._fwd_off.data_ptr(), self._fwd_term.data_ptr(),
+                                                                 None, self.n, m, 1, self._df.data_ptr(),
+                                                                 self._stream()), "mmrag_lexical_df_update")
+        self.n += m
+        self.n_live += m
+        self.sum_dl += int(np.asarray(dl, np.int64).sum())
+
+    def delete_rows(self, rows: np.ndarray):
+        """rows (live, distinct) became dead: df, N and sum(dl) drop them; the CSR stays valid"""
+        rows = np.ascontiguousarray(rows, np.int64)
+        if rows.size == 0:
+            return
+        dev_rows = torch.from_numpy(rows).to(self.device)
+        with torch.cuda.device(self.device):
+            _native._check(_native.lib().mmrag_lexical_df_update(self._fwd_off.data_ptr(), self._fwd_term.data_ptr(),
+                                                                 dev_rows.data_ptr(), 0, rows.size, -1,
+                                                                 self._df.data_ptr(), self._stream()),
+                           "mmrag_lexical_df_update")
+        self.n_live -= int(rows.size)
+        self.sum_dl -= int(self._dl_host[rows].astype(np.int64).sum())
+
+    def compact(self, keep: np.ndarray):
+        """keep only rows `keep` (ascending, the live ones), renumbered 0 .. len(keep): df, N and sum(dl) are
+        unchanged (the dropped rows were already subtracted); the CSR is rebuilt by the next search"""
+        keep = np.asarray(keep, np.int64)
+        P = self.n_postings
+        off = self._off_host
+        term = self._fwd_term[:P].cpu().numpy()
+        tf = self._fwd_tf[:P].cpu().numpy()
+        lens = off[keep + 1] - off[keep]
+        new_off = np.zeros(keep.size + 1, np.int64)
+        np.cumsum(lens, out=new_off[1:])
+        src = (np.repeat(off[keep] - new_off[:-1], lens) + np.arange(int(new_off[-1]), dtype=np.int64))
+        self._off_host = new_off
+        self._dl_host = self._dl_host[keep]
+        self.n = int(keep.size)
+        self._fwd_off[: self.n + 1].copy_(torch.from_numpy(new_off))
+        if src.size:
+            self._fwd_term[: src.size].copy_(torch.from_numpy(term[src]))
+            self._fwd_tf[: src.size].copy_(torch.from_numpy(tf[src]))
+        if self.n:
+            self._dl[: self.n].copy_(torch.from_numpy(self._dl_host))
+        self._csr_n = -1
+
+    def _ensure_csr(self):
+        V, n, P = self.n_terms, self.n, self.n_postings
+        if self._csr is not None and self._csr_n == n and self._csr_terms == V:
+            return self._csr
+        L = _native.lib()
+        term_off = torch.empty(V + 1, dtype=torch.int64, device=self.device)
+        post_row = torch.empty(max(P, 1), dtype=torch.int32, device=self.device)
+        post_tf = torch.empty(max(P, 1), dtype=torch.int32, device=self.device)
+        need = int(L.mmrag_lexical_csr_build_workspace_bytes(n, V))
+        if self._csr_ws is None or self._csr_ws.numel() < need:
+            self._csr_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _native._check(L.mmrag_lexical_csr_build(self._fwd_off.data_ptr(), self._fwd_term.data_ptr(),
+                                                     self._fwd_tf.data_ptr(), n, P, V, term_off.data_ptr(),
+                                                     post_row.data_ptr(), post_tf.data_ptr(), self._csr_ws.data_ptr(),
+                                                     self._csr_ws.numel(), self._stream()), "mmrag_lexical_csr_build")
+        self._csr, self._csr_n, self._csr_terms = (term_off, post_row, post_tf), n, V
+        self.csr_builds += 1
+        return self._csr
+
+    def analyze_queries(self, query_texts: Sequence[str]):
+        """(q_off int32 [B+1], q_terms int32) on the host: each query's distinct known terms, first occurrence first"""
+        off, ids, _, _ = self.lexicon.analyze_batch(list(query_texts), LEX_QUERIES)
+        return off.astype(np.int32), ids
+
+    def topk(self, query_texts: Sequence[str], k: int, alive_bits: Optional[torch.Tensor] = None,
+             k1: Optional[float] = None, b: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(scores [B, k] float32 desc, rows [B, k] int64; (-inf, -1) padding) on the device"""
+        if len(query_texts) == 0:
+            raise ValueError("no query texts")
+        if not 1 <= k <= _native.MAX_K_DEEP:
+            raise ValueError(f"n_results must be in 1..{_native.MAX_K_DEEP} for lexical search")
+        q_off, q_terms = self.analyze_queries(query_texts)
+        return self.topk_ids(q_off, q_terms, k, alive_bits, k1, b)
+
+    def topk_ids(self, q_off: np.ndarray, q_terms: np.ndarray, k: int, alive_bits: Optional[torch.Tensor] = None,
+                 k1: Optional[float] = None, b: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """topk over already analysed queries: query i's distinct term ids q_terms[q_off[i] .. q_off[i+1])"""
+        from .config import settings
+
+        k1 = settings.MMRAG_BM25_K1 if k1 is None else k1
+        b = settings.MMRAG_BM25_B if b is None else b
+        B = int(q_off.size) - 1
+        q_off = np.ascontiguousarray(q_off, np.int32)
+        q_terms = np.ascontiguousarray(q_terms, np.int32)
+        if q_terms.size and (q_terms.min() < 0 or q_terms.max() >= self.n_terms):
+            raise ValueError("query term id outside the lexicon")
+        term_off, post_row, post_tf = self._ensure_csr()
+        dq_off = torch.from_numpy(q_off).to(self.device)
+        dq_terms = torch.from_numpy(np.concatenate([q_terms, np.zeros(1, np.int32)])).to(self.device)
+        L = _native.lib()
+        need = int(L.mmrag_bm25_topk_workspace_bytes(B, self.n, k))
+        if self._search_ws is None or self._search_ws.numel() < need:
+            self._search_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        out_s = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        out_r = torch.empty((B, k), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _native._check(L.mmrag_bm25_topk(term_off.data_ptr(), post_row.data_ptr(), post_tf.data_ptr(),
+                                             self._dl.data_ptr(), self._df.data_ptr(), self.n_terms, self.n,
+                                             dq_off.data_ptr(), dq_terms.data_ptr(), B, self.n_live, self.sum_dl,
+                                             float(k1), float(b), k,
+                                             alive_bits.data_ptr() if alive_bits is not None else None,
+                                             out_s.data_ptr(), out_r.data_ptr(), self._search_ws.data_ptr(),
+                                             self._search_ws.numel(), self._stream()), "mmrag_bm25_topk")
+        return out_s, out_r
+
+    def df_host(self) -> np.ndarray:
+        """live df per term (tests)"""
+        return self._df[: self.n_terms].cpu().numpy()
+
+
+def rows_dot(q: torch.Tensor, corpus: torch.Tensor, d: int, qi: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+    """out[i] = <q[qi[i]], corpus[rows[i]]> over the first d columns, float32 (mmrag_rows_dot)"""
+    _native._dev_check(q, corpus, qi, rows)
+    qi = qi.to(torch.int32).contiguous()
+    rows = rows.to(torch.int64).contiguous()
+    out = torch.empty(rows.numel(), dtype=torch.float32, device=corpus.device)
+    with torch.cuda.device(corpus.device):
+        _native._check(_native.lib().mmrag_rows_dot(q.data_ptr(), corpus.data_ptr(), corpus.shape[1],
+                                                    _native._TORCH2DT[corpus.dtype], d, qi.data_ptr(), rows.data_ptr(),
+                                                    rows.numel(), out.data_ptr(), _native._stream_ptr(corpus.device)),
+                       "mmrag_rows_dot")
+    return out
+
+
+def bm25_workspace_bytes(B: int, n: int, k: int) -> int:
+    return int(_native.lib().mmrag_bm25_topk_workspace_bytes(B, n, k))
+
+
+def csr_build_workspace_bytes(n: int, n_terms: int) -> int:
+    return int(_native.lib().mmrag_lexical_csr_build_workspace_bytes(n, n_terms))
+
+
+def declare(lib):
+    """ctypes signatures of the lexical entry points (called from _native._declare)"""
+    lib.mmrag_lexicon_create.restype = c_void_p
+    lib.mmrag_lexicon_create.argtypes = []
+    lib.mmrag_lexicon_destroy.restype = None
+    lib.mmrag_lexicon_destroy.argtypes = [c_void_p]
+    lib.mmrag_lexicon_size.restype = c_int64
+    lib.mmrag_lexicon_size.argtypes = [c_void_p]
+    lib.mmrag_lexicon_analyze_batch.restype = c_int
+    lib.mmrag_lexicon_analyze_batch.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_int64, c_int]
+    lib.mmrag_lexical_df_update.restype = c_int
+    lib.mmrag_lexical_df_update.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]
+    lib.mmrag_lexical_csr_build_workspace_bytes.restype = c_size_t
+    lib.mmrag_lexical_csr_build_workspace_bytes.argtypes = [c_int64, c_int]
+    lib.mmrag_lexical_csr_build.restype = c_int
+    lib.mmrag_lexical_csr_build.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.mmrag_bm25_topk_workspace_bytes.restype = c_size_t
+    lib.mmrag_bm25_topk_workspace_bytes.argtypes = [c_int, c_int64, c_int]
+    lib.mmrag_bm25_topk.restype = c_int
+    lib.mmrag_bm25_topk.argtypes = [c_void_p] * 5 + [c_int, c_int64, c_void_p, c_void_p, c_int, c_int64, c_int64,
+                                                     c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                     c_size_t, c_void_p]
+    lib.mmrag_rows_dot.restype = c_int
+    lib.mmrag_rows_dot.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p,
+                                   c_void_p]

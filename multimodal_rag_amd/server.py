@@ -36,6 +36,10 @@ class QueryRequest(BaseModel):  # api.py:161-164
     # not in the reference: re-score max(top_k, MMRAG_RERANK_CANDIDATES) hits with the cross-encoder of
     # MMRAG_RERANKER_DIR and answer from the best top_k (each source then carries its `rerank_score`)
     rerank: bool = Field(False)
+    # not in the reference: candidates from dense + BM25 retrieval fused by reciprocal rank (EmbeddingManager
+    # .hybrid_query); each source then carries its `hybrid_score`.  With `rerank`, max(top_k, MMRAG_RERANK_CANDIDATES)
+    # hybrid hits are re-ranked
+    hybrid: bool = Field(False)
 
 
 class QueryResponse(BaseModel):  # api.py:167-170
@@ -122,15 +126,21 @@ class Pipeline:
         return {"doc_id": doc_id, "filename": filename, "doc_type": tree.get("doc_type", "unknown"),
                 "chunks_processed": stored}
 
-    async def answer(self, question: str, top_k: int, multimodal: bool, rerank: bool = False) -> Optional[dict]:
+    async def answer(self, question: str, top_k: int, multimodal: bool, rerank: bool = False,
+                     hybrid: bool = False) -> Optional[dict]:
         """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
-        max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the cross-encoder's best top_k"""
+        max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the cross-encoder's best top_k.  `hybrid`: the hits come from
+        dense + BM25 retrieval fused by reciprocal rank"""
+        search = self.embedder.hybrid_query if hybrid else self.embedder.query
         if rerank:
-            hits = await self.embedder.query(question, n_results=max(top_k, settings.MMRAG_RERANK_CANDIDATES))
+            hits = await search(question, n_results=max(top_k, settings.MMRAG_RERANK_CANDIDATES))
             if hits["ids"]:
+                fused = dict(zip(hits["ids"], hits["hybrid_scores"])) if hybrid else None
                 hits = await self.embedder.rerank_results(question, hits, top_k=top_k)
+                if hybrid:
+                    hits["hybrid_scores"] = [fused[found] for found in hits["ids"]]
         else:
-            hits = await self.embedder.query(question, n_results=top_k)
+            hits = await search(question, n_results=top_k)
         if not hits["ids"]:
             return None
         raw = await self.retriever.retrieve_raw_documents(hits["ids"])
@@ -150,6 +160,9 @@ class Pipeline:
         if rerank:
             for src, score in zip(ranked, hits["rerank_scores"]):
                 src["rerank_score"] = score
+        if hybrid:
+            for src, score in zip(ranked, hits["hybrid_scores"]):
+                src["hybrid_score"] = score
         return {"answer": text, "sources": ranked}
 
     async def health(self) -> dict:
@@ -238,7 +251,15 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
         if request.rerank and not (hasattr(pipe.embedder, "has_reranker") and pipe.embedder.has_reranker()):
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="Re-ranking is not configured: set MMRAG_RERANKER_DIR to a local cross-encoder")
-        if request.rerank:
+        if request.hybrid and not (hasattr(pipe.embedder, "hybrid_query")
+                                   and getattr(pipe.embedder, "supports_hybrid", lambda: True)()):
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                detail="Hybrid retrieval is not available with this embedder: it needs a single-GPU "
+                                       "collection with lexical search (EmbeddingManager.hybrid_query)")
+        if request.hybrid:
+            out = await pipe.answer(request.query, request.top_k, request.use_multimodal, rerank=request.rerank,
+                                    hybrid=True)
+        elif request.rerank:
             out = await pipe.answer(request.query, request.top_k, request.use_multimodal, rerank=True)
         else:
             out = await pipe.answer(request.query, request.top_k, request.use_multimodal)

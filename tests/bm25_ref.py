@@ -1,0 +1,131 @@
+"""float64 NumPy restatement of the lexical leg's contract (multimodal_rag_amd/lexical.py, include/mmrag.h): the
+analyzer (via unicodedata), BM25 over the live rows, the top-k order and reciprocal-rank fusion.  Independent of the
+package so the device path is checked against a second statement of the rules."""
+import math
+import unicodedata
+
+import numpy as np
+
+
+def _punct(ch):
+    cp = ord(ch)
+    return (33 <= cp <= 47) or (58 <= cp <= 64) or (91 <= cp <= 96) or (123 <= cp <= 126) or \
+        unicodedata.category(ch).startswith("P")
+
+
+def _cjk(cp):
+    return any(lo <= cp <= hi for lo, hi in ((0x4E00, 0x9FFF), (0x3400, 0x4DBF), (0x20000, 0x2A6DF),
+                                               (0x2A700, 0x2B73F), (0x2B740, 0x2B81F), (0x2B820, 0x2CEAF),
+                                               (0xF900, 0xFAFF), (0x2F800, 0x2FA1F)))
+
+
+def analyze(text):
+    """BERT cleaning + CJK spacing + whitespace split; per word lower() then NFD (marks kept); punctuation splits and
+    is dropped"""
+    if text is None:
+        return []
+    spaced = []
+    for ch in text:
+        cat = unicodedata.category(ch)
+        if ord(ch) in (0, 0xFFFD) or (cat in ("Cc", "Cf") and ch not in "\t\n\r"):
+            continue
+        spaced.append(f" {ch} " if _cjk(ord(ch)) else (" " if ch in " \t\n\r" or cat == "Zs" else ch))
+    terms = []
+    for word in "".join(spaced).split():
+        norm = unicodedata.normalize("NFD", word.lower())
+        terms.extend(t for t in "".join(" " if _punct(c) else c for c in norm).split(" ") if t)
+    return terms
+
+
+class RefIndex:
+    """rows as (term id -> tf) postings; scores in float64"""
+
+    def __init__(self, off, ids, tfs, dl):
+        self.off, self.ids, self.tfs = np.asarray(off, np.int64), np.asarray(ids, np.int64), np.asarray(tfs, np.int64)
+        self.dl = np.asarray(dl, np.int64)
+        self.n = self.dl.size
+        rows = np.repeat(np.arange(self.n), np.diff(self.off))
+        order = np.argsort(self.ids, kind="stable")
+        self.t_sorted, self.p_rows, self.p_tf = self.ids[order], rows[order], self.tfs[order]
+
+    @classmethod
+    def from_texts(cls, docs, vocab=None):
+        vocab = {} if vocab is None else vocab
+        off, ids, tfs, dl = [0], [], [], []
+        for d in docs:
+            terms = analyze(d)
+            dl.append(len(terms))
+            counts = {}
+            for t in terms:
+                tid = vocab.setdefault(t, len(vocab))
+                counts[tid] = counts.get(tid, 0) + 1
+            for tid in sorted(counts):
+                ids.append(tid)
+                tfs.append(counts[tid])
+            off.append(len(ids))
+        ref = cls(off, ids, tfs, dl)
+        ref.vocab = vocab
+        return ref
+
+    def query_ids(self, text):
+        seen = []
+        for t in analyze(text):
+            tid = self.vocab.get(t)
+            if tid is not None and tid not in seen:
+                seen.append(tid)
+        return seen
+
+    def scores(self, q_ids, live, k1=1.2, b=0.75):
+        """(score [n] float64, matched [n] bool) with N, avgdl and df over `live` rows"""
+        live = np.asarray(live, bool)
+        N = int(live.sum())
+        avgdl = self.dl[live].sum() / N if N and self.dl[live].sum() else 1.0
+        acc = np.zeros(self.n)
+        matched = np.zeros(self.n, bool)
+        for t in q_ids:
+            lo, hi = np.searchsorted(self.t_sorted, [t, t + 1])
+            rows, tf = self.p_rows[lo:hi], self.p_tf[lo:hi].astype(np.float64)
+            df = int(live[rows].sum())
+            idf = math.log(1.0 + (N - df + 0.5) / (df + 0.5))
+            acc[rows] += idf * tf * (k1 + 1) / (tf + k1 * (1 - b + b * self.dl[rows] / avgdl))
+            matched[rows] = True
+        return acc, matched
+
+
+def topk(acc, matched, allowed, k):
+    """rows (score desc, ties to the lower row) among matched & allowed, at most k"""
+    cand = np.nonzero(matched & np.asarray(allowed, bool))[0]
+    order = np.lexsort((cand, -acc[cand]))[:k]
+    return cand[order]
+
+
+def assert_topk(got_s, got_r, acc, matched, allowed, k, rtol=1e-5):
+    """device top-k vs the reference: same length, every returned row's reference score equals its reported score,
+    and the score sequence equals the reference's top-k sequence (rows may differ only across exact-score ties)"""
+    got_s, got_r = np.asarray(got_s), np.asarray(got_r)
+    want = topk(acc, matched, allowed, k)
+    hit = got_r >= 0
+    assert int(hit.sum()) == want.size, (int(hit.sum()), want.size)
+    assert np.all(got_r[: want.size] >= 0) and np.all(got_r[want.size:] == -1)
+    assert np.all(np.isneginf(got_s[want.size:]))
+    gs, gr = got_s[: want.size].astype(np.float64), got_r[: want.size]
+    assert np.all(matched[gr]) and np.all(np.asarray(allowed, bool)[gr])
+    assert len(set(gr.tolist())) == gr.size
+    np.testing.assert_allclose(gs, acc[gr], rtol=rtol, atol=0)
+    np.testing.assert_allclose(gs, acc[want], rtol=rtol, atol=0)
+    same = gr == want
+    for i in np.nonzero(~same)[0]:   # a different row only where the two scores tie
+        assert abs(acc[gr[i]] - acc[want[i]]) <= rtol * abs(acc[want[i]]), i
+
+
+def rrf(dense_rows, lexical_rows, k=60):
+    ranks = {}
+    for leg, rows in enumerate((dense_rows, lexical_rows)):
+        for i, r in enumerate(rows):
+            ranks.setdefault(int(r), [None, None])[leg] = i + 1
+    scored = []
+    for r, (rd, rl) in ranks.items():
+        s = (1.0 / (k + rd) if rd else 0.0) + (1.0 / (k + rl) if rl else 0.0)
+        scored.append((-s, rd if rd else len(dense_rows) + 1, r, s))
+    scored.sort()
+    return [(r, s) for _, _, r, s in scored]
