@@ -143,6 +143,15 @@ def _declare(lib):
     lib.mmrag_internal_pool_norm_f32.restype = c_int
     lib.mmrag_internal_pool_norm_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                                  c_void_p]
+    # test-only entry points of the CLIP towers' own kernels (csrc/encoder.hip, not in include/mmrag.h)
+    lib.mmrag_internal_patchify.restype = c_int
+    lib.mmrag_internal_patchify.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]
+    lib.mmrag_internal_vit_assemble_ln.restype = c_int
+    lib.mmrag_internal_vit_assemble_ln.argtypes = [c_void_p] * 6 + [c_int, c_int, c_int, c_float, c_void_p]
+    lib.mmrag_internal_normalize_rows.restype = c_int
+    lib.mmrag_internal_normalize_rows.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p]
+    lib.mmrag_internal_pool_f16.restype = c_int
+    lib.mmrag_internal_pool_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
     # cross-encoder (include/mmrag.h) and its test-only exports
     lib.mmrag_cross_encoder_workspace_bytes.restype = c_size_t
     lib.mmrag_cross_encoder_workspace_bytes.argtypes = [c_void_p, c_int64, c_int]
@@ -742,6 +751,71 @@ def vit_forward(desc: EncoderDesc, weight_ptrs, pixels: torch.Tensor, pixel_kind
                                      cu_seqlens.data_ptr(), B, out.data_ptr(), workspace.data_ptr(),
                                      workspace.numel() * workspace.element_size(), _stream_ptr(pixels.device))
     _check(st, "mmrag_vit_forward")
+    return out
+
+
+def patchify(pixels: torch.Tensor, image: int, patch: int) -> torch.Tensor:
+    """(tests) the vision tower's patchify kernel on its own: uint8 [B, image, image, 3] (CLIP normalisation fused) or
+    fp16 [B, 3, image, image] -> fp16 [B, (image/patch)^2, 3 * patch * patch], patch vector order (c, ph, pw)"""
+    _dev_check(pixels)
+    kind = PIXELS_U8_HWC if pixels.dtype == torch.uint8 else PIXELS_F16_CHW
+    want = (image, image, 3) if kind == PIXELS_U8_HWC else (3, image, image)
+    if pixels.dtype not in (torch.uint8, torch.float16) or tuple(pixels.shape[1:]) != want or not pixels.is_contiguous():
+        raise MMRagNativeError(f"patchify: bad pixel tensor {tuple(pixels.shape)} {pixels.dtype}")
+    if patch <= 0 or image % patch != 0:
+        raise MMRagNativeError(f"patchify: bad image/patch {image}/{patch}")
+    B, G = pixels.shape[0], image // patch
+    out = torch.empty((B, G * G, 3 * patch * patch), dtype=torch.float16, device=pixels.device)
+    with torch.cuda.device(pixels.device):
+        st = lib().mmrag_internal_patchify(pixels.data_ptr(), kind, out.data_ptr(), B, image, patch,
+                                           _stream_ptr(pixels.device))
+    _check(st, "mmrag_internal_patchify")
+    return out
+
+
+def vit_assemble_ln(emb: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                    eps: float) -> torch.Tensor:
+    """(tests) the vision tower's embedding kernel on its own: emb fp16 [B, S - 1, H], cls fp16 [H], pos fp16 [S, H]
+    -> LN(concat(cls, emb[b]) + pos) as fp16 [B * S, H]"""
+    _dev_check(emb, cls, pos, gamma, beta)
+    B, S, H = emb.shape[0], pos.shape[0], pos.shape[1]
+    if tuple(emb.shape) != (B, S - 1, H) or cls.numel() != H or gamma.numel() != H or beta.numel() != H:
+        raise MMRagNativeError("vit_assemble_ln: emb [B, S-1, H], cls [H], pos [S, H], gamma / beta [H]")
+    if any(t.dtype != torch.float16 or not t.is_contiguous() for t in (emb, cls, pos)):
+        raise MMRagNativeError("vit_assemble_ln: emb, cls, pos must be contiguous fp16")
+    out = torch.empty((B * S, H), dtype=torch.float16, device=emb.device)
+    with torch.cuda.device(emb.device):
+        st = lib().mmrag_internal_vit_assemble_ln(emb.data_ptr(), cls.data_ptr(), pos.data_ptr(), gamma.data_ptr(),
+                                                  beta.data_ptr(), out.data_ptr(), B, S, H, eps,
+                                                  _stream_ptr(emb.device))
+    _check(st, "mmrag_internal_vit_assemble_ln")
+    return out
+
+
+def normalize_rows(x: torch.Tensor) -> torch.Tensor:
+    """(tests) the pre-LN head's last kernel on its own: fp16 [B, D] -> x / max(||x||, 1e-12) as float32"""
+    _dev_check(x)
+    if x.dtype != torch.float16 or x.dim() != 2 or not x.is_contiguous():
+        raise MMRagNativeError("normalize_rows: x must be contiguous fp16 [B, D]")
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        st = lib().mmrag_internal_normalize_rows(x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1],
+                                                 _stream_ptr(x.device))
+    _check(st, "mmrag_internal_normalize_rows")
+    return out
+
+
+def pool_f16(x: torch.Tensor, cu_seqlens: torch.Tensor, pool: int, sel: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(tests) the pre-LN head's pooling on its own: the fp16-out pooling kernel without normalisation -> fp16 [B, H]"""
+    _dev_check(x, cu_seqlens, sel)
+    if x.dtype != torch.float16 or x.dim() != 2 or not x.is_contiguous():
+        raise MMRagNativeError("pool_f16: x must be contiguous fp16 [T, H]")
+    B, H = cu_seqlens.numel() - 1, x.shape[1]
+    out = torch.empty((B, H), dtype=torch.float16, device=x.device)
+    with torch.cuda.device(x.device):
+        st = lib().mmrag_internal_pool_f16(x.data_ptr(), cu_seqlens.data_ptr(), _ptr(sel), out.data_ptr(), B, H, pool,
+                                           _stream_ptr(x.device))
+    _check(st, "mmrag_internal_pool_f16")
     return out
 
 

@@ -1830,6 +1830,59 @@ int mmrag_vit_forward(const mmrag_encoder_desc *d, const void *const *w, const v
 }
 
 // ---------------------------------------------------------------------------------------------
+// (tests only, not in mmrag.h) the kernels of the CLIP towers that have no entry point of their own, launched as
+// mmrag_vit_forward / encoder_body launch them
+// ---------------------------------------------------------------------------------------------
+int mmrag_internal_patchify(const void *pixels, int kind, void *patches, int B, int image, int patch, void *stream) {
+    MMRAG_CHECK_ARG(pixels && patches, "patchify: null pointer");
+    MMRAG_CHECK_ARG(kind == MMRAG_PIXELS_F16_CHW || kind == MMRAG_PIXELS_U8_HWC, "patchify: bad pixel kind %d", kind);
+    MMRAG_CHECK_ARG(B > 0 && patch > 0 && image > 0 && image % patch == 0 && patch % 8 == 0,
+                    "patchify: bad shape B=%d image/patch %d/%d", B, image, patch);
+    MMRAG_CHECK_ARG(((uintptr_t)pixels % 16) == 0 && ((uintptr_t)patches % 16) == 0, "patchify: pointers must be 16-byte aligned");
+    const int G = image / patch;
+    const long long chunks = (long long)B * G * G * (3 * patch * patch / 8);
+    MMRAG_CHECK_ARG((chunks + 255) / 256 < INT_MAX, "patchify: batch too large B=%d", B);
+    patchify_kernel<<<(unsigned)((chunks + 255) / 256), 256, 0, (hipStream_t)stream>>>(pixels, kind, (_Float16 *)patches, B,
+                                                                                      image, patch);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    return MMRAG_OK;
+}
+
+int mmrag_internal_vit_assemble_ln(const void *emb, const void *cls, const void *pos, const float *gamma,
+                                   const float *beta, void *out, int B, int S, int H, float eps, void *stream) {
+    MMRAG_CHECK_ARG(emb && cls && pos && gamma && beta && out, "vit_assemble_ln: null pointer");
+    MMRAG_CHECK_ARG(B > 0 && S >= 2 && (int64_t)B * S < INT_MAX && H > 0 && H % 8 == 0 && H <= 1024,
+                    "vit_assemble_ln: bad shape B=%d S=%d H=%d (H a multiple of 8, <= 1024)", B, S, H);
+    MMRAG_CHECK_ARG(((uintptr_t)emb % 16) == 0 && ((uintptr_t)cls % 16) == 0 && ((uintptr_t)pos % 16) == 0 &&
+                        ((uintptr_t)out % 16) == 0 && ((uintptr_t)gamma % 16) == 0 && ((uintptr_t)beta % 16) == 0,
+                    "vit_assemble_ln: pointers must be 16-byte aligned");
+    const int T = B * S;
+    vit_assemble_ln_kernel<<<(unsigned)((T + 3) / 4), 256, 0, (hipStream_t)stream>>>(
+        (const _Float16 *)emb, (const _Float16 *)cls, (const _Float16 *)pos, gamma, beta, (_Float16 *)out, T, H, S, eps);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    return MMRAG_OK;
+}
+
+int mmrag_internal_normalize_rows(const void *x, float *out, int B, int D, void *stream) {
+    MMRAG_CHECK_ARG(x && out, "normalize_rows: null pointer");
+    MMRAG_CHECK_ARG(B > 0 && D > 0, "normalize_rows: bad shape B=%d D=%d", B, D);
+    normalize_rows_kernel<<<(unsigned)((B + 3) / 4), 256, 0, (hipStream_t)stream>>>((const _Float16 *)x, out, B, D);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    return MMRAG_OK;
+}
+
+int mmrag_internal_pool_f16(const void *x, const int32_t *cu_seqlens, const int32_t *sel, void *out_f16, int B, int H,
+                            int pool, void *stream) {
+    MMRAG_CHECK_ARG(x && cu_seqlens && out_f16, "pool_f16: null pointer");
+    MMRAG_CHECK_ARG(B > 0 && H > 0 && H <= 1024, "pool_f16: bad shape B=%d H=%d", B, H);
+    MMRAG_CHECK_ARG(pool >= 0 && pool <= 2 && (pool != 2 || sel), "pool_f16: bad mode %d", pool);
+    pool_norm_kernel<_Float16><<<(unsigned)B, 256, 0, (hipStream_t)stream>>>((const _Float16 *)x, cu_seqlens, sel,
+                                                                            (_Float16 *)out_f16, H, pool, 0);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    return MMRAG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // cross-encoder (sequence-pair classifier): embed with segment ids, the unchanged encoder body pooled at [CLS] without
 // normalisation into a float32 workspace buffer, then the classification head (cross_head.hip)
 // ---------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 from oracle import clip_oracle as C  # noqa: E402
+from tests import clip_ref as R  # noqa: E402
 
 
 def hf_clip(s, w):
@@ -61,5 +62,7 @@ def one(name, s, seed, lens, n_img):
 
 
 if __name__ == "__main__":
-    one("tiny", C.TINY_CLIP, 21, [4, 17, 32, 9], 3)
-    one("vitb32", C.VIT_B32, 22, [8, 77, 30], 2)
+    cases = {"tiny": (C.TINY_CLIP, 21, [4, 17, 32, 9], 3), "vitb32": (C.VIT_B32, 22, [8, 77, 30], 2),
+             "vitb16": (R.VITB16_2L, 23, [8, 20], 1)}     # 197 tokens per image, two layers
+    for name in sys.argv[1:] or list(cases):
+        one(name, *cases[name])

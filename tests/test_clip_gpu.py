@@ -41,6 +41,9 @@ def test_preprocess_and_patchify_shapes():
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["tiny", "vitb32"])
 def test_clip_towers_on_gpu(golden_dir, name):
+    """The goldens' own sequences and tiles against the float32 oracle.  Its 5e-3 / 0.9999 is a coarse net (5-10 % of a
+    typical entry); the deciding bounds are the e_store-relative ones of the tower tests below and the per-kernel ones
+    of tests/test_clip_ops_gpu.py"""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     from multimodal_rag_amd.clip import ClipConfig, DeviceClip
@@ -97,3 +100,300 @@ def test_joint_space_index(golden_dir):
     assert O.same_topk_sets(np.array([[idx._row_of[i] for i in r] for r in res["ids"]]), 1 - np.array(res["distances"]), er, es)
     only_text = idx.query(ie[:3], n_results=5, where={"type": "text"})
     assert all(i.split("_")[2] == "text" for r in only_text["ids"] for i in r)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The towers at the shapes the product takes, against tests/clip_ref.py (float64) on the same fp16-rounded weights.
+#
+# The deciding bound: the float64 reference runs twice, as it is and with every activation the device stores as fp16
+# rounded to fp16 at that point (clip_ref, `store=True`); e_store / (1 - cos_store) is the largest elementwise / cosine
+# distance between the two over all cases of a shape.  The device may be TOWER_K / TOWER_KC times as far from the
+# float64 reference as fp16 storage alone puts it:
+#       max |gpu - ref| <= TOWER_K * e_store          max (1 - cos(gpu, ref)) <= TOWER_KC * (1 - cos_store)
+# e_store is about 2.5e-4 on these unit vectors (entries 0.04-0.12), a twentieth of test_clip_towers_on_gpu's 5e-3.
+# Worst observed ratios on the MI355X (err / e_store, (1 - cos) / (1 - cos_store)); the constants are twice the worst:
+#       TINY_CLIP vision 1.00 / 1.36    ViT-B/32 vision 1.06 / 1.04    patch 16, 197 tokens (2 layers) vision 0.93 / 1.02
+#       TINY_CLIP text   0.93 / 1.16    ViT-B/32 text   1.05 / 0.96
+# ---------------------------------------------------------------------------------------------------------------------
+import functools  # noqa: E402
+
+from tests import clip_ref as R  # noqa: E402
+
+TOWER_K = 2.2
+TOWER_KC = 2.8
+
+TOWER_SHAPES = {"tiny": C.TINY_CLIP, "vitb32": C.VIT_B32, "vitb16_2l": R.VITB16_2L}
+TOWER_SEED = 41
+N_IMAGES = {"tiny": 64, "vitb32": 64, "vitb16_2l": 16}
+TEXT_SINGLE_LENS = [2, 9, 64, 65, 77]
+
+
+def clip_config(s):
+    from multimodal_rag_amd.clip import ClipConfig
+
+    return ClipConfig(s.t_layers, s.t_hidden, s.t_heads, s.t_inter, s.vocab, s.t_max_pos, s.eos_id, s.v_layers,
+                      s.v_hidden, s.v_heads, s.v_inter, s.image, s.patch, s.proj, s.ln_eps)
+
+
+@functools.lru_cache(maxsize=None)
+def tower_weights(name):
+    return C.make_clip_weights(TOWER_SHAPES[name], TOWER_SEED)
+
+
+@functools.lru_cache(maxsize=None)
+def device_clip(name):
+    from multimodal_rag_amd.clip import DeviceClip
+
+    return DeviceClip(clip_config(TOWER_SHAPES[name]), tower_weights(name), "cuda:0")
+
+
+def make_sequence(s, g, n, eos=True, bos=True):
+    """BOS, n - 2 ordinary tokens, EOS.  Without EOS the pooled token is the arg-max id; BOS is the largest id after
+    EOS and sees only itself under the causal mask, so `bos=False` puts the arg-max somewhere inside the sequence"""
+    body = g.integers(1, s.eos_id - 1, n).tolist()
+    if bos:
+        body[0] = s.eos_id - 1
+    if eos:
+        body[-1] = s.eos_id
+    return body
+
+
+@functools.lru_cache(maxsize=None)
+def text_cases(name):
+    """the first len(TEXT_SINGLE_LENS) sequences are the single-sequence cases, then one without EOS, one longer than
+    t_max_pos with its EOS cut off, then 256 of mixed lengths (eight of t_max_pos, four without EOS, four too long)"""
+    s = TOWER_SHAPES[name]
+    g = np.random.default_rng(7)
+    seqs = [make_sequence(s, g, n) for n in TEXT_SINGLE_LENS]
+    seqs += [make_sequence(s, g, 11, eos=False, bos=False), make_sequence(s, g, s.t_max_pos + 9, bos=False)]
+    lens = g.integers(2, s.t_max_pos + 1, 256)
+    lens[:8] = s.t_max_pos
+    lens[8:12] = s.t_max_pos + np.array([1, 2, 20, 50])
+    batch = [make_sequence(s, g, int(n), eos=not (12 <= i < 16), bos=not (10 <= i < 14)) for i, n in enumerate(lens)]
+    return seqs, batch
+
+
+@functools.lru_cache(maxsize=None)
+def text_reference(name):
+    s = TOWER_SHAPES[name]
+    w = R.widen(C.round_weights_fp16(tower_weights(name)), "text")
+    singles, batch = text_cases(name)
+    plain, stored = (R.text_embed(s, w, singles + batch, store=st) for st in (False, True))
+    return plain, R.store_error(plain, stored)
+
+
+@functools.lru_cache(maxsize=None)
+def image_cases(name):
+    s = TOWER_SHAPES[name]
+    tiles = np.random.default_rng(11).integers(0, 256, (N_IMAGES[name], s.image, s.image, 3), dtype=np.uint8)
+    return tiles, C.preprocess_tiles(tiles).astype(np.float16)
+
+
+@functools.lru_cache(maxsize=None)
+def image_reference(name):
+    s = TOWER_SHAPES[name]
+    w = R.widen(C.round_weights_fp16(tower_weights(name)), "vision")
+    px = image_cases(name)[1].astype(np.float64)
+    plain, stored = (R.image_embed(s, w, px, store=st) for st in (False, True))
+    return plain, R.store_error(plain, stored)
+
+
+def check_tower(got, ref, store, record_property, what):
+    e_store, c_store = store
+    got = np.asarray(got, np.float64)
+    assert np.allclose(np.linalg.norm(got, axis=1), 1.0, atol=1e-5)
+    k = float(np.abs(got - ref).max()) / e_store
+    kc = float(R.one_minus_cos(got, ref).max()) / c_store
+    record_property(what, "err/e_store %.3f  (1-cos)/(1-cos_store) %.3f  e_store %.3g" % (k, kc, e_store))
+    print("TOWER_RATIO", what, "%.3f %.3f %.3g %.3g" % (k, kc, e_store, c_store))
+    assert k <= TOWER_K and kc <= TOWER_KC, (what, "err / e_store", k, "(1 - cos) / (1 - cos_store)", kc)
+
+
+@pytest.mark.parametrize("name", ["tiny", "vitb32"])
+def test_clip_ref_matches_oracle_and_transformers_golden(golden_dir, name):
+    """tests/clip_ref.py (float64, batched) is the architecture of oracle/clip_oracle.py: same bar as the oracle's own pin"""
+    if name == "vitb32" and os.environ.get("MMRAG_FAST_TESTS"):
+        pytest.skip("fast mode")
+    s = SHAPES[name]
+    z, seqs = load(golden_dir, name)
+    w = C.make_clip_weights(s, int(z["seed"]))
+    t = R.text_embed(s, R.widen(w, "text"), seqs)
+    v = R.image_embed(s, R.widen(w, "vision"), R.normalize_u8(z["tiles"]))
+    assert np.abs(t - z["text"]).max() < 2e-6 and np.abs(t - C.text_embed(s, w, seqs)).max() < 2e-6
+    assert np.abs(v - z["image"]).max() < 2e-6
+    assert np.abs(v - C.image_embed(s, w, C.preprocess_tiles(z["tiles"]))).max() < 2e-6
+
+
+def test_clip_ref_vitb16_matches_transformers_golden(golden_dir):
+    """the 197-token shape (patch 16, G = 14): oracle and float64 reference against transformers.CLIPModel"""
+    s = R.VITB16_2L
+    z, seqs = load(golden_dir, "vitb16")
+    w = C.make_clip_weights(s, int(z["seed"]))
+    px = C.preprocess_tiles(z["tiles"])
+    assert np.abs(C.image_embed(s, w, px) - z["image"]).max() < 2e-6
+    assert np.abs(C.text_embed(s, w, seqs) - z["text"]).max() < 2e-6
+    assert np.abs(R.image_embed(s, R.widen(w, "vision"), R.normalize_u8(z["tiles"])) - z["image"]).max() < 2e-6
+
+
+def test_eos_index_rule_and_truncation():
+    """host-side rules of encode_text_ids, restated by clip_ref: cut to t_max_pos, pool at the FIRST EOS, arg-max of
+    the ids (first occurrence) where the cut sequence holds none"""
+    s = C.TINY_CLIP
+    eos, bos = s.eos_id, s.eos_id - 1
+    assert R.eos_index([bos, 5, eos], eos) == 2
+    assert R.eos_index([bos, 5, eos, 7, eos], eos) == 2
+    assert R.eos_index([bos, 5, 7], eos) == 0                      # no EOS: BOS is the largest id
+    assert R.eos_index([3, 900, 7, 900], eos) == 1
+    long = [bos] + [5] * 40 + [eos]
+    cut = R.cut_sequences(s, [long])[0]
+    assert len(cut) == s.t_max_pos and R.eos_index(cut, eos) == 0
+    # the oracle pools a sequence without EOS at the same token
+    w = C.make_clip_weights(s, 3)
+    seq = [bos, 5, 17, 4]
+    assert np.abs(R.text_embed(s, R.widen(w, "text"), [seq]) - C.text_embed(s, w, [seq])).max() < 2e-6
+    # and a too-long sequence embeds as its first t_max_pos tokens
+    wt = R.widen(w, "text")
+    assert np.array_equal(R.text_embed(s, wt, [long]), R.text_embed(s, wt, [long[:s.t_max_pos]]))
+
+
+def test_store_emulation_is_deterministic_and_small():
+    s = C.TINY_CLIP
+    w = C.round_weights_fp16(C.make_clip_weights(s, 5))
+    g = np.random.default_rng(0)
+    seqs = [make_sequence(s, g, n) for n in (3, 17, 32, 17)]
+    px = C.preprocess_tiles(g.integers(0, 256, (3, s.image, s.image, 3), dtype=np.uint8)).astype(np.float16).astype(np.float64)
+    wt, wv = R.widen(w, "text"), R.widen(w, "vision")
+    for plain, a, b in ((R.text_embed(s, wt, seqs), R.text_embed(s, wt, seqs, store=True), R.text_embed(s, wt, seqs, store=True)),
+                        (R.image_embed(s, wv, px), R.image_embed(s, wv, px, store=True), R.image_embed(s, wv, px, store=True))):
+        assert np.array_equal(a, b)
+        e, c = R.store_error(plain, a)
+        assert 0 < e < 2e-3 and 0 < c < 1e-4, (e, c)
+    # batching does not enter: a sequence alone and inside a batch give the same bits
+    assert np.array_equal(R.text_embed(s, wt, seqs[1:2], store=True)[0], R.text_embed(s, wt, seqs, store=True)[1])
+
+
+def encode_twice(fn, arg):
+    a, b = fn(arg), fn(arg)
+    torch.cuda.synchronize()
+    assert torch.equal(a.view(torch.int32), b.view(torch.int32)), "two launches differ"
+    return a.cpu().numpy()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", [1, 2, 5, 64])
+@pytest.mark.parametrize("name", ["tiny", "vitb32"])
+def test_vision_tower_batches(record_property, name, B):
+    """one image (every GEMM on the single-query kernels), a few, and an ingest batch; uint8 tiles (normalisation fused
+    into patchify) and the same tiles pre-normalised as fp16.  Rows are distinct random images: a permuted batch fails"""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    clip = device_clip(name)
+    tiles, px16 = image_cases(name)
+    ref, store = image_reference(name)
+    got_u8 = encode_twice(clip.encode_images, torch.from_numpy(tiles[:B]).cuda())
+    got_16 = encode_twice(clip.encode_images, torch.from_numpy(px16[:B]).cuda())
+    check_tower(got_u8, ref[:B], store, record_property, f"{name} vision u8 B={B}")
+    check_tower(got_16, ref[:B], store, record_property, f"{name} vision f16 B={B}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", [1, 3, 16])
+def test_vision_tower_patch16(record_property, B):
+    """197 tokens per image: attention_kernel<64, 2, true, 8> (K / V resident), G = 14, 96 chunks per patch row"""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    name = "vitb16_2l"
+    clip = device_clip(name)
+    assert clip.cfg.tokens_per_image == 197
+    tiles, px16 = image_cases(name)
+    ref, store = image_reference(name)
+    check_tower(encode_twice(clip.encode_images, torch.from_numpy(tiles[:B]).cuda()), ref[:B], store, record_property,
+                f"{name} vision u8 B={B}")
+    check_tower(encode_twice(clip.encode_images, torch.from_numpy(px16[:B]).cuda()), ref[:B], store, record_property,
+                f"{name} vision f16 B={B}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["tiny", "vitb32"])
+def test_vision_tower_image_alone_and_inside_a_batch(record_property, name):
+    """image i alone (single-query kernels) and as row i of the batch of 64 (tiled GEMMs, packed attention): both
+    within the bound of the reference's row i"""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    clip = device_clip(name)
+    tiles, _ = image_cases(name)
+    ref, store = image_reference(name)
+    batch = clip.encode_images(torch.from_numpy(tiles).cuda()).cpu().numpy()
+    check_tower(batch, ref, store, record_property, f"{name} vision batch of 64")
+    for i in (0, 17, 63):
+        alone = clip.encode_images(torch.from_numpy(tiles[i:i + 1]).cuda()).cpu().numpy()
+        check_tower(alone, ref[i:i + 1], store, record_property, f"{name} vision image {i} alone")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", list(range(len(TEXT_SINGLE_LENS) + 2)), ids=[f"len{n}" for n in TEXT_SINGLE_LENS] + ["no_eos", "too_long"])
+@pytest.mark.parametrize("name", ["tiny", "vitb32"])
+def test_text_tower_single_sequence(record_property, name, case):
+    """the online /query path of a CLIP collection: T <= 64 on the single-query GEMMs, 65 and 77 on the 64x64 tiles.
+    (TINY_CLIP has 32 positions: its longer cases are cut, which moves the pooled token to the arg-max rule)"""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    clip = device_clip(name)
+    singles, _ = text_cases(name)
+    ref, store = text_reference(name)
+    got = encode_twice(clip.encode_text_ids, [singles[case]])
+    check_tower(got, ref[case:case + 1], store, record_property, f"{name} text case {case} len {len(singles[case])}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["tiny", "vitb32"])
+def test_text_tower_batch_of_256(record_property, name):
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    clip = device_clip(name)
+    singles, batch = text_cases(name)
+    ref, store = text_reference(name)
+    got = encode_twice(clip.encode_text_ids, batch)
+    check_tower(got, ref[len(singles):], store, record_property, f"{name} text batch of 256")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["tiny", "vitb32"])
+def test_workspace_reuse_after_a_large_batch(name):
+    """one workspace per tower, grown by the largest batch: a single image / sequence after 64 images / 256 sequences
+    has the bits a fresh DeviceClip (fresh workspace) gives"""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from multimodal_rag_amd.clip import DeviceClip
+
+    used = device_clip(name)
+    tiles, _ = image_cases(name)
+    singles, batch = text_cases(name)
+    one_tile = torch.from_numpy(tiles[5:6]).cuda()
+    used.encode_images(torch.from_numpy(tiles).cuda())
+    used.encode_text_ids(batch)
+    big_v, big_t = used._ws_v.numel(), used._ws_t.numel()
+    after_v = used.encode_images(one_tile)
+    after_t = used.encode_text_ids([singles[1]])
+    assert used._ws_v.numel() == big_v and used._ws_t.numel() == big_t     # the grown workspace was reused
+    fresh = DeviceClip(clip_config(TOWER_SHAPES[name]), tower_weights(name), "cuda:0")
+    fresh_v = fresh.encode_images(one_tile)
+    fresh_t = fresh.encode_text_ids([singles[1]])
+    assert fresh._ws_v.numel() < big_v and fresh._ws_t.numel() < big_t
+    torch.cuda.synchronize()
+    assert torch.equal(after_v.view(torch.int32), fresh_v.view(torch.int32))
+    assert torch.equal(after_t.view(torch.int32), fresh_t.view(torch.int32))
+
+
+@pytest.mark.gpu
+def test_patch_size_not_a_multiple_of_8_is_rejected():
+    """ViT-L/14-style patches are refused with an error, not run"""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from multimodal_rag_amd import _native
+    from multimodal_rag_amd.clip import DeviceClip
+
+    s = C.ClipShape(1, 128, 4, 256, 1000, 32, 999, 1, 128, 4, 256, 56, 14, 64)
+    clip = DeviceClip(clip_config(s), C.make_clip_weights(s, 1), "cuda:0")
+    with pytest.raises(_native.MMRagNativeError):
+        clip.encode_images(torch.zeros((1, 56, 56, 3), dtype=torch.uint8, device="cuda"))

@@ -353,3 +353,151 @@ def test_single_query_forward_folded_layernorm_large_beta(N, monkeypatch, record
     assert d_passes <= 1e-3, d_passes
     for k, (err, cos) in errs.items():
         assert err <= 4e-3 and cos >= 0.9999, (k, err, cos)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# mmrag_linear_f16 the way the pre-LN (CLIP) body calls it: the residual added in place (resid is out), and no bias at
+# a large K (patch embedding, projections)
+# ---------------------------------------------------------------------------------------------------------------------
+import contextlib  # noqa: E402
+
+
+@contextlib.contextmanager
+def linear_debug(N, flags):
+    import ctypes
+
+    L = N.lib()
+    L.mmrag_internal_set_debug.argtypes = [ctypes.c_uint]
+    L.mmrag_internal_set_debug(flags)
+    try:
+        yield
+    finally:
+        L.mmrag_internal_set_debug(0)
+
+
+# (branch of launch_linear on a 256-CU device, developer switch that forces it or 0, M, K, N); the CLIP shapes: 50 / 77
+# tokens of one image / text, 3200 = 64 images, 12800 = 256 images
+INPLACE_CASES = [
+    ("small16", 0, 50, 768, 768), ("small16", 0, 50, 3072, 768),
+    ("small-splitk16", 0, 50, 256, 512), ("small-splitk8", 0, 50, 640, 512), ("small-splitk4", 0, 50, 448, 512),
+    ("small-splitk16", 256, 50, 768, 768),
+    ("64x64", 0, 77, 512, 512), ("64x64", 0, 77, 2048, 512), ("64x64", 1024, 3200, 768, 768),
+    ("128x128", 0, 3200, 768, 768), ("128x128", 0, 3200, 3072, 768), ("128x128", 0, 12800, 3072, 768),
+    ("128x128", 2048, 77, 512, 512),
+    ("256x256-plain", 1, 12800, 768, 3072), ("256x256-pipelined", 4, 12800, 768, 3072),
+    ("persistent-16x16x32", 0, 12800, 768, 3072), ("persistent-32x32x16", 8192, 12800, 768, 3072),
+]
+
+
+def _bits(t):
+    return t.view(torch.int16)
+
+
+@pytest.mark.parametrize("branch,dbg,M,K,Nf", INPLACE_CASES, ids=[f"{c[0]}-{c[1]}-{c[2]}x{c[3]}x{c[4]}" for c in INPLACE_CASES])
+def test_linear_residual_in_place(N, record_property, branch, dbg, M, K, Nf):
+    """encoder_body's pre-LN branch: mmrag_linear_f16(..., resid = x, out = x).  With and without QuickGELU, on every
+    kernel launch_linear can pick: the in-place result has the bits of the out-of-place result, and that one meets
+    test_linear's bound against float64"""
+    g = np.random.default_rng(M + K + Nf + dbg)
+    x = r16(g.standard_normal((M, K)) * 0.5)
+    w = r16(g.standard_normal((Nf, K)) * 0.05)
+    b = (g.standard_normal(Nf) * 0.1).astype(np.float32)
+    res = r16(g.standard_normal((M, Nf)))
+    z = x.astype(np.float64) @ w.astype(np.float64).T + b
+    xd, wd, bd, rd = dev16(x), dev16(w), dev32(b), dev16(res)
+    for act in (0, 2):
+        y = z if act == 0 else z / (1.0 + np.exp(-1.702 * z))
+        y = y.astype(np.float16).astype(np.float64) + res   # rounded to fp16 before the residual add
+        with linear_debug(N, dbg):
+            apart = N.linear_f16(xd, wd, bd, act, rd)
+            buf = rd.clone()
+            same = N.linear_f16(xd, wd, bd, act, buf, out=buf)
+            torch.cuda.synchronize()
+        assert same.data_ptr() == buf.data_ptr()
+        assert torch.equal(_bits(apart), _bits(buf)), (branch, act, "in-place differs from out-of-place",
+                                                       int((_bits(apart) != _bits(buf)).sum()))
+        err = float(np.abs(apart.float().cpu().numpy() - y).max())
+        lim = 2e-3 * max(1.0, float(np.abs(y).max()))
+        record_property(f"act {act} err / bound", round(err / lim, 3))
+        assert err <= lim, (branch, act, err, lim)
+
+
+def _integer_case(g, M, K, Nf):
+    x = g.integers(-4, 5, (M, K)).astype(np.float32)
+    w = g.integers(-2, 3, (Nf, K)).astype(np.float32)
+    w[:, 0] += np.arange(Nf) % 5
+    x[:, 1] += np.arange(M) % 3
+    return x, w
+
+
+@pytest.mark.parametrize("branch,dbg,M,K,Nf", [
+    ("small16", 0, 50, 768, 768), ("small-splitk4", 0, 50, 448, 512), ("small-splitk16", 256, 50, 768, 768),
+    ("64x64", 0, 77, 512, 512), ("128x128", 0, 3200, 768, 768), ("256x256-plain", 1, 12800, 768, 3072),
+    ("256x256-pipelined", 4, 12800, 768, 3072), ("persistent-16x16x32", 0, 12800, 768, 3072),
+    ("persistent-32x32x16", 8192, 12800, 768, 3072)], ids=lambda v: str(v))
+def test_linear_residual_in_place_exact_integers(N, branch, dbg, M, K, Nf):
+    """integer data (every partial sum exact in fp32, every result an integer below 2048, exact in fp16): the in-place
+    residual add gives x W^T + bias + resid exactly, element by element"""
+    g = np.random.default_rng(K + Nf + dbg)
+    x, w = _integer_case(g, M, K, Nf)
+    bias = (np.arange(Nf) % 4).astype(np.float32)
+    res = g.integers(-8, 9, (M, Nf)).astype(np.float32)
+    want = x.astype(np.float64) @ w.astype(np.float64).T + bias + res
+    assert np.abs(want).max() <= 2048
+    buf = dev16(res)
+    with linear_debug(N, dbg):
+        N.linear_f16(dev16(x), dev16(w), dev32(bias), 0, buf, out=buf)
+        torch.cuda.synchronize()
+    bad = np.argwhere(buf.float().cpu().numpy() != want)
+    assert bad.size == 0, (branch, bad[:5].tolist())
+
+
+NO_BIAS_SHAPES = [(49, 3072, 768), (49 * 64, 3072, 768), (1, 768, 512), (300, 512, 512), (4, 768, 64)]
+
+
+@pytest.mark.parametrize("M,K,Nf", NO_BIAS_SHAPES)
+def test_linear_without_bias(N, record_property, M, K, Nf):
+    """bias = None at the shapes of the ViT patch embedding (K = 3 * 32 * 32, one image and 64) and of the projections:
+    test_linear's bound against float64, and exact on integer data"""
+    g = np.random.default_rng(M + K + Nf)
+    x = r16(g.standard_normal((M, K)) * 0.5)
+    w = r16(g.standard_normal((Nf, K)) * 0.05)
+    y = x.astype(np.float64) @ w.astype(np.float64).T
+    got = N.linear_f16(dev16(x), dev16(w), None).float().cpu().numpy()
+    lim = 2e-3 * max(1.0, float(np.abs(y).max()))
+    record_property("err / bound", round(float(np.abs(got - y).max()) / lim, 3))
+    assert np.abs(got - y).max() <= lim, float(np.abs(got - y).max())
+    x, w = _integer_case(g, M, K, Nf)
+    want = x.astype(np.float64) @ w.astype(np.float64).T
+    assert np.abs(want).max() <= 2048
+    got = N.linear_f16(dev16(x), dev16(w), None).float().cpu().numpy()
+    assert np.array_equal(got, want), np.argwhere(got != want)[:5].tolist()
+
+
+# QuickGELU's own value.  test_linear's 2e-3 cannot tell a slope of 1.702 from 1.70 (2e-4 at |z| ~ 1); here the GEMM is
+# exact (W = I, x and bias multiples of 1/8), so what is left is z / (1 + exp(-1.702 z)) in fp32 and one rounding to fp16:
+#     |got - ref| <= (2^-11 + A_QG * 2^-24) |ref| + 2^-25        (2^-25: half the fp16 subnormal step, z = -8 gives -1e-5)
+# A_QG from the arithmetic: the argument of the device's exp2 reaches 1.702 * 8.5 * log2(e) = 21, formed by two fp32
+# roundings, so exp() is off by up to 21 * 2 * ln 2 = 29 units of 2^-24, plus one unit each for exp2, the add and about
+# three for the fast division: 34, doubled and rounded up to a power of two.  Observed on the MI355X: no element needs any of
+# it (all are within the two fp16 rounding terms); with a slope of 1.70 every case fails (0.8 % off at z = -4).
+A_QG = 64.0
+
+
+@pytest.mark.parametrize("branch,dbg,M,K", [("small16", 0, 50, 768), ("small-splitk16", 256, 50, 768), ("64x64", 0, 77, 512),
+                                            ("128x128", 0, 3200, 768), ("persistent-16x16x32", 0, 22016, 768),
+                                            ("persistent-32x32x16", 8192, 22016, 768)], ids=lambda v: str(v))
+def test_linear_quick_gelu_value(N, record_property, branch, dbg, M, K):
+    g = np.random.default_rng(M + K)
+    x = g.integers(-64, 65, (M, K)).astype(np.float64) / 8.0
+    b = g.integers(-4, 5, K).astype(np.float64) / 8.0
+    z = x + b
+    ref = z / (1.0 + np.exp(-1.702 * z))
+    with linear_debug(N, dbg):
+        got = N.linear_f16(dev16(x), dev16(np.eye(K)), dev32(b), 2).float().cpu().numpy().astype(np.float64)
+    err = np.abs(got - ref)
+    need = (err - 2.0 ** -25 - 2.0 ** -11 * np.abs(ref)) / np.where(ref != 0, 2.0 ** -24 * np.abs(ref), 1.0)
+    i = np.unravel_index(int(np.argmax(need)), need.shape)
+    record_property("worst A", round(float(need[i]), 2))
+    print("QUICKGELU_A", branch, float(need[i]))
+    assert need[i] <= A_QG, (branch, "z", z[i], "got", got[i], "ref", ref[i], "A needed", float(need[i]))
