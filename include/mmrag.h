@@ -318,6 +318,41 @@ int mmrag_bm25_topk(const int64_t *term_off, const int32_t *post_row, const int3
 int mmrag_rows_dot(const void *q, const void *corpus, int64_t ld, int dtype, int d, const int32_t *qi,
                    const int64_t *rows, int64_t m, float *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Diversified retrieval: maximal-marginal-relevance (MMR) selection of k of a query's C dense hits (what LangChain's
+ * max_marginal_relevance_search(k, fetch_k, lambda_mult) does over a Chroma collection).  The reference has no
+ * counterpart: app/utils/embedder.py hands the first top_k hits of collection.query to the generator as they come.
+ * One launch, one workgroup per query, everything in LDS; no atomics on global memory, no host synchronisation (the
+ * call can be captured into a graph).
+ *
+ * Definition, for one query:
+ *   - the candidates c_0 .. c_{C-1} are cand_rows[b, :] in the search's own order (score descending, ties to the lower
+ *     row); rel_i = cand_scores[b, i] exactly as given; a (-inf, -1) padded tail is allowed: the list ends at its first
+ *     row < 0 and the query selects from what it has;
+ *   - sim(i, j) = float32 dot product of the stored rows of c_i and c_j over the first d columns, elements widened to
+ *     float32, summed in one fixed order that does not depend on B, C, k or the grid (the row is cut into 16-byte
+ *     chunks; lane l of a 64-lane wave adds the elements of chunks l, l + 64, ... in ascending order into one
+ *     accumulator with fmaf; the 64 accumulators are added by the xor butterfly 32, 16, 8, 4, 2, 1);
+ *   - step 0 picks c_0; step t >= 1 picks the not yet picked i that maximises
+ *         v_i = fl(fl(lambda * rel_i) - fl(fl(1 - lambda) * max_{j in S} sim(i, j)))     (float32, S = the picks so far)
+ *     ties to the lower i (the better dense rank); selection stops after k picks or when the candidates run out;
+ *   - output in pick order: out_scores = rel, out_rows = the row, out_pos = i, out_mmr = v at the time of the pick
+ *     (rel_0 for step 0); unused slots are (-inf, -1, -1, -inf).
+ * lambda = 1 reproduces the first k candidates; lambda = 0 is pure diversity after the first pick.
+ *
+ *   corpus       dev [*, ld] rows of `dtype`, 16-byte aligned, ld * element size a multiple of 16 (any ld the index
+ *                uses); every cand_rows entry >= 0 must be a row of it (rows are not checked against a count)
+ *   cand_scores  dev [B, C] float32      cand_rows  dev [B, C] int64
+ *   out_*        dev [B, k]: float32, int64, int32, float32
+ *   workspace    >= mmrag_mmr_select_workspace_bytes(B, C, d, dtype) bytes, which is 0 today (NULL is accepted)
+ * MMRAG_EINVAL unless 1 <= k <= C <= MMRAG_MAX_MMR_CANDIDATES, 0 <= lambda <= 1 (NaN is rejected) and dtype is known;
+ * arguments are checked before any HIP call. */
+#define MMRAG_MAX_MMR_CANDIDATES 1024
+size_t mmrag_mmr_select_workspace_bytes(int B, int C, int d, int dtype);
+int mmrag_mmr_select(const void *corpus, int64_t ld, int dtype, int d, const float *cand_scores,
+                     const int64_t *cand_rows, int B, int C, int k, float lambda, float *out_scores, int64_t *out_rows,
+                     int32_t *out_pos, float *out_mmr, void *workspace, size_t workspace_bytes, void *stream);
+
 /* CLIP byte-level BPE (the text tower's tokenizer, BASELINE config 4; the reference only names CLIP in config.py:106).
  * Host code, multi-threaded; equals multimodal_rag_amd/tokenizer.py:ClipBpeTokenizer, which tests pin to
  * transformers.CLIPTokenizer.  The caller passes text already NFC-normalised, whitespace-collapsed and lower-cased.

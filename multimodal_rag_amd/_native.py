@@ -20,6 +20,7 @@ LIB_PATH = os.path.join(_PKG, "lib", "libmmrag.so")
 F32, F16, BF16 = 0, 1, 2
 MAX_K = 20
 MAX_K_DEEP = 4096   # mmrag_cosine_topk_deep
+MAX_MMR_CANDIDATES = 1024   # mmrag_mmr_select (MMRAG_MAX_MMR_CANDIDATES)
 _TORCH2DT = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 _DT2TORCH = {v: k for k, v in _TORCH2DT.items()}
 
@@ -174,6 +175,14 @@ def _declare(lib):
     lib.mmrag_internal_cls_head_f32.argtypes = [c_void_p] * 6 + [c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]
     lib.mmrag_internal_cls_head_workspace_bytes.restype = c_size_t
     lib.mmrag_internal_cls_head_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    # MMR selection (csrc/mmr.hip); the _ex form is its debug entry (not in include/mmrag.h)
+    lib.mmrag_mmr_select_workspace_bytes.restype = c_size_t
+    lib.mmrag_mmr_select_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    lib.mmrag_mmr_select.restype = c_int
+    lib.mmrag_mmr_select.argtypes = [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.mmrag_internal_mmr_select_ex.restype = c_int
+    lib.mmrag_internal_mmr_select_ex.argtypes = lib.mmrag_mmr_select.argtypes + [ctypes.c_uint]
     from .lexical import declare as declare_lexical   # BM25 analyzer, device index and search (csrc/lexical.hip)
 
     declare_lexical(lib)
@@ -311,6 +320,44 @@ def cosine_topk_deep(q: torch.Tensor, corpus: torch.Tensor, n: int, d: int, k: i
 
 def cosine_topk_deep_workspace_bytes(B: int, n: int, k: int) -> int:
     return int(lib().mmrag_cosine_topk_deep_workspace_bytes(B, n, k))
+
+
+# debug switch of the MMR selection (tests, tools/mmr_bench.py): the streamed form also where the staged one fits
+MMR_DBG_STREAM = 1
+
+
+def mmr_select_workspace_bytes(B: int, C: int, d: int, dtype: torch.dtype) -> int:
+    return int(lib().mmrag_mmr_select_workspace_bytes(B, C, d, _TORCH2DT[dtype]))
+
+
+def mmr_select(corpus: torch.Tensor, d: int, cand_scores: torch.Tensor, cand_rows: torch.Tensor, k: int,
+               lambda_mult: float, dbg: int = 0):
+    """Maximal-marginal-relevance selection (include/mmrag.h mmrag_mmr_select) of k of each query's C candidates:
+    cand_scores [B, C] float32 and cand_rows [B, C] int64 in the search's order, (-inf, -1) padded tails allowed.
+    Returns device tensors in pick order: (scores [B, k] float32, rows [B, k] int64, positions [B, k] int32,
+    mmr values [B, k] float32), unused slots (-inf, -1, -1, -inf).  One launch on the current stream, no host sync."""
+    _dev_check(corpus, cand_scores, cand_rows)
+    if corpus.dim() != 2 or not corpus.is_contiguous() or corpus.dtype not in _TORCH2DT:
+        raise MMRagNativeError("mmr_select: corpus must be a contiguous 2-D tensor of a storage dtype")
+    if (cand_scores.dim() != 2 or cand_scores.shape != cand_rows.shape or cand_scores.dtype != torch.float32
+            or cand_rows.dtype != torch.int64 or not cand_scores.is_contiguous() or not cand_rows.is_contiguous()):
+        raise MMRagNativeError("mmr_select: cand_scores [B, C] float32 and cand_rows [B, C] int64 must be contiguous "
+                               "and of one shape")
+    if cand_scores.device != corpus.device or cand_rows.device != corpus.device:
+        raise MMRagNativeError("mmr_select: candidates and corpus must be on one device")
+    B, C = cand_scores.shape
+    dev = corpus.device
+    out_s = torch.empty((B, k), dtype=torch.float32, device=dev)
+    out_r = torch.empty((B, k), dtype=torch.int64, device=dev)
+    out_p = torch.empty((B, k), dtype=torch.int32, device=dev)
+    out_v = torch.empty((B, k), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        st = lib().mmrag_internal_mmr_select_ex(corpus.data_ptr(), corpus.shape[1], _TORCH2DT[corpus.dtype], d,
+                                                cand_scores.data_ptr(), cand_rows.data_ptr(), B, C, k,
+                                                float(lambda_mult), out_s.data_ptr(), out_r.data_ptr(),
+                                                out_p.data_ptr(), out_v.data_ptr(), None, 0, _stream_ptr(dev), int(dbg))
+    _check(st, "mmrag_mmr_select")
+    return out_s, out_r, out_p, out_v
 
 
 def device_info() -> dict:

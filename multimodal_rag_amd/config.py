@@ -74,6 +74,11 @@ class Settings:
     # reciprocal rank with sum 1 / (MMRAG_HYBRID_RRF_K + rank)
     MMRAG_HYBRID_CANDIDATES: int = field(default_factory=lambda: int(os.getenv("MMRAG_HYBRID_CANDIDATES", "50")))
     MMRAG_HYBRID_RRF_K: int = field(default_factory=lambda: int(os.getenv("MMRAG_HYBRID_RRF_K", "60")))
+    # diversified retrieval (VectorIndex.mmr_query, csrc/mmr.hip): maximal marginal relevance picks n_results of
+    # max(n_results, MMRAG_MMR_CANDIDATES) dense hits (at most 1024) with v = lambda rel - (1 - lambda) max sim to the
+    # picks so far; lambda = 1 is the plain dense order, 0 pure diversity
+    MMRAG_MMR_CANDIDATES: int = field(default_factory=lambda: int(os.getenv("MMRAG_MMR_CANDIDATES", "50")))
+    MMRAG_MMR_LAMBDA: float = field(default_factory=lambda: float(os.getenv("MMRAG_MMR_LAMBDA", "0.5")))
     # CLIP engines only: embed image items from their pixels (vision tower) instead of their summary text
     MMRAG_EMBED_IMAGE_PIXELS: bool = field(default_factory=lambda: _b("MMRAG_EMBED_IMAGE_PIXELS", "true"))
 

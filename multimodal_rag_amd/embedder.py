@@ -38,6 +38,7 @@ logger = logging.getLogger(__name__)
 ITEM_KINDS = ("text", "table", "image")           # the kinds embed_and_store counts (embedder.py:477-479)
 RESULT_KEYS = ("ids", "distances", "metadatas", "documents")
 HYBRID_KEYS = RESULT_KEYS + ("hybrid_scores", "lexical_scores")
+MMR_KEYS = RESULT_KEYS + ("mmr_scores",)
 _HOSTROWS = load_hostrows()
 _COLLECTION_NOTE = {"description": "Multi-modal RAG embeddings"}
 
@@ -354,6 +355,72 @@ class EmbeddingManager:
             raise
         self.stats["total_queries"] += 1
         return hit
+
+    def supports_mmr(self) -> bool:
+        """True when the collection can answer mmr_query (a single-GPU VectorIndex; not the sharded serving path, whose
+        candidates' rows live on different GPUs)"""
+        return self.collection is None or hasattr(self.collection, "mmr_query")
+
+    def _answer_mmr(self, texts: Sequence[str], n_results: int, filter_dict: Optional[Dict], fetch_k: Optional[int],
+                    lambda_mult: Optional[float]) -> List[Dict[str, Any]]:
+        """blocking, one worker thread: cached or fresh embeddings (ONE encoder pass for the misses), then ONE
+        collection.mmr_query for all of them (one search, one selection launch)"""
+        rows, todo, keys = self._lookup(texts)
+        if todo:
+            self._encode_into(texts, rows, todo, keys)
+        matrix = self._stack(rows, len(todo))
+        res = self.collection.mmr_query(matrix, n_results=n_results, fetch_k=fetch_k, lambda_mult=lambda_mult,
+                                        where=filter_dict, include=self._INCLUDE)
+        return [{key: res[key][at] for key in MMR_KEYS} for at in range(len(texts))]
+
+    async def mmr_query(self, query_text: str, n_results: int = 5, filter_dict: Optional[Dict] = None,
+                        fetch_k: Optional[int] = None, lambda_mult: Optional[float] = None) -> Dict[str, Any]:
+        """Diversified retrieval (VectorIndex.mmr_query): maximal-marginal-relevance selection of n_results of the
+        fetch_k best dense hits.  One result dict with the keys of query() plus `mmr_scores`, in pick order (distances
+        are therefore not ascending).  Same empty-query error, embedding cache and query count as query(); it calls
+        the collection directly (no dynamic batching)."""
+        await self._ready()
+        if not query_text or not query_text.strip():
+            raise ValueError("Query text cannot be empty")
+        if not hasattr(self.collection, "mmr_query"):
+            raise ValueError("MMR retrieval needs a single-GPU collection (VectorIndex)")
+        try:
+            hit = (await self._engine_call("MMR query", self._answer_mmr, [query_text], n_results, filter_dict, fetch_k,
+                                           lambda_mult))[0]
+        except Exception as e:
+            logger.error("MMR query failed: %s", e, exc_info=True)
+            raise
+        self.stats["total_queries"] += 1
+        return hit
+
+    async def batch_mmr_query(self, queries: List[str], n_results: int = 5, filter_dict: Optional[Dict] = None,
+                              fetch_k: Optional[int] = None,
+                              lambda_mult: Optional[float] = None) -> List[Dict[str, Any]]:
+        """batch_query's twin for mmr_query: one batched encode, one search and one selection launch for all the
+        queries; a query that cannot be answered gets a dict with empty lists and an 'error' message."""
+        await self._ready()
+
+        def failed(why: str) -> Dict[str, Any]:
+            return {**{key: [] for key in MMR_KEYS}, "error": why}
+
+        answers: List[Optional[Dict[str, Any]]] = [None] * len(queries)
+        live = [at for at, q in enumerate(queries) if q and q.strip()]
+        for at in set(range(len(queries))) - set(live):
+            answers[at] = failed("Query text cannot be empty")
+        if live:
+            try:
+                if not hasattr(self.collection, "mmr_query"):
+                    raise ValueError("MMR retrieval needs a single-GPU collection (VectorIndex)")
+                hits = await self._engine_call("Batch MMR query", self._answer_mmr, [queries[at] for at in live],
+                                               n_results, filter_dict, fetch_k, lambda_mult)
+                for at, hit in zip(live, hits):
+                    answers[at] = hit
+                self.stats["total_queries"] += len(live)
+            except Exception as e:
+                logger.error("Batch MMR query failed: %s", e)
+                for at in live:
+                    answers[at] = failed(str(e))
+        return answers  # type: ignore[return-value]
 
     async def batch_query(self, queries: List[str], n_results: int = 5,
                           filter_dict: Optional[Dict] = None) -> List[Dict[str, Any]]:

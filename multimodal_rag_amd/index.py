@@ -633,6 +633,53 @@ class VectorIndex:
             if self._lex is not None:
                 self._lex.reset()
 
+    # ------------------------------------------------------------------ diversified (MMR) ----
+    def _launch_mmr(self, query_embeddings, n_results: int, fetch_k, lambda_mult, where, check_norm: bool = True):
+        """enqueue the dense search for the candidates and the MMR selection over them, on one stream (caller holds
+        the lock): device (scores, rows, positions, mmr values) [B, n_results] in pick order, no host sync of its own"""
+        from .config import settings
+
+        if n_results < 1:
+            raise ValueError("n_results must be >= 1")
+        if n_results > _native.MAX_MMR_CANDIDATES:
+            raise ValueError(f"n_results must be <= {_native.MAX_MMR_CANDIDATES} for MMR selection")
+        C = max(n_results, settings.MMRAG_MMR_CANDIDATES) if fetch_k is None else int(fetch_k)
+        C = max(min(C, _native.MAX_MMR_CANDIDATES), n_results)
+        lam = float(settings.MMRAG_MMR_LAMBDA if lambda_mult is None else lambda_mult)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"lambda_mult must be in [0, 1] (got {lambda_mult!r})")
+        scores, rows = self._launch_search(query_embeddings, C, where, check_norm)
+        return _native.mmr_select(self._matrix, self.dim, scores.contiguous(), rows.contiguous(), n_results, lam)
+
+    def mmr_search(self, query_embeddings, n_results: int, fetch_k: Optional[int] = None,
+                   lambda_mult: Optional[float] = None, where: Optional[Dict[str, Any]] = None):
+        """Raw diversified search: maximal-marginal-relevance selection (csrc/mmr.hip, include/mmrag.h
+        mmrag_mmr_select) of n_results of the fetch_k best dense hits.  Returns device tensors [B, n_results] in PICK
+        order: (scores float32 = the dense scores, rows int64, positions int32 in the dense order, mmr values float32),
+        unused slots (-inf, -1, -1, -inf).  fetch_k defaults to max(n_results, MMRAG_MMR_CANDIDATES), is clipped to
+        MAX_MMR_CANDIDATES = 1024 and raised to n_results; lambda_mult defaults to MMRAG_MMR_LAMBDA (1 = the dense
+        order, 0 = pure diversity after the first pick).  The candidates are search()'s, so deleted and filtered rows
+        never appear."""
+        with self._lock:
+            return self._launch_mmr(query_embeddings, n_results, fetch_k, lambda_mult, where)
+
+    def mmr_query(self, query_embeddings, n_results: int = 10, fetch_k: Optional[int] = None,
+                  lambda_mult: Optional[float] = None, where: Optional[Dict[str, Any]] = None,
+                  include: Sequence[str] = ("metadatas", "documents", "distances"),
+                  check_norm: bool = True) -> Dict[str, Any]:
+        """query() with maximal-marginal-relevance selection (see mmr_search): the Chroma-shaped dict of query() plus
+        `mmr_scores`, the value lambda * cos - (1 - lambda) * (largest cos to an earlier pick) each hit was picked
+        with (the first hit: its cos).  Results are in PICK order, so `distances` (1 - cos) are NOT ascending."""
+        with self._lock, stage("search"):
+            scores, rows, _, mmr = self._launch_mmr(query_embeddings, n_results, fetch_k, lambda_mult, where,
+                                                    check_norm)
+            ids_t, docs_t, metas_t = self._ids, self._documents, self._metadatas
+            emb_src = self._matrix if "embeddings" in include else None
+        with stage("collect"):
+            out = self._collect(scores, rows, include, ids_t, docs_t, metas_t, emb_src)
+            out["mmr_scores"] = [vals[: len(ids)] for vals, ids in zip(mmr.cpu().tolist(), out["ids"])]
+            return out
+
     # ------------------------------------------------------------------ lexical / hybrid ----
     def enable_lexical(self):
         """Build the BM25 state (lexical.LexicalIndex) from the stored documents in row order; from then on add,

@@ -9,6 +9,7 @@ LLM) can be the reference's real ones; defaults are the minimal stand-ins in ing
 """
 from __future__ import annotations
 
+import functools
 import logging
 import time
 import uuid
@@ -40,6 +41,12 @@ class QueryRequest(BaseModel):  # api.py:161-164
     # .hybrid_query); each source then carries its `hybrid_score`.  With `rerank`, max(top_k, MMRAG_RERANK_CANDIDATES)
     # hybrid hits are re-ranked
     hybrid: bool = Field(False)
+    # not in the reference: diversified hits (EmbeddingManager.mmr_query: maximal marginal relevance over
+    # MMRAG_MMR_CANDIDATES dense hits); each source then carries its `mmr_score`.  `mmr_lambda` (default
+    # MMRAG_MMR_LAMBDA): 1 = plain relevance, 0 = pure diversity.  With `rerank`, max(top_k, MMRAG_RERANK_CANDIDATES)
+    # diverse hits are re-ranked.  Not combined with `hybrid` yet
+    mmr: bool = Field(False)
+    mmr_lambda: Optional[float] = Field(None, ge=0.0, le=1.0)
 
 
 class QueryResponse(BaseModel):  # api.py:167-170
@@ -127,18 +134,23 @@ class Pipeline:
                 "chunks_processed": stored}
 
     async def answer(self, question: str, top_k: int, multimodal: bool, rerank: bool = False,
-                     hybrid: bool = False) -> Optional[dict]:
+                     hybrid: bool = False, mmr: bool = False, mmr_lambda: Optional[float] = None) -> Optional[dict]:
         """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
         max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the cross-encoder's best top_k.  `hybrid`: the hits come from
-        dense + BM25 retrieval fused by reciprocal rank"""
-        search = self.embedder.hybrid_query if hybrid else self.embedder.query
+        dense + BM25 retrieval fused by reciprocal rank.  `mmr`: the hits are a maximal-marginal-relevance selection of
+        the dense candidates (`mmr_lambda`, default MMRAG_MMR_LAMBDA)"""
+        if mmr:
+            search = functools.partial(self.embedder.mmr_query, lambda_mult=mmr_lambda)
+        else:
+            search = self.embedder.hybrid_query if hybrid else self.embedder.query
+        extra = "mmr_scores" if mmr else "hybrid_scores" if hybrid else None   # per-hit column re-ranking carries along
         if rerank:
             hits = await search(question, n_results=max(top_k, settings.MMRAG_RERANK_CANDIDATES))
             if hits["ids"]:
-                fused = dict(zip(hits["ids"], hits["hybrid_scores"])) if hybrid else None
+                fused = dict(zip(hits["ids"], hits[extra])) if extra else None
                 hits = await self.embedder.rerank_results(question, hits, top_k=top_k)
-                if hybrid:
-                    hits["hybrid_scores"] = [fused[found] for found in hits["ids"]]
+                if extra:
+                    hits[extra] = [fused[found] for found in hits["ids"]]
         else:
             hits = await search(question, n_results=top_k)
         if not hits["ids"]:
@@ -163,6 +175,9 @@ class Pipeline:
         if hybrid:
             for src, score in zip(ranked, hits["hybrid_scores"]):
                 src["hybrid_score"] = score
+        if mmr:
+            for src, score in zip(ranked, hits["mmr_scores"]):
+                src["mmr_score"] = score
         return {"answer": text, "sources": ranked}
 
     async def health(self) -> dict:
@@ -190,8 +205,6 @@ class Pipeline:
 def _as_http_500(fn):
     """route wrapper: anything but an HTTPException becomes a 500 with the message as detail (the reference's blanket
     `except Exception` around every route body)"""
-    import functools
-
     @functools.wraps(fn)
     async def wrapped(*a, **kw):
         try:
@@ -251,12 +264,23 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
         if request.rerank and not (hasattr(pipe.embedder, "has_reranker") and pipe.embedder.has_reranker()):
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="Re-ranking is not configured: set MMRAG_RERANKER_DIR to a local cross-encoder")
+        if request.mmr and request.hybrid:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                detail="MMR and hybrid retrieval are not combined yet: send `mmr` or `hybrid`, not both")
         if request.hybrid and not (hasattr(pipe.embedder, "hybrid_query")
                                    and getattr(pipe.embedder, "supports_hybrid", lambda: True)()):
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="Hybrid retrieval is not available with this embedder: it needs a single-GPU "
                                        "collection with lexical search (EmbeddingManager.hybrid_query)")
-        if request.hybrid:
+        if request.mmr and not (hasattr(pipe.embedder, "mmr_query")
+                                and getattr(pipe.embedder, "supports_mmr", lambda: True)()):
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                detail="MMR retrieval is not available with this embedder: it needs a single-GPU "
+                                       "collection (EmbeddingManager.mmr_query)")
+        if request.mmr:
+            out = await pipe.answer(request.query, request.top_k, request.use_multimodal, rerank=request.rerank,
+                                    mmr=True, mmr_lambda=request.mmr_lambda)
+        elif request.hybrid:
             out = await pipe.answer(request.query, request.top_k, request.use_multimodal, rerank=request.rerank,
                                     hybrid=True)
         elif request.rerank:
