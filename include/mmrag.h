@@ -39,6 +39,12 @@ extern "C" {
 #define MMRAG_F32 0
 #define MMRAG_F16 1
 #define MMRAG_BF16 2
+/* FP8 collections (gfx950 is OCP, not fnuz).  A stored element is the OCP E4M3 code of x * 256, rounded to nearest
+ * even from float32: subnormals kept, magnitudes above 448 saturate to 448, NaN stores +0.  Rows and queries share
+ * the constant scale 2^8, so a score is acc * 2^-16 (an exact scaling of the float32 accumulator).  Rows are padded
+ * to 128 elements (one 128-byte K-slab), pad columns are code 0x00.  Accepted by mmrag_padded_dim, append / gather /
+ * fetch rows, mmrag_cosine_topk(_lists) and mmrag_cosine_topk_deep (q and corpus both dtype 3); nowhere else. */
+#define MMRAG_F8E4M3 3
 
 #define MMRAG_MAX_K 20 /* api.py:163  top_k: int = Field(5, ge=1, le=20) */
 
@@ -99,6 +105,18 @@ int mmrag_cosine_topk_deep(const void *q, const void *corpus, int B, int64_t n, 
                            int dtype, int k, int64_t row_offset, const uint32_t *alive_bits,
                            float *out_scores, int64_t *out_rows, void *workspace,
                            size_t workspace_bytes, void *stream);
+
+/* Exact re-scoring of candidate lists (FP8 collections: the scan plane over-fetches, the full-precision plane ranks).
+ * For each of B queries and its C candidate rows (cand_rows dev [B, C] int64, rows below 2^31; a negative row ends
+ * that query's list) the float32 dot product of q[b] with plane[row] over the first d columns, in mmrag_rows_dot's
+ * summation order (bit-identical to it), then the best k ordered by (score desc, row asc), (-inf, -1) padded.
+ *   q, plane   dev [B, ld] / [n, ld], dtype MMRAG_F32 / F16 / BF16 (MMRAG_F8E4M3 is rejected)
+ *   1 <= k <= C <= MMRAG_MAX_RESCORE_CANDIDATES
+ * One launch, one workgroup per query, no host synchronisation, no float atomics: the result depends neither on B
+ * nor on the order in which the candidates are listed. */
+#define MMRAG_MAX_RESCORE_CANDIDATES 4096
+int mmrag_rescore_topk(const void *q, const void *plane, int64_t ld, int dtype, int d, const int64_t *cand_rows,
+                       int B, int C, int k, float *out_scores, int64_t *out_rows, void *stream);
 
 /* Merge G shards' local top-k (layout [G, B, k_in], as produced by an all-gather of
  * mmrag_cosine_topk outputs) into the global top-k [B, k].  Device version (one tiny

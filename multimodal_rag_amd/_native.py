@@ -17,12 +17,13 @@ import torch
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "lib", "libmmrag.so")
 
-F32, F16, BF16 = 0, 1, 2
+F32, F16, BF16, F8E4M3 = 0, 1, 2, 3
 MAX_K = 20
 MAX_K_DEEP = 4096   # mmrag_cosine_topk_deep
 MAX_MMR_CANDIDATES = 1024   # mmrag_mmr_select (MMRAG_MAX_MMR_CANDIDATES)
-_TORCH2DT = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
-_DT2TORCH = {v: k for k, v in _TORCH2DT.items()}
+MAX_RESCORE_CANDIDATES = 4096   # mmrag_rescore_topk (MMRAG_MAX_RESCORE_CANDIDATES)
+_DT2TORCH = {F32: torch.float32, F16: torch.float16, BF16: torch.bfloat16, F8E4M3: torch.float8_e4m3fn}
+_TORCH2DT = {v: k for k, v in _DT2TORCH.items()}
 
 _lib = None
 _lock = threading.Lock()
@@ -60,6 +61,9 @@ def _declare(lib):
     # debug form of mmrag_cosine_topk_deep (csrc/search_deep.hip, not in include/mmrag.h): switches + candidate capacity
     lib.mmrag_internal_cosine_topk_deep_ex.restype = c_int
     lib.mmrag_internal_cosine_topk_deep_ex.argtypes = lib.mmrag_cosine_topk.argtypes + [ctypes.c_uint, c_int64]
+    lib.mmrag_rescore_topk.restype = c_int
+    lib.mmrag_rescore_topk.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                       c_void_p, c_void_p, c_void_p]
     lib.mmrag_merge_topk.restype = c_int
     lib.mmrag_merge_topk.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.mmrag_merge_topk_host.restype = c_int
@@ -320,6 +324,36 @@ def cosine_topk_deep(q: torch.Tensor, corpus: torch.Tensor, n: int, d: int, k: i
 
 def cosine_topk_deep_workspace_bytes(B: int, n: int, k: int) -> int:
     return int(lib().mmrag_cosine_topk_deep_workspace_bytes(B, n, k))
+
+
+def rescore_topk(q: torch.Tensor, plane: torch.Tensor, d: int, cand_rows: torch.Tensor, k: int,
+                 packed_out: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact re-scoring of candidate lists (include/mmrag.h mmrag_rescore_topk): q [B, ld] and plane [cap, ld] in one
+    full-precision dtype, cand_rows [B, C] int64 (a negative row ends a list).  Returns (scores [B, k] float32, rows
+    [B, k] int64) ordered by (score desc, row asc), (-inf, -1) padded; scores are mmrag_rows_dot's, bit for bit.  One
+    launch on the current stream, no host sync."""
+    _dev_check(q, plane, cand_rows)
+    if q.dim() != 2 or plane.dim() != 2 or not q.is_contiguous() or not plane.is_contiguous():
+        raise MMRagNativeError("rescore_topk: q and plane must be contiguous 2-D tensors")
+    if q.dtype != plane.dtype or q.shape[1] != plane.shape[1]:
+        raise MMRagNativeError("rescore_topk: q and plane must share dtype and padded width")
+    if cand_rows.dim() != 2 or cand_rows.dtype != torch.int64 or not cand_rows.is_contiguous() \
+            or cand_rows.shape[0] != q.shape[0]:
+        raise MMRagNativeError("rescore_topk: cand_rows must be a contiguous [B, C] int64 tensor")
+    B, C = cand_rows.shape
+    if packed_out:   # [rows | scores] in one buffer, as cosine_topk(packed_out=True)
+        buf = torch.empty(B * k * 12, dtype=torch.uint8, device=q.device)
+        out_r = buf[: B * k * 8].view(torch.int64).view(B, k)
+        out_s = buf[B * k * 8:].view(torch.float32).view(B, k)
+    else:
+        out_s = torch.empty((B, k), dtype=torch.float32, device=q.device)
+        out_r = torch.empty((B, k), dtype=torch.int64, device=q.device)
+    with torch.cuda.device(q.device):
+        st = lib().mmrag_rescore_topk(q.data_ptr(), plane.data_ptr(), plane.shape[1], _TORCH2DT[plane.dtype], d,
+                                      cand_rows.data_ptr(), B, C, k, out_s.data_ptr(), out_r.data_ptr(),
+                                      _stream_ptr(q.device))
+    _check(st, "mmrag_rescore_topk")
+    return out_s, out_r
 
 
 # debug switch of the MMR selection (tests, tools/mmr_bench.py): the streamed form also where the staged one fits

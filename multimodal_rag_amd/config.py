@@ -41,7 +41,13 @@ class Settings:
     # local Hugging Face style directory with config.json + model.safetensors + vocab.txt; when
     # empty the named architecture is random-initialised and a stand-in tokenizer is used
     MMRAG_MODEL_DIR: str = field(default_factory=lambda: os.getenv("MMRAG_MODEL_DIR", ""))
+    # "float16" (default), "float32", "bfloat16", or "float8_e4m3fn": one-byte E4M3 codes scanned on the FP8 matrix
+    # instruction (index.py VectorIndex).  MMRAG_F8_RESCORE: "float16" keeps a full-precision plane next to the FP8 one
+    # and every search re-scores MMRAG_F8_OVERSAMPLE x n_results candidates (at least 20) exactly on it (1.5x the
+    # memory of a float16 collection, faster scans); "none" is the capacity mode (0.5x; FP8 scores, no mmr / hybrid)
     MMRAG_INDEX_DTYPE: str = field(default_factory=lambda: os.getenv("MMRAG_INDEX_DTYPE", "float16"))
+    MMRAG_F8_RESCORE: str = field(default_factory=lambda: os.getenv("MMRAG_F8_RESCORE", "float16"))
+    MMRAG_F8_OVERSAMPLE: int = field(default_factory=lambda: int(os.getenv("MMRAG_F8_OVERSAMPLE", "4")))
     # float32 collections: batches of more than 64 queries are scored on the bf16 matrix pipe from a three-term split
     # of the float32 operands (|score error| <= 4e-5: approximate, and a query's score then depends on how many
     # requests the dispatcher batched it with).  "true" keeps the exact float32 matrix instruction for every batch
@@ -81,6 +87,26 @@ class Settings:
     MMRAG_MMR_LAMBDA: float = field(default_factory=lambda: float(os.getenv("MMRAG_MMR_LAMBDA", "0.5")))
     # CLIP engines only: embed image items from their pixels (vision tower) instead of their summary text
     MMRAG_EMBED_IMAGE_PIXELS: bool = field(default_factory=lambda: _b("MMRAG_EMBED_IMAGE_PIXELS", "true"))
+
+    def index_dtype(self):
+        """MMRAG_INDEX_DTYPE as a torch dtype"""
+        import torch
+
+        names = {"float16": torch.float16, "float32": torch.float32, "bfloat16": torch.bfloat16,
+                 "float8_e4m3fn": torch.float8_e4m3fn}
+        if self.MMRAG_INDEX_DTYPE not in names:
+            raise ValueError(f"MMRAG_INDEX_DTYPE must be one of {sorted(names)} (got {self.MMRAG_INDEX_DTYPE!r})")
+        return names[self.MMRAG_INDEX_DTYPE]
+
+    def f8_rescore_dtype(self):
+        """MMRAG_F8_RESCORE as a torch dtype, None for "none" (capacity mode)"""
+        import torch
+
+        names = {"float16": torch.float16, "float32": torch.float32, "bfloat16": torch.bfloat16, "none": None}
+        key = self.MMRAG_F8_RESCORE.lower()
+        if key not in names:
+            raise ValueError(f"MMRAG_F8_RESCORE must be one of {sorted(names)} (got {self.MMRAG_F8_RESCORE!r})")
+        return names[key]
 
 
 settings = Settings()

@@ -89,6 +89,51 @@ __global__ void fetch_rows_kernel(const T *__restrict__ corpus, int64_t ld,
     }
 }
 
+// FP8 collections (MMRAG_F8E4M3): OCP E4M3 code of x * 256, round to nearest even; subnormals kept, |y| > 448 saturates
+// to 448 (0x7e), NaN stores +0.  Written out in integer arithmetic: the hardware converter's NaN and saturation rules
+// depend on mode bits this library does not own.
+__device__ inline unsigned char f8_encode(float x) {
+    const float y = x * 256.0f;
+    if (y != y) return 0;
+    const unsigned sign = (__float_as_uint(y) >> 24) & 0x80u;
+    const float a = fabsf(y);
+    if (a > 448.0f) return (unsigned char)(sign | 0x7eu);
+    if (a < 0.015625f) return (unsigned char)(sign | (unsigned)rintf(a * 512.0f));   // subnormal step 2^-9; 8 = 2^-6
+    unsigned u = __float_as_uint(a);
+    u += 0x7ffffu + ((u >> 20) & 1u);
+    return (unsigned char)(sign | ((u >> 20) - (120u << 3)));
+}
+
+// decode(code) / 256; the two NaN codes (0x7f, 0xff) are never stored and read back as NaN
+__device__ inline float f8_decode_unscaled(unsigned char c) {
+    const int e = (c >> 3) & 15, m = c & 7;
+    float v = e == 0 ? (float)m * 0x1p-17f : ldexpf((float)(8 + m), e - 18);
+    if ((c & 0x7f) == 0x7f) v = __builtin_nanf("");
+    return (c & 0x80) ? -v : v;
+}
+
+__global__ void append_rows_f8_kernel(unsigned char *__restrict__ corpus, int64_t ld, int64_t n_used,
+                                      const float *__restrict__ src, int64_t m, int d) {
+    const int64_t total = m * ld;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / ld;
+        const int c = (int)(i - r * ld);
+        corpus[(n_used + r) * ld + c] = c < d ? f8_encode(src[r * d + c]) : (unsigned char)0;
+    }
+}
+
+__global__ void fetch_rows_f8_kernel(const unsigned char *__restrict__ corpus, int64_t ld,
+                                     const int64_t *__restrict__ rows, int64_t m, int d, float *__restrict__ out) {
+    const int64_t total = m * d;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / d;
+        const int c = (int)(i - r * d);
+        out[i] = f8_decode_unscaled(corpus[rows[r] * ld + c]);
+    }
+}
+
 inline int grid_for(int64_t total, int block) {
     int64_t g = (total + block - 1) / block;
     int64_t cap = (int64_t)num_cus() * 8;
@@ -110,7 +155,7 @@ void mmrag_internal_set_debug(unsigned flags) { mmrag::g_debug.store(flags, std:
 const char *mmrag_last_error(void) { return mmrag::g_err; }
 
 int64_t mmrag_padded_dim(int d, int dtype) {
-    if (d <= 0 || dtype < 0 || dtype > 2) return -1;
+    if (d <= 0 || dtype < 0 || dtype > MMRAG_F8E4M3) return -1;
     const int per = 128 / esize(dtype);
     return ((int64_t)d + per - 1) / per * per;
 }
@@ -118,7 +163,7 @@ int64_t mmrag_padded_dim(int d, int dtype) {
 int mmrag_append_rows(void *corpus, int64_t capacity, int64_t ld, int dtype, int64_t n_used,
                       const float *new_rows, int64_t m, int d, void *stream) {
     MMRAG_CHECK_ARG(corpus && new_rows, "append_rows: null pointer");
-    MMRAG_CHECK_ARG(dtype >= 0 && dtype <= 2, "append_rows: bad dtype %d", dtype);
+    MMRAG_CHECK_ARG(dtype >= 0 && dtype <= MMRAG_F8E4M3, "append_rows: bad dtype %d", dtype);
     MMRAG_CHECK_ARG(d > 0 && ld >= d, "append_rows: need 0 < d <= ld (d=%d ld=%lld)", d, (long long)ld);
     MMRAG_CHECK_ARG(m >= 0 && n_used >= 0 && n_used + m <= capacity,
                     "append_rows: rows [%lld, %lld) exceed capacity %lld", (long long)n_used,
@@ -131,6 +176,8 @@ int mmrag_append_rows(void *corpus, int64_t capacity, int64_t ld, int dtype, int
         append_rows_kernel<float><<<grid, block, 0, s>>>((float *)corpus, ld, n_used, new_rows, m, d);
     else if (dtype == MMRAG_F16)
         append_rows_kernel<_Float16><<<grid, block, 0, s>>>((_Float16 *)corpus, ld, n_used, new_rows, m, d);
+    else if (dtype == MMRAG_F8E4M3)
+        append_rows_f8_kernel<<<grid, block, 0, s>>>((unsigned char *)corpus, ld, n_used, new_rows, m, d);
     else
         append_rows_kernel<__bf16><<<grid, block, 0, s>>>((__bf16 *)corpus, ld, n_used, new_rows, m, d);
     MMRAG_CHECK_HIP(hipGetLastError());
@@ -140,7 +187,7 @@ int mmrag_append_rows(void *corpus, int64_t capacity, int64_t ld, int dtype, int
 int mmrag_gather_rows(void *dst, const void *src, int64_t ld, int dtype, const int64_t *keep_rows,
                       int64_t m, void *stream) {
     MMRAG_CHECK_ARG(dst && src && (keep_rows || m == 0), "gather_rows: null pointer");
-    MMRAG_CHECK_ARG(dtype >= 0 && dtype <= 2, "gather_rows: bad dtype %d", dtype);
+    MMRAG_CHECK_ARG(dtype >= 0 && dtype <= MMRAG_F8E4M3, "gather_rows: bad dtype %d", dtype);
     const int64_t row_bytes = ld * esize(dtype);
     MMRAG_CHECK_ARG(ld > 0 && row_bytes % 16 == 0, "gather_rows: row bytes %lld not a multiple of 16",
                     (long long)row_bytes);
@@ -156,7 +203,7 @@ int mmrag_gather_rows(void *dst, const void *src, int64_t ld, int dtype, const i
 int mmrag_fetch_rows_f32(const void *corpus, int64_t ld, int dtype, const int64_t *rows, int64_t m,
                          int d, float *out, void *stream) {
     MMRAG_CHECK_ARG(corpus && out && (rows || m == 0), "fetch_rows: null pointer");
-    MMRAG_CHECK_ARG(dtype >= 0 && dtype <= 2, "fetch_rows: bad dtype %d", dtype);
+    MMRAG_CHECK_ARG(dtype >= 0 && dtype <= MMRAG_F8E4M3, "fetch_rows: bad dtype %d", dtype);
     MMRAG_CHECK_ARG(d > 0 && ld >= d, "fetch_rows: need 0 < d <= ld");
     if (m == 0) return MMRAG_OK;
     hipStream_t s = (hipStream_t)stream;
@@ -166,6 +213,8 @@ int mmrag_fetch_rows_f32(const void *corpus, int64_t ld, int dtype, const int64_
         fetch_rows_kernel<float><<<grid, block, 0, s>>>((const float *)corpus, ld, rows, m, d, out);
     else if (dtype == MMRAG_F16)
         fetch_rows_kernel<_Float16><<<grid, block, 0, s>>>((const _Float16 *)corpus, ld, rows, m, d, out);
+    else if (dtype == MMRAG_F8E4M3)
+        fetch_rows_f8_kernel<<<grid, block, 0, s>>>((const unsigned char *)corpus, ld, rows, m, d, out);
     else
         fetch_rows_kernel<__bf16><<<grid, block, 0, s>>>((const __bf16 *)corpus, ld, rows, m, d, out);
     MMRAG_CHECK_HIP(hipGetLastError());

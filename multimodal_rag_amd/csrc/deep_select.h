@@ -22,6 +22,28 @@ __device__ inline float deep_key_score(unsigned long long key) {
     return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 
+// descending bitonic sort of the P (a power of two) keys a[0 .. P) in LDS by one workgroup of THREADS threads; the caller
+// has synchronised after writing the keys, and the keys are in place for every thread on return
+template <int THREADS>
+__device__ inline void lds_bitonic_sort_desc(unsigned long long *a, unsigned P, int tid) {
+    for (unsigned size = 2; size <= P; size <<= 1) {
+        for (unsigned stride = size >> 1; stride > 0; stride >>= 1) {
+            for (unsigned i = tid; i < P; i += THREADS) {
+                const unsigned j = i ^ stride;
+                if (j > i) {
+                    const unsigned long long x = a[i], y = a[j];
+                    const bool desc = (i & size) == 0;
+                    if ((x < y) == desc) {
+                        a[i] = y;
+                        a[j] = x;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
 // bound != 0: tau[q] = max(tau[q], k-th best candidate) (unchanged with fewer than k), no outputs.
 // bound == 0: out_* [k] of this query; a query whose count exceeds cap is left to the overflow re-run.
 __global__ __launch_bounds__(SEL_THREADS) void deep_select_kernel(const float *__restrict__ bs,
@@ -126,22 +148,7 @@ __global__ __launch_bounds__(SEL_THREADS) void deep_select_kernel(const float *_
     while (P < want) P <<= 1;
     for (unsigned i = want + tid; i < P; i += SEL_THREADS) win[i] = 0ull;   // below every real key
     __syncthreads();
-    for (unsigned size = 2; size <= P; size <<= 1) {
-        for (unsigned stride = size >> 1; stride > 0; stride >>= 1) {
-            for (unsigned i = tid; i < P; i += SEL_THREADS) {
-                const unsigned j = i ^ stride;
-                if (j > i) {
-                    const unsigned long long a = win[i], b = win[j];
-                    const bool desc = (i & size) == 0;
-                    if ((a < b) == desc) {
-                        win[i] = b;
-                        win[j] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    lds_bitonic_sort_desc<SEL_THREADS>(win, P, tid);
     out_s += (size_t)q * k;
     out_r += (size_t)q * k;
     for (int i = tid; i < k; i += SEL_THREADS) {

@@ -11,7 +11,7 @@ namespace mmrag {
 
 void set_error(const char *fmt, ...);
 
-inline int esize(int dtype) { return dtype == MMRAG_F32 ? 4 : 2; }
+inline int esize(int dtype) { return dtype == MMRAG_F32 ? 4 : (dtype == MMRAG_F8E4M3 ? 1 : 2); }
 
 #define MMRAG_CHECK_ARG(cond, ...)            \
     do {                                      \

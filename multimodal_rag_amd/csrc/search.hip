@@ -651,6 +651,7 @@ void launch_filter(int WN, const KParams &p, dim3 grid, hipStream_t s) {
 }
 
 int deep_filter_launch(int dtype, int WN, const KParams &p, int grid_x, int grid_y, hipStream_t s) {
+    if (dtype == MMRAG_F8E4M3) return f8_filter_launch(WN, p, grid_x, grid_y, s);
     const dim3 grid(grid_x, grid_y);
     if (dtype == MMRAG_F32) launch_filter<MMRAG_F32>(WN, p, grid, s);
     else if (dtype == MMRAG_F16) launch_filter<MMRAG_F16>(WN, p, grid, s);
@@ -729,7 +730,7 @@ size_t mmrag_cosine_topk_workspace_bytes(int B, int64_t n, int k) {
 
 static int check_search_args(const void *q, const void *corpus, int B, int64_t n, int d, int64_t ld, int dtype,
                              int k) {
-    MMRAG_CHECK_ARG(dtype >= 0 && dtype <= 2, "cosine_topk: bad dtype %d", dtype);
+    MMRAG_CHECK_ARG(dtype >= 0 && dtype <= MMRAG_F8E4M3, "cosine_topk: bad dtype %d", dtype);
     MMRAG_CHECK_ARG(B > 0, "cosine_topk: B must be positive (got %d)", B);
     MMRAG_CHECK_ARG(k >= 1 && k <= MMRAG_MAX_K, "cosine_topk: k=%d outside 1..%d", k, MMRAG_MAX_K);
     MMRAG_CHECK_ARG(n >= 0 && n < (int64_t)INT_MAX - TM, "cosine_topk: n=%lld out of range", (long long)n);
@@ -842,6 +843,7 @@ int mmrag_internal_cosine_topk_lists_ex(const void *q, const void *corpus, int B
         kp.thr0 = thr0;
         Plan lp = pl;
         lp.grid_x = grid_x;
+        if (dtype == MMRAG_F8E4M3) return f8_lists_launch(lp.K, lp.WN, kp, lp.grid_x, lp.grid_y, s);
         if (dtype == MMRAG_F32) return dispatch_main<MMRAG_F32>(lp, kp, s);
         if (dtype == MMRAG_F16) return dispatch_main<MMRAG_F16>(lp, kp, s);
         return dispatch_main<MMRAG_BF16>(lp, kp, s);

@@ -119,7 +119,7 @@ int mmrag_internal_cosine_topk_deep_ex(const void *q, const void *corpus, int B,
                                        int dtype, int k, int64_t row_offset, const uint32_t *alive_bits,
                                        float *out_scores, int64_t *out_rows, void *workspace, size_t workspace_bytes,
                                        void *stream, unsigned dbg, int64_t cap) {
-    MMRAG_CHECK_ARG(dtype >= 0 && dtype <= 2, "cosine_topk_deep: bad dtype %d", dtype);
+    MMRAG_CHECK_ARG(dtype >= 0 && dtype <= MMRAG_F8E4M3, "cosine_topk_deep: bad dtype %d", dtype);
     MMRAG_CHECK_ARG(B > 0, "cosine_topk_deep: B must be positive (got %d)", B);
     MMRAG_CHECK_ARG(k >= 1 && k <= MMRAG_MAX_K_DEEP, "cosine_topk_deep: k=%d outside 1..%d", k, MMRAG_MAX_K_DEEP);
     MMRAG_CHECK_ARG(n >= 0 && n < (int64_t)INT_MAX - DEEP_TM, "cosine_topk_deep: n=%lld out of range", (long long)n);

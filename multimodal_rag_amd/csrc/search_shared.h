@@ -163,5 +163,11 @@ int qsw_launch(int dtype, int K, int mfma, const KParams &p, int grid_x, int gri
 // deep_cnt[q].  Walks p.n_tiles tiles: tile0 + (bx + i * walkers) * tile_stride.
 int deep_filter_launch(int dtype, int WN, const KParams &p, int grid_x, int grid_y, hipStream_t s);
 
+// ---- FP8 collections (search_f8.hip): the slab-ring kernel on the block-scaled FP8 MFMA, dtype MMRAG_F8E4M3 ------------
+// The list search (K = 5 / 10 / 20, the WN plan of search.hip's make_plan; p.thr0 seeds the thresholds) and
+// the filter mode, with the candidate-list and survivor-buffer layouts of the fp16 kernels.  Scores leave scaled by 2^-16.
+int f8_lists_launch(int K, int WN, const KParams &p, int grid_x, int grid_y, hipStream_t s);
+int f8_filter_launch(int WN, const KParams &p, int grid_x, int grid_y, hipStream_t s);
+
 
 }  // namespace mmrag_impl

@@ -325,7 +325,13 @@ class EmbeddingManager:
 
     def supports_hybrid(self) -> bool:
         """True when the collection can answer hybrid_query (a single-GPU VectorIndex; not the sharded serving path)"""
-        return self.collection is None or hasattr(self.collection, "hybrid_query")
+        return self.collection is None or (hasattr(self.collection, "hybrid_query") and self._has_full_rows())
+
+    def _has_full_rows(self) -> bool:
+        """False for a float8_e4m3fn collection without a re-scoring plane (MMRAG_F8_RESCORE=none): mmr and hybrid
+        queries read full-precision rows"""
+        c = self.collection
+        return not (getattr(c, "is_f8", False) and getattr(c, "plane", None) is None)
 
     def _answer_hybrid(self, text: str, n_results: int, filter_dict: Optional[Dict]) -> Dict[str, Any]:
         """blocking, one worker thread: cached or fresh embedding, then ONE collection.hybrid_query"""
@@ -359,7 +365,7 @@ class EmbeddingManager:
     def supports_mmr(self) -> bool:
         """True when the collection can answer mmr_query (a single-GPU VectorIndex; not the sharded serving path, whose
         candidates' rows live on different GPUs)"""
-        return self.collection is None or hasattr(self.collection, "mmr_query")
+        return self.collection is None or (hasattr(self.collection, "mmr_query") and self._has_full_rows())
 
     def _answer_mmr(self, texts: Sequence[str], n_results: int, filter_dict: Optional[Dict], fetch_k: Optional[int],
                     lambda_mult: Optional[float]) -> List[Dict[str, Any]]:
@@ -539,6 +545,9 @@ class EmbeddingManager:
         except Exception as e:
             logger.error("Failed to get collection stats: %s", e)
             return {"name": settings.CHROMA_COLLECTION_NAME, "count": 0, "error": str(e)}
+        if hasattr(self.collection, "bytes_per_row"):   # a VectorIndex: how its rows are stored
+            report["index_dtype"] = str(self.collection.dtype).split(".")[-1]
+            report["bytes_per_row"] = self.collection.bytes_per_row()
         if self.cache:
             report["cache"] = self.cache.get_stats()
         return report

@@ -82,9 +82,7 @@ class HipEngine:
     def new_collection(self, name: str, metadata: Optional[Dict[str, Any]] = None):
         from .index import VectorIndex
 
-        dtype = {"float16": self._torch.float16, "float32": self._torch.float32,
-                 "bfloat16": self._torch.bfloat16}[settings.MMRAG_INDEX_DTYPE]
-        return VectorIndex(self.dim, dtype=dtype, device=self.device, name=name, metadata=metadata)
+        return VectorIndex(self.dim, dtype=settings.index_dtype(), device=self.device, name=name, metadata=metadata)
 
     def release(self):
         self._torch.cuda.empty_cache()
@@ -150,9 +148,7 @@ class ClipEngine:
     def new_collection(self, name: str, metadata: Optional[Dict[str, Any]] = None):
         from .index import VectorIndex
 
-        dtype = {"float16": self._torch.float16, "float32": self._torch.float32,
-                 "bfloat16": self._torch.bfloat16}[settings.MMRAG_INDEX_DTYPE]
-        return VectorIndex(self.dim, dtype=dtype, device=self.device, name=name, metadata=metadata)
+        return VectorIndex(self.dim, dtype=settings.index_dtype(), device=self.device, name=name, metadata=metadata)
 
     def release(self):
         self._torch.cuda.empty_cache()

@@ -156,16 +156,37 @@ class VectorIndex:
 
     Vectors must be unit-norm (cosine = inner product of unit vectors; `distance = 1 - cos`).  The encoders of this
     package normalise; `add` / `query` reject rows whose norm is off by more than 1e-2 instead of silently ranking
-    by raw inner product (Chroma's cosine space would have normalised them)."""
+    by raw inner product (Chroma's cosine space would have normalised them).
+
+    FP8 collections (`dtype=torch.float8_e4m3fn`, include/mmrag.h MMRAG_F8E4M3): the matrix holds one-byte E4M3 codes
+    (a float8_e4m3fn tensor; torch only allocates, copies and zeroes it, through its uint8 view) and is the SCAN plane (csrc/search_f8.hip).  FP8 alone does not rank well enough, so with
+    a `rescore_dtype` (default float16; config MMRAG_F8_RESCORE) the index keeps a full-precision plane of the same
+    rows next to it -- appended, tombstoned and compacted together -- and a search over-fetches
+    C = min(max(20, MMRAG_F8_OVERSAMPLE * k), 4096) candidates from the scan plane and re-scores them exactly on that
+    plane (csrc/rescore.hip), so scores and `distances` read like an fp16 collection's.  That mode costs 1.5x the
+    memory of an fp16 collection: it buys scan time, not capacity.  `rescore_dtype=None` is the capacity mode (0.5x):
+    searches return the quantised collection's own scores, and mmr / hybrid queries are refused."""
 
     COMPACT_DEAD_FRACTION = 0.25
     COMPACT_MIN_DEAD = 4096
 
     def __init__(self, dim: int, dtype: torch.dtype = torch.float16, device: str = "cuda:0",
                  capacity: int = 4096, name: str = "multimodal_rag",
-                 metadata: Optional[Dict[str, Any]] = None):
-        if dtype not in (torch.float16, torch.float32, torch.bfloat16):
+                 metadata: Optional[Dict[str, Any]] = None, rescore_dtype: Any = "default"):
+        if dtype not in (torch.float16, torch.float32, torch.bfloat16, torch.float8_e4m3fn):
             raise ValueError(f"unsupported storage dtype {dtype}")
+        from .config import settings
+
+        self.is_f8 = dtype == torch.float8_e4m3fn
+        if not self.is_f8:
+            if rescore_dtype not in ("default", None):
+                raise ValueError("rescore_dtype applies to float8_e4m3fn collections only")
+            rescore_dtype = None
+        elif isinstance(rescore_dtype, str) and rescore_dtype == "default":
+            rescore_dtype = settings.f8_rescore_dtype()
+        if rescore_dtype not in (None, torch.float16, torch.float32, torch.bfloat16):
+            raise ValueError(f"unsupported rescore dtype {rescore_dtype}")
+        self.rescore_dtype: Optional[torch.dtype] = rescore_dtype
         _native.lib()  # fail loudly if the HIP library is absent
         self.name = name
         self.metadata = dict(metadata or {})
@@ -174,7 +195,11 @@ class VectorIndex:
         self.device = torch.device(device)
         self.ld = _native.padded_dim(self.dim, dtype)
         cap = max(int(capacity), 256)
-        self._matrix = torch.zeros((cap, self.ld), dtype=dtype, device=self.device)
+        self._matrix = self._new_rows(cap, zero=True)
+        self.plane_ld = _native.padded_dim(self.dim, rescore_dtype) if rescore_dtype is not None else 0
+        self._plane: Optional[torch.Tensor] = None     # FP8 collections: full-precision rows for the exact re-scoring
+        if rescore_dtype is not None:
+            self._plane = torch.zeros((cap, self.plane_ld), dtype=rescore_dtype, device=self.device)
         self._alive_dev = torch.zeros(self._n_words(cap), dtype=torch.int32, device=self.device)
         self._alive_host = np.zeros(self._n_words(cap), dtype=np.uint32)
         self._n = 0            # rows in use (alive + dead)
@@ -188,9 +213,18 @@ class VectorIndex:
         self._search_ws: Optional[torch.Tensor] = None    # candidate-list workspace of the search kernels, reused
         self._deep_ws: Optional[torch.Tensor] = None      # workspace of the deep search (n_results > 20), reused
         self._lex = None   # lexical.LexicalIndex once enable_lexical() ran (lazily: first lexical / hybrid query)
-        from .config import settings
-
         self.f32_exact = bool(settings.MMRAG_F32_EXACT_SEARCH)   # float32 collections only (see config.py)
+
+    def _new_rows(self, rows: int, zero: bool) -> torch.Tensor:
+        """[rows, ld] in the storage dtype; FP8 codes are allocated as bytes and viewed as float8_e4m3fn"""
+        make = torch.zeros if zero else torch.empty
+        if self.is_f8:
+            return make((rows, self.ld), dtype=torch.uint8, device=self.device).view(torch.float8_e4m3fn)
+        return make((rows, self.ld), dtype=self.dtype, device=self.device)
+
+    def _raw(self, t: torch.Tensor) -> torch.Tensor:
+        """the tensor torch's own copy / fill kernels see: the byte view of FP8 codes, anything else as it is"""
+        return t.view(torch.uint8) if t.dtype == torch.float8_e4m3fn else t
 
     @staticmethod
     def _n_words(rows: int) -> int:
@@ -200,6 +234,25 @@ class VectorIndex:
     @property
     def matrix(self) -> torch.Tensor:
         return self._matrix
+
+    @property
+    def plane(self) -> Optional[torch.Tensor]:
+        """FP8 collections: the full-precision re-scoring plane (None in capacity mode and for every other dtype)"""
+        return self._plane
+
+    @property
+    def _full(self) -> torch.Tensor:
+        """the most precise copy of the rows: what get(embeddings), MMR and the hybrid distances read"""
+        return self._plane if self._plane is not None else self._matrix
+
+    def bytes_per_row(self) -> int:
+        b = self.ld * self._matrix.element_size()
+        return b + (self.plane_ld * self._plane.element_size() if self._plane is not None else 0)
+
+    def _need_plane(self, what: str):
+        if self.is_f8 and self._plane is None:
+            raise ValueError(f"{what} needs full-precision rows: this float8_e4m3fn collection was created with "
+                             f"rescore_dtype=None (MMRAG_F8_RESCORE=none)")
 
     def count(self) -> int:
         return self._n - self._n_dead
@@ -214,10 +267,15 @@ class VectorIndex:
         if rows <= cap:
             return
         new_cap = max(rows, cap * 2)
-        grown = torch.empty((new_cap, self.ld), dtype=self.dtype, device=self.device)
-        grown[: self._n].copy_(self._matrix[: self._n])
-        grown[self._n:].zero_()
+        grown = self._new_rows(new_cap, zero=False)
+        self._raw(grown)[: self._n].copy_(self._raw(self._matrix)[: self._n])
+        self._raw(grown)[self._n:].zero_()
         self._matrix = grown
+        if self._plane is not None:
+            grown = torch.empty((new_cap, self.plane_ld), dtype=self.rescore_dtype, device=self.device)
+            grown[: self._n].copy_(self._plane[: self._n])
+            grown[self._n:].zero_()
+            self._plane = grown
         words = torch.zeros(self._n_words(new_cap), dtype=torch.int32, device=self.device)
         words[: self._alive_dev.numel()].copy_(self._alive_dev)
         self._alive_dev = words
@@ -278,7 +336,13 @@ class VectorIndex:
         qf = self._to_device_f32(q, "query", check_norm)
         if self.dtype == torch.float32 and self.ld == self.dim:
             return qf          # already the stored form: no cast pass (one launch less on the single-query path)
-        packed = torch.empty((qf.shape[0], self.ld), dtype=self.dtype, device=self.device)
+        packed = self._new_rows(qf.shape[0], zero=False)
+        _native.append_rows(packed, 0, qf, self.dim)
+        return packed
+
+    def _pack_plane_queries(self, qf: torch.Tensor) -> torch.Tensor:
+        """float32 [B, d] on the device -> the re-scoring plane's dtype and padded width"""
+        packed = torch.empty((qf.shape[0], self.plane_ld), dtype=self.rescore_dtype, device=self.device)
         _native.append_rows(packed, 0, qf, self.dim)
         return packed
 
@@ -310,6 +374,8 @@ class VectorIndex:
                 emb = emb[torch.tensor(keep, device=self.device)].contiguous()
             self._reserve(self._n + len(keep))
             _native.append_rows(self._matrix, self._n, emb, self.dim)
+            if self._plane is not None:
+                _native.append_rows(self._plane, self._n, emb, self.dim)
             for j, i in enumerate(keep):
                 self._row_of[ids[i]] = self._n + j
                 self._ids.append(ids[i])
@@ -322,12 +388,21 @@ class VectorIndex:
             self._n += len(keep)
             self._grown(len(keep))
 
-    def add_rows_device(self, rows_packed: torch.Tensor, documents, metadatas, ids):
-        """Append rows that are already in storage layout [m, ld] (bulk loads, benchmarks)."""
+    def add_rows_device(self, rows_packed: torch.Tensor, documents, metadatas, ids,
+                        plane_rows: Optional[torch.Tensor] = None):
+        """Append rows that are already in storage layout [m, ld] (bulk loads, benchmarks).  FP8 collections take the
+        E4M3 codes (uint8 or float8_e4m3fn) and, when they keep a re-scoring plane, the same rows in the plane's layout
+        [m, plane_ld] as `plane_rows`."""
         m = rows_packed.shape[0]
+        if self.is_f8 and rows_packed.dtype not in (torch.uint8, torch.float8_e4m3fn):
+            raise ValueError("a float8_e4m3fn collection takes E4M3 codes (uint8 or float8_e4m3fn)")
+        if (self._plane is None) != (plane_rows is None) or (plane_rows is not None and plane_rows.shape[0] != m):
+            raise ValueError("plane_rows must be given exactly when the collection keeps a re-scoring plane, one per row")
         with self._lock:
             self._reserve(self._n + m)
-            self._matrix[self._n: self._n + m].copy_(rows_packed)
+            self._raw(self._matrix)[self._n: self._n + m].copy_(self._raw(rows_packed))
+            if plane_rows is not None:
+                self._plane[self._n: self._n + m].copy_(plane_rows)
             for i in range(m):
                 self._row_of[ids[i]] = self._n + i
             self._ids.extend(ids)
@@ -375,8 +450,37 @@ class VectorIndex:
         """enqueue the search (caller holds the lock); returns device tensors, no host sync"""
         if n_results < 1:
             raise ValueError("n_results must be >= 1")
+        if self._plane is not None:
+            return self._launch_search_rescored(query_embeddings, n_results, where, check_norm)
         q = self._pack_queries(query_embeddings, check_norm)
         bits = self._where_bits(where)
+        return self._scan(q, n_results, bits)
+
+    def _launch_search_rescored(self, query_embeddings, n_results: int, where, check_norm: bool):
+        """FP8 collection with a re-scoring plane (caller holds the lock): over-fetch from the scan plane, then the
+        exact scores of those candidates on the full-precision plane and the best n_results of them, same stream"""
+        from .config import settings
+
+        qf = self._to_device_f32(query_embeddings, "query", check_norm)
+        q8 = self._new_rows(qf.shape[0], zero=False)
+        _native.append_rows(q8, 0, qf, self.dim)
+        qp = self._pack_plane_queries(qf)
+        bits = self._where_bits(where)
+        if n_results <= _native.MAX_K_DEEP:
+            C = min(max(_native.MAX_K, int(settings.MMRAG_F8_OVERSAMPLE) * n_results), _native.MAX_K_DEEP)
+            C = max(C, n_results)
+            _, cand = self._scan(q8, C, bits)
+            return _native.rescore_topk(qp, self._plane, self.dim, cand.contiguous(), n_results, packed_out=True)
+        # deeper than one candidate list: the single-query masked-pass loop, over-fetch 1, each pass re-scored (passes
+        # stay in the scan plane's order, each pass ordered by its exact scores)
+        scores, rows = self._scan(q8, n_results, bits)
+        parts = [_native.rescore_topk(qp, self._plane, self.dim, rows[:, i:i + _native.MAX_K].contiguous(),
+                                      min(_native.MAX_K, rows.shape[1] - i))
+                 for i in range(0, rows.shape[1], _native.MAX_K)]
+        return torch.cat([p[0] for p in parts], 1), torch.cat([p[1] for p in parts], 1)
+
+    def _scan(self, q: torch.Tensor, n_results: int, bits):
+        """the search kernels on the stored matrix for packed queries q (caller holds the lock)"""
         if n_results <= _native.MAX_K and self.f32_exact and self.dtype == torch.float32 and q.shape[0] > 64:
             # exact float32 scores whatever the batch size (MMRAG_F32_EXACT_SEARCH): 64 queries per scan keep the exact
             # float32 matrix instruction; bigger batches would take the bf16-split path of csrc/search.hip
@@ -459,7 +563,7 @@ class VectorIndex:
         with self._lock, stage("search"):
             scores, rows = self._launch_search(query_embeddings, n_results, where, check_norm)
             ids_t, docs_t, metas_t = self._ids, self._documents, self._metadatas
-            emb_src = self._matrix if "embeddings" in include else None
+            emb_src = self._full if "embeddings" in include else None
         with stage("collect"):
             return self._collect(scores, rows, include, ids_t, docs_t, metas_t, emb_src)
 
@@ -550,7 +654,7 @@ class VectorIndex:
     def _fetch(self, rows: List[int], matrix: Optional[torch.Tensor] = None) -> List[List[float]]:
         if not rows:
             return []
-        m = self._matrix if matrix is None else matrix
+        m = self._full if matrix is None else matrix
         t = _native.fetch_rows_f32(m, torch.tensor(rows, dtype=torch.int64, device=self.device), self.dim)
         return t.cpu().numpy().tolist()
 
@@ -603,10 +707,16 @@ class VectorIndex:
                 return
             keep = np.nonzero(~self._is_dead(np.arange(self._n, dtype=np.int64)))[0]
             cap = max(256, int(keep.size), self._matrix.shape[0] // 2 if keep.size < self._matrix.shape[0] // 4 else self._matrix.shape[0])
-            dst = torch.zeros((cap, self.ld), dtype=self.dtype, device=self.device)
+            keep_dev = torch.from_numpy(keep).to(self.device)
+            dst = self._new_rows(cap, zero=True)
             if keep.size:
-                _native.gather_rows(dst, self._matrix, torch.from_numpy(keep).to(self.device))
+                _native.gather_rows(dst, self._matrix, keep_dev)
             self._matrix = dst
+            if self._plane is not None:
+                dst = torch.zeros((cap, self.plane_ld), dtype=self.rescore_dtype, device=self.device)
+                if keep.size:
+                    _native.gather_rows(dst, self._plane, keep_dev)
+                self._plane = dst
             self._ids = [self._ids[r] for r in keep]
             self._documents = [self._documents[r] for r in keep]
             self._metadatas = [self._metadatas[r] for r in keep]
@@ -639,6 +749,7 @@ class VectorIndex:
         the lock): device (scores, rows, positions, mmr values) [B, n_results] in pick order, no host sync of its own"""
         from .config import settings
 
+        self._need_plane("mmr_query")
         if n_results < 1:
             raise ValueError("n_results must be >= 1")
         if n_results > _native.MAX_MMR_CANDIDATES:
@@ -649,7 +760,7 @@ class VectorIndex:
         if not 0.0 <= lam <= 1.0:
             raise ValueError(f"lambda_mult must be in [0, 1] (got {lambda_mult!r})")
         scores, rows = self._launch_search(query_embeddings, C, where, check_norm)
-        return _native.mmr_select(self._matrix, self.dim, scores.contiguous(), rows.contiguous(), n_results, lam)
+        return _native.mmr_select(self._full, self.dim, scores.contiguous(), rows.contiguous(), n_results, lam)
 
     def mmr_search(self, query_embeddings, n_results: int, fetch_k: Optional[int] = None,
                    lambda_mult: Optional[float] = None, where: Optional[Dict[str, Any]] = None):
@@ -674,7 +785,7 @@ class VectorIndex:
             scores, rows, _, mmr = self._launch_mmr(query_embeddings, n_results, fetch_k, lambda_mult, where,
                                                     check_norm)
             ids_t, docs_t, metas_t = self._ids, self._documents, self._metadatas
-            emb_src = self._matrix if "embeddings" in include else None
+            emb_src = self._full if "embeddings" in include else None
         with stage("collect"):
             out = self._collect(scores, rows, include, ids_t, docs_t, metas_t, emb_src)
             out["mmr_scores"] = [vals[: len(ids)] for vals, ids in zip(mmr.cpu().tolist(), out["ids"])]
@@ -745,11 +856,18 @@ class VectorIndex:
         from .lexical import rows_dot, rrf_fuse
 
         texts = list(query_texts)
+        self._need_plane("hybrid_query")
         if n_results < 1:
             raise ValueError("n_results must be >= 1")
         C = min(max(n_results, settings.MMRAG_HYBRID_CANDIDATES), _native.MAX_K_DEEP)
         with self._lock:
-            q = self._pack_queries(query_embeddings, check_norm)
+            if self._plane is not None:
+                # converted and norm-checked once: the search below takes the device tensor as it is
+                query_embeddings = self._to_device_f32(query_embeddings, "query", check_norm)
+                check_norm = False
+                q = self._pack_plane_queries(query_embeddings)
+            else:
+                q = self._pack_queries(query_embeddings, check_norm)
             if q.shape[0] != len(texts):
                 raise ValueError(f"{q.shape[0]} query embeddings for {len(texts)} query texts")
             d_scores, d_rows = self._launch_search(query_embeddings, C, where, check_norm)
@@ -767,7 +885,7 @@ class VectorIndex:
                 fused.append((top, dpos, {r: l_s[b][i] for i, r in enumerate(lrow)}))
                 need.extend((b, r) for r, _ in top if r not in dpos)
             if need:
-                dots = rows_dot(q, self._matrix, self.dim, torch.tensor([b for b, _ in need], device=self.device),
+                dots = rows_dot(q, self._full, self.dim, torch.tensor([b for b, _ in need], device=self.device),
                                 torch.tensor([r for _, r in need], device=self.device))
                 extra = dict(zip(need, (1.0 - dots.cpu()).tolist()))
             else:

@@ -1,7 +1,8 @@
 """Restart-ability for the GPU index.
 
-* `save_index` / `load_index`: the shard matrix (.npy, storage dtype as raw uint16/float32) plus the
-  host row tables (JSON).  Files written by this module are read back with `numpy.load(...,
+* `save_index` / `load_index`: the shard matrix (.npy, storage dtype as raw uint16/float32; an FP8 collection's
+  scan plane as raw uint8 codes, its re-scoring plane as plane.npy, both named in the JSON header) plus the host row
+  tables (JSON).  Files written by this module are read back with `numpy.load(...,
   allow_pickle=False)` and `json`.
 * `read_chroma_wal` / `replay_wal`: ingest an existing reference deployment directly from Chroma's
   write-ahead log, the `embeddings_queue` table of `chroma.sqlite3` (schema verified on the
@@ -99,11 +100,23 @@ def save_index(index, directory: str) -> None:
     os.makedirs(directory, exist_ok=True)
     index.compact()   # tombstoned rows are not persisted
     n = index.count()
-    m = index.matrix[:n].cpu()
-    raw = m.view(torch.int16).numpy() if m.dtype in (torch.float16, torch.bfloat16) else m.numpy()
-    np.save(os.path.join(directory, "matrix.npy"), raw, allow_pickle=False)
+    def raw_of(t):
+        if t.dtype == torch.float8_e4m3fn:
+            return t[:n].view(torch.uint8).cpu().numpy()
+        m = t[:n].cpu()
+        return m.view(torch.int16).numpy() if m.dtype in (torch.float16, torch.bfloat16) else m.numpy()
+
+    np.save(os.path.join(directory, "matrix.npy"), raw_of(index.matrix), allow_pickle=False)
+    planes = {}
+    if getattr(index, "is_f8", False):
+        planes["rescore_dtype"] = None
+        if index.plane is not None:
+            np.save(os.path.join(directory, "plane.npy"), raw_of(index.plane), allow_pickle=False)
+            planes = {"rescore_dtype": str(index.rescore_dtype).split(".")[-1], "plane_ld": index.plane_ld,
+                      "plane_file": "plane.npy"}
     with open(os.path.join(directory, "tables.json"), "w", encoding="utf-8") as f:
-        json.dump({"name": index.name, "dim": index.dim, "ld": index.ld, "dtype": str(index.dtype).split(".")[-1],
+        json.dump({**planes,
+                   "name": index.name, "dim": index.dim, "ld": index.ld, "dtype": str(index.dtype).split(".")[-1],
                    "count": n, "metadata": index.metadata, "ids": index._ids, "documents": index._documents,
                    "metadatas": index._metadatas}, f)
 
@@ -117,13 +130,27 @@ def load_index(directory: str, device: str = "cuda:0"):
         t = json.load(f)
     dtype = getattr(torch, t["dtype"])
     raw = np.load(os.path.join(directory, "matrix.npy"), allow_pickle=False)
+    extra = {}
+    if dtype == torch.float8_e4m3fn:
+        extra["rescore_dtype"] = getattr(torch, t["rescore_dtype"]) if t.get("rescore_dtype") else None
     idx = VectorIndex(t["dim"], dtype=dtype, device=device, capacity=max(t["count"], 256), name=t["name"],
-                      metadata=t.get("metadata"))
+                      metadata=t.get("metadata"), **extra)
     rows = torch.from_numpy(raw)
     if dtype in (torch.float16, torch.bfloat16):
         rows = rows.view(dtype)
     if rows.shape != (t["count"], idx.ld):
         raise ValueError(f"matrix shape {tuple(rows.shape)} does not match tables ({t['count']}, {idx.ld})")
+    plane_rows = None
+    if extra.get("rescore_dtype") is not None:
+        plane_rows = torch.from_numpy(np.load(os.path.join(directory, t["plane_file"]), allow_pickle=False))
+        if extra["rescore_dtype"] in (torch.float16, torch.bfloat16):
+            plane_rows = plane_rows.view(extra["rescore_dtype"])
+        if plane_rows.shape != (t["count"], idx.plane_ld):
+            raise ValueError(f"plane shape {tuple(plane_rows.shape)} does not match tables ({t['count']}, {idx.plane_ld})")
+        plane_rows = plane_rows.to(device)
     if t["count"]:
-        idx.add_rows_device(rows.to(device), t["documents"], t["metadatas"], t["ids"])
+        if plane_rows is not None:
+            idx.add_rows_device(rows.to(device), t["documents"], t["metadatas"], t["ids"], plane_rows=plane_rows)
+        else:
+            idx.add_rows_device(rows.to(device), t["documents"], t["metadatas"], t["ids"])
     return idx

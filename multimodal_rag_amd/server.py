@@ -271,12 +271,14 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
                                    and getattr(pipe.embedder, "supports_hybrid", lambda: True)()):
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="Hybrid retrieval is not available with this embedder: it needs a single-GPU "
-                                       "collection with lexical search (EmbeddingManager.hybrid_query)")
+                                       "collection with lexical search (EmbeddingManager.hybrid_query); a float8_e4m3fn "
+                                       "collection also needs its re-scoring plane (MMRAG_F8_RESCORE=float16)")
         if request.mmr and not (hasattr(pipe.embedder, "mmr_query")
                                 and getattr(pipe.embedder, "supports_mmr", lambda: True)()):
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="MMR retrieval is not available with this embedder: it needs a single-GPU "
-                                       "collection (EmbeddingManager.mmr_query)")
+                                       "collection (EmbeddingManager.mmr_query); a float8_e4m3fn collection also needs its "
+                                       "re-scoring plane (MMRAG_F8_RESCORE=float16)")
         if request.mmr:
             out = await pipe.answer(request.query, request.top_k, request.use_multimodal, rerank=request.rerank,
                                     mmr=True, mmr_lambda=request.mmr_lambda)
