@@ -1,5 +1,6 @@
-// Types shared by the two search translation units of libmmrag.so (search.hip: slab-ring kernel for every
-// shape; search_qs.hip: query-stationary kernel for big query batches).  Internal, gfx950 only.
+// Types shared by the search translation units of libmmrag.so (search.hip and search_f8.hip: the slab-ring kernel,
+// one body in slab_ring_body.inc, for every shape; search_qs.hip: query-stationary kernel for big query batches).
+// Internal, gfx950 only.
 #pragma once
 #include "mmrag_internal.h"
 #include "tile_dma.h"
@@ -164,6 +165,7 @@ int qsw_launch(int dtype, int K, int mfma, const KParams &p, int grid_x, int gri
 int deep_filter_launch(int dtype, int WN, const KParams &p, int grid_x, int grid_y, hipStream_t s);
 
 // ---- FP8 collections (search_f8.hip): the slab-ring kernel on the block-scaled FP8 MFMA, dtype MMRAG_F8E4M3 ------------
+// (the body search.hip's kernel has, slab_ring_body.inc, instantiated with DT = MMRAG_F8E4M3)
 // The list search (K = 5 / 10 / 20, the WN plan of search.hip's make_plan; p.thr0 seeds the thresholds) and
 // the filter mode, with the candidate-list and survivor-buffer layouts of the fp16 kernels.  Scores leave scaled by 2^-16.
 int f8_lists_launch(int K, int WN, const KParams &p, int grid_x, int grid_y, hipStream_t s);

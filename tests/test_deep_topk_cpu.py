@@ -5,16 +5,14 @@ filter epilogue).  Adding it must leave every list instantiation that existed be
 it was -- their scores are what the deep search is bit-identical to -- and the filter mode's tile loop must not spill
 (a scratch reload waits vmcnt(0), which drains the LDS-DMA ring)."""
 import ctypes
-import hashlib
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
+import asm_util
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "multimodal_rag_amd", "csrc", "search.hip")
 LIB = os.path.join(ROOT, "multimodal_rag_amd", "lib", "libmmrag.so")
 
 # sha256[:16] of the normalised body (instructions and block labels, comments and directives dropped, block numbers
@@ -104,41 +102,15 @@ def test_deep_workspace_bytes():
     assert ws(256, 1000000, 100) > ws(1, 1000000, 100)
 
 
-def _bodies(asm: str):
-    out, name, cur = {}, None, None
-    for line in asm.splitlines():
-        m = re.match(r"^(_Z\w+):", line)
-        if m:
-            name, cur = m.group(1), []
-            continue
-        if cur is None:
-            continue
-        if line.startswith(".Lfunc_end"):
-            out[name] = cur
-            name, cur = None, None
-            continue
-        t = line.split(";")[0].strip()
-        if re.match(r"^\.LBB\d+_\d+:", t) or (t and not t.startswith(".")):
-            cur.append(re.sub(r"\.LBB\d+_", ".LBB_", t))
-    return out
-
-
 @pytest.fixture(scope="module")
 def search_asm(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("asm") / "search.s")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-I",
-                        os.path.join(ROOT, "include"), SRC, "-o", out], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return _bodies(open(out).read())
+    return asm_util.bodies(asm_util.compile_asm("search.hip", tmp_path_factory.mktemp("asm")))
 
 
 def test_existing_instantiations_unchanged(search_asm):
     for name, want in BASELINE.items():
         assert name in search_asm, f"{name} no longer compiled"
-        got = hashlib.sha256("\n".join(search_asm[name]).encode()).hexdigest()[:16]
+        got = asm_util.body_hash(search_asm[name])
         assert got == want, f"{name}: instructions changed"
 
 
@@ -148,12 +120,7 @@ def test_filter_mode_tile_loop_has_no_spills(search_asm):
     for name, lines in filt.items():
         mfma = [i for i, l in enumerate(lines) if "v_mfma_f32" in l]
         assert mfma, name
-        labels = {m.group(1): i for i, l in enumerate(lines) if (m := re.match(r"^(\.LBB_\d+):", l))}
-        back = [(i, labels[m.group(1)]) for i, l in enumerate(lines)
-                if i > mfma[-1] and (m := re.search(r"s_c?branch\w*\s+(\.LBB_\d+)", l)) and m.group(1) in labels
-                and labels[m.group(1)] < mfma[0]]
-        assert back, f"{name}: tile loop not found"
-        end, start = back[-1]
+        start, end = asm_util.tile_loop(name, lines, mfma)
         for l in lines[start:end + 1]:
             assert "scratch_" not in l, f"{name}: spill access inside the tile loop: {l}"
         assert sum("global_atomic_add" in l for l in lines) == 1, name   # one returning atomic per lane per tile

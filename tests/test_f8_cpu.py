@@ -2,17 +2,15 @@
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import asm_util
 import f8_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "multimodal_rag_amd", "csrc", "search_f8.hip")
 LIB = os.path.join(ROOT, "multimodal_rag_amd", "lib", "libmmrag.so")
 EINVAL = 1
 
@@ -97,35 +95,32 @@ def test_index_rejects_bad_rescore_dtype_and_settings():
     assert int(Settings().MMRAG_F8_OVERSAMPLE) == int(os.getenv("MMRAG_F8_OVERSAMPLE", "4"))
 
 
-def _bodies(asm: str):
-    out, name, cur = {}, None, None
-    for line in asm.splitlines():
-        m = re.match(r"^(_Z\w+):", line)
-        if m:
-            name, cur = m.group(1), []
-            continue
-        if cur is None:
-            continue
-        if line.startswith(".Lfunc_end"):
-            out[name] = cur
-            name, cur = None, None
-            continue
-        t = line.split(";")[0].strip()
-        if re.match(r"^\.LBB\d+_\d+:", t) or (t and not t.startswith(".")):
-            cur.append(re.sub(r"\.LBB\d+_", ".LBB_", t))
-    return out
-
-
 @pytest.fixture(scope="module")
 def f8_asm(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("asm") / "search_f8.s")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-I",
-                        os.path.join(ROOT, "include"), SRC, "-o", out], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return _bodies(open(out).read())
+    return asm_util.bodies(asm_util.compile_asm("search_f8.hip", tmp_path_factory.mktemp("asm")))
+
+
+# sha256[:16] of the normalised body (asm_util.bodies, as test_deep_topk_cpu.py::BASELINE) of every function
+# search_f8.hip compiled to while the kernel was still its own copy, before its body moved to slab_ring_body.inc
+_F8_KERNEL = "_ZN10mmrag_impl12_GLOBAL__N_121cosine_topk_f8_kernelILi%dELi%dELi3EEEvNS_7KParamsE"
+F8_BASELINE = {
+    _F8_KERNEL % (2, 0): "d00faabe98f07dd7",
+    _F8_KERNEL % (2, 5): "b65e18344c1b22e0",
+    _F8_KERNEL % (2, 10): "8e937fb9a918ee51",
+    _F8_KERNEL % (2, 20): "371d4f009efe0276",
+    _F8_KERNEL % (4, 0): "5925728c63071711",
+    _F8_KERNEL % (4, 5): "a5baf65221c1cb7f",
+    _F8_KERNEL % (4, 10): "c710f3c1c6088642",
+    _F8_KERNEL % (4, 20): "a6a388c0d3d9af19",
+    "_ZN10mmrag_impl12_GLOBAL__N_126fill_f8_lists_empty_kernelEPfPiiiiii": "06420a1d94009280",
+}
+
+
+def test_f8_instantiations_unchanged(f8_asm):
+    """the body is shared with search.hip's kernel: a change there that disturbs an FP8 instruction stream fails here"""
+    for name, want in F8_BASELINE.items():
+        assert name in f8_asm, f"{name} no longer compiled"
+        assert asm_util.body_hash(f8_asm[name]) == want, f"{name}: instructions changed"
 
 
 def test_f8_tile_loops(f8_asm):
@@ -139,15 +134,10 @@ def test_f8_tile_loops(f8_asm):
         mfma = [i for i, l in enumerate(lines) if "v_mfma_scale_f32_32x32x64_f8f6f4" in l]
         assert mfma, name
         assert not any(re.search(r"v_mfma_f32_\d+x\d+x\d+_(f16|bf16|fp8)", l) for l in lines), name
-        labels = {m.group(1): i for i, l in enumerate(lines) if (m := re.match(r"^(\.LBB_\d+):", l))}
-        back = [(i, labels[m.group(1)]) for i, l in enumerate(lines)
-                if i > mfma[-1] and (m := re.search(r"s_c?branch\w*\s+(\.LBB_\d+)", l)) and m.group(1) in labels
-                and labels[m.group(1)] < mfma[0]]
-        assert back, f"{name}: tile loop not found"
-        end, start = back[-1]
+        start, end = asm_util.tile_loop(name, lines, mfma)
         for l in lines[start:end + 1]:
             assert "scratch_" not in l, f"{name}: spill access inside the tile loop: {l}"
-        # the wait between the tile's last MFMA and the epilogue (csrc/search_f8.hip: a stop-gap for a suspected
+        # the wait between the tile's last MFMA and the epilogue (csrc/slab_ring_body.inc: a stop-gap for a suspected
         # wait-state shortfall of the compiler): an s_sleep follows the last MFMA with nothing but scalar instructions
         # and labels in between, so no accumulator register is read before it
         sleeps = [i for i in range(start, end + 1) if re.match(r"s_sleep\s+1\b", lines[i])]

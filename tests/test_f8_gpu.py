@@ -115,7 +115,7 @@ def test_exact_data_deep_bit_for_bit(B, n, d, k):
 def test_exact_data_bounded_deep_two_block_waves(B, n, d, k):
     """the bounded path (n above the candidate capacity: few scores pass the filter) on the 64-query plan, whose waves
     own two row blocks: the filter epilogue reads the last block's last accumulator register right after the last
-    MFMA, and lost that row before the kernel waited for the instruction to drain (csrc/search_f8.hip)"""
+    MFMA, and lost that row before the kernel waited for the instruction to drain (csrc/slab_ring_body.inc)"""
     test_exact_data_deep_bit_for_bit(B, n, d, k)
 
 

@@ -7,15 +7,9 @@ flight.  Two things the compiler can do there cost far more than they look:
   * shuffling the stationary Q fragments between the accumulator file and arch VGPRs (`v_accvgpr_*`) every k-step.
 Both have happened after innocent-looking source edits, with correct results and a 10-30 % slower kernel, so the
 assembly is checked."""
-import os
 import re
-import shutil
-import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "multimodal_rag_amd", "csrc", "search_qs.hip")
+import asm_util
 
 
 def _kernels(asm: str):
@@ -32,25 +26,12 @@ def _kernels(asm: str):
 
 
 def test_tile_loop_has_no_spills_and_no_accvgpr_traffic(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path / "search_qs.s")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-I",
-                        os.path.join(ROOT, "include"), SRC, "-o", out], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
     seen = 0
-    for name, lines in _kernels(open(out).read()):
+    for name, lines in _kernels(asm_util.compile_asm("search_qs.hip", tmp_path)):
         seen += 1
         mfma = [i for i, l in enumerate(lines) if "v_mfma_f32" in l]
         assert mfma, name
-        labels = {m.group(1): i for i, l in enumerate(lines) if (m := re.match(r"^(\.LBB\d+_\d+):", l))}
-        # the tile loop: the last backward branch after the last MFMA whose target sits before the first MFMA
-        back = [(i, labels[m.group(1)]) for i, l in enumerate(lines)
-                if i > mfma[-1] and (m := re.search(r"s_c?branch\w*\s+(\.LBB\d+_\d+)", l)) and m.group(1) in labels
-                and labels[m.group(1)] < mfma[0]]
-        assert back, f"{name}: tile loop not found"
-        end, start = back[-1]
+        start, end = asm_util.tile_loop(name, lines, mfma, label=r"\.LBB\d+_\d+")   # raw, not normalised, lines
         body = lines[start:end + 1]
         in_k_steps = lines[mfma[0]:mfma[-1] + 1]
         assert sum("v_mfma_f32" in l for l in body) % 192 in (0, 96, 128), name      # one copy of the unrolled tile
@@ -78,15 +59,7 @@ def test_walk_kernel_tile_loop(tmp_path):
     register: the returning atomic of the dynamic tile hand-out is inline asm (hipcc would wait vmcnt(0) for a
     builtin's result at once), its value lands in the register some time during the tile and is read only by the asm
     store at the tile's end -- nothing may write or move that register in between."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path / "search_qsw.s")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-I",
-                        os.path.join(ROOT, "include"), os.path.join(ROOT, "multimodal_rag_amd", "csrc", "search_qsw.hip"),
-                        "-o", out], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    asm = open(out).read()
+    asm = asm_util.compile_asm("search_qsw.hip", tmp_path)
     kernels = re.findall(r"^(_ZN10mmrag_impl23cosine_topk_walk_kernel\w+):[^\n]*\n(.*?)s_endpgm", asm, re.S | re.M)
     assert len(kernels) >= 12          # 2 dtypes x 3 row lengths x 2 cache policies
     for name, body in kernels:
@@ -112,15 +85,7 @@ def test_persistent_linear_kernel_has_no_scratch(tmp_path):
     """csrc/encoder.hip, linear_persistent_kernel: its K loop carries 128 accumulator registers and two fragment sets
     with an LDS-DMA ring in flight; a spill reload inside it waits vmcnt(0) and stalls the ring (seen with 16 waves of
     128 registers: +15 %).  The 8-wave form must compile without any scratch."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path / "encoder.s")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-I",
-                        os.path.join(ROOT, "include"), os.path.join(ROOT, "multimodal_rag_amd", "csrc", "encoder.hip"),
-                        "-o", out], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    asm = open(out).read()
+    asm = asm_util.compile_asm("encoder.hip", tmp_path)
     body = re.search(r"^(_ZN10mmrag_impl24linear_persistent_kernel\w+):[^\n]*\n(.*?)s_endpgm", asm, re.S | re.M)
     assert body, "linear_persistent_kernel not found"
     assert "scratch_" not in body.group(2)
