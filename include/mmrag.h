@@ -371,6 +371,47 @@ int mmrag_mmr_select(const void *corpus, int64_t ld, int dtype, int d, const flo
                      const int64_t *cand_rows, int B, int C, int k, float lambda, float *out_scores, int64_t *out_rows,
                      int32_t *out_pos, float *out_mmr, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Grouping of search hits by a per-row key ("group by" / "collapse" of comparable vector stores): the first n_groups
+ * groups of a query's candidate list with up to group_size members each -- the top documents and the best passages of
+ * each, where the rows are chunks and the key is their document.  The reference has no counterpart: it ranks chunks.
+ * One launch, one workgroup per query, no workspace, no host synchronisation (the call can be captured into a graph),
+ * no float atomics; identical bits run to run, and the same result whatever else is in the batch.
+ *
+ * Definition.  For one query, take its candidate list c_0 .. c_{C-1} exactly as search() returns it: score descending,
+ * ties to the lower row.  The list ends at the first row < 0.
+ *   Group key
+ *   - Each candidate row has a group ordinal g = group_of_row[row], an int32.
+ *   - g < 0, or a row >= n_rows, means the row has no key.  Such a row is a group of its own, reported as ordinal -1.
+ *     It never merges with another row, and nothing read is out of bounds.
+ *   Group order
+ *   - Groups are ranked by first appearance in the list.
+ *   - A group is therefore ranked by its best member's score, with ties to the lower row.
+ *   Members
+ *   - A group's members are its candidates in list order.
+ *   - Only the first group_size (S) are kept.
+ *   Output
+ *   - The output is the first n_groups (G) groups.
+ *   - Per query it holds:
+ *       out_scores [G,S] float32, the input scores copied bit for bit
+ *       out_rows   [G,S] int64
+ *       out_pos    [G,S] int32, the position in the candidate list
+ *       out_group  [G]   int32
+ *       out_info   [2]   int32 = (groups found, capped at G; valid candidates)
+ *   - Unused slots hold (-inf, -1, -1), and -2 in out_group.
+ * Nothing here is floating-point arithmetic: the result is exact.
+ *
+ *   scores  dev [B, C] float32      rows  dev [B, C] int64      group_of_row  dev [n_rows] int32 (NULL only with n_rows 0)
+ *   out_scores, out_rows, out_pos  dev [B, G, S]      out_group  dev [B, G]      out_info  dev [B, 2]
+ * MMRAG_EINVAL unless B >= 1, 1 <= C <= MMRAG_MAX_GROUP_CANDIDATES, 1 <= n_groups <= MMRAG_MAX_GROUPS,
+ * 1 <= group_size <= MMRAG_MAX_GROUP_SIZE and n_rows >= 0; arguments are checked before any HIP call. */
+#define MMRAG_MAX_GROUP_CANDIDATES 4096
+#define MMRAG_MAX_GROUPS 256
+#define MMRAG_MAX_GROUP_SIZE 16
+int mmrag_group_select(const float *scores, const int64_t *rows, int B, int C, const int32_t *group_of_row,
+                       int64_t n_rows, int n_groups, int group_size, float *out_scores, int64_t *out_rows,
+                       int32_t *out_pos, int32_t *out_group, int32_t *out_info, void *stream);
+
 /* CLIP byte-level BPE (the text tower's tokenizer, BASELINE config 4; the reference only names CLIP in config.py:106).
  * Host code, multi-threaded; equals multimodal_rag_amd/tokenizer.py:ClipBpeTokenizer, which tests pin to
  * transformers.CLIPTokenizer.  The caller passes text already NFC-normalised, whitespace-collapsed and lower-cased.

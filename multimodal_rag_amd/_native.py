@@ -22,6 +22,8 @@ MAX_K = 20
 MAX_K_DEEP = 4096   # mmrag_cosine_topk_deep
 MAX_MMR_CANDIDATES = 1024   # mmrag_mmr_select (MMRAG_MAX_MMR_CANDIDATES)
 MAX_RESCORE_CANDIDATES = 4096   # mmrag_rescore_topk (MMRAG_MAX_RESCORE_CANDIDATES)
+# mmrag_group_select (MMRAG_MAX_GROUP_CANDIDATES, MMRAG_MAX_GROUPS, MMRAG_MAX_GROUP_SIZE)
+MAX_GROUP_CANDIDATES, MAX_GROUPS, MAX_GROUP_SIZE = 4096, 256, 16
 _DT2TORCH = {F32: torch.float32, F16: torch.float16, BF16: torch.bfloat16, F8E4M3: torch.float8_e4m3fn}
 _TORCH2DT = {v: k for k, v in _DT2TORCH.items()}
 
@@ -187,6 +189,10 @@ def _declare(lib):
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.mmrag_internal_mmr_select_ex.restype = c_int
     lib.mmrag_internal_mmr_select_ex.argtypes = lib.mmrag_mmr_select.argtypes + [ctypes.c_uint]
+    # grouping of hits by a per-row key (csrc/group.hip)
+    lib.mmrag_group_select.restype = c_int
+    lib.mmrag_group_select.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     from .lexical import declare as declare_lexical   # BM25 analyzer, device index and search (csrc/lexical.hip)
 
     declare_lexical(lib)
@@ -392,6 +398,41 @@ def mmr_select(corpus: torch.Tensor, d: int, cand_scores: torch.Tensor, cand_row
                                                 out_p.data_ptr(), out_v.data_ptr(), None, 0, _stream_ptr(dev), int(dbg))
     _check(st, "mmrag_mmr_select")
     return out_s, out_r, out_p, out_v
+
+
+def group_select(scores: torch.Tensor, rows: torch.Tensor, group_of_row: torch.Tensor, n_rows: int, n_groups: int,
+                 group_size: int):
+    """Group each query's candidates by group_of_row[row] (include/mmrag.h mmrag_group_select): scores [B, C] float32
+    and rows [B, C] int64 in the search's order, (-inf, -1) padded tails allowed; group_of_row [>= n_rows] int32.
+    Returns device tensors (scores [B, G, S] float32 = the input's bits, rows [B, G, S] int64, positions [B, G, S]
+    int32, group ordinals [B, G] int32, info [B, 2] int32 = (groups found, valid candidates)), unused slots
+    (-inf, -1, -1) and -2.  One launch on the current stream, no host sync."""
+    _dev_check(scores, rows, group_of_row)
+    if (scores.dim() != 2 or scores.shape != rows.shape or scores.dtype != torch.float32 or rows.dtype != torch.int64
+            or not scores.is_contiguous() or not rows.is_contiguous()):
+        raise MMRagNativeError("group_select: scores [B, C] float32 and rows [B, C] int64 must be contiguous and of "
+                               "one shape")
+    if group_of_row.dim() != 1 or group_of_row.dtype != torch.int32 or not group_of_row.is_contiguous():
+        raise MMRagNativeError("group_select: group_of_row must be a contiguous 1-D int32 tensor")
+    if rows.device != scores.device or group_of_row.device != scores.device:
+        raise MMRagNativeError("group_select: candidates and group_of_row must be on one device")
+    n_rows, G, S = int(n_rows), int(n_groups), int(group_size)
+    if n_rows > group_of_row.numel():
+        raise MMRagNativeError(f"group_select: n_rows={n_rows} but group_of_row holds {group_of_row.numel()} entries")
+    B, C = scores.shape
+    dev = scores.device
+    shape = (B, max(G, 0), max(S, 0))
+    out_s = torch.empty(shape, dtype=torch.float32, device=dev)
+    out_r = torch.empty(shape, dtype=torch.int64, device=dev)
+    out_p = torch.empty(shape, dtype=torch.int32, device=dev)
+    out_g = torch.empty(shape[:2], dtype=torch.int32, device=dev)
+    out_i = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        st = lib().mmrag_group_select(scores.data_ptr(), rows.data_ptr(), B, C, group_of_row.data_ptr(), n_rows, G, S,
+                                      out_s.data_ptr(), out_r.data_ptr(), out_p.data_ptr(), out_g.data_ptr(),
+                                      out_i.data_ptr(), _stream_ptr(dev))
+    _check(st, "mmrag_group_select")
+    return out_s, out_r, out_p, out_g, out_i
 
 
 def device_info() -> dict:

@@ -85,6 +85,10 @@ class Settings:
     # picks so far; lambda = 1 is the plain dense order, 0 pure diversity
     MMRAG_MMR_CANDIDATES: int = field(default_factory=lambda: int(os.getenv("MMRAG_MMR_CANDIDATES", "50")))
     MMRAG_MMR_LAMBDA: float = field(default_factory=lambda: float(os.getenv("MMRAG_MMR_LAMBDA", "0.5")))
+    # grouping hits by document (VectorIndex.grouped_query, csrc/group.hip): the first pass groups
+    # min(max(MMRAG_GROUP_CANDIDATES, 4 * n_groups * group_size), 4096) dense hits; queries that neither found
+    # n_groups groups nor exhausted their list are searched again 4 x deeper, up to 4096
+    MMRAG_GROUP_CANDIDATES: int = field(default_factory=lambda: int(os.getenv("MMRAG_GROUP_CANDIDATES", "64")))
     # CLIP engines only: embed image items from their pixels (vision tower) instead of their summary text
     MMRAG_EMBED_IMAGE_PIXELS: bool = field(default_factory=lambda: _b("MMRAG_EMBED_IMAGE_PIXELS", "true"))
 

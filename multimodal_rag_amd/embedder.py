@@ -428,6 +428,81 @@ class EmbeddingManager:
                     answers[at] = failed(str(e))
         return answers  # type: ignore[return-value]
 
+    def supports_grouping(self) -> bool:
+        """True when the collection can answer grouped_query (a single-GPU VectorIndex; not the sharded serving path,
+        whose rows' group ordinals live with their shards)"""
+        return self.collection is None or hasattr(self.collection, "grouped_query")
+
+    def _answer_grouped(self, texts: Sequence[str], n_groups: int, group_size: int, filter_dict: Optional[Dict],
+                        group_by: str, fetch_k: Optional[int]) -> List[Dict[str, Any]]:
+        """blocking, one worker thread: cached or fresh embeddings (ONE encoder pass for the misses), then ONE
+        collection.grouped_query for all of them (one batched search and one grouping launch per rung of its ladder)"""
+        rows, todo, keys = self._lookup(texts)
+        if todo:
+            self._encode_into(texts, rows, todo, keys)
+        matrix = self._stack(rows, len(todo))
+        res = self.collection.grouped_query(matrix, n_groups=n_groups, group_size=group_size, group_by=group_by,
+                                            fetch_k=fetch_k, where=filter_dict, include=self._INCLUDE)
+        out = []
+        for groups, whole, depth in zip(res["groups"], res["exhaustive"], res["fetch_k"]):
+            hit: Dict[str, Any] = {key: [x for g in groups for x in g[key]] for key in RESULT_KEYS}   # in group order
+            hit.update(groups=groups, exhaustive=whole, fetch_k=depth)
+            out.append(hit)
+        return out
+
+    async def grouped_query(self, query_text: str, n_groups: int = 5, group_size: int = 1,
+                            filter_dict: Optional[Dict] = None, group_by: str = "doc_id",
+                            fetch_k: Optional[int] = None) -> Dict[str, Any]:
+        """Retrieval grouped by document (VectorIndex.grouped_query): the n_groups best values of the metadata key
+        `group_by` and the group_size best hits of each.  One result dict with `groups` (group-rank order; each
+        {"key", "ids", "distances", "metadatas", "documents"}), `exhaustive` and `fetch_k`, plus the keys of query()
+        holding the same hits flattened in group order (so `distances` are not ascending, and
+        MultiVectorRetriever.retrieve_raw_documents(ids) works as it is).  Same empty-query error, embedding cache and
+        query count as query(); it calls the collection directly (no dynamic batching)."""
+        await self._ready()
+        if not query_text or not query_text.strip():
+            raise ValueError("Query text cannot be empty")
+        if not hasattr(self.collection, "grouped_query"):
+            raise ValueError("grouped retrieval needs a single-GPU collection (VectorIndex)")
+        try:
+            hit = (await self._engine_call("Grouped query", self._answer_grouped, [query_text], n_groups, group_size,
+                                           filter_dict, group_by, fetch_k))[0]
+        except Exception as e:
+            logger.error("Grouped query failed: %s", e, exc_info=True)
+            raise
+        self.stats["total_queries"] += 1
+        return hit
+
+    async def batch_grouped_query(self, queries: List[str], n_groups: int = 5, group_size: int = 1,
+                                  filter_dict: Optional[Dict] = None, group_by: str = "doc_id",
+                                  fetch_k: Optional[int] = None) -> List[Dict[str, Any]]:
+        """batch_query's twin for grouped_query: one batched encode and one batched grouped search for all the queries;
+        a query that cannot be answered gets a dict with empty lists and an 'error' message."""
+        await self._ready()
+
+        def failed(why: str) -> Dict[str, Any]:
+            return {**{key: [] for key in RESULT_KEYS}, "groups": [], "exhaustive": False, "fetch_k": 0, "error": why}
+
+        answers: List[Optional[Dict[str, Any]]] = [None] * len(queries)
+        live = [at for at, q in enumerate(queries) if q and q.strip()]
+        for at in set(range(len(queries))) - set(live):
+            answers[at] = failed("Query text cannot be empty")
+        if live:
+            try:
+                if not hasattr(self.collection, "grouped_query"):
+                    raise ValueError("grouped retrieval needs a single-GPU collection (VectorIndex)")
+                hits = await self._engine_call("Batch grouped query", self._answer_grouped,
+                                               [queries[at] for at in live], n_groups, group_size, filter_dict,
+                                               group_by, fetch_k)
+                for at, hit in zip(live, hits):
+                    answers[at] = hit
+                self.stats["total_queries"] += len(live)
+            except Exception as e:
+                logger.error("Batch grouped query failed: %s", e)
+                for at in live:
+                    answers[at] = failed(str(e))
+        return answers  # type: ignore[return-value]
+
     async def batch_query(self, queries: List[str], n_results: int = 5,
                           filter_dict: Optional[Dict] = None) -> List[Dict[str, Any]]:
         """embedder.py:784-832: one result dict per query, input order; a query that cannot be answered gets a dict

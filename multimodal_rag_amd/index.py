@@ -213,6 +213,7 @@ class VectorIndex:
         self._search_ws: Optional[torch.Tensor] = None    # candidate-list workspace of the search kernels, reused
         self._deep_ws: Optional[torch.Tensor] = None      # workspace of the deep search (n_results > 20), reused
         self._lex = None   # lexical.LexicalIndex once enable_lexical() ran (lazily: first lexical / hybrid query)
+        self._groups: Dict[str, Dict[str, Any]] = {}   # metadata key -> group column state once enable_grouping(key) ran
         self.f32_exact = bool(settings.MMRAG_F32_EXACT_SEARCH)   # float32 collections only (see config.py)
 
     def _new_rows(self, rows: int, zero: bool) -> torch.Tensor:
@@ -282,6 +283,10 @@ class VectorIndex:
         host = np.zeros(self._n_words(new_cap), dtype=np.uint32)
         host[: self._alive_host.size] = self._alive_host
         self._alive_host = host
+        for st in self._groups.values():
+            col = torch.full((new_cap,), -1, dtype=torch.int32, device=self.device)
+            col[: self._n].copy_(st["col"][: self._n])
+            st["col"] = col
 
     def _set_alive(self, lo: int, hi: int):
         """mark rows [lo, hi) alive (appends): touch only the words they fall in"""
@@ -385,6 +390,8 @@ class VectorIndex:
             self._set_alive(self._n, self._n + len(keep))
             if self._lex is not None:
                 self._lex.append([documents[i] for i in keep])
+            if self._groups:
+                self._groups_appended(self._n, self._n + len(keep))
             self._n += len(keep)
             self._grown(len(keep))
 
@@ -412,6 +419,8 @@ class VectorIndex:
             self._set_alive(self._n, self._n + m)
             if self._lex is not None:
                 self._lex.append(self._documents[self._n: self._n + m])
+            if self._groups:
+                self._groups_appended(self._n, self._n + m)
             self._n += m
             self._grown(m)
 
@@ -731,6 +740,11 @@ class VectorIndex:
                 self._set_alive(0, self._n)
             if self._lex is not None:
                 self._lex.compact(keep)
+            for st in self._groups.values():      # the same kept rows, in order; ordinals keep their values
+                col = torch.full((cap,), -1, dtype=torch.int32, device=self.device)
+                if keep.size:
+                    col[: keep.size] = st["col"][keep_dev]
+                st["col"] = col
 
     def reset(self):
         with self._lock:
@@ -742,6 +756,7 @@ class VectorIndex:
             self._alive_dev.zero_()
             if self._lex is not None:
                 self._lex.reset()
+            self._groups = {}
 
     # ------------------------------------------------------------------ diversified (MMR) ----
     def _launch_mmr(self, query_embeddings, n_results: int, fetch_k, lambda_mult, where, check_norm: bool = True):
@@ -790,6 +805,152 @@ class VectorIndex:
             out = self._collect(scores, rows, include, ids_t, docs_t, metas_t, emb_src)
             out["mmr_scores"] = [vals[: len(ids)] for vals, ids in zip(mmr.cpu().tolist(), out["ids"])]
             return out
+
+    # ------------------------------------------------------------------ grouped by a metadata key ----
+    def _group_ordinals(self, st: Dict[str, Any], metadatas: Sequence[Dict[str, Any]]) -> torch.Tensor:
+        """group ordinals (host int32) of rows with these metadatas, in row order: distinct values of meta.get(key) are
+        numbered by first appearance; a missing key, None or an unhashable value gives -1 (caller holds the lock)"""
+        key, ordinal, values = st["key"], st["ordinal"], st["values"]
+        out = np.full(len(metadatas), -1, dtype=np.int32)
+        for i, meta in enumerate(metadatas):
+            v = meta.get(key)
+            if v is None:
+                continue
+            try:
+                o = ordinal.get(v)
+                if o is None:
+                    o = ordinal[v] = len(values)
+                    values.append(v)
+            except TypeError:        # unhashable: the row has no key
+                continue
+            out[i] = o
+        return torch.from_numpy(out)
+
+    def enable_grouping(self, key: str = "doc_id") -> Dict[str, Any]:
+        """Build the group column of metadata key `key`: a device int32 [capacity] with each row's group ordinal
+        (distinct values of meta.get(key) numbered by first appearance in row order; -1 where the key is missing, None
+        or unhashable) and the host table ordinal -> value.  From then on add, add_rows_device, capacity growth and
+        compact keep it current; reset drops it; delete needs nothing (dead rows are never candidates).  Until then
+        they do no grouping work.  Runs by itself on the first grouped_search / grouped_query for that key.  The column
+        is derived from the metadata and is not persisted: a loaded collection rebuilds it on first use."""
+        with self._lock:
+            st = self._groups.get(key)
+            if st is None:
+                st = {"key": key, "ordinal": {}, "values": []}
+                col = torch.full((self._matrix.shape[0],), -1, dtype=torch.int32, device=self.device)
+                if self._n:
+                    col[: self._n].copy_(self._group_ordinals(st, self._metadatas[: self._n]))
+                st["col"] = col
+                self._groups[key] = st
+            return st
+
+    def _groups_appended(self, lo: int, hi: int):
+        """rows [lo, hi) were appended to the row tables (caller holds the lock)"""
+        for st in self._groups.values():
+            st["col"][lo:hi].copy_(self._group_ordinals(st, self._metadatas[lo:hi]))
+
+    def _launch_grouped(self, query_embeddings, n_groups: int, group_size: int, group_by: str, fetch_k, where,
+                        check_norm: bool = True):
+        """enqueue the search(es) and the grouping of their hits (caller holds the lock): the five device tensors of
+        _native.group_select for the whole batch, and each query's candidate depth"""
+        from .config import settings
+
+        G, S = int(n_groups), int(group_size)
+        if not 1 <= G <= _native.MAX_GROUPS:
+            raise ValueError(f"n_groups must be in 1..{_native.MAX_GROUPS}")
+        if not 1 <= S <= _native.MAX_GROUP_SIZE:
+            raise ValueError(f"group_size must be in 1..{_native.MAX_GROUP_SIZE}")
+        top = _native.MAX_GROUP_CANDIDATES
+        if fetch_k is None:
+            C = min(max(int(settings.MMRAG_GROUP_CANDIDATES), 4 * G * S), top)
+        else:
+            C = min(max(int(fetch_k), G), top)
+        st = self.enable_grouping(group_by)
+        qf = self._to_device_f32(query_embeddings, "query", check_norm)     # converted and norm-checked once
+
+        def one_pass(q: torch.Tensor, depth: int):
+            scores, rows = self._launch_search(q, depth, where, check_norm=False)
+            return _native.group_select(scores.contiguous(), rows.contiguous(), st["col"], self._n, G, S)
+
+        out = one_pass(qf, C)
+        depths = [C] * qf.shape[0]
+        if fetch_k is None:
+            todo, cur = torch.arange(qf.shape[0]), out
+            while C < top:
+                info = cur[4].cpu()                                          # the rung's host synchronisation
+                todo = todo[(info[:, 0] < G) & (info[:, 1] >= C)]            # neither G groups nor an exhausted list
+                if not todo.numel():
+                    break
+                C = min(4 * C, top)
+                at = todo.to(self.device)
+                cur = one_pass(qf[at].contiguous(), C)
+                for whole, part in zip(out, cur):
+                    whole[at] = part
+                for b in todo.tolist():
+                    depths[b] = C
+        return out, depths
+
+    def grouped_search(self, query_embeddings, n_groups: int, group_size: int = 1, group_by: str = "doc_id",
+                       fetch_k: Optional[int] = None, where: Optional[Dict[str, Any]] = None):
+        """Raw grouped search: the first n_groups groups of each query's dense hits with up to group_size members each,
+        grouped by the metadata key `group_by` (csrc/group.hip, include/mmrag.h mmrag_group_select, where the
+        definition is).  Returns device tensors (scores [B, G, S] float32 = the search's own scores, rows [B, G, S]
+        int64, positions [B, G, S] int32 in the candidate list, group ordinals [B, G] int32 (-1 = a row without the
+        key, a group of its own), info [B, 2] int32 = (groups found, valid candidates)) and the list of each query's
+        candidate depth; unused slots hold (-inf, -1, -1) and -2.  n_groups <= 256, group_size <= 16.
+
+        Candidate depth.  An explicit fetch_k is one pass at that depth, clipped to [n_groups, 4096], with no host
+        synchronisation.  fetch_k=None walks a ladder: the first pass takes
+        C0 = min(max(MMRAG_GROUP_CANDIDATES, 4 * n_groups * group_size), 4096) hits; a query is complete when it found
+        n_groups groups or its list was exhausted (fewer than C valid candidates); the queries that are not are searched
+        again, as a sub-batch, at min(4 * C, 4096), until all are complete or C = 4096.  A query's answer is the pass at
+        which it first became complete, so it is the same alone or inside any batch.  Reading the info block costs ONE
+        HOST SYNCHRONISATION PER RUNG below 4096.
+
+        The candidates are search()'s: tombstones and `where` are honoured, a float8_e4m3fn collection is re-scored on
+        its plane (in capacity mode the scores are the quantised collection's own, as in query())."""
+        with self._lock:
+            out, depths = self._launch_grouped(query_embeddings, n_groups, group_size, group_by, fetch_k, where)
+        return (*out, depths)
+
+    def grouped_query(self, query_embeddings, n_groups: int = 5, group_size: int = 1, group_by: str = "doc_id",
+                      fetch_k: Optional[int] = None, where: Optional[Dict[str, Any]] = None,
+                      include: Sequence[str] = ("metadatas", "documents", "distances"),
+                      check_norm: bool = True) -> Dict[str, Any]:
+        """query() grouped by a metadata key (see grouped_search): the n_groups best documents and the group_size best
+        hits of each.  Returns
+            {"groups": [[{"key": value or None, "ids": [...], "distances": [...], "metadatas": [...],
+                          "documents": [...]}, ...] per query, in group-rank order],
+             "exhaustive": [bool per query], "fetch_k": [int per query]}
+        A group is ranked by its best hit; its hits are in ascending distance.  `key` is None for a row without the
+        key, which is a group of its own.  `fetch_k` is the candidate depth the answer was taken at; `exhaustive` is
+        False where that depth gave neither n_groups groups nor the end of the list (on the ladder: only at 4096), so
+        further groups may exist below it.  Lists an `include` leaves out are None."""
+        G = int(n_groups)
+        with self._lock, stage("search"):
+            out, depths = self._launch_grouped(query_embeddings, n_groups, group_size, group_by, fetch_k, where,
+                                               check_norm)
+            ids_t, docs_t, metas_t = self._ids, self._documents, self._metadatas
+            values = self._groups[group_by]["values"]
+        with stage("collect"):
+            scores_h, rows_h, _, group_h, info_h = (t.cpu() for t in out)
+            dist_l = (1.0 - scores_h).tolist() if "distances" in include else None     # float32 arithmetic, as query()
+            rows_l, group_l, info_l = rows_h.tolist(), group_h.tolist(), info_h.tolist()
+            want_m, want_d = "metadatas" in include, "documents" in include
+            res: Dict[str, Any] = {"groups": [], "exhaustive": [], "fetch_k": depths}
+            for b, (found, valid) in enumerate(info_l):
+                groups = []
+                for gi in range(found):
+                    rows = [r for r in rows_l[b][gi] if r >= 0]                        # unused slots only trail
+                    o = group_l[b][gi]
+                    groups.append({"key": values[o] if o >= 0 else None,
+                                   "ids": [ids_t[r] for r in rows],
+                                   "distances": dist_l[b][gi][: len(rows)] if dist_l is not None else None,
+                                   "metadatas": [dict(metas_t[r]) for r in rows] if want_m else None,
+                                   "documents": [docs_t[r] for r in rows] if want_d else None})
+                res["groups"].append(groups)
+                res["exhaustive"].append(found >= G or valid < depths[b])
+            return res
 
     # ------------------------------------------------------------------ lexical / hybrid ----
     def enable_lexical(self):

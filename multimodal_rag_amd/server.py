@@ -47,6 +47,12 @@ class QueryRequest(BaseModel):  # api.py:161-164
     # diverse hits are re-ranked.  Not combined with `hybrid` yet
     mmr: bool = Field(False)
     mmr_lambda: Optional[float] = Field(None, ge=0.0, le=1.0)
+    # not in the reference: hits grouped by document (EmbeddingManager.grouped_query over the `doc_id` metadata).
+    # `top_k` then counts DOCUMENTS and `per_document` is the number of hits kept of each; every source carries its
+    # `document` and 1-based `document_rank`, sources are in document order.  Not combined with `mmr`, `hybrid` or
+    # `rerank` yet
+    group_by_document: bool = Field(False)
+    per_document: int = Field(1, ge=1, le=16)
 
 
 class QueryResponse(BaseModel):  # api.py:167-170
@@ -134,17 +140,21 @@ class Pipeline:
                 "chunks_processed": stored}
 
     async def answer(self, question: str, top_k: int, multimodal: bool, rerank: bool = False,
-                     hybrid: bool = False, mmr: bool = False, mmr_lambda: Optional[float] = None) -> Optional[dict]:
+                     hybrid: bool = False, mmr: bool = False, mmr_lambda: Optional[float] = None,
+                     group_by_document: bool = False, per_document: int = 1) -> Optional[dict]:
         """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
         max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the cross-encoder's best top_k.  `hybrid`: the hits come from
         dense + BM25 retrieval fused by reciprocal rank.  `mmr`: the hits are a maximal-marginal-relevance selection of
-        the dense candidates (`mmr_lambda`, default MMRAG_MMR_LAMBDA)"""
+        the dense candidates (`mmr_lambda`, default MMRAG_MMR_LAMBDA).  `group_by_document` (alone): the hits are the
+        `per_document` best of each of the top_k best documents, flattened in document order"""
         if mmr:
             search = functools.partial(self.embedder.mmr_query, lambda_mult=mmr_lambda)
         else:
             search = self.embedder.hybrid_query if hybrid else self.embedder.query
         extra = "mmr_scores" if mmr else "hybrid_scores" if hybrid else None   # per-hit column re-ranking carries along
-        if rerank:
+        if group_by_document:
+            hits = await self.embedder.grouped_query(question, n_groups=top_k, group_size=per_document)
+        elif rerank:
             hits = await search(question, n_results=max(top_k, settings.MMRAG_RERANK_CANDIDATES))
             if hits["ids"]:
                 fused = dict(zip(hits["ids"], hits[extra])) if extra else None
@@ -178,6 +188,13 @@ class Pipeline:
         if mmr:
             for src, score in zip(ranked, hits["mmr_scores"]):
                 src["mmr_score"] = score
+        if group_by_document:
+            at = 0
+            for document_rank, group in enumerate(hits["groups"], 1):
+                for src in ranked[at: at + len(group["ids"])]:
+                    src["document"] = group["key"]
+                    src["document_rank"] = document_rank
+                at += len(group["ids"])
         return {"answer": text, "sources": ranked}
 
     async def health(self) -> dict:
@@ -261,12 +278,21 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
     @_as_http_500
     async def query_documents(request: QueryRequest):  # api.py:325-413
         t0 = time.time()
+        if request.group_by_document and (request.mmr or request.hybrid or request.rerank):
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                detail="Grouping by document is not combined with MMR, hybrid retrieval or re-ranking "
+                                       "yet: send `group_by_document` without `mmr`, `hybrid` and `rerank`")
         if request.rerank and not (hasattr(pipe.embedder, "has_reranker") and pipe.embedder.has_reranker()):
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="Re-ranking is not configured: set MMRAG_RERANKER_DIR to a local cross-encoder")
         if request.mmr and request.hybrid:
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="MMR and hybrid retrieval are not combined yet: send `mmr` or `hybrid`, not both")
+        if request.group_by_document and not (hasattr(pipe.embedder, "grouped_query")
+                                              and getattr(pipe.embedder, "supports_grouping", lambda: True)()):
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                detail="Grouping by document is not available with this embedder: it needs a "
+                                       "single-GPU collection (EmbeddingManager.grouped_query)")
         if request.hybrid and not (hasattr(pipe.embedder, "hybrid_query")
                                    and getattr(pipe.embedder, "supports_hybrid", lambda: True)()):
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
@@ -279,7 +305,10 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
                                 detail="MMR retrieval is not available with this embedder: it needs a single-GPU "
                                        "collection (EmbeddingManager.mmr_query); a float8_e4m3fn collection also needs its "
                                        "re-scoring plane (MMRAG_F8_RESCORE=float16)")
-        if request.mmr:
+        if request.group_by_document:
+            out = await pipe.answer(request.query, request.top_k, request.use_multimodal, group_by_document=True,
+                                    per_document=request.per_document)
+        elif request.mmr:
             out = await pipe.answer(request.query, request.top_k, request.use_multimodal, rerank=request.rerank,
                                     mmr=True, mmr_lambda=request.mmr_lambda)
         elif request.hybrid:
