@@ -230,6 +230,32 @@ def _dev_check(*tensors):
             raise MMRagNativeError("libmmrag entry points take device (HIP) tensors only; got a CPU tensor")
 
 
+def _nbytes(t: torch.Tensor) -> int:
+    return t.numel() * t.element_size()
+
+
+def _check_q_rows(who: str, q: torch.Tensor, rows: torch.Tensor, n: Optional[int] = None, other: str = "corpus"):
+    """q [B, ld] against stored rows [capacity, ld] (`other`: what `who` calls them): contiguous 2-D, one dtype, one
+    padded width, and n rows within the capacity"""
+    if q.dim() != 2 or rows.dim() != 2 or not q.is_contiguous() or not rows.is_contiguous():
+        raise MMRagNativeError(f"{who}: q and {other} must be contiguous 2-D tensors")
+    if q.dtype != rows.dtype or q.shape[1] != rows.shape[1]:
+        raise MMRagNativeError(f"{who}: q and {other} must share dtype and padded width")
+    if n is not None and n > rows.shape[0]:
+        raise MMRagNativeError(f"{who}: n={n} exceeds corpus capacity {rows.shape[0]}")
+
+
+def _topk_out(B: int, k: int, device, packed: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(scores [B, k] float32, rows [B, k] int64) to be written by a kernel.  `packed`: both in ONE buffer
+    [rows B*k int64 | scores B*k float32], so a caller that wants both on the host copies once (VectorIndex._collect
+    recognises the pair by its shared `_base`)"""
+    if not packed:
+        return (torch.empty((B, k), dtype=torch.float32, device=device),
+                torch.empty((B, k), dtype=torch.int64, device=device))
+    buf = torch.empty(B * k * 12, dtype=torch.uint8, device=device)
+    return buf[B * k * 8:].view(torch.float32).view(B, k), buf[: B * k * 8].view(torch.int64).view(B, k)
+
+
 def search_uses_query_stationary(B: int, n: int, d: int, k: int, dtype: torch.dtype) -> bool:
     """which kernel a search of this shape runs on (True: a query-stationary kernel, False: the slab-ring cosine_topk_kernel)"""
     return bool(lib().mmrag_internal_search_uses_qs(B, n, padded_dim(d, dtype), _TORCH2DT[dtype], k))
@@ -265,32 +291,21 @@ def cosine_topk(q: torch.Tensor, corpus: torch.Tensor, n: int, d: int, k: int, r
     contiguous, same dtype, same padded leading dimension (pad columns zero).
     """
     _dev_check(q, corpus, alive_bits)
-    if q.dim() != 2 or corpus.dim() != 2 or not q.is_contiguous() or not corpus.is_contiguous():
-        raise MMRagNativeError("cosine_topk: q and corpus must be contiguous 2-D tensors")
-    if q.dtype != corpus.dtype or q.shape[1] != corpus.shape[1]:
-        raise MMRagNativeError("cosine_topk: q and corpus must share dtype and padded width")
-    if n > corpus.shape[0]:
-        raise MMRagNativeError(f"cosine_topk: n={n} exceeds corpus capacity {corpus.shape[0]}")
+    _check_q_rows("cosine_topk", q, corpus, n)
     B, ld = q.shape
     L = lib()
     need = L.mmrag_cosine_topk_workspace_bytes(B, n, k)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
+    if workspace is None or _nbytes(workspace) < need:
         workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
-    if packed_out:   # ONE buffer [rows B*k int64 | scores B*k float32]: a caller that wants both on the host copies once
-        buf = torch.empty(B * k * 12, dtype=torch.uint8, device=q.device)
-        out_r = buf[: B * k * 8].view(torch.int64).view(B, k)
-        out_s = buf[B * k * 8:].view(torch.float32).view(B, k)
-    else:
-        out_s = torch.empty((B, k), dtype=torch.float32, device=q.device)
-        out_r = torch.empty((B, k), dtype=torch.int64, device=q.device)
+    out_s, out_r = _topk_out(B, k, q.device, packed_out)
     if dbg:
         cosine_topk_lists(q, corpus, n, d, k, workspace, alive_bits=alive_bits, dbg=dbg)
         return cosine_topk_select(B, n, k, row_offset, workspace, out_s, out_r)
     with torch.cuda.device(q.device):
         st = L.mmrag_cosine_topk(q.data_ptr(), corpus.data_ptr(), B, n, d, ld, _TORCH2DT[q.dtype], k, row_offset,
                                  alive_bits.data_ptr() if alive_bits is not None else None,
-                                 out_s.data_ptr(), out_r.data_ptr(), workspace.data_ptr(),
-                                 workspace.numel() * workspace.element_size(), _stream_ptr(q.device))
+                                 out_s.data_ptr(), out_r.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
+                                 _stream_ptr(q.device))
     _check(st, "mmrag_cosine_topk")
     return out_s, out_r
 
@@ -306,24 +321,18 @@ def cosine_topk_deep(q: torch.Tensor, corpus: torch.Tensor, n: int, d: int, k: i
     results as cosine_topk, scores bit-identical to it.  Synchronises the current stream once (the survivor counts).
     `dbg` / `cap` (tests only): DEEP_DBG_NO_BOUND, and a candidate capacity smaller than the library's."""
     _dev_check(q, corpus, alive_bits)
-    if q.dim() != 2 or corpus.dim() != 2 or not q.is_contiguous() or not corpus.is_contiguous():
-        raise MMRagNativeError("cosine_topk_deep: q and corpus must be contiguous 2-D tensors")
-    if q.dtype != corpus.dtype or q.shape[1] != corpus.shape[1]:
-        raise MMRagNativeError("cosine_topk_deep: q and corpus must share dtype and padded width")
-    if n > corpus.shape[0]:
-        raise MMRagNativeError(f"cosine_topk_deep: n={n} exceeds corpus capacity {corpus.shape[0]}")
+    _check_q_rows("cosine_topk_deep", q, corpus, n)
     B, ld = q.shape
     L = lib()
     need = cosine_topk_deep_workspace_bytes(B, n, k)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
+    if workspace is None or _nbytes(workspace) < need:
         workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
-    out_s = torch.empty((B, k), dtype=torch.float32, device=q.device)
-    out_r = torch.empty((B, k), dtype=torch.int64, device=q.device)
+    out_s, out_r = _topk_out(B, k, q.device)
     with torch.cuda.device(q.device):
         st = L.mmrag_internal_cosine_topk_deep_ex(
             q.data_ptr(), corpus.data_ptr(), B, n, d, ld, _TORCH2DT[q.dtype], k, row_offset,
             alive_bits.data_ptr() if alive_bits is not None else None, out_s.data_ptr(), out_r.data_ptr(),
-            workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream_ptr(q.device), dbg, cap)
+            workspace.data_ptr(), _nbytes(workspace), _stream_ptr(q.device), dbg, cap)
     _check(st, "mmrag_cosine_topk_deep")
     return out_s, out_r
 
@@ -339,21 +348,12 @@ def rescore_topk(q: torch.Tensor, plane: torch.Tensor, d: int, cand_rows: torch.
     [B, k] int64) ordered by (score desc, row asc), (-inf, -1) padded; scores are mmrag_rows_dot's, bit for bit.  One
     launch on the current stream, no host sync."""
     _dev_check(q, plane, cand_rows)
-    if q.dim() != 2 or plane.dim() != 2 or not q.is_contiguous() or not plane.is_contiguous():
-        raise MMRagNativeError("rescore_topk: q and plane must be contiguous 2-D tensors")
-    if q.dtype != plane.dtype or q.shape[1] != plane.shape[1]:
-        raise MMRagNativeError("rescore_topk: q and plane must share dtype and padded width")
+    _check_q_rows("rescore_topk", q, plane, other="plane")
     if cand_rows.dim() != 2 or cand_rows.dtype != torch.int64 or not cand_rows.is_contiguous() \
             or cand_rows.shape[0] != q.shape[0]:
         raise MMRagNativeError("rescore_topk: cand_rows must be a contiguous [B, C] int64 tensor")
     B, C = cand_rows.shape
-    if packed_out:   # [rows | scores] in one buffer, as cosine_topk(packed_out=True)
-        buf = torch.empty(B * k * 12, dtype=torch.uint8, device=q.device)
-        out_r = buf[: B * k * 8].view(torch.int64).view(B, k)
-        out_s = buf[B * k * 8:].view(torch.float32).view(B, k)
-    else:
-        out_s = torch.empty((B, k), dtype=torch.float32, device=q.device)
-        out_r = torch.empty((B, k), dtype=torch.int64, device=q.device)
+    out_s, out_r = _topk_out(B, k, q.device, packed_out)
     with torch.cuda.device(q.device):
         st = lib().mmrag_rescore_topk(q.data_ptr(), plane.data_ptr(), plane.shape[1], _TORCH2DT[plane.dtype], d,
                                       cand_rows.data_ptr(), B, C, k, out_s.data_ptr(), out_r.data_ptr(),
@@ -504,8 +504,7 @@ def merge_topk(scores: torch.Tensor, rows: torch.Tensor, k: int) -> Tuple[torch.
     G, B, k_in = scores.shape
     scores = scores.contiguous()
     rows = rows.contiguous()
-    out_s = torch.empty((B, k), dtype=torch.float32, device=scores.device)
-    out_r = torch.empty((B, k), dtype=torch.int64, device=scores.device)
+    out_s, out_r = _topk_out(B, k, scores.device)
     with torch.cuda.device(scores.device):
         st = lib().mmrag_merge_topk(scores.data_ptr(), rows.data_ptr(), G, B, k_in, k, out_s.data_ptr(),
                                     out_r.data_ptr(), _stream_ptr(scores.device))
@@ -587,7 +586,7 @@ def cosine_topk_lists(q: torch.Tensor, corpus: torch.Tensor, n: int, d: int, k: 
         st = lib().mmrag_internal_cosine_topk_lists_ex(
             q.data_ptr(), corpus.data_ptr(), B, n, d, ld, _TORCH2DT[q.dtype], k,
             alive_bits.data_ptr() if alive_bits is not None else None, workspace.data_ptr(),
-            workspace.numel() * workspace.element_size(), _stream_ptr(q.device), int(dbg))
+            _nbytes(workspace), _stream_ptr(q.device), int(dbg))
     _check(st, "mmrag_cosine_topk_lists")
 
 
@@ -780,7 +779,7 @@ def encoder_forward(desc: EncoderDesc, weight_ptrs, ids: torch.Tensor, pos_ids: 
     _dev_check(ids, pos_ids, cu_seqlens, sel, workspace, out)
     T, B = ids.numel(), cu_seqlens.numel() - 1
     need = encoder_workspace_bytes(desc, T, B, f32)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
+    if workspace is None or _nbytes(workspace) < need:
         workspace = torch.empty(need, dtype=torch.uint8, device=ids.device)
     if out is None:
         out = torch.empty((B, desc.out_dim), dtype=torch.float32, device=ids.device)
@@ -788,7 +787,7 @@ def encoder_forward(desc: EncoderDesc, weight_ptrs, ids: torch.Tensor, pos_ids: 
     with torch.cuda.device(ids.device):
         st = fn(ctypes.byref(desc), weight_ptrs, ids.data_ptr(), pos_ids.data_ptr(),
                                          cu_seqlens.data_ptr(), _ptr(sel), T, B, max_len, out.data_ptr(),
-                                         workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                         workspace.data_ptr(), _nbytes(workspace),
                                          _stream_ptr(ids.device))
     _check(st, "mmrag_encoder_forward")
     return out
@@ -808,7 +807,7 @@ def cross_encoder_forward(desc: EncoderDesc, weight_ptrs, n_labels: int, ids: to
     _dev_check(ids, type_ids, pos_ids, cu_seqlens, workspace, out)
     T, B = ids.numel(), cu_seqlens.numel() - 1
     need = cross_encoder_workspace_bytes(desc, T, B, f32)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
+    if workspace is None or _nbytes(workspace) < need:
         workspace = torch.empty(need, dtype=torch.uint8, device=ids.device)
     if out is None:
         out = torch.empty((B, n_labels), dtype=torch.float32, device=ids.device)
@@ -816,7 +815,7 @@ def cross_encoder_forward(desc: EncoderDesc, weight_ptrs, n_labels: int, ids: to
     with torch.cuda.device(ids.device):
         st = fn(ctypes.byref(desc), weight_ptrs, n_labels, ids.data_ptr(), type_ids.data_ptr(), pos_ids.data_ptr(),
                 cu_seqlens.data_ptr(), T, B, max_len, out.data_ptr(), workspace.data_ptr(),
-                workspace.numel() * workspace.element_size(), _stream_ptr(ids.device))
+                _nbytes(workspace), _stream_ptr(ids.device))
     _check(st, "mmrag_cross_encoder_forward")
     return out
 
@@ -864,14 +863,14 @@ def vit_forward(desc: EncoderDesc, weight_ptrs, pixels: torch.Tensor, pixel_kind
     B = pixels.shape[0]
     S = (desc.image // desc.patch) ** 2 + 1
     need = encoder_workspace_bytes(desc, B * S, B)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
+    if workspace is None or _nbytes(workspace) < need:
         workspace = torch.empty(need, dtype=torch.uint8, device=pixels.device)
     if out is None:
         out = torch.empty((B, desc.out_dim), dtype=torch.float32, device=pixels.device)
     with torch.cuda.device(pixels.device):
         st = lib().mmrag_vit_forward(ctypes.byref(desc), weight_ptrs, pixels.data_ptr(), pixel_kind,
                                      cu_seqlens.data_ptr(), B, out.data_ptr(), workspace.data_ptr(),
-                                     workspace.numel() * workspace.element_size(), _stream_ptr(pixels.device))
+                                     _nbytes(workspace), _stream_ptr(pixels.device))
     _check(st, "mmrag_vit_forward")
     return out
 
@@ -997,13 +996,13 @@ class SearchPlan:
         if n > corpus.shape[0]:
             raise MMRagNativeError(f"SearchPlan: n={n} exceeds corpus capacity {corpus.shape[0]}")
         need = lib().mmrag_cosine_topk_workspace_bytes(q.shape[0], n, k)
-        if workspace.numel() * workspace.element_size() < need:
+        if _nbytes(workspace) < need:
             raise MMRagNativeError("SearchPlan: workspace too small")
         self._keep = (q, corpus, workspace, alive_bits)
         self.B, self.n, self.k = q.shape[0], n, k
         self._scan_args = (q.data_ptr(), corpus.data_ptr(), q.shape[0], n, d, q.shape[1], _TORCH2DT[q.dtype], k,
                            alive_bits.data_ptr() if alive_bits is not None else None, workspace.data_ptr(),
-                           workspace.numel() * workspace.element_size())
+                           _nbytes(workspace))
         self._ws = workspace.data_ptr()
         self._scan = lib().mmrag_cosine_topk_lists
         self._select = lib().mmrag_cosine_topk_select

@@ -20,6 +20,7 @@ Deliberate differences:
 from __future__ import annotations
 
 import asyncio
+import copy
 import hashlib
 import logging
 import threading
@@ -41,6 +42,14 @@ HYBRID_KEYS = RESULT_KEYS + ("hybrid_scores", "lexical_scores")
 MMR_KEYS = RESULT_KEYS + ("mmr_scores",)
 _HOSTROWS = load_hostrows()
 _COLLECTION_NOTE = {"description": "Multi-modal RAG embeddings"}
+# what a retrieval mode needs of the collection: (method, the error of a collection that lacks it)
+_NEEDS_HYBRID = ("hybrid_query", "hybrid retrieval needs a single-GPU collection (VectorIndex)")
+_NEEDS_MMR = ("mmr_query", "MMR retrieval needs a single-GPU collection (VectorIndex)")
+_NEEDS_GROUPING = ("grouped_query", "grouped retrieval needs a single-GPU collection (VectorIndex)")
+# the answer of a batch's query that could not be answered, before its 'error' (copied for every such query)
+_EMPTY = {key: [] for key in RESULT_KEYS}
+_EMPTY_MMR = {key: [] for key in MMR_KEYS}
+_EMPTY_GROUPED = {**_EMPTY, "groups": [], "exhaustive": False, "fetch_k": 0}
 
 
 class LRUCache(CountingLRU):
@@ -276,10 +285,18 @@ class EmbeddingManager:
             return _HOSTROWS.split(RESULT_KEYS, tuple(cols))
         return [dict(zip(RESULT_KEYS, per_query)) for per_query in zip(*(col[:n] for col in cols))]
 
+    def _embed(self, texts: Sequence[str], looked=None) -> np.ndarray:
+        """blocking: [len(texts), dim] float32, cached rows reused and ONE encoder pass for the misses (`looked`: the
+        _lookup(texts) the caller already made)"""
+        rows, todo, keys = looked or self._lookup(texts)
+        if todo:
+            self._encode_into(texts, rows, todo, keys)
+        return self._stack(rows, len(todo))
+
     def _answer(self, texts: Sequence[str], n_results: int, filter_dict: Optional[Dict]) -> List[Dict[str, Any]]:
         """Blocking, runs in ONE worker thread: cache lookups, ONE encoder pass for the misses, ONE collection.query
         for all of them (embedder.py:566 + :595-601).  One thread hop per request instead of one per stage."""
-        rows, todo, keys = self._lookup(texts)
+        rows, todo, keys = looked = self._lookup(texts)
         if (len(todo) == len(texts) and texts and hasattr(self.text_model, "encode_device")
                 and getattr(self.collection, "accepts_device_queries", False)):
             # nothing cached: the embeddings go from the encoder to the search kernel on the device; the host does not
@@ -293,11 +310,8 @@ class EmbeddingManager:
             self._stack([], len(todo))
             with tracing.stage("split"):
                 return self._split(res, len(texts))
-        if todo:
-            self._encode_into(texts, rows, todo, keys)
-        matrix = self._stack(rows, len(todo))
-        res = self.collection.query(query_embeddings=matrix, n_results=n_results, where=filter_dict,
-                                    include=self._INCLUDE)
+        res = self.collection.query(query_embeddings=self._embed(texts, looked), n_results=n_results,
+                                    where=filter_dict, include=self._INCLUDE)
         return self._split(res, len(texts))
 
     async def _query_with_retry(self, query_embedding: List[float], n_results: int,
@@ -308,20 +322,56 @@ class EmbeddingManager:
                                       where=filter_dict, include=self._INCLUDE)
         return self._split(res, 1)[0]
 
-    async def query(self, query_text: str, n_results: int = 5, filter_dict: Optional[Dict] = None) -> Dict[str, Any]:
-        """embedder.py:539-583."""
+    async def _single(self, label: str, needs, answer, query_text: str, *args, dispatched: bool = False):
+        """One query of any mode: the checks in the reference's order (embedder.py:539-583), then `answer([query_text],
+        *args)[0]` through the retry helper.  `needs`: None or (collection method, message when it is missing);
+        `dispatched`: hand the query to the dynamic-batching dispatcher when there is one."""
         await self._ready()
         if not query_text or not query_text.strip():
             raise ValueError("Query text cannot be empty")
-        if self._dispatcher is not None:
-            return await self._dispatcher.submit(query_text, n_results, filter_dict)
+        if needs and not hasattr(self.collection, needs[0]):
+            raise ValueError(needs[1])
+        if dispatched and self._dispatcher is not None:
+            return await self._dispatcher.submit(query_text, *args)
         try:
-            hit = (await self._engine_call("Query", self._answer, [query_text], n_results, filter_dict))[0]
+            hit = (await self._engine_call(label, answer, [query_text], *args))[0]
         except Exception as e:
-            logger.error("Query failed: %s", e, exc_info=True)
+            logger.error(label + " failed: %s", e, exc_info=True)
             raise
         self.stats["total_queries"] += 1
         return hit
+
+    async def _batch(self, label: str, needs, empty: Dict[str, Any], answer, queries: List[str],
+                     *args) -> List[Dict[str, Any]]:
+        """A list of queries of any mode (embedder.py:784-832): ONE `answer(live queries, *args)` call; a query that
+        cannot be answered -- empty, or all of them when the call or a capability (`needs`, as in _single) fails --
+        gets a copy of `empty` with the reason under 'error' instead of an exception (:817-830)."""
+        await self._ready()
+
+        def failed(why: str) -> Dict[str, Any]:
+            return {**copy.deepcopy(empty), "error": why}
+
+        answers: List[Optional[Dict[str, Any]]] = [None] * len(queries)
+        live = [at for at, q in enumerate(queries) if q and q.strip()]
+        for at in set(range(len(queries))) - set(live):
+            answers[at] = failed("Query text cannot be empty")
+        if live:
+            try:
+                if needs and not hasattr(self.collection, needs[0]):
+                    raise ValueError(needs[1])
+                hits = await self._engine_call(label, answer, [queries[at] for at in live], *args)
+                for at, hit in zip(live, hits):
+                    answers[at] = hit
+                self.stats["total_queries"] += len(live)
+            except Exception as e:
+                logger.error(label + " failed: %s", e)
+                for at in live:
+                    answers[at] = failed(str(e))
+        return answers  # type: ignore[return-value]
+
+    async def query(self, query_text: str, n_results: int = 5, filter_dict: Optional[Dict] = None) -> Dict[str, Any]:
+        """embedder.py:539-583."""
+        return await self._single("Query", None, self._answer, query_text, n_results, filter_dict, dispatched=True)
 
     def supports_hybrid(self) -> bool:
         """True when the collection can answer hybrid_query (a single-GPU VectorIndex; not the sharded serving path)"""
@@ -333,15 +383,11 @@ class EmbeddingManager:
         c = self.collection
         return not (getattr(c, "is_f8", False) and getattr(c, "plane", None) is None)
 
-    def _answer_hybrid(self, text: str, n_results: int, filter_dict: Optional[Dict]) -> Dict[str, Any]:
-        """blocking, one worker thread: cached or fresh embedding, then ONE collection.hybrid_query"""
-        rows, todo, keys = self._lookup([text])
-        if todo:
-            self._encode_into([text], rows, todo, keys)
-        matrix = self._stack(rows, len(todo))
-        res = self.collection.hybrid_query(matrix, [text], n_results=n_results, where=filter_dict,
+    def _answer_hybrid(self, texts: Sequence[str], n_results: int, filter_dict: Optional[Dict]) -> List[Dict[str, Any]]:
+        """blocking, one worker thread: cached or fresh embeddings, then ONE collection.hybrid_query"""
+        res = self.collection.hybrid_query(self._embed(texts), list(texts), n_results=n_results, where=filter_dict,
                                            include=self._INCLUDE)
-        return {key: res[key][0] for key in HYBRID_KEYS}
+        return [{key: res[key][at] for key in HYBRID_KEYS} for at in range(len(texts))]
 
     async def hybrid_query(self, query_text: str, n_results: int = 5,
                            filter_dict: Optional[Dict] = None) -> Dict[str, Any]:
@@ -349,18 +395,7 @@ class EmbeddingManager:
         `distances`, `metadatas`, `documents`, `hybrid_scores` and `lexical_scores`, in hybrid-score order (distances
         are therefore not ascending).  Same empty-query error, embedding cache and query count as query(); it calls
         the collection directly (no dynamic batching)."""
-        await self._ready()
-        if not query_text or not query_text.strip():
-            raise ValueError("Query text cannot be empty")
-        if not hasattr(self.collection, "hybrid_query"):
-            raise ValueError("hybrid retrieval needs a single-GPU collection (VectorIndex)")
-        try:
-            hit = await self._engine_call("Hybrid query", self._answer_hybrid, query_text, n_results, filter_dict)
-        except Exception as e:
-            logger.error("Hybrid query failed: %s", e, exc_info=True)
-            raise
-        self.stats["total_queries"] += 1
-        return hit
+        return await self._single("Hybrid query", _NEEDS_HYBRID, self._answer_hybrid, query_text, n_results, filter_dict)
 
     def supports_mmr(self) -> bool:
         """True when the collection can answer mmr_query (a single-GPU VectorIndex; not the sharded serving path, whose
@@ -371,12 +406,8 @@ class EmbeddingManager:
                     lambda_mult: Optional[float]) -> List[Dict[str, Any]]:
         """blocking, one worker thread: cached or fresh embeddings (ONE encoder pass for the misses), then ONE
         collection.mmr_query for all of them (one search, one selection launch)"""
-        rows, todo, keys = self._lookup(texts)
-        if todo:
-            self._encode_into(texts, rows, todo, keys)
-        matrix = self._stack(rows, len(todo))
-        res = self.collection.mmr_query(matrix, n_results=n_results, fetch_k=fetch_k, lambda_mult=lambda_mult,
-                                        where=filter_dict, include=self._INCLUDE)
+        res = self.collection.mmr_query(self._embed(texts), n_results=n_results, fetch_k=fetch_k,
+                                        lambda_mult=lambda_mult, where=filter_dict, include=self._INCLUDE)
         return [{key: res[key][at] for key in MMR_KEYS} for at in range(len(texts))]
 
     async def mmr_query(self, query_text: str, n_results: int = 5, filter_dict: Optional[Dict] = None,
@@ -385,48 +416,16 @@ class EmbeddingManager:
         fetch_k best dense hits.  One result dict with the keys of query() plus `mmr_scores`, in pick order (distances
         are therefore not ascending).  Same empty-query error, embedding cache and query count as query(); it calls
         the collection directly (no dynamic batching)."""
-        await self._ready()
-        if not query_text or not query_text.strip():
-            raise ValueError("Query text cannot be empty")
-        if not hasattr(self.collection, "mmr_query"):
-            raise ValueError("MMR retrieval needs a single-GPU collection (VectorIndex)")
-        try:
-            hit = (await self._engine_call("MMR query", self._answer_mmr, [query_text], n_results, filter_dict, fetch_k,
-                                           lambda_mult))[0]
-        except Exception as e:
-            logger.error("MMR query failed: %s", e, exc_info=True)
-            raise
-        self.stats["total_queries"] += 1
-        return hit
+        return await self._single("MMR query", _NEEDS_MMR, self._answer_mmr, query_text, n_results, filter_dict,
+                                  fetch_k, lambda_mult)
 
     async def batch_mmr_query(self, queries: List[str], n_results: int = 5, filter_dict: Optional[Dict] = None,
                               fetch_k: Optional[int] = None,
                               lambda_mult: Optional[float] = None) -> List[Dict[str, Any]]:
         """batch_query's twin for mmr_query: one batched encode, one search and one selection launch for all the
         queries; a query that cannot be answered gets a dict with empty lists and an 'error' message."""
-        await self._ready()
-
-        def failed(why: str) -> Dict[str, Any]:
-            return {**{key: [] for key in MMR_KEYS}, "error": why}
-
-        answers: List[Optional[Dict[str, Any]]] = [None] * len(queries)
-        live = [at for at, q in enumerate(queries) if q and q.strip()]
-        for at in set(range(len(queries))) - set(live):
-            answers[at] = failed("Query text cannot be empty")
-        if live:
-            try:
-                if not hasattr(self.collection, "mmr_query"):
-                    raise ValueError("MMR retrieval needs a single-GPU collection (VectorIndex)")
-                hits = await self._engine_call("Batch MMR query", self._answer_mmr, [queries[at] for at in live],
-                                               n_results, filter_dict, fetch_k, lambda_mult)
-                for at, hit in zip(live, hits):
-                    answers[at] = hit
-                self.stats["total_queries"] += len(live)
-            except Exception as e:
-                logger.error("Batch MMR query failed: %s", e)
-                for at in live:
-                    answers[at] = failed(str(e))
-        return answers  # type: ignore[return-value]
+        return await self._batch("Batch MMR query", _NEEDS_MMR, _EMPTY_MMR, self._answer_mmr, queries,
+                                 n_results, filter_dict, fetch_k, lambda_mult)
 
     def supports_grouping(self) -> bool:
         """True when the collection can answer grouped_query (a single-GPU VectorIndex; not the sharded serving path,
@@ -437,12 +436,9 @@ class EmbeddingManager:
                         group_by: str, fetch_k: Optional[int]) -> List[Dict[str, Any]]:
         """blocking, one worker thread: cached or fresh embeddings (ONE encoder pass for the misses), then ONE
         collection.grouped_query for all of them (one batched search and one grouping launch per rung of its ladder)"""
-        rows, todo, keys = self._lookup(texts)
-        if todo:
-            self._encode_into(texts, rows, todo, keys)
-        matrix = self._stack(rows, len(todo))
-        res = self.collection.grouped_query(matrix, n_groups=n_groups, group_size=group_size, group_by=group_by,
-                                            fetch_k=fetch_k, where=filter_dict, include=self._INCLUDE)
+        res = self.collection.grouped_query(self._embed(texts), n_groups=n_groups, group_size=group_size,
+                                            group_by=group_by, fetch_k=fetch_k, where=filter_dict,
+                                            include=self._INCLUDE)
         out = []
         for groups, whole, depth in zip(res["groups"], res["exhaustive"], res["fetch_k"]):
             hit: Dict[str, Any] = {key: [x for g in groups for x in g[key]] for key in RESULT_KEYS}   # in group order
@@ -459,75 +455,23 @@ class EmbeddingManager:
         holding the same hits flattened in group order (so `distances` are not ascending, and
         MultiVectorRetriever.retrieve_raw_documents(ids) works as it is).  Same empty-query error, embedding cache and
         query count as query(); it calls the collection directly (no dynamic batching)."""
-        await self._ready()
-        if not query_text or not query_text.strip():
-            raise ValueError("Query text cannot be empty")
-        if not hasattr(self.collection, "grouped_query"):
-            raise ValueError("grouped retrieval needs a single-GPU collection (VectorIndex)")
-        try:
-            hit = (await self._engine_call("Grouped query", self._answer_grouped, [query_text], n_groups, group_size,
-                                           filter_dict, group_by, fetch_k))[0]
-        except Exception as e:
-            logger.error("Grouped query failed: %s", e, exc_info=True)
-            raise
-        self.stats["total_queries"] += 1
-        return hit
+        return await self._single("Grouped query", _NEEDS_GROUPING, self._answer_grouped, query_text, n_groups,
+                                  group_size, filter_dict, group_by, fetch_k)
 
     async def batch_grouped_query(self, queries: List[str], n_groups: int = 5, group_size: int = 1,
                                   filter_dict: Optional[Dict] = None, group_by: str = "doc_id",
                                   fetch_k: Optional[int] = None) -> List[Dict[str, Any]]:
         """batch_query's twin for grouped_query: one batched encode and one batched grouped search for all the queries;
         a query that cannot be answered gets a dict with empty lists and an 'error' message."""
-        await self._ready()
-
-        def failed(why: str) -> Dict[str, Any]:
-            return {**{key: [] for key in RESULT_KEYS}, "groups": [], "exhaustive": False, "fetch_k": 0, "error": why}
-
-        answers: List[Optional[Dict[str, Any]]] = [None] * len(queries)
-        live = [at for at, q in enumerate(queries) if q and q.strip()]
-        for at in set(range(len(queries))) - set(live):
-            answers[at] = failed("Query text cannot be empty")
-        if live:
-            try:
-                if not hasattr(self.collection, "grouped_query"):
-                    raise ValueError("grouped retrieval needs a single-GPU collection (VectorIndex)")
-                hits = await self._engine_call("Batch grouped query", self._answer_grouped,
-                                               [queries[at] for at in live], n_groups, group_size, filter_dict,
-                                               group_by, fetch_k)
-                for at, hit in zip(live, hits):
-                    answers[at] = hit
-                self.stats["total_queries"] += len(live)
-            except Exception as e:
-                logger.error("Batch grouped query failed: %s", e)
-                for at in live:
-                    answers[at] = failed(str(e))
-        return answers  # type: ignore[return-value]
+        return await self._batch("Batch grouped query", _NEEDS_GROUPING, _EMPTY_GROUPED, self._answer_grouped, queries,
+                                 n_groups, group_size, filter_dict, group_by, fetch_k)
 
     async def batch_query(self, queries: List[str], n_results: int = 5,
                           filter_dict: Optional[Dict] = None) -> List[Dict[str, Any]]:
         """embedder.py:784-832: one result dict per query, input order; a query that cannot be answered gets a dict
         with empty lists and an 'error' message instead of an exception (:817-830)."""
-        await self._ready()
-
-        def failed(why: str) -> Dict[str, Any]:
-            return {**{key: [] for key in RESULT_KEYS}, "error": why}
-
-        answers: List[Optional[Dict[str, Any]]] = [None] * len(queries)
-        live = [at for at, q in enumerate(queries) if q and q.strip()]
-        for at in set(range(len(queries))) - set(live):
-            answers[at] = failed("Query text cannot be empty")
-        if live:
-            try:
-                hits = await self._engine_call("Batch query", self._answer, [queries[at] for at in live], n_results,
-                                               filter_dict)
-                for at, hit in zip(live, hits):
-                    answers[at] = hit
-                self.stats["total_queries"] += len(live)
-            except Exception as e:
-                logger.error("Batch query failed: %s", e)
-                for at in live:
-                    answers[at] = failed(str(e))
-        return answers  # type: ignore[return-value]
+        return await self._batch("Batch query", None, _EMPTY, self._answer, queries, n_results,
+                                 filter_dict)
 
     async def get_similar_documents(self, doc_id: str, item_id: str, n_results: int = 5) -> Dict[str, Any]:
         """embedder.py:861-930: the stored vector of one item searched for its n nearest OTHER items."""

@@ -144,6 +144,13 @@ class MetaIndex:
 _UNHASHABLE = object()
 
 
+def _cat_pairs(parts, dim: int):
+    """(scores, rows) pairs of partial searches joined along `dim`; a single pair is returned as it is"""
+    if len(parts) == 1:
+        return parts[0]
+    return torch.cat([p[0] for p in parts], dim), torch.cat([p[1] for p in parts], dim)
+
+
 class VectorIndex:
     """One shard of the corpus matrix on one GPU plus its host-side row tables.
 
@@ -268,15 +275,9 @@ class VectorIndex:
         if rows <= cap:
             return
         new_cap = max(rows, cap * 2)
-        grown = self._new_rows(new_cap, zero=False)
-        self._raw(grown)[: self._n].copy_(self._raw(self._matrix)[: self._n])
-        self._raw(grown)[self._n:].zero_()
-        self._matrix = grown
+        self._matrix = self._regrown(self._matrix, new_cap, 0)
         if self._plane is not None:
-            grown = torch.empty((new_cap, self.plane_ld), dtype=self.rescore_dtype, device=self.device)
-            grown[: self._n].copy_(self._plane[: self._n])
-            grown[self._n:].zero_()
-            self._plane = grown
+            self._plane = self._regrown(self._plane, new_cap, 0)
         words = torch.zeros(self._n_words(new_cap), dtype=torch.int32, device=self.device)
         words[: self._alive_dev.numel()].copy_(self._alive_dev)
         self._alive_dev = words
@@ -284,9 +285,27 @@ class VectorIndex:
         host[: self._alive_host.size] = self._alive_host
         self._alive_host = host
         for st in self._groups.values():
-            col = torch.full((new_cap,), -1, dtype=torch.int32, device=self.device)
-            col[: self._n].copy_(st["col"][: self._n])
-            st["col"] = col
+            st["col"] = self._regrown(st["col"], new_cap, -1)
+
+    def _regrown(self, t: torch.Tensor, cap: int, fill: int) -> torch.Tensor:
+        """a per-row device tensor (matrix, plane, group column) at capacity `cap`: rows in use copied, tail filled"""
+        raw = self._raw(t)
+        new = torch.empty((cap,) + raw.shape[1:], dtype=raw.dtype, device=raw.device)
+        new[: self._n].copy_(raw[: self._n])
+        new[self._n:].fill_(fill)
+        return new if raw is t else new.view(t.dtype)
+
+    def _compacted(self, t: torch.Tensor, cap: int, keep_dev: torch.Tensor, fill: int) -> torch.Tensor:
+        """a per-row device tensor at capacity `cap` holding the rows `keep_dev` of `t` in order, the tail filled; rows
+        of vectors move with the gather kernel, a column (a scalar per row, below its 16-byte granule) by index copy"""
+        raw = self._raw(t)
+        new = torch.full((cap,) + raw.shape[1:], fill, dtype=raw.dtype, device=raw.device)
+        new = new if raw is t else new.view(t.dtype)
+        if keep_dev.numel() and t.dim() == 2:
+            _native.gather_rows(new, t, keep_dev)
+        elif keep_dev.numel():
+            new[: keep_dev.numel()] = t[keep_dev]
+        return new
 
     def _set_alive(self, lo: int, hi: int):
         """mark rows [lo, hi) alive (appends): touch only the words they fall in"""
@@ -337,7 +356,8 @@ class VectorIndex:
         return t.to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous()
 
     def _pack_queries(self, q, check_norm: bool = True) -> torch.Tensor:
-        """float32 [B, d] -> storage dtype [B, ld] with zero pad columns (device-side cast kernel)."""
+        """float32 [B, d] -> storage dtype [B, ld] with zero pad columns (device-side cast kernel).  A float32 device
+        tensor that _to_device_f32 already returned passes through it unchanged (give check_norm=False)."""
         qf = self._to_device_f32(q, "query", check_norm)
         if self.dtype == torch.float32 and self.ld == self.dim:
             return qf          # already the stored form: no cast pass (one launch less on the single-query path)
@@ -386,14 +406,7 @@ class VectorIndex:
                 self._ids.append(ids[i])
                 self._documents.append(documents[i])
                 self._metadatas.append(metadatas[i])
-            self._meta_index.append([metadatas[i] for i in keep])
-            self._set_alive(self._n, self._n + len(keep))
-            if self._lex is not None:
-                self._lex.append([documents[i] for i in keep])
-            if self._groups:
-                self._groups_appended(self._n, self._n + len(keep))
-            self._n += len(keep)
-            self._grown(len(keep))
+            self._appended(len(keep))
 
     def add_rows_device(self, rows_packed: torch.Tensor, documents, metadatas, ids,
                         plane_rows: Optional[torch.Tensor] = None):
@@ -415,14 +428,19 @@ class VectorIndex:
             self._ids.extend(ids)
             self._documents.extend(documents if documents is not None else [None] * m)
             self._metadatas.extend(metadatas if metadatas is not None else [{} for _ in range(m)])
-            self._meta_index.append(self._metadatas[self._n: self._n + m])
-            self._set_alive(self._n, self._n + m)
-            if self._lex is not None:
-                self._lex.append(self._documents[self._n: self._n + m])
-            if self._groups:
-                self._groups_appended(self._n, self._n + m)
-            self._n += m
-            self._grown(m)
+            self._appended(m)
+
+    def _appended(self, m: int):
+        """m rows were appended to the matrix and the row tables (caller holds the lock): what is derived follows"""
+        lo, hi = self._n, self._n + m
+        self._meta_index.append(self._metadatas[lo:hi])
+        self._set_alive(lo, hi)
+        if self._lex is not None:
+            self._lex.append(self._documents[lo:hi])
+        if self._groups:
+            self._groups_appended(lo, hi)
+        self._n = hi
+        self._grown(m)
 
     def _grown(self, m: int):
         """row tables grew by m (caller holds the lock): see config.MMRAG_GC_FREEZE_ROWS"""
@@ -470,9 +488,8 @@ class VectorIndex:
         exact scores of those candidates on the full-precision plane and the best n_results of them, same stream"""
         from .config import settings
 
-        qf = self._to_device_f32(query_embeddings, "query", check_norm)
-        q8 = self._new_rows(qf.shape[0], zero=False)
-        _native.append_rows(q8, 0, qf, self.dim)
+        qf = self._to_device_f32(query_embeddings, "query", check_norm)     # converted and norm-checked once
+        q8 = self._pack_queries(qf, check_norm=False)
         qp = self._pack_plane_queries(qf)
         bits = self._where_bits(where)
         if n_results <= _native.MAX_K_DEEP:
@@ -483,46 +500,32 @@ class VectorIndex:
         # deeper than one candidate list: the single-query masked-pass loop, over-fetch 1, each pass re-scored (passes
         # stay in the scan plane's order, each pass ordered by its exact scores)
         scores, rows = self._scan(q8, n_results, bits)
-        parts = [_native.rescore_topk(qp, self._plane, self.dim, rows[:, i:i + _native.MAX_K].contiguous(),
-                                      min(_native.MAX_K, rows.shape[1] - i))
-                 for i in range(0, rows.shape[1], _native.MAX_K)]
-        return torch.cat([p[0] for p in parts], 1), torch.cat([p[1] for p in parts], 1)
+        return _cat_pairs([_native.rescore_topk(qp, self._plane, self.dim, rows[:, i:i + _native.MAX_K].contiguous(),
+                                                min(_native.MAX_K, rows.shape[1] - i))
+                           for i in range(0, rows.shape[1], _native.MAX_K)], 1)
 
     def _scan(self, q: torch.Tensor, n_results: int, bits):
         """the search kernels on the stored matrix for packed queries q (caller holds the lock)"""
         if n_results <= _native.MAX_K and self.f32_exact and self.dtype == torch.float32 and q.shape[0] > 64:
             # exact float32 scores whatever the batch size (MMRAG_F32_EXACT_SEARCH): 64 queries per scan keep the exact
             # float32 matrix instruction; bigger batches would take the bf16-split path of csrc/search.hip
-            parts = [_native.cosine_topk(q[i:i + 64], self._matrix, self._n, self.dim, n_results, alive_bits=bits)
-                     for i in range(0, q.shape[0], 64)]
-            return torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)
+            return self._in_slices(q, 64, lambda qi: _native.cosine_topk(qi, self._matrix, self._n, self.dim, n_results,
+                                                                         alive_bits=bits))
         if n_results <= _native.MAX_K:
             need = _native.cosine_topk_workspace_bytes(q.shape[0], self._n, n_results)
-            if self._search_ws is None or self._search_ws.numel() < need:
-                self._search_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
-            # (one workspace per index: searches are enqueued under the lock on the caller's current stream, and every
-            # caller thread of the service uses the default stream, so consecutive scans are ordered on the device)
             return _native.cosine_topk(q, self._matrix, self._n, self.dim, n_results, alive_bits=bits,
-                                       workspace=self._search_ws if torch.cuda.current_stream(self.device) == torch.cuda.default_stream(self.device) else None,
-                                       packed_out=True)
+                                       workspace=self._workspace("_search_ws", need), packed_out=True)
         if n_results <= _native.MAX_K_DEEP:
             # deeper than the kernel's lists (get_similar_documents asks for n_results + 1): the threshold-filter scan
             # and per-query select of csrc/search_deep.hip, any batch, one call (it synchronises the stream once)
             step = 64 if self.f32_exact and self.dtype == torch.float32 else q.shape[0]   # as above: exact float32
-            parts = []
-            for i in range(0, q.shape[0], step):
-                qi = q[i:i + step]
+
+            def deep(qi: torch.Tensor):
                 need = _native.cosine_topk_deep_workspace_bytes(qi.shape[0], self._n, n_results)
-                ws = None
-                if torch.cuda.current_stream(self.device) == torch.cuda.default_stream(self.device):
-                    if self._deep_ws is None or self._deep_ws.numel() < need:
-                        self._deep_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
-                    ws = self._deep_ws
-                parts.append(_native.cosine_topk_deep(qi, self._matrix, self._n, self.dim, n_results, alive_bits=bits,
-                                                      workspace=ws))
-            if len(parts) == 1:
-                return parts[0]
-            return torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)
+                return _native.cosine_topk_deep(qi, self._matrix, self._n, self.dim, n_results, alive_bits=bits,
+                                                workspace=self._workspace("_deep_ws", need))
+
+            return self._in_slices(q, step, deep)
         if q.shape[0] != 1:
             raise ValueError(f"n_results > {_native.MAX_K_DEEP} is supported for single queries only")
         # deeper than the deep search (MAX_K_DEEP): further passes with the rows already returned masked out -- still
@@ -547,6 +550,23 @@ class VectorIndex:
             left -= k
         return torch.cat(out_s, 1), torch.cat(out_r, 1)
 
+    def _workspace(self, name: str, need: int) -> Optional[torch.Tensor]:
+        """the reusable workspace `name` (_search_ws, _deep_ws) with at least `need` bytes if the caller is on the
+        default stream, else None.  One per index: searches are enqueued under the lock on the caller's current stream,
+        and every caller thread of the service uses the default stream, so consecutive scans are ordered on the device"""
+        if torch.cuda.current_stream(self.device) != torch.cuda.default_stream(self.device):
+            return None
+        ws = getattr(self, name)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+            setattr(self, name, ws)
+        return ws
+
+    @staticmethod
+    def _in_slices(q: torch.Tensor, step: int, run):
+        """run(q[i:i + step]) -> (scores, rows), `step` queries at a time, joined in query order"""
+        return _cat_pairs([run(q[i:i + step]) for i in range(0, q.shape[0], step)], 0)
+
     def search(self, query_embeddings, n_results: int, where: Optional[Dict[str, Any]] = None):
         """Raw device search: (scores [B, k] float32 desc, rows [B, k] int64, -1 = none).
 
@@ -555,6 +575,27 @@ class VectorIndex:
         single queries only, in passes of 20 with the rows already returned masked out."""
         with self._lock:
             return self._launch_search(query_embeddings, n_results, where)
+
+    def _tables(self):
+        """the row tables as they are now (caller holds the lock).  They are append-only between compactions (a delete
+        only clears alive bits and the id map) and a compaction swaps in NEW lists, so a result is built from this
+        snapshot after the lock is dropped: a hit deleted after the launch is returned whole, as if the delete came later"""
+        return self._ids, self._documents, self._metadatas
+
+    @staticmethod
+    def _rows_of(tables, rows: Sequence[int], include: Sequence[str]):
+        """(ids, documents or None, metadatas or None) of these rows of a _tables() snapshot; the metadatas are copies"""
+        ids_t, docs_t, metas_t = tables
+        return ([ids_t[r] for r in rows],
+                [docs_t[r] for r in rows] if "documents" in include else None,
+                [dict(metas_t[r]) for r in rows] if "metadatas" in include else None)
+
+    @classmethod
+    def _append_hits(cls, out: Dict[str, Any], tables, rows: Sequence[int], include: Sequence[str]):
+        """one query's hits appended to the lists of lists of a Chroma-shaped result (a None list stays None)"""
+        for key, col in zip(("ids", "documents", "metadatas"), cls._rows_of(tables, rows, include)):
+            if col is not None:
+                out[key].append(col)
 
     accepts_device_queries = True   # query() takes a device tensor as it is (EmbeddingManager's no-round-trip path)
 
@@ -565,16 +606,13 @@ class VectorIndex:
         device, where the check would cost a host synchronisation per call.
 
         The lock is held only while the kernels are enqueued: concurrent callers (asyncio.to_thread workers,
-        embedder.py:595) overlap their host waits and result building.  Row tables are append-only between
-        compactions (a delete only clears alive bits and the id map) and a compaction swaps in NEW lists, so the
-        snapshot taken under the lock stays valid: a hit whose row is deleted after the launch is still returned
-        whole, exactly as if the delete had come a moment later."""
+        embedder.py:595) overlap their host waits and result building, which reads the snapshot of _tables()."""
         with self._lock, stage("search"):
             scores, rows = self._launch_search(query_embeddings, n_results, where, check_norm)
-            ids_t, docs_t, metas_t = self._ids, self._documents, self._metadatas
+            tables = self._tables()
             emb_src = self._full if "embeddings" in include else None
         with stage("collect"):
-            return self._collect(scores, rows, include, ids_t, docs_t, metas_t, emb_src)
+            return self._collect(scores, rows, include, *tables, emb_src)
 
     def _collect(self, scores, rows, include, ids_t, docs_t, metas_t, emb_src) -> Dict[str, Any]:
         # one device -> host copy each, then plain Python lists: per-element numpy scalars cost 10x a list item
@@ -610,49 +648,35 @@ class VectorIndex:
             if dist_l is not None:
                 out["distances"] = dist_l
             return out
-        if no_miss:                                                              # no misses at all (the usual batch)
-            counts = None
-            flat = rows_h.reshape(-1).tolist()
-        else:
-            rows_l = rows_h.tolist()
-            counts = [k_ if row[-1] >= 0 else sum(1 for r in row if r >= 0) for row in rows_l for k_ in (len(row),)]
-            flat = [r for row, c in zip(rows_l, counts) for r in row[:c]]        # misses (-1) only trail
+        if not no_miss:                                                          # short lists: query by query
+            for b, row in enumerate(rows_h.tolist()):
+                hit = [r for r in row if r >= 0]                                 # misses (-1) only trail
+                self._append_hits(out, (ids_t, docs_t, metas_t), hit, include)
+                if dist_l is not None:
+                    out["distances"].append(dist_l[b][: len(hit)])
+                if want_e:
+                    out["embeddings"].append(self._fetch(hit, emb_src))
+            return out
+        flat = rows_h.reshape(-1).tolist()                                       # every query has all its k hits
         if len(flat) == 1:
             pick = lambda table: (table[flat[0]],)                               # noqa: E731  (itemgetter(x) alone returns the item)
-        elif flat:
+        else:
             getter = operator.itemgetter(*flat)
             pick = lambda table: getter(table)                                   # noqa: E731
-        else:
-            pick = lambda table: ()                                              # noqa: E731
         ids_f = pick(ids_t)
         metas_f = list(map(dict, pick(metas_t))) if want_m else None
         docs_f = pick(docs_t) if want_d else None
-        if counts is None:
-            # the common case, every query has all its k hits: cut the flat columns with one comprehension each
-            k_, nf = rows_h.shape[1], len(flat)
-            out["ids"] = [list(ids_f[lo:lo + k_]) for lo in range(0, nf, k_)]
-            if dist_l is not None:
-                out["distances"] = dist_l
-            if want_m:
-                out["metadatas"] = [metas_f[lo:lo + k_] for lo in range(0, nf, k_)]
-            if want_d:
-                out["documents"] = [list(docs_f[lo:lo + k_]) for lo in range(0, nf, k_)]
-            if want_e:
-                out["embeddings"] = [self._fetch(flat[lo:lo + k_], emb_src) for lo in range(0, nf, k_)]
-            return out
-        lo = 0
-        for b, c in enumerate(counts):
-            hi = lo + c
-            out["ids"].append(list(ids_f[lo:hi]))
-            if dist_l is not None:
-                out["distances"].append(dist_l[b][:c])
-            if want_m:
-                out["metadatas"].append(metas_f[lo:hi])
-            if want_d:
-                out["documents"].append(list(docs_f[lo:hi]))
-            if want_e:
-                out["embeddings"].append(self._fetch(flat[lo:hi], emb_src))
-            lo = hi
+        # cut the flat columns with one comprehension each
+        k_, nf = rows_h.shape[1], len(flat)
+        out["ids"] = [list(ids_f[lo:lo + k_]) for lo in range(0, nf, k_)]
+        if dist_l is not None:
+            out["distances"] = dist_l
+        if want_m:
+            out["metadatas"] = [metas_f[lo:lo + k_] for lo in range(0, nf, k_)]
+        if want_d:
+            out["documents"] = [list(docs_f[lo:lo + k_]) for lo in range(0, nf, k_)]
+        if want_e:
+            out["embeddings"] = [self._fetch(flat[lo:lo + k_], emb_src) for lo in range(0, nf, k_)]
         return out
 
     def ids_of_rows(self, rows: Sequence[int]) -> List[str]:
@@ -675,11 +699,9 @@ class VectorIndex:
                 rows = [r for r in rows if match_where(self._metadatas[r], where)]
             else:
                 rows = self._rows_where(where).tolist()
-            out: Dict[str, Any] = {"ids": [self._ids[r] for r in rows]}
-            out["metadatas"] = [dict(self._metadatas[r]) for r in rows] if "metadatas" in include else None
-            out["documents"] = [self._documents[r] for r in rows] if "documents" in include else None
-            out["embeddings"] = self._fetch(rows) if "embeddings" in include else None
-            return out
+            ids_l, docs_l, metas_l = self._rows_of(self._tables(), rows, include)
+            return {"ids": ids_l, "metadatas": metas_l, "documents": docs_l,
+                    "embeddings": self._fetch(rows) if "embeddings" in include else None}
 
     def delete(self, ids: Optional[Sequence[str]] = None, where: Optional[Dict[str, Any]] = None) -> List[str]:
         """Tombstone the matching rows (collection.delete, embedder.py:639-642): clear their alive bits on the
@@ -717,15 +739,9 @@ class VectorIndex:
             keep = np.nonzero(~self._is_dead(np.arange(self._n, dtype=np.int64)))[0]
             cap = max(256, int(keep.size), self._matrix.shape[0] // 2 if keep.size < self._matrix.shape[0] // 4 else self._matrix.shape[0])
             keep_dev = torch.from_numpy(keep).to(self.device)
-            dst = self._new_rows(cap, zero=True)
-            if keep.size:
-                _native.gather_rows(dst, self._matrix, keep_dev)
-            self._matrix = dst
+            self._matrix = self._compacted(self._matrix, cap, keep_dev, 0)
             if self._plane is not None:
-                dst = torch.zeros((cap, self.plane_ld), dtype=self.rescore_dtype, device=self.device)
-                if keep.size:
-                    _native.gather_rows(dst, self._plane, keep_dev)
-                self._plane = dst
+                self._plane = self._compacted(self._plane, cap, keep_dev, 0)
             self._ids = [self._ids[r] for r in keep]
             self._documents = [self._documents[r] for r in keep]
             self._metadatas = [self._metadatas[r] for r in keep]
@@ -741,10 +757,7 @@ class VectorIndex:
             if self._lex is not None:
                 self._lex.compact(keep)
             for st in self._groups.values():      # the same kept rows, in order; ordinals keep their values
-                col = torch.full((cap,), -1, dtype=torch.int32, device=self.device)
-                if keep.size:
-                    col[: keep.size] = st["col"][keep_dev]
-                st["col"] = col
+                st["col"] = self._compacted(st["col"], cap, keep_dev, -1)
 
     def reset(self):
         with self._lock:
@@ -799,10 +812,10 @@ class VectorIndex:
         with self._lock, stage("search"):
             scores, rows, _, mmr = self._launch_mmr(query_embeddings, n_results, fetch_k, lambda_mult, where,
                                                     check_norm)
-            ids_t, docs_t, metas_t = self._ids, self._documents, self._metadatas
+            tables = self._tables()
             emb_src = self._full if "embeddings" in include else None
         with stage("collect"):
-            out = self._collect(scores, rows, include, ids_t, docs_t, metas_t, emb_src)
+            out = self._collect(scores, rows, include, *tables, emb_src)
             out["mmr_scores"] = [vals[: len(ids)] for vals, ids in zip(mmr.cpu().tolist(), out["ids"])]
             return out
 
@@ -930,24 +943,22 @@ class VectorIndex:
         with self._lock, stage("search"):
             out, depths = self._launch_grouped(query_embeddings, n_groups, group_size, group_by, fetch_k, where,
                                                check_norm)
-            ids_t, docs_t, metas_t = self._ids, self._documents, self._metadatas
+            tables = self._tables()
             values = self._groups[group_by]["values"]
         with stage("collect"):
             scores_h, rows_h, _, group_h, info_h = (t.cpu() for t in out)
             dist_l = (1.0 - scores_h).tolist() if "distances" in include else None     # float32 arithmetic, as query()
             rows_l, group_l, info_l = rows_h.tolist(), group_h.tolist(), info_h.tolist()
-            want_m, want_d = "metadatas" in include, "documents" in include
             res: Dict[str, Any] = {"groups": [], "exhaustive": [], "fetch_k": depths}
             for b, (found, valid) in enumerate(info_l):
                 groups = []
                 for gi in range(found):
                     rows = [r for r in rows_l[b][gi] if r >= 0]                        # unused slots only trail
                     o = group_l[b][gi]
-                    groups.append({"key": values[o] if o >= 0 else None,
-                                   "ids": [ids_t[r] for r in rows],
+                    ids_l, docs_l, metas_l = self._rows_of(tables, rows, include)
+                    groups.append({"key": values[o] if o >= 0 else None, "ids": ids_l,
                                    "distances": dist_l[b][gi][: len(rows)] if dist_l is not None else None,
-                                   "metadatas": [dict(metas_t[r]) for r in rows] if want_m else None,
-                                   "documents": [docs_t[r] for r in rows] if want_d else None})
+                                   "metadatas": metas_l, "documents": docs_l})
                 res["groups"].append(groups)
                 res["exhaustive"].append(found >= G or valid < depths[b])
             return res
@@ -989,18 +1000,14 @@ class VectorIndex:
         the results only."""
         with self._lock:
             scores, rows = self._lexical_search(query_texts, n_results, where)
-            ids_t, docs_t, metas_t = self._ids, self._documents, self._metadatas
+            tables = self._tables()
         scores_h, rows_h = scores.cpu(), rows.cpu()
         out: Dict[str, Any] = {"ids": [], "documents": [] if "documents" in include else None,
                                "metadatas": [] if "metadatas" in include else None, "lexical_scores": []}
         for srow, rrow in zip(scores_h.tolist(), rows_h.tolist()):
             hit = [r for r in rrow if r >= 0]
-            out["ids"].append([ids_t[r] for r in hit])
+            self._append_hits(out, tables, hit, include)
             out["lexical_scores"].append(srow[: len(hit)])
-            if out["documents"] is not None:
-                out["documents"].append([docs_t[r] for r in hit])
-            if out["metadatas"] is not None:
-                out["metadatas"].append([dict(metas_t[r]) for r in hit])
         return out
 
     def hybrid_query(self, query_embeddings, query_texts: Sequence[str], n_results: int = 10,
@@ -1033,7 +1040,7 @@ class VectorIndex:
                 raise ValueError(f"{q.shape[0]} query embeddings for {len(texts)} query texts")
             d_scores, d_rows = self._launch_search(query_embeddings, C, where, check_norm)
             l_scores, l_rows = self._lexical_search(texts, C, where)
-            ids_t, docs_t, metas_t = self._ids, self._documents, self._metadatas
+            tables = self._tables()
             d_s, d_r = d_scores.cpu(), d_rows.cpu()
             l_s, l_r = l_scores.cpu().tolist(), l_rows.cpu().tolist()
             dist_dense = (1.0 - d_s).tolist()                    # float32 arithmetic, as query() does
@@ -1056,12 +1063,8 @@ class VectorIndex:
                                "metadatas": [] if "metadatas" in include else None}
         for b, (top, dpos, lex) in enumerate(fused):
             rows = [r for r, _ in top]
-            out["ids"].append([ids_t[r] for r in rows])
+            self._append_hits(out, tables, rows, include)
             out["hybrid_scores"].append([s for _, s in top])
             out["lexical_scores"].append([lex.get(r, 0.0) for r in rows])
             out["distances"].append([dist_dense[b][dpos[r]] if r in dpos else extra[(b, r)] for r in rows])
-            if out["documents"] is not None:
-                out["documents"].append([docs_t[r] for r in rows])
-            if out["metadatas"] is not None:
-                out["metadatas"].append([dict(metas_t[r]) for r in rows])
         return out

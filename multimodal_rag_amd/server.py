@@ -55,6 +55,23 @@ class QueryRequest(BaseModel):  # api.py:161-164
     per_document: int = Field(1, ge=1, le=16)
 
 
+# request flag -> what it needs of the embedder (method, `supports_*` check) and the 400 detail when that is missing;
+# /query checks them in this order
+MODE_NEEDS = (
+    ("group_by_document", "grouped_query", "supports_grouping",
+     "Grouping by document is not available with this embedder: it needs a single-GPU collection "
+     "(EmbeddingManager.grouped_query)"),
+    ("hybrid", "hybrid_query", "supports_hybrid",
+     "Hybrid retrieval is not available with this embedder: it needs a single-GPU collection with lexical search "
+     "(EmbeddingManager.hybrid_query); a float8_e4m3fn collection also needs its re-scoring plane "
+     "(MMRAG_F8_RESCORE=float16)"),
+    ("mmr", "mmr_query", "supports_mmr",
+     "MMR retrieval is not available with this embedder: it needs a single-GPU collection "
+     "(EmbeddingManager.mmr_query); a float8_e4m3fn collection also needs its re-scoring plane "
+     "(MMRAG_F8_RESCORE=float16)"),
+)
+
+
 class QueryResponse(BaseModel):  # api.py:167-170
     answer: str
     sources: List[dict]
@@ -179,15 +196,11 @@ class Pipeline:
         ranked = [{"rank": at, "doc_id": found, "relevance_score": round(float(1.0 - min(dist, 1.0)), 3),   # api.py:390
                    "type": meta.get("type", "unknown")}
                   for at, (found, dist, meta) in enumerate(zip(hits["ids"], hits["distances"], hits["metadatas"]), 1)]
-        if rerank:
-            for src, score in zip(ranked, hits["rerank_scores"]):
-                src["rerank_score"] = score
-        if hybrid:
-            for src, score in zip(ranked, hits["hybrid_scores"]):
-                src["hybrid_score"] = score
-        if mmr:
-            for src, score in zip(ranked, hits["mmr_scores"]):
-                src["mmr_score"] = score
+        for on, column, key in ((rerank, "rerank_scores", "rerank_score"), (hybrid, "hybrid_scores", "hybrid_score"),
+                                (mmr, "mmr_scores", "mmr_score")):
+            if on:
+                for src, score in zip(ranked, hits[column]):
+                    src[key] = score
         if group_by_document:
             at = 0
             for document_rank, group in enumerate(hits["groups"], 1):
@@ -288,36 +301,14 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
         if request.mmr and request.hybrid:
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="MMR and hybrid retrieval are not combined yet: send `mmr` or `hybrid`, not both")
-        if request.group_by_document and not (hasattr(pipe.embedder, "grouped_query")
-                                              and getattr(pipe.embedder, "supports_grouping", lambda: True)()):
-            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
-                                detail="Grouping by document is not available with this embedder: it needs a "
-                                       "single-GPU collection (EmbeddingManager.grouped_query)")
-        if request.hybrid and not (hasattr(pipe.embedder, "hybrid_query")
-                                   and getattr(pipe.embedder, "supports_hybrid", lambda: True)()):
-            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
-                                detail="Hybrid retrieval is not available with this embedder: it needs a single-GPU "
-                                       "collection with lexical search (EmbeddingManager.hybrid_query); a float8_e4m3fn "
-                                       "collection also needs its re-scoring plane (MMRAG_F8_RESCORE=float16)")
-        if request.mmr and not (hasattr(pipe.embedder, "mmr_query")
-                                and getattr(pipe.embedder, "supports_mmr", lambda: True)()):
-            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
-                                detail="MMR retrieval is not available with this embedder: it needs a single-GPU "
-                                       "collection (EmbeddingManager.mmr_query); a float8_e4m3fn collection also needs its "
-                                       "re-scoring plane (MMRAG_F8_RESCORE=float16)")
-        if request.group_by_document:
-            out = await pipe.answer(request.query, request.top_k, request.use_multimodal, group_by_document=True,
-                                    per_document=request.per_document)
-        elif request.mmr:
-            out = await pipe.answer(request.query, request.top_k, request.use_multimodal, rerank=request.rerank,
-                                    mmr=True, mmr_lambda=request.mmr_lambda)
-        elif request.hybrid:
-            out = await pipe.answer(request.query, request.top_k, request.use_multimodal, rerank=request.rerank,
-                                    hybrid=True)
-        elif request.rerank:
-            out = await pipe.answer(request.query, request.top_k, request.use_multimodal, rerank=True)
-        else:
-            out = await pipe.answer(request.query, request.top_k, request.use_multimodal)
+        for flag, method, supports, detail in MODE_NEEDS:
+            if getattr(request, flag) and not (hasattr(pipe.embedder, method)
+                                               and getattr(pipe.embedder, supports, lambda: True)()):
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=detail)
+        # (combinations of modes were refused above: Pipeline.answer sees at most one of mmr / hybrid / grouping)
+        out = await pipe.answer(request.query, request.top_k, request.use_multimodal, rerank=request.rerank,
+                                hybrid=request.hybrid, mmr=request.mmr, mmr_lambda=request.mmr_lambda,
+                                group_by_document=request.group_by_document, per_document=request.per_document)
         if out is None:
             out = {"answer": NO_DOCS_ANSWER, "sources": []}
         return {**out, "processing_time": time.time() - t0}

@@ -454,3 +454,111 @@ def test_row_tables_leave_the_cyclic_collector_after_bulk_growth(monkeypatch):
         assert gc.get_freeze_count() == 0
     finally:
         gc.unfreeze()
+
+
+# ---------------------------------------------------------------- rows -> (ids, documents, metadatas) (index.VectorIndex._rows_of)
+def test_rows_of_hand_made_tables_every_include_subset():
+    from itertools import combinations
+
+    from multimodal_rag_amd.index import VectorIndex
+
+    ids = ["id a", "id b", "id c"]
+    docs = ["text a", None, "text c"]
+    metas = [{"doc_id": "d0", "n": 1}, {}, {"doc_id": "d1", "tags": ["x"]}]
+    stored = [dict(m) for m in metas]
+    fields = ("metadatas", "documents", "distances", "embeddings")
+    for rows in ([], [2], [1, 1, 0]):                      # none, one, a repeated row
+        for include in (c for n in range(len(fields) + 1) for c in combinations(fields, n)):
+            got_ids, got_docs, got_metas = VectorIndex._rows_of((ids, docs, metas), rows, include)
+            assert len(got_ids) == len(rows) and all(x is ids[r] for x, r in zip(got_ids, rows))
+            if "documents" in include:
+                assert len(got_docs) == len(rows) and all(x is docs[r] for x, r in zip(got_docs, rows))
+            else:
+                assert got_docs is None
+            if "metadatas" in include:
+                assert got_metas == [metas[r] for r in rows]
+                assert all(x is not metas[r] for x, r in zip(got_metas, rows))
+                assert len({id(x) for x in got_metas}) == len(rows)          # a repeated row: a copy each
+                for x in got_metas:
+                    x["mutated"] = True
+                assert metas == stored
+            else:
+                assert got_metas is None
+
+
+# ---------------------------------------------------------------- the single-query and the batch wrapper, every mode
+_NO_HITS = {"ids": [], "distances": [], "metadatas": [], "documents": []}
+# mode -> (single form, batch form, an unanswered query's dict before 'error', error of a collection without the mode)
+WRAPPED = {
+    "query": ("query", "batch_query", _NO_HITS, None),
+    "mmr": ("mmr_query", "batch_mmr_query", {**_NO_HITS, "mmr_scores": []},
+            "MMR retrieval needs a single-GPU collection (VectorIndex)"),
+    "grouped": ("grouped_query", "batch_grouped_query", {**_NO_HITS, "groups": [], "exhaustive": False, "fetch_k": 0},
+                "grouped retrieval needs a single-GPU collection (VectorIndex)"),
+}
+
+
+def _wrapped_manager(mode, monkeypatch, capable=True):
+    """a manager over tests/fakes.py; mmr_query / grouped_query are the fakes of test_mmr_cpu / test_group_cpu"""
+    from tests.test_group_cpu import _grouped_manager
+    from tests.test_mmr_cpu import _mmr_manager
+
+    if mode == "query" or not capable:
+        m = EmbeddingManager(engine=FakeEngine())
+    else:
+        m = (_mmr_manager if mode == "mmr" else _grouped_manager)(monkeypatch)
+    m._sleep = no_sleep
+    run(m.embed_and_store(summaries(6), "doc_aaaaaaaaaaaa"))
+    m._engine.calls.clear()
+    run(m.clear_cache())
+    return m
+
+
+@pytest.mark.parametrize("mode", sorted(WRAPPED))
+def test_wrappers_error_dicts_one_encode_and_query_count(mode, monkeypatch):
+    single, batch, empty, _ = WRAPPED[mode]
+    m = _wrapped_manager(mode, monkeypatch)
+    queries = ["summary number 1", "", "summary number 4", "   "]
+    out = run(getattr(m, batch)(queries))
+    assert m._engine.calls == [2]                                   # one encode for the two live queries
+    assert out[1] == out[3] == {**empty, "error": "Query text cannot be empty"}
+    assert out[1]["ids"] is not out[3]["ids"] and out[1]["ids"] is not out[1]["distances"]
+    assert all("error" not in out[at] and out[at]["ids"] and set(out[at]) == set(empty) for at in (0, 2))
+    assert m.stats["total_queries"] == 2                            # the live ones only
+    assert run(getattr(m, batch)([])) == [] and run(getattr(m, batch)(["", " "]))[1]["error"] == "Query text cannot be empty"
+    assert m.stats["total_queries"] == 2 and m._engine.calls == [2]
+    one = run(getattr(m, single)("summary number 1"))
+    # (the best hit only: the fakes' CPU scores move in the last bit with the batch size, and so may later MMR picks)
+    assert one["ids"][0] == out[0]["ids"][0] and set(one) == set(empty) and m.stats["total_queries"] == 3
+    for bad in ("", "   "):
+        with pytest.raises(ValueError, match="Query text cannot be empty"):
+            run(getattr(m, single)(bad))
+    assert m.stats["total_queries"] == 3
+    if mode == "query":                                             # (the fakes' mmr / grouped forms never fail)
+        m.collection.fail_next = 3
+        with pytest.raises(RuntimeError, match="injected engine failure"):
+            run(m.query("summary number 4"))
+        m.collection.fail_next = 3
+        out = run(m.batch_query(queries))
+        assert out[0] == out[2] == {**empty, "error": "injected engine failure"}
+        assert out[1] == {**empty, "error": "Query text cannot be empty"}
+        assert m.stats["total_queries"] == 3
+
+
+@pytest.mark.parametrize("mode", ["grouped", "mmr"])
+def test_wrappers_on_a_collection_without_the_mode(mode, monkeypatch):
+    single, batch, empty, needs = WRAPPED[mode]
+    m = _wrapped_manager(mode, monkeypatch, capable=False)
+    assert not hasattr(m.collection, single)
+    with pytest.raises(ValueError) as e:
+        run(getattr(m, single)("summary number 1"))
+    assert str(e.value) == needs
+    with pytest.raises(ValueError, match="Query text cannot be empty"):         # the empty text is found first
+        run(getattr(m, single)(" "))
+    out = run(getattr(m, batch)(["summary number 1", "", "summary number 4"]))    # no exception: error dicts
+    assert out[0] == out[2] == {**empty, "error": needs}
+    assert out[1] == {**empty, "error": "Query text cannot be empty"}
+    assert m.stats["total_queries"] == 0 and m._engine.calls == []               # nothing was encoded for it
+    with pytest.raises(ValueError) as e:
+        run(m.hybrid_query("summary number 1"))
+    assert str(e.value) == "hybrid retrieval needs a single-GPU collection (VectorIndex)"
