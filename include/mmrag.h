@@ -412,6 +412,33 @@ int mmrag_group_select(const float *scores, const int64_t *rows, int B, int C, c
                        int64_t n_rows, int n_groups, int group_size, float *out_scores, int64_t *out_rows,
                        int32_t *out_pos, int32_t *out_group, int32_t *out_info, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Near-duplicate detection: the exact all-pairs threshold self-join of a row matrix.  The reference has no counterpart:
+ * app/utils/embedder.py stores every chunk of every upload again (ids are f"{doc_id}_{item id}", :514-523).
+ * X . X^T over the upper triangle in 128 x 128 tiles; the N x N matrix is never written.
+ *
+ * Contract
+ *   - emits every pair (i, j) with 0 <= i < j < n, both rows alive and dot(row_i, row_j) >= threshold, each once, in no
+ *     defined order: out_pairs[s] = (i, j), out_scores[s] = the dot;
+ *   - the dot is over the stored rows (unit rows => cosine), float32 accumulation in one fixed order: a pair's score
+ *     bits depend on its two rows and d only, not on n, the bitmap, the capacity or the grid;
+ *   - *count receives the TOTAL number of qualifying pairs, exact also above `capacity`; then exactly `capacity`
+ *     distinct qualifying pairs are stored and nothing is written past them;
+ *   - one launch after a memset of *count, no host synchronisation, no workspace; the only global atomics are integer
+ *     adds on *count (the call can be captured into a graph).
+ *
+ *   rows        dev [n, ld] of `dtype` MMRAG_F32 / F16 / BF16, pad columns zero; MMRAG_F8E4M3 returns
+ *               MMRAG_EUNSUPPORTED (an FP8 collection is joined on its re-scoring plane)
+ *   ld          mmrag_padded_dim(d, dtype) or a larger width of whole 128-byte slabs
+ *   alive       dev, optional (NULL = every row): bit r & 31 of word r >> 5, at least (n + 31) / 32 words
+ *   out_pairs   dev [capacity, 2] int64, 16-byte aligned      out_scores  dev [capacity] float32
+ *   count       dev, one unsigned 64-bit integer; zeroed by the call
+ * MMRAG_EINVAL before anything is launched: a null pointer, n < 0 or above 2^23, d <= 0, ld < d, capacity < 0 or above
+ * MMRAG_MAX_JOIN_PAIRS, a threshold that is NaN or <= 0.  n < 2 succeeds with count 0. */
+#define MMRAG_MAX_JOIN_PAIRS (1 << 26)
+int mmrag_sim_join(const void *rows, int64_t n, int64_t ld, int dtype, int d, const uint32_t *alive, float threshold,
+                   int64_t *out_pairs, float *out_scores, int64_t capacity, unsigned long long *count, void *stream);
+
 /* CLIP byte-level BPE (the text tower's tokenizer, BASELINE config 4; the reference only names CLIP in config.py:106).
  * Host code, multi-threaded; equals multimodal_rag_amd/tokenizer.py:ClipBpeTokenizer, which tests pin to
  * transformers.CLIPTokenizer.  The caller passes text already NFC-normalised, whitespace-collapsed and lower-cased.

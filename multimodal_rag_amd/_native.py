@@ -24,6 +24,7 @@ MAX_MMR_CANDIDATES = 1024   # mmrag_mmr_select (MMRAG_MAX_MMR_CANDIDATES)
 MAX_RESCORE_CANDIDATES = 4096   # mmrag_rescore_topk (MMRAG_MAX_RESCORE_CANDIDATES)
 # mmrag_group_select (MMRAG_MAX_GROUP_CANDIDATES, MMRAG_MAX_GROUPS, MMRAG_MAX_GROUP_SIZE)
 MAX_GROUP_CANDIDATES, MAX_GROUPS, MAX_GROUP_SIZE = 4096, 256, 16
+MAX_JOIN_PAIRS = 1 << 26   # mmrag_sim_join (MMRAG_MAX_JOIN_PAIRS)
 _DT2TORCH = {F32: torch.float32, F16: torch.float16, BF16: torch.bfloat16, F8E4M3: torch.float8_e4m3fn}
 _TORCH2DT = {v: k for k, v in _DT2TORCH.items()}
 
@@ -193,6 +194,13 @@ def _declare(lib):
     lib.mmrag_group_select.restype = c_int
     lib.mmrag_group_select.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    # near-duplicate join (csrc/simjoin.hip); the join_*tile entries are its test-only exports (csrc/mmrag_internal.h)
+    lib.mmrag_sim_join.restype = c_int
+    lib.mmrag_sim_join.argtypes = [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p,
+                                   c_int64, c_void_p, c_void_p]
+    for name in ("mmrag_internal_join_tile", "mmrag_internal_join_slot_tile"):
+        getattr(lib, name).restype = c_int
+        getattr(lib, name).argtypes = [c_int64, c_int64, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]
     from .lexical import declare as declare_lexical   # BM25 analyzer, device index and search (csrc/lexical.hip)
 
     declare_lexical(lib)
@@ -433,6 +441,48 @@ def group_select(scores: torch.Tensor, rows: torch.Tensor, group_of_row: torch.T
                                       out_i.data_ptr(), _stream_ptr(dev))
     _check(st, "mmrag_group_select")
     return out_s, out_r, out_p, out_g, out_i
+
+
+def sim_join(rows: torch.Tensor, n: int, d: int, threshold: float, alive: Optional[torch.Tensor] = None,
+             capacity: int = 1 << 20) -> Tuple[torch.Tensor, torch.Tensor, int]:
+    """Exact threshold self-join of the first n rows of `rows` [cap, ld] (include/mmrag.h mmrag_sim_join): every pair
+    i < j of alive rows whose dot product is >= threshold.  `alive`: the index's bitmap (int32 words, bit r & 31 of word
+    r >> 5), None = every row.  Returns (pairs [m, 2] int64, scores [m] float32, total): total is the exact number of
+    qualifying pairs, m = min(total, capacity) of them are returned, sorted on the device by (i, j).  One launch on the
+    current stream, then ONE synchronisation to read the count."""
+    _dev_check(rows, alive)
+    if rows.dim() != 2 or not rows.is_contiguous() or rows.dtype not in _TORCH2DT:
+        raise MMRagNativeError("sim_join: rows must be a contiguous 2-D tensor of a storage dtype")
+    n, cap = int(n), int(capacity)
+    if n > rows.shape[0]:
+        raise MMRagNativeError(f"sim_join: n={n} exceeds the {rows.shape[0]} rows given")
+    if alive is not None and (alive.dim() != 1 or alive.dtype != torch.int32 or not alive.is_contiguous()
+                              or alive.numel() * 32 < n or alive.device != rows.device):
+        raise MMRagNativeError("sim_join: alive must be a contiguous int32 bitmap of at least n bits on the rows' device")
+    dev = rows.device
+    pairs = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=dev)
+    scores = torch.empty(max(cap, 1), dtype=torch.float32, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        st = lib().mmrag_sim_join(rows.data_ptr(), n, rows.shape[1], _TORCH2DT[rows.dtype], int(d),
+                                  alive.data_ptr() if alive is not None else None, float(threshold), pairs.data_ptr(),
+                                  scores.data_ptr(), cap, count.data_ptr(), _stream_ptr(dev))
+    _check(st, "mmrag_sim_join")
+    total = int(count.item())
+    m = min(total, cap)
+    pairs, scores = pairs[:m], scores[:m]
+    if m > 1:
+        order = torch.argsort(pairs[:, 0] * max(n, 1) + pairs[:, 1])   # n <= 2^23: the key is below 2^46
+        pairs, scores = pairs[order], scores[order]
+    return pairs, scores, total
+
+
+def join_tile(T: int, at: int, slot_order: bool = False) -> Tuple[int, int]:
+    """(ti, tj) of tile-pair id `at` of a T x T triangle: row-major, or (slot_order) in the order the join kernel runs"""
+    ti, tj = c_int64(0), c_int64(0)
+    fn = lib().mmrag_internal_join_slot_tile if slot_order else lib().mmrag_internal_join_tile
+    _check(fn(int(T), int(at), ctypes.byref(ti), ctypes.byref(tj)), "mmrag_internal_join_tile")
+    return ti.value, tj.value
 
 
 def device_info() -> dict:

@@ -89,8 +89,25 @@ class Settings:
     # min(max(MMRAG_GROUP_CANDIDATES, 4 * n_groups * group_size), 4096) dense hits; queries that neither found
     # n_groups groups nor exhausted their list are searched again 4 x deeper, up to 4096
     MMRAG_GROUP_CANDIDATES: int = field(default_factory=lambda: int(os.getenv("MMRAG_GROUP_CANDIDATES", "64")))
+    # near-duplicate detection (VectorIndex.near_duplicates / add(dedup_threshold=...), csrc/simjoin.hip).
+    # MMRAG_DEDUP_THRESHOLD: 0 = off (default); above 0 (at most 1) embed_and_store skips a chunk whose cosine to a stored
+    # chunk, or to an earlier kept chunk of the same upload, is at least this.  MMRAG_DEDUP_REPORT_THRESHOLD: the default
+    # threshold of near_duplicates / drop_duplicates and of the /duplicates routes
+    MMRAG_DEDUP_THRESHOLD: float = field(default_factory=lambda: float(os.getenv("MMRAG_DEDUP_THRESHOLD", "0")))
+    MMRAG_DEDUP_REPORT_THRESHOLD: float = field(
+        default_factory=lambda: float(os.getenv("MMRAG_DEDUP_REPORT_THRESHOLD", "0.98")))
     # CLIP engines only: embed image items from their pixels (vision tower) instead of their summary text
     MMRAG_EMBED_IMAGE_PIXELS: bool = field(default_factory=lambda: _b("MMRAG_EMBED_IMAGE_PIXELS", "true"))
+
+    def __post_init__(self):
+        self.dedup_threshold()
+
+    def dedup_threshold(self) -> float:
+        """MMRAG_DEDUP_THRESHOLD checked: 0 (off) or a cosine in (0, 1]"""
+        t = float(self.MMRAG_DEDUP_THRESHOLD)
+        if not 0.0 <= t <= 1.0:     # false for NaN too
+            raise ValueError(f"MMRAG_DEDUP_THRESHOLD must be 0 (off) or a cosine in (0, 1] (got {self.MMRAG_DEDUP_THRESHOLD!r})")
+        return t
 
     def index_dtype(self):
         """MMRAG_INDEX_DTYPE as a torch dtype"""

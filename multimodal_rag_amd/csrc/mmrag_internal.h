@@ -47,6 +47,14 @@ constexpr unsigned DBG_LINEAR_TILE64 = 1024u, DBG_LINEAR_TILE128 = 2048u;   // m
 
 }  // namespace mmrag
 
+// test-only exports of the similarity join (simjoin.hip): the tile pair (ti <= tj) of id / slot in [0, T (T + 1) / 2),
+// T = ceil(n / 128) <= 65536.  join_tile: row-major over the triangle; join_slot_tile: the order the kernel runs
+// (bands of tile rows, column by column inside a band).  Host code, no device needed.
+extern "C" {
+int mmrag_internal_join_tile(int64_t T, int64_t id, int64_t *ti, int64_t *tj);
+int mmrag_internal_join_slot_tile(int64_t T, int64_t slot, int64_t *ti, int64_t *tj);
+}
+
 // the cross-encoder's classification head (cross_head.hip), shared by the fp16 and fp32 forwards
 namespace mmrag_impl {
 size_t cls_head_workspace_bytes(int B, int H, int NL);

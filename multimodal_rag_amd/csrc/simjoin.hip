@@ -1,0 +1,368 @@
+// Near-duplicate detection: the exact all-pairs threshold self-join of a row matrix (include/mmrag.h mmrag_sim_join).
+//
+// X . X^T over the upper triangle, 128 x 128 output tiles, the N x N matrix never written.  A workgroup is 4 waves in a
+// 2 x 2 grid, 64 x 64 outputs per wave as 4 x 4 MFMA tiles of 16 x 16 (v_mfma_f32_16x16x32_f16 / _bf16; float32 rows:
+// v_mfma_f32_16x16x4_f32, the exact float32 matrix instruction).  Both operand tiles arrive by the tile_dma.h ring in
+// 128-byte K-slabs (two stages of 2 x 16 KiB, so two workgroups share a CU); rows past n read as zero through the
+// buffer descriptor.  Tile edges are fixed multiples of 128 and the K order is fixed, so a pair's score bits depend on
+// its two rows and d alone.
+//
+// Nearly every tile has no hit: its exit is one wave-wide "any accumulator >= threshold" test.  A wave with survivors
+// applies the alive bits, i < j and the range check, reserves its slots with ONE returning atomic add by one lane and
+// writes its pairs with 16-byte stores.
+//
+// Tile order.  Workgroups are persistent.  The triangle is cut into bands of JOIN_BAND tile rows; inside a band the
+// tile pairs run column by column (all the band's i-tiles against one j-tile, then the next j-tile), so the band's
+// i-tiles stay in L2 and a j-tile is fetched once per band and XCD.  Workgroup w of G runs the slots
+// (t * 8 + w % 8) * (G / 8) + w / 8, t = 0, 1, ...: the workgroups of one XCD (ids 8 apart) hold a contiguous run of
+// slots, i.e. a few columns of one band.
+#include <math.h>
+
+#include "mmrag_internal.h"
+#include "tile_dma.h"
+
+namespace mmrag_impl {
+
+constexpr int JT = 128;          // tile edge (rows of i and of j per workgroup)
+constexpr int JOIN_BAND = 8;     // tile rows per band
+constexpr int JOIN_NSTAGE = 2;
+constexpr int JOIN_STAGE = 2 * JT * SLAB;   // i-tile then j-tile, one K-slab each
+
+// ---- workgroup id -> tile pair -----------------------------------------------------------------------------------
+// first id of tile row r in the row-major order of the triangle (ti <= tj) of a T x T tile grid
+__host__ __device__ inline long long join_row_start(long long T, long long r) { return r * (2 * T - r + 1) / 2; }
+
+// id in [0, T (T + 1) / 2) -> (ti, tj), row-major over the triangle.  Exact for T up to 2^16: (2T + 1)^2 < 2^35 is
+// exact in a double, the root is off by less than one row, and the integer steps below settle it.
+__host__ __device__ inline void join_tile_rowmajor(long long T, long long id, long long &ti, long long &tj) {
+    const double b = 2.0 * (double)T + 1.0;
+    long long r = (long long)((b - sqrt(b * b - 8.0 * (double)id)) * 0.5);
+    r = r < 0 ? 0 : (r > T - 1 ? T - 1 : r);
+    while (join_row_start(T, r) > id) --r;
+    while (r + 1 < T && join_row_start(T, r + 1) <= id) ++r;
+    ti = r;
+    tj = r + (id - join_row_start(T, r));
+}
+
+// slot in [0, T (T + 1) / 2) -> (ti, tj) in the order the kernel runs: bands of JOIN_BAND tile rows, column-major
+// inside a band.  A band holds the same ids as its rows do in the row-major order, so the map is one to one.
+__host__ __device__ inline void join_tile_banded(long long T, long long slot, long long &ti, long long &tj) {
+    long long r, unused;
+    join_tile_rowmajor(T, slot, r, unused);
+    const long long b0 = r / JOIN_BAND * JOIN_BAND;
+    const long long h = T - b0 < JOIN_BAND ? T - b0 : JOIN_BAND;   // tile rows of this band
+    long long k = slot - join_row_start(T, b0);
+    const long long tri = h * (h + 1) / 2;                         // columns 0 .. h-1 hold 1 .. h tiles
+    long long c = 0;
+    if (k < tri) {
+        while (k > c) {
+            k -= c + 1;
+            ++c;
+        }
+    } else {
+        k -= tri;
+        c = h + k / h;
+        k = k % h;
+    }
+    ti = b0 + k;
+    tj = b0 + c;
+}
+
+struct JoinParams {
+    const char *rows;
+    long long n;
+    unsigned row_bytes;     // ld * element size
+    int nk;                 // K-slabs that hold the d logical columns
+    const unsigned *alive;
+    float thr;
+    long long *out_pairs;
+    float *out_scores;
+    unsigned long long capacity;
+    unsigned long long *count;
+    long long T, total;     // tile rows, tile pairs
+};
+
+typedef long long i64x2_t __attribute__((ext_vector_type(2)));
+
+template <int DT>
+__global__ __launch_bounds__(256, 2) void sim_join_kernel(const JoinParams p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int LOADS = 2 * JT / 8 / 4;   // 1 KiB DMA instructions per wave per ring item: 32 pieces over 4 waves
+    static_assert(JOIN_NSTAGE * JOIN_STAGE <= 80 * 1024, "two workgroups per CU");
+    __shared__ __attribute__((aligned(1024))) char smem[JOIN_NSTAGE * JOIN_STAGE];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wm = wave >> 1, wn = wave & 1;     // this wave's 64 x 64 quadrant: i rows wm * 64 .., j rows wn * 64 ..
+    const int c16 = lane & 15, g4 = lane >> 4;
+    const unsigned RB = p.row_bytes;
+    const int nk = p.nk;
+
+    // this wave's DMA pieces: 8 consecutive 8-row pieces of the stage (waves 0, 1: the i-tile; waves 2, 3: the j-tile)
+    unsigned src_off[LOADS];
+#pragma unroll
+    for (int i = 0; i < LOADS; ++i) src_off[i] = dma_src_offset((wave & 1) * LOADS + i, lane, RB);
+    char *const my_dst = smem + wave * LOADS * 1024;
+
+    const int sw = (c16 >> 1) & 7;
+    const int a_base = (wm * 64 + c16) * SLAB;
+    const int b_base = JT * SLAB + (wn * 64 + c16) * SLAB;
+
+    const long long G8 = (long long)(gridDim.x >> 3);
+    for (long long t = 0;; ++t) {
+        const long long slot = (t * 8 + (blockIdx.x & 7)) * G8 + (blockIdx.x >> 3);
+        if (slot >= p.total) break;
+        long long ti, tj;
+        join_tile_banded(p.T, slot, ti, tj);
+        const long long i_row0 = ti * JT, j_row0 = tj * JT;
+
+        if (p.alive != nullptr) {
+            // a tile whose 128 i-rows or 128 j-rows are all dead has nothing to emit (uniform: the whole workgroup leaves)
+            unsigned any_i = 0, any_j = 0;
+#pragma unroll
+            for (int w = 0; w < JT / 32; ++w) {
+                if (i_row0 + 32 * w < p.n) any_i |= p.alive[(i_row0 >> 5) + w];
+                if (j_row0 + 32 * w < p.n) any_j |= p.alive[(j_row0 >> 5) + w];
+            }
+            if (any_i == 0 || any_j == 0) continue;
+        }
+
+        const long long my_row0 = wave < 2 ? i_row0 : j_row0;
+        const long long left = p.n - my_row0;
+        const __amdgpu_buffer_rsrc_t rsrc =
+            make_rsrc(p.rows + (size_t)my_row0 * RB, (unsigned)((left < JT ? left : (long long)JT) * (long long)RB));
+        auto issue = [&](int item) {
+            char *dst = my_dst + (item % JOIN_NSTAGE) * JOIN_STAGE;
+            const unsigned koff = (unsigned)item * SLAB;
+#pragma unroll
+            for (int i = 0; i < LOADS; ++i)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(dst + i * 1024), 16, src_off[i] + koff, 0, 0, 0);
+        };
+
+        f32x4_t acc[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[a][b][r] = 0.0f;
+
+        int issued = 0;
+        for (; issued < JOIN_NSTAGE - 1 && issued < nk; ++issued) issue(issued);
+        for (int it = 0; it < nk; ++it) {
+            wait_items<LOADS, JOIN_NSTAGE - 2>(issued - it - 1);
+            __builtin_amdgcn_s_barrier();
+            if (issued < nk) {
+                issue(issued);
+                ++issued;
+            }
+            const char *st = smem + (it % JOIN_NSTAGE) * JOIN_STAGE;
+            // a 128-byte slab is two k-steps; lane (c16, g4) reads chunk 4 s + g4 of row c16 of every 16-row block.
+            // One fixed K order for every pair: the score bits do not depend on the tile pair or the grid.
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const int off = ((4 * s + g4) ^ sw) * 16;
+                if constexpr (DT == MMRAG_F32) {
+                    // exact float32: chunk 4 s + g4 holds four consecutive floats of the row; MFMA e takes element e of
+                    // every lane's chunk, i.e. k = 4 (4 s + g4) + e for g4 = 0 .. 3 -- the same k for both operands
+                    f32x4_t fa[4], fb[4];
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) fa[a] = *(const f32x4_t *)(st + a_base + a * (16 * SLAB) + off);
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) fb[b] = *(const f32x4_t *)(st + b_base + b * (16 * SLAB) + off);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+#pragma unroll
+                        for (int a = 0; a < 4; ++a)
+#pragma unroll
+                            for (int b = 0; b < 4; ++b)
+                                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[a][e], fb[b][e], acc[a][b], 0, 0, 0);
+                } else if constexpr (DT == MMRAG_F16) {
+                    half8_t fa[4], fb[4];
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) fa[a] = *(const half8_t *)(st + a_base + a * (16 * SLAB) + off);
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) fb[b] = *(const half8_t *)(st + b_base + b * (16 * SLAB) + off);
+#pragma unroll
+                    for (int a = 0; a < 4; ++a)
+#pragma unroll
+                        for (int b = 0; b < 4; ++b)
+                            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[a], fb[b], acc[a][b], 0, 0, 0);
+                } else {
+                    bf16x8_t fa[4], fb[4];
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) fa[a] = *(const bf16x8_t *)(st + a_base + a * (16 * SLAB) + off);
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) fb[b] = *(const bf16x8_t *)(st + b_base + b * (16 * SLAB) + off);
+#pragma unroll
+                    for (int a = 0; a < 4; ++a)
+#pragma unroll
+                        for (int b = 0; b < 4; ++b)
+                            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], fb[b], acc[a][b], 0, 0, 0);
+                }
+            }
+        }
+
+        // ---- epilogue: acc[a][b][r] = <row i, row j>, i = i_row0 + wm*64 + 16a + 4 g4 + r, j = j_row0 + wn*64 + 16b + c16
+        float mx = acc[0][0][0];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) mx = fmaxf(mx, acc[a][b][r]);
+        if (__builtin_amdgcn_ballot_w64(mx >= p.thr) != 0ull) {
+            // rows fit an int: n <= 2^23 (the launcher's check)
+            const int n = (int)p.n;
+            const int gi0 = (int)i_row0 + wm * 64 + 4 * g4, gj0 = (int)j_row0 + wn * 64 + c16;
+            unsigned ok_i = 0, ok_j = 0;    // bit 4a + r / bit b: the row is in range and alive
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                // the four rows 16a + 4 g4 .. + 3 sit in one bitmap word
+                const int gi = gi0 + 16 * a;
+                unsigned word = 0xffffffffu;
+                if (p.alive != nullptr && gi < n) word = p.alive[gi >> 5];
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (gi + r < n && ((word >> ((gi + r) & 31)) & 1u)) ok_i |= 1u << (4 * a + r);
+            }
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int gj = gj0 + 16 * b;
+                unsigned word = 0xffffffffu;
+                if (p.alive != nullptr && gj < n) word = p.alive[gj >> 5];
+                if (gj < n && ((word >> (gj & 31)) & 1u)) ok_j |= 1u << b;
+            }
+            // bit 16a + 4b + r of this lane's mask: the element qualifies (score, both rows alive and in range, i < j)
+            unsigned long long mask = 0;
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const bool ok = acc[a][b][r] >= p.thr && ((ok_i >> (4 * a + r)) & 1u) && ((ok_j >> b) & 1u) &&
+                                        gi0 + 16 * a + r < gj0 + 16 * b;
+                        mask |= (unsigned long long)(ok ? 1 : 0) << (16 * a + 4 * b + r);
+                    }
+            const int n_pass = __popcll(mask);
+            // inclusive prefix sum over the wave, then one returning atomic by lane 63 (it holds the wave's total)
+            int incl = n_pass;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int up = __shfl_up(incl, d);
+                if (lane >= d) incl += up;
+            }
+            const int total = __shfl(incl, 63);
+            if (total > 0) {
+                unsigned lo = 0, hi = 0;
+                if (lane == 63) {
+                    const unsigned long long base = atomicAdd(p.count, (unsigned long long)total);
+                    lo = (unsigned)base;
+                    hi = (unsigned)(base >> 32);
+                }
+                lo = (unsigned)__shfl((int)lo, 63);
+                hi = (unsigned)__shfl((int)hi, 63);
+                unsigned long long at = (((unsigned long long)hi << 32) | lo) + (unsigned long long)(incl - n_pass);
+                if (n_pass > 0) {
+#pragma unroll
+                    for (int a = 0; a < 4; ++a)
+#pragma unroll
+                        for (int b = 0; b < 4; ++b)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                if ((mask >> (16 * a + 4 * b + r)) & 1ull) {
+                                    if (at < p.capacity) {
+                                        i64x2_t pr;
+                                        pr[0] = gi0 + 16 * a + r;
+                                        pr[1] = gj0 + 16 * b;
+                                        *(i64x2_t *)(p.out_pairs + 2 * at) = pr;
+                                        p.out_scores[at] = acc[a][b][r];
+                                    }
+                                    ++at;
+                                }
+                }
+            }
+        }
+        __syncthreads();   // every wave is done with the ring before the next tile's first slab lands
+    }
+#endif
+}
+
+template <int DT>
+static int launch_join(const JoinParams &p, hipStream_t s) {
+    // persistent grid: two workgroups per CU (the LDS allows two), a multiple of 8 so every XCD runs whole slot runs
+    long long g = 2LL * mmrag::num_cus();
+    if (g > p.total) g = p.total;
+    g = (g + 7) / 8 * 8;
+    hipLaunchKernelGGL(sim_join_kernel<DT>, dim3((unsigned)g), dim3(256), 0, s, p);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    return MMRAG_OK;
+}
+
+}  // namespace mmrag_impl
+
+extern "C" {
+
+int mmrag_internal_join_tile(int64_t T, int64_t id, int64_t *ti, int64_t *tj) {
+    MMRAG_CHECK_ARG(ti && tj, "join_tile: null pointer");
+    MMRAG_CHECK_ARG(T >= 1 && T <= 65536 && id >= 0 && id < T * (T + 1) / 2, "join_tile: need 1 <= T <= 65536 and "
+                    "0 <= id < T (T + 1) / 2 (T=%lld id=%lld)", (long long)T, (long long)id);
+    long long a, b;
+    mmrag_impl::join_tile_rowmajor(T, id, a, b);
+    *ti = a;
+    *tj = b;
+    return MMRAG_OK;
+}
+
+int mmrag_internal_join_slot_tile(int64_t T, int64_t slot, int64_t *ti, int64_t *tj) {
+    MMRAG_CHECK_ARG(ti && tj, "join_slot_tile: null pointer");
+    MMRAG_CHECK_ARG(T >= 1 && T <= 65536 && slot >= 0 && slot < T * (T + 1) / 2, "join_slot_tile: need 1 <= T <= 65536 "
+                    "and 0 <= slot < T (T + 1) / 2 (T=%lld slot=%lld)", (long long)T, (long long)slot);
+    long long a, b;
+    mmrag_impl::join_tile_banded(T, slot, a, b);
+    *ti = a;
+    *tj = b;
+    return MMRAG_OK;
+}
+
+int mmrag_sim_join(const void *rows, int64_t n, int64_t ld, int dtype, int d, const uint32_t *alive, float threshold,
+                   int64_t *out_pairs, float *out_scores, int64_t capacity, unsigned long long *count, void *stream) {
+    using namespace mmrag_impl;
+    MMRAG_CHECK_ARG(rows && out_pairs && out_scores && count, "sim_join: null pointer");
+    MMRAG_CHECK_ARG(dtype >= 0 && dtype <= MMRAG_F8E4M3, "sim_join: bad dtype %d", dtype);
+    MMRAG_CHECK_ARG(n >= 0 && d > 0 && ld >= d, "sim_join: need n >= 0 and 0 < d <= ld (n=%lld d=%d ld=%lld)",
+                    (long long)n, d, (long long)ld);
+    MMRAG_CHECK_ARG(capacity >= 0 && capacity <= MMRAG_MAX_JOIN_PAIRS, "sim_join: capacity %lld outside 0..%d",
+                    (long long)capacity, MMRAG_MAX_JOIN_PAIRS);
+    MMRAG_CHECK_ARG(threshold > 0.0f, "sim_join: the threshold must be a number above 0");   // false for NaN too
+    if (dtype == MMRAG_F8E4M3) {
+        mmrag::set_error("sim_join: float8_e4m3 rows are not joined; join the collection's re-scoring plane");
+        return MMRAG_EUNSUPPORTED;
+    }
+    const int es = mmrag::esize(dtype);
+    MMRAG_CHECK_ARG(ld * es % SLAB == 0 && ld * es <= (1LL << 24), "sim_join: ld must cover whole 128-byte slabs "
+                    "(mmrag_padded_dim), rows of at most 16 MiB (ld=%lld)", (long long)ld);
+    MMRAG_CHECK_ARG((n + JT - 1) / JT <= 65536, "sim_join: at most 2^23 rows (n=%lld)", (long long)n);
+    hipStream_t s = (hipStream_t)stream;
+    MMRAG_CHECK_HIP(hipMemsetAsync(count, 0, sizeof(unsigned long long), s));
+    if (n < 2) return MMRAG_OK;
+    JoinParams p;
+    p.rows = (const char *)rows;
+    p.n = n;
+    p.row_bytes = (unsigned)(ld * es);
+    p.nk = (int)(((long long)d * es + SLAB - 1) / SLAB);
+    p.alive = alive;
+    p.thr = threshold;
+    p.out_pairs = (long long *)out_pairs;
+    p.out_scores = out_scores;
+    p.capacity = (unsigned long long)capacity;
+    p.count = count;
+    p.T = (n + JT - 1) / JT;
+    p.total = p.T * (p.T + 1) / 2;
+    if (dtype == MMRAG_F32) return launch_join<MMRAG_F32>(p, s);
+    if (dtype == MMRAG_F16) return launch_join<MMRAG_F16>(p, s);
+    return launch_join<MMRAG_BF16>(p, s);
+}
+
+}  // extern "C"

@@ -46,6 +46,9 @@ _COLLECTION_NOTE = {"description": "Multi-modal RAG embeddings"}
 _NEEDS_HYBRID = ("hybrid_query", "hybrid retrieval needs a single-GPU collection (VectorIndex)")
 _NEEDS_MMR = ("mmr_query", "MMR retrieval needs a single-GPU collection (VectorIndex)")
 _NEEDS_GROUPING = ("grouped_query", "grouped retrieval needs a single-GPU collection (VectorIndex)")
+_NEEDS_DEDUP = ("near_duplicates", "near-duplicate detection needs a single-GPU collection (VectorIndex) with "
+                                   "full-precision rows")
+_dedup_warned = False    # "MMRAG_DEDUP_THRESHOLD is set but this collection cannot de-duplicate": once per process
 # the answer of a batch's query that could not be answered, before its 'error' (copied for every such query)
 _EMPTY = {key: [] for key in RESULT_KEYS}
 _EMPTY_MMR = {key: [] for key in MMR_KEYS}
@@ -241,6 +244,14 @@ class EmbeddingManager:
             if item["type"] in counts:           # other kinds are stored but not counted (:477-479)
                 counts[item["type"]] += 1
         joint = hasattr(self._engine, "encode_images")
+        dedup = settings.dedup_threshold()
+        if dedup > 0 and not self.supports_dedup():
+            global _dedup_warned
+            if not _dedup_warned:
+                _dedup_warned = True
+                logger.warning("MMRAG_DEDUP_THRESHOLD=%s is ignored: %s", dedup, _NEEDS_DEDUP[1])
+            dedup = 0.0
+        skipped = None
         if getattr(self.collection, "encode_fn", None) is not None and not joint:
             # multi-GPU serving loop with an encoder on every rank: ship the strings, each rank embeds and stores the
             # items it owns (serving.ShardedCollection.add_texts) -- no vector leaves its GPU
@@ -255,7 +266,15 @@ class EmbeddingManager:
                     async with self._encode_lock:
                         vecs = await asyncio.to_thread(self._engine.encode_images, list(pixels.values()))
                     matrix[list(pixels)] = np.asarray(vecs, dtype=np.float32)
-            await self._store_with_retry(embeddings=matrix, documents=texts, metadatas=metas, ids=ids)
+            if dedup > 0:
+                done = await self._engine_call("Store", self.collection.add, embeddings=matrix, documents=texts,
+                                               metadatas=metas, ids=ids, dedup_threshold=dedup)
+                skipped = len(done["skipped"])
+                counts["duplicates_skipped"] = skipped     # the per-kind counts keep counting items processed
+            else:
+                await self._store_with_retry(embeddings=matrix, documents=texts, metadatas=metas, ids=ids)
+        if skipped:
+            logger.info("Skipped %d near-duplicate items of doc %s (cosine >= %s)", skipped, doc_id, dedup)
         self.stats["total_items_stored"] += len(summaries)
         logger.info("Stored %d embeddings for doc %s (text: %d, table: %d, image: %d) in %.2fs", len(summaries), doc_id,
                     counts["text"], counts["table"], counts["image"], time.time() - t0)
@@ -426,6 +445,43 @@ class EmbeddingManager:
         queries; a query that cannot be answered gets a dict with empty lists and an 'error' message."""
         return await self._batch("Batch MMR query", _NEEDS_MMR, _EMPTY_MMR, self._answer_mmr, queries,
                                  n_results, filter_dict, fetch_k, lambda_mult)
+
+    def supports_dedup(self) -> bool:
+        """True when the collection can find near-duplicates (a single-GPU VectorIndex with full-precision rows; not the
+        sharded serving path, whose rows live on different GPUs, nor a float8_e4m3fn collection without its re-scoring
+        plane)"""
+        return self.collection is None or (hasattr(self.collection, "near_duplicates") and self._has_full_rows())
+
+    async def _dedup_call(self, label: str, method: str, threshold: Optional[float], doc_id: Optional[str],
+                          max_pairs: int):
+        await self._ready()
+        if not self.supports_dedup():
+            raise ValueError(_NEEDS_DEDUP[1])
+        fn = getattr(self.collection, method)
+
+        def run(**kw):
+            try:
+                return fn(**kw)
+            except ValueError as refusal:     # a bad threshold, a truncated report: not worth a retry
+                return refusal
+
+        out = await self._engine_call(label, run, threshold=threshold, where={"doc_id": doc_id} if doc_id else None,
+                                      max_pairs=max_pairs)
+        if isinstance(out, ValueError):
+            raise out
+        return out
+
+    async def find_duplicates(self, threshold: Optional[float] = None, doc_id: Optional[str] = None,
+                              max_pairs: int = 1 << 20) -> Dict[str, Any]:
+        """The near-duplicate report of the collection (VectorIndex.near_duplicates), of one document's chunks with
+        `doc_id`: pairs at or above the cosine `threshold` (default MMRAG_DEDUP_REPORT_THRESHOLD) and their groups."""
+        return await self._dedup_call("Find duplicates", "near_duplicates", threshold, doc_id, max_pairs)
+
+    async def remove_duplicates(self, threshold: Optional[float] = None, doc_id: Optional[str] = None,
+                                max_pairs: int = 1 << 20) -> List[str]:
+        """Delete all but the earliest stored member of every near-duplicate group (VectorIndex.drop_duplicates);
+        returns the deleted ids.  ValueError, and nothing deleted, when the groups would come from a truncated report."""
+        return await self._dedup_call("Remove duplicates", "drop_duplicates", threshold, doc_id, max_pairs)
 
     def supports_grouping(self) -> bool:
         """True when the collection can answer grouped_query (a single-GPU VectorIndex; not the sharded serving path,

@@ -19,7 +19,7 @@ import gc
 import logging
 import operator
 import threading
-from typing import Any, Callable, Dict, List, Optional, Sequence
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -149,6 +149,10 @@ def _cat_pairs(parts, dim: int):
     if len(parts) == 1:
         return parts[0]
     return torch.cat([p[0] for p in parts], dim), torch.cat([p[1] for p in parts], dim)
+
+
+class DuplicateReportTruncated(ValueError):
+    """drop_duplicates refused: the near-duplicate report holds fewer pairs than exist, so its groups are wrong"""
 
 
 class VectorIndex:
@@ -373,9 +377,17 @@ class VectorIndex:
 
     # ------------------------------------------------------------------ collection API ----
     def add(self, embeddings, documents: Optional[Sequence[Optional[str]]] = None,
-            metadatas: Optional[Sequence[Dict[str, Any]]] = None, ids: Optional[Sequence[str]] = None):
+            metadatas: Optional[Sequence[Dict[str, Any]]] = None, ids: Optional[Sequence[str]] = None,
+            dedup_threshold: Optional[float] = None):
+        """Append rows (collection.add).  `dedup_threshold` (None: off, returns None): a cosine t in (0, 1]; a row whose
+        best stored row scores >= t, or that pairs (>= t) with an earlier row of this batch that is itself kept, is
+        skipped and never reaches the matrix, the row tables or the lexical / group columns.  Returns then
+        {"added": [ids], "skipped": [(id, duplicate_of, cosine)]}."""
         if ids is None:
             raise ValueError("ids are required")
+        if dedup_threshold is not None:
+            dedup_threshold = self._join_threshold(dedup_threshold, "dedup_threshold")
+            self._need_plane("add(dedup_threshold=...)")
         emb = self._to_device_f32(embeddings, "add")
         m = emb.shape[0]
         if len(ids) != m:
@@ -392,11 +404,19 @@ class VectorIndex:
                 if ids[i] not in seen:
                     seen.add(ids[i])
                     keep.append(i)
+            skipped: List[Tuple[str, str, float]] = []
             if len(keep) != m:
                 logger.warning("Add of existing embedding ID ignored for %d of %d items", m - len(keep), m)
                 if not keep:
-                    return
+                    return None if dedup_threshold is None else {"added": [], "skipped": []}
                 emb = emb[torch.tensor(keep, device=self.device)].contiguous()
+            if dedup_threshold is not None:
+                kept, skipped = self._dedup_batch(emb, [ids[i] for i in keep], dedup_threshold)
+                if len(kept) != len(keep):
+                    if not kept:
+                        return {"added": [], "skipped": skipped}
+                    emb = emb[torch.tensor(kept, device=self.device)].contiguous()
+                    keep = [keep[j] for j in kept]
             self._reserve(self._n + len(keep))
             _native.append_rows(self._matrix, self._n, emb, self.dim)
             if self._plane is not None:
@@ -407,6 +427,107 @@ class VectorIndex:
                 self._documents.append(documents[i])
                 self._metadatas.append(metadatas[i])
             self._appended(len(keep))
+            return None if dedup_threshold is None else {"added": [ids[i] for i in keep], "skipped": skipped}
+
+    # ------------------------------------------------------------------ near-duplicates ----
+    DEDUP_BATCH_PAIRS_PER_ROW = 4     # pair capacity of an ingest batch's first join; an overflow is joined once more
+    DEDUP_BATCH_MIN_PAIRS = 1024
+
+    @staticmethod
+    def _join_threshold(t, what: str) -> float:
+        t = float(t)
+        if not 0.0 < t <= 1.0:      # false for NaN too
+            raise ValueError(f"{what} must be a cosine in (0, 1] (got {t!r})")
+        return t
+
+    def _dedup_batch(self, emb: torch.Tensor, ids: Sequence[str], t: float):
+        """which rows of the new batch `emb` [m, dim] (float32, device) to keep at threshold t (caller holds the lock):
+        (positions kept, [(id, duplicate_of, cosine)] of the rest).  Greedy in input order, first wins: a row is
+        skipped for a stored duplicate (the top-1 search: exact, tombstones honoured, FP8 re-scored), else for the
+        lowest earlier row of the batch that pairs with it AND is kept (the join of the batch as it would be stored).
+        A row whose only partners were skipped is kept -- unlike near_duplicates' components (a~b~c without a~c keeps
+        a and c here)."""
+        m = emb.shape[0]
+        best_s = best_r = None
+        if self.count() > 0:
+            s_dev, r_dev = self._launch_search(emb, 1, None, check_norm=False)
+            best_s, best_r = s_dev[:, 0].cpu().numpy(), r_dev[:, 0].cpu().numpy()
+        packed = self._pack_plane_queries(emb) if self._plane is not None else self._pack_queries(emb, check_norm=False)
+        cap = max(self.DEDUP_BATCH_PAIRS_PER_ROW * m, self.DEDUP_BATCH_MIN_PAIRS)
+        pairs, scores, total = _native.sim_join(packed, m, self.dim, t, capacity=cap)
+        if total > cap:
+            if total > _native.MAX_JOIN_PAIRS:
+                raise ValueError(f"add(dedup_threshold={t}): {total} duplicate pairs inside one batch exceed "
+                                 f"{_native.MAX_JOIN_PAIRS}; add it in smaller batches")
+            pairs, scores, total = _native.sim_join(packed, m, self.dim, t, capacity=total)   # the count is exact
+        pairs_h, scores_h = pairs.cpu().numpy(), scores.cpu().numpy()
+        partners: Dict[int, List[Tuple[int, float]]] = {}
+        for (i, j), s in zip(pairs_h.tolist(), scores_h.tolist()):     # sorted by (i, j): ascending i per j
+            partners.setdefault(j, []).append((i, s))
+        alive = [False] * m
+        kept: List[int] = []
+        skipped: List[Tuple[str, str, float]] = []
+        for j in range(m):
+            if best_s is not None and best_r[j] >= 0 and best_s[j] >= t:
+                skipped.append((ids[j], self._ids[int(best_r[j])], float(best_s[j])))
+                continue
+            first = next(((i, s) for i, s in partners.get(j, ()) if alive[i]), None)
+            if first is not None:
+                skipped.append((ids[j], ids[first[0]], float(first[1])))
+                continue
+            alive[j] = True
+            kept.append(j)
+        return kept, skipped
+
+    def near_duplicates(self, threshold: Optional[float] = None, where: Optional[Dict[str, Any]] = None,
+                        max_pairs: int = 1 << 20) -> Dict[str, Any]:
+        """Every pair of live rows (matching `where`) whose cosine is >= threshold (default
+        MMRAG_DEDUP_REPORT_THRESHOLD): the exact self-join of csrc/simjoin.hip over the full-precision rows (an FP8
+        collection's re-scoring plane).  Returns {"threshold", "total_pairs" (exact), "truncated" (more than max_pairs),
+        "pairs": [(id_a, id_b, cosine)] in (row_a, row_b) order with row_a < row_b, "groups": the connected components
+        of the pair graph, each in row order (its first id, the earliest stored, is the keeper), in keeper order}."""
+        from .config import settings
+
+        t = self._join_threshold(settings.MMRAG_DEDUP_REPORT_THRESHOLD if threshold is None else threshold, "threshold")
+        with self._lock:
+            self._need_plane("near_duplicates")
+            bits = self._where_bits(where)
+            pairs, scores, total = _native.sim_join(self._full, self._n, self.dim, t, alive=bits, capacity=int(max_pairs))
+            pairs_h, scores_h = pairs.cpu().numpy().tolist(), scores.cpu().numpy().tolist()
+            parent: Dict[int, int] = {}
+
+            def find(x: int) -> int:
+                root = x
+                while parent.setdefault(root, root) != root:
+                    root = parent[root]
+                while parent[x] != root:
+                    parent[x], x = root, parent[x]
+                return root
+
+            for a, b in pairs_h:
+                ra, rb = find(a), find(b)
+                if ra != rb:
+                    parent[max(ra, rb)] = min(ra, rb)      # the root of a component is its lowest row: the keeper
+            members: Dict[int, List[int]] = {}
+            for row in sorted(parent):
+                members.setdefault(find(row), []).append(row)
+            ids = self._ids
+            return {"threshold": t, "total_pairs": total, "truncated": total > len(pairs_h),
+                    "pairs": [(ids[a], ids[b], s) for (a, b), s in zip(pairs_h, scores_h)],
+                    "groups": [[ids[r] for r in members[root]] for root in sorted(members)]}
+
+    def drop_duplicates(self, threshold: Optional[float] = None, where: Optional[Dict[str, Any]] = None,
+                        max_pairs: int = 1 << 20) -> List[str]:
+        """Delete every non-keeper of near_duplicates(...) (through delete(ids=...): tombstones, lazy compaction, the
+        lexical and group columns follow) and return the deleted ids.  A truncated report has wrong components: then
+        DuplicateReportTruncated (a ValueError), nothing deleted."""
+        with self._lock:
+            report = self.near_duplicates(threshold, where, max_pairs)
+            if report["truncated"]:
+                raise DuplicateReportTruncated(f"drop_duplicates: {report['total_pairs']} pairs at threshold {report['threshold']} "
+                                 f"exceed max_pairs={max_pairs}; nothing was deleted (raise max_pairs or the threshold)")
+            victims = [s for group in report["groups"] for s in group[1:]]
+            return self.delete(ids=victims) if victims else []
 
     def add_rows_device(self, rows_packed: torch.Tensor, documents, metadatas, ids,
                         plane_rows: Optional[torch.Tensor] = None):

@@ -22,6 +22,7 @@ from pydantic import BaseModel, Field
 
 from .config import settings
 from .embedder import EmbeddingManager
+from .index import DuplicateReportTruncated
 from .ingest import ExtractiveAnswerer, PassthroughSummarizer, TextDocumentParser
 from .retriever import MultiVectorRetriever
 
@@ -70,6 +71,13 @@ MODE_NEEDS = (
      "(EmbeddingManager.mmr_query); a float8_e4m3fn collection also needs its re-scoring plane "
      "(MMRAG_F8_RESCORE=float16)"),
 )
+
+
+# /duplicates: what it needs of the embedder and the 400 detail when that is missing (worded like MODE_NEEDS)
+DEDUP_NEEDS = ("find_duplicates", "supports_dedup",
+               "Near-duplicate detection is not available with this embedder: it needs a single-GPU collection "
+               "(EmbeddingManager.find_duplicates); a float8_e4m3fn collection also needs its re-scoring plane "
+               "(MMRAG_F8_RESCORE=float16)")
 
 
 class QueryResponse(BaseModel):  # api.py:167-170
@@ -155,6 +163,32 @@ class Pipeline:
         await self.retriever.store_raw_documents(doc_id, items, filename)
         return {"doc_id": doc_id, "filename": filename, "doc_type": tree.get("doc_type", "unknown"),
                 "chunks_processed": stored}
+
+    def need_dedup(self):
+        method, supports, detail = DEDUP_NEEDS
+        if not (hasattr(self.embedder, method) and getattr(self.embedder, supports, lambda: True)()):
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=detail)
+
+    async def duplicates(self, threshold: Optional[float], doc_id: Optional[str], limit: int) -> dict:
+        """the near-duplicate report (EmbeddingManager.find_duplicates) with `pairs` cut to `limit`"""
+        self.need_dedup()
+        try:
+            report = await self.embedder.find_duplicates(threshold=threshold, doc_id=doc_id)
+        except ValueError as e:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
+        return {"threshold": report["threshold"], "total_pairs": report["total_pairs"], "truncated": report["truncated"],
+                "pairs": [{"a": a, "b": b, "cosine": c} for a, b, c in report["pairs"][:max(limit, 0)]],
+                "groups": [{"keep": g[0], "duplicates": list(g[1:])} for g in report["groups"]]}
+
+    async def remove_duplicates(self, threshold: Optional[float], doc_id: Optional[str]) -> dict:
+        self.need_dedup()
+        try:
+            gone = await self.embedder.remove_duplicates(threshold=threshold, doc_id=doc_id)
+        except DuplicateReportTruncated as e:
+            raise HTTPException(status_code=status.HTTP_409_CONFLICT, detail=str(e))
+        except ValueError as e:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
+        return {"deleted": len(gone), "ids": list(gone)}
 
     async def answer(self, question: str, top_k: int, multimodal: bool, rerank: bool = False,
                      hybrid: bool = False, mmr: bool = False, mmr_lambda: Optional[float] = None,
@@ -285,7 +319,9 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
             raise HTTPException(status_code=413, detail=f"File too large. Max: {settings.MAX_UPLOAD_SIZE}MB")
         out = await pipe.ingest(filename, content_type, data)
         took = time.time() - t0
-        return {**out, "message": f"Processed in {took:.2f}s", "processing_time": took}
+        skipped = out["chunks_processed"].get("duplicates_skipped", 0)
+        note = f", {skipped} duplicates skipped" if skipped > 0 else ""
+        return {**out, "message": f"Processed in {took:.2f}s{note}", "processing_time": took}
 
     @app.post("/query", response_model=QueryResponse)
     @_as_http_500
@@ -333,6 +369,16 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
         for store in (pipe.embedder, pipe.retriever):
             await store.delete_all_documents()
         return {"message": f"Deleted {n} documents", "count": n}
+
+    @app.get("/duplicates")
+    @_as_http_500
+    async def find_duplicates(threshold: Optional[float] = None, doc_id: Optional[str] = None, limit: int = 100):
+        return await pipe.duplicates(threshold, doc_id, limit)
+
+    @app.delete("/duplicates")
+    @_as_http_500
+    async def remove_duplicates(threshold: Optional[float] = None, doc_id: Optional[str] = None):
+        return await pipe.remove_duplicates(threshold, doc_id)
 
     @app.get("/stats")
     @_as_http_500
