@@ -1,0 +1,100 @@
+// The host sequence around deep_select.h's select, shared by the deep top-k (search_deep.hip) and the BM25 search
+// (lexical.hip): a producer appends (score, local row) candidates to B x cap slots and counts them per query, the select
+// turns each query's slots into its sorted top-k, and a query whose candidates overflowed its slots is produced again
+// alone into n slots.  The callers supply the two producer launches.  Internal, gfx950 only.
+#pragma once
+#include "deep_select.h"
+
+#include <stdlib.h>
+
+namespace mmrag_impl {
+
+namespace {
+
+// candidate slots per query for a top-k of k: 32 k, at least 16384, in whole 256s
+inline long long candidate_capacity(int k) {
+    return (long long)mmrag::align_up((size_t)(32LL * k > 16384 ? 32LL * k : 16384), 256);
+}
+
+struct CandWs {
+    size_t off_cnt, off_one_cnt, off_floats, off_bs, off_br, off_os, off_or, total;
+};
+
+// [B counters | the re-run's counter | B floats, if asked for | B x cap scores | B x cap rows | n scores | n rows],
+// every block on a 256-byte boundary
+inline CandWs candidate_ws_layout(int B, long long cap, long long n, bool per_query_floats) {
+    CandWs w;
+    w.off_cnt = 0;
+    w.off_one_cnt = mmrag::align_up((size_t)B * sizeof(unsigned), 256);
+    w.off_floats = w.off_one_cnt + 256;
+    w.off_bs = mmrag::align_up(w.off_floats + (per_query_floats ? (size_t)B * sizeof(float) : 0), 256);
+    w.off_br = mmrag::align_up(w.off_bs + (size_t)B * cap * sizeof(float), 256);
+    // one query x n slots: the re-run of an overflowed query
+    w.off_os = mmrag::align_up(w.off_br + (size_t)B * cap * sizeof(int), 256);
+    w.off_or = mmrag::align_up(w.off_os + (size_t)n * sizeof(float), 256);
+    w.total = mmrag::align_up(w.off_or + (size_t)n * sizeof(int), 256);
+    return w;
+}
+
+// every output (-inf, -1): an empty collection, or nothing that can match
+inline int candidate_fill_empty(float *out_s, long long *out_r, int B, int k, hipStream_t s) {
+    const long long total = (long long)B * k;
+    deep_fill_empty_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(out_s, out_r, total);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    return MMRAG_OK;
+}
+
+// out_s / out_r [B, k] = each query's top-k (score desc, row + row_offset; (-inf, -1) padded) of what the producers
+// append.  `ws` is laid out by candidate_ws_layout(B, cap, n, ...).  Both launchers return a status:
+//   launch_batch(cand_s, cand_r, cnt, cap)     all B queries: query b into slots [b * cap, (b + 1) * cap), count in cnt[b]
+//   launch_one(qi, cand_s, cand_r, cnt, cap)   query qi alone into slots [0, cap = n), count in cnt[0]
+// A counter keeps the TRUE number of candidates; appends past cap are dropped.  The counters are read on the host
+// once (the call's only stream synchronisation; none when n <= cap, where nothing can overflow), and since a query
+// has at most n candidates its re-run fits on the first try.  `name` is the entry point, for error texts.
+template <typename LaunchBatch, typename LaunchOne>
+int candidate_select(const char *name, int B, long long n, long long cap, int k, long long row_offset, float *out_s,
+                     long long *out_r, char *ws, const CandWs &wl, hipStream_t s, LaunchBatch &&launch_batch,
+                     LaunchOne &&launch_one) {
+    unsigned *cnt = (unsigned *)(ws + wl.off_cnt), *one_cnt = (unsigned *)(ws + wl.off_one_cnt);
+    float *bs = (float *)(ws + wl.off_bs), *os = (float *)(ws + wl.off_os);
+    int *br = (int *)(ws + wl.off_br), *orr = (int *)(ws + wl.off_or);
+    MMRAG_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)B * sizeof(unsigned), s));
+    if (int st = launch_batch(bs, br, cnt, cap)) return st;
+    deep_select_kernel<<<B, SEL_THREADS, 0, s>>>(bs, br, cnt, cap, k, row_offset, 0, out_s, out_r, nullptr);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    if (n <= cap) return MMRAG_OK;   // no query can have more than n candidates
+
+    struct HostCounts {
+        unsigned *v;
+        ~HostCounts() { free(v); }
+    } host = {(unsigned *)malloc((size_t)B * sizeof(unsigned))};
+    if (!host.v) {
+        mmrag::set_error("%s: out of host memory", name);
+        return MMRAG_EHIP;
+    }
+    hipError_t e = hipMemcpyAsync(host.v, cnt, (size_t)B * sizeof(unsigned), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        mmrag::set_error("%s: reading the candidate counts failed: %s", name, hipGetErrorString(e));
+        return MMRAG_EHIP;
+    }
+    for (int qi = 0; qi < B; ++qi) {
+        if (host.v[qi] <= (unsigned)cap) continue;
+        e = hipMemsetAsync(one_cnt, 0, sizeof(unsigned), s);
+        if (e == hipSuccess) {
+            if (int st = launch_one(qi, os, orr, one_cnt, n)) return st;
+            deep_select_kernel<<<1, SEL_THREADS, 0, s>>>(os, orr, one_cnt, n, k, row_offset, 0, out_s + (size_t)qi * k,
+                                                         out_r + (size_t)qi * k, nullptr);
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) {
+            mmrag::set_error("%s: overflow re-run failed: %s", name, hipGetErrorString(e));
+            return MMRAG_EHIP;
+        }
+    }
+    return MMRAG_OK;
+}
+
+}  // namespace
+
+}  // namespace mmrag_impl

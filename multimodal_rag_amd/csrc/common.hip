@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <type_traits>
 
 namespace mmrag {
 
@@ -40,6 +41,10 @@ int num_cus() {
 using namespace mmrag;
 
 namespace mmrag_impl {
+
+// the compiler's own type of a full-precision storage dtype (the constant with_elem_type hands out)
+template <int DT>
+using stored_t = std::conditional_t<DT == MMRAG_F32, float, std::conditional_t<DT == MMRAG_F16, _Float16, __bf16>>;
 
 template <typename T>
 __device__ inline T from_f32(float x);
@@ -172,14 +177,13 @@ int mmrag_append_rows(void *corpus, int64_t capacity, int64_t ld, int dtype, int
     hipStream_t s = (hipStream_t)stream;
     const int block = 256;
     const int grid = grid_for(m * ld, block);
-    if (dtype == MMRAG_F32)
-        append_rows_kernel<float><<<grid, block, 0, s>>>((float *)corpus, ld, n_used, new_rows, m, d);
-    else if (dtype == MMRAG_F16)
-        append_rows_kernel<_Float16><<<grid, block, 0, s>>>((_Float16 *)corpus, ld, n_used, new_rows, m, d);
-    else if (dtype == MMRAG_F8E4M3)
+    if (dtype == MMRAG_F8E4M3)
         append_rows_f8_kernel<<<grid, block, 0, s>>>((unsigned char *)corpus, ld, n_used, new_rows, m, d);
     else
-        append_rows_kernel<__bf16><<<grid, block, 0, s>>>((__bf16 *)corpus, ld, n_used, new_rows, m, d);
+        with_elem_type(dtype, [&](auto tag) {
+            using T = stored_t<decltype(tag)::value>;
+            append_rows_kernel<T><<<grid, block, 0, s>>>((T *)corpus, ld, n_used, new_rows, m, d);
+        });
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
 }
@@ -209,14 +213,13 @@ int mmrag_fetch_rows_f32(const void *corpus, int64_t ld, int dtype, const int64_
     hipStream_t s = (hipStream_t)stream;
     const int block = 256;
     const int grid = grid_for(m * d, block);
-    if (dtype == MMRAG_F32)
-        fetch_rows_kernel<float><<<grid, block, 0, s>>>((const float *)corpus, ld, rows, m, d, out);
-    else if (dtype == MMRAG_F16)
-        fetch_rows_kernel<_Float16><<<grid, block, 0, s>>>((const _Float16 *)corpus, ld, rows, m, d, out);
-    else if (dtype == MMRAG_F8E4M3)
+    if (dtype == MMRAG_F8E4M3)
         fetch_rows_f8_kernel<<<grid, block, 0, s>>>((const unsigned char *)corpus, ld, rows, m, d, out);
     else
-        fetch_rows_kernel<__bf16><<<grid, block, 0, s>>>((const __bf16 *)corpus, ld, rows, m, d, out);
+        with_elem_type(dtype, [&](auto tag) {
+            using T = stored_t<decltype(tag)::value>;
+            fetch_rows_kernel<T><<<grid, block, 0, s>>>((const T *)corpus, ld, rows, m, d, out);
+        });
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
 }

@@ -17,13 +17,11 @@
 // slot between the barriers of consecutive terms, and every score is summed in the same order whatever the batch, the
 // grid or the run.  Rows with a positive score, alive and passing `where`, are appended to the query's candidate buffer
 // and the deep top-k's select (deep_select.h) sorts them; a query whose matches overflow the buffer is re-run alone
-// into n slots after one read of the counters, as search_deep.hip does.
-#include "deep_select.h"
+// into n slots after one read of the counters: the driver of candidate_select.h, which search_deep.hip runs too.
+#include "candidate_select.h"
+#include "row_dot.h"
 
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
 #include <math.h>
-#include <stdlib.h>
 
 using namespace mmrag;
 
@@ -293,38 +291,17 @@ __global__ __launch_bounds__(LEX_THREADS) void bm25_score_kernel(Bm25Params p) {
     }
 }
 
-struct Bm25Ws {
-    long long cap;
-    size_t off_cnt, off_one, off_bs, off_br, off_os, off_or, total;
-};
+// candidate slots per query: no more than n in whole 256s (with >= n slots nothing can overflow)
+long long bm25_capacity(long long n, int k) {
+    const long long c = candidate_capacity(k), nn = (long long)align_up((size_t)(n > 0 ? n : 1), 256);
+    return c < nn ? c : nn;
+}
 
-Bm25Ws bm25_ws_layout(int B, long long n, int k) {
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    Bm25Ws w;
-    const long long c = 32LL * k > 16384 ? 32LL * k : 16384;
-    const long long nn = (n > 0 ? n : 1);
-    w.cap = (c + 255) / 256 * 256;
-    if (w.cap > (nn + 255) / 256 * 256) w.cap = (nn + 255) / 256 * 256;   // >= n: nothing can overflow
-    w.off_cnt = 0;
-    w.off_one = up((size_t)B * sizeof(unsigned));
-    w.off_bs = w.off_one + 256;
-    w.off_br = up(w.off_bs + (size_t)B * w.cap * sizeof(float));
-    w.off_os = up(w.off_br + (size_t)B * w.cap * sizeof(int));
-    w.off_or = up(w.off_os + (size_t)nn * sizeof(float));
-    w.total = up(w.off_or + (size_t)nn * sizeof(int));
-    return w;
+CandWs bm25_ws_layout(int B, long long n, int k) {
+    return candidate_ws_layout(B, bm25_capacity(n, k), n > 0 ? n : 1, false);
 }
 
 // ---- row dot products ----------------------------------------------------------------------------------------------
-template <typename T>
-__device__ inline float to_f(T x) {
-    return (float)x;
-}
-template <>
-__device__ inline float to_f<__hip_bfloat16>(__hip_bfloat16 x) {
-    return __bfloat162float(x);
-}
-
 template <typename T>
 __global__ __launch_bounds__(LEX_THREADS) void rows_dot_kernel(const T *__restrict__ q, const T *__restrict__ corpus,
                                                                long long ld, int d, const int *__restrict__ qi,
@@ -333,12 +310,7 @@ __global__ __launch_bounds__(LEX_THREADS) void rows_dot_kernel(const T *__restri
     const long long i = (long long)blockIdx.x * (LEX_THREADS / 64) + threadIdx.x / 64;   // one wave per pair
     if (i >= m) return;
     const int lane = threadIdx.x & 63;
-    const T *a = q + (size_t)qi[i] * ld;
-    const T *c = corpus + (size_t)rows[i] * ld;
-    float s = 0.0f;
-    for (int j = lane; j < d; j += 64) s = fmaf(to_f(a[j]), to_f(c[j]), s);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    const float s = wave_row_dot(q + (size_t)qi[i] * ld, corpus + (size_t)rows[i] * ld, d, lane);
     if (lane == 0) out[i] = s;
 }
 
@@ -364,8 +336,8 @@ int mmrag_lexical_df_update(const int64_t *fwd_off, const int32_t *fwd_term, con
 
 size_t mmrag_lexical_csr_build_workspace_bytes(int64_t n, int n_terms) {
     if (n < 0 || n_terms < 0) return 0;
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    return up((size_t)n_terms * 4) + up((size_t)n_terms * 8) + up((size_t)SORT_GRID * ((n + 31) / 32) * 4) + 256;
+    return align_up((size_t)n_terms * 4, 256) + align_up((size_t)n_terms * 8, 256) +
+           align_up((size_t)SORT_GRID * ((n + 31) / 32) * 4, 256) + 256;
 }
 
 int mmrag_lexical_csr_build(const int64_t *fwd_off, const int32_t *fwd_term, const int32_t *fwd_tf, int64_t n,
@@ -384,11 +356,10 @@ int mmrag_lexical_csr_build(const int64_t *fwd_off, const int32_t *fwd_term, con
     }
     MMRAG_CHECK_ARG(((uintptr_t)workspace % 16) == 0, "lexical_csr_build: workspace must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     char *ws = (char *)workspace;
     unsigned *cnt = (unsigned *)ws;
-    unsigned long long *cursor = (unsigned long long *)(ws + up((size_t)n_terms * 4));
-    unsigned *bitmaps = (unsigned *)(ws + up((size_t)n_terms * 4) + up((size_t)n_terms * 8));
+    unsigned long long *cursor = (unsigned long long *)(ws + align_up((size_t)n_terms * 4, 256));
+    unsigned *bitmaps = (unsigned *)(ws + align_up((size_t)n_terms * 4, 256) + align_up((size_t)n_terms * 8, 256));
     if (n_terms > 0) MMRAG_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)n_terms * 4, s));
     if (n_postings > 0) {
         long long g = (n_postings + LEX_THREADS - 1) / LEX_THREADS;
@@ -425,21 +396,16 @@ int mmrag_bm25_topk(const int64_t *term_off, const int32_t *post_row, const int3
     MMRAG_CHECK_ARG(k1 >= 0.0f && b >= 0.0f && b <= 1.0f, "bm25_topk: need k1 >= 0 and 0 <= b <= 1");
     MMRAG_CHECK_ARG(out_scores && out_rows && q_off, "bm25_topk: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    const long long total = (long long)B * k;
-    if (n == 0 || n_live == 0 || n_terms == 0) {   // nothing can match
-        deep_fill_empty_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(out_scores, (long long *)out_rows, total);
-        MMRAG_CHECK_HIP(hipGetLastError());
-        return MMRAG_OK;
-    }
+    if (n == 0 || n_live == 0 || n_terms == 0)   // nothing can match
+        return candidate_fill_empty(out_scores, (long long *)out_rows, B, k, s);
     MMRAG_CHECK_ARG(term_off && post_row && post_tf && dl && df && q_terms, "bm25_topk: null pointer");
-    const Bm25Ws wl = bm25_ws_layout(B, n, k);
+    const CandWs wl = bm25_ws_layout(B, n, k);
     if (!workspace || workspace_bytes < wl.total) {
         set_error("bm25_topk: workspace %zu bytes < required %zu", workspace_bytes, wl.total);
         return MMRAG_EWORKSPACE;
     }
     MMRAG_CHECK_ARG(((uintptr_t)workspace % 16) == 0, "bm25_topk: workspace must be 16-byte aligned");
-    char *ws = (char *)workspace;
-    Bm25Params p;
+    Bm25Params p = {};
     p.term_off = (const long long *)term_off;
     p.post_row = post_row;
     p.post_tf = post_tf;
@@ -453,60 +419,27 @@ int mmrag_bm25_topk(const int64_t *term_off, const int32_t *post_row, const int3
     p.b = b;
     p.avgdl = sum_dl > 0 ? (float)((double)sum_dl / (double)n_live) : 1.0f;
     p.n_live = (double)n_live;
-    p.q_base = 0;
-    p.cap = wl.cap;
-    p.cnt = (unsigned *)(ws + wl.off_cnt);
-    p.cand_s = (float *)(ws + wl.off_bs);
-    p.cand_r = (int *)(ws + wl.off_br);
     const unsigned blocks = (unsigned)((n + SCORE_R - 1) / SCORE_R);
-    MMRAG_CHECK_HIP(hipMemsetAsync(p.cnt, 0, (size_t)B * sizeof(unsigned), s));
-    bm25_score_kernel<<<dim3(blocks, (unsigned)B), LEX_THREADS, 0, s>>>(p);
-    MMRAG_CHECK_HIP(hipGetLastError());
-    deep_select_kernel<<<B, SEL_THREADS, 0, s>>>(p.cand_s, p.cand_r, p.cnt, p.cap, k, 0, 0, out_scores,
-                                                 (long long *)out_rows, nullptr);
-    MMRAG_CHECK_HIP(hipGetLastError());
-    if (n <= p.cap) return MMRAG_OK;   // no query can match more than n rows
-
-    // overflow: one read of the counters, then each query with more matches than slots alone into n slots
-    unsigned *host_cnt = (unsigned *)malloc((size_t)B * sizeof(unsigned));
-    if (!host_cnt) {
-        set_error("bm25_topk: out of host memory");
-        return MMRAG_EHIP;
-    }
-    hipError_t e = hipMemcpyAsync(host_cnt, p.cnt, (size_t)B * sizeof(unsigned), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        free(host_cnt);
-        set_error("bm25_topk: reading the match counts failed: %s", hipGetErrorString(e));
-        return MMRAG_EHIP;
-    }
-    int status = MMRAG_OK;
-    for (int qi = 0; qi < B && status == MMRAG_OK; ++qi) {
-        if (host_cnt[qi] <= (unsigned)p.cap) continue;
-        Bm25Params p1 = p;
-        p1.q_base = qi;
-        p1.cap = n;
-        p1.cnt = (unsigned *)(ws + wl.off_one);
-        p1.cand_s = (float *)(ws + wl.off_os);
-        p1.cand_r = (int *)(ws + wl.off_or);
-        e = hipMemsetAsync(p1.cnt, 0, sizeof(unsigned), s);
-        if (e == hipSuccess) {
-            bm25_score_kernel<<<dim3(blocks, 1), LEX_THREADS, 0, s>>>(p1);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) {
-            deep_select_kernel<<<1, SEL_THREADS, 0, s>>>(p1.cand_s, p1.cand_r, p1.cnt, n, k, 0, 0,
-                                                         out_scores + (size_t)qi * k,
-                                                         (long long *)out_rows + (size_t)qi * k, nullptr);
-            e = hipGetLastError();
-        }
-        if (e != hipSuccess) {
-            set_error("bm25_topk: overflow re-run failed: %s", hipGetErrorString(e));
-            status = MMRAG_EHIP;
-        }
-    }
-    free(host_cnt);
-    return status;
+    const auto score_into = [&](int q_base, unsigned n_queries, float *cand_s, int *cand_r, unsigned *counts,
+                                long long slots) -> int {
+        Bm25Params pq = p;
+        pq.q_base = q_base;
+        pq.cap = slots;
+        pq.cnt = counts;
+        pq.cand_s = cand_s;
+        pq.cand_r = cand_r;
+        bm25_score_kernel<<<dim3(blocks, n_queries), LEX_THREADS, 0, s>>>(pq);
+        MMRAG_CHECK_HIP(hipGetLastError());
+        return MMRAG_OK;
+    };
+    return candidate_select(
+        "bm25_topk", B, n, bm25_capacity(n, k), k, 0, out_scores, (long long *)out_rows, (char *)workspace, wl, s,
+        [&](float *cand_s, int *cand_r, unsigned *counts, long long slots) {
+            return score_into(0, (unsigned)B, cand_s, cand_r, counts, slots);
+        },
+        [&](int qi, float *cand_s, int *cand_r, unsigned *counts, long long slots) {
+            return score_into(qi, 1u, cand_s, cand_r, counts, slots);
+        });
 }
 
 int mmrag_rows_dot(const void *q, const void *corpus, int64_t ld, int dtype, int d, const int32_t *qi,
@@ -519,16 +452,11 @@ int mmrag_rows_dot(const void *q, const void *corpus, int64_t ld, int dtype, int
     hipStream_t s = (hipStream_t)stream;
     const long long per = LEX_THREADS / 64;
     const unsigned grid = (unsigned)((m + per - 1) / per);
-    if (dtype == MMRAG_F32)
-        rows_dot_kernel<float><<<grid, LEX_THREADS, 0, s>>>((const float *)q, (const float *)corpus, ld, d, qi,
-                                                            (const long long *)rows, m, out);
-    else if (dtype == MMRAG_F16)
-        rows_dot_kernel<__half><<<grid, LEX_THREADS, 0, s>>>((const __half *)q, (const __half *)corpus, ld, d, qi,
-                                                             (const long long *)rows, m, out);
-    else
-        rows_dot_kernel<__hip_bfloat16><<<grid, LEX_THREADS, 0, s>>>((const __hip_bfloat16 *)q,
-                                                                     (const __hip_bfloat16 *)corpus, ld, d, qi,
-                                                                     (const long long *)rows, m, out);
+    with_elem_type(dtype, [&](auto tag) {
+        using T = elem_t<decltype(tag)::value>;
+        rows_dot_kernel<T><<<grid, LEX_THREADS, 0, s>>>((const T *)q, (const T *)corpus, ld, d, qi,
+                                                        (const long long *)rows, m, out);
+    });
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
 }

@@ -254,12 +254,7 @@ int mmrag_internal_mmr_select_ex(const void *corpus, int64_t ld, int dtype, int 
     const long long chunks = ((long long)d * esize(dtype) + 15) / 16;
     const bool staged = !(dbg & 1u) && (long long)C * chunks * 16 <= MMR_STAGE_BYTES;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == MMRAG_F32)
-        mmr_launch<MMRAG_F32>(p, B, staged, s);
-    else if (dtype == MMRAG_F16)
-        mmr_launch<MMRAG_F16>(p, B, staged, s);
-    else
-        mmr_launch<MMRAG_BF16>(p, B, staged, s);
+    with_elem_type(dtype, [&](auto tag) { mmr_launch<decltype(tag)::value>(p, B, staged, s); });
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
 }

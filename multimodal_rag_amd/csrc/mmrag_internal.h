@@ -13,6 +13,22 @@ void set_error(const char *fmt, ...);
 
 inline int esize(int dtype) { return dtype == MMRAG_F32 ? 4 : (dtype == MMRAG_F8E4M3 ? 1 : 2); }
 
+constexpr size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// f(tag) for the full-precision storage type of `dtype` (checked by the caller; FP8 is dispatched before this):
+// decltype(tag)::value is MMRAG_F32 / MMRAG_F16 / MMRAG_BF16 as a compile-time constant, for kernels templated on the
+// integer; row_dot.h's elem_t<> turns it into float / __half / __hip_bfloat16 for those templated on the element
+template <int DT>
+struct ElemTag {
+    static constexpr int value = DT;
+};
+template <typename F>
+inline auto with_elem_type(int dtype, F &&f) {
+    if (dtype == MMRAG_F32) return f(ElemTag<MMRAG_F32>{});
+    if (dtype == MMRAG_F16) return f(ElemTag<MMRAG_F16>{});
+    return f(ElemTag<MMRAG_BF16>{});
+}
+
 #define MMRAG_CHECK_ARG(cond, ...)            \
     do {                                      \
         if (!(cond)) {                        \

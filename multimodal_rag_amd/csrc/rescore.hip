@@ -2,15 +2,13 @@
 // query, this kernel scores them against the full-precision plane and keeps the best k.
 //
 // One launch, one 512-thread workgroup per query.  The 8 waves take the candidates round-robin; a wave computes one
-// float32 dot product exactly as rows_dot_kernel (lexical.hip) does -- lane j accumulates columns j, j + 64, ... with
-// fmaf, then the xor-shuffle tree 32 .. 1 -- so a rescored score is bit-identical to mmrag_rows_dot's for that pair
-// whatever B, C or the candidate's position (a score of -0 is returned as +0: the sort key folds the two zeros).  The
+// float32 dot product with the same function as rows_dot_kernel (lexical.hip), row_dot.h's wave_row_dot -- lane j
+// accumulates columns j, j + 64, ... with fmaf, then the xor-shuffle tree 32 .. 1 -- so a rescored score is
+// bit-identical to mmrag_rows_dot's for that pair whatever B, C or the candidate's position (a score of -0 is returned as +0: the sort key folds the two zeros).  The
 // (score, row) keys are bitonic-sorted in LDS (deep_select.h's sort; C <= 4096, 32 KiB): keys are distinct for distinct rows, so the order
 // (score desc, row asc) does not depend on how the candidates were listed.  No atomics on floats, no host sync.
 #include "deep_select.h"
-
-#include <hip/hip_fp16.h>
-#include <hip/hip_bf16.h>
+#include "row_dot.h"
 
 using namespace mmrag;
 
@@ -20,15 +18,6 @@ namespace {
 
 constexpr int RS_THREADS = 512;
 constexpr int RS_MAX_C = MMRAG_MAX_RESCORE_CANDIDATES;
-
-template <typename T>
-__device__ inline float rs_to_f(T x) {
-    return (float)x;
-}
-template <>
-__device__ inline float rs_to_f<__hip_bfloat16>(__hip_bfloat16 x) {
-    return __bfloat162float(x);
-}
 
 template <typename T>
 __global__ __launch_bounds__(RS_THREADS) void rescore_topk_kernel(const T *__restrict__ q, const T *__restrict__ plane,
@@ -58,10 +47,7 @@ __global__ __launch_bounds__(RS_THREADS) void rescore_topk_kernel(const T *__res
     for (int c = wave; c < len; c += RS_THREADS / 64) {
         const long long row = cand[c];
         const T *v = plane + (size_t)row * ld;
-        float s = 0.0f;
-        for (int j = lane; j < d; j += 64) s = fmaf(rs_to_f(a[j]), rs_to_f(v[j]), s);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+        const float s = wave_row_dot(a, v, d, lane);
         if (lane == 0) keys[c] = deep_key(s, (int)row);
     }
     for (unsigned i = (unsigned)len + tid; i < P; i += RS_THREADS) keys[i] = 0ull;   // below every real key
@@ -100,16 +86,11 @@ int mmrag_rescore_topk(const void *q, const void *plane, int64_t ld, int dtype, 
     hipStream_t s = (hipStream_t)stream;
     const long long *cand = (const long long *)cand_rows;
     long long *orr = (long long *)out_rows;
-    if (dtype == MMRAG_F32)
-        rescore_topk_kernel<float><<<B, RS_THREADS, 0, s>>>((const float *)q, (const float *)plane, ld, d, cand, C, k,
-                                                            out_scores, orr);
-    else if (dtype == MMRAG_F16)
-        rescore_topk_kernel<__half><<<B, RS_THREADS, 0, s>>>((const __half *)q, (const __half *)plane, ld, d, cand, C, k,
-                                                             out_scores, orr);
-    else
-        rescore_topk_kernel<__hip_bfloat16><<<B, RS_THREADS, 0, s>>>((const __hip_bfloat16 *)q,
-                                                                     (const __hip_bfloat16 *)plane, ld, d, cand, C, k,
-                                                                     out_scores, orr);
+    with_elem_type(dtype, [&](auto tag) {
+        using T = elem_t<decltype(tag)::value>;
+        rescore_topk_kernel<T><<<B, RS_THREADS, 0, s>>>((const T *)q, (const T *)plane, ld, d, cand, C, k, out_scores,
+                                                        orr);
+    });
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
 }

@@ -204,18 +204,12 @@ constexpr unsigned DBG_OLD_QS = 0x10000u, DBG_MFMA32 = 0x20000u, DBG_MFMA16 = 0x
 Plan make_plan(int B, long long n, int k, unsigned dbg = 0) {
     Plan pl;
     pl.K = k <= 5 ? 5 : (k <= 10 ? 10 : 20);
-    pl.WN = B <= 64 ? 2 : (B <= 128 ? 4 : 8);
+    pl.WN = plan_wn(B);
     const int qrows = 32 * pl.WN;
     pl.grid_y = (B + qrows - 1) / qrows;
     pl.n_tiles = (int)((n + TM - 1) / TM);
     const int cus = num_cus();
-    pl.grid_x = pl.n_tiles < cus ? pl.n_tiles : cus;
-    if (pl.grid_y > 1 && pl.n_tiles >= cus) {
-        // all query groups of a tile resident together: cus / grid_y walkers, rounded to whole XCD rounds
-        int w = cus / pl.grid_y / 8 * 8;
-        pl.grid_x = w >= 8 ? w : (cus / pl.grid_y > 0 ? cus / pl.grid_y : 1);
-    }
-    if (pl.grid_x < 1) pl.grid_x = 1;
+    pl.grid_x = plan_walkers(pl.n_tiles, pl.grid_y);
     pl.NW = (pl.K == 5 && pl.WN == 8 && !(dbg & DBG_8_WAVES)) ? 16 : 8;  // 4 waves/SIMD hide LDS + barrier latency
     // Sample pre-pass (256-query shape, and every shape with deep lists: there the epilogue, not HBM, is
     // what thresholds relieve).
@@ -285,9 +279,7 @@ void launch_filter(int WN, const KParams &p, dim3 grid, hipStream_t s) {
 int deep_filter_launch(int dtype, int WN, const KParams &p, int grid_x, int grid_y, hipStream_t s) {
     if (dtype == MMRAG_F8E4M3) return f8_filter_launch(WN, p, grid_x, grid_y, s);
     const dim3 grid(grid_x, grid_y);
-    if (dtype == MMRAG_F32) launch_filter<MMRAG_F32>(WN, p, grid, s);
-    else if (dtype == MMRAG_F16) launch_filter<MMRAG_F16>(WN, p, grid, s);
-    else launch_filter<MMRAG_BF16>(WN, p, grid, s);
+    with_elem_type(dtype, [&](auto tag) { launch_filter<decltype(tag)::value>(WN, p, grid, s); });
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
 }
@@ -326,6 +318,24 @@ __global__ void fill_seed_empty_kernel(float *s, int *r, long long q_stride, int
         }
 }
 
+int check_search_args(const char *name, int k_max, const void *q, const void *corpus, int B, int64_t n, int d, int64_t ld,
+                      int dtype, int k) {
+    MMRAG_CHECK_ARG(dtype >= 0 && dtype <= MMRAG_F8E4M3, "%s: bad dtype %d", name, dtype);
+    MMRAG_CHECK_ARG(B > 0, "%s: B must be positive (got %d)", name, B);
+    MMRAG_CHECK_ARG(k >= 1 && k <= k_max, "%s: k=%d outside 1..%d", name, k, k_max);
+    MMRAG_CHECK_ARG(n >= 0 && n < (int64_t)INT_MAX - TM, "%s: n=%lld out of range", name, (long long)n);
+    MMRAG_CHECK_ARG(d > 0 && ld >= d, "%s: need 0 < d <= ld (d=%d ld=%lld)", name, d, (long long)ld);
+    const int64_t row_bytes = ld * esize(dtype);
+    MMRAG_CHECK_ARG(row_bytes % SLAB == 0, "%s: row bytes %lld not a multiple of %d (use mmrag_padded_dim)", name,
+                    (long long)row_bytes, SLAB);
+    MMRAG_CHECK_ARG(row_bytes * TM < (int64_t)UINT_MAX, "%s: rows too long", name);
+    MMRAG_CHECK_ARG(q, "%s: null q", name);
+    MMRAG_CHECK_ARG(n == 0 || corpus, "%s: null corpus", name);
+    MMRAG_CHECK_ARG(((uintptr_t)q % 16) == 0 && ((uintptr_t)corpus % 16) == 0, "%s: q/corpus must be 16-byte aligned",
+                    name);
+    return MMRAG_OK;
+}
+
 }  // namespace mmrag_impl
 using namespace mmrag_impl;
 
@@ -360,30 +370,12 @@ size_t mmrag_cosine_topk_workspace_bytes(int B, int64_t n, int k) {
     return ws_layout(make_plan(B, n, k)).total + 256;
 }
 
-static int check_search_args(const void *q, const void *corpus, int B, int64_t n, int d, int64_t ld, int dtype,
-                             int k) {
-    MMRAG_CHECK_ARG(dtype >= 0 && dtype <= MMRAG_F8E4M3, "cosine_topk: bad dtype %d", dtype);
-    MMRAG_CHECK_ARG(B > 0, "cosine_topk: B must be positive (got %d)", B);
-    MMRAG_CHECK_ARG(k >= 1 && k <= MMRAG_MAX_K, "cosine_topk: k=%d outside 1..%d", k, MMRAG_MAX_K);
-    MMRAG_CHECK_ARG(n >= 0 && n < (int64_t)INT_MAX - TM, "cosine_topk: n=%lld out of range", (long long)n);
-    MMRAG_CHECK_ARG(d > 0 && ld >= d, "cosine_topk: need 0 < d <= ld (d=%d ld=%lld)", d, (long long)ld);
-    const int64_t row_bytes = ld * esize(dtype);
-    MMRAG_CHECK_ARG(row_bytes % SLAB == 0,
-                    "cosine_topk: row bytes %lld not a multiple of %d (use mmrag_padded_dim)", (long long)row_bytes, SLAB);
-    MMRAG_CHECK_ARG(row_bytes * TM < (int64_t)UINT_MAX, "cosine_topk: rows too long");
-    MMRAG_CHECK_ARG(q, "cosine_topk: null q");
-    MMRAG_CHECK_ARG(n == 0 || corpus, "cosine_topk: null corpus");
-    MMRAG_CHECK_ARG(((uintptr_t)q % 16) == 0 && ((uintptr_t)corpus % 16) == 0,
-                    "cosine_topk: q/corpus must be 16-byte aligned");
-    return MMRAG_OK;
-}
-
 // mmrag_cosine_topk_lists with debug switches (DBG_*): kernel-shape A/B runs and the tests that pin every code
 // path against the oracle.  Exported for them, deliberately absent from include/mmrag.h.
 int mmrag_internal_cosine_topk_lists_ex(const void *q, const void *corpus, int B, int64_t n, int d, int64_t ld,
                                         int dtype, int k, const uint32_t *alive_bits, void *workspace,
                                         size_t workspace_bytes, void *stream, unsigned dbg) {
-    if (int st = check_search_args(q, corpus, B, n, d, ld, dtype, k)) return st;
+    if (int st = check_search_args("cosine_topk", MMRAG_MAX_K, q, corpus, B, n, d, ld, dtype, k)) return st;
     if (n == 0) return MMRAG_OK;
     const Plan pl = make_plan(B, n, k, dbg);
     const WsLayout wl = ws_layout(pl);
@@ -476,9 +468,7 @@ int mmrag_internal_cosine_topk_lists_ex(const void *q, const void *corpus, int B
         Plan lp = pl;
         lp.grid_x = grid_x;
         if (dtype == MMRAG_F8E4M3) return f8_lists_launch(lp.K, lp.WN, kp, lp.grid_x, lp.grid_y, s);
-        if (dtype == MMRAG_F32) return dispatch_main<MMRAG_F32>(lp, kp, s);
-        if (dtype == MMRAG_F16) return dispatch_main<MMRAG_F16>(lp, kp, s);
-        return dispatch_main<MMRAG_BF16>(lp, kp, s);
+        return with_elem_type(dtype, [&](auto tag) { return dispatch_main<decltype(tag)::value>(lp, kp, s); });
     };
     if (pl.pre_tiles > 0) {
         // 1. sample pre-pass over the first pre_tiles tiles, one per workgroup

@@ -24,41 +24,9 @@ using namespace mmrag;
 
 namespace mmrag_impl {
 
-template <int DT>
-struct Frag;
-template <>
-struct Frag<MMRAG_F16> {
-    using T = half8_t;
-    static __device__ inline f32x16_t mfma(T a, T b, f32x16_t c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-};
-template <>
-struct Frag<MMRAG_BF16> {
-    using T = bf16x8_t;
-    static __device__ inline f32x16_t mfma(T a, T b, f32x16_t c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-};
-
 constexpr int qs_lists_bytes(int K) { return K * 2 * QS_QROWS * 8; }  // (score f32, row i32) x 2 lists per query
 
-struct QsRing {
-    int G;    // K-slabs per ring stage (one s_barrier per stage)
-    int NST;  // ring stages
-};
-// biggest stage (fewest barriers) that still leaves >= 4 stages in the LDS left over by the lists
-constexpr QsRing qs_ring(int NK, int K) {
-    const int budget = 160 * 1024 - qs_lists_bytes(K);
-    for (int need = 4; need >= 3; --need)
-        for (int g = 4; g >= 1; --g) {
-            if (NK % g) continue;
-            int nst = budget / (g * QS_TILE_ROWS * SLAB);
-            if (nst > 6) nst = 6;
-            if (nst >= need) return QsRing{g, nst};
-        }
-    return QsRing{1, 2};
-}
+constexpr SlabRing qs_ring(int NK, int K) { return slab_ring(NK, qs_lists_bytes(K)); }
 
 // One 16-deep k-step of a wave's 64-row x 64-query tile, as ONE asm statement so that the instruction order is
 // exactly this: the two A-fragment reads of the NEXT k-step go out first, the four MFMAs of this k-step cover
@@ -101,12 +69,12 @@ __device__ __forceinline__ void qs_kstep(f32x16_t &c00, f32x16_t &c01, f32x16_t 
 template <int DT, int NK, int K, bool NT>
 __global__ __launch_bounds__(256, 1) void cosine_topk_qs_kernel(const KParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    using FT = typename Frag<DT>::T;
+    using FT = typename FragType<DT>::T;
     constexpr int R = QS_TILE_ROWS;
     constexpr int RB = R / 32;             // 32-row MFMA blocks per tile
     static_assert(RB == 2, "the k-step statement is written for two row blocks");
     constexpr int SLABB = R * SLAB;        // one K-slab of a tile: 8 KiB
-    constexpr QsRing RING = qs_ring(NK, K);
+    constexpr SlabRing RING = qs_ring(NK, K);
     constexpr int G = RING.G, NST = RING.NST;
     constexpr int SPT = NK / G;            // ring stages per tile
     constexpr int STAGE = G * SLABB;

@@ -33,17 +33,6 @@ namespace mmrag_impl {
 
 namespace {
 
-template <int DT>
-struct WFrag;
-template <>
-struct WFrag<MMRAG_F16> {
-    using T = half8_t;
-};
-template <>
-struct WFrag<MMRAG_BF16> {
-    using T = bf16x8_t;
-};
-
 template <typename F, int... I>
 __device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>) {
     (f(std::integral_constant<int, I>{}), ...);
@@ -56,24 +45,11 @@ __device__ __forceinline__ void static_for(F &&f) {
 constexpr int QSW_XCH = 2048 + 64;   // gather buffer 1 KiB + poll buffer 1 KiB + 8 ticket slots (padded)
 constexpr int qsw_lists_bytes(int K, int MS) { return K * (MS == 32 ? 2 : 4) * QS_QROWS * 8; }
 
-struct WRing {
-    int G;    // K-slabs per ring stage (one s_barrier per stage)
-    int NST;  // ring stages
-};
-// biggest stage (fewest barriers) that still leaves >= 4 stages in the LDS left over by the lists
-constexpr WRing qsw_ring(int NK, int K, int MS) {
+constexpr SlabRing qsw_ring(int NK, int K, int MS) {
 #if defined(MMRAG_QSW_RING16)   // developer builds: ring of the 16x16x32 shape as G * 10 + NST (A/B of stage size vs depth)
-    if (MS == 16 && NK % (MMRAG_QSW_RING16 / 10) == 0) return WRing{MMRAG_QSW_RING16 / 10, MMRAG_QSW_RING16 % 10};
+    if (MS == 16 && NK % (MMRAG_QSW_RING16 / 10) == 0) return SlabRing{MMRAG_QSW_RING16 / 10, MMRAG_QSW_RING16 % 10};
 #endif
-    const int budget = 160 * 1024 - qsw_lists_bytes(K, MS) - QSW_XCH;
-    for (int need = 4; need >= 3; --need)
-        for (int g = 4; g >= 1; --g) {
-            if (NK % g) continue;
-            int nst = budget / (g * QS_TILE_ROWS * SLAB);
-            if (nst > 6) nst = 6;
-            if (nst >= need) return WRing{g, nst};
-        }
-    return WRing{1, 2};
+    return slab_ring(NK, qsw_lists_bytes(K, MS) + QSW_XCH);
 }
 
 // ---- one statement of the k loop = ONE asm statement: the two A-fragment reads of the NEXT statement go out first,
@@ -189,7 +165,7 @@ constexpr int CP_SC1 = 16;   // cache-policy bit of the buffer builtins' aux ope
 template <int DT, int NK, int K, int MS, bool NT>
 __global__ __launch_bounds__(256, 1) void cosine_topk_walk_kernel(const KParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    using FT = typename WFrag<DT>::T;
+    using FT = typename FragType<DT>::T;
     static_assert(MS == 32 || MS == 16, "MFMA shape");
     constexpr int R = QS_TILE_ROWS;
     static_assert(R == 64, "statements are written for 64-row tiles");
@@ -199,7 +175,7 @@ __global__ __launch_bounds__(256, 1) void cosine_topk_walk_kernel(const KParams 
     constexpr int QW = MS;                 // queries per block = lanes that hold different queries
     constexpr int NSUB = 64 / QW;          // lanes that share a query (they hold different rows)
     constexpr int NGRP = 16 / NSUB;        // groups of 4 consecutive rows per lane per query block and tile
-    constexpr WRing RING = qsw_ring(NK, K, MS);
+    constexpr SlabRing RING = qsw_ring(NK, K, MS);
     constexpr int G = RING.G, NST = RING.NST;
     constexpr int SPT = NK / G;            // ring stages per tile
     constexpr int STAGE = G * SLABB;

@@ -142,11 +142,58 @@ __device__ inline float wave_kth_largest(float a, float b, float c, float d, int
     return res;
 }
 
-// ---- query-stationary kernel (search_qs.hip) -------------------------------------------------------------
+// ---- the batch plan of the slab-ring kernel: the list search (search.hip make_plan) and the deep search's filter mode
+// (search_deep.hip) take both rules from here, which is what makes their scores bit-identical ---------------------------
+// waves along the queries (32 queries each) of a workgroup that serves B queries
+inline int plan_wn(int B) { return B <= 64 ? 2 : (B <= 128 ? 4 : 8); }
+// workgroups that walk `tiles` corpus tiles, per query group
+inline int plan_walkers(int tiles, int grid_y) {
+    const int cus = mmrag::num_cus();
+    int gx = tiles < cus ? tiles : cus;
+    if (grid_y > 1 && tiles >= cus) {
+        // all query groups of a tile resident together: cus / grid_y walkers, rounded to whole XCD rounds
+        const int w = cus / grid_y / 8 * 8;
+        gx = w >= 8 ? w : (cus / grid_y > 0 ? cus / grid_y : 1);
+    }
+    return gx < 1 ? 1 : gx;
+}
+// the argument checks of a search entry point `name` ("cosine_topk", "cosine_topk_deep") whose k goes up to k_max
+int check_search_args(const char *name, int k_max, const void *q, const void *corpus, int B, int64_t n, int d, int64_t ld,
+                      int dtype, int k);
+
+// ---- query-stationary kernels (search_qs.hip, search_qsw.hip) --------------------------------------------------------
 // supported(): storage dtype, row bytes and list depth the kernel is instantiated for
 bool qs_supported(int dtype, unsigned row_bytes, int K);
 constexpr int QS_TILE_ROWS = 64;   // corpus rows per tile
 constexpr int QS_QROWS = 256;      // queries per workgroup
+// a wave's MFMA operand fragment of 8 elements
+template <int DT>
+struct FragType;
+template <>
+struct FragType<MMRAG_F16> {
+    using T = half8_t;
+};
+template <>
+struct FragType<MMRAG_BF16> {
+    using T = bf16x8_t;
+};
+struct SlabRing {
+    int G;    // K-slabs per ring stage (one s_barrier per stage)
+    int NST;  // ring stages
+};
+// the LDS-DMA ring of a kernel whose lists (and exchange block) take `used_bytes` of the 160 KiB: the biggest stage
+// (fewest barriers) that still leaves >= 4 stages
+constexpr SlabRing slab_ring(int NK, int used_bytes) {
+    const int budget = 160 * 1024 - used_bytes;
+    for (int need = 4; need >= 3; --need)
+        for (int g = 4; g >= 1; --g) {
+            if (NK % g) continue;
+            int nst = budget / (g * QS_TILE_ROWS * SLAB);
+            if (nst > 6) nst = 6;
+            if (nst >= need) return SlabRing{g, nst};
+        }
+    return SlabRing{1, 2};
+}
 // launches over `grid_x * grid_y` workgroups of 256 threads (walkers x query groups)
 int qs_launch(int dtype, int K, const KParams &p, int grid_x, int grid_y, hipStream_t s);
 // thr0[q] = K-th largest of best[q][0 .. walkers): the threshold a sample pass yields

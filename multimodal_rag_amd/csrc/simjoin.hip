@@ -360,9 +360,7 @@ int mmrag_sim_join(const void *rows, int64_t n, int64_t ld, int dtype, int d, co
     p.count = count;
     p.T = (n + JT - 1) / JT;
     p.total = p.T * (p.T + 1) / 2;
-    if (dtype == MMRAG_F32) return launch_join<MMRAG_F32>(p, s);
-    if (dtype == MMRAG_F16) return launch_join<MMRAG_F16>(p, s);
-    return launch_join<MMRAG_BF16>(p, s);
+    return mmrag::with_elem_type(dtype, [&](auto tag) { return launch_join<decltype(tag)::value>(p, s); });
 }
 
 }  // extern "C"

@@ -189,6 +189,29 @@ def test_overflow_small_capacity_and_no_bound(N, dbg, cap):
     assert np.array_equal(s, s0) and np.array_equal(r, r0)
 
 
+def test_overflow_of_one_query_in_a_batch(N):
+    """two tiles and 256 candidate slots: query 0 ties on every row, so its 512 survivors overflow and it is re-run
+    alone.  Queries 1 and 2 have 512 distinct scores each, rising and falling with the row: whichever 256 rows the
+    bound pass kept, at least 30 of them come from one tile, so at least one of the two gets a bound with at most
+    256 survivors and is selected from the batch's slots.  Every value is exact in float16 and every sum in float32:
+    bit for bit against the oracle"""
+    d, n, k = 384, 512, 30
+    c = np.zeros((n, d), np.float32)
+    c[:, 0] = np.arange(n) / 512
+    c[:, 1] = 0.25
+    q = np.zeros((3, d), np.float32)
+    q[0, 1] = 1.0
+    q[1, 0] = 1.0
+    q[2, :2] = (-1.0, 0.5)
+    cd, cs = to_dev(N, c, torch.float16)
+    qd, qs = to_dev(N, q, torch.float16)
+    s, r = deep(N, qd, cd, n, d, k, cap=256)
+    es, er = O.cosine_topk(qs, cs, k)
+    assert np.array_equal(r, er) and np.array_equal(s, es)
+    assert np.array_equal(r[0], np.arange(k)) and np.array_equal(r[1], n - 1 - np.arange(k))
+    assert np.array_equal(r[2], np.arange(k))
+
+
 def unit(n, d, seed):
     x = np.random.default_rng(seed).standard_normal((n, d)).astype(np.float32)
     return x / np.linalg.norm(x, axis=1, keepdims=True)
