@@ -439,6 +439,48 @@ int mmrag_group_select(const float *scores, const int64_t *rows, int B, int C, c
 int mmrag_sim_join(const void *rows, int64_t n, int64_t ld, int dtype, int d, const uint32_t *alive, float threshold,
                    int64_t *out_pairs, float *out_scores, int64_t capacity, unsigned long long *count, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Topic clustering: the two device steps of a spherical k-means (Lloyd) iteration over the stored unit rows.  The
+ * reference has no counterpart: nothing in it describes what a collection holds.  The host loop (rounding the master
+ * centroids, the sort by cluster, the re-normalisation, the stop rule) is multimodal_rag_amd/index.py
+ * VectorIndex.cluster.
+ *
+ * mmrag_kmeans_assign: the nearest centroid of every row, X . C^T in 128 x 128 tiles with an arg-max epilogue; the
+ * [n, k] scores are never written.
+ * Contract
+ *   - for an alive row r: out_score[r] = max over c of dot(rows[r], centroids[c]) (float32 accumulation in one fixed
+ *     K order), out_assign[r] = the LOWEST c that attains it; a row whose alive bit is clear gets (-1, -inf);
+ *   - a row's two outputs depend on that row, the centroid matrix and d only: not on n, the bitmap, the grid or the
+ *     workgroup that ran it;
+ *   - one launch, no workspace, no host synchronisation, no atomics (the call can be captured into a graph).
+ *
+ *   rows        dev [n, ld] of `dtype` MMRAG_F32 / F16 / BF16, pad columns zero; MMRAG_F8E4M3 returns
+ *               MMRAG_EUNSUPPORTED (an FP8 collection is clustered on its re-scoring plane)
+ *   centroids   dev [k, ld], same dtype and ld, pad columns zero (the caller rounds its float32 master centroids)
+ *   ld          mmrag_padded_dim(d, dtype) or a larger width of whole 128-byte slabs
+ *   alive       dev, optional (NULL = every row): bit r & 31 of word r >> 5, at least (n + 31) / 32 words
+ *   out_assign  dev [n] int32      out_score  dev [n] float32
+ * MMRAG_EINVAL before anything is launched: a null pointer, n < 0 or >= 2^31, k < 1 or above MMRAG_MAX_CLUSTERS,
+ * d <= 0, ld < d.  n == 0 succeeds.
+ *
+ * mmrag_cluster_sums: out_sums[c, :] = the float32 sum of the rows order[seg_off[c] .. seg_off[c + 1]), c < k.
+ *   - every element of out_sums is written; an empty segment gives zeros;
+ *   - deterministic: member i of a segment goes to partial sum i % 32, each partial adds its members in segment order,
+ *     and the 32 partials are added by the fixed tree of strides 16, 8, 4, 2, 1.  A cluster's bits depend on its own
+ *     member rows in that order only: not on the other clusters, n or the grid.  No atomics, no workspace;
+ *   - one launch, no host synchronisation.
+ *
+ *   rows, ld, dtype, d   as above
+ *   order       dev [seg_off[k]] int32 row numbers, every one a row of `rows` (not checked against a count)
+ *   seg_off     dev [k + 1] int64, non-decreasing offsets into `order`
+ *   out_sums    dev [k, d] float32
+ * MMRAG_EINVAL / MMRAG_EUNSUPPORTED as for mmrag_kmeans_assign. */
+#define MMRAG_MAX_CLUSTERS 4096
+int mmrag_kmeans_assign(const void *rows, int64_t n, int64_t ld, int dtype, int d, const void *centroids, int k,
+                        const uint32_t *alive, int32_t *out_assign, float *out_score, void *stream);
+int mmrag_cluster_sums(const void *rows, int64_t ld, int dtype, int d, const int32_t *order, const int64_t *seg_off,
+                       int k, float *out_sums, void *stream);
+
 /* CLIP byte-level BPE (the text tower's tokenizer, BASELINE config 4; the reference only names CLIP in config.py:106).
  * Host code, multi-threaded; equals multimodal_rag_amd/tokenizer.py:ClipBpeTokenizer, which tests pin to
  * transformers.CLIPTokenizer.  The caller passes text already NFC-normalised, whitespace-collapsed and lower-cased.

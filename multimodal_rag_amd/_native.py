@@ -25,6 +25,7 @@ MAX_RESCORE_CANDIDATES = 4096   # mmrag_rescore_topk (MMRAG_MAX_RESCORE_CANDIDAT
 # mmrag_group_select (MMRAG_MAX_GROUP_CANDIDATES, MMRAG_MAX_GROUPS, MMRAG_MAX_GROUP_SIZE)
 MAX_GROUP_CANDIDATES, MAX_GROUPS, MAX_GROUP_SIZE = 4096, 256, 16
 MAX_JOIN_PAIRS = 1 << 26   # mmrag_sim_join (MMRAG_MAX_JOIN_PAIRS)
+MAX_CLUSTERS = 4096   # mmrag_kmeans_assign / mmrag_cluster_sums (MMRAG_MAX_CLUSTERS)
 _DT2TORCH = {F32: torch.float32, F16: torch.float16, BF16: torch.bfloat16, F8E4M3: torch.float8_e4m3fn}
 _TORCH2DT = {v: k for k, v in _DT2TORCH.items()}
 
@@ -201,6 +202,12 @@ def _declare(lib):
     for name in ("mmrag_internal_join_tile", "mmrag_internal_join_slot_tile"):
         getattr(lib, name).restype = c_int
         getattr(lib, name).argtypes = [c_int64, c_int64, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]
+    # topic clustering (csrc/kmeans.hip)
+    lib.mmrag_kmeans_assign.restype = c_int
+    lib.mmrag_kmeans_assign.argtypes = [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]
+    lib.mmrag_cluster_sums.restype = c_int
+    lib.mmrag_cluster_sums.argtypes = [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
     from .lexical import declare as declare_lexical   # BM25 analyzer, device index and search (csrc/lexical.hip)
 
     declare_lexical(lib)
@@ -475,6 +482,68 @@ def sim_join(rows: torch.Tensor, n: int, d: int, threshold: float, alive: Option
         order = torch.argsort(pairs[:, 0] * max(n, 1) + pairs[:, 1])   # n <= 2^23: the key is below 2^46
         pairs, scores = pairs[order], scores[order]
     return pairs, scores, total
+
+
+def _check_stored_rows(who: str, rows: torch.Tensor):
+    if rows.dim() != 2 or not rows.is_contiguous() or rows.dtype not in _TORCH2DT:
+        raise MMRagNativeError(f"{who}: rows must be a contiguous 2-D tensor of a storage dtype")
+
+
+def kmeans_assign(rows: torch.Tensor, n: int, d: int, centroids: torch.Tensor,
+                  alive: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Nearest centroid of each of the first n rows of `rows` [cap, ld] (include/mmrag.h mmrag_kmeans_assign):
+    `centroids` [k, ld] in the rows' dtype and padded width, pad columns zero.  `alive`: the index's bitmap (int32 words,
+    bit r & 31 of word r >> 5), None = every row.  Returns device tensors (assign [n] int32 = the lowest centroid at the
+    row's maximum dot product, score [n] float32 = that maximum); a dead row holds (-1, -inf).  One launch on the
+    current stream, no host sync."""
+    _dev_check(rows, centroids, alive)
+    _check_stored_rows("kmeans_assign", rows)
+    if (centroids.dim() != 2 or not centroids.is_contiguous() or centroids.dtype != rows.dtype
+            or centroids.shape[1] != rows.shape[1] or centroids.device != rows.device):
+        raise MMRagNativeError("kmeans_assign: centroids must be a contiguous [k, ld] tensor of the rows' dtype, padded "
+                               "width and device")
+    n = int(n)
+    if n > rows.shape[0]:
+        raise MMRagNativeError(f"kmeans_assign: n={n} exceeds the {rows.shape[0]} rows given")
+    if alive is not None and (alive.dim() != 1 or alive.dtype != torch.int32 or not alive.is_contiguous()
+                              or alive.numel() * 32 < n or alive.device != rows.device):
+        raise MMRagNativeError("kmeans_assign: alive must be a contiguous int32 bitmap of at least n bits on the rows' "
+                               "device")
+    dev = rows.device
+    # one spare element: the pointers are real at n == 0 too (an empty tensor's data_ptr() is null)
+    assign = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    score = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        st = lib().mmrag_kmeans_assign(rows.data_ptr(), n, rows.shape[1], _TORCH2DT[rows.dtype], int(d),
+                                       centroids.data_ptr(), centroids.shape[0],
+                                       alive.data_ptr() if alive is not None else None,
+                                       assign.data_ptr(), score.data_ptr(), _stream_ptr(dev))
+    _check(st, "mmrag_kmeans_assign")
+    return assign[: max(n, 0)], score[: max(n, 0)]
+
+
+def cluster_sums(rows: torch.Tensor, d: int, order: torch.Tensor, seg_off: torch.Tensor, k: int) -> torch.Tensor:
+    """Float32 sum of each cluster's member rows (include/mmrag.h mmrag_cluster_sums): `order` [m] int32 row numbers of
+    `rows` [cap, ld] sorted by cluster (the caller guarantees they are rows of it), `seg_off` [k + 1] int64 offsets of
+    the clusters' segments in `order`.  Returns sums [k, d] float32 on the device, zeros for an empty segment; identical
+    bits run to run.  One launch on the current stream, no host sync."""
+    _dev_check(rows, order, seg_off)
+    _check_stored_rows("cluster_sums", rows)
+    k = int(k)
+    if order.dim() != 1 or order.dtype != torch.int32 or not order.is_contiguous() or order.device != rows.device:
+        raise MMRagNativeError("cluster_sums: order must be a contiguous 1-D int32 tensor on the rows' device")
+    if (seg_off.dim() != 1 or seg_off.dtype != torch.int64 or not seg_off.is_contiguous()
+            or seg_off.numel() != k + 1 or seg_off.device != rows.device):
+        raise MMRagNativeError("cluster_sums: seg_off must be a contiguous int64 tensor of k + 1 offsets on the rows' "
+                               "device")
+    dev = rows.device
+    sums = torch.empty((max(k, 1), max(int(d), 1)), dtype=torch.float32, device=dev)
+    order_ptr = order.data_ptr() if order.numel() else seg_off.data_ptr()    # no members: never read
+    with torch.cuda.device(dev):
+        st = lib().mmrag_cluster_sums(rows.data_ptr(), rows.shape[1], _TORCH2DT[rows.dtype], int(d),
+                                      order_ptr, seg_off.data_ptr(), k, sums.data_ptr(), _stream_ptr(dev))
+    _check(st, "mmrag_cluster_sums")
+    return sums
 
 
 def join_tile(T: int, at: int, slot_order: bool = False) -> Tuple[int, int]:

@@ -3,6 +3,7 @@
 environment-variable overrides.  Extra keys (MMRAG_*) select the MI355X engine's options."""
 from __future__ import annotations
 
+import math
 import os
 from dataclasses import dataclass, field
 
@@ -96,11 +97,15 @@ class Settings:
     MMRAG_DEDUP_THRESHOLD: float = field(default_factory=lambda: float(os.getenv("MMRAG_DEDUP_THRESHOLD", "0")))
     MMRAG_DEDUP_REPORT_THRESHOLD: float = field(
         default_factory=lambda: float(os.getenv("MMRAG_DEDUP_REPORT_THRESHOLD", "0.98")))
+    # topic clustering (VectorIndex.cluster, csrc/kmeans.hip): the default number of topics of cluster() / GET /topics;
+    # 0 (default) = automatic, auto_topics(live rows); else 1 .. 4096
+    MMRAG_TOPICS: int = field(default_factory=lambda: int(os.getenv("MMRAG_TOPICS", "0")))
     # CLIP engines only: embed image items from their pixels (vision tower) instead of their summary text
     MMRAG_EMBED_IMAGE_PIXELS: bool = field(default_factory=lambda: _b("MMRAG_EMBED_IMAGE_PIXELS", "true"))
 
     def __post_init__(self):
         self.dedup_threshold()
+        self.topics()
 
     def dedup_threshold(self) -> float:
         """MMRAG_DEDUP_THRESHOLD checked: 0 (off) or a cosine in (0, 1]"""
@@ -108,6 +113,13 @@ class Settings:
         if not 0.0 <= t <= 1.0:     # false for NaN too
             raise ValueError(f"MMRAG_DEDUP_THRESHOLD must be 0 (off) or a cosine in (0, 1] (got {self.MMRAG_DEDUP_THRESHOLD!r})")
         return t
+
+    def topics(self) -> int:
+        """MMRAG_TOPICS checked: 0 (automatic) or a cluster count in 1 .. 4096"""
+        k = int(self.MMRAG_TOPICS)
+        if not 0 <= k <= 4096:
+            raise ValueError(f"MMRAG_TOPICS must be 0 (automatic) or in 1..4096 (got {self.MMRAG_TOPICS!r})")
+        return k
 
     def index_dtype(self):
         """MMRAG_INDEX_DTYPE as a torch dtype"""
@@ -128,6 +140,11 @@ class Settings:
         if key not in names:
             raise ValueError(f"MMRAG_F8_RESCORE must be one of {sorted(names)} (got {self.MMRAG_F8_RESCORE!r})")
         return names[key]
+
+
+def auto_topics(live: int) -> int:
+    """the automatic number of topics of `live` rows (MMRAG_TOPICS=0): min(256, max(2, round(sqrt(live / 2)))), halves up"""
+    return min(256, max(2, int(math.floor(math.sqrt(max(int(live), 0) / 2.0) + 0.5))))
 
 
 settings = Settings()

@@ -1,0 +1,399 @@
+// Topic clustering (spherical k-means over the stored unit rows): the two device steps of a Lloyd iteration
+// (include/mmrag.h mmrag_kmeans_assign, mmrag_cluster_sums).
+//
+// mmrag_kmeans_assign: X . C^T with an arg-max epilogue, the [n, k] scores never written.  The tile body is the
+// similarity join's (simjoin.hip): a workgroup is 4 waves in a 2 x 2 grid over a 128-row x 128-centroid tile, 64 x 64
+// outputs per wave as 4 x 4 MFMA tiles of 16 x 16 (v_mfma_f32_16x16x32_f16 / _bf16; float32 rows:
+// v_mfma_f32_16x16x4_f32).  Both operands arrive by the tile_dma.h ring in 128-byte K-slabs (two stages of 2 x 16 KiB,
+// so two workgroups share a CU); rows past n and centroids past k read as zero through the buffer descriptor.
+// Workgroups are persistent over row tiles.  Inside a row tile the ring runs over ALL (centroid tile, K-slab) items
+// without draining between centroid tiles; the row tile's slabs are fetched again for each centroid tile (L2).  After a
+// centroid tile's last slab every lane folds its 64 accumulators into a running (best, arg) for its 16 rows: columns
+// ascend with the centroid tile and inside the lane and only a strictly greater score replaces, so the lowest index
+// wins a tie; columns >= k are set to -inf by INDEX first (a zero column can win a row whose scores are all negative).
+// After the last centroid tile the 16 lanes that share rows are folded by an xor butterfly, the two waves that share
+// rows through LDS, both with "greater score, else lower index"; 128 threads store the tile's results coalesced.
+// The K order and the tile edges are fixed, so a row's outputs depend on the row, the centroids and d alone.
+//
+// mmrag_cluster_sums: one workgroup per (cluster, 128-byte column slab).  Thread (row lane j of 32, chunk c of 8) adds
+// the 16-byte chunk c of the segment's members j, j + 32, j + 64, ... in that order; the 32 partial sums of a column
+// are added by the fixed tree of strides 16, 8, 4, 2, 1.  No atomics, no workspace: a cluster's bits depend on its own
+// member list alone.
+#include <math.h>
+
+#include "mmrag_internal.h"
+#include "tile_dma.h"
+
+namespace mmrag_impl {
+
+constexpr int KT = 128;            // tile edge (rows and centroids per workgroup tile)
+constexpr int KM_NSTAGE = 2;
+constexpr int KM_STAGE = 2 * KT * SLAB;   // row tile then centroid tile, one K-slab each
+
+struct AssignParams {
+    const char *rows;
+    const char *centroids;
+    long long n;
+    int k;
+    unsigned row_bytes;     // ld * element size
+    int nk;                 // K-slabs that hold the d logical columns
+    int nct;                // centroid tiles
+    const unsigned *alive;
+    int *out_assign;
+    float *out_score;
+    long long T;            // row tiles
+};
+
+// (v, i) <- the better of (v, i) and (ov, oi): the greater score, else the lower index
+__device__ inline void km_better(float &v, int &i, float ov, int oi) {
+    if (ov > v || (ov == v && oi < i)) {
+        v = ov;
+        i = oi;
+    }
+}
+
+template <int DT>
+__global__ __launch_bounds__(256, 2) void kmeans_assign_kernel(const AssignParams p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int LOADS = 2 * KT / 8 / 4;   // 1 KiB DMA instructions per wave per ring item: 32 pieces over 4 waves
+    static_assert(KM_NSTAGE * KM_STAGE + 2 * KT * 8 <= 80 * 1024, "two workgroups per CU");
+    __shared__ __attribute__((aligned(1024))) char smem[KM_NSTAGE * KM_STAGE];
+    __shared__ float red_v[2][KT];
+    __shared__ int red_a[2][KT];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wm = wave >> 1, wn = wave & 1;     // this wave's 64 x 64 quadrant: rows wm * 64 .., centroids wn * 64 ..
+    const int c16 = lane & 15, g4 = lane >> 4;
+    const unsigned RB = p.row_bytes;
+    const int nk = p.nk, nct = p.nct;
+    const int total = nk * nct;
+    const float NEG_INF = -__builtin_inff();
+
+    // this wave's DMA pieces: 8 consecutive 8-row pieces of the stage (waves 0, 1: the rows; waves 2, 3: the centroids)
+    unsigned src_off[LOADS];
+#pragma unroll
+    for (int i = 0; i < LOADS; ++i) src_off[i] = dma_src_offset((wave & 1) * LOADS + i, lane, RB);
+    char *const my_dst = smem + wave * LOADS * 1024;
+
+    const int sw = (c16 >> 1) & 7;
+    const int a_base = (wm * 64 + c16) * SLAB;
+    const int b_base = KT * SLAB + (wn * 64 + c16) * SLAB;
+
+    for (long long tile = blockIdx.x; tile < p.T; tile += gridDim.x) {
+        const long long row0 = tile * KT;
+        const long long left = p.n - row0;            // >= 1
+        const int in_tile = left < KT ? (int)left : KT;
+
+        unsigned any = 1u;
+        if (p.alive != nullptr) {
+            any = 0u;
+#pragma unroll
+            for (int w = 0; w < KT / 32; ++w)
+                if (32 * w < in_tile) any |= p.alive[(row0 >> 5) + w];
+        }
+        if (any == 0u) {
+            // a tile of dead rows (uniform: the whole workgroup takes this path; no LDS is touched)
+            if ((int)threadIdx.x < in_tile) {
+                p.out_assign[row0 + threadIdx.x] = -1;
+                p.out_score[row0 + threadIdx.x] = NEG_INF;
+            }
+            continue;
+        }
+
+        const char *const rows_base = p.rows + (size_t)row0 * RB;
+        const unsigned rows_bytes = (unsigned)in_tile * RB;
+        int issued = 0, i_ct = 0, i_ks = 0;
+        auto issue = [&]() {
+            // ring item `issued` = K-slab i_ks of (this row tile, centroid tile i_ct)
+            const int c_left = p.k - i_ct * KT;
+            const char *base = wave < 2 ? rows_base : p.centroids + (size_t)i_ct * KT * RB;
+            const unsigned bytes = wave < 2 ? rows_bytes : (unsigned)(c_left < KT ? c_left : KT) * RB;
+            const __amdgpu_buffer_rsrc_t rsrc = make_rsrc(base, bytes);
+            char *dst = my_dst + (issued % KM_NSTAGE) * KM_STAGE;
+            const unsigned koff = (unsigned)i_ks * SLAB;
+#pragma unroll
+            for (int i = 0; i < LOADS; ++i)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(dst + i * 1024), 16, src_off[i] + koff, 0, 0, 0);
+            ++issued;
+            if (++i_ks == nk) {
+                i_ks = 0;
+                ++i_ct;
+            }
+        };
+
+        // running best of this lane's rows wm * 64 + 16 a + 4 g4 + r over the columns it has seen
+        float bv[4][4];
+        int ba[4][4];
+        f32x4_t acc[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                bv[a][r] = NEG_INF;
+                ba[a][r] = 0;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) acc[a][b][r] = 0.0f;
+            }
+
+        issue();
+        int ks = 0, ct = 0;
+        for (int it = 0; it < total; ++it) {
+            wait_vmcnt<0>();
+            __builtin_amdgcn_s_barrier();
+            if (issued < total) issue();
+            const char *st = smem + (it % KM_NSTAGE) * KM_STAGE;
+            // a 128-byte slab is two k-steps; lane (c16, g4) reads chunk 4 s + g4 of row c16 of every 16-row block.
+            // One fixed K order for every (row, centroid): the score bits do not depend on the tile or the grid.
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const int off = ((4 * s + g4) ^ sw) * 16;
+                if constexpr (DT == MMRAG_F32) {
+                    // exact float32: chunk 4 s + g4 holds four consecutive floats of the row; MFMA e takes element e of
+                    // every lane's chunk, the same k for both operands
+                    f32x4_t fa[4], fb[4];
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) fa[a] = *(const f32x4_t *)(st + a_base + a * (16 * SLAB) + off);
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) fb[b] = *(const f32x4_t *)(st + b_base + b * (16 * SLAB) + off);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+#pragma unroll
+                        for (int a = 0; a < 4; ++a)
+#pragma unroll
+                            for (int b = 0; b < 4; ++b)
+                                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[a][e], fb[b][e], acc[a][b], 0, 0, 0);
+                } else if constexpr (DT == MMRAG_F16) {
+                    half8_t fa[4], fb[4];
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) fa[a] = *(const half8_t *)(st + a_base + a * (16 * SLAB) + off);
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) fb[b] = *(const half8_t *)(st + b_base + b * (16 * SLAB) + off);
+#pragma unroll
+                    for (int a = 0; a < 4; ++a)
+#pragma unroll
+                        for (int b = 0; b < 4; ++b)
+                            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[a], fb[b], acc[a][b], 0, 0, 0);
+                } else {
+                    bf16x8_t fa[4], fb[4];
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) fa[a] = *(const bf16x8_t *)(st + a_base + a * (16 * SLAB) + off);
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) fb[b] = *(const bf16x8_t *)(st + b_base + b * (16 * SLAB) + off);
+#pragma unroll
+                    for (int a = 0; a < 4; ++a)
+#pragma unroll
+                        for (int b = 0; b < 4; ++b)
+                            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], fb[b], acc[a][b], 0, 0, 0);
+                }
+            }
+            if (++ks == nk) {
+                // ---- the centroid tile is complete: acc[a][b][r] = <row wm*64 + 16a + 4 g4 + r, centroid col0 + 16b>
+                ks = 0;
+                const int col0 = ct * KT + wn * 64 + c16;
+                const bool ragged = (ct + 1) * KT > p.k;     // uniform: only the last centroid tile can hold columns >= k
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const int col = col0 + 16 * b;
+                    const bool pad = ragged && col >= p.k;
+#pragma unroll
+                    for (int a = 0; a < 4; ++a)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float v = pad ? NEG_INF : acc[a][b][r];
+                            if (v > bv[a][r]) {
+                                bv[a][r] = v;
+                                ba[a][r] = col;
+                            }
+                            acc[a][b][r] = 0.0f;
+                        }
+                }
+                ++ct;
+            }
+        }
+
+        // ---- fold the 16 lanes that hold other columns of the same rows, then the two waves wn = 0, 1
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+#pragma unroll
+                for (int m = 1; m < 16; m <<= 1) {
+                    const float ov = __shfl_xor(bv[a][r], m);
+                    const int oa = __shfl_xor(ba[a][r], m);
+                    km_better(bv[a][r], ba[a][r], ov, oa);
+                }
+                if (c16 == 0) {
+                    red_v[wn][wm * 64 + 16 * a + 4 * g4 + r] = bv[a][r];
+                    red_a[wn][wm * 64 + 16 * a + 4 * g4 + r] = ba[a][r];
+                }
+            }
+        __syncthreads();   // also: every wave is done with the ring before the next tile's first slab lands
+        if ((int)threadIdx.x < in_tile) {
+            const int t = threadIdx.x;
+            float v = red_v[0][t];
+            int arg = red_a[0][t];
+            km_better(v, arg, red_v[1][t], red_a[1][t]);
+            const long long row = row0 + t;
+            if (p.alive != nullptr && ((p.alive[row >> 5] >> (row & 31)) & 1u) == 0u) {
+                v = NEG_INF;
+                arg = -1;
+            }
+            p.out_assign[row] = arg;
+            p.out_score[row] = v;
+        }
+        // the next tile writes red_* only after its item loop's barriers, which every thread reaches after these reads
+    }
+#endif
+}
+
+template <int DT>
+static int launch_assign(const AssignParams &p, hipStream_t s) {
+    long long g = 2LL * mmrag::num_cus();    // persistent grid: two workgroups per CU (the LDS allows two)
+    if (g > p.T) g = p.T;
+    hipLaunchKernelGGL(kmeans_assign_kernel<DT>, dim3((unsigned)g), dim3(256), 0, s, p);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    return MMRAG_OK;
+}
+
+// ---- cluster sums ------------------------------------------------------------------------------------------------
+constexpr int CS_LANES = 32;    // row lanes of a workgroup: member i of the segment belongs to lane i % 32
+
+struct SumsParams {
+    const char *rows;
+    unsigned row_bytes;
+    int d;
+    const int *order;
+    const long long *seg_off;
+    float *out_sums;
+};
+
+template <int DT>
+__global__ __launch_bounds__(256) void cluster_sums_kernel(const SumsParams p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int PER = DT == MMRAG_F32 ? 4 : 8;     // elements of a 16-byte chunk
+    constexpr int COLS = 8 * PER;                    // columns of a 128-byte slab
+    __shared__ float part[CS_LANES][COLS + 1];
+    const int chunk = threadIdx.x & 7, rl = threadIdx.x >> 3;
+    const int slab = blockIdx.x, c = blockIdx.y;   // k <= 4096 fits grid.y; a row holds up to 2^17 slabs
+    const long long lo = p.seg_off[c], hi = p.seg_off[c + 1];
+    const char *const col_base = p.rows + (size_t)slab * SLAB + chunk * 16;
+
+    float acc[PER];
+#pragma unroll
+    for (int e = 0; e < PER; ++e) acc[e] = 0.0f;
+    auto add = [&](int row) {
+        const char *src = col_base + (size_t)row * p.row_bytes;
+        if constexpr (DT == MMRAG_F32) {
+            const f32x4_t v = *(const f32x4_t *)src;
+#pragma unroll
+            for (int e = 0; e < PER; ++e) acc[e] += v[e];
+        } else if constexpr (DT == MMRAG_F16) {
+            const half8_t v = *(const half8_t *)src;
+#pragma unroll
+            for (int e = 0; e < PER; ++e) acc[e] += (float)v[e];
+        } else {
+            const bf16x8_t v = *(const bf16x8_t *)src;
+#pragma unroll
+            for (int e = 0; e < PER; ++e) acc[e] += (float)v[e];
+        }
+    };
+    // members rl, rl + 32, ... in order; four row numbers are fetched ahead so their loads overlap
+    long long i = lo + rl;
+    for (; i + 3 * CS_LANES < hi; i += 4 * CS_LANES) {
+        const int r0 = p.order[i], r1 = p.order[i + CS_LANES], r2 = p.order[i + 2 * CS_LANES], r3 = p.order[i + 3 * CS_LANES];
+        add(r0);
+        add(r1);
+        add(r2);
+        add(r3);
+    }
+    for (; i < hi; i += CS_LANES) add(p.order[i]);
+
+#pragma unroll
+    for (int e = 0; e < PER; ++e) part[rl][chunk * PER + e] = acc[e];
+    __syncthreads();
+    if ((int)threadIdx.x < COLS) {
+        float s[CS_LANES];
+#pragma unroll
+        for (int j = 0; j < CS_LANES; ++j) s[j] = part[j][threadIdx.x];
+#pragma unroll
+        for (int stride = CS_LANES / 2; stride >= 1; stride >>= 1)
+#pragma unroll
+            for (int j = 0; j < stride; ++j) s[j] += s[j + stride];
+        const int col = slab * COLS + threadIdx.x;
+        if (col < p.d) p.out_sums[(size_t)c * p.d + col] = s[0];
+    }
+#endif
+}
+
+template <int DT>
+static int launch_sums(const SumsParams &p, int k, int slabs, hipStream_t s) {
+    hipLaunchKernelGGL(cluster_sums_kernel<DT>, dim3((unsigned)slabs, (unsigned)k), dim3(256), 0, s, p);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    return MMRAG_OK;
+}
+
+// the checks the two entry points share; FP8 is reported, not joined
+static int check_rows(const char *who, int64_t ld, int dtype, int d, int k) {
+    MMRAG_CHECK_ARG(dtype >= 0 && dtype <= MMRAG_F8E4M3, "%s: bad dtype %d", who, dtype);
+    MMRAG_CHECK_ARG(d > 0 && ld >= d, "%s: need 0 < d <= ld (d=%d ld=%lld)", who, d, (long long)ld);
+    MMRAG_CHECK_ARG(k >= 1 && k <= MMRAG_MAX_CLUSTERS, "%s: k=%d outside 1..%d", who, k, MMRAG_MAX_CLUSTERS);
+    if (dtype == MMRAG_F8E4M3) {
+        mmrag::set_error("%s: float8_e4m3 rows are not clustered; cluster the collection's re-scoring plane", who);
+        return MMRAG_EUNSUPPORTED;
+    }
+    MMRAG_CHECK_ARG(ld * mmrag::esize(dtype) % SLAB == 0 && ld * mmrag::esize(dtype) <= (1LL << 24),
+                    "%s: ld must cover whole 128-byte slabs (mmrag_padded_dim), rows of at most 16 MiB (ld=%lld)", who,
+                    (long long)ld);
+    return MMRAG_OK;
+}
+
+}  // namespace mmrag_impl
+
+extern "C" {
+
+int mmrag_kmeans_assign(const void *rows, int64_t n, int64_t ld, int dtype, int d, const void *centroids, int k,
+                        const uint32_t *alive, int32_t *out_assign, float *out_score, void *stream) {
+    using namespace mmrag_impl;
+    MMRAG_CHECK_ARG(rows && centroids && out_assign && out_score, "kmeans_assign: null pointer");
+    MMRAG_CHECK_ARG(n >= 0 && n < (1LL << 31), "kmeans_assign: need 0 <= n < 2^31 (n=%lld)", (long long)n);
+    const int st = check_rows("kmeans_assign", ld, dtype, d, k);
+    if (st != MMRAG_OK) return st;
+    if (n == 0) return MMRAG_OK;
+    const int es = mmrag::esize(dtype);
+    AssignParams p;
+    p.rows = (const char *)rows;
+    p.centroids = (const char *)centroids;
+    p.n = n;
+    p.k = k;
+    p.row_bytes = (unsigned)(ld * es);
+    p.nk = (int)(((long long)d * es + SLAB - 1) / SLAB);
+    p.nct = (k + KT - 1) / KT;
+    p.alive = alive;
+    p.out_assign = out_assign;
+    p.out_score = out_score;
+    p.T = (n + KT - 1) / KT;
+    hipStream_t s = (hipStream_t)stream;
+    return mmrag::with_elem_type(dtype, [&](auto tag) { return launch_assign<decltype(tag)::value>(p, s); });
+}
+
+int mmrag_cluster_sums(const void *rows, int64_t ld, int dtype, int d, const int32_t *order, const int64_t *seg_off,
+                       int k, float *out_sums, void *stream) {
+    using namespace mmrag_impl;
+    MMRAG_CHECK_ARG(rows && order && seg_off && out_sums, "cluster_sums: null pointer");
+    const int st = check_rows("cluster_sums", ld, dtype, d, k);
+    if (st != MMRAG_OK) return st;
+    const int es = mmrag::esize(dtype);
+    SumsParams p;
+    p.rows = (const char *)rows;
+    p.row_bytes = (unsigned)(ld * es);
+    p.d = d;
+    p.order = order;
+    p.seg_off = (const long long *)seg_off;
+    p.out_sums = out_sums;
+    const int slabs = (int)(((long long)d * es + SLAB - 1) / SLAB);
+    hipStream_t s = (hipStream_t)stream;
+    return mmrag::with_elem_type(dtype, [&](auto tag) { return launch_sums<decltype(tag)::value>(p, k, slabs, s); });
+}
+
+}  // extern "C"

@@ -48,6 +48,7 @@ _NEEDS_MMR = ("mmr_query", "MMR retrieval needs a single-GPU collection (VectorI
 _NEEDS_GROUPING = ("grouped_query", "grouped retrieval needs a single-GPU collection (VectorIndex)")
 _NEEDS_DEDUP = ("near_duplicates", "near-duplicate detection needs a single-GPU collection (VectorIndex) with "
                                    "full-precision rows")
+_NEEDS_CLUSTERING = ("cluster", "topic clustering needs a single-GPU collection (VectorIndex) with full-precision rows")
 _dedup_warned = False    # "MMRAG_DEDUP_THRESHOLD is set but this collection cannot de-duplicate": once per process
 # the answer of a batch's query that could not be answered, before its 'error' (copied for every such query)
 _EMPTY = {key: [] for key in RESULT_KEYS}
@@ -457,16 +458,19 @@ class EmbeddingManager:
         await self._ready()
         if not self.supports_dedup():
             raise ValueError(_NEEDS_DEDUP[1])
-        fn = getattr(self.collection, method)
+        return await self._refusing_call(label, getattr(self.collection, method), threshold=threshold,
+                                         where={"doc_id": doc_id} if doc_id else None, max_pairs=max_pairs)
 
+    async def _refusing_call(self, label: str, fn, **kw):
+        """fn(**kw) through _engine_call; a ValueError of fn's (a bad threshold, a truncated report, a bad cluster count)
+        is the caller's answer, not worth a retry: raised as it is"""
         def run(**kw):
             try:
                 return fn(**kw)
-            except ValueError as refusal:     # a bad threshold, a truncated report: not worth a retry
+            except ValueError as refusal:
                 return refusal
 
-        out = await self._engine_call(label, run, threshold=threshold, where={"doc_id": doc_id} if doc_id else None,
-                                      max_pairs=max_pairs)
+        out = await self._engine_call(label, run, **kw)
         if isinstance(out, ValueError):
             raise out
         return out
@@ -482,6 +486,32 @@ class EmbeddingManager:
         """Delete all but the earliest stored member of every near-duplicate group (VectorIndex.drop_duplicates);
         returns the deleted ids.  ValueError, and nothing deleted, when the groups would come from a truncated report."""
         return await self._dedup_call("Remove duplicates", "drop_duplicates", threshold, doc_id, max_pairs)
+
+    def supports_clustering(self) -> bool:
+        """True when the collection can report its topics (where supports_dedup() is: a single-GPU VectorIndex with
+        full-precision rows; not the sharded serving path)"""
+        return self.collection is None or (hasattr(self.collection, "cluster") and self._has_full_rows())
+
+    async def cluster_topics(self, n_topics: Optional[int] = None, doc_id: Optional[str] = None,
+                             representatives: int = 3, seed: int = 0) -> Dict[str, Any]:
+        """The topics of the collection, of one document's chunks with `doc_id` (VectorIndex.cluster): its report
+        without the centroid tensor, every representative expanded to {"id", "score", "document", "metadata"}.
+        n_topics None: MMRAG_TOPICS.  ValueError for a cluster count the collection refuses."""
+        await self._ready()
+        if not self.supports_clustering():
+            raise ValueError(_NEEDS_CLUSTERING[1])
+        report = await self._refusing_call("Cluster topics", self.collection.cluster, n_clusters=n_topics,
+                                           where={"doc_id": doc_id} if doc_id else None,
+                                           representatives=representatives, seed=seed)
+        report = {key: val for key, val in report.items() if key != "centroids"}
+        wanted = [i for c in report["clusters"] for i, _ in c["representatives"]]
+        got = self.collection.get(ids=wanted, include=["metadatas", "documents"]) if wanted else {"ids": []}
+        row = {i: at for at, i in enumerate(got["ids"])}
+        for c in report["clusters"]:
+            c["representatives"] = [{"id": i, "score": s, "document": got["documents"][row[i]] if i in row else None,
+                                     "metadata": got["metadatas"][row[i]] if i in row else {}}
+                                    for i, s in c["representatives"]]
+        return report
 
     def supports_grouping(self) -> bool:
         """True when the collection can answer grouped_query (a single-GPU VectorIndex; not the sharded serving path,

@@ -11,7 +11,8 @@ kernel's 128-byte slabs); ids / documents / metadata stay in host tables indexed
 SURVEY.md section 8b "Ownership" lays out.  Search is exact (fused MFMA GEMM + top-k in
 libmmrag.so), distance = 1 - cos (the committed collection's hnsw:space=cosine).
 
-No vector arithmetic happens in this file: torch provides device buffers and copies only.
+No arithmetic over the stored rows happens in this file: torch provides device buffers and copies, and in cluster() the
+sort of the labels and the [k, d] centroid update between the two kernels of csrc/kmeans.hip.
 """
 from __future__ import annotations
 
@@ -528,6 +529,137 @@ class VectorIndex:
                                  f"exceed max_pairs={max_pairs}; nothing was deleted (raise max_pairs or the threshold)")
             victims = [s for group in report["groups"] for s in group[1:]]
             return self.delete(ids=victims) if victims else []
+
+    # ------------------------------------------------------------------ topic clustering ----
+    def _cluster_k(self, n_clusters: Optional[int], init, live: int) -> int:
+        """the number of clusters of cluster(...): explicit, from `init`, or MMRAG_TOPICS (0 = automatic), see there"""
+        from .config import auto_topics, settings
+
+        if init is not None:
+            if n_clusters is not None and int(n_clusters) != len(init):
+                raise ValueError(f"cluster: n_clusters={n_clusters} but init names {len(init)} rows")
+            n_clusters = len(init)
+        if n_clusters is None:
+            k = settings.topics() or auto_topics(live)
+            return min(k, live)
+        k = int(n_clusters)
+        if not 1 <= k <= _native.MAX_CLUSTERS:
+            raise ValueError(f"cluster: n_clusters must be in 1..{_native.MAX_CLUSTERS} (got {n_clusters!r})")
+        if live and k > live:
+            raise ValueError(f"cluster: n_clusters={k} exceeds the {live} live rows that match")
+        return k
+
+    def cluster(self, n_clusters: Optional[int] = None, where: Optional[Dict[str, Any]] = None, max_iter: int = 25,
+                tol: float = 1e-3, seed: int = 0, init: Optional[Sequence[str]] = None, representatives: int = 3,
+                return_labels: bool = False) -> Dict[str, Any]:
+        """Topics of the collection: spherical k-means over the live rows (matching `where`), on the full-precision rows
+        (an FP8 collection's re-scoring plane).  The two hot steps are csrc/kmeans.hip (nearest centroid of every row;
+        deterministic per-cluster sums); the rest is torch on [k, d] and a device sort.  It changes no search result.
+
+        k: `n_clusters`, else len(init), else MMRAG_TOPICS, whose 0 means min(256, max(2, round(sqrt(live / 2)))); a
+        default k is capped at the live rows, an explicit one above them (or outside 1..4096) is a ValueError.
+        Seeds: the rows of the stored ids `init` (k distinct live matching ids), else k distinct live rows drawn
+        reproducibly from (`seed`, the live rows, k).
+        One iteration: round the float32 master centroids to the storage dtype; assign; count the rows that changed
+        cluster; stop (converged) when at most tol * live rows changed and no cluster is empty; else each centroid
+        becomes sum / |sum| of its members and every empty (or zero-sum) cluster, in index order, takes the alive row
+        with the lowest score (distinct rows, ties to the lower row).  One host synchronisation per iteration.  After
+        `max_iter` iterations without convergence one more assign follows, so labels, scores and centroids agree.
+
+        Returns {"n_clusters", "iterations" (assign + update rounds), "converged", "objective": the mean score of the
+        live rows after every assign, "clusters": [{"cluster", "size", "cohesion" (mean cosine to the centroid),
+        "representatives": [(id, cosine)] best first, ties to the lower row, "documents": the five most frequent doc_id
+        values [(value, count)]}] by size descending then cluster index, "centroids": float32 [k, d] on the device}
+        and, with return_labels, "labels": {id: cluster}.  No matching row: a report without clusters."""
+        if int(max_iter) < 1 or not float(tol) >= 0.0 or int(representatives) < 0:
+            raise ValueError("cluster: need max_iter >= 1, tol >= 0 and representatives >= 0")
+        with self._lock:
+            self._need_plane("cluster")
+            live_rows = self._rows_where(where)
+            m = int(live_rows.size)
+            k = self._cluster_k(n_clusters, init, m)
+            if m == 0:
+                out = {"n_clusters": 0, "iterations": 0, "converged": True, "objective": [], "clusters": [],
+                       "centroids": torch.zeros((0, self.dim), dtype=torch.float32, device=self.device)}
+                if return_labels:
+                    out["labels"] = {}
+                return out
+            if init is not None:
+                seeds = [self._row_of.get(i, -1) for i in init]
+                ok = set(live_rows.tolist())
+                if len(set(seeds)) != k or any(r not in ok for r in seeds):
+                    raise ValueError("cluster: init must name distinct stored ids of live rows that match `where`")
+                seeds = np.asarray(seeds, dtype=np.int64)
+            else:
+                seeds = np.random.default_rng(int(seed)).choice(live_rows, k, replace=False)
+            rows, n, d, dev = self._full, self._n, self.dim, self.device
+            bits = self._where_bits(where)
+            cent = rows[torch.from_numpy(seeds).to(dev), :d].float()           # float32 master centroids [k, d]
+            packed = torch.zeros((k, rows.shape[1]), dtype=rows.dtype, device=dev)
+
+            def assign():
+                packed[:, :d] = cent.to(rows.dtype)
+                return _native.kmeans_assign(rows, n, d, packed, alive=bits)
+
+            def live_mean(score):
+                return float(torch.where(labels >= 0, score, torch.zeros_like(score)).double().sum().item()) / m
+
+            prev = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            objective: List[float] = []
+            iterations, converged = 0, False
+            for _ in range(int(max_iter)):
+                labels, score = assign()
+                iterations += 1
+                # members by cluster, ascending rows inside one; dead rows (label -1) sort first and are skipped by seg_off
+                order = torch.sort(labels, stable=True).indices.to(torch.int32)
+                seg_off = torch.cumsum(torch.bincount(labels.long() + 1, minlength=k + 1), 0)
+                sums = _native.cluster_sums(rows, d, order, seg_off, k)
+                norms = torch.linalg.vector_norm(sums, dim=1)
+                bad = (seg_off[1:] == seg_off[:-1]) | (norms == 0)
+                changed, n_bad = torch.stack([(labels != prev).sum(), bad.sum()]).tolist()    # the iteration's one sync
+                objective.append(live_mean(score))
+                prev = labels
+                if changed <= tol * m and n_bad == 0:
+                    converged = True
+                    break
+                cent = sums / torch.where(norms > 0, norms, torch.ones_like(norms)).unsqueeze(1)
+                if n_bad:
+                    # score ascending, ties to the lower row (stable); dead rows hold -inf: push them behind
+                    low = torch.sort(torch.where(labels >= 0, score, torch.full_like(score, float("inf"))),
+                                     stable=True).indices[:n_bad]
+                    cent[bad.nonzero().squeeze(1)] = rows[low, :d].float()
+            if not converged:
+                labels, score = assign()
+                objective.append(live_mean(score))
+
+            # ---- the report (not a hot path): members by (cluster, cosine descending, row ascending)
+            live_dev = (labels >= 0).nonzero().squeeze(1)
+            by_score = live_dev[torch.sort(score[live_dev], descending=True, stable=True).indices]
+            by_cluster = by_score[torch.sort(labels[by_score], stable=True).indices]
+            members = by_cluster.cpu().numpy()
+            labels_h, score_h = labels.cpu().numpy(), score.cpu().numpy().astype(np.float64)
+            sizes = np.bincount(labels_h[members], minlength=k)
+            starts = np.concatenate([[0], np.cumsum(sizes)])
+            ids, metas = self._ids, self._metadatas
+            clusters = []
+            for c in range(k):
+                mine = members[starts[c]: starts[c + 1]]
+                docs: Dict[Any, int] = {}
+                for r in np.sort(mine).tolist():
+                    v = metas[r].get("doc_id")
+                    if v is not None:
+                        docs[v] = docs.get(v, 0) + 1
+                clusters.append({
+                    "cluster": c, "size": int(sizes[c]),
+                    "cohesion": float(score_h[mine].mean()) if mine.size else 0.0,
+                    "representatives": [(ids[r], float(score_h[r])) for r in mine[: int(representatives)].tolist()],
+                    "documents": sorted(docs.items(), key=lambda kv: -kv[1])[:5]})    # stable: ties by first appearance
+            clusters.sort(key=lambda c: (-c["size"], c["cluster"]))
+            out = {"n_clusters": k, "iterations": iterations, "converged": converged, "objective": objective,
+                   "clusters": clusters, "centroids": cent}
+            if return_labels:
+                out["labels"] = {ids[r]: int(labels_h[r]) for r in np.sort(members).tolist()}
+            return out
 
     def add_rows_device(self, rows_packed: torch.Tensor, documents, metadatas, ids,
                         plane_rows: Optional[torch.Tensor] = None):

@@ -80,6 +80,13 @@ DEDUP_NEEDS = ("find_duplicates", "supports_dedup",
                "(MMRAG_F8_RESCORE=float16)")
 
 
+# /topics: the same for topic clustering
+TOPICS_NEEDS = ("cluster_topics", "supports_clustering",
+                "Topic clustering is not available with this embedder: it needs a single-GPU collection "
+                "(EmbeddingManager.cluster_topics); a float8_e4m3fn collection also needs its re-scoring plane "
+                "(MMRAG_F8_RESCORE=float16)")
+
+
 class QueryResponse(BaseModel):  # api.py:167-170
     answer: str
     sources: List[dict]
@@ -164,14 +171,15 @@ class Pipeline:
         return {"doc_id": doc_id, "filename": filename, "doc_type": tree.get("doc_type", "unknown"),
                 "chunks_processed": stored}
 
-    def need_dedup(self):
-        method, supports, detail = DEDUP_NEEDS
+    def _need(self, needs):
+        """400 with the detail of `needs` unless the embedder has its method and says it supports it"""
+        method, supports, detail = needs
         if not (hasattr(self.embedder, method) and getattr(self.embedder, supports, lambda: True)()):
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=detail)
 
     async def duplicates(self, threshold: Optional[float], doc_id: Optional[str], limit: int) -> dict:
         """the near-duplicate report (EmbeddingManager.find_duplicates) with `pairs` cut to `limit`"""
-        self.need_dedup()
+        self._need(DEDUP_NEEDS)
         try:
             report = await self.embedder.find_duplicates(threshold=threshold, doc_id=doc_id)
         except ValueError as e:
@@ -180,8 +188,25 @@ class Pipeline:
                 "pairs": [{"a": a, "b": b, "cosine": c} for a, b, c in report["pairs"][:max(limit, 0)]],
                 "groups": [{"keep": g[0], "duplicates": list(g[1:])} for g in report["groups"]]}
 
+    async def topics(self, n_topics: Optional[int], doc_id: Optional[str], representatives: int, seed: int) -> dict:
+        """the topic report (EmbeddingManager.cluster_topics); `objective` is its last value"""
+        self._need(TOPICS_NEEDS)
+        if not 1 <= representatives <= 10:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail="representatives must be in 1..10")
+        try:
+            report = await self.embedder.cluster_topics(n_topics=n_topics, doc_id=doc_id,
+                                                        representatives=representatives, seed=seed)
+        except ValueError as e:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
+        return {"n_topics": report["n_clusters"], "iterations": report["iterations"], "converged": report["converged"],
+                "objective": report["objective"][-1] if report["objective"] else None,
+                "topics": [{"topic": c["cluster"], "size": c["size"], "cohesion": c["cohesion"],
+                            "representatives": c["representatives"],
+                            "documents": [{"doc_id": v, "count": n} for v, n in c["documents"]]}
+                           for c in report["clusters"]]}
+
     async def remove_duplicates(self, threshold: Optional[float], doc_id: Optional[str]) -> dict:
-        self.need_dedup()
+        self._need(DEDUP_NEEDS)
         try:
             gone = await self.embedder.remove_duplicates(threshold=threshold, doc_id=doc_id)
         except DuplicateReportTruncated as e:
@@ -379,6 +404,12 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
     @_as_http_500
     async def remove_duplicates(threshold: Optional[float] = None, doc_id: Optional[str] = None):
         return await pipe.remove_duplicates(threshold, doc_id)
+
+    @app.get("/topics")
+    @_as_http_500
+    async def topics(n_topics: Optional[int] = None, doc_id: Optional[str] = None, representatives: int = 3,
+                     seed: int = 0):
+        return await pipe.topics(n_topics, doc_id, representatives, seed)
 
     @app.get("/stats")
     @_as_http_500
