@@ -450,6 +450,20 @@ def group_select(scores: torch.Tensor, rows: torch.Tensor, group_of_row: torch.T
     return out_s, out_r, out_p, out_g, out_i
 
 
+def _check_stored_rows(who: str, rows: torch.Tensor):
+    if rows.dim() != 2 or not rows.is_contiguous() or rows.dtype not in _TORCH2DT:
+        raise MMRagNativeError(f"{who}: rows must be a contiguous 2-D tensor of a storage dtype")
+
+
+def _check_alive(who: str, alive: Optional[torch.Tensor], n: int, rows: torch.Tensor):
+    """the first n of `rows` are given, and `alive` (None = every row) is the index's bitmap of at least n bits"""
+    if n > rows.shape[0]:
+        raise MMRagNativeError(f"{who}: n={n} exceeds the {rows.shape[0]} rows given")
+    if alive is not None and (alive.dim() != 1 or alive.dtype != torch.int32 or not alive.is_contiguous()
+                              or alive.numel() * 32 < n or alive.device != rows.device):
+        raise MMRagNativeError(f"{who}: alive must be a contiguous int32 bitmap of at least n bits on the rows' device")
+
+
 def sim_join(rows: torch.Tensor, n: int, d: int, threshold: float, alive: Optional[torch.Tensor] = None,
              capacity: int = 1 << 20) -> Tuple[torch.Tensor, torch.Tensor, int]:
     """Exact threshold self-join of the first n rows of `rows` [cap, ld] (include/mmrag.h mmrag_sim_join): every pair
@@ -458,14 +472,9 @@ def sim_join(rows: torch.Tensor, n: int, d: int, threshold: float, alive: Option
     qualifying pairs, m = min(total, capacity) of them are returned, sorted on the device by (i, j).  One launch on the
     current stream, then ONE synchronisation to read the count."""
     _dev_check(rows, alive)
-    if rows.dim() != 2 or not rows.is_contiguous() or rows.dtype not in _TORCH2DT:
-        raise MMRagNativeError("sim_join: rows must be a contiguous 2-D tensor of a storage dtype")
+    _check_stored_rows("sim_join", rows)
     n, cap = int(n), int(capacity)
-    if n > rows.shape[0]:
-        raise MMRagNativeError(f"sim_join: n={n} exceeds the {rows.shape[0]} rows given")
-    if alive is not None and (alive.dim() != 1 or alive.dtype != torch.int32 or not alive.is_contiguous()
-                              or alive.numel() * 32 < n or alive.device != rows.device):
-        raise MMRagNativeError("sim_join: alive must be a contiguous int32 bitmap of at least n bits on the rows' device")
+    _check_alive("sim_join", alive, n, rows)
     dev = rows.device
     pairs = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=dev)
     scores = torch.empty(max(cap, 1), dtype=torch.float32, device=dev)
@@ -484,11 +493,6 @@ def sim_join(rows: torch.Tensor, n: int, d: int, threshold: float, alive: Option
     return pairs, scores, total
 
 
-def _check_stored_rows(who: str, rows: torch.Tensor):
-    if rows.dim() != 2 or not rows.is_contiguous() or rows.dtype not in _TORCH2DT:
-        raise MMRagNativeError(f"{who}: rows must be a contiguous 2-D tensor of a storage dtype")
-
-
 def kmeans_assign(rows: torch.Tensor, n: int, d: int, centroids: torch.Tensor,
                   alive: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Nearest centroid of each of the first n rows of `rows` [cap, ld] (include/mmrag.h mmrag_kmeans_assign):
@@ -503,12 +507,7 @@ def kmeans_assign(rows: torch.Tensor, n: int, d: int, centroids: torch.Tensor,
         raise MMRagNativeError("kmeans_assign: centroids must be a contiguous [k, ld] tensor of the rows' dtype, padded "
                                "width and device")
     n = int(n)
-    if n > rows.shape[0]:
-        raise MMRagNativeError(f"kmeans_assign: n={n} exceeds the {rows.shape[0]} rows given")
-    if alive is not None and (alive.dim() != 1 or alive.dtype != torch.int32 or not alive.is_contiguous()
-                              or alive.numel() * 32 < n or alive.device != rows.device):
-        raise MMRagNativeError("kmeans_assign: alive must be a contiguous int32 bitmap of at least n bits on the rows' "
-                               "device")
+    _check_alive("kmeans_assign", alive, n, rows)
     dev = rows.device
     # one spare element: the pointers are real at n == 0 too (an empty tensor's data_ptr() is null)
     assign = torch.empty(max(n, 1), dtype=torch.int32, device=dev)

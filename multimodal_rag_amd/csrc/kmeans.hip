@@ -1,11 +1,9 @@
 // Topic clustering (spherical k-means over the stored unit rows): the two device steps of a Lloyd iteration
 // (include/mmrag.h mmrag_kmeans_assign, mmrag_cluster_sums).
 //
-// mmrag_kmeans_assign: X . C^T with an arg-max epilogue, the [n, k] scores never written.  The tile body is the
-// similarity join's (simjoin.hip): a workgroup is 4 waves in a 2 x 2 grid over a 128-row x 128-centroid tile, 64 x 64
-// outputs per wave as 4 x 4 MFMA tiles of 16 x 16 (v_mfma_f32_16x16x32_f16 / _bf16; float32 rows:
-// v_mfma_f32_16x16x4_f32).  Both operands arrive by the tile_dma.h ring in 128-byte K-slabs (two stages of 2 x 16 KiB,
-// so two workgroups share a CU); rows past n and centroids past k read as zero through the buffer descriptor.
+// mmrag_kmeans_assign: X . C^T with an arg-max epilogue, the [n, k] scores never written.  The tile body (LDS ring, DMA
+// split, MFMA fragments, K order) is pair_tile.h's, the one the similarity join runs, with a 128-row tile as A and a
+// 128-centroid tile as B; rows past n and centroids past k read as zero through the buffer descriptor.
 // Workgroups are persistent over row tiles.  Inside a row tile the ring runs over ALL (centroid tile, K-slab) items
 // without draining between centroid tiles; the row tile's slabs are fetched again for each centroid tile (L2).  After a
 // centroid tile's last slab every lane folds its 64 accumulators into a running (best, arg) for its 16 rows: columns
@@ -21,14 +19,9 @@
 // member list alone.
 #include <math.h>
 
-#include "mmrag_internal.h"
-#include "tile_dma.h"
+#include "pair_tile.h"
 
 namespace mmrag_impl {
-
-constexpr int KT = 128;            // tile edge (rows and centroids per workgroup tile)
-constexpr int KM_NSTAGE = 2;
-constexpr int KM_STAGE = 2 * KT * SLAB;   // row tile then centroid tile, one K-slab each
 
 struct AssignParams {
     const char *rows;
@@ -55,41 +48,28 @@ __device__ inline void km_better(float &v, int &i, float ov, int oi) {
 template <int DT>
 __global__ __launch_bounds__(256, 2) void kmeans_assign_kernel(const AssignParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int LOADS = 2 * KT / 8 / 4;   // 1 KiB DMA instructions per wave per ring item: 32 pieces over 4 waves
-    static_assert(KM_NSTAGE * KM_STAGE + 2 * KT * 8 <= 80 * 1024, "two workgroups per CU");
-    __shared__ __attribute__((aligned(1024))) char smem[KM_NSTAGE * KM_STAGE];
-    __shared__ float red_v[2][KT];
-    __shared__ int red_a[2][KT];
+    static_assert(PT_LDS + 2 * PT * 8 <= 80 * 1024, "two workgroups per CU");
+    __shared__ __attribute__((aligned(1024))) char smem[PT_LDS];
+    __shared__ float red_v[2][PT];
+    __shared__ int red_a[2][PT];
 
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wave >> 1, wn = wave & 1;     // this wave's 64 x 64 quadrant: rows wm * 64 .., centroids wn * 64 ..
-    const int c16 = lane & 15, g4 = lane >> 4;
     const unsigned RB = p.row_bytes;
+    const PairTileCtx c = pair_tile_ctx(threadIdx.x, RB, smem);
+    const int wave = c.wave, wm = c.wm, wn = c.wn, c16 = c.c16, g4 = c.g4;
     const int nk = p.nk, nct = p.nct;
     const int total = nk * nct;
     const float NEG_INF = -__builtin_inff();
 
-    // this wave's DMA pieces: 8 consecutive 8-row pieces of the stage (waves 0, 1: the rows; waves 2, 3: the centroids)
-    unsigned src_off[LOADS];
-#pragma unroll
-    for (int i = 0; i < LOADS; ++i) src_off[i] = dma_src_offset((wave & 1) * LOADS + i, lane, RB);
-    char *const my_dst = smem + wave * LOADS * 1024;
-
-    const int sw = (c16 >> 1) & 7;
-    const int a_base = (wm * 64 + c16) * SLAB;
-    const int b_base = KT * SLAB + (wn * 64 + c16) * SLAB;
-
     for (long long tile = blockIdx.x; tile < p.T; tile += gridDim.x) {
-        const long long row0 = tile * KT;
+        const long long row0 = tile * PT;
         const long long left = p.n - row0;            // >= 1
-        const int in_tile = left < KT ? (int)left : KT;
+        const int in_tile = left < PT ? (int)left : PT;
 
         unsigned any = 1u;
         if (p.alive != nullptr) {
             any = 0u;
 #pragma unroll
-            for (int w = 0; w < KT / 32; ++w)
+            for (int w = 0; w < PT / 32; ++w)
                 if (32 * w < in_tile) any |= p.alive[(row0 >> 5) + w];
         }
         if (any == 0u) {
@@ -106,15 +86,10 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_kernel(const AssignParam
         int issued = 0, i_ct = 0, i_ks = 0;
         auto issue = [&]() {
             // ring item `issued` = K-slab i_ks of (this row tile, centroid tile i_ct)
-            const int c_left = p.k - i_ct * KT;
-            const char *base = wave < 2 ? rows_base : p.centroids + (size_t)i_ct * KT * RB;
-            const unsigned bytes = wave < 2 ? rows_bytes : (unsigned)(c_left < KT ? c_left : KT) * RB;
-            const __amdgpu_buffer_rsrc_t rsrc = make_rsrc(base, bytes);
-            char *dst = my_dst + (issued % KM_NSTAGE) * KM_STAGE;
-            const unsigned koff = (unsigned)i_ks * SLAB;
-#pragma unroll
-            for (int i = 0; i < LOADS; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(dst + i * 1024), 16, src_off[i] + koff, 0, 0, 0);
+            const int c_left = p.k - i_ct * PT;
+            const char *base = wave < 2 ? rows_base : p.centroids + (size_t)i_ct * PT * RB;
+            const unsigned bytes = wave < 2 ? rows_bytes : (unsigned)(c_left < PT ? c_left : PT) * RB;
+            pair_tile_issue(c, make_rsrc(base, bytes), issued % PT_NSTAGE, i_ks);
             ++issued;
             if (++i_ks == nk) {
                 i_ks = 0;
@@ -126,72 +101,27 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_kernel(const AssignParam
         float bv[4][4];
         int ba[4][4];
         f32x4_t acc[4][4];
+        pair_tile_clear(acc);
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 bv[a][r] = NEG_INF;
                 ba[a][r] = 0;
-#pragma unroll
-                for (int b = 0; b < 4; ++b) acc[a][b][r] = 0.0f;
             }
 
         issue();
         int ks = 0, ct = 0;
         for (int it = 0; it < total; ++it) {
-            wait_vmcnt<0>();
+            wait_vmcnt<0>();     // two stages: item `it` is the only one in flight
             __builtin_amdgcn_s_barrier();
             if (issued < total) issue();
-            const char *st = smem + (it % KM_NSTAGE) * KM_STAGE;
-            // a 128-byte slab is two k-steps; lane (c16, g4) reads chunk 4 s + g4 of row c16 of every 16-row block.
-            // One fixed K order for every (row, centroid): the score bits do not depend on the tile or the grid.
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const int off = ((4 * s + g4) ^ sw) * 16;
-                if constexpr (DT == MMRAG_F32) {
-                    // exact float32: chunk 4 s + g4 holds four consecutive floats of the row; MFMA e takes element e of
-                    // every lane's chunk, the same k for both operands
-                    f32x4_t fa[4], fb[4];
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) fa[a] = *(const f32x4_t *)(st + a_base + a * (16 * SLAB) + off);
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) fb[b] = *(const f32x4_t *)(st + b_base + b * (16 * SLAB) + off);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-#pragma unroll
-                        for (int a = 0; a < 4; ++a)
-#pragma unroll
-                            for (int b = 0; b < 4; ++b)
-                                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[a][e], fb[b][e], acc[a][b], 0, 0, 0);
-                } else if constexpr (DT == MMRAG_F16) {
-                    half8_t fa[4], fb[4];
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) fa[a] = *(const half8_t *)(st + a_base + a * (16 * SLAB) + off);
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) fb[b] = *(const half8_t *)(st + b_base + b * (16 * SLAB) + off);
-#pragma unroll
-                    for (int a = 0; a < 4; ++a)
-#pragma unroll
-                        for (int b = 0; b < 4; ++b)
-                            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[a], fb[b], acc[a][b], 0, 0, 0);
-                } else {
-                    bf16x8_t fa[4], fb[4];
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) fa[a] = *(const bf16x8_t *)(st + a_base + a * (16 * SLAB) + off);
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) fb[b] = *(const bf16x8_t *)(st + b_base + b * (16 * SLAB) + off);
-#pragma unroll
-                    for (int a = 0; a < 4; ++a)
-#pragma unroll
-                        for (int b = 0; b < 4; ++b)
-                            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], fb[b], acc[a][b], 0, 0, 0);
-                }
-            }
+            slab_step<DT>(smem + (it % PT_NSTAGE) * PT_STAGE, c, acc);
             if (++ks == nk) {
                 // ---- the centroid tile is complete: acc[a][b][r] = <row wm*64 + 16a + 4 g4 + r, centroid col0 + 16b>
                 ks = 0;
-                const int col0 = ct * KT + wn * 64 + c16;
-                const bool ragged = (ct + 1) * KT > p.k;     // uniform: only the last centroid tile can hold columns >= k
+                const int col0 = ct * PT + wn * 64 + c16;
+                const bool ragged = (ct + 1) * PT > p.k;     // uniform: only the last centroid tile can hold columns >= k
 #pragma unroll
                 for (int b = 0; b < 4; ++b) {
                     const int col = col0 + 16 * b;
@@ -333,18 +263,11 @@ static int launch_sums(const SumsParams &p, int k, int slabs, hipStream_t s) {
     return MMRAG_OK;
 }
 
-// the checks the two entry points share; FP8 is reported, not joined
+// the checks the two entry points share
 static int check_rows(const char *who, int64_t ld, int dtype, int d, int k) {
-    MMRAG_CHECK_ARG(dtype >= 0 && dtype <= MMRAG_F8E4M3, "%s: bad dtype %d", who, dtype);
-    MMRAG_CHECK_ARG(d > 0 && ld >= d, "%s: need 0 < d <= ld (d=%d ld=%lld)", who, d, (long long)ld);
+    const int st = check_stored_rows(who, "clustered", "cluster", ld, dtype, d);
+    if (st != MMRAG_OK) return st;
     MMRAG_CHECK_ARG(k >= 1 && k <= MMRAG_MAX_CLUSTERS, "%s: k=%d outside 1..%d", who, k, MMRAG_MAX_CLUSTERS);
-    if (dtype == MMRAG_F8E4M3) {
-        mmrag::set_error("%s: float8_e4m3 rows are not clustered; cluster the collection's re-scoring plane", who);
-        return MMRAG_EUNSUPPORTED;
-    }
-    MMRAG_CHECK_ARG(ld * mmrag::esize(dtype) % SLAB == 0 && ld * mmrag::esize(dtype) <= (1LL << 24),
-                    "%s: ld must cover whole 128-byte slabs (mmrag_padded_dim), rows of at most 16 MiB (ld=%lld)", who,
-                    (long long)ld);
     return MMRAG_OK;
 }
 
@@ -360,19 +283,18 @@ int mmrag_kmeans_assign(const void *rows, int64_t n, int64_t ld, int dtype, int 
     const int st = check_rows("kmeans_assign", ld, dtype, d, k);
     if (st != MMRAG_OK) return st;
     if (n == 0) return MMRAG_OK;
-    const int es = mmrag::esize(dtype);
     AssignParams p;
     p.rows = (const char *)rows;
     p.centroids = (const char *)centroids;
     p.n = n;
     p.k = k;
-    p.row_bytes = (unsigned)(ld * es);
-    p.nk = (int)(((long long)d * es + SLAB - 1) / SLAB);
-    p.nct = (k + KT - 1) / KT;
+    p.row_bytes = stored_row_bytes(ld, dtype);
+    p.nk = stored_k_slabs(d, dtype);
+    p.nct = (k + PT - 1) / PT;
     p.alive = alive;
     p.out_assign = out_assign;
     p.out_score = out_score;
-    p.T = (n + KT - 1) / KT;
+    p.T = (n + PT - 1) / PT;
     hipStream_t s = (hipStream_t)stream;
     return mmrag::with_elem_type(dtype, [&](auto tag) { return launch_assign<decltype(tag)::value>(p, s); });
 }
@@ -383,15 +305,14 @@ int mmrag_cluster_sums(const void *rows, int64_t ld, int dtype, int d, const int
     MMRAG_CHECK_ARG(rows && order && seg_off && out_sums, "cluster_sums: null pointer");
     const int st = check_rows("cluster_sums", ld, dtype, d, k);
     if (st != MMRAG_OK) return st;
-    const int es = mmrag::esize(dtype);
     SumsParams p;
     p.rows = (const char *)rows;
-    p.row_bytes = (unsigned)(ld * es);
+    p.row_bytes = stored_row_bytes(ld, dtype);
     p.d = d;
     p.order = order;
     p.seg_off = (const long long *)seg_off;
     p.out_sums = out_sums;
-    const int slabs = (int)(((long long)d * es + SLAB - 1) / SLAB);
+    const int slabs = stored_k_slabs(d, dtype);
     hipStream_t s = (hipStream_t)stream;
     return mmrag::with_elem_type(dtype, [&](auto tag) { return launch_sums<decltype(tag)::value>(p, k, slabs, s); });
 }

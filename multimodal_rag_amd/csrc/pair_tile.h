@@ -1,0 +1,134 @@
+// The 128 x 128 "rows against rows" tile body of the similarity join (simjoin.hip) and of the k-means assign step
+// (kmeans.hip): A . B^T of a 128-row A tile and a 128-row B tile of stored rows, float32 accumulators in registers.
+//
+// A workgroup is 4 waves in a 2 x 2 grid, 64 x 64 outputs per wave as 4 x 4 MFMA tiles of 16 x 16
+// (v_mfma_f32_16x16x32_f16 / _bf16; float32 rows: v_mfma_f32_16x16x4_f32, the exact float32 matrix instruction).  Both
+// operand tiles arrive by the tile_dma.h ring in 128-byte K-slabs: a stage is the A tile's slab then the B tile's
+// (2 x 16 KiB), two stages, so two workgroups share a CU.  Waves 0, 1 fetch the A tile, waves 2, 3 the B tile; rows
+// past the buffer descriptor's range read as zero.  The kernels keep what differs: which tiles, the ring loop, the
+// descriptors (the caller builds them) and the epilogue.
+#pragma once
+#include "mmrag_internal.h"
+#include "tile_dma.h"
+
+namespace mmrag_impl {
+
+constexpr int PT = 128;                      // tile edge (rows of A and of B per workgroup)
+constexpr int PT_NSTAGE = 2;
+constexpr int PT_STAGE = 2 * PT * SLAB;      // A tile then B tile, one K-slab each
+constexpr int PT_LDS = PT_NSTAGE * PT_STAGE;
+constexpr int PT_LOADS = 2 * PT / 8 / 4;     // 1 KiB DMA instructions per wave per ring item: 32 pieces over 4 waves
+static_assert(PT_LDS <= 80 * 1024, "two workgroups per CU");
+
+struct PairTileCtx {
+    int lane, wave;         // wave: uniform (a scalar register)
+    int wm, wn;             // this wave's 64 x 64 quadrant: A rows wm * 64 .., B rows wn * 64 ..
+    int c16, g4;            // lane & 15, lane >> 4
+    int sw;                 // the fragment reads' chunk swizzle
+    int a_base, b_base;     // byte offset in a stage of row c16 of the quadrant's first 16-row block
+    unsigned src_off[PT_LOADS];
+    char *dst;              // where this wave's DMA pieces land in stage 0
+};
+
+// `smem`: PT_LDS bytes, 1 KiB aligned; `row_bytes`: the pitch of both operands' rows
+__device__ __forceinline__ PairTileCtx pair_tile_ctx(unsigned tid, unsigned row_bytes, char *smem) {
+    PairTileCtx c;
+    c.lane = tid & 63;
+    c.wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    c.wm = c.wave >> 1;
+    c.wn = c.wave & 1;
+    c.c16 = c.lane & 15;
+    c.g4 = c.lane >> 4;
+    // this wave's DMA pieces: 8 consecutive 8-row pieces of the stage (waves 0, 1: the A tile; waves 2, 3: the B tile)
+#pragma unroll
+    for (int i = 0; i < PT_LOADS; ++i) c.src_off[i] = dma_src_offset((c.wave & 1) * PT_LOADS + i, c.lane, row_bytes);
+    c.dst = smem + c.wave * PT_LOADS * 1024;
+    c.sw = (c.c16 >> 1) & 7;
+    c.a_base = (c.wm * 64 + c.c16) * SLAB;
+    c.b_base = PT * SLAB + (c.wn * 64 + c.c16) * SLAB;
+    return c;
+}
+
+// this wave's share of K-slab `kslab` of the tile behind `rsrc` (waves 0, 1: the A tile's; waves 2, 3: the B tile's)
+__device__ __forceinline__ void pair_tile_issue(const PairTileCtx &c, __amdgpu_buffer_rsrc_t rsrc, int stage, int kslab) {
+    char *dst = c.dst + stage * PT_STAGE;
+    const unsigned koff = (unsigned)kslab * SLAB;
+#pragma unroll
+    for (int i = 0; i < PT_LOADS; ++i)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(dst + i * 1024), 16, c.src_off[i] + koff, 0, 0, 0);
+}
+
+__device__ __forceinline__ void pair_tile_clear(f32x4_t (&acc)[4][4]) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[a][b][r] = 0.0f;
+}
+
+// acc[a][b][r] += <A row wm*64 + 16a + 4 g4 + r, B row wn*64 + 16b + c16> over the K-slab in `stage`.
+// A 128-byte slab is two k-steps; lane (c16, g4) reads chunk 4 s + g4 of row c16 of every 16-row block.  One fixed K
+// order for every pair of rows: the score bits depend on the two rows and d alone, not on the tile, the grid or the
+// kernel.
+template <int DT>
+__device__ __forceinline__ void slab_step(const char *stage, const PairTileCtx &c, f32x4_t (&acc)[4][4]) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int off = ((4 * s + c.g4) ^ c.sw) * 16;
+        if constexpr (DT == MMRAG_F32) {
+            // exact float32: chunk 4 s + g4 holds four consecutive floats of the row; MFMA e takes element e of
+            // every lane's chunk, i.e. k = 4 (4 s + g4) + e for g4 = 0 .. 3 -- the same k for both operands
+            f32x4_t fa[4], fb[4];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) fa[a] = *(const f32x4_t *)(stage + c.a_base + a * (16 * SLAB) + off);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) fb[b] = *(const f32x4_t *)(stage + c.b_base + b * (16 * SLAB) + off);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+                        acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[a][e], fb[b][e], acc[a][b], 0, 0, 0);
+        } else {
+            using Frag = FragType<DT>;
+            typename Frag::T fa[4], fb[4];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) fa[a] = *(const typename Frag::T *)(stage + c.a_base + a * (16 * SLAB) + off);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) fb[b] = *(const typename Frag::T *)(stage + c.b_base + b * (16 * SLAB) + off);
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) acc[a][b] = Frag::mfma_16x16x32(fa[a], fb[b], acc[a][b]);
+        }
+    }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------
+inline unsigned stored_row_bytes(int64_t ld, int dtype) { return (unsigned)(ld * mmrag::esize(dtype)); }
+// K-slabs that hold the d logical columns
+inline int stored_k_slabs(int d, int dtype) { return (int)(((long long)d * mmrag::esize(dtype) + SLAB - 1) / SLAB); }
+
+// Stored rows the tile body (and mmrag_cluster_sums) can read: a full-precision dtype, 0 < d <= ld, rows of whole
+// 128-byte slabs and at most 16 MiB.  FP8 is reported, not read: "... rows are not `done`; `verb` the collection's
+// re-scoring plane".  `n`: the row count of a caller that reports it with d and ld (null: the caller checks its own).
+inline int check_stored_rows(const char *who, const char *done, const char *verb, int64_t ld, int dtype, int d,
+                             const int64_t *n = nullptr) {
+    MMRAG_CHECK_ARG(dtype >= 0 && dtype <= MMRAG_F8E4M3, "%s: bad dtype %d", who, dtype);
+    if (n != nullptr)
+        MMRAG_CHECK_ARG(*n >= 0 && d > 0 && ld >= d, "%s: need n >= 0 and 0 < d <= ld (n=%lld d=%d ld=%lld)", who,
+                        (long long)*n, d, (long long)ld);
+    MMRAG_CHECK_ARG(d > 0 && ld >= d, "%s: need 0 < d <= ld (d=%d ld=%lld)", who, d, (long long)ld);
+    if (dtype == MMRAG_F8E4M3) {
+        mmrag::set_error("%s: float8_e4m3 rows are not %s; %s the collection's re-scoring plane", who, done, verb);
+        return MMRAG_EUNSUPPORTED;
+    }
+    MMRAG_CHECK_ARG(ld * mmrag::esize(dtype) % SLAB == 0 && ld * mmrag::esize(dtype) <= (1LL << 24),
+                    "%s: ld must cover whole 128-byte slabs (mmrag_padded_dim), rows of at most 16 MiB (ld=%lld)", who,
+                    (long long)ld);
+    return MMRAG_OK;
+}
+
+}  // namespace mmrag_impl

@@ -166,17 +166,6 @@ int check_search_args(const char *name, int k_max, const void *q, const void *co
 bool qs_supported(int dtype, unsigned row_bytes, int K);
 constexpr int QS_TILE_ROWS = 64;   // corpus rows per tile
 constexpr int QS_QROWS = 256;      // queries per workgroup
-// a wave's MFMA operand fragment of 8 elements
-template <int DT>
-struct FragType;
-template <>
-struct FragType<MMRAG_F16> {
-    using T = half8_t;
-};
-template <>
-struct FragType<MMRAG_BF16> {
-    using T = bf16x8_t;
-};
 struct SlabRing {
     int G;    // K-slabs per ring stage (one s_barrier per stage)
     int NST;  // ring stages

@@ -1,11 +1,9 @@
 // Near-duplicate detection: the exact all-pairs threshold self-join of a row matrix (include/mmrag.h mmrag_sim_join).
 //
-// X . X^T over the upper triangle, 128 x 128 output tiles, the N x N matrix never written.  A workgroup is 4 waves in a
-// 2 x 2 grid, 64 x 64 outputs per wave as 4 x 4 MFMA tiles of 16 x 16 (v_mfma_f32_16x16x32_f16 / _bf16; float32 rows:
-// v_mfma_f32_16x16x4_f32, the exact float32 matrix instruction).  Both operand tiles arrive by the tile_dma.h ring in
-// 128-byte K-slabs (two stages of 2 x 16 KiB, so two workgroups share a CU); rows past n read as zero through the
-// buffer descriptor.  Tile edges are fixed multiples of 128 and the K order is fixed, so a pair's score bits depend on
-// its two rows and d alone.
+// X . X^T over the upper triangle, 128 x 128 output tiles, the N x N matrix never written.  The tile body (LDS ring,
+// DMA split, MFMA fragments, K order) is pair_tile.h's, with the i-tile as A and the j-tile as B; rows past n read as
+// zero through the buffer descriptor.  Tile edges are fixed multiples of 128 and the K order is fixed, so a pair's
+// score bits depend on its two rows and d alone.
 //
 // Nearly every tile has no hit: its exit is one wave-wide "any accumulator >= threshold" test.  A wave with survivors
 // applies the alive bits, i < j and the range check, reserves its slots with ONE returning atomic add by one lane and
@@ -18,15 +16,11 @@
 // slots, i.e. a few columns of one band.
 #include <math.h>
 
-#include "mmrag_internal.h"
-#include "tile_dma.h"
+#include "pair_tile.h"
 
 namespace mmrag_impl {
 
-constexpr int JT = 128;          // tile edge (rows of i and of j per workgroup)
 constexpr int JOIN_BAND = 8;     // tile rows per band
-constexpr int JOIN_NSTAGE = 2;
-constexpr int JOIN_STAGE = 2 * JT * SLAB;   // i-tile then j-tile, one K-slab each
 
 // ---- workgroup id -> tile pair -----------------------------------------------------------------------------------
 // first id of tile row r in the row-major order of the triangle (ti <= tj) of a T x T tile grid
@@ -87,26 +81,11 @@ typedef long long i64x2_t __attribute__((ext_vector_type(2)));
 template <int DT>
 __global__ __launch_bounds__(256, 2) void sim_join_kernel(const JoinParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int LOADS = 2 * JT / 8 / 4;   // 1 KiB DMA instructions per wave per ring item: 32 pieces over 4 waves
-    static_assert(JOIN_NSTAGE * JOIN_STAGE <= 80 * 1024, "two workgroups per CU");
-    __shared__ __attribute__((aligned(1024))) char smem[JOIN_NSTAGE * JOIN_STAGE];
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wave >> 1, wn = wave & 1;     // this wave's 64 x 64 quadrant: i rows wm * 64 .., j rows wn * 64 ..
-    const int c16 = lane & 15, g4 = lane >> 4;
+    __shared__ __attribute__((aligned(1024))) char smem[PT_LDS];
     const unsigned RB = p.row_bytes;
     const int nk = p.nk;
-
-    // this wave's DMA pieces: 8 consecutive 8-row pieces of the stage (waves 0, 1: the i-tile; waves 2, 3: the j-tile)
-    unsigned src_off[LOADS];
-#pragma unroll
-    for (int i = 0; i < LOADS; ++i) src_off[i] = dma_src_offset((wave & 1) * LOADS + i, lane, RB);
-    char *const my_dst = smem + wave * LOADS * 1024;
-
-    const int sw = (c16 >> 1) & 7;
-    const int a_base = (wm * 64 + c16) * SLAB;
-    const int b_base = JT * SLAB + (wn * 64 + c16) * SLAB;
+    const PairTileCtx c = pair_tile_ctx(threadIdx.x, RB, smem);
+    const int lane = c.lane, wave = c.wave, wm = c.wm, wn = c.wn, c16 = c.c16, g4 = c.g4;
 
     const long long G8 = (long long)(gridDim.x >> 3);
     for (long long t = 0;; ++t) {
@@ -114,13 +93,13 @@ __global__ __launch_bounds__(256, 2) void sim_join_kernel(const JoinParams p) {
         if (slot >= p.total) break;
         long long ti, tj;
         join_tile_banded(p.T, slot, ti, tj);
-        const long long i_row0 = ti * JT, j_row0 = tj * JT;
+        const long long i_row0 = ti * PT, j_row0 = tj * PT;
 
         if (p.alive != nullptr) {
             // a tile whose 128 i-rows or 128 j-rows are all dead has nothing to emit (uniform: the whole workgroup leaves)
             unsigned any_i = 0, any_j = 0;
 #pragma unroll
-            for (int w = 0; w < JT / 32; ++w) {
+            for (int w = 0; w < PT / 32; ++w) {
                 if (i_row0 + 32 * w < p.n) any_i |= p.alive[(i_row0 >> 5) + w];
                 if (j_row0 + 32 * w < p.n) any_j |= p.alive[(j_row0 >> 5) + w];
             }
@@ -130,77 +109,22 @@ __global__ __launch_bounds__(256, 2) void sim_join_kernel(const JoinParams p) {
         const long long my_row0 = wave < 2 ? i_row0 : j_row0;
         const long long left = p.n - my_row0;
         const __amdgpu_buffer_rsrc_t rsrc =
-            make_rsrc(p.rows + (size_t)my_row0 * RB, (unsigned)((left < JT ? left : (long long)JT) * (long long)RB));
-        auto issue = [&](int item) {
-            char *dst = my_dst + (item % JOIN_NSTAGE) * JOIN_STAGE;
-            const unsigned koff = (unsigned)item * SLAB;
-#pragma unroll
-            for (int i = 0; i < LOADS; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)(dst + i * 1024), 16, src_off[i] + koff, 0, 0, 0);
-        };
+            make_rsrc(p.rows + (size_t)my_row0 * RB, (unsigned)((left < PT ? left : (long long)PT) * (long long)RB));
+        auto issue = [&](int item) { pair_tile_issue(c, rsrc, item % PT_NSTAGE, item); };   // ring item = K-slab
 
         f32x4_t acc[4][4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[a][b][r] = 0.0f;
+        pair_tile_clear(acc);
 
         int issued = 0;
-        for (; issued < JOIN_NSTAGE - 1 && issued < nk; ++issued) issue(issued);
+        for (; issued < PT_NSTAGE - 1 && issued < nk; ++issued) issue(issued);
         for (int it = 0; it < nk; ++it) {
-            wait_items<LOADS, JOIN_NSTAGE - 2>(issued - it - 1);
+            wait_vmcnt<0>();     // two stages: item `it` is the only one in flight
             __builtin_amdgcn_s_barrier();
             if (issued < nk) {
                 issue(issued);
                 ++issued;
             }
-            const char *st = smem + (it % JOIN_NSTAGE) * JOIN_STAGE;
-            // a 128-byte slab is two k-steps; lane (c16, g4) reads chunk 4 s + g4 of row c16 of every 16-row block.
-            // One fixed K order for every pair: the score bits do not depend on the tile pair or the grid.
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const int off = ((4 * s + g4) ^ sw) * 16;
-                if constexpr (DT == MMRAG_F32) {
-                    // exact float32: chunk 4 s + g4 holds four consecutive floats of the row; MFMA e takes element e of
-                    // every lane's chunk, i.e. k = 4 (4 s + g4) + e for g4 = 0 .. 3 -- the same k for both operands
-                    f32x4_t fa[4], fb[4];
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) fa[a] = *(const f32x4_t *)(st + a_base + a * (16 * SLAB) + off);
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) fb[b] = *(const f32x4_t *)(st + b_base + b * (16 * SLAB) + off);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-#pragma unroll
-                        for (int a = 0; a < 4; ++a)
-#pragma unroll
-                            for (int b = 0; b < 4; ++b)
-                                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[a][e], fb[b][e], acc[a][b], 0, 0, 0);
-                } else if constexpr (DT == MMRAG_F16) {
-                    half8_t fa[4], fb[4];
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) fa[a] = *(const half8_t *)(st + a_base + a * (16 * SLAB) + off);
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) fb[b] = *(const half8_t *)(st + b_base + b * (16 * SLAB) + off);
-#pragma unroll
-                    for (int a = 0; a < 4; ++a)
-#pragma unroll
-                        for (int b = 0; b < 4; ++b)
-                            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[a], fb[b], acc[a][b], 0, 0, 0);
-                } else {
-                    bf16x8_t fa[4], fb[4];
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) fa[a] = *(const bf16x8_t *)(st + a_base + a * (16 * SLAB) + off);
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) fb[b] = *(const bf16x8_t *)(st + b_base + b * (16 * SLAB) + off);
-#pragma unroll
-                    for (int a = 0; a < 4; ++a)
-#pragma unroll
-                        for (int b = 0; b < 4; ++b)
-                            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], fb[b], acc[a][b], 0, 0, 0);
-                }
-            }
+            slab_step<DT>(smem + (it % PT_NSTAGE) * PT_STAGE, c, acc);
         }
 
         // ---- epilogue: acc[a][b][r] = <row i, row j>, i = i_row0 + wm*64 + 16a + 4 g4 + r, j = j_row0 + wn*64 + 16b + c16
@@ -330,35 +254,27 @@ int mmrag_sim_join(const void *rows, int64_t n, int64_t ld, int dtype, int d, co
                    int64_t *out_pairs, float *out_scores, int64_t capacity, unsigned long long *count, void *stream) {
     using namespace mmrag_impl;
     MMRAG_CHECK_ARG(rows && out_pairs && out_scores && count, "sim_join: null pointer");
-    MMRAG_CHECK_ARG(dtype >= 0 && dtype <= MMRAG_F8E4M3, "sim_join: bad dtype %d", dtype);
-    MMRAG_CHECK_ARG(n >= 0 && d > 0 && ld >= d, "sim_join: need n >= 0 and 0 < d <= ld (n=%lld d=%d ld=%lld)",
-                    (long long)n, d, (long long)ld);
+    const int st = check_stored_rows("sim_join", "joined", "join", ld, dtype, d, &n);
+    if (st != MMRAG_OK) return st;
     MMRAG_CHECK_ARG(capacity >= 0 && capacity <= MMRAG_MAX_JOIN_PAIRS, "sim_join: capacity %lld outside 0..%d",
                     (long long)capacity, MMRAG_MAX_JOIN_PAIRS);
     MMRAG_CHECK_ARG(threshold > 0.0f, "sim_join: the threshold must be a number above 0");   // false for NaN too
-    if (dtype == MMRAG_F8E4M3) {
-        mmrag::set_error("sim_join: float8_e4m3 rows are not joined; join the collection's re-scoring plane");
-        return MMRAG_EUNSUPPORTED;
-    }
-    const int es = mmrag::esize(dtype);
-    MMRAG_CHECK_ARG(ld * es % SLAB == 0 && ld * es <= (1LL << 24), "sim_join: ld must cover whole 128-byte slabs "
-                    "(mmrag_padded_dim), rows of at most 16 MiB (ld=%lld)", (long long)ld);
-    MMRAG_CHECK_ARG((n + JT - 1) / JT <= 65536, "sim_join: at most 2^23 rows (n=%lld)", (long long)n);
+    MMRAG_CHECK_ARG((n + PT - 1) / PT <= 65536, "sim_join: at most 2^23 rows (n=%lld)", (long long)n);
     hipStream_t s = (hipStream_t)stream;
     MMRAG_CHECK_HIP(hipMemsetAsync(count, 0, sizeof(unsigned long long), s));
     if (n < 2) return MMRAG_OK;
     JoinParams p;
     p.rows = (const char *)rows;
     p.n = n;
-    p.row_bytes = (unsigned)(ld * es);
-    p.nk = (int)(((long long)d * es + SLAB - 1) / SLAB);
+    p.row_bytes = stored_row_bytes(ld, dtype);
+    p.nk = stored_k_slabs(d, dtype);
     p.alive = alive;
     p.thr = threshold;
     p.out_pairs = (long long *)out_pairs;
     p.out_scores = out_scores;
     p.capacity = (unsigned long long)capacity;
     p.count = count;
-    p.T = (n + JT - 1) / JT;
+    p.T = (n + PT - 1) / PT;
     p.total = p.T * (p.T + 1) / 2;
     return mmrag::with_elem_type(dtype, [&](auto tag) { return launch_join<decltype(tag)::value>(p, s); });
 }

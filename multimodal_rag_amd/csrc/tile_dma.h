@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/mmrag.h"
+
 namespace mmrag_impl {
 
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
@@ -18,6 +20,25 @@ typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) void *lds_ptr_t;
+
+// a wave's MFMA operand fragment of 8 elements of storage dtype DT (MMRAG_F16 / MMRAG_BF16), and the 16 x 16 x 32
+// matrix instruction that takes it
+template <int DT>
+struct FragType;
+template <>
+struct FragType<MMRAG_F16> {
+    using T = half8_t;
+    __device__ static __forceinline__ f32x4_t mfma_16x16x32(T a, T b, f32x4_t c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+    }
+};
+template <>
+struct FragType<MMRAG_BF16> {
+    using T = bf16x8_t;
+    __device__ static __forceinline__ f32x4_t mfma_16x16x32(T a, T b, f32x4_t c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
+};
 
 constexpr int SLAB = 128;  // bytes of K per row per ring stage
 

@@ -174,6 +174,28 @@ def test_bitmap_and_position_independence(dev, dtype):
     assert np.array_equal(part_a, full_a[:300]) and part_s.tobytes() == full_s[:300].tobytes()
 
 
+@pytest.mark.parametrize("dtype", ["fp16", "bf16", "fp32"])
+def test_assign_and_join_scores_are_the_same_bits(dev, dtype):
+    """The assign kernel and the similarity join run one tile body (csrc/pair_tile.h): a pair of rows has the same score
+    bits in both.  The first k rows are the centroids; ragged last tiles in both dimensions, a padded last K-slab."""
+    from multimodal_rag_amd import _native
+
+    n, d, k = 300, 72, 130
+    x = np.abs(np.random.default_rng(130).standard_normal((n, d)))     # every dot product is positive
+    x = R.stored(x / np.linalg.norm(x, axis=1, keepdims=True), dtype).astype(np.float32)
+    rows = pack(dev, x, dtype)
+    pairs, scores, total = _native.sim_join(rows, n, d, 1e-6, capacity=1 << 16)
+    assert total == n * (n - 1) // 2 == 44850 and len(scores) == total        # nothing is left out
+    pairs, scores = pairs.cpu().numpy(), scores.cpu().numpy()
+    join = np.full((n, n), -np.inf, np.float32)
+    join[pairs[:, 0], pairs[:, 1]] = scores                                    # join[j, i], j < i
+    got_a, got_s = _native.kmeans_assign(rows, n, d, rows[:k])
+    got_a, got_s = got_a.cpu().numpy(), got_s.cpu().numpy()
+    want = join[:k, k:]                                                        # centroid j < k against row i >= k
+    assert np.array_equal(got_s[k:].view(np.int32), want.max(axis=0).view(np.int32))
+    assert np.array_equal(got_a[k:], want.argmax(axis=0))                      # argmax: the lowest j at the maximum
+
+
 # ---------------------------------------------------------------- 3. cluster_sums
 SEGMENTS = (0, 1, 255, 256, 257, 1025, 0, 37)
 
