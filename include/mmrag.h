@@ -413,6 +413,60 @@ int mmrag_group_select(const float *scores, const int64_t *rows, int B, int C, c
                        int32_t *out_pos, int32_t *out_group, int32_t *out_info, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Multi-query retrieval ("query expansion", "RAG-fusion"): the ranked lists that several phrasings of one question got
+ * from the search, fused into one ranking, so that a row several phrasings agree on outranks a row only one of them
+ * likes.  The reference has no counterpart: it searches one phrasing.
+ * One launch, one workgroup per group (one question), everything in LDS; no workspace, no atomics on global memory, no
+ * host synchronisation (the call can be captured into a graph); identical bits run to run, and a group's result does
+ * not depend on G, on the grid, or on what else is in the call.
+ *
+ * Definition.  Group g owns the lists list_off[g] .. list_off[g + 1] - 1 (none is allowed); list l of the group is its
+ * l-th, a group-local index.  For one group:
+ *   List length and duplicates
+ *   - List l ends at its first row < 0; what follows in the list is not read as entries.
+ *   - Entry (l, p) at 0-based position p has rank p + 1.
+ *   - If a row occurs more than once in one list, only its first occurrence counts.
+ *   Contribution of entry (l, p), w_l the list's weight (1.0 when weights is NULL)
+ *   - MMRAG_FUSE_RRF: c(l, p) = w_l / (float)(rrf_k + p + 1), ONE correctly rounded float32 division.
+ *   - MMRAG_FUSE_MAX: c(l, p) = fl(w_l * score(l, p)), one float32 multiplication.
+ *   Fused score of a row, over the lists that returned it in ascending l
+ *   - RRF: the first contribution, then each further one added to it in float32, one list after the other.
+ *   - MAX: the largest contribution (a later one replaces the value only where it compares greater).
+ *   Per row
+ *   - best: the largest input score of the row over its lists, copied bit for bit (a later list replaces it only
+ *     where its score compares greater); best_list: the list that gave it, so ties go to the lower list.
+ *   - count: the number of lists that returned the row.
+ *   Order
+ *   - fused descending, then best descending, then row ascending.
+ *   - Floats compare as floats: -0.0 equals 0.0, and such a pair falls through to the next key.
+ *   Output, per group
+ *   - out_fused [n] float32, out_rows [n] int64, out_best [n] float32, out_best_list [n] int32, out_count [n] int32:
+ *     the first n rows of that order;
+ *     out_info [2] int32 = (distinct rows found, valid entries read = the sum of the list lengths).
+ *   - Unused slots hold (-inf, -1, -inf, -1, 0).
+ * Scores of valid entries and the weights must be finite (a NaN has no place in the order); weights may be zero or
+ * negative.  Rows are full int64 in [0, 2^63 - 1).
+ *
+ *   scores  dev [L, C] float32     rows  dev [L, C] int64: the lists as mmrag_cosine_topk / _deep wrote them (score
+ *           descending, (-inf, -1) padded tail allowed; the order is not checked and nothing depends on it)
+ *   list_off  dev [G + 1] int32, ascending, list_off[0] = 0, list_off[G] = L.  A group must own at most
+ *           MMRAG_MAX_FUSE_LISTS lists; the offsets are on the device, so the CALLER checks that.  Nothing is read out
+ *           of bounds whatever they hold: offsets outside [0, L] or descending make the group empty, and of a group
+ *           with more lists only the first MMRAG_MAX_FUSE_LISTS are read.
+ *   weights   dev [L] float32 or NULL
+ *   out_*     dev [G, n]      out_info  dev [G, 2]
+ * MMRAG_EINVAL unless G >= 1, L >= 0, 1 <= C <= MMRAG_MAX_FUSE_CANDIDATES, 1 <= n <= MMRAG_MAX_FUSE_RESULTS,
+ * rrf_k >= 0 and method is MMRAG_FUSE_RRF or MMRAG_FUSE_MAX; arguments are checked before any HIP call. */
+#define MMRAG_MAX_FUSE_LISTS 16
+#define MMRAG_MAX_FUSE_CANDIDATES 256
+#define MMRAG_MAX_FUSE_RESULTS 4096
+#define MMRAG_FUSE_RRF 0
+#define MMRAG_FUSE_MAX 1
+int mmrag_fuse_select(const float *scores, const int64_t *rows, int L, int C, const int32_t *list_off, int G,
+                      const float *weights, int method, int rrf_k, int n, float *out_fused, int64_t *out_rows,
+                      float *out_best, int32_t *out_best_list, int32_t *out_count, int32_t *out_info, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Near-duplicate detection: the exact all-pairs threshold self-join of a row matrix.  The reference has no counterpart:
  * app/utils/embedder.py stores every chunk of every upload again (ids are f"{doc_id}_{item id}", :514-523).
  * X . X^T over the upper triangle in 128 x 128 tiles; the N x N matrix is never written.

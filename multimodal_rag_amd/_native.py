@@ -24,6 +24,9 @@ MAX_MMR_CANDIDATES = 1024   # mmrag_mmr_select (MMRAG_MAX_MMR_CANDIDATES)
 MAX_RESCORE_CANDIDATES = 4096   # mmrag_rescore_topk (MMRAG_MAX_RESCORE_CANDIDATES)
 # mmrag_group_select (MMRAG_MAX_GROUP_CANDIDATES, MMRAG_MAX_GROUPS, MMRAG_MAX_GROUP_SIZE)
 MAX_GROUP_CANDIDATES, MAX_GROUPS, MAX_GROUP_SIZE = 4096, 256, 16
+# mmrag_fuse_select (MMRAG_MAX_FUSE_LISTS, MMRAG_MAX_FUSE_CANDIDATES, MMRAG_MAX_FUSE_RESULTS, MMRAG_FUSE_RRF / _MAX)
+MAX_FUSE_LISTS, MAX_FUSE_CANDIDATES, MAX_FUSE_RESULTS = 16, 256, 4096
+FUSE_METHODS = {"rrf": 0, "max": 1}
 MAX_JOIN_PAIRS = 1 << 26   # mmrag_sim_join (MMRAG_MAX_JOIN_PAIRS)
 MAX_CLUSTERS = 4096   # mmrag_kmeans_assign / mmrag_cluster_sums (MMRAG_MAX_CLUSTERS)
 _DT2TORCH = {F32: torch.float32, F16: torch.float16, BF16: torch.bfloat16, F8E4M3: torch.float8_e4m3fn}
@@ -195,6 +198,10 @@ def _declare(lib):
     lib.mmrag_group_select.restype = c_int
     lib.mmrag_group_select.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    # fusion of the ranked lists of query variants (csrc/fuse.hip)
+    lib.mmrag_fuse_select.restype = c_int
+    lib.mmrag_fuse_select.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     # near-duplicate join (csrc/simjoin.hip); the join_*tile entries are its test-only exports (csrc/mmrag_internal.h)
     lib.mmrag_sim_join.restype = c_int
     lib.mmrag_sim_join.argtypes = [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p,
@@ -448,6 +455,73 @@ def group_select(scores: torch.Tensor, rows: torch.Tensor, group_of_row: torch.T
                                       out_i.data_ptr(), _stream_ptr(dev))
     _check(st, "mmrag_group_select")
     return out_s, out_r, out_p, out_g, out_i
+
+
+def _pinned_to_device(host: torch.Tensor, device) -> torch.Tensor:
+    """a small host tensor on `device` through pinned memory: the copy is enqueued on the current stream and the
+    caller does not wait for what the stream already holds (a copy from pageable memory may)"""
+    return host.contiguous().pin_memory().to(device, non_blocking=True)
+
+
+def fuse_offsets(list_off, L: int, device) -> torch.Tensor:
+    """the device int32 list_off of fuse_select from a host sequence, checked (the one place the rule lives): ascending
+    from 0 to L over at least one group, at most MAX_FUSE_LISTS lists per group"""
+    host = torch.as_tensor(list_off).to(torch.int64).reshape(-1)
+    steps = host[1:] - host[:-1]
+    if host.numel() < 2 or int(host[0]) != 0 or int(host[-1]) != L or bool((steps < 0).any()):
+        raise MMRagNativeError(f"fuse_select: list_off must ascend from 0 to L={L} over at least one group")
+    if int(steps.max()) > MAX_FUSE_LISTS:
+        raise MMRagNativeError(f"fuse_select: a group owns {int(steps.max())} lists, at most {MAX_FUSE_LISTS} "
+                               "are fused")
+    return _pinned_to_device(host.to(torch.int32), device)
+
+
+def fuse_select(scores: torch.Tensor, rows: torch.Tensor, list_off, n: int, weights: Optional[torch.Tensor] = None,
+                method: str = "rrf", rrf_k: int = 60):
+    """Fuse the ranked lists of query variants (include/mmrag.h mmrag_fuse_select): scores [L, C] float32 and rows
+    [L, C] int64 in the search's order, (-inf, -1) padded tails allowed; group g owns the lists list_off[g] ..
+    list_off[g + 1] - 1 (ascending, from 0 to L; a group may own none, at most MAX_FUSE_LISTS = 16); weights [L]
+    float32 or None = all 1.0; method "rrf" (weight / (rrf_k + rank), summed) or "max" (largest weight * score).
+    `list_off` is a HOST sequence or int32 tensor (checked and copied by fuse_offsets through pinned memory), or a
+    device int32 tensor the caller vouches for (fuse_offsets made it, or the caller's own).  Returns device tensors (fused [G, n] float32,
+    rows [G, n] int64, best [G, n] float32 = the row's largest input score, best list [G, n] int32 local to the group,
+    count [G, n] int32 lists that returned the row, info [G, 2] int32 = (distinct rows, valid entries)), unused slots
+    (-inf, -1, -inf, -1, 0).  One launch on the current stream, no host sync."""
+    _dev_check(scores, rows, weights)
+    if (scores.dim() != 2 or scores.shape != rows.shape or scores.dtype != torch.float32 or rows.dtype != torch.int64
+            or not scores.is_contiguous() or not rows.is_contiguous()):
+        raise MMRagNativeError("fuse_select: scores [L, C] float32 and rows [L, C] int64 must be contiguous and of "
+                               "one shape")
+    L, C = scores.shape
+    dev = scores.device
+    if rows.device != dev:
+        raise MMRagNativeError("fuse_select: scores and rows must be on one device")
+    if weights is not None and (weights.dim() != 1 or weights.numel() != L or weights.dtype != torch.float32
+                                or not weights.is_contiguous() or weights.device != dev):
+        raise MMRagNativeError("fuse_select: weights must be a contiguous float32 tensor [L] on the lists' device")
+    if method not in FUSE_METHODS:
+        raise MMRagNativeError(f"fuse_select: unknown method {method!r} (one of {sorted(FUSE_METHODS)})")
+    if isinstance(list_off, torch.Tensor) and list_off.is_cuda:
+        if list_off.dim() != 1 or list_off.dtype != torch.int32 or not list_off.is_contiguous() or list_off.device != dev:
+            raise MMRagNativeError("fuse_select: list_off must be a contiguous 1-D int32 tensor on the lists' device")
+        off_dev = list_off
+    else:
+        off_dev = fuse_offsets(list_off, L, dev)
+    G, n = off_dev.numel() - 1, int(n)
+    shape = (max(G, 0), max(n, 0))
+    out_f = torch.empty(shape, dtype=torch.float32, device=dev)
+    out_r = torch.empty(shape, dtype=torch.int64, device=dev)
+    out_b = torch.empty(shape, dtype=torch.float32, device=dev)
+    out_l = torch.empty(shape, dtype=torch.int32, device=dev)
+    out_c = torch.empty(shape, dtype=torch.int32, device=dev)
+    out_i = torch.empty((shape[0], 2), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        st = lib().mmrag_fuse_select(scores.data_ptr(), rows.data_ptr(), L, C, off_dev.data_ptr(), G,
+                                     weights.data_ptr() if weights is not None else None, FUSE_METHODS[method],
+                                     int(rrf_k), n, out_f.data_ptr(), out_r.data_ptr(), out_b.data_ptr(),
+                                     out_l.data_ptr(), out_c.data_ptr(), out_i.data_ptr(), _stream_ptr(dev))
+    _check(st, "mmrag_fuse_select")
+    return out_f, out_r, out_b, out_l, out_c, out_i
 
 
 def _check_stored_rows(who: str, rows: torch.Tensor):

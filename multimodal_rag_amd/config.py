@@ -90,6 +90,12 @@ class Settings:
     # min(max(MMRAG_GROUP_CANDIDATES, 4 * n_groups * group_size), 4096) dense hits; queries that neither found
     # n_groups groups nor exhausted their list are searched again 4 x deeper, up to 4096
     MMRAG_GROUP_CANDIDATES: int = field(default_factory=lambda: int(os.getenv("MMRAG_GROUP_CANDIDATES", "64")))
+    # multi-query retrieval (VectorIndex.fused_query, csrc/fuse.hip): every phrasing of a question returns
+    # max(n_results, MMRAG_FUSE_CANDIDATES) hits (at most 256); the lists are fused by MMRAG_FUSE_METHOD: "rrf" = sum of
+    # weight / (MMRAG_FUSE_RRF_K + rank), "max" = largest weight * cosine
+    MMRAG_FUSE_CANDIDATES: int = field(default_factory=lambda: int(os.getenv("MMRAG_FUSE_CANDIDATES", "50")))
+    MMRAG_FUSE_METHOD: str = field(default_factory=lambda: os.getenv("MMRAG_FUSE_METHOD", "rrf"))
+    MMRAG_FUSE_RRF_K: int = field(default_factory=lambda: int(os.getenv("MMRAG_FUSE_RRF_K", "60")))
     # near-duplicate detection (VectorIndex.near_duplicates / add(dedup_threshold=...), csrc/simjoin.hip).
     # MMRAG_DEDUP_THRESHOLD: 0 = off (default); above 0 (at most 1) embed_and_store skips a chunk whose cosine to a stored
     # chunk, or to an earlier kept chunk of the same upload, is at least this.  MMRAG_DEDUP_REPORT_THRESHOLD: the default

@@ -40,11 +40,13 @@ ITEM_KINDS = ("text", "table", "image")           # the kinds embed_and_store co
 RESULT_KEYS = ("ids", "distances", "metadatas", "documents")
 HYBRID_KEYS = RESULT_KEYS + ("hybrid_scores", "lexical_scores")
 MMR_KEYS = RESULT_KEYS + ("mmr_scores",)
+FUSED_KEYS = RESULT_KEYS + ("fused_scores", "matched_queries", "best_query")
 _HOSTROWS = load_hostrows()
 _COLLECTION_NOTE = {"description": "Multi-modal RAG embeddings"}
 # what a retrieval mode needs of the collection: (method, the error of a collection that lacks it)
 _NEEDS_HYBRID = ("hybrid_query", "hybrid retrieval needs a single-GPU collection (VectorIndex)")
 _NEEDS_MMR = ("mmr_query", "MMR retrieval needs a single-GPU collection (VectorIndex)")
+_NEEDS_MULTI = ("fused_query", "multi-query retrieval needs a single-GPU collection (VectorIndex)")
 _NEEDS_GROUPING = ("grouped_query", "grouped retrieval needs a single-GPU collection (VectorIndex)")
 _NEEDS_DEDUP = ("near_duplicates", "near-duplicate detection needs a single-GPU collection (VectorIndex) with "
                                    "full-precision rows")
@@ -53,6 +55,7 @@ _dedup_warned = False    # "MMRAG_DEDUP_THRESHOLD is set but this collection can
 # the answer of a batch's query that could not be answered, before its 'error' (copied for every such query)
 _EMPTY = {key: [] for key in RESULT_KEYS}
 _EMPTY_MMR = {key: [] for key in MMR_KEYS}
+_EMPTY_FUSED = {key: [] for key in FUSED_KEYS}
 _EMPTY_GROUPED = {**_EMPTY, "groups": [], "exhaustive": False, "fetch_k": 0}
 
 
@@ -551,6 +554,105 @@ class EmbeddingManager:
         a query that cannot be answered gets a dict with empty lists and an 'error' message."""
         return await self._batch("Batch grouped query", _NEEDS_GROUPING, _EMPTY_GROUPED, self._answer_grouped, queries,
                                  n_groups, group_size, filter_dict, group_by, fetch_k)
+
+    def supports_multi_query(self) -> bool:
+        """True when the collection can answer fused_query (a single-GPU VectorIndex; not the sharded serving path,
+        whose per-variant lists would have to be merged across the shards before they are fused)"""
+        return self.collection is None or hasattr(self.collection, "fused_query")
+
+    def _answer_fused(self, questions: Sequence[Sequence[str]], n_results: int, filter_dict: Optional[Dict],
+                      weights: Optional[Sequence[Optional[Sequence[float]]]],
+                      method: Optional[str]) -> List[Dict[str, Any]]:
+        """blocking, one worker thread: every variant of every question through the cache and ONE encoder pass for the
+        misses, then ONE collection.fused_query (one search over all of them, one fusion launch)"""
+        flat = [text for variants in questions for text in variants]
+        list_off = [0]
+        for variants in questions:
+            list_off.append(list_off[-1] + len(variants))
+        flat_w = None
+        if weights is not None and any(w is not None for w in weights):
+            flat_w = []
+            for variants, w in zip(questions, weights):
+                w = [1.0] * len(variants) if w is None else [float(x) for x in w]
+                if len(w) != len(variants):
+                    raise ValueError(f"{len(w)} weights for {len(variants)} query variants")
+                flat_w.extend(w)
+        res = self.collection.fused_query(self._embed(flat), list_off, n_results=n_results, weights=flat_w,
+                                          method=method, where=filter_dict, include=self._INCLUDE)
+        return [{key: res[key][at] for key in FUSED_KEYS} for at in range(len(questions))]
+
+    @staticmethod
+    def _variants_problem(variants) -> Optional[str]:
+        """why these variants cannot be searched (query()'s own message for an empty text), or None"""
+        if isinstance(variants, str) or not variants or any(not isinstance(v, str) or not v.strip() for v in variants):
+            return "Query text cannot be empty"
+        if len(variants) > 16:
+            return "at most 16 query variants are fused per question"
+        return None
+
+    async def multi_query(self, queries: List[str], n_results: int = 5, filter_dict: Optional[Dict] = None,
+                          weights: Optional[List[float]] = None, method: Optional[str] = None) -> Dict[str, Any]:
+        """Multi-query retrieval (VectorIndex.fused_query): `queries` are phrasings or sub-questions of ONE question
+        (at most 16); each is searched and the ranked lists are fused on the device, so a hit several phrasings agree
+        on outranks a hit only one of them likes.  One result dict with the keys of query() plus `fused_scores`,
+        `matched_queries` (how many phrasings returned the hit) and `best_query` (the index of the phrasing that
+        scored it best), in fused order; `distances` are 1 - the best cosine over the phrasings, so they are not
+        ascending.  weights: one per phrasing (default 1.0); method: "rrf" or "max" (default MMRAG_FUSE_METHOD).  An
+        empty list or an empty phrasing raises query()'s empty-query error; same embedding cache; counts as one query;
+        it calls the collection directly (no dynamic batching)."""
+        await self._ready()
+        why = self._variants_problem(queries)
+        if why:
+            raise ValueError(why)
+        if not hasattr(self.collection, _NEEDS_MULTI[0]):
+            raise ValueError(_NEEDS_MULTI[1])
+        try:
+            hit = (await self._engine_call("Multi-query", self._answer_fused, [list(queries)], n_results, filter_dict,
+                                           [weights], method))[0]
+        except Exception as e:
+            logger.error("Multi-query failed: %s", e, exc_info=True)
+            raise
+        self.stats["total_queries"] += 1
+        return hit
+
+    async def batch_multi_query(self, question_variants: List[List[str]], n_results: int = 5,
+                                filter_dict: Optional[Dict] = None,
+                                weights: Optional[List[Optional[List[float]]]] = None,
+                                method: Optional[str] = None) -> List[Dict[str, Any]]:
+        """batch_query's twin for multi_query: every phrasing of every question in one batched encode, one search and
+        one fusion launch; `weights` is one list per question (or None).  A question that cannot be answered -- no
+        phrasings, an empty one, or all of them when the call fails -- gets a dict with empty lists and an 'error'
+        message."""
+        await self._ready()
+
+        def failed(why: str) -> Dict[str, Any]:
+            return {**copy.deepcopy(_EMPTY_FUSED), "error": why}
+
+        answers: List[Optional[Dict[str, Any]]] = [None] * len(question_variants)
+        live = []
+        for at, variants in enumerate(question_variants):
+            why = self._variants_problem(variants)
+            if why:
+                answers[at] = failed(why)
+            else:
+                live.append(at)
+        if live:
+            try:
+                if not hasattr(self.collection, _NEEDS_MULTI[0]):
+                    raise ValueError(_NEEDS_MULTI[1])
+                if weights is not None and len(weights) != len(question_variants):
+                    raise ValueError(f"{len(weights)} weight lists for {len(question_variants)} questions")
+                hits = await self._engine_call("Batch multi-query", self._answer_fused,
+                                               [list(question_variants[at]) for at in live], n_results, filter_dict,
+                                               [weights[at] for at in live] if weights is not None else None, method)
+                for at, hit in zip(live, hits):
+                    answers[at] = hit
+                self.stats["total_queries"] += len(live)
+            except Exception as e:
+                logger.error("Batch multi-query failed: %s", e)
+                for at in live:
+                    answers[at] = failed(str(e))
+        return answers  # type: ignore[return-value]
 
     async def batch_query(self, queries: List[str], n_results: int = 5,
                           filter_dict: Optional[Dict] = None) -> List[Dict[str, Any]]:

@@ -1216,6 +1216,78 @@ class VectorIndex:
                 res["exhaustive"].append(found >= G or valid < depths[b])
             return res
 
+    # ------------------------------------------------------------------ multi-query fusion ----
+    def _launch_fused(self, query_embeddings, list_off, n_results: int, fetch_k, weights, method, where,
+                      check_norm: bool = True):
+        """enqueue ONE search over all the variants' rows and the fusion of their lists, on one stream (caller holds
+        the lock): the six device tensors of _native.fuse_select, no host sync of its own"""
+        from .config import settings
+
+        n = int(n_results)
+        if not 1 <= n <= _native.MAX_FUSE_RESULTS:
+            raise ValueError(f"n_results must be in 1..{_native.MAX_FUSE_RESULTS} for multi-query fusion")
+        C = max(n, int(settings.MMRAG_FUSE_CANDIDATES)) if fetch_k is None else int(fetch_k)
+        if C < 1:
+            raise ValueError("fetch_k must be >= 1")
+        C = min(C, _native.MAX_FUSE_CANDIDATES)
+        method = str(settings.MMRAG_FUSE_METHOD if method is None else method).lower()
+        if method not in _native.FUSE_METHODS:
+            raise ValueError(f"fusion method must be one of {sorted(_native.FUSE_METHODS)} (got {method!r})")
+        # everything the fuse launch needs is on its way to the device BEFORE the scan is enqueued (offsets and weights
+        # through pinned memory), so nothing between the scan and the fuse launch can make the host wait for the stream
+        qf = self._to_device_f32(query_embeddings, "query", check_norm)     # converted and norm-checked once
+        L = int(qf.shape[0])
+        try:
+            off_dev = _native.fuse_offsets(list_off, L, self.device)        # the one check of list_off
+        except _native.MMRagNativeError as e:
+            raise ValueError(str(e)) from None
+        w = None
+        if weights is not None:
+            w = np.asarray(weights, dtype=np.float32).reshape(-1)
+            if w.size != L or not np.isfinite(w).all():
+                raise ValueError(f"weights must be {L} finite numbers, one per query variant")
+            w = _native._pinned_to_device(torch.from_numpy(w), self.device)
+        scores, rows = self._launch_search(qf, C, where, check_norm=False)
+        return _native.fuse_select(scores.contiguous(), rows.contiguous(), off_dev, n, weights=w, method=method,
+                                   rrf_k=int(settings.MMRAG_FUSE_RRF_K))
+
+    def fused_search(self, query_embeddings, list_off, n_results: int, fetch_k: Optional[int] = None,
+                     weights=None, method: Optional[str] = None, where: Optional[Dict[str, Any]] = None):
+        """Raw multi-query search: the L rows of query_embeddings are phrasings ("variants") of G questions, question g
+        owning rows list_off[g] .. list_off[g + 1] - 1 (ascending from 0 to L, at most 16 each, none allowed).  ONE
+        search() call answers all L rows at depth fetch_k, then one launch (csrc/fuse.hip, include/mmrag.h
+        mmrag_fuse_select, where the definition is) fuses each question's lists on the same stream.  Returns device
+        tensors (fused scores [G, n] float32 descending, rows [G, n] int64, best [G, n] float32 = a row's largest cosine
+        over the variants, best variant [G, n] int32 local to the question, count [G, n] int32 variants that returned
+        the row, info [G, 2] int32 = (distinct rows, valid entries)), unused slots (-inf, -1, -inf, -1, 0).
+
+        fetch_k defaults to max(n_results, MMRAG_FUSE_CANDIDATES) and is capped at 256; depths above 20 take the deep
+        search as in search().  method: "rrf" (sum of weight / (MMRAG_FUSE_RRF_K + rank), the default
+        MMRAG_FUSE_METHOD) or "max" (largest weight * cosine); weights: one per row, default 1.0.  The lists are
+        search()'s: tombstones and `where` are honoured, a float8_e4m3fn collection is re-scored on its plane (in
+        capacity mode the scores are the quantised collection's own)."""
+        with self._lock:
+            return self._launch_fused(query_embeddings, list_off, n_results, fetch_k, weights, method, where)
+
+    def fused_query(self, query_embeddings, list_off, n_results: int = 10, fetch_k: Optional[int] = None,
+                    weights=None, method: Optional[str] = None, where: Optional[Dict[str, Any]] = None,
+                    include: Sequence[str] = ("metadatas", "documents", "distances"),
+                    check_norm: bool = True) -> Dict[str, Any]:
+        """query() over several phrasings of each question (see fused_search): one Chroma-shaped dict with one entry
+        per QUESTION, in fused order, plus `fused_scores`, `matched_queries` (how many variants returned the hit) and
+        `best_query` (the variant, local to the question, that scored it best).  `distances` are 1 - the best cosine
+        over the variants, so they are NOT ascending."""
+        with self._lock, stage("search"):
+            fused, rows, best, best_list, count, _ = self._launch_fused(query_embeddings, list_off, n_results, fetch_k,
+                                                                        weights, method, where, check_norm)
+            tables = self._tables()
+            emb_src = self._full if "embeddings" in include else None
+        with stage("collect"):
+            out = self._collect(best, rows, include, *tables, emb_src)
+            for key, t in (("fused_scores", fused), ("matched_queries", count), ("best_query", best_list)):
+                out[key] = [vals[: len(ids)] for vals, ids in zip(t.cpu().tolist(), out["ids"])]
+            return out
+
     # ------------------------------------------------------------------ lexical / hybrid ----
     def enable_lexical(self):
         """Build the BM25 state (lexical.LexicalIndex) from the stored documents in row order; from then on add,

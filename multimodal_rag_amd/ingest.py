@@ -130,3 +130,32 @@ class ExtractiveAnswerer:
                                   temperature: float = 0.7) -> str:
         parts = [text] + list(tables or [])
         return "\n\n".join(p for p in parts if p)[: max_tokens * 4]
+
+
+class LLMQueryExpander:
+    """Query expansion for multi-query retrieval (`create_app(query_expander=...)`, not installed by default): asks any
+    generator with `generate_text` for other phrasings of a question -- one prompt, one phrasing per line.  Blank
+    lines, list markers, repeats and the question itself are dropped; at most n phrasings are returned."""
+
+    PROMPT = ("Viết lại câu hỏi sau theo {n} cách diễn đạt khác nhau để tìm kiếm tài liệu. "
+              "Mỗi dòng một câu hỏi, không đánh số, không giải thích.\n\nCâu hỏi: {question}\n\nCác cách diễn đạt:")
+
+    def __init__(self, generator, max_tokens: int = 400, temperature: float = 0.7):
+        self.generator, self.max_tokens, self.temperature = generator, max_tokens, temperature
+
+    async def expand(self, question: str, n: int) -> List[str]:
+        if n < 1:
+            return []
+        text = await self.generator.generate_text(self.PROMPT.format(n=n, question=question),
+                                                  max_tokens=self.max_tokens, temperature=self.temperature)
+        out: List[str] = []
+        seen = {question.strip().casefold()}
+        for line in (text or "").splitlines():
+            line = line.strip().lstrip("-*\u2022").strip()
+            head, dot, rest = line.partition(".")
+            if dot and head.strip().isdigit():           # "1. ..." from a model that numbers anyway
+                line = rest.strip()
+            if line and line.casefold() not in seen:
+                seen.add(line.casefold())
+                out.append(line[:2000])
+        return out[:n]

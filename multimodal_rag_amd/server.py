@@ -15,7 +15,7 @@ import time
 import uuid
 from contextlib import asynccontextmanager
 from datetime import datetime
-from typing import Any, List, Optional
+from typing import Annotated, Any, List, Literal, Optional
 
 from fastapi import FastAPI, HTTPException, Request, status
 from pydantic import BaseModel, Field
@@ -54,6 +54,20 @@ class QueryRequest(BaseModel):  # api.py:161-164
     # `rerank` yet
     group_by_document: bool = Field(False)
     per_document: int = Field(1, ge=1, le=16)
+    # not in the reference: multi-query retrieval (EmbeddingManager.multi_query).  `variants` are up to 15 further
+    # phrasings or sub-questions searched together with `query`; the ranked lists are fused on the device (`fusion`:
+    # "rrf" or "max", default MMRAG_FUSE_METHOD) and each source carries its `fused_score` and `matched_queries`
+    # (the number of DISTINCT phrasings that returned it: one repeating `query` or an earlier one is searched once).
+    # `query` is always list 0 and is the text the generator and the re-ranker see; `variant_weight` is the weight of
+    # each further phrasing against 1.0 for `query`.  `expand` asks the application's query expander
+    # (create_app(query_expander=...)) for that many phrasings more.  With `rerank`,
+    # max(top_k, MMRAG_RERANK_CANDIDATES) fused hits are re-ranked against `query`.  Not combined with `mmr`, `hybrid`
+    # or `group_by_document` yet
+    variants: Optional[Annotated[List[Annotated[str, Field(min_length=1, max_length=2000)]],
+                                 Field(max_length=15)]] = None
+    variant_weight: Optional[float] = Field(None, ge=-1000.0, le=1000.0)
+    fusion: Optional[Literal["rrf", "max"]] = None
+    expand: int = Field(0, ge=0, le=15)
 
 
 # request flag -> what it needs of the embedder (method, `supports_*` check) and the 400 detail when that is missing;
@@ -71,6 +85,12 @@ MODE_NEEDS = (
      "(EmbeddingManager.mmr_query); a float8_e4m3fn collection also needs its re-scoring plane "
      "(MMRAG_F8_RESCORE=float16)"),
 )
+
+
+# multi-query retrieval (`variants` / `expand`): the same
+MULTI_NEEDS = ("multi_query", "supports_multi_query",
+               "Multi-query retrieval is not available with this embedder: it needs a single-GPU collection "
+               "(EmbeddingManager.multi_query)")
 
 
 # /duplicates: what it needs of the embedder and the 400 detail when that is missing (worded like MODE_NEEDS)
@@ -217,26 +237,40 @@ class Pipeline:
 
     async def answer(self, question: str, top_k: int, multimodal: bool, rerank: bool = False,
                      hybrid: bool = False, mmr: bool = False, mmr_lambda: Optional[float] = None,
-                     group_by_document: bool = False, per_document: int = 1) -> Optional[dict]:
+                     group_by_document: bool = False, per_document: int = 1,
+                     variants: Optional[List[str]] = None, variant_weight: Optional[float] = None,
+                     fusion: Optional[str] = None) -> Optional[dict]:
         """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
         max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the cross-encoder's best top_k.  `hybrid`: the hits come from
         dense + BM25 retrieval fused by reciprocal rank.  `mmr`: the hits are a maximal-marginal-relevance selection of
         the dense candidates (`mmr_lambda`, default MMRAG_MMR_LAMBDA).  `group_by_document` (alone): the hits are the
-        `per_document` best of each of the top_k best documents, flattened in document order"""
-        if mmr:
+        `per_document` best of each of the top_k best documents, flattened in document order.  `variants` (a list,
+        possibly empty; alone or with `rerank`): the hits are the fusion of the ranked lists of `question` and these
+        further phrasings (EmbeddingManager.multi_query; `variant_weight` for each of them against 1.0, `fusion`
+        "rrf" or "max"); the generator and the re-ranker see `question` only"""
+        multi = variants is not None
+        if multi:
+            weights = None if variant_weight is None else [1.0] + [float(variant_weight)] * len(variants)
+
+            def search(text, n_results):
+                return self.embedder.multi_query([text] + list(variants), n_results=n_results, weights=weights,
+                                                 method=fusion)
+        elif mmr:
             search = functools.partial(self.embedder.mmr_query, lambda_mult=mmr_lambda)
         else:
             search = self.embedder.hybrid_query if hybrid else self.embedder.query
-        extra = "mmr_scores" if mmr else "hybrid_scores" if hybrid else None   # per-hit column re-ranking carries along
+        # per-hit columns re-ranking carries along
+        extra = ("fused_scores", "matched_queries") if multi else ("mmr_scores",) if mmr else \
+            ("hybrid_scores",) if hybrid else ()
         if group_by_document:
             hits = await self.embedder.grouped_query(question, n_groups=top_k, group_size=per_document)
         elif rerank:
             hits = await search(question, n_results=max(top_k, settings.MMRAG_RERANK_CANDIDATES))
             if hits["ids"]:
-                fused = dict(zip(hits["ids"], hits[extra])) if extra else None
+                carried = {column: dict(zip(hits["ids"], hits[column])) for column in extra}
                 hits = await self.embedder.rerank_results(question, hits, top_k=top_k)
-                if extra:
-                    hits[extra] = [fused[found] for found in hits["ids"]]
+                for column, of_id in carried.items():
+                    hits[column] = [of_id[found] for found in hits["ids"]]
         else:
             hits = await search(question, n_results=top_k)
         if not hits["ids"]:
@@ -256,7 +290,8 @@ class Pipeline:
                    "type": meta.get("type", "unknown")}
                   for at, (found, dist, meta) in enumerate(zip(hits["ids"], hits["distances"], hits["metadatas"]), 1)]
         for on, column, key in ((rerank, "rerank_scores", "rerank_score"), (hybrid, "hybrid_scores", "hybrid_score"),
-                                (mmr, "mmr_scores", "mmr_score")):
+                                (mmr, "mmr_scores", "mmr_score"), (multi, "fused_scores", "fused_score"),
+                                (multi, "matched_queries", "matched_queries")):
             if on:
                 for src, score in zip(ranked, hits[column]):
                     src[key] = score
@@ -309,9 +344,11 @@ def _as_http_500(fn):
 
 def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, parser: Optional[Any] = None,
                summarizer: Optional[Any] = None, llm_adapter: Optional[Any] = None,
-               mllm_adapter: Optional[Any] = None) -> FastAPI:
+               mllm_adapter: Optional[Any] = None, query_expander: Optional[Any] = None) -> FastAPI:
+    """`query_expander`: optional, any object with `async expand(question, n) -> List[str]` (ingest.LLMQueryExpander
+    over a generator is one); /query's `expand` field asks it for further phrasings of the question"""
     pipe = Pipeline({"embedder": embedder, "retriever": retriever, "parser": parser, "summarizer": summarizer,
-                     "llm": llm_adapter, "mllm": mllm_adapter})
+                     "llm": llm_adapter, "mllm": mllm_adapter, "expander": query_expander})
 
     @asynccontextmanager
     async def lifespan(app: FastAPI):  # api.py:65-128
@@ -352,6 +389,12 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
     @_as_http_500
     async def query_documents(request: QueryRequest):  # api.py:325-413
         t0 = time.time()
+        multi = request.variants is not None or request.expand > 0
+        if multi and (request.mmr or request.hybrid or request.group_by_document):
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                detail="Multi-query retrieval is not combined with MMR, hybrid retrieval or grouping "
+                                       "by document yet: send `variants` / `expand` without `mmr`, `hybrid` and "
+                                       "`group_by_document`")
         if request.group_by_document and (request.mmr or request.hybrid or request.rerank):
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="Grouping by document is not combined with MMR, hybrid retrieval or re-ranking "
@@ -366,10 +409,28 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
             if getattr(request, flag) and not (hasattr(pipe.embedder, method)
                                                and getattr(pipe.embedder, supports, lambda: True)()):
                 raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=detail)
-        # (combinations of modes were refused above: Pipeline.answer sees at most one of mmr / hybrid / grouping)
+        variants = None
+        if multi:
+            pipe._need(MULTI_NEEDS)
+            if request.expand > 0 and pipe.expander is None:
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                    detail="Query expansion is not configured: pass a `query_expander` to create_app, "
+                                           "or send the phrasings as `variants`")
+            variants = list(request.variants or [])
+            if request.expand > 0:
+                variants += [str(v)[:2000] for v in await pipe.expander.expand(request.query, request.expand)]
+            seen, kept = {request.query.strip()}, []
+            for v in variants:                      # a phrasing searched twice would only count twice
+                if v.strip() and v.strip() not in seen:
+                    seen.add(v.strip())
+                    kept.append(v)
+            variants = kept[:15]
+        # (combinations of modes were refused above: Pipeline.answer sees at most one of mmr / hybrid / grouping /
+        # variants)
         out = await pipe.answer(request.query, request.top_k, request.use_multimodal, rerank=request.rerank,
                                 hybrid=request.hybrid, mmr=request.mmr, mmr_lambda=request.mmr_lambda,
-                                group_by_document=request.group_by_document, per_document=request.per_document)
+                                group_by_document=request.group_by_document, per_document=request.per_document,
+                                variants=variants, variant_weight=request.variant_weight, fusion=request.fusion)
         if out is None:
             out = {"answer": NO_DOCS_ANSWER, "sources": []}
         return {**out, "processing_time": time.time() - t0}
