@@ -535,6 +535,46 @@ int mmrag_kmeans_assign(const void *rows, int64_t n, int64_t ld, int dtype, int 
 int mmrag_cluster_sums(const void *rows, int64_t ld, int dtype, int d, const int32_t *order, const int64_t *seg_off,
                        int k, float *out_sums, void *stream);
 
+/* Document-scoped top-k (csrc/scoped.hip): a batch of queries in ONE masked scan, each query seeing only the rows whose
+ * group ordinal (e.g. document) is in its own scope.  VectorIndex.scoped_search.
+ *
+ * A scope is a set of group ordinals.  Query b sees row r iff r < n, r's alive bit is set (when alive_bits is given)
+ * and group_of_row[r] is in scope scope_of_query[b]; a row with ordinal -1 is in no scope.
+ * Contract
+ *   - out_scores / out_rows [B, k] as mmrag_cosine_topk_deep's: score descending, ties to the lower row,
+ *     row + row_offset, (-inf, -1) padded; an empty scope, or one whose rows are all dead, gives padding only;
+ *   - a score's bits depend on the query row, the stored row and d alone (one fixed K order): not on the batch, the
+ *     scopes or the grid;
+ *   - a 128-row tile of stored rows whose ordinals no query of a 128-query tile can see is not fetched for that tile;
+ *   - every visible row is a candidate: a query has candidate slots for 32 k rows, at least 16384.  With
+ *     max_candidates at or below that nothing can overflow and the call does not synchronise; otherwise `stream` is
+ *     synchronised once to read the counts and a query with more visible rows is produced again alone.
+ *
+ *   q, rows         dev [B, ld] and [n, ld] of one `dtype` MMRAG_F32 / F16 / BF16 and one ld (mmrag_padded_dim or a
+ *                   larger width of whole 128-byte slabs), pad columns zero; MMRAG_F8E4M3 returns MMRAG_EUNSUPPORTED (an FP8
+ *                   collection is searched by scope on its re-scoring plane)
+ *   k               1..MMRAG_MAX_K_DEEP
+ *   alive_bits      dev, optional (NULL = every row): bit r & 31 of word r >> 5
+ *   group_of_row    dev [n] int32 ordinals in -1..n_groups-1
+ *   scope_of_query  dev [B] int32 in 0..S-1
+ *   scope_off       dev [S + 1] int32 ascending offsets into scope_groups; scope s = scope_groups[scope_off[s] ..
+ *                   scope_off[s + 1]), at most MMRAG_MAX_SCOPE_GROUPS ordinals, ascending
+ *   max_candidates  the caller's upper bound on the rows any ONE scope holds (n if unknown); a scope that holds more
+ *                   loses candidates
+ *   workspace       dev, >= mmrag_scoped_topk_workspace_bytes(B, n, k, n_groups) bytes (0 for arguments out of range),
+ *                   16-byte aligned
+ * MMRAG_EINVAL before anything is launched: a null pointer, B < 1, S < 1, n < 0 or >= 2^31, k out of range, d <= 0,
+ * ld < d, n_groups < 0, max_candidates < 0.  The scope tables live on the device and are not read by the host: a
+ * scope_of_query outside 0..S-1, a scope longer than MMRAG_MAX_SCOPE_GROUPS and an ordinal outside 0..n_groups-1 match
+ * nothing (the Python wrapper checks the host copies it is given). */
+#define MMRAG_MAX_SCOPE_GROUPS 64
+size_t mmrag_scoped_topk_workspace_bytes(int B, int64_t n, int k, int n_groups);
+int mmrag_scoped_topk(const void *q, const void *rows, int B, int64_t n, int d, int64_t ld, int dtype, int k,
+                      int64_t row_offset, const uint32_t *alive_bits, const int32_t *group_of_row, int n_groups,
+                      const int32_t *scope_of_query, int S, const int32_t *scope_off, const int32_t *scope_groups,
+                      int64_t max_candidates, float *out_scores, int64_t *out_rows, void *workspace,
+                      size_t workspace_bytes, void *stream);
+
 /* CLIP byte-level BPE (the text tower's tokenizer, BASELINE config 4; the reference only names CLIP in config.py:106).
  * Host code, multi-threaded; equals multimodal_rag_amd/tokenizer.py:ClipBpeTokenizer, which tests pin to
  * transformers.CLIPTokenizer.  The caller passes text already NFC-normalised, whitespace-collapsed and lower-cased.

@@ -29,6 +29,7 @@ MAX_FUSE_LISTS, MAX_FUSE_CANDIDATES, MAX_FUSE_RESULTS = 16, 256, 4096
 FUSE_METHODS = {"rrf": 0, "max": 1}
 MAX_JOIN_PAIRS = 1 << 26   # mmrag_sim_join (MMRAG_MAX_JOIN_PAIRS)
 MAX_CLUSTERS = 4096   # mmrag_kmeans_assign / mmrag_cluster_sums (MMRAG_MAX_CLUSTERS)
+MAX_SCOPE_GROUPS = 64   # mmrag_scoped_topk (MMRAG_MAX_SCOPE_GROUPS)
 _DT2TORCH = {F32: torch.float32, F16: torch.float16, BF16: torch.bfloat16, F8E4M3: torch.float8_e4m3fn}
 _TORCH2DT = {v: k for k, v in _DT2TORCH.items()}
 
@@ -215,6 +216,17 @@ def _declare(lib):
                                         c_void_p, c_void_p]
     lib.mmrag_cluster_sums.restype = c_int
     lib.mmrag_cluster_sums.argtypes = [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+    # document-scoped top-k (csrc/scoped.hip); the _ex entry adds a candidate capacity (tests, not in include/mmrag.h)
+    lib.mmrag_scoped_topk_workspace_bytes.restype = c_size_t
+    lib.mmrag_scoped_topk_workspace_bytes.argtypes = [c_int, c_int64, c_int, c_int]
+    lib.mmrag_scoped_topk.restype = c_int
+    lib.mmrag_scoped_topk.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int64, c_int, c_int, c_int64,
+                                      c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64,
+                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.mmrag_internal_scoped_topk_ex.restype = c_int
+    lib.mmrag_internal_scoped_topk_ex.argtypes = lib.mmrag_scoped_topk.argtypes + [c_int64]
+    lib.mmrag_internal_candidate_capacity.restype = c_int64
+    lib.mmrag_internal_candidate_capacity.argtypes = [c_int]
     from .lexical import declare as declare_lexical   # BM25 analyzer, device index and search (csrc/lexical.hip)
 
     declare_lexical(lib)
@@ -617,6 +629,85 @@ def cluster_sums(rows: torch.Tensor, d: int, order: torch.Tensor, seg_off: torch
                                       order_ptr, seg_off.data_ptr(), k, sums.data_ptr(), _stream_ptr(dev))
     _check(st, "mmrag_cluster_sums")
     return sums
+
+
+def scoped_topk_workspace_bytes(B: int, n: int, k: int, n_groups: int) -> int:
+    return int(lib().mmrag_scoped_topk_workspace_bytes(int(B), int(n), int(k), int(n_groups)))
+
+
+def candidate_capacity(k: int) -> int:
+    """candidate slots a query of scoped_topk has for a top-k of k (csrc/candidate_select.h): with max_candidates at or
+    below it the call cannot overflow and does not synchronise"""
+    return int(lib().mmrag_internal_candidate_capacity(int(k)))
+
+
+def check_scopes(B: int, n_groups: int, scope_of_query, scope_off, scope_groups) -> int:
+    """The scope tables of scoped_topk as HOST integer sequences, checked the way the device cannot report: returns S.
+    Raises MMRagNativeError for a scope of more than MAX_SCOPE_GROUPS ordinals, a query whose scope index is outside
+    0..S-1, offsets that do not ascend from 0 to len(scope_groups), and ordinals that are not ascending inside a scope
+    or outside 0..n_groups-1."""
+    soq = [int(v) for v in scope_of_query]
+    off = [int(v) for v in scope_off]
+    grp = [int(v) for v in scope_groups]
+    S = len(off) - 1
+    if len(soq) != B:
+        raise MMRagNativeError(f"scoped_topk: scope_of_query holds {len(soq)} entries for {B} queries")
+    if S < 1 or off[0] != 0 or off[-1] != len(grp) or any(b < a for a, b in zip(off, off[1:])):
+        raise MMRagNativeError("scoped_topk: scope_off must hold S + 1 >= 2 ascending offsets from 0 to "
+                               "len(scope_groups)")
+    for s in range(S):
+        mine = grp[off[s]: off[s + 1]]
+        if len(mine) > MAX_SCOPE_GROUPS:
+            raise MMRagNativeError(f"scoped_topk: scope {s} holds {len(mine)} groups, at most {MAX_SCOPE_GROUPS}")
+        if any(b <= a for a, b in zip(mine, mine[1:])) or (mine and (mine[0] < 0 or mine[-1] >= n_groups)):
+            raise MMRagNativeError(f"scoped_topk: scope {s} must hold ascending ordinals in 0..{n_groups - 1}")
+    bad = [v for v in soq if not 0 <= v < S]
+    if bad:
+        raise MMRagNativeError(f"scoped_topk: scope_of_query {bad[0]} outside 0..{S - 1}")
+    return S
+
+
+def scoped_topk(q: torch.Tensor, rows: torch.Tensor, n: int, d: int, k: int, group_col: torch.Tensor, n_groups: int,
+                scope_of_query, scope_off, scope_groups, max_candidates: int,
+                alive_bits: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                row_offset: int = 0, cap: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-k of each query of q [B, ld] over the rows of ITS scope among the first n of `rows` [cap, ld]
+    (include/mmrag.h mmrag_scoped_topk): query b sees row r iff r is alive and group_col[r] (int32 ordinal, -1 = none)
+    is one of scope_groups[scope_off[s] : scope_off[s + 1]] for s = scope_of_query[b].  The three scope tables are HOST
+    integer tensors or sequences: they are checked here (check_scopes; the device cannot report a malformed table) and
+    copied to the device in one transfer.  `max_candidates`: an upper bound on the rows one scope holds (n if unknown).
+    Returns (scores [B, k] float32 descending, rows [B, k] int64 + row_offset), (-inf, -1) padded.  No host
+    synchronisation unless max_candidates exceeds the candidate slots of a query.  `cap` (tests only): fewer slots."""
+    _dev_check(q, rows, alive_bits, group_col)
+    _check_q_rows("scoped_topk", q, rows, n, other="rows")
+    _check_stored_rows("scoped_topk", rows)
+    B, ld = q.shape
+    n, k, n_groups = int(n), int(k), int(n_groups)
+    _check_alive("scoped_topk", alive_bits, n, rows)
+    dev = q.device
+    if (group_col.dim() != 1 or group_col.dtype != torch.int32 or not group_col.is_contiguous()
+            or group_col.numel() < n or group_col.device != dev):
+        raise MMRagNativeError("scoped_topk: group_col must be a contiguous int32 tensor of at least n ordinals on the "
+                               "rows' device")
+    tables = [torch.as_tensor(t, dtype=torch.int32).reshape(-1).cpu()
+              for t in (scope_of_query, scope_off, scope_groups)]
+    S = check_scopes(B, n_groups, *(t.tolist() for t in tables))
+    at = [0, B, B + S + 1]
+    # one pinned copy; a spare element keeps the ordinals' pointer real when no scope holds any
+    packed = _pinned_to_device(torch.cat(tables + [torch.zeros(1, dtype=torch.int32)]), dev)
+    soq, off, grp = (packed[lo:] for lo in at)
+    need = scoped_topk_workspace_bytes(B, n, k, n_groups)
+    if workspace is None or _nbytes(workspace) < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    out_s, out_r = _topk_out(B, k, dev)
+    with torch.cuda.device(dev):
+        st = lib().mmrag_internal_scoped_topk_ex(
+            q.data_ptr(), rows.data_ptr(), B, n, int(d), ld, _TORCH2DT[q.dtype], k, int(row_offset),
+            alive_bits.data_ptr() if alive_bits is not None else None, group_col.data_ptr(), n_groups,
+            soq.data_ptr(), S, off.data_ptr(), grp.data_ptr(), int(max_candidates), out_s.data_ptr(), out_r.data_ptr(),
+            workspace.data_ptr(), _nbytes(workspace), _stream_ptr(dev), int(cap))
+    _check(st, "mmrag_scoped_topk")
+    return out_s, out_r
 
 
 def join_tile(T: int, at: int, slot_order: bool = False) -> Tuple[int, int]:

@@ -25,7 +25,7 @@ import hashlib
 import logging
 import threading
 import time
-from typing import Any, Dict, List, Optional, Sequence
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -295,7 +295,11 @@ class EmbeddingManager:
         queries are served by one batched encode + one batched search."""
         from .dispatcher import QueryDispatcher
 
-        self._dispatcher = QueryDispatcher(self.batch_query, max_batch=max_batch, max_wait_ms=max_wait_ms)
+        def scoped(texts, n_results, doc_ids_per_query):      # the dispatcher's (texts, k, documents) order
+            return self.batch_scoped_query(texts, doc_ids_per_query, n_results=n_results)
+
+        self._dispatcher = QueryDispatcher(self.batch_query, max_batch=max_batch, max_wait_ms=max_wait_ms,
+                                           scoped_fn=scoped if self.supports_scoped() else None)
         return self._dispatcher
 
     _INCLUDE = ["metadatas", "documents", "distances"]
@@ -395,6 +399,54 @@ class EmbeddingManager:
     async def query(self, query_text: str, n_results: int = 5, filter_dict: Optional[Dict] = None) -> Dict[str, Any]:
         """embedder.py:539-583."""
         return await self._single("Query", None, self._answer, query_text, n_results, filter_dict, dispatched=True)
+
+    def supports_scoped(self) -> bool:
+        """True when ONE search serves a batch whose queries each name their own documents (VectorIndex.scoped_query; a
+        float8_e4m3fn collection needs its re-scoring plane).  Any other collection still answers scoped_query, by one
+        filtered search per distinct set of documents."""
+        return self.collection is None or (hasattr(self.collection, "scoped_query") and self._has_full_rows())
+
+    def _answer_scoped(self, texts: Sequence[str], n_results: int,
+                       doc_ids_per_query: Sequence[Sequence[str]]) -> List[Dict[str, Any]]:
+        """blocking, one worker thread: cached or fresh embeddings (ONE encoder pass for the misses), then ONE
+        collection.scoped_query for all of them; a collection without it (sharded) is asked once per distinct scope
+        with the scope as a `where` filter"""
+        emb = self._embed(texts)
+        if hasattr(self.collection, "scoped_query") and self._has_full_rows():
+            res = self.collection.scoped_query(emb, n_results=n_results, scopes=[list(ids) for ids in doc_ids_per_query],
+                                               include=self._INCLUDE)
+            return self._split(res, len(texts))
+        by_scope: Dict[Tuple[str, ...], List[int]] = {}
+        for at, ids in enumerate(doc_ids_per_query):
+            by_scope.setdefault(tuple(ids), []).append(at)
+        out: List[Optional[Dict[str, Any]]] = [None] * len(texts)
+        for ids, mine in by_scope.items():
+            res = self.collection.query(query_embeddings=emb[mine], n_results=n_results,
+                                        where={"doc_id": {"$in": list(ids)}}, include=self._INCLUDE)
+            for at, hit in zip(mine, self._split(res, len(mine))):
+                out[at] = hit
+        return out  # type: ignore[return-value]
+
+    async def scoped_query(self, query_text: str, doc_ids: Sequence[str], n_results: int = 5) -> Dict[str, Any]:
+        """query() answered from the documents `doc_ids` only: the result dict of query().  Unknown ids match nothing
+        (empty lists).  Same empty-query error, embedding cache and query count as query(); with dynamic batching on,
+        concurrent callers share one encode and one scoped search whatever their documents."""
+        if self._dispatcher is not None:
+            await self._ready()
+            if not query_text or not query_text.strip():
+                raise ValueError("Query text cannot be empty")
+            return await self._dispatcher.submit(query_text, n_results, None, list(doc_ids))
+        return await self._single("Scoped query", None, self._answer_scoped, query_text, n_results, [list(doc_ids)])
+
+    async def batch_scoped_query(self, queries: List[str], doc_ids_per_query: Sequence[Sequence[str]],
+                                 n_results: int = 5) -> List[Dict[str, Any]]:
+        """batch_query's twin for scoped_query: query i is answered from the documents doc_ids_per_query[i]; one batched
+        encode and one search for all of them; a query that cannot be answered gets a dict with empty lists and an
+        'error' message."""
+        if len(doc_ids_per_query) != len(queries):
+            raise ValueError(f"{len(doc_ids_per_query)} document lists for {len(queries)} queries")
+        live = [list(ids) for q, ids in zip(queries, doc_ids_per_query) if q and q.strip()]    # as _batch picks them
+        return await self._batch("Batch scoped query", None, _EMPTY, self._answer_scoped, queries, n_results, live)
 
     def supports_hybrid(self) -> bool:
         """True when the collection can answer hybrid_query (a single-GPU VectorIndex; not the sharded serving path)"""

@@ -224,6 +224,7 @@ class VectorIndex:
         self._lock = threading.RLock()
         self._search_ws: Optional[torch.Tensor] = None    # candidate-list workspace of the search kernels, reused
         self._deep_ws: Optional[torch.Tensor] = None      # workspace of the deep search (n_results > 20), reused
+        self._scoped_ws: Optional[torch.Tensor] = None    # workspace of the scoped search, reused
         self._lex = None   # lexical.LexicalIndex once enable_lexical() ran (lazily: first lexical / hybrid query)
         self._groups: Dict[str, Dict[str, Any]] = {}   # metadata key -> group column state once enable_grouping(key) ran
         self.f32_exact = bool(settings.MMRAG_F32_EXACT_SEARCH)   # float32 collections only (see config.py)
@@ -1011,6 +1012,8 @@ class VectorIndex:
                 self._lex.compact(keep)
             for st in self._groups.values():      # the same kept rows, in order; ordinals keep their values
                 st["col"] = self._compacted(st["col"], cap, keep_dev, -1)
+                live = st["col"][: self._n]
+                st["counts"] = torch.bincount(live[live >= 0], minlength=len(st["values"])).tolist()
 
     def reset(self):
         with self._lock:
@@ -1076,7 +1079,7 @@ class VectorIndex:
     def _group_ordinals(self, st: Dict[str, Any], metadatas: Sequence[Dict[str, Any]]) -> torch.Tensor:
         """group ordinals (host int32) of rows with these metadatas, in row order: distinct values of meta.get(key) are
         numbered by first appearance; a missing key, None or an unhashable value gives -1 (caller holds the lock)"""
-        key, ordinal, values = st["key"], st["ordinal"], st["values"]
+        key, ordinal, values, counts = st["key"], st["ordinal"], st["values"], st["counts"]
         out = np.full(len(metadatas), -1, dtype=np.int32)
         for i, meta in enumerate(metadatas):
             v = meta.get(key)
@@ -1087,22 +1090,26 @@ class VectorIndex:
                 if o is None:
                     o = ordinal[v] = len(values)
                     values.append(v)
+                    counts.append(0)
             except TypeError:        # unhashable: the row has no key
                 continue
             out[i] = o
+            counts[o] += 1
         return torch.from_numpy(out)
 
     def enable_grouping(self, key: str = "doc_id") -> Dict[str, Any]:
         """Build the group column of metadata key `key`: a device int32 [capacity] with each row's group ordinal
         (distinct values of meta.get(key) numbered by first appearance in row order; -1 where the key is missing, None
-        or unhashable) and the host table ordinal -> value.  From then on add, add_rows_device, capacity growth and
-        compact keep it current; reset drops it; delete needs nothing (dead rows are never candidates).  Until then
-        they do no grouping work.  Runs by itself on the first grouped_search / grouped_query for that key.  The column
-        is derived from the metadata and is not persisted: a loaded collection rebuilds it on first use."""
+        or unhashable), the host table ordinal -> value and, beside it, the rows stored per ordinal (dead rows still
+        counted until compact: an upper bound, what scoped_search sizes its candidate slots by).  From then on add,
+        add_rows_device, capacity growth and compact keep them current; reset drops them; delete needs nothing (dead
+        rows are never candidates).  Until then they do no grouping work.  Runs by itself on the first grouped_search /
+        grouped_query / scoped_search for that key.  The column is derived from the metadata and is not persisted: a
+        loaded collection rebuilds it on first use."""
         with self._lock:
             st = self._groups.get(key)
             if st is None:
-                st = {"key": key, "ordinal": {}, "values": []}
+                st = {"key": key, "ordinal": {}, "values": [], "counts": []}
                 col = torch.full((self._matrix.shape[0],), -1, dtype=torch.int32, device=self.device)
                 if self._n:
                     col[: self._n].copy_(self._group_ordinals(st, self._metadatas[: self._n]))
@@ -1215,6 +1222,110 @@ class VectorIndex:
                 res["groups"].append(groups)
                 res["exhaustive"].append(found >= G or valid < depths[b])
             return res
+
+    # ------------------------------------------------------------------ per-query document scopes ----
+    def _scope_tables(self, st: Dict[str, Any], scopes, B: int):
+        """`scopes` (one entry per query: a metadata value or a list / tuple / set of values) as the host tables of
+        _native.scoped_topk (caller holds the lock): (scope of each query, the S distinct scopes as ascending ordinal
+        tuples, each scope's row-count bound, each query's values as given).  An unknown value matches nothing; equal
+        ordinal sets are one scope."""
+        scopes = list(scopes)
+        if len(scopes) != B:
+            raise ValueError(f"scopes holds {len(scopes)} entries for {B} queries")
+        ordinal, counts = st["ordinal"], st["counts"]
+        index: Dict[Tuple[int, ...], int] = {}
+        of_query, given = [], []
+        for entry in scopes:
+            vals = list(entry) if isinstance(entry, (list, tuple, set, frozenset)) else [entry]
+            ords = set()
+            for v in vals:
+                try:
+                    o = ordinal.get(v)
+                except TypeError:        # unhashable: no row has it as its key
+                    o = None
+                if o is not None:
+                    ords.add(o)
+            of_query.append(index.setdefault(tuple(sorted(ords)), len(index)))
+            given.append(vals)
+        sets = list(index)
+        return of_query, sets, [sum(counts[o] for o in t) for t in sets], given
+
+    def _launch_scoped(self, query_embeddings, n_results: int, scopes, key: str, where, check_norm: bool = True):
+        """enqueue the scoped search (caller holds the lock): device (scores, rows) [B, n_results], no host sync on
+        the kernel's path"""
+        self._need_plane("scoped_query")
+        k = int(n_results)
+        if not 1 <= k <= _native.MAX_K_DEEP:
+            raise ValueError(f"n_results must be in 1..{_native.MAX_K_DEEP} for a scoped search")
+        st = self.enable_grouping(key)
+        qf = self._to_device_f32(query_embeddings, "query", check_norm)     # converted and norm-checked once
+        B = qf.shape[0]
+        of_query, sets, bound, given = self._scope_tables(st, scopes, B)
+        cap = _native.candidate_capacity(k)
+        slow = [len(t) > _native.MAX_SCOPE_GROUPS or bound[s] > cap for s, t in enumerate(sets)]
+        fast_q = [b for b in range(B) if not slow[of_query[b]]]
+        out_s = out_r = None
+        if fast_q:
+            rows = self._full
+            q = self._pack_plane_queries(qf) if self._plane is not None else self._pack_queries(qf, check_norm=False)
+            if len(fast_q) < B:
+                q = q[torch.tensor(fast_q, device=self.device)].contiguous()
+            used = sorted({of_query[b] for b in fast_q})
+            renum = {s: i for i, s in enumerate(used)}
+            off = [0]
+            for s in used:
+                off.append(off[-1] + len(sets[s]))
+            need = _native.scoped_topk_workspace_bytes(len(fast_q), self._n, k, len(st["values"]))
+            out_s, out_r = _native.scoped_topk(
+                q, rows, self._n, self.dim, k, st["col"], len(st["values"]), [renum[of_query[b]] for b in fast_q], off,
+                [o for s in used for o in sets[s]], max([bound[s] for s in used] + [1]),
+                alive_bits=self._where_bits(where), workspace=self._workspace("_scoped_ws", need))
+            if len(fast_q) == B:
+                return out_s, out_r
+        # a scope of more groups than the kernel's lists hold, or of more rows than a query has candidate slots: the
+        # filtered search, one per distinct scope, joined in query order
+        scores = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        rows_o = torch.empty((B, k), dtype=torch.int64, device=self.device)
+        if fast_q:
+            at = torch.tensor(fast_q, device=self.device)
+            scores[at], rows_o[at] = out_s, out_r
+        for s in sorted({of_query[b] for b in range(B) if slow[of_query[b]]}):
+            mine = [b for b in range(B) if of_query[b] == s]
+            at = torch.tensor(mine, device=self.device)
+            only = {key: {"$in": given[mine[0]]}}
+            ss, rr = self._launch_search(qf[at].contiguous(), k, {"$and": [where, only]} if where else only,
+                                         check_norm=False)
+            scores[at], rows_o[at] = ss, rr
+        return scores, rows_o
+
+    def scoped_search(self, query_embeddings, n_results: int, scopes, key: str = "doc_id",
+                      where: Optional[Dict[str, Any]] = None):
+        """Raw device search with a scope PER QUERY (csrc/scoped.hip, include/mmrag.h mmrag_scoped_topk): query b is
+        answered from the rows whose metadata `key` is one of the values of scopes[b] (a value or a list of values; an
+        unknown value matches nothing, an empty list gives no hits) -- what search(where={key: {"$in": scopes[b]}})
+        returns for each query, in ONE encode-free batch: one launch sequence, no host bitmap per scope, and the row
+        tiles no query of the batch can see are not read.  Returns (scores [B, k] float32 desc, rows [B, k] int64,
+        -1 = none), n_results up to MAX_K_DEEP.
+
+        `where` narrows the whole batch further; tombstones are honoured.  A float8_e4m3fn collection is searched on its
+        re-scoring plane (exact scores; capacity mode raises ValueError).  A scope of more than MAX_SCOPE_GROUPS values,
+        or whose documents hold more rows than a query has candidate slots (32 * n_results, at least 16384; dead rows
+        count until compact()), takes the filtered search instead, in the same result."""
+        with self._lock:
+            return self._launch_scoped(query_embeddings, n_results, scopes, key, where)
+
+    def scoped_query(self, query_embeddings, n_results: int = 10, scopes=(), key: str = "doc_id",
+                     where: Optional[Dict[str, Any]] = None,
+                     include: Sequence[str] = ("metadatas", "documents", "distances"),
+                     check_norm: bool = True) -> Dict[str, Any]:
+        """query() with a scope per query (see scoped_search): the Chroma-shaped dict of query(), query b's hits taken
+        from the rows whose `key` is in scopes[b] only."""
+        with self._lock, stage("search"):
+            scores, rows = self._launch_scoped(query_embeddings, n_results, scopes, key, where, check_norm)
+            tables = self._tables()
+            emb_src = self._full if "embeddings" in include else None
+        with stage("collect"):
+            return self._collect(scores, rows, include, *tables, emb_src)
 
     # ------------------------------------------------------------------ multi-query fusion ----
     def _launch_fused(self, query_embeddings, list_off, n_results: int, fetch_k, weights, method, where,

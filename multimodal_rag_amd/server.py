@@ -68,6 +68,12 @@ class QueryRequest(BaseModel):  # api.py:161-164
     variant_weight: Optional[float] = Field(None, ge=-1000.0, le=1000.0)
     fusion: Optional[Literal["rrf", "max"]] = None
     expand: int = Field(0, ge=0, le=15)
+    # not in the reference: answer from these documents only (the `doc_id`s /upload returned; 1 to 64 of them).  A
+    # plain or re-ranked query takes EmbeddingManager.scoped_query, where concurrent callers with different documents
+    # share one search; `hybrid`, `mmr`, `group_by_document` and `variants` get the same restriction as their filter.
+    # Ids no stored document has match nothing: the answer then has no sources
+    doc_ids: Optional[Annotated[List[Annotated[str, Field(min_length=1, max_length=200)]],
+                                Field(min_length=1, max_length=64)]] = None
 
 
 # request flag -> what it needs of the embedder (method, `supports_*` check) and the 400 detail when that is missing;
@@ -239,7 +245,7 @@ class Pipeline:
                      hybrid: bool = False, mmr: bool = False, mmr_lambda: Optional[float] = None,
                      group_by_document: bool = False, per_document: int = 1,
                      variants: Optional[List[str]] = None, variant_weight: Optional[float] = None,
-                     fusion: Optional[str] = None) -> Optional[dict]:
+                     fusion: Optional[str] = None, doc_ids: Optional[List[str]] = None) -> Optional[dict]:
         """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
         max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the cross-encoder's best top_k.  `hybrid`: the hits come from
         dense + BM25 retrieval fused by reciprocal rank.  `mmr`: the hits are a maximal-marginal-relevance selection of
@@ -247,23 +253,31 @@ class Pipeline:
         `per_document` best of each of the top_k best documents, flattened in document order.  `variants` (a list,
         possibly empty; alone or with `rerank`): the hits are the fusion of the ranked lists of `question` and these
         further phrasings (EmbeddingManager.multi_query; `variant_weight` for each of them against 1.0, `fusion`
-        "rrf" or "max"); the generator and the re-ranker see `question` only"""
+        "rrf" or "max"); the generator and the re-ranker see `question` only.  `doc_ids`: hits from these documents
+        only -- a plain (or re-ranked) query through EmbeddingManager.scoped_query, every other mode through its
+        filter"""
         multi = variants is not None
+        # the restriction as the filter the embedder's methods take (nothing is passed when there is none)
+        only = {} if doc_ids is None else {"filter_dict": {"doc_id": {"$in": list(doc_ids)}}}
         if multi:
             weights = None if variant_weight is None else [1.0] + [float(variant_weight)] * len(variants)
 
             def search(text, n_results):
                 return self.embedder.multi_query([text] + list(variants), n_results=n_results, weights=weights,
-                                                 method=fusion)
+                                                 method=fusion, **only)
         elif mmr:
-            search = functools.partial(self.embedder.mmr_query, lambda_mult=mmr_lambda)
+            search = functools.partial(self.embedder.mmr_query, lambda_mult=mmr_lambda, **only)
+        elif hybrid:
+            search = functools.partial(self.embedder.hybrid_query, **only)
+        elif doc_ids is not None and hasattr(self.embedder, "scoped_query"):
+            search = functools.partial(self.embedder.scoped_query, doc_ids=list(doc_ids))
         else:
-            search = self.embedder.hybrid_query if hybrid else self.embedder.query
+            search = functools.partial(self.embedder.query, **only)
         # per-hit columns re-ranking carries along
         extra = ("fused_scores", "matched_queries") if multi else ("mmr_scores",) if mmr else \
             ("hybrid_scores",) if hybrid else ()
         if group_by_document:
-            hits = await self.embedder.grouped_query(question, n_groups=top_k, group_size=per_document)
+            hits = await self.embedder.grouped_query(question, n_groups=top_k, group_size=per_document, **only)
         elif rerank:
             hits = await search(question, n_results=max(top_k, settings.MMRAG_RERANK_CANDIDATES))
             if hits["ids"]:
@@ -430,7 +444,8 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
         out = await pipe.answer(request.query, request.top_k, request.use_multimodal, rerank=request.rerank,
                                 hybrid=request.hybrid, mmr=request.mmr, mmr_lambda=request.mmr_lambda,
                                 group_by_document=request.group_by_document, per_document=request.per_document,
-                                variants=variants, variant_weight=request.variant_weight, fusion=request.fusion)
+                                variants=variants, variant_weight=request.variant_weight, fusion=request.fusion,
+                                doc_ids=request.doc_ids)
         if out is None:
             out = {"answer": NO_DOCS_ANSWER, "sources": []}
         return {**out, "processing_time": time.time() - t0}
