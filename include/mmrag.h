@@ -575,6 +575,75 @@ int mmrag_scoped_topk(const void *q, const void *rows, int B, int64_t n, int d, 
                       int64_t max_candidates, float *out_scores, int64_t *out_rows, void *workspace,
                       size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Late-interaction re-ranking (ColBERT's MaxSim) with the bi-encoder alone.  The reference has no counterpart: its
+ * EmbeddingManager.rerank_results is a placeholder (app/utils/embedder.py:834-859).  The encoder's per-token outputs are
+ * kept instead of pooled; a (query, passage) pair scores the mean, over the query's tokens, of each token's best cosine
+ * against the passage's tokens, and the arg-max says which passage token each query token matched.
+ * multimodal_rag_amd/late.py LateInteractionScorer.
+ *
+ * mmrag_encoder_forward_tokens (csrc/encoder.hip): the blocks of mmrag_encoder_forward, ending in token rows instead of
+ * the pooled row.
+ * Contract
+ *   - out_tokens row t = the last hidden state of packed token t, times `proj`^T when proj is given (ONE
+ *     mmrag_linear_f16, bias-free), divided by max(||.||, 1e-12): float32 sum of squares, the epsilon and the arithmetic
+ *     of the pooled path's normalise, rounded to fp16 once;
+ *   - out_dim is a multiple of 64, i.e. whole 128-byte fp16 slabs, so ld = mmrag_padded_dim(out_dim, MMRAG_F16) equals
+ *     out_dim for every admissible shape: the rows have no pad columns (nothing to zero);
+ *   - desc.pool and desc.normalize are IGNORED; desc.arch must be MMRAG_ARCH_BERT (else MMRAG_EUNSUPPORTED);
+ *   - mmrag_encoder_forward is unchanged and may share the workspace (calls are stream-ordered).
+ *
+ *   desc, w, ids, pos_ids, cu_seqlens, T, B, max_len   as for mmrag_encoder_forward
+ *   proj        dev [out_dim, H] fp16 (a ColBERT-style checkpoint's `linear`) or NULL, then out_dim must equal H
+ *   out_dim     a multiple of 64, at most 1024
+ *   out_tokens  dev [T, ld] fp16, ld = mmrag_padded_dim(out_dim, MMRAG_F16) = out_dim, 16-byte aligned
+ *   workspace   >= mmrag_encoder_tokens_workspace_bytes(desc, T, B, out_dim) bytes (0 for arguments out of range)
+ * MMRAG_EINVAL before anything is launched: a null pointer, a bad shape, out_dim not a multiple of 64 or above 1024, a
+ * NULL proj with out_dim != H.  A short workspace returns MMRAG_EWORKSPACE.
+ *
+ * mmrag_maxsim_scores (csrc/maxsim.hip): one workgroup per pair, the query's tokens one 128-row tile, the passage walked
+ * in 128-token tiles of the rows-against-rows tile body the similarity join and the k-means assign step run.
+ * Contract
+ *   Sequences
+ *   - Query sequence s is rows q_start[s] .. q_start[s] + q_len[s] of q_tok; passage sequences likewise in d_tok.  The
+ *     starts are explicit, so a caller trims [CLS] / [SEP] by moving them.  q_tok and d_tok may be one buffer.
+ *   - Pair p scores query sequence pair_q[p] against passage sequence pair_d[p]; sequences may be shared between pairs.
+ *   Per pair p, i over its query tokens, j over its passage tokens
+ *   - best_sim[p][i] = max over j of <q_i, d_j>: float32 accumulation of the fp16 rows in the tile body's fixed K
+ *     order, so its bits depend on the two rows and dim alone;
+ *   - best_idx[p][i] = the LOWEST j that attains it;
+ *   - out_sum[p] = the float32 sum of best_sim[p][0 .. q_len), added in ascending i starting from 0.0f;
+ *   - rows past a sequence's last token are never part of a maximum (a zero row is not a token) and slots
+ *     i >= q_len of best_sim / best_idx are not written.
+ *   - one launch, no workspace, no host synchronisation, no atomics (the call can be captured into a graph);
+ *     identical calls give identical bits.
+ *
+ *   q_tok, d_tok   dev [q_rows, q_ld] and [d_rows, d_ld] fp16, pad columns zero, 16-byte aligned
+ *   q_ld, d_ld     mmrag_padded_dim(dim, MMRAG_F16) or a larger width of whole 128-byte slabs
+ *   dim            a multiple of 64, at most 1024
+ *   q_start, q_len dev [n_q] int32      d_start, d_len  dev [n_d] int32
+ *   pair_q, pair_d dev [P] int32
+ *   out_sum        dev [P] float32
+ *   out_best_sim   dev [P, MMRAG_MAX_LATE_QUERY_TOKENS] float32 or NULL
+ *   out_best_idx   dev [P, MMRAG_MAX_LATE_QUERY_TOKENS] int32 or NULL
+ * MMRAG_EINVAL before anything is launched: a null pointer (the two optional outputs aside), dim out of range,
+ * ld < dim or not whole slabs, P outside 1..65535, n_q, n_d, q_rows or d_rows below 1.  The tables live on the device
+ * and are not read by the host: a pair whose sequence index is outside its table, whose q_len is outside
+ * 1..MMRAG_MAX_LATE_QUERY_TOKENS or d_len outside 1..MMRAG_MAX_LATE_DOC_TOKENS, or whose rows do not lie inside
+ * q_rows / d_rows reads no row and gets out_sum[p] = NaN (the Python wrapper checks the host copies it uploads). */
+#define MMRAG_MAX_LATE_QUERY_TOKENS 128
+#define MMRAG_MAX_LATE_DOC_TOKENS 512
+size_t mmrag_encoder_tokens_workspace_bytes(const mmrag_encoder_desc *desc, int64_t T, int B, int out_dim);
+int mmrag_encoder_forward_tokens(const mmrag_encoder_desc *desc, const void *const *w, const int32_t *ids,
+                                 const int32_t *pos_ids, const int32_t *cu_seqlens, int64_t T, int B, int max_len,
+                                 const void *proj, int out_dim, void *out_tokens, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int mmrag_maxsim_scores(const void *q_tok, int64_t q_rows, int64_t q_ld, const void *d_tok, int64_t d_rows,
+                        int64_t d_ld, int dim, const int32_t *q_start, const int32_t *q_len, int n_q,
+                        const int32_t *d_start, const int32_t *d_len, int n_d, const int32_t *pair_q,
+                        const int32_t *pair_d, int P, float *out_sum, float *out_best_sim, int32_t *out_best_idx,
+                        void *stream);
+
 /* CLIP byte-level BPE (the text tower's tokenizer, BASELINE config 4; the reference only names CLIP in config.py:106).
  * Host code, multi-threaded; equals multimodal_rag_amd/tokenizer.py:ClipBpeTokenizer, which tests pin to
  * transformers.CLIPTokenizer.  The caller passes text already NFC-normalised, whitespace-collapsed and lower-cased.

@@ -30,6 +30,9 @@ FUSE_METHODS = {"rrf": 0, "max": 1}
 MAX_JOIN_PAIRS = 1 << 26   # mmrag_sim_join (MMRAG_MAX_JOIN_PAIRS)
 MAX_CLUSTERS = 4096   # mmrag_kmeans_assign / mmrag_cluster_sums (MMRAG_MAX_CLUSTERS)
 MAX_SCOPE_GROUPS = 64   # mmrag_scoped_topk (MMRAG_MAX_SCOPE_GROUPS)
+# mmrag_maxsim_scores (MMRAG_MAX_LATE_QUERY_TOKENS, MMRAG_MAX_LATE_DOC_TOKENS)
+MAX_LATE_QUERY_TOKENS, MAX_LATE_DOC_TOKENS = 128, 512
+MAX_LATE_PAIRS = 65535
 _DT2TORCH = {F32: torch.float32, F16: torch.float16, BF16: torch.bfloat16, F8E4M3: torch.float8_e4m3fn}
 _TORCH2DT = {v: k for k, v in _DT2TORCH.items()}
 
@@ -227,6 +230,16 @@ def _declare(lib):
     lib.mmrag_internal_scoped_topk_ex.argtypes = lib.mmrag_scoped_topk.argtypes + [c_int64]
     lib.mmrag_internal_candidate_capacity.restype = c_int64
     lib.mmrag_internal_candidate_capacity.argtypes = [c_int]
+    # late interaction (csrc/encoder.hip token rows, csrc/maxsim.hip)
+    lib.mmrag_encoder_tokens_workspace_bytes.restype = c_size_t
+    lib.mmrag_encoder_tokens_workspace_bytes.argtypes = [c_void_p, c_int64, c_int, c_int]
+    lib.mmrag_encoder_forward_tokens.restype = c_int
+    lib.mmrag_encoder_forward_tokens.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                                 c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.mmrag_maxsim_scores.restype = c_int
+    lib.mmrag_maxsim_scores.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
+                                        c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]
     from .lexical import declare as declare_lexical   # BM25 analyzer, device index and search (csrc/lexical.hip)
 
     declare_lexical(lib)
@@ -710,6 +723,68 @@ def scoped_topk(q: torch.Tensor, rows: torch.Tensor, n: int, d: int, k: int, gro
     return out_s, out_r
 
 
+def check_late_tables(q_rows: int, d_rows: int, q_start, q_len, d_start, d_len, pair_q, pair_d) -> Tuple[int, int, int]:
+    """The sequence and pair tables of maxsim_scores as HOST integer sequences, checked the way the device cannot
+    report (there a bad pair only gets a NaN): returns (n_q, n_d, P).  Raises MMRagNativeError for tables of unequal
+    length, no pair or more than MAX_LATE_PAIRS, a pair index outside its table, a query of 0 or more than
+    MAX_LATE_QUERY_TOKENS tokens, a passage of 0 or more than MAX_LATE_DOC_TOKENS, and a sequence that does not lie
+    inside its buffer's rows."""
+    qs, ql, ds, dl = ([int(v) for v in t] for t in (q_start, q_len, d_start, d_len))
+    pq, pd = [int(v) for v in pair_q], [int(v) for v in pair_d]
+    if len(qs) != len(ql) or len(ds) != len(dl) or not qs or not ds:
+        raise MMRagNativeError("maxsim_scores: start and len tables must have one entry per sequence, at least one "
+                               "sequence on each side")
+    if len(pq) != len(pd) or not 1 <= len(pq) <= MAX_LATE_PAIRS:
+        raise MMRagNativeError(f"maxsim_scores: pair_q and pair_d must hold the same 1..{MAX_LATE_PAIRS} pairs "
+                               f"(got {len(pq)} and {len(pd)})")
+    for side, starts, lens, rows, most in (("query", qs, ql, int(q_rows), MAX_LATE_QUERY_TOKENS),
+                                           ("passage", ds, dl, int(d_rows), MAX_LATE_DOC_TOKENS)):
+        for s, (a, n) in enumerate(zip(starts, lens)):
+            if not 1 <= n <= most:
+                raise MMRagNativeError(f"maxsim_scores: {side} {s} has {n} tokens, outside 1..{most}")
+            if a < 0 or a + n > rows:
+                raise MMRagNativeError(f"maxsim_scores: {side} {s} (rows {a}..{a + n}) is outside the {rows} rows given")
+    for name, idx, n in (("pair_q", pq, len(qs)), ("pair_d", pd, len(ds))):
+        bad = [v for v in idx if not 0 <= v < n]
+        if bad:
+            raise MMRagNativeError(f"maxsim_scores: {name} {bad[0]} outside 0..{n - 1}")
+    return len(qs), len(ds), len(pq)
+
+
+def maxsim_scores(q_tok: torch.Tensor, d_tok: torch.Tensor, dim: int, q_start, q_len, d_start, d_len, pair_q, pair_d,
+                  want_best: bool = True):
+    """Late-interaction (MaxSim) scores of (query, passage) pairs over fp16 token rows (include/mmrag.h
+    mmrag_maxsim_scores).  `q_tok` [q_rows, ld] and `d_tok` [d_rows, ld] are device tensors of unit rows (they may be the
+    same tensor); sequence s of a side is rows start[s] .. start[s] + len[s].  The six tables are HOST integer tensors
+    or sequences: they are checked here (check_late_tables) and copied to the device in one transfer.  Returns device
+    tensors (sums [P] float32, best_sim [P, MAX_LATE_QUERY_TOKENS] float32, best_idx [P, MAX_LATE_QUERY_TOKENS] int32),
+    the last two None unless `want_best`; slots i >= q_len of a pair are not written.  One launch on the current
+    stream, no host synchronisation."""
+    _dev_check(q_tok, d_tok)
+    for name, t in (("q_tok", q_tok), ("d_tok", d_tok)):
+        if t.dim() != 2 or not t.is_contiguous() or t.dtype != torch.float16:
+            raise MMRagNativeError(f"maxsim_scores: {name} must be a contiguous 2-D float16 tensor")
+    if q_tok.device != d_tok.device:
+        raise MMRagNativeError("maxsim_scores: q_tok and d_tok must be on one device")
+    tables = [torch.as_tensor(t, dtype=torch.int32).reshape(-1).cpu()
+              for t in (q_start, q_len, d_start, d_len, pair_q, pair_d)]
+    n_q, n_d, P = check_late_tables(q_tok.shape[0], d_tok.shape[0], *(t.tolist() for t in tables))
+    dev = q_tok.device
+    packed = _pinned_to_device(torch.cat(tables), dev)
+    at = [0, n_q, 2 * n_q, 2 * n_q + n_d, 2 * n_q + 2 * n_d, 2 * n_q + 2 * n_d + P]
+    qs, ql, ds, dl, pq, pd = (packed[lo:] for lo in at)
+    sums = torch.empty(P, dtype=torch.float32, device=dev)
+    best_sim = torch.empty((P, MAX_LATE_QUERY_TOKENS), dtype=torch.float32, device=dev) if want_best else None
+    best_idx = torch.empty((P, MAX_LATE_QUERY_TOKENS), dtype=torch.int32, device=dev) if want_best else None
+    with torch.cuda.device(dev):
+        st = lib().mmrag_maxsim_scores(q_tok.data_ptr(), q_tok.shape[0], q_tok.shape[1], d_tok.data_ptr(),
+                                       d_tok.shape[0], d_tok.shape[1], int(dim), qs.data_ptr(), ql.data_ptr(), n_q,
+                                       ds.data_ptr(), dl.data_ptr(), n_d, pq.data_ptr(), pd.data_ptr(), P,
+                                       sums.data_ptr(), _ptr(best_sim), _ptr(best_idx), _stream_ptr(dev))
+    _check(st, "mmrag_maxsim_scores")
+    return sums, best_sim, best_idx
+
+
 def join_tile(T: int, at: int, slot_order: bool = False) -> Tuple[int, int]:
     """(ti, tj) of tile-pair id `at` of a T x T triangle: row-major, or (slot_order) in the order the join kernel runs"""
     ti, tj = c_int64(0), c_int64(0)
@@ -1073,6 +1148,38 @@ def encoder_forward(desc: EncoderDesc, weight_ptrs, ids: torch.Tensor, pos_ids: 
                                          workspace.data_ptr(), _nbytes(workspace),
                                          _stream_ptr(ids.device))
     _check(st, "mmrag_encoder_forward")
+    return out
+
+
+def encoder_tokens_workspace_bytes(desc: EncoderDesc, T: int, B: int, out_dim: int) -> int:
+    return int(lib().mmrag_encoder_tokens_workspace_bytes(ctypes.byref(desc), T, B, int(out_dim)))
+
+
+def encoder_forward_tokens(desc: EncoderDesc, weight_ptrs, ids: torch.Tensor, pos_ids: torch.Tensor,
+                           cu_seqlens: torch.Tensor, max_len: int, proj: Optional[torch.Tensor] = None,
+                           workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One encoder pass over packed token ids -> token rows [T, ld] float16 (include/mmrag.h
+    mmrag_encoder_forward_tokens): row t is the L2-normalised last hidden state of packed token t, through `proj`
+    [out_dim, hidden] fp16 (bias-free) when given.  out_dim is a multiple of 64, so ld = padded_dim(out_dim, float16)
+    is out_dim itself: the rows have no pad columns."""
+    _dev_check(ids, pos_ids, cu_seqlens, proj, workspace, out)
+    T, B = ids.numel(), cu_seqlens.numel() - 1
+    out_dim = desc.hidden
+    if proj is not None:
+        if proj.dim() != 2 or proj.dtype != torch.float16 or not proj.is_contiguous() or proj.shape[1] != desc.hidden:
+            raise MMRagNativeError("encoder_forward_tokens: proj must be a contiguous [out_dim, hidden] float16 tensor")
+        out_dim = int(proj.shape[0])
+    need = encoder_tokens_workspace_bytes(desc, T, B, out_dim)
+    if workspace is None or _nbytes(workspace) < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=ids.device)
+    if out is None:
+        out = torch.empty((max(T, 1), max(out_dim, 1)), dtype=torch.float16, device=ids.device)
+    with torch.cuda.device(ids.device):
+        st = lib().mmrag_encoder_forward_tokens(ctypes.byref(desc), weight_ptrs, ids.data_ptr(), pos_ids.data_ptr(),
+                                                cu_seqlens.data_ptr(), T, B, max_len, _ptr(proj), out_dim,
+                                                out.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
+                                                _stream_ptr(ids.device))
+    _check(st, "mmrag_encoder_forward_tokens")
     return out
 
 

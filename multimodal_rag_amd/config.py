@@ -73,6 +73,11 @@ class Settings:
     # reference's placeholder (truncation only).  /query re-ranks max(top_k, MMRAG_RERANK_CANDIDATES) search hits
     MMRAG_RERANKER_DIR: str = field(default_factory=lambda: os.getenv("MMRAG_RERANKER_DIR", ""))
     MMRAG_RERANK_CANDIDATES: int = field(default_factory=lambda: int(os.getenv("MMRAG_RERANK_CANDIDATES", "20")))
+    # which re-ranker rerank_results uses when its caller names none: "cross" (the cross-encoder above; without one the
+    # placeholder) or "late" (late interaction: token-level MaxSim with the bi-encoder itself, late.py -- needs no
+    # second model).  MMRAG_LATE_MAX_DOC_TOKENS: passage tokens "late" scores (0 = the encoder's length; at most 512)
+    MMRAG_RERANK_METHOD: str = field(default_factory=lambda: os.getenv("MMRAG_RERANK_METHOD", "cross"))
+    MMRAG_LATE_MAX_DOC_TOKENS: int = field(default_factory=lambda: int(os.getenv("MMRAG_LATE_MAX_DOC_TOKENS", "0")))
     # BM25 lexical leg (VectorIndex.lexical_query / hybrid_query, csrc/lexical.hip): term-frequency saturation k1 and
     # length normalisation b of the score, the same for every query
     MMRAG_BM25_K1: float = field(default_factory=lambda: float(os.getenv("MMRAG_BM25_K1", "1.2")))
@@ -112,6 +117,7 @@ class Settings:
     def __post_init__(self):
         self.dedup_threshold()
         self.topics()
+        self.rerank_method()
 
     def dedup_threshold(self) -> float:
         """MMRAG_DEDUP_THRESHOLD checked: 0 (off) or a cosine in (0, 1]"""
@@ -119,6 +125,12 @@ class Settings:
         if not 0.0 <= t <= 1.0:     # false for NaN too
             raise ValueError(f"MMRAG_DEDUP_THRESHOLD must be 0 (off) or a cosine in (0, 1] (got {self.MMRAG_DEDUP_THRESHOLD!r})")
         return t
+
+    def rerank_method(self) -> str:
+        """MMRAG_RERANK_METHOD checked: 'cross' or 'late' (tests set the attribute after start-up, so users call this)"""
+        if self.MMRAG_RERANK_METHOD not in ("cross", "late"):
+            raise ValueError(f"MMRAG_RERANK_METHOD must be 'cross' or 'late' (got {self.MMRAG_RERANK_METHOD!r})")
+        return self.MMRAG_RERANK_METHOD
 
     def topics(self) -> int:
         """MMRAG_TOPICS checked: 0 (automatic) or a cluster count in 1 .. 4096"""

@@ -1141,6 +1141,35 @@ __global__ __launch_bounds__(256) void pool_norm_kernel(const _Float16 *__restri
     }
 }
 
+// Token rows for late interaction (mmrag_encoder_forward_tokens): out[t, :] = x[t, :] / max(||x[t, :]||, 1e-12) as fp16,
+// one workgroup per token.  The sum of squares is pool_norm_kernel's (same thread-to-column map, the same wave and
+// workgroup folds), so with a CLS-pooled desc row 0 of a sequence is the pooled float32 row rounded to fp16 once.
+// D is a multiple of 64, i.e. whole 128-byte slabs: the output's padded width is D itself and there is no pad column.
+__global__ __launch_bounds__(256) void token_norm_kernel(const _Float16 *__restrict__ x, _Float16 *__restrict__ out,
+                                                          int D) {
+    __shared__ float red[4];
+    const size_t t = blockIdx.x;
+    float vals[4];  // D <= 1024
+    float sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = threadIdx.x + i * 256;
+        const float v = c < D ? (float)x[t * D + c] : 0.f;
+        vals[i] = v;
+        sq += v * v;
+    }
+    sq = wave_sum(sq);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
+    __syncthreads();
+    const float nrm = sqrtf(red[0] + red[1] + red[2] + red[3]);
+    const float inv = 1.0f / fmaxf(nrm, 1e-12f);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = threadIdx.x + i * 256;
+        if (c < D) out[t * D + c] = (_Float16)(vals[i] * inv);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // ViT front end.  patchify: image -> rows of the patch-embedding GEMM, vector order (c, ph, pw) =
 // the conv kernel's order.  Input either fp16 CHW already normalised, or raw uint8 HWC crops, in
@@ -1690,10 +1719,34 @@ static int carve(const mmrag_encoder_desc *d, int64_t T, int B, void *workspace,
 
 #define RUN(call) do { if ((st = (call)) != MMRAG_OK) return st; } while (0)
 
-// transformer blocks + head over the packed activations already in b.x
+// what a forward that ends in token rows (mmrag_encoder_forward_tokens) does instead of pooling
+struct TokenTail {
+    const void *proj;       // [out_dim, H] fp16 or null
+    int out_dim;
+    void *projected;        // [T, out_dim] fp16 scratch (proj only)
+    void *out;              // [T, out_dim] fp16
+};
+
+// `hidden` [T, H]: the final hidden states -> (projection) -> L2-normalised fp16 rows
+static int token_tail(const TokenTail &tk, const void *hidden, int64_t T, int H, void *stream) {
+    const void *rows = hidden;
+    if (tk.proj != nullptr) {
+        const int st = mmrag_linear_f16(hidden, T, H, tk.proj, tk.out_dim, nullptr, MMRAG_ACT_NONE, nullptr,
+                                        tk.projected, stream);
+        if (st != MMRAG_OK) return st;
+        rows = tk.projected;
+    }
+    token_norm_kernel<<<(unsigned)T, 256, 0, (hipStream_t)stream>>>((const _Float16 *)rows, (_Float16 *)tk.out,
+                                                                    tk.out_dim);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    return MMRAG_OK;
+}
+
+// transformer blocks + head over the packed activations already in b.x.  `tokens` (BERT only): end in token rows instead
+// of the pooled row; `out` and `sel` are then unused
 static int encoder_body(const mmrag_encoder_desc *d, const void *const *lw, const EncBuffers &b,
                         const int32_t *cu_seqlens, const int32_t *sel, int64_t T, int B, int max_len, float *out,
-                        void *stream) {
+                        void *stream, const TokenTail *tokens = nullptr) {
     const int H = d->hidden, I = d->intermediate, L = d->n_layers;
     void *x = b.x, *y = b.y, *qkv = b.qkv, *ctx = b.ctx, *hm = b.hm;
     int st;
@@ -1728,6 +1781,7 @@ static int encoder_body(const mmrag_encoder_desc *d, const void *const *lw, cons
         }
         MMRAG_CHECK_HIP(hipGetLastError());
         RUN(mmrag_layernorm_f16(x, y, g_prev, b_prev, T, H, d->ln_eps, stream));
+        if (tokens != nullptr) return token_tail(*tokens, y, T, H, stream);
         return mmrag_pool_normalize_f16(y, cu_seqlens, sel, out, B, H, d->pool, d->normalize, stream);
     }
     for (int l = 0; l < L; ++l, lw += 12) {
@@ -1754,6 +1808,7 @@ static int encoder_body(const mmrag_encoder_desc *d, const void *const *lw, cons
         }
     }
     if (d->arch == MMRAG_ARCH_BERT) {
+        if (tokens != nullptr) return token_tail(*tokens, x, T, H, stream);
         RUN(mmrag_pool_normalize_f16(x, cu_seqlens, sel, out, B, H, d->pool, d->normalize, stream));
     } else {
         // final LayerNorm (tail[0..1]), pooled token, bias-free projection (tail[2]), L2 normalise
@@ -1796,6 +1851,59 @@ int mmrag_encoder_forward(const mmrag_encoder_desc *d, const void *const *w, con
     g_last_forward_us.store((long long)std::chrono::duration_cast<std::chrono::microseconds>(
                                 std::chrono::steady_clock::now() - t0).count(), std::memory_order_relaxed);
     return st;
+}
+
+// ---------------------------------------------------------------------------------------------
+// token rows for late interaction: the same embedding and blocks, token_tail() instead of the pooling
+// ---------------------------------------------------------------------------------------------
+static bool tokens_dim_ok(const mmrag_encoder_desc *d, int out_dim) {
+    return d != nullptr && d->hidden > 0 && out_dim > 0 && out_dim % 64 == 0 && out_dim <= 1024;
+}
+
+size_t mmrag_encoder_tokens_workspace_bytes(const mmrag_encoder_desc *d, int64_t T, int B, int out_dim) {
+    if (!tokens_dim_ok(d, out_dim) || T <= 0 || B <= 0) return 0;
+    mmrag_encoder_desc dc = *d;
+    dc.out_dim = d->hidden;
+    return mmrag_encoder_workspace_bytes(&dc, T, B) + align256((size_t)T * (size_t)out_dim * 2);
+}
+
+int mmrag_encoder_forward_tokens(const mmrag_encoder_desc *d, const void *const *w, const int32_t *ids,
+                                 const int32_t *pos_ids, const int32_t *cu_seqlens, int64_t T, int B, int max_len,
+                                 const void *proj, int out_dim, void *out_tokens, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+    MMRAG_CHECK_ARG(d && w && ids && pos_ids && cu_seqlens && out_tokens, "encoder_forward_tokens: null pointer");
+    MMRAG_CHECK_ARG(T > 0 && T < INT_MAX && B > 0 && max_len > 0, "encoder_forward_tokens: bad shape T=%lld B=%d",
+                    (long long)T, B);
+    if (d->arch != MMRAG_ARCH_BERT) {
+        set_error("encoder_forward_tokens: BERT family only (arch %d)", d->arch);
+        return MMRAG_EUNSUPPORTED;
+    }
+    mmrag_encoder_desc dc = *d;   // pool / normalize of the caller's desc are ignored
+    dc.pool = MMRAG_POOL_FIRST, dc.normalize = 1, dc.out_dim = d->hidden;
+    int st;
+    RUN(check_desc(&dc));
+    MMRAG_CHECK_ARG(tokens_dim_ok(&dc, out_dim), "encoder_forward_tokens: out_dim must be a multiple of 64, at most 1024 "
+                    "(out_dim=%d)", out_dim);
+    MMRAG_CHECK_ARG(proj != nullptr || out_dim == dc.hidden, "encoder_forward_tokens: without a projection out_dim must "
+                    "equal hidden (out_dim=%d hidden=%d)", out_dim, dc.hidden);
+    MMRAG_CHECK_ARG(((uintptr_t)proj % 16) == 0 && ((uintptr_t)out_tokens % 16) == 0,
+                    "encoder_forward_tokens: proj and out_tokens must be 16-byte aligned");
+    const size_t body = mmrag_encoder_workspace_bytes(&dc, T, B), need = body + align256((size_t)T * (size_t)out_dim * 2);
+    if (!workspace || workspace_bytes < need) {
+        set_error("encoder_forward_tokens: workspace %zu bytes < required %zu", workspace_bytes, need);
+        return MMRAG_EWORKSPACE;
+    }
+    EncBuffers b;
+    RUN(carve(&dc, T, B, workspace, body, &b));
+    TokenTail tk;
+    tk.proj = proj;
+    tk.out_dim = out_dim;
+    // the tail: carve() aligned the workspace start up to 256 bytes inside its own 256-byte slack
+    tk.projected = (char *)(((uintptr_t)workspace + 255) / 256 * 256) + (body - 256);
+    tk.out = out_tokens;
+    RUN(mmrag_embed_ln_f16(ids, pos_ids, w[0], w[1], w[2], (const float *)w[3], (const float *)w[4], b.x, T,
+                           dc.hidden, dc.vocab, dc.max_pos, dc.ln_eps, stream));
+    return encoder_body(&dc, w + 5, b, cu_seqlens, nullptr, T, B, max_len, nullptr, stream, &tk);
 }
 
 int mmrag_vit_forward(const mmrag_encoder_desc *d, const void *const *w, const void *pixels, int pixel_kind,

@@ -90,6 +90,7 @@ class EmbeddingManager:
         self._sleep = asyncio.sleep              # (tests swap the back-off sleep out)
         self._reranker = None                    # cross-encoder (MMRAG_RERANKER_DIR), loaded on first use
         self._reranker_lock = threading.Lock()
+        self._late = None                        # late.LateInteractionScorer over the engine's own encoder, on first use
 
     # ------------------------------------------------------------------ lifecycle -----------
     async def initialize(self):
@@ -743,12 +744,88 @@ class EmbeddingManager:
                 self._reranker = DeviceCrossEncoder.from_local_dir(settings.MMRAG_RERANKER_DIR, device)
             return self._reranker
 
+    # ---- late interaction: re-ranking with the bi-encoder alone (late.py, csrc/maxsim.hip) ----
+    def has_late_reranker(self) -> bool:
+        """True when late_rerank can run: ONE BERT-family HIP engine in fp16 mode with a tokenizer (not the CLIP
+        towers, not the fp32 encoder mode, not a sharded engine)"""
+        enc = getattr(self._engine, "encoder", None)
+        return (enc is not None and hasattr(enc, "encode_tokens") and getattr(enc, "precision", None) == "fp16"
+                and getattr(self._engine, "tokenizer", None) is not None)
+
+    def _get_late(self):
+        with self._reranker_lock:
+            if self._late is None:
+                if not self.has_late_reranker():
+                    raise ValueError("late-interaction re-ranking needs a single BERT-family fp16 HIP engine with a "
+                                     "tokenizer")
+                from .late import LateInteractionScorer
+
+                self._late = LateInteractionScorer(self._engine.encoder, self._engine.tokenizer)
+            return self._late
+
+    def _late_rerank_sync(self, queries: List[str], results_list: List[Dict[str, Any]], top_k: Optional[int],
+                          explain: bool) -> List[Dict[str, Any]]:
+        scorer = self._get_late()
+        docs: List[str] = []
+        pairs: List[Tuple[int, int]] = []
+        for at, results in enumerate(results_list):
+            for d in results["documents"]:
+                pairs.append((at, len(docs)))
+                docs.append(d if d is not None else "")
+        scores: Any = []
+        records: List[Any] = []
+        if pairs:
+            if explain:
+                scores, records = scorer.explain_pairs(list(queries), docs, pairs)
+            else:
+                scores = scorer.score_pairs(list(queries), docs, pairs)
+        out, lo = [], 0
+        for results in results_list:
+            n = len(results["documents"])
+            mine = [float(x) for x in scores[lo: lo + n]]
+            order = sorted(range(n), key=lambda i: -mine[i])
+            if top_k:
+                order = order[:top_k]
+            hit = {key: [results[key][i] for i in order] for key in RESULT_KEYS}
+            hit["rerank_scores"] = [mine[i] for i in order]
+            if explain:
+                hit["late_matches"] = [records[lo + i] for i in order]
+            out.append(hit)
+            lo += n
+        return out
+
+    async def late_rerank(self, query_text: str, results: Dict[str, Any], top_k: Optional[int] = None,
+                          explain: bool = False) -> Dict[str, Any]:
+        """Re-rank `results` (any retrieval mode's answer: only its `documents` are read) by late interaction with the
+        bi-encoder itself: every (query_text, document) pair scores the mean over the query's tokens of each token's
+        best cosine against the document's tokens.  Output as the cross-encoder path's: reordered by descending score
+        (stable), truncated to top_k, with `rerank_scores`; `explain` adds `late_matches`, per hit one dict per query
+        token (query_token, doc_token, doc_index, similarity).  One encoder forward and one MaxSim launch."""
+        await self._ready()
+        return (await asyncio.to_thread(self._late_rerank_sync, [query_text], [results], top_k, explain))[0]
+
+    async def batch_late_rerank(self, queries: List[str], results_list: List[Dict[str, Any]],
+                                top_k: Optional[int] = None) -> List[Dict[str, Any]]:
+        """late_rerank of results_list[i] against queries[i], ONE scoring call (one forward, one launch) for all"""
+        if len(queries) != len(results_list):
+            raise ValueError(f"{len(results_list)} result dicts for {len(queries)} queries")
+        await self._ready()
+        return await asyncio.to_thread(self._late_rerank_sync, list(queries), list(results_list), top_k, False)
+
     async def rerank_results(self, query_text: str, results: Dict[str, Any],
-                             top_k: Optional[int] = None) -> Dict[str, Any]:
-        """embedder.py:834-859.  Without a cross-encoder (MMRAG_RERANKER_DIR empty): the reference's placeholder -- no
+                             top_k: Optional[int] = None, method: Optional[str] = None,
+                             explain: bool = False) -> Dict[str, Any]:
+        """embedder.py:834-859.  `method`: "cross" or "late" (default MMRAG_RERANK_METHOD, whose default is "cross").
+        "late": late_rerank (the bi-encoder's token rows; `explain` adds `late_matches`).  "cross", without a
+        cross-encoder (MMRAG_RERANKER_DIR empty): the reference's placeholder -- no
         re-ranking, only truncation to top_k.  With one: every (query_text, document) pair is scored (a None document
         as ""), the results are reordered by descending score (stable: ties keep the search order), truncated to top_k
         and carry their scores in `rerank_scores` (a multi-label model's first logit column is the score)."""
+        method = method or settings.rerank_method()
+        if method not in ("cross", "late"):
+            raise ValueError(f"rerank method must be 'cross' or 'late', not {method!r}")
+        if method == "late":
+            return await self.late_rerank(query_text, results, top_k=top_k, explain=explain)
         if not self.has_reranker():
             logger.warning("Re-ranking not implemented yet")
             if top_k and top_k < len(results["ids"]):

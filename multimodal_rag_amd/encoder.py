@@ -237,15 +237,21 @@ class DeviceEncoder:
             raise ValueError("empty token sequence")
         if lens.size == 1 and lens[0] <= self.GRAPH_MAX_TOKENS and self._use_graphs:
             return self.encode_one(ids2d[0, : int(lens[0])])
+        ids, pos, cu = self._pack_rows(ids2d, lens)
+        with stage("encode.upload"):
+            dev = self._upload(ids, pos, cu)
+        return self.forward_packed(*dev, int(lens.max()))
+
+    @staticmethod
+    def _pack_rows(ids2d: np.ndarray, lens: np.ndarray):
+        """rows of `ids2d` [B, W] cut to lens[i] ids -> packed (ids [T], pos_ids [T], cu_seqlens [B + 1]), numpy only"""
         W = ids2d.shape[1]
         keep = np.arange(W, dtype=np.int32)[None, :] < lens[:, None]
         ids = np.ascontiguousarray(ids2d[keep], dtype=np.int32)
         pos = np.broadcast_to(np.arange(W, dtype=np.int32)[None, :], ids2d.shape)[keep]
         cu = np.zeros(len(lens) + 1, dtype=np.int32)
         np.cumsum(lens, out=cu[1:])
-        with stage("encode.upload"):
-            dev = self._upload(ids, pos, cu)
-        return self.forward_packed(*dev, int(lens.max()))
+        return ids, pos, cu
 
     # ---- one sequence of at most 64 tokens (the online /query shape): the forward is a chain of ~33 kernels of 3-5 us and
     # the HOST's launch calls (4 us each) are what paces it.  The chain is captured once per token count into a HIP graph;
@@ -311,6 +317,34 @@ class DeviceEncoder:
                                                workspace=self._workspace, out=out, f32=self._f32)
         finally:
             self._launch_lock.release()
+
+    def encode_tokens(self, ids2d: np.ndarray, lens: np.ndarray, proj: Optional[torch.Tensor] = None):
+        """Token-level output for late interaction (mmrag_encoder_forward_tokens): row i of `ids2d` [B, W] int32 holds
+        lens[i] token ids (truncated to the encoder's length, as encode_id_rows does).  Returns (tokens, cu): `tokens`
+        [T, ld] float16 on the device, row cu[b] + t the L2-normalised last hidden state of token t of sequence b
+        (through `proj` [out_dim, hidden] fp16 when given; ld = out_dim, a multiple of 64), and `cu` [B + 1] the host
+        int32 row offsets.  One forward over all sequences; the pooled path's workspace is shared.  fp16 mode only."""
+        if self._f32:
+            raise RuntimeError("encode_tokens needs the fp16 encoder (MMRAG_ENCODER_PRECISION=fp16): the fp32 mode has "
+                               "no token-level output")
+        L = min(self.cfg.max_seq_length, self.cfg.max_pos)
+        ids2d = np.asarray(ids2d)
+        lens = np.minimum(np.asarray(lens, dtype=np.int32), L)
+        if lens.size == 0 or lens.min() <= 0:
+            raise ValueError("empty token sequence")
+        ids, pos, cu = self._pack_rows(ids2d, lens)
+        if proj is not None:
+            proj = proj.to(device=self.device, dtype=torch.float16).contiguous()
+        d_ids, d_pos, d_cu = self._upload(ids, pos, cu)
+        T, B = int(ids.size), len(lens)
+        out_dim = self.cfg.hidden if proj is None else int(proj.shape[0])
+        need = _native.encoder_tokens_workspace_bytes(self.desc, T, B, out_dim)
+        with self._launch_lock:
+            if self._workspace is None or self._workspace.numel() < need:
+                self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            tokens = _native.encoder_forward_tokens(self.desc, self._ptrs, d_ids, d_pos, d_cu, int(lens.max()),
+                                                    proj=proj, workspace=self._workspace)
+        return tokens, cu
 
     @property
     def dim(self) -> int:

@@ -38,6 +38,12 @@ class QueryRequest(BaseModel):  # api.py:161-164
     # not in the reference: re-score max(top_k, MMRAG_RERANK_CANDIDATES) hits with the cross-encoder of
     # MMRAG_RERANKER_DIR and answer from the best top_k (each source then carries its `rerank_score`)
     rerank: bool = Field(False)
+    # with `rerank`: which re-ranker (default MMRAG_RERANK_METHOD).  "cross" is the cross-encoder above; "late" is late
+    # interaction with the bi-encoder itself (EmbeddingManager.late_rerank: token-level MaxSim), which needs no second
+    # model.  `explain` (late only): each source also carries `matches`, one entry per query token -- the passage token
+    # it matched, that token's position and the cosine
+    rerank_method: Optional[Literal["cross", "late"]] = None
+    explain: bool = Field(False)
     # not in the reference: candidates from dense + BM25 retrieval fused by reciprocal rank (EmbeddingManager
     # .hybrid_query); each source then carries its `hybrid_score`.  With `rerank`, max(top_k, MMRAG_RERANK_CANDIDATES)
     # hybrid hits are re-ranked
@@ -97,6 +103,12 @@ MODE_NEEDS = (
 MULTI_NEEDS = ("multi_query", "supports_multi_query",
                "Multi-query retrieval is not available with this embedder: it needs a single-GPU collection "
                "(EmbeddingManager.multi_query)")
+
+
+# `rerank` with the method "late": the same
+LATE_NEEDS = ("late_rerank", "has_late_reranker",
+              "Late-interaction re-ranking is not available with this embedder: it needs a single BERT-family HIP "
+              "engine in fp16 mode with a tokenizer (EmbeddingManager.late_rerank)")
 
 
 # /duplicates: what it needs of the embedder and the 400 detail when that is missing (worded like MODE_NEEDS)
@@ -245,9 +257,11 @@ class Pipeline:
                      hybrid: bool = False, mmr: bool = False, mmr_lambda: Optional[float] = None,
                      group_by_document: bool = False, per_document: int = 1,
                      variants: Optional[List[str]] = None, variant_weight: Optional[float] = None,
-                     fusion: Optional[str] = None, doc_ids: Optional[List[str]] = None) -> Optional[dict]:
+                     fusion: Optional[str] = None, doc_ids: Optional[List[str]] = None,
+                     rerank_method: Optional[str] = None, explain: bool = False) -> Optional[dict]:
         """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
-        max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the cross-encoder's best top_k.  `hybrid`: the hits come from
+        max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the re-ranker's best top_k (`rerank_method` "cross" or "late",
+        default MMRAG_RERANK_METHOD; `explain`: late interaction's per-token matches on every source).  `hybrid`: from
         dense + BM25 retrieval fused by reciprocal rank.  `mmr`: the hits are a maximal-marginal-relevance selection of
         the dense candidates (`mmr_lambda`, default MMRAG_MMR_LAMBDA).  `group_by_document` (alone): the hits are the
         `per_document` best of each of the top_k best documents, flattened in document order.  `variants` (a list,
@@ -282,7 +296,10 @@ class Pipeline:
             hits = await search(question, n_results=max(top_k, settings.MMRAG_RERANK_CANDIDATES))
             if hits["ids"]:
                 carried = {column: dict(zip(hits["ids"], hits[column])) for column in extra}
-                hits = await self.embedder.rerank_results(question, hits, top_k=top_k)
+                # (the method is passed on only when one was chosen: an embedder without late interaction keeps its
+                # two-argument rerank_results)
+                chosen = {} if rerank_method is None and not explain else {"method": rerank_method, "explain": explain}
+                hits = await self.embedder.rerank_results(question, hits, top_k=top_k, **chosen)
                 for column, of_id in carried.items():
                     hits[column] = [of_id[found] for found in hits["ids"]]
         else:
@@ -309,6 +326,9 @@ class Pipeline:
             if on:
                 for src, score in zip(ranked, hits[column]):
                     src[key] = score
+        if rerank and "late_matches" in hits:
+            for src, found in zip(ranked, hits["late_matches"]):
+                src["matches"] = found
         if group_by_document:
             at = 0
             for document_rank, group in enumerate(hits["groups"], 1):
@@ -413,7 +433,21 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="Grouping by document is not combined with MMR, hybrid retrieval or re-ranking "
                                        "yet: send `group_by_document` without `mmr`, `hybrid` and `rerank`")
-        if request.rerank and not (hasattr(pipe.embedder, "has_reranker") and pipe.embedder.has_reranker()):
+        if (request.rerank_method is not None or request.explain) and not request.rerank:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                detail="`rerank_method` and `explain` belong to re-ranking: send them with `rerank`")
+        try:
+            late = request.rerank and (request.rerank_method or settings.rerank_method()) == "late"
+        except ValueError as e:      # a setting changed to neither method after start-up
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
+        if request.explain and not late:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                detail="`explain` needs late-interaction re-ranking: send `rerank_method`: \"late\"")
+        if late:
+            method, supports, detail = LATE_NEEDS
+            if not (hasattr(pipe.embedder, method) and getattr(pipe.embedder, supports, lambda: False)()):
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=detail)
+        elif request.rerank and not (hasattr(pipe.embedder, "has_reranker") and pipe.embedder.has_reranker()):
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="Re-ranking is not configured: set MMRAG_RERANKER_DIR to a local cross-encoder")
         if request.mmr and request.hybrid:
@@ -445,7 +479,8 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
                                 hybrid=request.hybrid, mmr=request.mmr, mmr_lambda=request.mmr_lambda,
                                 group_by_document=request.group_by_document, per_document=request.per_document,
                                 variants=variants, variant_weight=request.variant_weight, fusion=request.fusion,
-                                doc_ids=request.doc_ids)
+                                doc_ids=request.doc_ids,
+                                rerank_method="late" if late else request.rerank_method, explain=request.explain)
         if out is None:
             out = {"answer": NO_DOCS_ANSWER, "sources": []}
         return {**out, "processing_time": time.time() - t0}

@@ -173,6 +173,7 @@ class NativeWordPieceTokenizer:
         self._h = self._lib.mmrag_wordpiece_create(cps.ctypes.data, offs.ctypes.data, n, int(lower))
         if not self._h:
             raise RuntimeError(self._lib.mmrag_last_error().decode())
+        self.vocab = vocab                   # (late.py names matched tokens with it)
         self.vocab_size = n
         self.cls = vocab.get("[CLS]", CLS)
         self.sep = vocab.get("[SEP]", SEP)
