@@ -575,6 +575,43 @@ int mmrag_scoped_topk(const void *q, const void *rows, int B, int64_t n, int d, 
                       int64_t max_candidates, float *out_scores, int64_t *out_rows, void *workspace,
                       size_t workspace_bytes, void *stream);
 
+/* Boosted top-k (csrc/boosted.hip): a batch of queries ranked by cosine plus a per-row score prior, applied inside ONE
+ * exact scan.  VectorIndex.boosted_search.
+ *
+ * final[b][r] = fmaf(weight[b], prior[r], dot[b][r]).  Row r is a candidate iff r < n and its alive bit is set (when
+ * alive_bits is given).
+ * Contract
+ *   - one rounding: dot is the float32 accumulation of the pair-tile body's fixed K order, so a dot's bits depend on the
+ *     query row, the stored row and d alone and equal mmrag_scoped_topk's for the same two rows; final's bits depend on
+ *     those plus weight[b] and prior[r]: not on the batch, the grid, the threshold or whether bound passes ran;
+ *   - out_scores / out_rows [B, k] as mmrag_cosine_topk_deep's: final descending, ties to the lower row,
+ *     row + row_offset, (-inf, -1) padded;
+ *   - out_boost [B, k], optional (NULL allowed): weight[b] * prior[row], the exact float32 product, 0.0 in padding;
+ *   - with weight[b] == 0 a query's result is the plain exact top-k with this body's dot bits;
+ *   - exact under ANY finite prior: when n exceeds the candidate slots of a query (32 k, at least 16384) a sampled
+ *     lower bound on the k-th final is staged first (the k-th best of any subset of live rows is at most the true k-th),
+ *     and only finals at or above it are kept;
+ *   - at most one stream synchronisation per call, and only when n exceeds the candidate slots: the counts are read
+ *     once and a query with more survivors than slots is produced again alone.
+ *
+ *   q, rows         as mmrag_scoped_topk's: dev [B, ld] and [n, ld] of one `dtype` MMRAG_F32 / F16 / BF16 and one ld of
+ *                   whole 128-byte slabs, pad columns zero; MMRAG_F8E4M3 returns MMRAG_EUNSUPPORTED (an FP8 collection is
+ *                   searched with a prior on its re-scoring plane)
+ *   k               1..MMRAG_MAX_K_DEEP
+ *   alive_bits      dev, optional (NULL = every row): bit r & 31 of word r >> 5
+ *   prior           dev [n] float32, finite
+ *   weight          dev [B] float32, finite
+ *   workspace       dev, >= mmrag_boosted_topk_workspace_bytes(B, n, k) bytes (0 for arguments out of range), 16-byte
+ *                   aligned; short or misaligned: MMRAG_EWORKSPACE
+ * MMRAG_EINVAL before anything is launched: a null pointer (the optional ones aside), B < 1, n < 0 or >= 2^31, k out of
+ * range, d <= 0, ld < d or not whole slabs.  prior and weight live on the device and are not read by the host (the
+ * Python wrapper checks the host copies it uploads); a non-finite value gives an unspecified ranking. */
+size_t mmrag_boosted_topk_workspace_bytes(int B, int64_t n, int k);
+int mmrag_boosted_topk(const void *q, const void *rows, int B, int64_t n, int d, int64_t ld, int dtype, int k,
+                       int64_t row_offset, const uint32_t *alive_bits, const float *prior, const float *weight,
+                       float *out_scores, int64_t *out_rows, float *out_boost, void *workspace, size_t workspace_bytes,
+                       void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Late-interaction re-ranking (ColBERT's MaxSim) with the bi-encoder alone.  The reference has no counterpart: its
  * EmbeddingManager.rerank_results is a placeholder (app/utils/embedder.py:834-859).  The encoder's per-token outputs are

@@ -230,6 +230,16 @@ def _declare(lib):
     lib.mmrag_internal_scoped_topk_ex.argtypes = lib.mmrag_scoped_topk.argtypes + [c_int64]
     lib.mmrag_internal_candidate_capacity.restype = c_int64
     lib.mmrag_internal_candidate_capacity.argtypes = [c_int]
+    # boosted top-k (csrc/boosted.hip); the _ex entry adds a candidate capacity and debug switches (tests, not in
+    # include/mmrag.h)
+    lib.mmrag_boosted_topk_workspace_bytes.restype = c_size_t
+    lib.mmrag_boosted_topk_workspace_bytes.argtypes = [c_int, c_int64, c_int]
+    lib.mmrag_boosted_topk.restype = c_int
+    lib.mmrag_boosted_topk.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int64, c_int, c_int, c_int64,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                       c_void_p]
+    lib.mmrag_internal_boosted_topk_ex.restype = c_int
+    lib.mmrag_internal_boosted_topk_ex.argtypes = lib.mmrag_boosted_topk.argtypes + [c_int64, ctypes.c_uint]
     # late interaction (csrc/encoder.hip token rows, csrc/maxsim.hip)
     lib.mmrag_encoder_tokens_workspace_bytes.restype = c_size_t
     lib.mmrag_encoder_tokens_workspace_bytes.argtypes = [c_void_p, c_int64, c_int, c_int]
@@ -721,6 +731,69 @@ def scoped_topk(q: torch.Tensor, rows: torch.Tensor, n: int, d: int, k: int, gro
             workspace.data_ptr(), _nbytes(workspace), _stream_ptr(dev), int(cap))
     _check(st, "mmrag_scoped_topk")
     return out_s, out_r
+
+
+def boosted_topk_workspace_bytes(B: int, n: int, k: int) -> int:
+    return int(lib().mmrag_boosted_topk_workspace_bytes(int(B), int(n), int(k)))
+
+
+def _boost_operand(who: str, what: str, t, count: int, exact: bool, device) -> torch.Tensor:
+    """`what` (prior / weight) of boosted_topk on `device`: a HOST array is checked (float32-representable finite
+    values, `count` entries; at least `count` when not `exact`) and uploaded through pinned memory, a device float32
+    tensor is the caller's own (VectorIndex checked it when the column was built).  Raises ValueError."""
+    if isinstance(t, torch.Tensor) and t.is_cuda:
+        if (t.dim() != 1 or t.dtype != torch.float32 or not t.is_contiguous() or t.device != device
+                or (t.numel() != count if exact else t.numel() < count)):
+            raise ValueError(f"{who}: {what} must be a contiguous float32 tensor of {count} entries on the rows' device")
+        return t
+    host = torch.as_tensor(t, dtype=torch.float64).reshape(-1).to(torch.float32)
+    if host.numel() != count:
+        raise ValueError(f"{who}: {what} holds {host.numel()} entries, expected {count}")
+    if not bool(torch.isfinite(host).all()):
+        raise ValueError(f"{who}: {what} must be finite")
+    if host.numel() == 0:
+        host = torch.zeros(1, dtype=torch.float32)    # keeps the pointer real
+    return _pinned_to_device(host, device)
+
+
+def boosted_topk(q: torch.Tensor, rows: torch.Tensor, n: int, d: int, k: int, prior, weight,
+                 alive_bits: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                 row_offset: int = 0, cap: int = 0, dbg: int = 0,
+                 want_boost: bool = True) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """Top-k of each query of q [B, ld] over the first n of `rows` [cap, ld] by cosine plus a score prior
+    (include/mmrag.h mmrag_boosted_topk): final[b][r] = fmaf(weight[b], prior[r], <q_b, x_r>), applied inside one exact
+    scan.  `prior`: n float32 values, a host array (checked finite and uploaded) or a device tensor of at least n the
+    caller vouches for; `weight`: a number or one per query, likewise.  Returns (scores [B, k] float32 = final
+    descending, rows [B, k] int64 + row_offset, boosts [B, k] float32 = weight * prior of each hit or None), (-inf, -1,
+    0) padded.  No host synchronisation unless n exceeds the candidate slots of a query.  Raises ValueError for a
+    non-finite or wrong-length prior or weight and k outside 1..MAX_K_DEEP, before anything is launched.  `cap`, `dbg`
+    (tests only): fewer slots; dbg & 1 = no bound passes."""
+    _dev_check(q, rows, alive_bits)
+    _check_q_rows("boosted_topk", q, rows, n, other="rows")
+    _check_stored_rows("boosted_topk", rows)
+    B, ld = q.shape
+    n, k = int(n), int(k)
+    if not 1 <= k <= MAX_K_DEEP:
+        raise ValueError(f"boosted_topk: k={k} outside 1..{MAX_K_DEEP}")
+    _check_alive("boosted_topk", alive_bits, n, rows)
+    dev = q.device
+    if not isinstance(weight, torch.Tensor) and not hasattr(weight, "__len__"):
+        weight = [float(weight)] * B
+    prior_dev = _boost_operand("boosted_topk", "prior", prior, n, False, dev)
+    weight_dev = _boost_operand("boosted_topk", "weight", weight, B, True, dev)
+    need = boosted_topk_workspace_bytes(B, n, k)
+    if workspace is None or _nbytes(workspace) < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    out_s, out_r = _topk_out(B, k, dev)
+    out_b = torch.empty((B, k), dtype=torch.float32, device=dev) if want_boost else None
+    with torch.cuda.device(dev):
+        st = lib().mmrag_internal_boosted_topk_ex(
+            q.data_ptr(), rows.data_ptr(), B, n, int(d), ld, _TORCH2DT[q.dtype], k, int(row_offset),
+            alive_bits.data_ptr() if alive_bits is not None else None, prior_dev.data_ptr(), weight_dev.data_ptr(),
+            out_s.data_ptr(), out_r.data_ptr(), out_b.data_ptr() if out_b is not None else None,
+            workspace.data_ptr(), _nbytes(workspace), _stream_ptr(dev), int(cap), int(dbg))
+    _check(st, "mmrag_boosted_topk")
+    return out_s, out_r, out_b
 
 
 def check_late_tables(q_rows: int, d_rows: int, q_start, q_len, d_start, d_len, pair_q, pair_d) -> Tuple[int, int, int]:

@@ -108,6 +108,16 @@ class Settings:
     MMRAG_DEDUP_THRESHOLD: float = field(default_factory=lambda: float(os.getenv("MMRAG_DEDUP_THRESHOLD", "0")))
     MMRAG_DEDUP_REPORT_THRESHOLD: float = field(
         default_factory=lambda: float(os.getenv("MMRAG_DEDUP_REPORT_THRESHOLD", "0.98")))
+    # boosted retrieval (VectorIndex.boosted_query, csrc/boosted.hip): the defaults of a request's "boost" object.
+    # MMRAG_BOOST_RECENCY: the weight of the recency term (0 = none); a non-zero default applies only to a request that
+    # asks with "boost": true -- plain requests never change.  MMRAG_BOOST_HALF_LIFE_DAYS: the age at which the recency
+    # term has halved.  MMRAG_BOOST_REFRESH_S: a spec's prior column is rebuilt when the clock passes a multiple of this.
+    # MMRAG_BOOST_TIME_KEY: a key of an uploaded item that holds its UNIX time ("" = the time of the upload call)
+    MMRAG_BOOST_RECENCY: float = field(default_factory=lambda: float(os.getenv("MMRAG_BOOST_RECENCY", "0.0")))
+    MMRAG_BOOST_HALF_LIFE_DAYS: float = field(
+        default_factory=lambda: float(os.getenv("MMRAG_BOOST_HALF_LIFE_DAYS", "30")))
+    MMRAG_BOOST_REFRESH_S: float = field(default_factory=lambda: float(os.getenv("MMRAG_BOOST_REFRESH_S", "3600")))
+    MMRAG_BOOST_TIME_KEY: str = field(default_factory=lambda: os.getenv("MMRAG_BOOST_TIME_KEY", ""))
     # topic clustering (VectorIndex.cluster, csrc/kmeans.hip): the default number of topics of cluster() / GET /topics;
     # 0 (default) = automatic, auto_topics(live rows); else 1 .. 4096
     MMRAG_TOPICS: int = field(default_factory=lambda: int(os.getenv("MMRAG_TOPICS", "0")))

@@ -1,0 +1,366 @@
+// Boosted top-k (include/mmrag.h mmrag_boosted_topk): a batch of queries against the stored rows, ranked by
+// final[b][r] = fmaf(weight[b], prior[r], <q_b, x_r>) -- a per-row score prior applied INSIDE one exact scan.  A row
+// with a large prior and a middling cosine belongs in the answer but is in no cosine top-k, so the prior cannot be
+// applied to a finished list.
+//
+//   1. bound passes, only when n exceeds the candidate capacity: the scan kernel below over a sample of whole 128-row
+//      tiles spread evenly over the collection (rows are in ingest order and a recency prior rises with the row number:
+//      a prefix would be biased), every live final >= tau_q appended; deep_select_kernel in its bound mode then sets
+//      tau_q = max(tau_q, the k-th best of those).  The k-th best of ANY subset of live rows is at most the true k-th
+//      final, whatever the prior looks like, so tau_q stays a valid lower bound (-inf while fewer than k rows were seen).
+//      The stages grow as search_deep.hip's do.
+//   2. main pass: every tile, every live final >= tau_q appended as (final, local row) through the query's counter.
+//   3. select and overflow: candidate_select.h's driver, unchanged; an overflowed query is produced again alone with the
+//      same tau_q into n slots.
+//
+// scan kernel: scoped.hip's scan without the scope test.  Q . X^T with pair_tile.h's body, a 128-row tile of stored rows
+// as A and a 128-query tile as B; rows past n and queries past B read as zero through the buffer descriptor.  Workgroups
+// are persistent over row tiles.  Every wave reads the tile's 128 priors and alive bits once (two rows per lane, plain
+// vector loads); a tile with no live row is skipped without a fetch.  The ring runs over the K-slabs of all the query
+// tiles without draining between them.  After a query tile's last slab a lane takes its 16 rows' priors by __shfl, reads
+// weight and tau of its 4 query columns, forms final with one fmaf and appends the finals that reach tau.  The K order is
+// slab_step's, so a dot's bits depend on the query row, the stored row and d alone (and equal mmrag_scoped_topk's), and
+// final's on those plus weight[b] and prior[r]: not on the batch, the grid, tau or whether bound passes ran.
+#include "candidate_select.h"
+#include "pair_tile.h"
+
+using namespace mmrag;
+
+namespace mmrag_impl {
+
+namespace {
+
+constexpr int BO_MAX_QT = 64;            // query tiles of one scan launch, as scoped.hip cuts its batches
+constexpr int BO_SAMPLE0_TILES = 96;     // first bound sample: 12288 rows, the select's LDS key cache
+constexpr int BO_MAX_STAGES = 8;
+
+// debug switches of mmrag_internal_boosted_topk_ex (tests only)
+constexpr unsigned BO_DBG_NO_BOUND = 1u;  // no bound passes: tau = -inf, every live row survives the main pass
+
+struct BoostedParams {
+    const char *rows;
+    const char *q;
+    long long n;
+    int B;
+    unsigned row_bytes;     // ld * element size, of the rows and of the queries
+    int nk;                 // K-slabs that hold the d logical columns
+    int nqt;                // query tiles, <= BO_MAX_QT
+    const unsigned *alive;
+    const float *prior;     // [n]
+    const float *weight;    // [B]
+    const float *tau;       // [B], or null: -inf
+    float *cand_s;
+    int *cand_r;
+    unsigned *cnt;
+    unsigned cap;
+    long long T;            // row tiles of the collection
+    long long walk;         // tiles this launch visits: tile i * T / walk for i in 0 .. walk (walk == T: every tile)
+};
+
+struct BoostedPlan {
+    long long cap;          // candidate slots per query
+    int n_stages;
+    long long stage_tiles[BO_MAX_STAGES];
+};
+
+// search_deep.hip's make_deep_plan in 128-row tiles.  The stages are planned against the capacity of k itself: a
+// smaller cap_override (tests) only makes the slots fewer, so that queries overflow.
+BoostedPlan make_boosted_plan(long long n, int k, long long cap_override, unsigned dbg) {
+    BoostedPlan pl;
+    const long long C = candidate_capacity(k);
+    pl.cap = cap_override > 0 && cap_override < C ? cap_override : C;
+    pl.n_stages = 0;
+    if (n <= C || (dbg & BO_DBG_NO_BOUND)) return pl;   // every live row fits: no bound needed
+    const long long n_tiles = (n + PT - 1) / PT;
+    // main-pass survivors ~ k * n / m for a bound from m sampled rows: aim at C / 4
+    const long long target_rows = (4LL * k * n + C - 1) / C;
+    const long long target = (target_rows + PT - 1) / PT;
+    long long t = BO_SAMPLE0_TILES < n_tiles ? BO_SAMPLE0_TILES : n_tiles;
+    for (;;) {
+        pl.stage_tiles[pl.n_stages++] = t;
+        if (t >= target || pl.n_stages == BO_MAX_STAGES) break;
+        // the next sample's survivors ~ k * m' / m must fit C / 4 as well
+        long long nt = t * C / (4LL * k);
+        if (nt > target) nt = target;
+        if (nt > n_tiles) nt = n_tiles;
+        if (nt <= t) break;
+        t = nt;
+    }
+    return pl;
+}
+
+template <int DT>
+__global__ __launch_bounds__(256, 2) void boosted_scan_kernel(const BoostedParams p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ __attribute__((aligned(1024))) char smem[PT_LDS];
+
+    const unsigned RB = p.row_bytes;
+    const PairTileCtx c = pair_tile_ctx(threadIdx.x, RB, smem);
+    const int lane = c.lane, wave = c.wave, wm = c.wm, wn = c.wn, c16 = c.c16, g4 = c.g4;
+    const int nk = p.nk, nqt = p.nqt;
+    const int total = nk * nqt;
+
+    for (long long i = blockIdx.x; i < p.walk; i += gridDim.x) {
+        const long long tile = i * p.T / p.walk;      // < T
+        const long long row0 = tile * PT;
+        const long long left = p.n - row0;            // >= 1
+        const int in_tile = left < PT ? (int)left : PT;
+
+        // priors of rows `lane` and `lane + 64` of the tile, and whether they are candidates (below n, alive)
+        float pr[2];
+        bool live[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const long long r = row0 + lane + 64 * h;
+            pr[h] = 0.0f;
+            live[h] = false;
+            if (r < p.n) {
+                pr[h] = p.prior[r];
+                live[h] = p.alive == nullptr || ((p.alive[r >> 5] >> (r & 31)) & 1u) != 0u;
+            }
+        }
+        // bit i of m0 = row i is live, of m1 = row 64 + i: the same two scalars in all four waves
+        const unsigned long long m0 = __builtin_amdgcn_ballot_w64(live[0]);
+        const unsigned long long m1 = __builtin_amdgcn_ballot_w64(live[1]);
+        // uniform: the whole workgroup takes this path; nothing was fetched, no LDS is touched
+        if ((m0 | m1) == 0ull) continue;
+
+        const char *const rows_base = p.rows + (size_t)row0 * RB;
+        const unsigned rows_bytes = (unsigned)in_tile * RB;
+        int issued = 0, i_ks = 0, i_qt = 0;
+        auto issue = [&]() {
+            // ring item `issued` = K-slab i_ks of (this row tile, query tile i_qt)
+            const int q_left = p.B - i_qt * PT;
+            const char *base = wave < 2 ? rows_base : p.q + (size_t)i_qt * PT * RB;
+            const unsigned bytes = wave < 2 ? rows_bytes : (unsigned)(q_left < PT ? q_left : PT) * RB;
+            pair_tile_issue(c, make_rsrc(base, bytes), issued % PT_NSTAGE, i_ks);
+            ++issued;
+            if (++i_ks == nk) {
+                i_ks = 0;
+                ++i_qt;
+            }
+        };
+
+        const unsigned long long mw = wm ? m1 : m0;      // this wave's 64 rows
+        const float pw = wm ? pr[1] : pr[0];
+        f32x4_t acc[4][4];
+        pair_tile_clear(acc);
+        issue();
+        int ks = 0, qt = 0;
+        for (int it = 0; it < total; ++it) {
+            wait_vmcnt<0>();     // two stages: item `it` is the only one in flight
+            __builtin_amdgcn_s_barrier();
+            if (issued < total) issue();
+            slab_step<DT>(smem + (it % PT_NSTAGE) * PT_STAGE, c, acc);
+            if (++ks < nk) continue;
+            // ---- the query tile is complete: acc[a][b][r] = <row wm*64 + 16a + 4 g4 + r, query col0 + 16b>
+            ks = 0;
+            if (mw != 0ull) {
+                // this lane's 16 rows: bit 4a + r of `vis` = row 16a + 4 g4 + r of the wave's 64 is live
+                float my_p[16];
+                unsigned vis = 0;
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int src = 16 * a + 4 * g4 + r;
+                        my_p[4 * a + r] = __shfl(pw, src);
+                        vis |= (unsigned)((mw >> src) & 1ull) << (4 * a + r);
+                    }
+                const int lrow0 = (int)row0 + wm * 64 + 4 * g4;      // n < 2^31 (the entry point's check)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const int col = qt * PT + wn * 64 + 16 * b + c16;
+                    if (col >= p.B || vis == 0u) continue;
+                    const float w = p.weight[col];
+                    const float t = p.tau != nullptr ? p.tau[col] : NEG_INF;
+                    float fin[16];
+                    unsigned hit = 0;
+#pragma unroll
+                    for (int a = 0; a < 4; ++a)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float f = __builtin_fmaf(w, my_p[4 * a + r], acc[a][b][r]);   // one rounding
+                            fin[4 * a + r] = f;
+                            hit |= (unsigned)(f >= t) << (4 * a + r);
+                        }
+                    hit &= vis;
+                    if (hit == 0u) continue;
+                    // reserve the slots with one returning atomic; the counter keeps the true count, slots at or past
+                    // cap are not written
+                    unsigned at = atomicAdd(p.cnt + col, (unsigned)__popc(hit));
+                    float *bs = p.cand_s + (size_t)col * p.cap;
+                    int *br = p.cand_r + (size_t)col * p.cap;
+#pragma unroll
+                    for (int j = 0; j < 16; ++j)
+                        if ((hit >> j) & 1u) {
+                            if (at < p.cap) {
+                                bs[at] = fin[j];
+                                br[at] = lrow0 + 16 * (j >> 2) + (j & 3);
+                            }
+                            ++at;
+                        }
+                }
+            }
+            ++qt;
+            pair_tile_clear(acc);
+        }
+        __syncthreads();   // every wave is done with the ring before the next tile's first slab lands
+    }
+#endif
+}
+
+// out_boost[i] = weight[b] * prior[row] of winner i = (b, slot), 0 in padding: the exact float32 product
+__global__ __launch_bounds__(256) void boosted_finish_kernel(const long long *__restrict__ out_r,
+                                                            const float *__restrict__ prior,
+                                                            const float *__restrict__ weight, long long row_offset,
+                                                            long long n, int k, long long total,
+                                                            float *__restrict__ out_boost) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long long r = out_r[i];
+    float v = 0.0f;
+    if (r >= 0) {
+        const long long local = r - row_offset;
+        if (local >= 0 && local < n) v = __fmul_rn(weight[i / k], prior[local]);
+    }
+    out_boost[i] = v;
+}
+
+template <int DT>
+int launch_scan(const BoostedParams &p, hipStream_t s) {
+    long long g = 2LL * num_cus();    // persistent grid: two workgroups per CU (the LDS allows two)
+    if (g > p.walk) g = p.walk;
+    hipLaunchKernelGGL(boosted_scan_kernel<DT>, dim3((unsigned)g), dim3(256), 0, s, p);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    return MMRAG_OK;
+}
+
+}  // namespace
+
+}  // namespace mmrag_impl
+using namespace mmrag_impl;
+
+extern "C" {
+
+size_t mmrag_boosted_topk_workspace_bytes(int B, int64_t n, int k) {
+    if (B <= 0 || n < 0 || n >= (1LL << 31) || k < 1 || k > MMRAG_MAX_K_DEEP) return 0;
+    return candidate_ws_layout(B, candidate_capacity(k), n, true).total;
+}
+
+// mmrag_boosted_topk with a smaller candidate capacity (cap_override > 0) and debug switches (BO_DBG_*): the tests that
+// pin the overflow re-run and the unbounded scan.  Exported for them, deliberately absent from include/mmrag.h.
+int mmrag_internal_boosted_topk_ex(const void *q, const void *rows, int B, int64_t n, int d, int64_t ld, int dtype, int k,
+                                   int64_t row_offset, const uint32_t *alive_bits, const float *prior,
+                                   const float *weight, float *out_scores, int64_t *out_rows, float *out_boost,
+                                   void *workspace, size_t workspace_bytes, void *stream, int64_t cap_override,
+                                   unsigned dbg) {
+    MMRAG_CHECK_ARG(q && rows && weight, "boosted_topk: null pointer");
+    MMRAG_CHECK_ARG(out_scores && out_rows, "boosted_topk: null output");
+    if (int st = check_stored_rows("boosted_topk", "searched with a prior", "search", ld, dtype, d, &n)) return st;
+    MMRAG_CHECK_ARG(n < (1LL << 31), "boosted_topk: need n < 2^31 (n=%lld)", (long long)n);
+    MMRAG_CHECK_ARG(prior || n == 0, "boosted_topk: null prior");
+    MMRAG_CHECK_ARG(B >= 1, "boosted_topk: need B >= 1 (B=%d)", B);
+    MMRAG_CHECK_ARG(k >= 1 && k <= MMRAG_MAX_K_DEEP, "boosted_topk: k=%d outside 1..%d", k, MMRAG_MAX_K_DEEP);
+    hipStream_t s = (hipStream_t)stream;
+    const long long total_out = (long long)B * k;
+    if (n == 0) {
+        if (out_boost) MMRAG_CHECK_HIP(hipMemsetAsync(out_boost, 0, (size_t)total_out * sizeof(float), s));
+        return candidate_fill_empty(out_scores, (long long *)out_rows, B, k, s);
+    }
+
+    const BoostedPlan pl = make_boosted_plan(n, k, cap_override, dbg);
+    const CandWs wl = candidate_ws_layout(B, pl.cap, n, true);
+    if (!workspace || workspace_bytes < wl.total) {
+        set_error("boosted_topk: workspace %zu bytes < required %zu", workspace_bytes, wl.total);
+        return MMRAG_EWORKSPACE;
+    }
+    if (((uintptr_t)workspace % 16) != 0) {
+        set_error("boosted_topk: workspace must be 16-byte aligned");
+        return MMRAG_EWORKSPACE;
+    }
+
+    char *ws = (char *)workspace;
+    unsigned *cnt = (unsigned *)(ws + wl.off_cnt);
+    float *tau = (float *)(ws + wl.off_floats);
+    BoostedParams p;
+    p.rows = (const char *)rows;
+    p.q = (const char *)q;
+    p.n = n;
+    p.B = B;
+    p.row_bytes = stored_row_bytes(ld, dtype);
+    p.nk = stored_k_slabs(d, dtype);
+    p.nqt = 0;
+    p.alive = alive_bits;
+    p.prior = prior;
+    p.weight = weight;
+    p.tau = nullptr;
+    p.cand_s = (float *)(ws + wl.off_bs);
+    p.cand_r = (int *)(ws + wl.off_br);
+    p.cnt = cnt;
+    p.cap = (unsigned)pl.cap;
+    p.T = (n + PT - 1) / PT;
+    p.walk = p.T;
+
+    // queries q0 .. q0 + Bq of the caller's batch over `walk` tiles into their slots: scans of at most BO_MAX_QT query
+    // tiles each
+    const auto produce = [&](int q0, int Bq, long long walk, float *cand_s, int *cand_r, unsigned *counts,
+                             long long slots) -> int {
+        const int tiles = (Bq + PT - 1) / PT;
+        for (int t0 = 0; t0 < tiles; t0 += BO_MAX_QT) {
+            BoostedParams pc = p;
+            const int c0 = q0 + t0 * PT;
+            pc.q = p.q + (size_t)c0 * p.row_bytes;
+            pc.weight = weight + c0;
+            pc.tau = p.tau != nullptr ? p.tau + c0 : nullptr;
+            pc.B = Bq - t0 * PT < BO_MAX_QT * PT ? Bq - t0 * PT : BO_MAX_QT * PT;
+            pc.nqt = (pc.B + PT - 1) / PT;
+            pc.walk = walk;
+            pc.cap = (unsigned)slots;
+            pc.cand_s = cand_s + (size_t)(t0 * PT) * slots;
+            pc.cand_r = cand_r + (size_t)(t0 * PT) * slots;
+            pc.cnt = counts + t0 * PT;
+            if (int st = with_elem_type(dtype, [&](auto tag) { return launch_scan<decltype(tag)::value>(pc, s); }))
+                return st;
+        }
+        return MMRAG_OK;
+    };
+
+    // 1. bound passes (tau starts at -inf: the bit pattern 0xff800000)
+    if (pl.n_stages > 0) {
+        MMRAG_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)tau, (int)0xff800000u, (size_t)B, s));
+        p.tau = tau;
+    }
+    for (int st = 0; st < pl.n_stages; ++st) {
+        MMRAG_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)B * sizeof(unsigned), s));
+        if (int e = produce(0, B, pl.stage_tiles[st], p.cand_s, p.cand_r, cnt, pl.cap)) return e;
+        deep_select_kernel<<<B, SEL_THREADS, 0, s>>>(p.cand_s, p.cand_r, cnt, pl.cap, k, 0, 1, nullptr, nullptr, tau);
+        MMRAG_CHECK_HIP(hipGetLastError());
+    }
+    // 2. main pass over every tile, 3. select, 4. each query with more survivors than slots alone, same tau_q
+    if (int st = candidate_select(
+            "boosted_topk", B, n, pl.cap, k, row_offset, out_scores, (long long *)out_rows, ws, wl, s,
+            [&](float *cand_s, int *cand_r, unsigned *counts, long long slots) {
+                return produce(0, B, p.T, cand_s, cand_r, counts, slots);
+            },
+            [&](int qi, float *cand_s, int *cand_r, unsigned *counts, long long slots) {
+                return produce(qi, 1, p.T, cand_s, cand_r, counts, slots);
+            }))
+        return st;
+    if (out_boost) {
+        boosted_finish_kernel<<<(unsigned)((total_out + 255) / 256), 256, 0, s>>>(
+            (const long long *)out_rows, prior, weight, row_offset, n, k, total_out, out_boost);
+        MMRAG_CHECK_HIP(hipGetLastError());
+    }
+    return MMRAG_OK;
+}
+
+int mmrag_boosted_topk(const void *q, const void *rows, int B, int64_t n, int d, int64_t ld, int dtype, int k,
+                       int64_t row_offset, const uint32_t *alive_bits, const float *prior, const float *weight,
+                       float *out_scores, int64_t *out_rows, float *out_boost, void *workspace, size_t workspace_bytes,
+                       void *stream) {
+    return mmrag_internal_boosted_topk_ex(q, rows, B, n, d, ld, dtype, k, row_offset, alive_bits, prior, weight,
+                                          out_scores, out_rows, out_boost, workspace, workspace_bytes, stream, 0, 0u);
+}
+
+}  // extern "C"

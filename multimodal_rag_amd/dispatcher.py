@@ -15,20 +15,23 @@ from typing import Any, Awaitable, Callable, Dict, List, Optional, Tuple
 BatchFn = Callable[[List[str], int, Optional[Dict]], Awaitable[List[Dict[str, Any]]]]
 # (texts, k, each text's doc_ids): ONE batched encode and ONE scoped search whatever the scopes (csrc/scoped.hip)
 ScopedFn = Callable[[List[str], int, List[List[str]]], Awaitable[List[Dict[str, Any]]]]
+# (texts, k, filter, the batch's boost spec): ONE batched encode and ONE boosted search (csrc/boosted.hip)
+BoostedFn = Callable[[List[str], int, Optional[Dict], Any], Awaitable[List[Dict[str, Any]]]]
 
 
 class QueryDispatcher:
     def __init__(self, batch_fn: BatchFn, max_batch: int = 256, max_wait_ms: float = 2.0, idle_ms: float = 0.25,
-                 scoped_fn: Optional[ScopedFn] = None):
+                 scoped_fn: Optional[ScopedFn] = None, boosted_fn: Optional[BoostedFn] = None):
         self.batch_fn = batch_fn
         self.scoped_fn = scoped_fn
+        self.boosted_fn = boosted_fn
         self.max_batch = max_batch
         self.max_wait = max_wait_ms / 1e3
         # a batch also closes when nothing new has arrived for `idle_ms`: with a fixed set of callers that all come back
         # right after their answers, waiting out the whole window for requests that cannot exist is a quarter of the cycle
         self.idle = idle_ms / 1e3
-        # (text, k, filter, the caller's future, doc_ids)
-        self._queue: "asyncio.Queue[Tuple[str, int, Optional[Dict], asyncio.Future, Optional[List[str]]]]" = \
+        # (text, k, filter, the caller's future, doc_ids, boost spec)
+        self._queue: "asyncio.Queue[Tuple[str, int, Optional[Dict], asyncio.Future, Optional[List[str]], Any]]" = \
             asyncio.Queue()
         self._task: Optional[asyncio.Task] = None
         self.stats = {"requests": 0, "batches": 0, "max_batch_seen": 0}
@@ -47,16 +50,20 @@ class QueryDispatcher:
             self._task = None
 
     async def submit(self, text: str, n_results: int = 5, filter_dict: Optional[Dict] = None,
-                     doc_ids: Optional[List[str]] = None) -> Dict[str, Any]:
-        """`doc_ids`: answer from these documents only.  With a `scoped_fn`, requests that carry doc_ids and no
+                     doc_ids: Optional[List[str]] = None, boost: Any = None) -> Dict[str, Any]:
+        """`boost`: a boost spec (an object with a canonical `batch_key()`; needs a `boosted_fn`): the request is ranked with
+        that score prior, and requests of one k, filter and spec key share one batch.
+        `doc_ids`: answer from these documents only.  With a `scoped_fn`, requests that carry doc_ids and no
         filter_dict share one batch per k whatever their documents; without one (or next to a filter_dict) the
         restriction becomes part of the filter and the request is grouped by it like any other."""
+        if boost is not None and (self.boosted_fn is None or doc_ids is not None):
+            raise ValueError("a boosted request needs a boosted_fn and takes no doc_ids")
         self.start()
         if doc_ids is not None and (self.scoped_fn is None or filter_dict is not None):
             only = {"doc_id": {"$in": list(doc_ids)}}
             filter_dict, doc_ids = ({"$and": [filter_dict, only]} if filter_dict else only), None
         fut: asyncio.Future = asyncio.get_running_loop().create_future()
-        await self._queue.put((text, n_results, filter_dict, fut, doc_ids))
+        await self._queue.put((text, n_results, filter_dict, fut, doc_ids, boost))
         return await fut
 
     async def _run(self):
@@ -77,14 +84,23 @@ class QueryDispatcher:
                     batch.append(await asyncio.wait_for(self._queue.get(), timeout))
                 except asyncio.TimeoutError:
                     break
-            # one kernel batch per (k, filter) group; the requests with doc_ids are one group per k
+            # one kernel batch per (k, filter) group; the requests with doc_ids are one group per k, the boosted ones
+            # one per (k, filter, spec key)
             groups: Dict[Any, List[int]] = {}
-            for i, (_, k, flt, _, docs) in enumerate(batch):
-                groups.setdefault((k, repr(flt)) if docs is None else (k,), []).append(i)
+            for i, (_, k, flt, _, docs, boost) in enumerate(batch):
+                if boost is not None:
+                    key = ("boosted", k, repr(flt), boost.batch_key())
+                elif docs is not None:
+                    key = ("scoped", k)
+                else:
+                    key = ("plain", k, repr(flt))
+                groups.setdefault(key, []).append(i)
             for key, idxs in groups.items():
                 k, flt = batch[idxs[0]][1], batch[idxs[0]][2]
                 try:
-                    if len(key) == 1:
+                    if key[0] == "boosted":
+                        results = await self.boosted_fn([batch[i][0] for i in idxs], k, flt, batch[idxs[0]][5])
+                    elif key[0] == "scoped":
                         results = await self.scoped_fn([batch[i][0] for i in idxs], k, [batch[i][4] for i in idxs])
                     else:
                         results = await self.batch_fn([batch[i][0] for i in idxs], k, flt)

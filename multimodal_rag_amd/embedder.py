@@ -23,6 +23,7 @@ import asyncio
 import copy
 import hashlib
 import logging
+import math
 import threading
 import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
@@ -41,6 +42,7 @@ RESULT_KEYS = ("ids", "distances", "metadatas", "documents")
 HYBRID_KEYS = RESULT_KEYS + ("hybrid_scores", "lexical_scores")
 MMR_KEYS = RESULT_KEYS + ("mmr_scores",)
 FUSED_KEYS = RESULT_KEYS + ("fused_scores", "matched_queries", "best_query")
+BOOST_KEYS = RESULT_KEYS + ("scores", "boosts")
 _HOSTROWS = load_hostrows()
 _COLLECTION_NOTE = {"description": "Multi-modal RAG embeddings"}
 # what a retrieval mode needs of the collection: (method, the error of a collection that lacks it)
@@ -51,11 +53,15 @@ _NEEDS_GROUPING = ("grouped_query", "grouped retrieval needs a single-GPU collec
 _NEEDS_DEDUP = ("near_duplicates", "near-duplicate detection needs a single-GPU collection (VectorIndex) with "
                                    "full-precision rows")
 _NEEDS_CLUSTERING = ("cluster", "topic clustering needs a single-GPU collection (VectorIndex) with full-precision rows")
+_NEEDS_BOOST = ("boosted_query", "boosted retrieval needs a single-GPU collection (VectorIndex) with full-precision "
+                                 "rows")
+_boost_warned = False    # "this collection cannot boost": once per process
 _dedup_warned = False    # "MMRAG_DEDUP_THRESHOLD is set but this collection cannot de-duplicate": once per process
 # the answer of a batch's query that could not be answered, before its 'error' (copied for every such query)
 _EMPTY = {key: [] for key in RESULT_KEYS}
 _EMPTY_MMR = {key: [] for key in MMR_KEYS}
 _EMPTY_FUSED = {key: [] for key in FUSED_KEYS}
+_EMPTY_BOOST = {key: [] for key in BOOST_KEYS}
 _EMPTY_GROUPED = {**_EMPTY, "groups": [], "exhaustive": False, "fetch_k": 0}
 
 
@@ -249,6 +255,11 @@ class EmbeddingManager:
             if item["type"] in counts:           # other kinds are stored but not counted (:477-479)
                 counts[item["type"]] += 1
         joint = hasattr(self._engine, "encode_images")
+        # when the rows were added (what a recency boost reads): the time of this call, or each item's own UNIX time
+        # under MMRAG_BOOST_TIME_KEY; kept beside the rows, never in their metadata
+        extra = {}
+        if hasattr(self.collection, "boosted_query"):
+            extra["timestamps"] = self._item_times(summaries, t0)
         dedup = settings.dedup_threshold()
         if dedup > 0 and not self.supports_dedup():
             global _dedup_warned
@@ -273,11 +284,11 @@ class EmbeddingManager:
                     matrix[list(pixels)] = np.asarray(vecs, dtype=np.float32)
             if dedup > 0:
                 done = await self._engine_call("Store", self.collection.add, embeddings=matrix, documents=texts,
-                                               metadatas=metas, ids=ids, dedup_threshold=dedup)
+                                               metadatas=metas, ids=ids, dedup_threshold=dedup, **extra)
                 skipped = len(done["skipped"])
                 counts["duplicates_skipped"] = skipped     # the per-kind counts keep counting items processed
             else:
-                await self._store_with_retry(embeddings=matrix, documents=texts, metadatas=metas, ids=ids)
+                await self._store_with_retry(embeddings=matrix, documents=texts, metadatas=metas, ids=ids, **extra)
         if skipped:
             logger.info("Skipped %d near-duplicate items of doc %s (cosine >= %s)", skipped, doc_id, dedup)
         self.stats["total_items_stored"] += len(summaries)
@@ -285,10 +296,23 @@ class EmbeddingManager:
                     counts["text"], counts["table"], counts["image"], time.time() - t0)
         return counts
 
-    async def _store_with_retry(self, embeddings, documents, metadatas, ids):
+    async def _store_with_retry(self, embeddings, documents, metadatas, ids, **extra):
         """embedder.py:502-537."""
         await self._engine_call("Store", self.collection.add, embeddings=embeddings, documents=documents,
-                                metadatas=metadatas, ids=ids)
+                                metadatas=metadatas, ids=ids, **extra)
+
+    @staticmethod
+    def _item_times(summaries: List[Dict[str, Any]], call_time: float) -> List[float]:
+        """each item's add time: its own finite UNIX time under MMRAG_BOOST_TIME_KEY when that is set, else call_time"""
+        key = settings.MMRAG_BOOST_TIME_KEY
+        times = []
+        for item in summaries:
+            t = item.get(key) if key else None
+            if t is None and key and isinstance(item.get("metadata"), dict):
+                t = item["metadata"].get(key)
+            ok = isinstance(t, (int, float)) and not isinstance(t, bool) and math.isfinite(t)
+            times.append(float(t) if ok else call_time)
+        return times
 
     # ------------------------------------------------------------------ query ---------------
     def enable_dynamic_batching(self, max_batch: int = 256, max_wait_ms: float = 2.0):
@@ -299,8 +323,12 @@ class EmbeddingManager:
         def scoped(texts, n_results, doc_ids_per_query):      # the dispatcher's (texts, k, documents) order
             return self.batch_scoped_query(texts, doc_ids_per_query, n_results=n_results)
 
+        def boosted(texts, n_results, filter_dict, spec):
+            return self.batch_boosted_query(texts, n_results=n_results, filter_dict=filter_dict, boost=spec)
+
         self._dispatcher = QueryDispatcher(self.batch_query, max_batch=max_batch, max_wait_ms=max_wait_ms,
-                                           scoped_fn=scoped if self.supports_scoped() else None)
+                                           scoped_fn=scoped if self.supports_scoped() else None,
+                                           boosted_fn=boosted if self.supports_boost() else None)
         return self._dispatcher
 
     _INCLUDE = ["metadatas", "documents", "distances"]
@@ -448,6 +476,65 @@ class EmbeddingManager:
             raise ValueError(f"{len(doc_ids_per_query)} document lists for {len(queries)} queries")
         live = [list(ids) for q, ids in zip(queries, doc_ids_per_query) if q and q.strip()]    # as _batch picks them
         return await self._batch("Batch scoped query", None, _EMPTY, self._answer_scoped, queries, n_results, live)
+
+    def supports_boost(self) -> bool:
+        """True when the collection can rank with a score prior (a single-GPU VectorIndex with full-precision rows; not
+        the sharded serving path, which does not carry the request: one warning says so)"""
+        ok = self.collection is None or (hasattr(self.collection, "boosted_query") and self._has_full_rows())
+        if not ok:
+            global _boost_warned
+            if not _boost_warned:
+                _boost_warned = True
+                logger.warning("Boosted retrieval is not available: %s", _NEEDS_BOOST[1])
+        return ok
+
+    @staticmethod
+    def _boost_spec(boost):
+        """a request's `boost` (None / True: the configured defaults; a dict {"recency", "half_life_days", "values"};
+        or a ready BoostSpec) as a BoostSpec; ValueError for a malformed one and for False, which means "no boost" to
+        POST /query: such a request belongs to query()"""
+        from .boost import BoostSpec, parse_boost
+
+        if isinstance(boost, BoostSpec):
+            return boost
+        if boost is False:
+            raise ValueError("'boost' is false: a query without a boost is query(), not boosted_query()")
+        return parse_boost(True if boost is None else boost, settings.MMRAG_BOOST_RECENCY,
+                           settings.MMRAG_BOOST_HALF_LIFE_DAYS)
+
+    def _answer_boosted(self, texts: Sequence[str], n_results: int, filter_dict: Optional[Dict],
+                        spec) -> List[Dict[str, Any]]:
+        """blocking, one worker thread: cached or fresh embeddings (ONE encoder pass for the misses), then ONE
+        collection.boosted_query for all of them (one scan with the spec's prior column)"""
+        if not self._has_full_rows():
+            raise ValueError(_NEEDS_BOOST[1])
+        res = self.collection.boosted_query(self._embed(texts), n_results=n_results, prior=spec, weight=1.0,
+                                            where=filter_dict, include=self._INCLUDE)
+        return [{key: res[key][at] for key in BOOST_KEYS} for at in range(len(texts))]
+
+    async def boosted_query(self, query_text: str, n_results: int = 5, filter_dict: Optional[Dict] = None,
+                            boost=None) -> Dict[str, Any]:
+        """query() ranked by cosine + a score prior (VectorIndex.boosted_query): `boost` is {"recency": weight of the
+        recency term, "half_life_days": the age at which it has halved, "values": {metadata key: {value: added
+        score}}}, missing fields from MMRAG_BOOST_RECENCY / MMRAG_BOOST_HALF_LIFE_DAYS.  One result dict with the keys of
+        query() plus `scores` (final, descending) and `boosts`; `distances` stay 1 - cosine and are not ascending.  Same
+        empty-query error, embedding cache and query count as query(); with dynamic batching on, concurrent callers of
+        one n_results and one boost share one encode and one search."""
+        spec = self._boost_spec(boost)
+        if self._dispatcher is not None and self._dispatcher.boosted_fn is not None:
+            await self._ready()
+            if not query_text or not query_text.strip():
+                raise ValueError("Query text cannot be empty")
+            return await self._dispatcher.submit(query_text, n_results, filter_dict, None, boost=spec)
+        return await self._single("Boosted query", _NEEDS_BOOST, self._answer_boosted, query_text, n_results,
+                                  filter_dict, spec)
+
+    async def batch_boosted_query(self, queries: List[str], n_results: int = 5, filter_dict: Optional[Dict] = None,
+                                  boost=None) -> List[Dict[str, Any]]:
+        """batch_query's twin for boosted_query: one batched encode and one boosted search for all the queries; a query
+        that cannot be answered gets a dict with empty lists and an 'error' message."""
+        return await self._batch("Batch boosted query", _NEEDS_BOOST, _EMPTY_BOOST, self._answer_boosted, queries,
+                                 n_results, filter_dict, self._boost_spec(boost))
 
     def supports_hybrid(self) -> bool:
         """True when the collection can answer hybrid_query (a single-GPU VectorIndex; not the sharded serving path)"""

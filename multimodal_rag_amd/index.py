@@ -20,12 +20,15 @@ import gc
 import logging
 import operator
 import threading
+import time
+from collections import OrderedDict
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _native
+from .boost import BoostSpec, check_prior_values
 from .hostutil import load_hostrows
 from .tracing import stage
 
@@ -227,6 +230,11 @@ class VectorIndex:
         self._scoped_ws: Optional[torch.Tensor] = None    # workspace of the scoped search, reused
         self._lex = None   # lexical.LexicalIndex once enable_lexical() ran (lazily: first lexical / hybrid query)
         self._groups: Dict[str, Dict[str, Any]] = {}   # metadata key -> group column state once enable_grouping(key) ran
+        self._boosted_ws: Optional[torch.Tensor] = None   # workspace of the boosted search, reused
+        self._added_at = np.full(cap, np.nan, dtype=np.float64)   # when each row in use was added (NaN = unknown)
+        self._priors: Dict[str, Any] = {}     # set_prior names -> a device float32 [capacity] column, or a BoostSpec
+        # spec columns by (canonical JSON of the spec, floored now) -> {"spec", "now", "col"}; at most MAX_SPEC_COLUMNS
+        self._spec_cols: "OrderedDict[Tuple[str, float], Dict[str, Any]]" = OrderedDict()
         self.f32_exact = bool(settings.MMRAG_F32_EXACT_SEARCH)   # float32 collections only (see config.py)
 
     def _new_rows(self, rows: int, zero: bool) -> torch.Tensor:
@@ -292,6 +300,10 @@ class VectorIndex:
         self._alive_host = host
         for st in self._groups.values():
             st["col"] = self._regrown(st["col"], new_cap, -1)
+        times = np.full(new_cap, np.nan, dtype=np.float64)
+        times[: self._n] = self._added_at[: self._n]
+        self._added_at = times
+        self._map_prior_columns(lambda col: self._regrown(col, new_cap, 0))
 
     def _regrown(self, t: torch.Tensor, cap: int, fill: int) -> torch.Tensor:
         """a per-row device tensor (matrix, plane, group column) at capacity `cap`: rows in use copied, tail filled"""
@@ -380,8 +392,10 @@ class VectorIndex:
     # ------------------------------------------------------------------ collection API ----
     def add(self, embeddings, documents: Optional[Sequence[Optional[str]]] = None,
             metadatas: Optional[Sequence[Dict[str, Any]]] = None, ids: Optional[Sequence[str]] = None,
-            dedup_threshold: Optional[float] = None):
-        """Append rows (collection.add).  `dedup_threshold` (None: off, returns None): a cosine t in (0, 1]; a row whose
+            dedup_threshold: Optional[float] = None, timestamps=None):
+        """Append rows (collection.add).  `timestamps`: when each row was added, a UNIX time or one per row (NaN =
+        unknown; default: now) -- what a recency prior reads (set_prior), stored beside the rows and never in their
+        metadata.  `dedup_threshold` (None: off, returns None): a cosine t in (0, 1]; a row whose
         best stored row scores >= t, or that pairs (>= t) with an earlier row of this batch that is itself kept, is
         skipped and never reaches the matrix, the row tables or the lexical / group columns.  Returns then
         {"added": [ids], "skipped": [(id, duplicate_of, cosine)]}."""
@@ -398,6 +412,7 @@ class VectorIndex:
         metadatas = [dict(x) if x else {} for x in metadatas] if metadatas is not None else [{} for _ in range(m)]
         if len(documents) != m or len(metadatas) != m:
             raise ValueError("documents / metadatas length mismatch")
+        times = self._row_times(timestamps, m)
         with self._lock:
             fresh = [i for i, s in enumerate(ids) if s not in self._row_of]
             seen = set()
@@ -428,7 +443,7 @@ class VectorIndex:
                 self._ids.append(ids[i])
                 self._documents.append(documents[i])
                 self._metadatas.append(metadatas[i])
-            self._appended(len(keep))
+            self._appended(len(keep), times[keep])
             return None if dedup_threshold is None else {"added": [ids[i] for i in keep], "skipped": skipped}
 
     # ------------------------------------------------------------------ near-duplicates ----
@@ -663,15 +678,16 @@ class VectorIndex:
             return out
 
     def add_rows_device(self, rows_packed: torch.Tensor, documents, metadatas, ids,
-                        plane_rows: Optional[torch.Tensor] = None):
+                        plane_rows: Optional[torch.Tensor] = None, timestamps=None):
         """Append rows that are already in storage layout [m, ld] (bulk loads, benchmarks).  FP8 collections take the
         E4M3 codes (uint8 or float8_e4m3fn) and, when they keep a re-scoring plane, the same rows in the plane's layout
-        [m, plane_ld] as `plane_rows`."""
+        [m, plane_ld] as `plane_rows`.  `timestamps` as add()'s."""
         m = rows_packed.shape[0]
         if self.is_f8 and rows_packed.dtype not in (torch.uint8, torch.float8_e4m3fn):
             raise ValueError("a float8_e4m3fn collection takes E4M3 codes (uint8 or float8_e4m3fn)")
         if (self._plane is None) != (plane_rows is None) or (plane_rows is not None and plane_rows.shape[0] != m):
             raise ValueError("plane_rows must be given exactly when the collection keeps a re-scoring plane, one per row")
+        times = self._row_times(timestamps, m)
         with self._lock:
             self._reserve(self._n + m)
             self._raw(self._matrix)[self._n: self._n + m].copy_(self._raw(rows_packed))
@@ -682,11 +698,35 @@ class VectorIndex:
             self._ids.extend(ids)
             self._documents.extend(documents if documents is not None else [None] * m)
             self._metadatas.extend(metadatas if metadatas is not None else [{} for _ in range(m)])
-            self._appended(m)
+            self._appended(m, times)
 
-    def _appended(self, m: int):
-        """m rows were appended to the matrix and the row tables (caller holds the lock): what is derived follows"""
+    @staticmethod
+    def _row_times(timestamps, m: int) -> np.ndarray:
+        """`timestamps` of add() as float64 [m]: None = now, a number = that time for every row"""
+        if timestamps is None:
+            return np.full(m, time.time(), dtype=np.float64)
+        t = np.asarray(timestamps, dtype=np.float64)
+        if np.isinf(t).any():
+            raise ValueError("timestamps must be UNIX times or NaN")
+        if t.ndim == 0:
+            return np.full(m, float(t), dtype=np.float64)
+        if t.shape != (m,):
+            raise ValueError(f"{t.size} timestamps for {m} rows")
+        return t.copy()
+
+    def _appended(self, m: int, times: np.ndarray):
+        """m rows, added at `times`, were appended to the matrix and the row tables (caller holds the lock): what is
+        derived follows"""
         lo, hi = self._n, self._n + m
+        self._added_at[lo:hi] = times
+        # a cached spec column stays current, at ITS now; one of a floored hour that has passed is dropped instead: no
+        # search asks for it again, and the cost of an add stays that of the columns in use
+        for key, st in list(self._spec_cols.items()):
+            if st["spec"].now is None and st["spec"].resolved_now() != st["now"]:
+                del self._spec_cols[key]
+                continue
+            new = st["spec"].column(times, self._metadatas[lo:hi], st["now"])
+            st["col"][lo:hi].copy_(_native._pinned_to_device(torch.from_numpy(new), self.device))
         self._meta_index.append(self._metadatas[lo:hi])
         self._set_alive(lo, hi)
         if self._lex is not None:
@@ -1014,6 +1054,10 @@ class VectorIndex:
                 st["col"] = self._compacted(st["col"], cap, keep_dev, -1)
                 live = st["col"][: self._n]
                 st["counts"] = torch.bincount(live[live >= 0], minlength=len(st["values"])).tolist()
+            times = np.full(cap, np.nan, dtype=np.float64)
+            times[: self._n] = self._added_at[keep]
+            self._added_at = times
+            self._map_prior_columns(lambda col: self._compacted(col, cap, keep_dev, 0))
 
     def reset(self):
         with self._lock:
@@ -1026,6 +1070,9 @@ class VectorIndex:
             if self._lex is not None:
                 self._lex.reset()
             self._groups = {}
+            self._added_at[:] = np.nan
+            self._priors = {}
+            self._spec_cols.clear()
 
     # ------------------------------------------------------------------ diversified (MMR) ----
     def _launch_mmr(self, query_embeddings, n_results: int, fetch_k, lambda_mult, where, check_norm: bool = True):
@@ -1326,6 +1373,128 @@ class VectorIndex:
             emb_src = self._full if "embeddings" in include else None
         with stage("collect"):
             return self._collect(scores, rows, include, *tables, emb_src)
+
+    # ------------------------------------------------------------------ score priors (boosted retrieval) ----
+    MAX_SPEC_COLUMNS = 4
+
+    def _map_prior_columns(self, f: Callable[[torch.Tensor], torch.Tensor]):
+        """every prior column through f (capacity growth, compaction; caller holds the lock)"""
+        for name, p in self._priors.items():
+            if isinstance(p, torch.Tensor):
+                self._priors[name] = f(p)
+        for st in self._spec_cols.values():
+            st["col"] = f(st["col"])
+
+    def row_times(self) -> np.ndarray:
+        """when each LIVE row was added (float64 UNIX times, NaN = unknown), in row order"""
+        with self._lock:
+            t = self._added_at[: self._n]
+            return t[~self._is_dead(np.arange(self._n, dtype=np.int64))].copy() if self._n_dead else t.copy()
+
+    def set_prior(self, name: str = "default", values=None, spec: Optional[BoostSpec] = None):
+        """Name a score prior for boosted_search: either `values`, the caller's own finite numbers (pins, click counts),
+        one per live row in row order -- rows added later get 0.0 until it is set again -- or a BoostSpec, whose column
+        is built from the rows' add times and metadata when a search first needs it and kept current from then on.
+        Columns are float32 on the device, follow add / growth / compact like the group columns, are dropped by reset()
+        and are not persisted."""
+        if (values is None) == (spec is None):
+            raise ValueError("set_prior takes exactly one of values and spec")
+        if spec is not None and not isinstance(spec, BoostSpec):
+            raise ValueError("spec must be a BoostSpec")
+        with self._lock:
+            if spec is not None:
+                self._priors[name] = spec
+                return
+            vals = check_prior_values(values, self.count())
+            col = np.zeros(self._matrix.shape[0], dtype=np.float32)
+            if self._n_dead:
+                col[np.nonzero(~self._is_dead(np.arange(self._n, dtype=np.int64)))[0]] = vals
+            else:
+                col[: self._n] = vals
+            self._priors[name] = torch.from_numpy(col).to(self.device)
+
+    def _spec_column(self, spec: BoostSpec) -> torch.Tensor:
+        """the device column of a spec at its (floored) now, from the cache or built as one numpy expression and one
+        upload (caller holds the lock)"""
+        key = spec.cache_key()
+        st = self._spec_cols.get(key)
+        if st is None:
+            col = np.zeros(self._matrix.shape[0], dtype=np.float32)
+            col[: self._n] = spec.column(self._added_at[: self._n], self._metadatas, key[1])
+            st = {"spec": spec, "now": key[1], "col": torch.from_numpy(col).to(self.device)}
+            self._spec_cols[key] = st
+            while len(self._spec_cols) > self.MAX_SPEC_COLUMNS:
+                self._spec_cols.popitem(last=False)
+        return st["col"]
+
+    def _prior_column(self, prior) -> torch.Tensor:
+        if isinstance(prior, BoostSpec):
+            return self._spec_column(prior)
+        p = self._priors.get(prior) if isinstance(prior, str) else None
+        if p is None:
+            raise ValueError(f"unknown prior {prior!r}: name one with set_prior, or pass a BoostSpec")
+        return self._spec_column(p) if isinstance(p, BoostSpec) else p
+
+    def _launch_boosted(self, query_embeddings, n_results: int, prior, weight, where, check_norm: bool = True):
+        """enqueue the boosted search (caller holds the lock): device (scores, rows, boosts, packed queries), no host
+        sync unless the collection is larger than a query's candidate slots"""
+        self._need_plane("boosted_query")
+        k = int(n_results)
+        if not 1 <= k <= _native.MAX_K_DEEP:
+            raise ValueError(f"n_results must be in 1..{_native.MAX_K_DEEP} for a boosted search")
+        col = self._prior_column(prior)
+        qf = self._to_device_f32(query_embeddings, "query", check_norm)     # converted and norm-checked once
+        q = self._pack_plane_queries(qf) if self._plane is not None else self._pack_queries(qf, check_norm=False)
+        B = q.shape[0]
+        w = np.asarray(weight, dtype=np.float64).reshape(-1)
+        if w.size == 1:
+            w = np.full(B, float(w[0]))
+        if w.size != B:
+            raise ValueError(f"weight holds {w.size} entries for {B} queries")
+        need = _native.boosted_topk_workspace_bytes(B, self._n, k)
+        scores, rows, boosts = _native.boosted_topk(
+            q, self._full, self._n, self.dim, k, col, w, alive_bits=self._where_bits(where),
+            workspace=self._workspace("_boosted_ws", need))
+        return scores, rows, boosts, q
+
+    def boosted_search(self, query_embeddings, n_results: int, prior="default", weight=1.0,
+                       where: Optional[Dict[str, Any]] = None):
+        """Raw device search ranked by cos(q_b, x_r) + weight_b * prior[r] (csrc/boosted.hip, include/mmrag.h
+        mmrag_boosted_topk): the prior is applied INSIDE one exact scan, so a row with a large prior and a middling cosine
+        is found although it is in no cosine top-k -- re-sorting a finished list cannot do that.  `prior`: a name given
+        to set_prior, or a BoostSpec; `weight`: a number, or one per query.  Returns (scores [B, k] float32 = the final
+        scores descending, rows [B, k] int64, -1 = none, boosts [B, k] float32 = weight * prior of each hit), n_results
+        up to MAX_K_DEEP.  `where` narrows the batch and tombstones are honoured; a float8_e4m3fn collection is searched
+        on its re-scoring plane (capacity mode raises ValueError)."""
+        with self._lock:
+            return self._launch_boosted(query_embeddings, n_results, prior, weight, where)[:3]
+
+    def boosted_query(self, query_embeddings, n_results: int = 10, prior="default", weight=1.0,
+                      where: Optional[Dict[str, Any]] = None,
+                      include: Sequence[str] = ("metadatas", "documents", "distances"),
+                      check_norm: bool = True) -> Dict[str, Any]:
+        """query() ranked by boosted_search: the Chroma-shaped dict of query() plus `scores` (the final scores, descending)
+        and `boosts` (weight * prior of each hit).  `distances` stay 1 - cosine -- the hits' own cosines, computed from
+        the stored rows -- and are therefore NOT ascending."""
+        from .lexical import rows_dot
+
+        with self._lock, stage("search"):
+            scores, rows, boosts, q = self._launch_boosted(query_embeddings, n_results, prior, weight, where, check_norm)
+            B, k = rows.shape
+            flat = rows.reshape(-1)
+            qi = torch.arange(B, device=self.device, dtype=torch.int32).repeat_interleave(k)
+            cos = rows_dot(q, self._full, self.dim, qi, flat.clamp(min=0)).view(B, k)    # padding: row 0, cut below
+            tables = self._tables()
+            emb_src = self._full if "embeddings" in include else None
+        with stage("collect"):
+            want = tuple(include) if "distances" in include else tuple(include) + ("distances",)
+            out = self._collect(cos, rows, want, *tables, emb_src)
+            lens = [len(ids) for ids in out["ids"]]
+            if "distances" not in include:
+                out["distances"] = None
+            out["scores"] = [row[:m] for row, m in zip(scores.cpu().tolist(), lens)]
+            out["boosts"] = [row[:m] for row, m in zip(boosts.cpu().tolist(), lens)]
+            return out
 
     # ------------------------------------------------------------------ multi-query fusion ----
     def _launch_fused(self, query_embeddings, list_off, n_results: int, fetch_k, weights, method, where,

@@ -2,7 +2,7 @@
 
 * `save_index` / `load_index`: the shard matrix (.npy, storage dtype as raw uint16/float32; an FP8 collection's
   scan plane as raw uint8 codes, its re-scoring plane as plane.npy, both named in the JSON header) plus the host row
-  tables (JSON).  Files written by this module are read back with `numpy.load(...,
+  tables (JSON; the rows' add times as an optional "added_at" list, null where unknown).  Files written by this module are read back with `numpy.load(...,
   allow_pickle=False)` and `json`.
 * `read_chroma_wal` / `replay_wal`: ingest an existing reference deployment directly from Chroma's
   write-ahead log, the `embeddings_queue` table of `chroma.sqlite3` (schema verified on the
@@ -97,6 +97,8 @@ def save_index(index, directory: str) -> None:
     """Persist a VectorIndex: matrix rows [0, n) + id/document/metadata tables."""
     import torch
 
+    from .boost import times_to_tables
+
     os.makedirs(directory, exist_ok=True)
     index.compact()   # tombstoned rows are not persisted
     n = index.count()
@@ -118,12 +120,14 @@ def save_index(index, directory: str) -> None:
         json.dump({**planes,
                    "name": index.name, "dim": index.dim, "ld": index.ld, "dtype": str(index.dtype).split(".")[-1],
                    "count": n, "metadata": index.metadata, "ids": index._ids, "documents": index._documents,
-                   "metadatas": index._metadatas}, f)
+                   "metadatas": index._metadatas,
+                   **({"added_at": times_to_tables(index.row_times())} if hasattr(index, "row_times") else {})}, f)
 
 
 def load_index(directory: str, device: str = "cuda:0"):
     import torch
 
+    from .boost import times_from_tables
     from .index import VectorIndex
 
     with open(os.path.join(directory, "tables.json"), encoding="utf-8") as f:
@@ -149,8 +153,10 @@ def load_index(directory: str, device: str = "cuda:0"):
             raise ValueError(f"plane shape {tuple(plane_rows.shape)} does not match tables ({t['count']}, {idx.plane_ld})")
         plane_rows = plane_rows.to(device)
     if t["count"]:
+        times = times_from_tables(t, t["count"])    # optional "added_at": NaN (unknown) for a directory without it
         if plane_rows is not None:
-            idx.add_rows_device(rows.to(device), t["documents"], t["metadatas"], t["ids"], plane_rows=plane_rows)
+            idx.add_rows_device(rows.to(device), t["documents"], t["metadatas"], t["ids"], plane_rows=plane_rows,
+                                timestamps=times)
         else:
-            idx.add_rows_device(rows.to(device), t["documents"], t["metadatas"], t["ids"])
+            idx.add_rows_device(rows.to(device), t["documents"], t["metadatas"], t["ids"], timestamps=times)
     return idx

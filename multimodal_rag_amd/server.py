@@ -15,11 +15,12 @@ import time
 import uuid
 from contextlib import asynccontextmanager
 from datetime import datetime
-from typing import Annotated, Any, List, Literal, Optional
+from typing import Annotated, Any, Dict, List, Literal, Optional, Union
 
 from fastapi import FastAPI, HTTPException, Request, status
-from pydantic import BaseModel, Field
+from pydantic import BaseModel, Field, StrictBool
 
+from .boost import parse_boost
 from .config import settings
 from .embedder import EmbeddingManager
 from .index import DuplicateReportTruncated
@@ -80,6 +81,13 @@ class QueryRequest(BaseModel):  # api.py:161-164
     # Ids no stored document has match nothing: the answer then has no sources
     doc_ids: Optional[Annotated[List[Annotated[str, Field(min_length=1, max_length=200)]],
                                 Field(min_length=1, max_length=64)]] = None
+    # not in the reference: boosted retrieval (EmbeddingManager.boosted_query): hits are ranked by cosine + a score
+    # prior applied inside the scan.  {"recency": -10..10 (weight of 2 ** (-age / half life)), "half_life_days": > 0,
+    # "values": {metadata key: {value: -10..10 added to the score}}}, at most 8 keys of 32 values; missing fields and
+    # `true` take MMRAG_BOOST_RECENCY / MMRAG_BOOST_HALF_LIFE_DAYS.  Each source then carries its `boost` and final
+    # `score`; `relevance_score` stays the cosine.  With `rerank`, max(top_k, MMRAG_RERANK_CANDIDATES) boosted hits are
+    # re-ranked.  Not combined with `hybrid`, `mmr`, `group_by_document`, `variants` / `expand` or `doc_ids` yet
+    boost: Optional[Union[StrictBool, Dict[str, Any]]] = None
 
 
 # request flag -> what it needs of the embedder (method, `supports_*` check) and the 400 detail when that is missing;
@@ -103,6 +111,13 @@ MODE_NEEDS = (
 MULTI_NEEDS = ("multi_query", "supports_multi_query",
                "Multi-query retrieval is not available with this embedder: it needs a single-GPU collection "
                "(EmbeddingManager.multi_query)")
+
+
+# boosted retrieval (`boost`): the same
+BOOST_NEEDS = ("boosted_query", "supports_boost",
+               "Boosted retrieval is not available with this embedder: it needs a single-GPU collection "
+               "(EmbeddingManager.boosted_query); a float8_e4m3fn collection also needs its re-scoring plane "
+               "(MMRAG_F8_RESCORE=float16)")
 
 
 # `rerank` with the method "late": the same
@@ -258,7 +273,7 @@ class Pipeline:
                      group_by_document: bool = False, per_document: int = 1,
                      variants: Optional[List[str]] = None, variant_weight: Optional[float] = None,
                      fusion: Optional[str] = None, doc_ids: Optional[List[str]] = None,
-                     rerank_method: Optional[str] = None, explain: bool = False) -> Optional[dict]:
+                     rerank_method: Optional[str] = None, explain: bool = False, boost: Any = None) -> Optional[dict]:
         """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
         max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the re-ranker's best top_k (`rerank_method` "cross" or "late",
         default MMRAG_RERANK_METHOD; `explain`: late interaction's per-token matches on every source).  `hybrid`: from
@@ -269,7 +284,8 @@ class Pipeline:
         further phrasings (EmbeddingManager.multi_query; `variant_weight` for each of them against 1.0, `fusion`
         "rrf" or "max"); the generator and the re-ranker see `question` only.  `doc_ids`: hits from these documents
         only -- a plain (or re-ranked) query through EmbeddingManager.scoped_query, every other mode through its
-        filter"""
+        filter.  `boost` (a BoostSpec; alone or with `rerank`): the hits are ranked by cosine + the spec's score prior
+        (EmbeddingManager.boosted_query)"""
         multi = variants is not None
         # the restriction as the filter the embedder's methods take (nothing is passed when there is none)
         only = {} if doc_ids is None else {"filter_dict": {"doc_id": {"$in": list(doc_ids)}}}
@@ -279,6 +295,8 @@ class Pipeline:
             def search(text, n_results):
                 return self.embedder.multi_query([text] + list(variants), n_results=n_results, weights=weights,
                                                  method=fusion, **only)
+        elif boost is not None:
+            search = functools.partial(self.embedder.boosted_query, boost=boost)
         elif mmr:
             search = functools.partial(self.embedder.mmr_query, lambda_mult=mmr_lambda, **only)
         elif hybrid:
@@ -289,7 +307,7 @@ class Pipeline:
             search = functools.partial(self.embedder.query, **only)
         # per-hit columns re-ranking carries along
         extra = ("fused_scores", "matched_queries") if multi else ("mmr_scores",) if mmr else \
-            ("hybrid_scores",) if hybrid else ()
+            ("hybrid_scores",) if hybrid else ("scores", "boosts") if boost is not None else ()
         if group_by_document:
             hits = await self.embedder.grouped_query(question, n_groups=top_k, group_size=per_document, **only)
         elif rerank:
@@ -322,7 +340,8 @@ class Pipeline:
                   for at, (found, dist, meta) in enumerate(zip(hits["ids"], hits["distances"], hits["metadatas"]), 1)]
         for on, column, key in ((rerank, "rerank_scores", "rerank_score"), (hybrid, "hybrid_scores", "hybrid_score"),
                                 (mmr, "mmr_scores", "mmr_score"), (multi, "fused_scores", "fused_score"),
-                                (multi, "matched_queries", "matched_queries")):
+                                (multi, "matched_queries", "matched_queries"), (boost is not None, "scores", "score"),
+                                (boost is not None, "boosts", "boost")):
             if on:
                 for src, score in zip(ranked, hits[column]):
                     src[key] = score
@@ -450,6 +469,18 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
         elif request.rerank and not (hasattr(pipe.embedder, "has_reranker") and pipe.embedder.has_reranker()):
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="Re-ranking is not configured: set MMRAG_RERANKER_DIR to a local cross-encoder")
+        spec = None
+        if request.boost is not None and request.boost is not False:
+            if multi or request.mmr or request.hybrid or request.group_by_document or request.doc_ids is not None:
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                    detail="Boosted retrieval is not combined with hybrid retrieval, MMR, grouping by "
+                                           "document, multi-query retrieval or `doc_ids` yet: send `boost` without "
+                                           "`hybrid`, `mmr`, `group_by_document`, `variants` / `expand` and `doc_ids`")
+            try:
+                spec = parse_boost(request.boost, settings.MMRAG_BOOST_RECENCY, settings.MMRAG_BOOST_HALF_LIFE_DAYS)
+            except ValueError as e:
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
+            pipe._need(BOOST_NEEDS)
         if request.mmr and request.hybrid:
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="MMR and hybrid retrieval are not combined yet: send `mmr` or `hybrid`, not both")
@@ -480,7 +511,8 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
                                 group_by_document=request.group_by_document, per_document=request.per_document,
                                 variants=variants, variant_weight=request.variant_weight, fusion=request.fusion,
                                 doc_ids=request.doc_ids,
-                                rerank_method="late" if late else request.rerank_method, explain=request.explain)
+                                rerank_method="late" if late else request.rerank_method, explain=request.explain,
+                                **({} if spec is None else {"boost": spec}))
         if out is None:
             out = {"answer": NO_DOCS_ANSWER, "sources": []}
         return {**out, "processing_time": time.time() - t0}
