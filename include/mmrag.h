@@ -612,6 +612,53 @@ int mmrag_boosted_topk(const void *q, const void *rows, int B, int64_t n, int d,
                        float *out_scores, int64_t *out_rows, float *out_boost, void *workspace, size_t workspace_bytes,
                        void *stream);
 
+/* Recommend top-k (csrc/recommend.hip): "more like these, less like those" -- a batch of requests, each a group of
+ * signed example vectors, ranked inside ONE exact scan.  VectorIndex.recommend_search.
+ *
+ * A request owns MMRAG_MAX_RECOMMEND_EXAMPLES slots.  Each holds a unit vector with a sign: +1 positive, -1 negative,
+ * 0 unused.  For a live stored row x (r < n, alive bit set when alive_bits is given):
+ *   pos   = max over the request's positive examples e of <e, x>
+ *   neg   = max over its negative examples e of <e, x>          (no negatives: neg = 0)
+ *   final = fmaf(-w, max(neg, 0), pos)                           one rounding, w >= 0 per request
+ * max(neg, 0): a row is never rewarded for being unlike a negative.  With no negatives final = pos, "nearest to any of
+ * these".  A request needs at least one positive; one without gets padding only.
+ * Contract
+ *   - a dot is the float32 accumulation of the pair-tile body's fixed K order: its bits depend on the example row, the
+ *     stored row and d alone; final's bits depend on the request's examples, signs and weight plus the stored row: not on
+ *     the batch, the slot or tile the request sits in, the order of its examples, the grid, the threshold or whether
+ *     bound passes ran;
+ *   - rows of slots with sign 0 are ignored whatever they hold;
+ *   - out_scores / out_rows [R, k] as mmrag_cosine_topk_deep's: final descending, ties to the lower row,
+ *     row + row_offset, (-inf, -1) padded;
+ *   - out_pos / out_neg [R, k] float32, optional (NULL allowed): pos and neg of each hit (neg as defined above, before
+ *     max(., 0); 0 when the request has no negative), recomputed as mmrag_rows_dot computes a dot, so they agree with
+ *     the scan's to the float32 summation order (1e-4 on unit rows) and exactly on exactly representable data;
+ *     out_scores stays authoritative.  out_pos_arg / out_neg_arg [R, k] int32, optional: the slot 0..15 that gave pos /
+ *     neg, the lowest on equal dots, -1 for none.  Padding: 0 / -1;
+ *   - exact: when n exceeds the candidate slots of a request (32 k, at least 16384) a sampled lower bound on the k-th
+ *     final is staged first (the k-th best of any subset of live rows is at most the true k-th, whatever the score
+ *     function), and only finals at or above it are kept;
+ *   - at most one stream synchronisation per call, and only when n exceeds the candidate slots.
+ *
+ *   examples        dev [16 R, ld] of the rows' dtype and ld, pad columns zero: request g owns rows 16 g .. 16 g + 15
+ *   sign            dev int8 [16 R], 4-byte aligned, values in {-1, 0, 1}
+ *   neg_weight      dev float32 [R], finite, >= 0
+ *   rows            dev [n, ld], MMRAG_F32 / F16 / BF16, ld of whole 128-byte slabs; MMRAG_F8E4M3 returns
+ *                   MMRAG_EUNSUPPORTED (an FP8 collection is searched by examples on its re-scoring plane)
+ *   k               1..MMRAG_MAX_K_DEEP
+ *   alive_bits      dev, optional (NULL = every row): bit r & 31 of word r >> 5
+ *   workspace       dev, >= mmrag_recommend_topk_workspace_bytes(R, n, k) bytes (0 for arguments out of range), 16-byte
+ *                   aligned; short or misaligned: MMRAG_EWORKSPACE
+ * MMRAG_EINVAL before anything is launched: a null pointer (the optional ones aside), R < 1 or > 2^20, n < 0 or >= 2^31,
+ * k out of range, d <= 0, ld < d or not whole slabs.  sign and neg_weight live on the device and are not read by the host (the
+ * Python wrapper checks the host copies it uploads). */
+#define MMRAG_MAX_RECOMMEND_EXAMPLES 16
+size_t mmrag_recommend_topk_workspace_bytes(int R, int64_t n, int k);
+int mmrag_recommend_topk(const void *examples, const int8_t *sign, const float *neg_weight, const void *rows, int R,
+                         int64_t n, int d, int64_t ld, int dtype, int k, int64_t row_offset, const uint32_t *alive_bits,
+                         float *out_scores, int64_t *out_rows, float *out_pos, float *out_neg, int32_t *out_pos_arg,
+                         int32_t *out_neg_arg, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Late-interaction re-ranking (ColBERT's MaxSim) with the bi-encoder alone.  The reference has no counterpart: its
  * EmbeddingManager.rerank_results is a placeholder (app/utils/embedder.py:834-859).  The encoder's per-token outputs are

@@ -12,6 +12,7 @@ import threading
 from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -30,6 +31,7 @@ FUSE_METHODS = {"rrf": 0, "max": 1}
 MAX_JOIN_PAIRS = 1 << 26   # mmrag_sim_join (MMRAG_MAX_JOIN_PAIRS)
 MAX_CLUSTERS = 4096   # mmrag_kmeans_assign / mmrag_cluster_sums (MMRAG_MAX_CLUSTERS)
 MAX_SCOPE_GROUPS = 64   # mmrag_scoped_topk (MMRAG_MAX_SCOPE_GROUPS)
+MAX_RECOMMEND_EXAMPLES = 16   # mmrag_recommend_topk (MMRAG_MAX_RECOMMEND_EXAMPLES)
 # mmrag_maxsim_scores (MMRAG_MAX_LATE_QUERY_TOKENS, MMRAG_MAX_LATE_DOC_TOKENS)
 MAX_LATE_QUERY_TOKENS, MAX_LATE_DOC_TOKENS = 128, 512
 MAX_LATE_PAIRS = 65535
@@ -240,6 +242,15 @@ def _declare(lib):
                                        c_void_p]
     lib.mmrag_internal_boosted_topk_ex.restype = c_int
     lib.mmrag_internal_boosted_topk_ex.argtypes = lib.mmrag_boosted_topk.argtypes + [c_int64, ctypes.c_uint]
+    # recommend top-k (csrc/recommend.hip); the _ex entry as the boosted one's
+    lib.mmrag_recommend_topk_workspace_bytes.restype = c_size_t
+    lib.mmrag_recommend_topk_workspace_bytes.argtypes = [c_int, c_int64, c_int]
+    lib.mmrag_recommend_topk.restype = c_int
+    lib.mmrag_recommend_topk.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int64, c_int,
+                                         c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.mmrag_internal_recommend_topk_ex.restype = c_int
+    lib.mmrag_internal_recommend_topk_ex.argtypes = lib.mmrag_recommend_topk.argtypes + [c_int64, ctypes.c_uint]
     # late interaction (csrc/encoder.hip token rows, csrc/maxsim.hip)
     lib.mmrag_encoder_tokens_workspace_bytes.restype = c_size_t
     lib.mmrag_encoder_tokens_workspace_bytes.argtypes = [c_void_p, c_int64, c_int, c_int]
@@ -794,6 +805,156 @@ def boosted_topk(q: torch.Tensor, rows: torch.Tensor, n: int, d: int, k: int, pr
             workspace.data_ptr(), _nbytes(workspace), _stream_ptr(dev), int(cap), int(dbg))
     _check(st, "mmrag_boosted_topk")
     return out_s, out_r, out_b
+
+
+def recommend_topk_workspace_bytes(R: int, n: int, k: int) -> int:
+    return int(lib().mmrag_recommend_topk_workspace_bytes(int(R), int(n), int(k)))
+
+
+def pack_examples(positives, negatives, dim: int, dtype: torch.dtype, device,
+                  rows: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The example block of recommend_topk from ragged lists: `positives[g]` / `negatives[g]` (negatives, or one of its
+    entries, may be None) are request g's examples, each a vector of `dim` numbers -- or, when the stored `rows`
+    [capacity, ld] are given, an int: that stored row, gathered on the device.  Returns (examples [16 R, ld] of `dtype`
+    with zero pad columns, sign int8 [16 R]) on `device`: a request's positives first (+1), then its negatives (-1),
+    the rest of its 16 slots zero with sign 0.  The one place the request rules live -- ValueError for no request, a
+    request without a positive or with more than MAX_RECOMMEND_EXAMPLES examples, a vector of the wrong length and
+    one whose norm is off by more than 1e-2 (as queries are checked)."""
+    E = MAX_RECOMMEND_EXAMPLES
+    positives = list(positives)
+    R = len(positives)
+    if R == 0:
+        raise ValueError("pack_examples: no request")
+    negatives = [None] * R if negatives is None else list(negatives)
+    if len(negatives) != R:
+        raise ValueError(f"pack_examples: {len(negatives)} negative lists for {R} requests")
+    ld = int(rows.shape[1]) if rows is not None else padded_dim(dim, dtype)
+    host = np.zeros((E * R, dim), dtype=np.float32)
+    sign = np.zeros(E * R, dtype=np.int8)
+    slots, gathered = [], []
+    for g in range(R):
+        pos = list(positives[g]) if positives[g] is not None else []
+        neg = list(negatives[g]) if negatives[g] is not None else []
+        if not pos:
+            raise ValueError(f"pack_examples: request {g} has no positive example")
+        if len(pos) + len(neg) > E:
+            raise ValueError(f"pack_examples: request {g} has {len(pos) + len(neg)} examples, at most {E}")
+        for j, e in enumerate(pos + neg):
+            at = E * g + j
+            sign[at] = 1 if j < len(pos) else -1
+            if rows is not None and isinstance(e, (int, np.integer)) and not isinstance(e, bool):
+                if not 0 <= int(e) < rows.shape[0]:
+                    raise ValueError(f"pack_examples: request {g}: stored row {int(e)} out of range")
+                slots.append(at)
+                gathered.append(int(e))
+                continue
+            v = np.asarray(e.detach().cpu() if isinstance(e, torch.Tensor) else e, dtype=np.float32).reshape(-1)
+            if v.size != dim:
+                raise ValueError(f"pack_examples: request {g}: an example holds {v.size} numbers, expected {dim}")
+            nrm = float(np.sqrt(np.dot(v.astype(np.float64), v.astype(np.float64))))
+            if not abs(nrm - 1.0) <= 1e-2:       # false for NaN too
+                raise ValueError(f"pack_examples: request {g}: example {j} has norm {nrm:.4f}; examples are unit "
+                                 f"vectors, as queries are -- L2-normalise them first")
+            host[at] = v
+    packed = torch.zeros((E * R, ld), dtype=dtype)
+    packed[:, :dim] = torch.from_numpy(host).to(dtype)
+    dev = torch.device(device)
+    if dev.type == "cpu":
+        if gathered:
+            packed[slots] = rows[gathered].to(dtype)
+        return packed, torch.from_numpy(sign)
+    examples = _pinned_to_device(packed, dev)
+    if gathered:
+        examples[_pinned_to_device(torch.tensor(slots, dtype=torch.int64), dev)] = \
+            rows[_pinned_to_device(torch.tensor(gathered, dtype=torch.int64), dev)]
+    return examples, _pinned_to_device(torch.from_numpy(sign), dev)
+
+
+def check_recommend_request(who: str, sign, neg_weight, R: int):
+    """HOST sign [16 R] and weights [R] (or one number) of recommend_topk, checked: (int8 [16 R], float32 [R]); None
+    passes through (a device tensor the caller vouches for).  ValueError for a wrong length, a sign outside
+    {-1, 0, 1}, a request without a positive and a non-finite or negative weight."""
+    E = MAX_RECOMMEND_EXAMPLES
+    s = w = None
+    if sign is not None:
+        s = np.asarray(sign.cpu() if isinstance(sign, torch.Tensor) else sign).reshape(-1)
+        if s.size != E * R:
+            raise ValueError(f"{who}: sign holds {s.size} entries, expected {E} per request = {E * R}")
+        if not np.isin(s, (-1, 0, 1)).all():
+            raise ValueError(f"{who}: a sign must be -1, 0 or 1")
+        s = s.astype(np.int8)
+        lacking = np.nonzero(~(s.reshape(R, E) > 0).any(axis=1))[0]
+        if lacking.size:
+            raise ValueError(f"{who}: request {int(lacking[0])} has no positive example")
+    if neg_weight is not None:
+        w = np.asarray(neg_weight.cpu() if isinstance(neg_weight, torch.Tensor) else neg_weight,
+                       dtype=np.float64).reshape(-1)
+        if np.ndim(neg_weight) == 0:                  # a number, or a 0-d array / tensor: the same for every request
+            w = np.full(R, w[0])
+        if w.size != R:
+            raise ValueError(f"{who}: neg_weight holds {w.size} entries, expected {R}")
+        if not (np.isfinite(w).all() and (w >= 0).all()):
+            raise ValueError(f"{who}: neg_weight must be finite and >= 0")
+        w = w.astype(np.float32)
+    return s, w
+
+
+def recommend_topk(examples: torch.Tensor, sign, neg_weight, rows: torch.Tensor, n: int, d: int, k: int,
+                   alive_bits: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                   row_offset: int = 0, cap: int = 0, dbg: int = 0, want_explain: bool = True, checked: bool = False):
+    """Top-k of each request over the first n of `rows` [cap, ld] by "more like these, less like those"
+    (include/mmrag.h mmrag_recommend_topk): `examples` [16 R, ld] and `sign` [16 R] as pack_examples returns them,
+    final = fmaf(-w, max(neg, 0), pos) inside one exact scan.  `sign` / `neg_weight` (a number, or one per request)
+    are checked on the host and uploaded; device tensors (int8 / float32) are used as they are after a copy of them was
+    checked, which waits for the stream -- unless `checked`: pack_examples and check_recommend_request made them
+    (VectorIndex).  Returns (scores [R, k] float32 = final descending, rows [R, k] int64 + row_offset, pos, neg [R, k]
+    float32, pos_arg, neg_arg [R, k] int32 = the slot that gave them, -1 for none), (-inf, -1, 0, 0, -1, -1) padded;
+    the last four are None without `want_explain`.  Raises ValueError for a request without a positive, a sign outside
+    {-1, 0, 1}, a non-finite or negative weight, a wrong length and k outside 1..MAX_K_DEEP, before anything is
+    launched.  `cap`, `dbg` (tests only): fewer slots; dbg & 1 = no bound passes."""
+    E = MAX_RECOMMEND_EXAMPLES
+    _dev_check(examples, rows, alive_bits)
+    _check_q_rows("recommend_topk", examples, rows, n, other="rows")
+    _check_stored_rows("recommend_topk", rows)
+    n, k = int(n), int(k)
+    if examples.shape[0] == 0 or examples.shape[0] % E:
+        raise ValueError(f"recommend_topk: examples hold {examples.shape[0]} rows, expected {E} per request")
+    R, ld = examples.shape[0] // E, examples.shape[1]
+    if not 1 <= k <= MAX_K_DEEP:
+        raise ValueError(f"recommend_topk: k={k} outside 1..{MAX_K_DEEP}")
+    _check_alive("recommend_topk", alive_bits, n, rows)
+    dev = examples.device
+    sign_dev = sign if isinstance(sign, torch.Tensor) and sign.is_cuda else None
+    w_dev = neg_weight if isinstance(neg_weight, torch.Tensor) and neg_weight.is_cuda else None
+    if sign_dev is not None and (sign_dev.dtype != torch.int8 or sign_dev.numel() != E * R
+                                 or not sign_dev.is_contiguous() or sign_dev.device != dev):
+        raise ValueError(f"recommend_topk: sign must be a contiguous int8 tensor of {E * R} entries on the rows' device")
+    if w_dev is not None and (w_dev.dtype != torch.float32 or w_dev.numel() != R or not w_dev.is_contiguous()
+                              or w_dev.device != dev):
+        raise ValueError(f"recommend_topk: neg_weight must be a contiguous float32 tensor of {R} entries on the rows' "
+                         f"device")
+    s_host, w_host = check_recommend_request("recommend_topk", None if checked and sign_dev is not None else sign,
+                                             None if checked and w_dev is not None else neg_weight, R)
+    if sign_dev is None:
+        sign_dev = _pinned_to_device(torch.from_numpy(s_host), dev)
+    if w_dev is None:
+        w_dev = _pinned_to_device(torch.from_numpy(w_host), dev)
+    need = recommend_topk_workspace_bytes(R, n, k)
+    if workspace is None or _nbytes(workspace) < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    out_s, out_r = _topk_out(R, k, dev)
+    expl = [None] * 4
+    if want_explain:
+        expl = [torch.empty((R, k), dtype=t, device=dev)
+                for t in (torch.float32, torch.float32, torch.int32, torch.int32)]
+    with torch.cuda.device(dev):
+        st = lib().mmrag_internal_recommend_topk_ex(
+            examples.data_ptr(), sign_dev.data_ptr(), w_dev.data_ptr(), rows.data_ptr(), R, n, int(d), ld,
+            _TORCH2DT[examples.dtype], k, int(row_offset), alive_bits.data_ptr() if alive_bits is not None else None,
+            out_s.data_ptr(), out_r.data_ptr(), *[t.data_ptr() if t is not None else None for t in expl],
+            workspace.data_ptr(), _nbytes(workspace), _stream_ptr(dev), int(cap), int(dbg))
+    _check(st, "mmrag_recommend_topk")
+    return (out_s, out_r, *expl)
 
 
 def check_late_tables(q_rows: int, d_rows: int, q_start, q_len, d_start, d_len, pair_q, pair_d) -> Tuple[int, int, int]:

@@ -118,6 +118,10 @@ class Settings:
         default_factory=lambda: float(os.getenv("MMRAG_BOOST_HALF_LIFE_DAYS", "30")))
     MMRAG_BOOST_REFRESH_S: float = field(default_factory=lambda: float(os.getenv("MMRAG_BOOST_REFRESH_S", "3600")))
     MMRAG_BOOST_TIME_KEY: str = field(default_factory=lambda: os.getenv("MMRAG_BOOST_TIME_KEY", ""))
+    # recommend retrieval (VectorIndex.recommend_query, csrc/recommend.hip): the default weight w >= 0 of the penalty in
+    # final = pos - w * max(neg, 0) when a request names negatives and gives none
+    MMRAG_RECOMMEND_NEGATIVE_WEIGHT: float = field(
+        default_factory=lambda: float(os.getenv("MMRAG_RECOMMEND_NEGATIVE_WEIGHT", "1.0")))
     # topic clustering (VectorIndex.cluster, csrc/kmeans.hip): the default number of topics of cluster() / GET /topics;
     # 0 (default) = automatic, auto_topics(live rows); else 1 .. 4096
     MMRAG_TOPICS: int = field(default_factory=lambda: int(os.getenv("MMRAG_TOPICS", "0")))

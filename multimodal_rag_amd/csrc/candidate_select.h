@@ -20,6 +20,8 @@ struct CandWs {
     size_t off_cnt, off_one_cnt, off_floats, off_bs, off_br, off_os, off_or, total;
 };
 
+// The B counters stay first (off_cnt == 0) and the driver leaves the main pass's counts in them: the re-run has its own
+// counter.  tools/boost_bench.py and tools/recommend_bench.py read the survivors per query from there.
 // [B counters | the re-run's counter | B floats, if asked for | B x cap scores | B x cap rows | n scores | n rows],
 // every block on a 256-byte boundary
 inline CandWs candidate_ws_layout(int B, long long cap, long long n, bool per_query_floats) {

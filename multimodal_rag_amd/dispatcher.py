@@ -17,21 +17,26 @@ BatchFn = Callable[[List[str], int, Optional[Dict]], Awaitable[List[Dict[str, An
 ScopedFn = Callable[[List[str], int, List[List[str]]], Awaitable[List[Dict[str, Any]]]]
 # (texts, k, filter, the batch's boost spec): ONE batched encode and ONE boosted search (csrc/boosted.hip)
 BoostedFn = Callable[[List[str], int, Optional[Dict], Any], Awaitable[List[Dict[str, Any]]]]
+# (requests, k, filter): ONE encode of every request's texts and ONE recommend search (csrc/recommend.hip).  An 'error'
+# dict it returns is the request's own fault (a ValueError for its caller); anything else it raises
+RecommendFn = Callable[[List[Dict[str, Any]], int, Optional[Dict]], Awaitable[List[Dict[str, Any]]]]
 
 
 class QueryDispatcher:
     def __init__(self, batch_fn: BatchFn, max_batch: int = 256, max_wait_ms: float = 2.0, idle_ms: float = 0.25,
-                 scoped_fn: Optional[ScopedFn] = None, boosted_fn: Optional[BoostedFn] = None):
+                 scoped_fn: Optional[ScopedFn] = None, boosted_fn: Optional[BoostedFn] = None,
+                 recommend_fn: Optional[RecommendFn] = None):
         self.batch_fn = batch_fn
         self.scoped_fn = scoped_fn
         self.boosted_fn = boosted_fn
+        self.recommend_fn = recommend_fn
         self.max_batch = max_batch
         self.max_wait = max_wait_ms / 1e3
         # a batch also closes when nothing new has arrived for `idle_ms`: with a fixed set of callers that all come back
         # right after their answers, waiting out the whole window for requests that cannot exist is a quarter of the cycle
         self.idle = idle_ms / 1e3
-        # (text, k, filter, the caller's future, doc_ids, boost spec)
-        self._queue: "asyncio.Queue[Tuple[str, int, Optional[Dict], asyncio.Future, Optional[List[str]], Any]]" = \
+        # (text, k, filter, the caller's future, doc_ids, boost spec, recommend request)
+        self._queue: "asyncio.Queue[Tuple[str, int, Optional[Dict], asyncio.Future, Optional[List[str]], Any, Any]]" = \
             asyncio.Queue()
         self._task: Optional[asyncio.Task] = None
         self.stats = {"requests": 0, "batches": 0, "max_batch_seen": 0}
@@ -50,20 +55,26 @@ class QueryDispatcher:
             self._task = None
 
     async def submit(self, text: str, n_results: int = 5, filter_dict: Optional[Dict] = None,
-                     doc_ids: Optional[List[str]] = None, boost: Any = None) -> Dict[str, Any]:
-        """`boost`: a boost spec (an object with a canonical `batch_key()`; needs a `boosted_fn`): the request is ranked with
+                     doc_ids: Optional[List[str]] = None, boost: Any = None,
+                     recommend: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        """`recommend`: a request of positive and negative examples (EmbeddingManager.recommend's dict; needs a
+        `recommend_fn`; `text` is not read): requests of one k -- and one filter, which is one alive bitmap per scan --
+        share one batch whatever their examples.
+        `boost`: a boost spec (an object with a canonical `batch_key()`; needs a `boosted_fn`): the request is ranked with
         that score prior, and requests of one k, filter and spec key share one batch.
         `doc_ids`: answer from these documents only.  With a `scoped_fn`, requests that carry doc_ids and no
         filter_dict share one batch per k whatever their documents; without one (or next to a filter_dict) the
         restriction becomes part of the filter and the request is grouped by it like any other."""
         if boost is not None and (self.boosted_fn is None or doc_ids is not None):
             raise ValueError("a boosted request needs a boosted_fn and takes no doc_ids")
+        if recommend is not None and (self.recommend_fn is None or doc_ids is not None or boost is not None):
+            raise ValueError("a recommend request needs a recommend_fn and takes neither doc_ids nor a boost")
         self.start()
         if doc_ids is not None and (self.scoped_fn is None or filter_dict is not None):
             only = {"doc_id": {"$in": list(doc_ids)}}
             filter_dict, doc_ids = ({"$and": [filter_dict, only]} if filter_dict else only), None
         fut: asyncio.Future = asyncio.get_running_loop().create_future()
-        await self._queue.put((text, n_results, filter_dict, fut, doc_ids, boost))
+        await self._queue.put((text, n_results, filter_dict, fut, doc_ids, boost, recommend))
         return await fut
 
     async def _run(self):
@@ -85,10 +96,12 @@ class QueryDispatcher:
                 except asyncio.TimeoutError:
                     break
             # one kernel batch per (k, filter) group; the requests with doc_ids are one group per k, the boosted ones
-            # one per (k, filter, spec key)
+            # one per (k, filter, spec key), the recommend ones one per (k, filter)
             groups: Dict[Any, List[int]] = {}
-            for i, (_, k, flt, _, docs, boost) in enumerate(batch):
-                if boost is not None:
+            for i, (_, k, flt, _, docs, boost, rec) in enumerate(batch):
+                if rec is not None:
+                    key = ("recommend", k, repr(flt))
+                elif boost is not None:
                     key = ("boosted", k, repr(flt), boost.batch_key())
                 elif docs is not None:
                     key = ("scoped", k)
@@ -98,7 +111,9 @@ class QueryDispatcher:
             for key, idxs in groups.items():
                 k, flt = batch[idxs[0]][1], batch[idxs[0]][2]
                 try:
-                    if key[0] == "boosted":
+                    if key[0] == "recommend":
+                        results = await self.recommend_fn([batch[i][6] for i in idxs], k, flt)
+                    elif key[0] == "boosted":
                         results = await self.boosted_fn([batch[i][0] for i in idxs], k, flt, batch[idxs[0]][5])
                     elif key[0] == "scoped":
                         results = await self.scoped_fn([batch[i][0] for i in idxs], k, [batch[i][4] for i in idxs])
@@ -109,7 +124,10 @@ class QueryDispatcher:
                         if fut.done():
                             continue
                         if isinstance(res, dict) and "error" in res:
-                            fut.set_exception(ValueError(res["error"]) if "empty" in res["error"]
+                            # (a recommend_fn raises what is not the request's own fault: its error dicts are all
+                            # broken request rules and unknown ids)
+                            fut.set_exception(ValueError(res["error"])
+                                              if "empty" in res["error"] or key[0] == "recommend"
                                               else RuntimeError(res["error"]))
                         else:
                             fut.set_result(res)

@@ -31,6 +31,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import tracing
+from ._native import MAX_RECOMMEND_EXAMPLES
 from .config import settings
 from .engines import CLIP_MODEL_NAMES, ClipEngine, HipEngine, _is_clip_dir, load_item_image  # noqa: F401 (re-exported)
 from .hostutil import CountingLRU, call_with_retry, load_hostrows
@@ -43,6 +44,7 @@ HYBRID_KEYS = RESULT_KEYS + ("hybrid_scores", "lexical_scores")
 MMR_KEYS = RESULT_KEYS + ("mmr_scores",)
 FUSED_KEYS = RESULT_KEYS + ("fused_scores", "matched_queries", "best_query")
 BOOST_KEYS = RESULT_KEYS + ("scores", "boosts")
+RECOMMEND_KEYS = RESULT_KEYS + ("scores", "penalties", "matched", "repelled_by")
 _HOSTROWS = load_hostrows()
 _COLLECTION_NOTE = {"description": "Multi-modal RAG embeddings"}
 # what a retrieval mode needs of the collection: (method, the error of a collection that lacks it)
@@ -55,6 +57,8 @@ _NEEDS_DEDUP = ("near_duplicates", "near-duplicate detection needs a single-GPU 
 _NEEDS_CLUSTERING = ("cluster", "topic clustering needs a single-GPU collection (VectorIndex) with full-precision rows")
 _NEEDS_BOOST = ("boosted_query", "boosted retrieval needs a single-GPU collection (VectorIndex) with full-precision "
                                  "rows")
+_NEEDS_RECOMMEND = ("recommend_query", "recommend retrieval needs a single-GPU collection (VectorIndex) with "
+                                        "full-precision rows")
 _boost_warned = False    # "this collection cannot boost": once per process
 _dedup_warned = False    # "MMRAG_DEDUP_THRESHOLD is set but this collection cannot de-duplicate": once per process
 # the answer of a batch's query that could not be answered, before its 'error' (copied for every such query)
@@ -62,6 +66,7 @@ _EMPTY = {key: [] for key in RESULT_KEYS}
 _EMPTY_MMR = {key: [] for key in MMR_KEYS}
 _EMPTY_FUSED = {key: [] for key in FUSED_KEYS}
 _EMPTY_BOOST = {key: [] for key in BOOST_KEYS}
+_EMPTY_RECOMMEND = {key: [] for key in RECOMMEND_KEYS}
 _EMPTY_GROUPED = {**_EMPTY, "groups": [], "exhaustive": False, "fetch_k": 0}
 
 
@@ -326,9 +331,14 @@ class EmbeddingManager:
         def boosted(texts, n_results, filter_dict, spec):
             return self.batch_boosted_query(texts, n_results=n_results, filter_dict=filter_dict, boost=spec)
 
+        def recommend(requests, n_results, filter_dict):      # a failing engine raises: only a request's own fault
+            return self.batch_recommend(requests, n_results=n_results, filter_dict=filter_dict,     # is an 'error'
+                                        raise_engine_errors=True)
+
         self._dispatcher = QueryDispatcher(self.batch_query, max_batch=max_batch, max_wait_ms=max_wait_ms,
                                            scoped_fn=scoped if self.supports_scoped() else None,
-                                           boosted_fn=boosted if self.supports_boost() else None)
+                                           boosted_fn=boosted if self.supports_boost() else None,
+                                           recommend_fn=recommend if self.supports_recommend() else None)
         return self._dispatcher
 
     _INCLUDE = ["metadatas", "documents", "distances"]
@@ -535,6 +545,149 @@ class EmbeddingManager:
         that cannot be answered gets a dict with empty lists and an 'error' message."""
         return await self._batch("Batch boosted query", _NEEDS_BOOST, _EMPTY_BOOST, self._answer_boosted, queries,
                                  n_results, filter_dict, self._boost_spec(boost))
+
+    # ---- recommend retrieval: positive and negative examples (VectorIndex.recommend_query, csrc/recommend.hip) ----
+    def supports_recommend(self) -> bool:
+        """True when the collection can search by examples (a single-GPU VectorIndex with full-precision rows; not a
+        sharded engine or one without the method: recommend() raises ValueError there)"""
+        return self.collection is None or (hasattr(self.collection, "recommend_query") and self._has_full_rows())
+
+    @staticmethod
+    def _recommend_request(query_text=None, like=(), unlike=(), unlike_texts=(), negative_weight=None) -> Dict[str, Any]:
+        """one request of recommend(), checked: the question (if given) is one positive, `like` / `unlike` are stored
+        ids, `unlike_texts` are encoded; at least one of query_text and like, at most 16 examples in all"""
+        if isinstance(like, str) or isinstance(unlike, str) or isinstance(unlike_texts, str):
+            raise ValueError("like, unlike and unlike_texts are lists")
+        text = query_text if query_text and query_text.strip() else None
+        req = {"query_text": text, "like": list(like or ()), "unlike": list(unlike or ()),
+               "unlike_texts": list(unlike_texts or ()), "negative_weight": negative_weight}
+        if query_text is not None and text is None:
+            raise ValueError("Query text cannot be empty")
+        if text is None and not req["like"]:
+            raise ValueError("recommend needs a question or at least one `like` id")
+        if not all(isinstance(x, str) and x for x in req["like"] + req["unlike"]):
+            raise ValueError("like and unlike hold the ids of stored items")
+        if not all(isinstance(x, str) and x.strip() for x in req["unlike_texts"]):
+            raise ValueError("unlike_texts holds non-empty texts")
+        total = (text is not None) + len(req["like"]) + len(req["unlike"]) + len(req["unlike_texts"])
+        if total > MAX_RECOMMEND_EXAMPLES:
+            raise ValueError(f"a recommend request takes at most {MAX_RECOMMEND_EXAMPLES} examples in all (got {total})")
+        if negative_weight is not None:
+            w = float(negative_weight)
+            if not (math.isfinite(w) and w >= 0.0):
+                raise ValueError("negative_weight must be finite and >= 0")
+        return req
+
+    def _answer_recommend(self, requests: Sequence[Dict[str, Any]], n_results: int,
+                          filter_dict: Optional[Dict]) -> List[Dict[str, Any]]:
+        """blocking, one worker thread: the questions and the unwanted texts of ALL requests in ONE encoder batch, then
+        ONE collection.recommend_query (one scan).  A request that names an id no stored item has gets an 'error'
+        dict; the others are answered."""
+        if not (hasattr(self.collection, "recommend_query") and self._has_full_rows()):
+            raise ValueError(_NEEDS_RECOMMEND[1])
+        named = sorted({i for r in requests for i in r["like"] + r["unlike"]})
+        known = set(self.collection.get(ids=named, include=[])["ids"]) if named else set()
+        out: List[Optional[Dict[str, Any]]] = [None] * len(requests)
+        live = []
+        for at, r in enumerate(requests):
+            missing = [i for i in r["like"] + r["unlike"] if i not in known]
+            if missing:
+                out[at] = {**copy.deepcopy(_EMPTY_RECOMMEND), "error": f"Item not found: {missing[0]}"}
+            else:
+                live.append(at)
+        if not live:
+            return out  # type: ignore[return-value]
+        texts: List[str] = []
+        for at in live:
+            r = requests[at]
+            texts.extend(([r["query_text"]] if r["query_text"] is not None else []) + r["unlike_texts"])
+        emb = self._embed(texts) if texts else np.zeros((0, 0), np.float32)
+        pos, neg, weights, at_text = [], [], [], 0
+        default_w = settings.MMRAG_RECOMMEND_NEGATIVE_WEIGHT
+        for at in live:
+            r = requests[at]
+            mine_pos: List[Any] = []
+            if r["query_text"] is not None:
+                mine_pos.append(emb[at_text])
+                at_text += 1
+            pos.append(mine_pos + r["like"])
+            neg.append(r["unlike"] + [emb[at_text + j] for j in range(len(r["unlike_texts"]))])
+            at_text += len(r["unlike_texts"])
+            weights.append(float(default_w if r["negative_weight"] is None else r["negative_weight"]))
+        res = self.collection.recommend_query(pos, neg, n_results=n_results, negative_weight=weights,
+                                              where=filter_dict, include=self._INCLUDE)
+        for j, at in enumerate(live):
+            r = requests[at]
+            hit = {key: res[key][j] for key in RECOMMEND_KEYS}
+            # an example that is a vector is named by what it was: the question, or the unwanted text
+            has_q = r["query_text"] is not None
+            hit["matched"] = ["query" if has_q and m == "vector:0" else m for m in hit["matched"]]
+            n_ids = len(r["unlike"])
+            hit["repelled_by"] = [r["unlike_texts"][int(m[7:]) - n_ids] if isinstance(m, str) and m.startswith("vector:")
+                                  and int(m[7:]) >= n_ids else m for m in hit["repelled_by"]]
+            out[at] = hit
+        return out  # type: ignore[return-value]
+
+    async def recommend(self, query_text: Optional[str] = None, like: Sequence[str] = (), unlike: Sequence[str] = (),
+                        unlike_texts: Sequence[str] = (), n_results: int = 5, filter_dict: Optional[Dict] = None,
+                        negative_weight: Optional[float] = None) -> Dict[str, Any]:
+        """"More like these, less like those" (VectorIndex.recommend_query): the question, if given, is one positive
+        example, `like` / `unlike` are ids of stored items, `unlike_texts` ("jaguar, NOT the car") are encoded in the
+        same encoder batch as the question.  At least one of query_text and like; at most 16 examples in all.  A hit x
+        scores pos - w * max(neg, 0) (pos / neg: its best cosine to a positive / negative example; w: negative_weight,
+        default MMRAG_RECOMMEND_NEGATIVE_WEIGHT), formed inside one exact scan.  One result dict with the keys of
+        query() plus `scores` (descending), `penalties`, `matched` ("query" or the id of the positive that scored best)
+        and `repelled_by` (the id or the text of the negative that fired, else None); `distances` are 1 - pos and not
+        ascending; the stored items named are not returned.  ValueError for a malformed request, an unknown id and a
+        collection that cannot (supports_recommend).  With dynamic batching on, concurrent callers of one n_results
+        and filter share one encode and one search whatever their examples."""
+        req = self._recommend_request(query_text, like, unlike, unlike_texts, negative_weight)
+        await self._ready()
+        if not self.supports_recommend():
+            raise ValueError(_NEEDS_RECOMMEND[1])
+        if self._dispatcher is not None and self._dispatcher.recommend_fn is not None:
+            return await self._dispatcher.submit("", n_results, filter_dict, None, recommend=req)
+        try:
+            hit = (await self._engine_call("Recommend", self._answer_recommend, [req], n_results, filter_dict))[0]
+        except Exception as e:
+            logger.error("Recommend failed: %s", e, exc_info=True)
+            raise
+        if "error" in hit:
+            raise ValueError(hit["error"])
+        self.stats["total_queries"] += 1
+        return hit
+
+    async def batch_recommend(self, requests: Sequence[Dict[str, Any]], n_results: int = 5,
+                              filter_dict: Optional[Dict] = None, raise_engine_errors: bool = False) -> List[Dict[str, Any]]:
+        """recommend() for a list of requests (dicts with recommend()'s keys query_text, like, unlike, unlike_texts,
+        negative_weight): ONE encoder batch and ONE search for all of them; a request that cannot be answered gets a
+        dict with empty lists and an 'error' message.  `raise_engine_errors` (the dispatcher): only a request's own
+        fault -- a broken rule, an id no stored item has -- becomes such a dict; a failure of the encoder or the search
+        is raised, so that it is not mistaken for a bad request."""
+        await self._ready()
+        answers: List[Optional[Dict[str, Any]]] = [None] * len(requests)
+        checked, live = [], []
+        for at, r in enumerate(requests):
+            try:
+                checked.append(self._recommend_request(**{k: r.get(k) for k in ("query_text", "like", "unlike",
+                                                                                 "unlike_texts", "negative_weight")
+                                                          if r.get(k) is not None}))
+                live.append(at)
+            except (ValueError, TypeError) as e:
+                answers[at] = {**copy.deepcopy(_EMPTY_RECOMMEND), "error": str(e)}
+        if live:
+            try:
+                hits = await self._engine_call("Batch recommend", self._answer_recommend, checked, n_results, filter_dict)
+                for at, hit in zip(live, hits):
+                    answers[at] = hit
+                self.stats["total_queries"] += sum("error" not in h for h in hits)
+            except Exception as e:
+                logger.error("Batch recommend failed: %s", e)
+                if raise_engine_errors:
+                    raise
+                for at in live:
+                    answers[at] = {**copy.deepcopy(_EMPTY_RECOMMEND), "error": str(e)}
+        return answers  # type: ignore[return-value]
 
     def supports_hybrid(self) -> bool:
         """True when the collection can answer hybrid_query (a single-GPU VectorIndex; not the sharded serving path)"""

@@ -231,6 +231,7 @@ class VectorIndex:
         self._lex = None   # lexical.LexicalIndex once enable_lexical() ran (lazily: first lexical / hybrid query)
         self._groups: Dict[str, Dict[str, Any]] = {}   # metadata key -> group column state once enable_grouping(key) ran
         self._boosted_ws: Optional[torch.Tensor] = None   # workspace of the boosted search, reused
+        self._recommend_ws: Optional[torch.Tensor] = None   # workspace of the recommend search, reused
         self._added_at = np.full(cap, np.nan, dtype=np.float64)   # when each row in use was added (NaN = unknown)
         self._priors: Dict[str, Any] = {}     # set_prior names -> a device float32 [capacity] column, or a BoostSpec
         # spec columns by (canonical JSON of the spec, floored now) -> {"spec", "now", "col"}; at most MAX_SPEC_COLUMNS
@@ -1494,6 +1495,124 @@ class VectorIndex:
                 out["distances"] = None
             out["scores"] = [row[:m] for row, m in zip(scores.cpu().tolist(), lens)]
             out["boosts"] = [row[:m] for row, m in zip(boosts.cpu().tolist(), lens)]
+            return out
+
+    # ------------------------------------------------------------------ recommend (positive / negative examples) ----
+    @staticmethod
+    def _example_lists(positive, negative):
+        """`positive` / `negative` of recommend_search: one list of entries per request, as lists.  ValueError for
+        anything else: an id or a vector where a request's list belongs is not guessed at"""
+        def per_request(x, what):
+            if x is None or isinstance(x, (str, np.ndarray, torch.Tensor)) or not hasattr(x, "__iter__"):
+                raise ValueError(f"recommend: `{what}` takes one list of ids and vectors per request")
+            return list(x)
+
+        pos = [per_request(x, "positive") for x in per_request(positive, "positive")]
+        if negative is None:
+            return pos, [[] for _ in pos]
+        return pos, [[] if x is None else per_request(x, "negative") for x in per_request(negative, "negative")]
+
+    def _launch_recommend(self, positive, negative, n_results: int, negative_weight, where, extra_depth: bool):
+        """enqueue the recommend search (caller holds the lock): (the six device tensors of recommend_topk, the
+        requests' positive and negative entries with ids replaced by their int rows, the weights float32 [R]).
+        `extra_depth`: search n_results + the largest number of stored rows one request names, capped by MAX_K_DEEP"""
+        from .config import settings
+
+        self._need_plane("recommend_query")
+        k = int(n_results)
+        if not 1 <= k <= _native.MAX_K_DEEP:
+            raise ValueError(f"n_results must be in 1..{_native.MAX_K_DEEP} for a recommend search")
+        pos, neg = self._example_lists(positive, negative)
+        if not pos:
+            raise ValueError("recommend: no request")
+        if len(neg) != len(pos):
+            raise ValueError(f"recommend: {len(neg)} negative lists for {len(pos)} requests")
+
+        def resolve(entries):
+            out = []
+            for e in entries or []:
+                if isinstance(e, str):
+                    r = self._row_of.get(e)      # live rows only: a delete drops the id from the map
+                    if r is None:
+                        raise ValueError(f"recommend: no stored item has the id {e!r}")
+                    out.append(int(r))
+                elif isinstance(e, (int, np.integer)) or np.ndim(e) != 1:
+                    # (a row number would reach pack_examples' gather without the tombstone check above)
+                    raise ValueError("recommend: an example is a vector or the id of a stored item")
+                else:
+                    out.append(e)
+            return out
+
+        pos_r, neg_r = [resolve(x) for x in pos], [resolve(x) for x in neg]
+        examples, sign = _native.pack_examples(pos_r, neg_r, self.dim, self._full.dtype, self.device, rows=self._full)
+        R = len(pos_r)
+        w = settings.MMRAG_RECOMMEND_NEGATIVE_WEIGHT if negative_weight is None else negative_weight
+        _, w = _native.check_recommend_request("recommend", None, w, R)
+        if extra_depth:
+            named = max(sum(isinstance(e, int) for e in p_ + n_) for p_, n_ in zip(pos_r, neg_r))
+            k = min(k + named, _native.MAX_K_DEEP)
+        need = _native.recommend_topk_workspace_bytes(R, self._n, k)
+        out = _native.recommend_topk(examples, sign, w, self._full, self._n, self.dim, k, checked=True,
+                                     alive_bits=self._where_bits(where),
+                                     workspace=self._workspace("_recommend_ws", need))
+        return out, pos_r, neg_r, w
+
+    def recommend_search(self, positive, negative=None, n_results: int = 10, negative_weight=None,
+                         where: Optional[Dict[str, Any]] = None):
+        """Raw device search by examples, "more like these, less like those" (csrc/recommend.hip, include/mmrag.h
+        mmrag_recommend_topk): `positive` / `negative` hold one list per request,
+        each entry a unit vector or the id of a stored row, at most 16 per request and at least one positive.  A row x
+        scores final = pos - w * max(neg, 0), pos / neg the largest cosine to a positive / negative example, formed
+        INSIDE one exact scan: with negatives the winners are often far down the positive ranking, which no re-sort of
+        a finished list finds.  Stored rows are gathered on the device.  Returns (scores [R, k] float32 = final
+        descending, rows [R, k] int64, -1 = none, pos, neg [R, k] float32, pos_slot, neg_slot [R, k] int32: the
+        request's example that gave them, positives counted first, -1 = none).  The examples themselves are NOT
+        excluded here (recommend_query does that).  `negative_weight`: w, a number or one per request, default
+        MMRAG_RECOMMEND_NEGATIVE_WEIGHT.  `where` narrows the batch and tombstones are honoured; a float8_e4m3fn
+        collection is searched on its re-scoring plane (capacity mode raises ValueError); an unknown or deleted id
+        raises ValueError."""
+        with self._lock:
+            return self._launch_recommend(positive, negative, n_results, negative_weight, where, False)[0]
+
+    def recommend_query(self, positive, negative=None, n_results: int = 10, negative_weight=None,
+                        where: Optional[Dict[str, Any]] = None,
+                        include: Sequence[str] = ("metadatas", "documents", "distances"),
+                        exclude_examples: bool = True) -> Dict[str, Any]:
+        """query() ranked by recommend_search: the Chroma-shaped dict of query() plus `scores` (the finals, descending),
+        `penalties` (w * max(neg, 0)), `matched` (per hit, the positive example that scored best: the stored id, or
+        "vector:<i>" for entry i of the request's positives) and `repelled_by` (the same for the negatives, None when
+        none fired).  `distances` are 1 - pos and therefore NOT ascending.  With `exclude_examples` the stored rows a
+        request names are not returned: the search goes n_results + their number deep (at most MAX_K_DEEP) and they are
+        dropped on the host, as get_similar_documents drops its source."""
+        with self._lock, stage("search"):
+            out_dev, pos_r, neg_r, w = self._launch_recommend(positive, negative, n_results, negative_weight, where,
+                                                              exclude_examples)
+            tables = self._tables()
+            emb_src = self._full if "embeddings" in include else None
+        with stage("collect"):
+            scores, rows, p_dot, n_dot, p_arg, n_arg = [t.cpu().tolist() for t in out_dev]
+            keys = ("ids", "distances", "metadatas", "documents", "embeddings")
+            out: Dict[str, Any] = {key: [] if key == "ids" or key in include else None for key in keys}
+            out.update(scores=[], penalties=[], matched=[], repelled_by=[])
+
+            def name(entries, slot):
+                e = entries[slot]
+                return tables[0][e] if isinstance(e, int) else f"vector:{slot}"
+
+            for g, (p_ent, n_ent) in enumerate(zip(pos_r, neg_r)):
+                named = {e for e in p_ent + n_ent if isinstance(e, int)} if exclude_examples else set()
+                keep = [j for j, r in enumerate(rows[g]) if r >= 0 and r not in named][: int(n_results)]
+                hit = [rows[g][j] for j in keep]
+                self._append_hits(out, tables, hit, include)
+                if out["distances"] is not None:
+                    out["distances"].append([1.0 - p_dot[g][j] for j in keep])
+                if out["embeddings"] is not None:
+                    out["embeddings"].append(self._fetch(hit, emb_src))
+                out["scores"].append([scores[g][j] for j in keep])
+                out["penalties"].append([float(w[g]) * max(n_dot[g][j], 0.0) for j in keep])
+                out["matched"].append([name(p_ent, p_arg[g][j]) for j in keep])
+                out["repelled_by"].append([name(n_ent, n_arg[g][j] - len(p_ent))
+                                           if n_arg[g][j] >= 0 and n_dot[g][j] > 0 else None for j in keep])
             return out
 
     # ------------------------------------------------------------------ multi-query fusion ----

@@ -32,6 +32,11 @@ logger = logging.getLogger(__name__)
 NO_DOCS_ANSWER = "Không tìm thấy tài liệu liên quan. Vui lòng upload tài liệu hoặc thử câu hỏi khác."  # api.py:342
 
 
+# the examples of a recommend request: ids of stored items, texts of unwanted topics (16 examples in all at most)
+ExampleIds = Annotated[List[Annotated[str, Field(min_length=1, max_length=200)]], Field(min_length=1, max_length=16)]
+ExampleTexts = Annotated[List[Annotated[str, Field(min_length=1, max_length=2000)]], Field(min_length=1, max_length=16)]
+
+
 class QueryRequest(BaseModel):  # api.py:161-164
     query: str = Field(..., min_length=1, max_length=2000)
     top_k: int = Field(5, ge=1, le=20)
@@ -88,6 +93,27 @@ class QueryRequest(BaseModel):  # api.py:161-164
     # `score`; `relevance_score` stays the cosine.  With `rerank`, max(top_k, MMRAG_RERANK_CANDIDATES) boosted hits are
     # re-ranked.  Not combined with `hybrid`, `mmr`, `group_by_document`, `variants` / `expand` or `doc_ids` yet
     boost: Optional[Union[StrictBool, Dict[str, Any]]] = None
+    # not in the reference: recommend retrieval (EmbeddingManager.recommend), "about X, but not Y" and "more like these,
+    # less like those".  `like` / `unlike`: ids of stored items (the `doc_id` of a source) used as positive / negative
+    # examples next to the question; `not`: texts of unwanted topics, encoded with the question.  A hit scores
+    # pos - w * max(neg, 0) inside one exact scan (w: `negative_weight`, default MMRAG_RECOMMEND_NEGATIVE_WEIGHT); each
+    # source then carries its `score`, `penalty`, `matched` and `repelled_by`, and `relevance_score` stays the best
+    # positive cosine.  At most 16 examples in all.  Not combined with `mmr`, `group_by_document`, `boost`, `variants`
+    # / `expand`, `doc_ids` or `hybrid` yet
+    like: Optional[ExampleIds] = None
+    unlike: Optional[ExampleIds] = None
+    not_: Optional[ExampleTexts] = Field(None, alias="not")
+    negative_weight: Optional[float] = Field(None, ge=0.0, le=1000.0)
+
+
+class RecommendRequest(BaseModel):
+    """POST /recommend, the "more like this" button: stored items as examples, no question and no generator call"""
+    like: ExampleIds = Field(...)
+    unlike: Optional[ExampleIds] = None
+    not_: Optional[ExampleTexts] = Field(None, alias="not")
+    top_k: int = Field(5, ge=1, le=20)
+    filter: Optional[Dict[str, Any]] = None
+    negative_weight: Optional[float] = Field(None, ge=0.0, le=1000.0)
 
 
 # request flag -> what it needs of the embedder (method, `supports_*` check) and the 400 detail when that is missing;
@@ -118,6 +144,15 @@ BOOST_NEEDS = ("boosted_query", "supports_boost",
                "Boosted retrieval is not available with this embedder: it needs a single-GPU collection "
                "(EmbeddingManager.boosted_query); a float8_e4m3fn collection also needs its re-scoring plane "
                "(MMRAG_F8_RESCORE=float16)")
+
+
+# recommend retrieval (`like` / `unlike` / `not`, POST /recommend): the same
+RECOMMEND_NEEDS = ("recommend", "supports_recommend",
+                   "Recommend retrieval is not available with this embedder: it needs a single-GPU collection "
+                   "(EmbeddingManager.recommend); a float8_e4m3fn collection also needs its re-scoring plane "
+                   "(MMRAG_F8_RESCORE=float16)")
+RECOMMEND_COLUMNS = (("scores", "score"), ("penalties", "penalty"), ("matched", "matched"),
+                     ("repelled_by", "repelled_by"))
 
 
 # `rerank` with the method "late": the same
@@ -268,12 +303,20 @@ class Pipeline:
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
         return {"deleted": len(gone), "ids": list(gone)}
 
+    @staticmethod
+    def _sources(hits: dict) -> List[dict]:
+        """the `sources` of a response from one query's hits (api.py:390); the modes add their own columns"""
+        return [{"rank": at, "doc_id": found, "relevance_score": round(float(1.0 - min(dist, 1.0)), 3),
+                 "type": meta.get("type", "unknown")}
+                for at, (found, dist, meta) in enumerate(zip(hits["ids"], hits["distances"], hits["metadatas"]), 1)]
+
     async def answer(self, question: str, top_k: int, multimodal: bool, rerank: bool = False,
                      hybrid: bool = False, mmr: bool = False, mmr_lambda: Optional[float] = None,
                      group_by_document: bool = False, per_document: int = 1,
                      variants: Optional[List[str]] = None, variant_weight: Optional[float] = None,
                      fusion: Optional[str] = None, doc_ids: Optional[List[str]] = None,
-                     rerank_method: Optional[str] = None, explain: bool = False, boost: Any = None) -> Optional[dict]:
+                     rerank_method: Optional[str] = None, explain: bool = False, boost: Any = None,
+                     recommend: Optional[Dict[str, Any]] = None) -> Optional[dict]:
         """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
         max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the re-ranker's best top_k (`rerank_method` "cross" or "late",
         default MMRAG_RERANK_METHOD; `explain`: late interaction's per-token matches on every source).  `hybrid`: from
@@ -285,7 +328,8 @@ class Pipeline:
         "rrf" or "max"); the generator and the re-ranker see `question` only.  `doc_ids`: hits from these documents
         only -- a plain (or re-ranked) query through EmbeddingManager.scoped_query, every other mode through its
         filter.  `boost` (a BoostSpec; alone or with `rerank`): the hits are ranked by cosine + the spec's score prior
-        (EmbeddingManager.boosted_query)"""
+        (EmbeddingManager.boosted_query).  `recommend` ({"like", "unlike", "unlike_texts", "negative_weight"}; alone or
+        with `rerank`): the question is one positive example next to these (EmbeddingManager.recommend)"""
         multi = variants is not None
         # the restriction as the filter the embedder's methods take (nothing is passed when there is none)
         only = {} if doc_ids is None else {"filter_dict": {"doc_id": {"$in": list(doc_ids)}}}
@@ -297,6 +341,8 @@ class Pipeline:
                                                  method=fusion, **only)
         elif boost is not None:
             search = functools.partial(self.embedder.boosted_query, boost=boost)
+        elif recommend is not None:
+            search = functools.partial(self.embedder.recommend, **recommend)
         elif mmr:
             search = functools.partial(self.embedder.mmr_query, lambda_mult=mmr_lambda, **only)
         elif hybrid:
@@ -307,7 +353,8 @@ class Pipeline:
             search = functools.partial(self.embedder.query, **only)
         # per-hit columns re-ranking carries along
         extra = ("fused_scores", "matched_queries") if multi else ("mmr_scores",) if mmr else \
-            ("hybrid_scores",) if hybrid else ("scores", "boosts") if boost is not None else ()
+            ("hybrid_scores",) if hybrid else ("scores", "boosts") if boost is not None else \
+            tuple(column for column, _ in RECOMMEND_COLUMNS) if recommend is not None else ()
         if group_by_document:
             hits = await self.embedder.grouped_query(question, n_groups=top_k, group_size=per_document, **only)
         elif rerank:
@@ -335,13 +382,12 @@ class Pipeline:
                 body += "\n\nBảng:\n" + "\n\n".join(tables)
             text = await self.llm.generate_text(f"Context:\n{body}\n\nCâu hỏi: {question}\n\nTrả lời:",
                                                 max_tokens=1000, temperature=0.7)
-        ranked = [{"rank": at, "doc_id": found, "relevance_score": round(float(1.0 - min(dist, 1.0)), 3),   # api.py:390
-                   "type": meta.get("type", "unknown")}
-                  for at, (found, dist, meta) in enumerate(zip(hits["ids"], hits["distances"], hits["metadatas"]), 1)]
+        ranked = self._sources(hits)
         for on, column, key in ((rerank, "rerank_scores", "rerank_score"), (hybrid, "hybrid_scores", "hybrid_score"),
                                 (mmr, "mmr_scores", "mmr_score"), (multi, "fused_scores", "fused_score"),
                                 (multi, "matched_queries", "matched_queries"), (boost is not None, "scores", "score"),
-                                (boost is not None, "boosts", "boost")):
+                                (boost is not None, "boosts", "boost"),
+                                *((recommend is not None, column, key) for column, key in RECOMMEND_COLUMNS)):
             if on:
                 for src, score in zip(ranked, hits[column]):
                     src[key] = score
@@ -356,6 +402,22 @@ class Pipeline:
                     src["document_rank"] = document_rank
                 at += len(group["ids"])
         return {"answer": text, "sources": ranked}
+
+    async def recommend(self, like: List[str], unlike: List[str], unlike_texts: List[str], top_k: int,
+                        filter_dict: Optional[Dict], negative_weight: Optional[float]) -> dict:
+        """POST /recommend: the sources of EmbeddingManager.recommend for stored items as examples; no generator call"""
+        self._need(RECOMMEND_NEEDS)
+        try:
+            hits = await self.embedder.recommend(None, like=like, unlike=unlike, unlike_texts=unlike_texts,
+                                                 n_results=top_k, filter_dict=filter_dict,
+                                                 negative_weight=negative_weight)
+        except ValueError as e:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
+        ranked = self._sources(hits)
+        for column, key in RECOMMEND_COLUMNS:
+            for src, value in zip(ranked, hits[column]):
+                src[key] = value
+        return {"sources": ranked}
 
     async def health(self) -> dict:
         parts = {"llm_adapter": await self.llm.health_check(),
@@ -481,6 +543,26 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
             except ValueError as e:
                 raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
             pipe._need(BOOST_NEEDS)
+        recommend = None
+        if request.like is not None or request.unlike is not None or request.not_ is not None:
+            if (multi or request.mmr or request.hybrid or request.group_by_document or request.doc_ids is not None
+                    or spec is not None):
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                    detail="Recommend retrieval is not combined with hybrid retrieval, MMR, grouping by "
+                                           "document, boosted retrieval, multi-query retrieval or `doc_ids` yet: send "
+                                           "`like` / `unlike` / `not` without `hybrid`, `mmr`, `group_by_document`, "
+                                           "`boost`, `variants` / `expand` and `doc_ids`")
+            recommend = {"like": request.like or [], "unlike": request.unlike or [],
+                         "unlike_texts": request.not_ or [], "negative_weight": request.negative_weight}
+            if 1 + sum(len(recommend[key]) for key in ("like", "unlike", "unlike_texts")) > 16:
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                    detail="A recommend request takes at most 16 examples in all: the question, "
+                                           "`like`, `unlike` and `not` together")
+            pipe._need(RECOMMEND_NEEDS)
+        elif request.negative_weight is not None:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                detail="`negative_weight` belongs to recommend retrieval: send it with `like`, "
+                                       "`unlike` or `not`")
         if request.mmr and request.hybrid:
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="MMR and hybrid retrieval are not combined yet: send `mmr` or `hybrid`, not both")
@@ -506,15 +588,33 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
             variants = kept[:15]
         # (combinations of modes were refused above: Pipeline.answer sees at most one of mmr / hybrid / grouping /
         # variants)
-        out = await pipe.answer(request.query, request.top_k, request.use_multimodal, rerank=request.rerank,
-                                hybrid=request.hybrid, mmr=request.mmr, mmr_lambda=request.mmr_lambda,
-                                group_by_document=request.group_by_document, per_document=request.per_document,
-                                variants=variants, variant_weight=request.variant_weight, fusion=request.fusion,
-                                doc_ids=request.doc_ids,
-                                rerank_method="late" if late else request.rerank_method, explain=request.explain,
-                                **({} if spec is None else {"boost": spec}))
+        try:
+            out = await pipe.answer(request.query, request.top_k, request.use_multimodal, rerank=request.rerank,
+                                    hybrid=request.hybrid, mmr=request.mmr, mmr_lambda=request.mmr_lambda,
+                                    group_by_document=request.group_by_document, per_document=request.per_document,
+                                    variants=variants, variant_weight=request.variant_weight, fusion=request.fusion,
+                                    doc_ids=request.doc_ids,
+                                    rerank_method="late" if late else request.rerank_method, explain=request.explain,
+                                    **({} if spec is None else {"boost": spec}),
+                                    **({} if recommend is None else {"recommend": recommend}))
+        except ValueError as e:
+            if recommend is None:
+                raise
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))   # an id no stored item has
         if out is None:
             out = {"answer": NO_DOCS_ANSWER, "sources": []}
+        return {**out, "processing_time": time.time() - t0}
+
+    @app.post("/recommend")
+    @_as_http_500
+    async def recommend_documents(request: RecommendRequest):
+        t0 = time.time()
+        if len(request.like) + len(request.unlike or []) + len(request.not_ or []) > 16:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                detail="A recommend request takes at most 16 examples in all: `like`, `unlike` and "
+                                       "`not` together")
+        out = await pipe.recommend(request.like, request.unlike or [], request.not_ or [], request.top_k,
+                                   request.filter, request.negative_weight)
         return {**out, "processing_time": time.time() - t0}
 
     @app.get("/documents")
