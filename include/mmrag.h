@@ -659,6 +659,52 @@ int mmrag_recommend_topk(const void *examples, const int8_t *sign, const float *
                          float *out_scores, int64_t *out_rows, float *out_pos, float *out_neg, int32_t *out_pos_arg,
                          int32_t *out_neg_arg, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Related groups (csrc/related.hip): S sets of vectors against every stored group (document) in ONE exact scan -- which
+ * documents are like this set, and how much of it do they contain.  VectorIndex.related_search.
+ *
+ * Set s owns the columns a in set_off[s] .. set_off[s + 1]) of set_rows.  With
+ *   dot[a][r]         the pair-tile body's float32 accumulation (one fixed K order: the bits equal mmrag_scoped_topk's for
+ *                     the same two rows),
+ *   candidate rows    r < n, alive bit set (when alive_bits is given), 0 <= group_of_row[r] < n_groups,
+ *   best[a][g]        = max of dot[a][r] over the candidate rows of g, -0 read as +0,
+ *   best_row[a][g]    = the LOWEST candidate row of g that attains it,
+ *   similarity[s][g]  = the float64 sum of best[a][g] over the set's columns in ascending a, divided by the set's size,
+ *                       rounded once to float32,
+ *   covered[s][g]     = the number of the set's columns with best[a][g] >= threshold (a float32 compare),
+ * the candidate groups of set s are the groups with at least one candidate row, exclude_group[s] aside, and the
+ * winners are the k candidate groups of highest similarity, descending, ties to the lower ordinal.
+ * Contract
+ *   - out_similarity / out_group / out_covered [S, k]: the winners, (-inf, -1, 0) padded; an empty set gives padding only;
+ *   - out_best / out_best_row [M, k]: for column a of set s, best[a][g] and best_row[a][g] of winner j of s,
+ *     (-inf, -1) padded;
+ *   - every output is a pure function of the inputs: not of the grid, the batch, or the order atomics arrive in (the
+ *     scan reduces with an integer maximum of (score, lowest row) keys);
+ *   - a 128-row tile of stored rows with no candidate row is not fetched;
+ *   - no host synchronisation.
+ *
+ *   set_rows        dev [M, ld] of the rows' dtype and ld, pad columns zero; M in 0..8192
+ *   set_off         dev [S + 1] int32 ascending offsets from 0 to M; S in 1..64.  Offsets that do not ascend inside
+ *                   0..M own no column
+ *   rows            dev [n, ld], MMRAG_F32 / F16 / BF16, ld of whole 128-byte slabs; MMRAG_F8E4M3 returns
+ *                   MMRAG_EUNSUPPORTED (an FP8 collection is compared on its re-scoring plane)
+ *   alive_bits      dev, optional (NULL = every row): bit r & 31 of word r >> 5
+ *   group_of_row    dev [n] int32 ordinals; values outside 0..n_groups-1 are rows of no group
+ *   exclude_group   dev [S] int32, -1 = none
+ *   k               1..MMRAG_MAX_K_DEEP
+ *   workspace       dev, >= mmrag_related_groups_workspace_bytes(M, S, n, n_groups, k) bytes (0 for arguments out of
+ *                   range; it holds the 8 * M * n_groups byte table of keys), 16-byte aligned
+ * MMRAG_EINVAL before anything is launched: a null pointer, M < 0 or > 8192, S < 1 or > 64, n < 0 or >= 2^31, k out of
+ * range, d <= 0, ld < d or not whole slabs, n_groups < 0, a threshold that is not a number, a workspace that is too
+ * small. */
+#define MMRAG_MAX_RELATED_ROWS 8192
+#define MMRAG_MAX_RELATED_SETS 64
+size_t mmrag_related_groups_workspace_bytes(int M, int S, int64_t n, int n_groups, int k);
+int mmrag_related_groups(const void *set_rows, int M, const int32_t *set_off, int S, const void *rows, int64_t n, int d,
+                         int64_t ld, int dtype, const uint32_t *alive_bits, const int32_t *group_of_row, int n_groups,
+                         const int32_t *exclude_group, float threshold, int k, float *out_similarity, int32_t *out_group,
+                         int32_t *out_covered, float *out_best, int64_t *out_best_row, void *workspace,
+                         size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Late-interaction re-ranking (ColBERT's MaxSim) with the bi-encoder alone.  The reference has no counterpart: its
  * EmbeddingManager.rerank_results is a placeholder (app/utils/embedder.py:834-859).  The encoder's per-token outputs are

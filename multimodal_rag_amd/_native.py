@@ -31,7 +31,8 @@ FUSE_METHODS = {"rrf": 0, "max": 1}
 MAX_JOIN_PAIRS = 1 << 26   # mmrag_sim_join (MMRAG_MAX_JOIN_PAIRS)
 MAX_CLUSTERS = 4096   # mmrag_kmeans_assign / mmrag_cluster_sums (MMRAG_MAX_CLUSTERS)
 MAX_SCOPE_GROUPS = 64   # mmrag_scoped_topk (MMRAG_MAX_SCOPE_GROUPS)
-MAX_RECOMMEND_EXAMPLES = 16   # mmrag_recommend_topk (MMRAG_MAX_RECOMMEND_EXAMPLES)
+MAX_RELATED_ROWS, MAX_RELATED_SETS = 8192, 64   # mmrag_related_groups (MMRAG_MAX_RELATED_ROWS, MMRAG_MAX_RELATED_SETS)
+MAX_RECOMMEND_EXAMPLES = 16  # mmrag_recommend_topk (MMRAG_MAX_RECOMMEND_EXAMPLES)
 # mmrag_maxsim_scores (MMRAG_MAX_LATE_QUERY_TOKENS, MMRAG_MAX_LATE_DOC_TOKENS)
 MAX_LATE_QUERY_TOKENS, MAX_LATE_DOC_TOKENS = 128, 512
 MAX_LATE_PAIRS = 65535
@@ -230,6 +231,15 @@ def _declare(lib):
                                       c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.mmrag_internal_scoped_topk_ex.restype = c_int
     lib.mmrag_internal_scoped_topk_ex.argtypes = lib.mmrag_scoped_topk.argtypes + [c_int64]
+    # related groups (csrc/related.hip); the _ex entry adds the scan's grid (tests, not in include/mmrag.h)
+    lib.mmrag_related_groups_workspace_bytes.restype = c_size_t
+    lib.mmrag_related_groups_workspace_bytes.argtypes = [c_int, c_int, c_int64, c_int, c_int]
+    lib.mmrag_related_groups.restype = c_int
+    lib.mmrag_related_groups.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_int64, c_int,
+                                         c_void_p, c_void_p, c_int, c_void_p, c_float, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.mmrag_internal_related_groups_ex.restype = c_int
+    lib.mmrag_internal_related_groups_ex.argtypes = lib.mmrag_related_groups.argtypes + [c_int64]
     lib.mmrag_internal_candidate_capacity.restype = c_int64
     lib.mmrag_internal_candidate_capacity.argtypes = [c_int]
     # boosted top-k (csrc/boosted.hip); the _ex entry adds a candidate capacity and debug switches (tests, not in
@@ -742,6 +752,91 @@ def scoped_topk(q: torch.Tensor, rows: torch.Tensor, n: int, d: int, k: int, gro
             workspace.data_ptr(), _nbytes(workspace), _stream_ptr(dev), int(cap))
     _check(st, "mmrag_scoped_topk")
     return out_s, out_r
+
+
+def related_groups_workspace_bytes(M: int, S: int, n: int, n_groups: int, k: int) -> int:
+    return int(lib().mmrag_related_groups_workspace_bytes(int(M), int(S), int(n), int(n_groups), int(k)))
+
+
+def related_groups(sets: torch.Tensor, set_off, rows: torch.Tensor, n: int, d: int, k: int, group_col: torch.Tensor,
+                   n_groups: int, threshold: float, exclude=None, alive_bits: Optional[torch.Tensor] = None,
+                   table_bytes: Optional[int] = None, grid: int = 0):
+    """Set-to-group similarity of S sets of vectors against the first n of `rows` [cap, ld] (include/mmrag.h
+    mmrag_related_groups, where the definition is): `sets` [M, ld] in the rows' dtype and padded width holds the sets'
+    vectors, set s owning rows set_off[s] : set_off[s + 1] (a HOST sequence of S + 1 ascending offsets from 0 to M);
+    group_col [>= n] int32 is the rows' group ordinal (outside 0..n_groups-1 = no group); `exclude`: one ordinal per set
+    that is no candidate of it (HOST sequence, -1 or None = none).  Returns device tensors
+        (similarity [S, k] float32 desc, group [S, k] int32, covered [S, k] int32, best [M, k] float32,
+         best_row [M, k] int64),
+    (-inf, -1, 0, -inf, -1) padded.  No host synchronisation.  A call whose table of 8 * M * n_groups bytes would exceed
+    `table_bytes` (default: settings.MMRAG_RELATED_TABLE_BYTES) runs as sub-calls of whole sets, which is exact; raises
+    ValueError when one set alone exceeds it, for more than MAX_RELATED_SETS sets or MAX_RELATED_ROWS vectors, k outside
+    1..MAX_K_DEEP, or offsets that do not fit.  `grid` (tests only): the scan's workgroups."""
+    _dev_check(sets, rows, alive_bits, group_col)
+    _check_q_rows("related_groups", sets, rows, n, other="rows")
+    _check_stored_rows("related_groups", rows)
+    M, ld = sets.shape
+    n, k, n_groups = int(n), int(k), int(n_groups)
+    _check_alive("related_groups", alive_bits, n, rows)
+    dev = rows.device
+    if (group_col.dim() != 1 or group_col.dtype != torch.int32 or not group_col.is_contiguous()
+            or group_col.numel() < n or group_col.device != dev):
+        raise MMRagNativeError("related_groups: group_col must be a contiguous int32 tensor of at least n ordinals on "
+                               "the rows' device")
+    off = [int(v) for v in set_off]
+    S = len(off) - 1
+    if S < 1 or off[0] != 0 or off[-1] != M or any(b < a for a, b in zip(off, off[1:])):
+        raise ValueError(f"related_groups: set_off must hold S + 1 >= 2 ascending offsets from 0 to M={M}")
+    if S > MAX_RELATED_SETS or M > MAX_RELATED_ROWS:
+        raise ValueError(f"related_groups: at most {MAX_RELATED_SETS} sets and {MAX_RELATED_ROWS} vectors per call "
+                         f"(S={S}, M={M})")
+    if not 1 <= k <= MAX_K_DEEP:
+        raise ValueError(f"related_groups: k={k} outside 1..{MAX_K_DEEP}")
+    excl = [-1] * S if exclude is None else [-1 if v is None else int(v) for v in exclude]
+    if len(excl) != S:
+        raise ValueError(f"related_groups: exclude holds {len(excl)} entries for {S} sets")
+    if table_bytes is None:
+        from .config import settings
+
+        table_bytes = int(settings.MMRAG_RELATED_TABLE_BYTES)
+    # sub-calls of whole sets [s0, s1) whose tables fit the budget
+    cell = 8 * max(n_groups, 0)
+    parts, s0 = [], 0
+    for s in range(S):
+        if (off[s + 1] - off[s]) * cell > table_bytes:
+            raise ValueError(f"related_groups: set {s} alone needs a table of {(off[s + 1] - off[s]) * cell} bytes, "
+                             f"above MMRAG_RELATED_TABLE_BYTES={table_bytes}")
+        if (off[s + 1] - off[s0]) * cell > table_bytes:
+            parts.append((s0, s))
+            s0 = s
+    parts.append((s0, S))
+    # one pinned copy of every sub-call's offsets and exclusions
+    host = []
+    for a, b in parts:
+        host += [v - off[a] for v in off[a: b + 1]] + excl[a:b]
+    packed = _pinned_to_device(torch.tensor(host, dtype=torch.int32), dev)
+    out_sim = torch.empty((S, k), dtype=torch.float32, device=dev)
+    out_grp = torch.empty((S, k), dtype=torch.int32, device=dev)
+    out_cov = torch.empty((S, k), dtype=torch.int32, device=dev)
+    # one spare row: the pointers are real at M == 0 too
+    out_best = torch.empty((M + 1, k), dtype=torch.float32, device=dev)
+    out_row = torch.empty((M + 1, k), dtype=torch.int64, device=dev)
+    need = max(related_groups_workspace_bytes(off[b] - off[a], b - a, n, n_groups, k) for a, b in parts)
+    workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    sets_ptr = sets.data_ptr() if M else workspace.data_ptr()      # no vectors: never read
+    at = 0
+    with torch.cuda.device(dev):
+        for a, b in parts:
+            Sp, c0, Mp = b - a, off[a], off[b] - off[a]
+            st = lib().mmrag_internal_related_groups_ex(
+                sets_ptr + c0 * ld * sets.element_size(), Mp, packed[at:].data_ptr(), Sp, rows.data_ptr(), n, int(d),
+                ld, _TORCH2DT[rows.dtype], alive_bits.data_ptr() if alive_bits is not None else None,
+                group_col.data_ptr(), n_groups, packed[at + Sp + 1:].data_ptr(), float(threshold), k,
+                out_sim[a:].data_ptr(), out_grp[a:].data_ptr(), out_cov[a:].data_ptr(), out_best[c0:].data_ptr(),
+                out_row[c0:].data_ptr(), workspace.data_ptr(), _nbytes(workspace), _stream_ptr(dev), int(grid))
+            _check(st, "mmrag_related_groups")
+            at += 2 * Sp + 1
+    return out_sim, out_grp, out_cov, out_best[:M], out_row[:M]
 
 
 def boosted_topk_workspace_bytes(B: int, n: int, k: int) -> int:

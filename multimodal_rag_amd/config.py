@@ -122,6 +122,11 @@ class Settings:
     # final = pos - w * max(neg, 0) when a request names negatives and gives none
     MMRAG_RECOMMEND_NEGATIVE_WEIGHT: float = field(
         default_factory=lambda: float(os.getenv("MMRAG_RECOMMEND_NEGATIVE_WEIGHT", "1.0")))
+    # related-document retrieval (VectorIndex.related_query, csrc/related.hip): the scan keeps one 8-byte key per
+    # (vector of the sets, stored document); a call whose table would exceed this many bytes is split by whole sets
+    # (exact: sets are independent), a single set that exceeds it alone is refused.  A memory budget, not a measurement
+    MMRAG_RELATED_TABLE_BYTES: int = field(
+        default_factory=lambda: int(os.getenv("MMRAG_RELATED_TABLE_BYTES", str(1 << 30))))
     # topic clustering (VectorIndex.cluster, csrc/kmeans.hip): the default number of topics of cluster() / GET /topics;
     # 0 (default) = automatic, auto_topics(live rows); else 1 .. 4096
     MMRAG_TOPICS: int = field(default_factory=lambda: int(os.getenv("MMRAG_TOPICS", "0")))

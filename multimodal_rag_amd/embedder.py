@@ -31,7 +31,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import tracing
-from ._native import MAX_RECOMMEND_EXAMPLES
+from ._native import MAX_RECOMMEND_EXAMPLES, MAX_RELATED_ROWS
 from .config import settings
 from .engines import CLIP_MODEL_NAMES, ClipEngine, HipEngine, _is_clip_dir, load_item_image  # noqa: F401 (re-exported)
 from .hostutil import CountingLRU, call_with_retry, load_hostrows
@@ -59,7 +59,9 @@ _NEEDS_BOOST = ("boosted_query", "boosted retrieval needs a single-GPU collectio
                                  "rows")
 _NEEDS_RECOMMEND = ("recommend_query", "recommend retrieval needs a single-GPU collection (VectorIndex) with "
                                         "full-precision rows")
-_boost_warned = False    # "this collection cannot boost": once per process
+_NEEDS_RELATED = ("related_query", "related-document retrieval needs a single-GPU collection (VectorIndex) with "
+                                   "full-precision rows")
+_boost_warned = False   # "this collection cannot boost": once per process
 _dedup_warned = False    # "MMRAG_DEDUP_THRESHOLD is set but this collection cannot de-duplicate": once per process
 # the answer of a batch's query that could not be answered, before its 'error' (copied for every such query)
 _EMPTY = {key: [] for key in RESULT_KEYS}
@@ -808,6 +810,42 @@ class EmbeddingManager:
                                      "metadata": got["metadatas"][row[i]] if i in row else {}}
                                     for i, s in c["representatives"]]
         return report
+
+    def supports_related(self) -> bool:
+        """True when the collection can rank documents against a set of vectors (where supports_dedup() is: a
+        single-GPU VectorIndex with full-precision rows; not the sharded serving path)"""
+        return self.collection is None or (hasattr(self.collection, "related_query") and self._has_full_rows())
+
+    async def related_documents(self, doc_id: Optional[str] = None, texts: Optional[Sequence[str]] = None,
+                                n_results: int = 5, threshold: Optional[float] = None,
+                                filter_dict: Optional[Dict] = None) -> Dict[str, Any]:
+        """The stored documents most like ONE set of passages (VectorIndex.related_query): the chunks stored under
+        `doc_id` (that document itself is no candidate) or the given `texts`, encoded in one batched call -- exactly one
+        of the two.  Returns {"chunks": m, "threshold": t, "related": [{"key": doc_id, "similarity", "coverage",
+        "matched", "rows_in_group", "pairs": [...]}, ...]} in rank order; `threshold` (default
+        MMRAG_DEDUP_REPORT_THRESHOLD) is the cosine from which a chunk counts as contained.  LookupError when no stored
+        item has `doc_id`; ValueError for arguments the collection refuses."""
+        if (doc_id is None) == (texts is None):
+            raise ValueError("related_documents takes exactly one of doc_id and texts")
+        await self._ready()
+        if not self.supports_related():
+            raise ValueError(_NEEDS_RELATED[1])
+        if texts is not None:
+            texts = list(texts)
+            if not texts or not all(isinstance(t, str) and t.strip() for t in texts):
+                raise ValueError("texts must be a non-empty list of non-empty strings")
+            if len(texts) > MAX_RELATED_ROWS:
+                raise ValueError(f"texts holds {len(texts)} passages, at most {MAX_RELATED_ROWS}")
+            entry, m = await self._embed_matrix(texts, self.batch_size), len(texts)
+        else:
+            m = len(self.collection.get(where={"doc_id": doc_id}, include=())["ids"])
+            if not m:
+                raise LookupError(f"no stored item has doc_id {doc_id!r}")
+            entry = {"value": doc_id}
+        t = settings.MMRAG_DEDUP_REPORT_THRESHOLD if threshold is None else threshold
+        found = await self._refusing_call("Related documents", self.collection.related_query, sets=[entry],
+                                          n_results=n_results, threshold=t, where=filter_dict)
+        return {"chunks": m, "threshold": float(t), "related": found[0]}
 
     def supports_grouping(self) -> bool:
         """True when the collection can answer grouped_query (a single-GPU VectorIndex; not the sharded serving path,

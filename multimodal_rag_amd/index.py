@@ -1375,6 +1375,133 @@ class VectorIndex:
         with stage("collect"):
             return self._collect(scores, rows, include, *tables, emb_src)
 
+    # ------------------------------------------------------------------ related documents (set-to-document) ----
+    def _launch_related(self, sets, n_results: int, key: str, threshold, exclude, where, check_norm: bool = True):
+        """enqueue the related-groups scan (caller holds the lock): (the five device tensors of
+        _native.related_groups, the sets' offsets, each column's item: the stored row of a {"value": v} set or the
+        index inside a set of vectors, the threshold used)"""
+        from .config import settings
+
+        self._need_plane("related_query")
+        k = int(n_results)
+        if not 1 <= k <= _native.MAX_K_DEEP:
+            raise ValueError(f"n_results must be in 1..{_native.MAX_K_DEEP} for a related search")
+        t = self._join_threshold(settings.MMRAG_DEDUP_REPORT_THRESHOLD if threshold is None else threshold,
+                                 "threshold")
+        sets = list(sets)
+        if not 1 <= len(sets) <= _native.MAX_RELATED_SETS:
+            raise ValueError(f"sets must hold 1..{_native.MAX_RELATED_SETS} entries")
+        if exclude is not None and len(list(exclude)) != len(sets):
+            raise ValueError(f"exclude holds {len(list(exclude))} entries for {len(sets)} sets")
+        st = self.enable_grouping(key)
+        ordinal = st["ordinal"]
+
+        def ordinal_of(v):
+            try:
+                return ordinal.get(v)
+            except TypeError:        # unhashable: no row has it as its key
+                return None
+
+        parts, off, items, excl = [], [0], [], []
+        for i, entry in enumerate(sets):
+            if isinstance(entry, dict):
+                if set(entry) != {"value"}:
+                    raise ValueError(f'sets[{i}]: a dict entry is {{"value": v}}')
+                o = ordinal_of(entry["value"])
+                rows = self._rows_where({key: entry["value"]}) if o is not None else np.zeros(0, dtype=np.int64)
+                if not rows.size:
+                    raise ValueError(f"sets[{i}]: no stored row has {key}={entry['value']!r}")
+                parts.append(rows)
+                items += rows.tolist()
+                own = o
+            else:
+                qf = self._to_device_f32(entry, f"sets[{i}]", check_norm)
+                parts.append(qf)
+                items += list(range(qf.shape[0]))
+                own = None
+            if exclude is not None:
+                v = list(exclude)[i]
+                own = ordinal_of(v) if v is not None else None
+            excl.append(-1 if own is None else own)
+            off.append(len(items))
+        M = off[-1]
+        if M > _native.MAX_RELATED_ROWS:
+            raise ValueError(f"the sets hold {M} vectors, at most {_native.MAX_RELATED_ROWS} per call")
+        full = self._full
+        packed = torch.empty((max(M, 1), full.shape[1]), dtype=full.dtype, device=self.device)
+        for c0, part in zip(off, parts):
+            if isinstance(part, np.ndarray):     # stored rows, gathered on the device in row order
+                _native.gather_rows(packed[c0: c0 + part.size], full, torch.from_numpy(part).to(self.device))
+            elif part.shape[0]:
+                _native.append_rows(packed, c0, part, self.dim)
+        out = _native.related_groups(packed[:M], off, full, self._n, self.dim, k, st["col"], len(st["values"]), t,
+                                     exclude=excl, alive_bits=self._where_bits(where))
+        return out, off, items, t
+
+    def related_search(self, sets, n_results: int, key: str = "doc_id", threshold: Optional[float] = None,
+                       exclude=None, where: Optional[Dict[str, Any]] = None):
+        """Raw device set-to-document similarity (csrc/related.hip, include/mmrag.h mmrag_related_groups, where the
+        definition is): for each entry of `sets` -- a [m, dim] array of unit vectors, or {"value": v} = the live stored
+        rows whose metadata `key` is v, gathered on the device in row order -- the n_results stored documents (distinct
+        values of `key`) of highest
+            similarity = mean over the set's vectors a of  max over the document's live rows r of cos(a, x_r),
+        formed inside ONE exact scan of the collection, with covered = the number of the set's vectors whose best
+        match in the document is >= threshold (default MMRAG_DEDUP_REPORT_THRESHOLD, "the same passage").  Returns
+        device tensors (similarity [S, k] float32 desc, group ordinals [S, k] int32, covered [S, k] int32,
+        best [M, k] float32, best_row [M, k] int64: each vector's best match in each winner of its set),
+        (-inf, -1, 0, -inf, -1) padded; ordinal o is enable_grouping(key)["values"][o].  No host synchronisation on the
+        kernels' path.
+
+        `exclude`: one key value (or None) per set that is no candidate of it; by default a {"value": v} set excludes v
+        itself and a set of vectors nothing.  An unknown v raises ValueError.  `where` narrows the candidate rows;
+        tombstones are honoured; rows without the key belong to no document.  A float8_e4m3fn collection is compared on
+        its re-scoring plane (capacity mode raises ValueError).  At most MAX_RELATED_SETS sets and MAX_RELATED_ROWS
+        vectors per call.  One direction only: how much of the SET a document holds, not how much of the document the
+        set holds."""
+        with self._lock:
+            return self._launch_related(sets, n_results, key, threshold, exclude, where)[0]
+
+    def related_query(self, sets, n_results: int = 5, key: str = "doc_id", threshold: Optional[float] = None,
+                      exclude=None, where: Optional[Dict[str, Any]] = None,
+                      include: Sequence[str] = ("metadatas", "documents"), check_norm: bool = True) -> List[List[Dict]]:
+        """related_search as host lists: per set, its related documents in rank order, each
+            {"key": value, "similarity", "coverage": covered / m, "matched": covered, "rows_in_group": live rows,
+             "pairs": [{"item": the id of the set's stored row, or the vector's index, "match_id", "score"}, ...]}
+        with one pair per vector of the set, in set order; "documents" / "metadatas" in `include` add the matched
+        row's "match_document" / "match_metadata" to each pair."""
+        sets = list(sets)
+        with self._lock, stage("search"):
+            out, off, items, _ = self._launch_related(sets, n_results, key, threshold, exclude, where, check_norm)
+            tables = self._tables()
+            values = self._groups[key]["values"]
+            by_value = [isinstance(e, dict) for e in sets]
+            sim, grp, cov, best, best_row = (t.cpu() for t in out)       # the call's host synchronisation
+            live = {o: int(self._rows_where({key: values[o]}).size) for o in set(grp.flatten().tolist()) if o >= 0}
+        with stage("collect"):
+            ids_t, docs_t, metas_t = tables
+            sim_l, grp_l, cov_l, best_l, row_l = sim.tolist(), grp.tolist(), cov.tolist(), best.tolist(), best_row.tolist()
+            res = []
+            for s, stored in enumerate(by_value):
+                lo, hi = off[s], off[s + 1]
+                found = []
+                for j, o in enumerate(grp_l[s]):
+                    if o < 0:
+                        break
+                    pairs = []
+                    for a in range(lo, hi):
+                        r = row_l[a][j]
+                        pair = {"item": ids_t[items[a]] if stored else items[a], "match_id": ids_t[r],
+                                "score": best_l[a][j]}
+                        if "documents" in include:
+                            pair["match_document"] = docs_t[r]
+                        if "metadatas" in include:
+                            pair["match_metadata"] = dict(metas_t[r])
+                        pairs.append(pair)
+                    found.append({"key": values[o], "similarity": sim_l[s][j], "coverage": cov_l[s][j] / (hi - lo),
+                                  "matched": cov_l[s][j], "rows_in_group": live[o], "pairs": pairs})
+                res.append(found)
+            return res
+
     # ------------------------------------------------------------------ score priors (boosted retrieval) ----
     MAX_SPEC_COLUMNS = 4
 

@@ -116,6 +116,14 @@ class RecommendRequest(BaseModel):
     negative_weight: Optional[float] = Field(None, ge=0.0, le=1000.0)
 
 
+class RelatedRequest(BaseModel):
+    """POST /related: which stored documents cover these passages; no question and no generator call"""
+    texts: List[str] = Field(..., min_length=1, max_length=8192)
+    top_k: int = Field(5, ge=1, le=100)
+    threshold: Optional[float] = Field(None, gt=0.0, le=1.0)
+    filter: Optional[Dict[str, Any]] = None
+
+
 # request flag -> what it needs of the embedder (method, `supports_*` check) and the 400 detail when that is missing;
 # /query checks them in this order
 MODE_NEEDS = (
@@ -173,6 +181,14 @@ TOPICS_NEEDS = ("cluster_topics", "supports_clustering",
                 "Topic clustering is not available with this embedder: it needs a single-GPU collection "
                 "(EmbeddingManager.cluster_topics); a float8_e4m3fn collection also needs its re-scoring plane "
                 "(MMRAG_F8_RESCORE=float16)")
+
+
+# /documents/{doc_id}/related and /related: the same for related-document retrieval
+RELATED_NEEDS = ("related_documents", "supports_related",
+                 "Related-document retrieval is not available with this embedder: it needs a single-GPU collection "
+                 "(EmbeddingManager.related_documents); a float8_e4m3fn collection also needs its re-scoring plane "
+                 "(MMRAG_F8_RESCORE=float16)")
+RELATED_PAIRS = 5     # the best pairs of a related document that a response carries
 
 
 class QueryResponse(BaseModel):  # api.py:167-170
@@ -292,6 +308,22 @@ class Pipeline:
                             "representatives": c["representatives"],
                             "documents": [{"doc_id": v, "count": n} for v, n in c["documents"]]}
                            for c in report["clusters"]]}
+
+    async def related(self, doc_id: Optional[str], texts: Optional[List[str]], top_k: int,
+                      threshold: Optional[float], filter_dict: Optional[Dict] = None) -> dict:
+        """the related documents of a stored document or of passages (EmbeddingManager.related_documents), each with
+        its RELATED_PAIRS best pairs by score; 404 when no stored item has `doc_id`"""
+        self._need(RELATED_NEEDS)
+        try:
+            out = await self.embedder.related_documents(doc_id=doc_id, texts=texts, n_results=top_k,
+                                                        threshold=threshold, filter_dict=filter_dict)
+        except LookupError as e:
+            raise HTTPException(status_code=status.HTTP_404_NOT_FOUND, detail=str(e.args[0]) if e.args else str(e))
+        except ValueError as e:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
+        related = [{**doc, "pairs": sorted(doc["pairs"], key=lambda p: -p["score"])[:RELATED_PAIRS]}
+                   for doc in out["related"]]
+        return {"chunks": out["chunks"], "threshold": out["threshold"], "related": related}
 
     async def remove_duplicates(self, threshold: Optional[float], doc_id: Optional[str]) -> dict:
         self._need(DEDUP_NEEDS)
@@ -616,6 +648,22 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
         out = await pipe.recommend(request.like, request.unlike or [], request.not_ or [], request.top_k,
                                    request.filter, request.negative_weight)
         return {**out, "processing_time": time.time() - t0}
+
+    @app.post("/related")
+    @_as_http_500
+    async def related_to_texts(request: RelatedRequest):
+        t0 = time.time()
+        out = await pipe.related(None, request.texts, request.top_k, request.threshold, request.filter)
+        return {**out, "processing_time": time.time() - t0}
+
+    @app.get("/documents/{doc_id}/related")
+    @_as_http_500
+    async def related_documents(doc_id: str, top_k: int = 5, threshold: Optional[float] = None):
+        t0 = time.time()
+        if not 1 <= top_k <= 100:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail="top_k must be in 1..100")
+        out = await pipe.related(doc_id, None, top_k, threshold)
+        return {"doc_id": doc_id, **out, "processing_time": time.time() - t0}
 
     @app.get("/documents")
     @_as_http_500
