@@ -44,13 +44,21 @@ __device__ __forceinline__ void static_for(F &&f) {
 
 constexpr int QSW_XCH = 2048 + 64;   // gather buffer 1 KiB + poll buffer 1 KiB + 8 ticket slots (padded)
 constexpr int qsw_lists_bytes(int K, int MS) { return K * (MS == 32 ? 2 : 4) * QS_QROWS * 8; }
+// The Q fragments of the LAST k-step are parked in LDS ([fragment][thread], 16 bytes each) and read back once per tile,
+// a few statements before the two that use them: their 16 registers are free across the end of a tile, where the
+// selection wants them (16x16x32 only; the developer-only 32x32x16 shape keeps all of Q in registers).
+constexpr int qsw_park_bytes(int MS) { return MS == 16 ? 4 * QS_QROWS * 16 : 0; }
 
 constexpr SlabRing qsw_ring(int NK, int K, int MS) {
 #if defined(MMRAG_QSW_RING16)   // developer builds: ring of the 16x16x32 shape as G * 10 + NST (A/B of stage size vs depth)
     if (MS == 16 && NK % (MMRAG_QSW_RING16 / 10) == 0) return SlabRing{MMRAG_QSW_RING16 / 10, MMRAG_QSW_RING16 % 10};
 #endif
-    return slab_ring(NK, qsw_lists_bytes(K, MS) + QSW_XCH);
+    return slab_ring(NK, qsw_lists_bytes(K, MS) + QSW_XCH + qsw_park_bytes(MS));
 }
+// (the parked k-step must not cost the ring a stage at any row length the product dispatches)
+static_assert(qsw_ring(12, 5, 16).G == 3 && qsw_ring(12, 5, 16).NST == 4, "ring at 1536-byte rows");
+static_assert(qsw_ring(8, 5, 16).G == 2 && qsw_ring(8, 5, 16).NST == 6, "ring at 1024-byte rows");
+static_assert(qsw_ring(6, 5, 16).G == 3 && qsw_ring(6, 5, 16).NST == 4, "ring at 768-byte rows");
 
 // ---- one statement of the k loop = ONE asm statement: the two A-fragment reads of the NEXT statement go out first,
 // this statement's MFMAs (128 matrix-pipe cycles) cover their latency, the wait for them closes the statement.  The
@@ -112,6 +120,61 @@ __device__ __forceinline__ void qsw_stmt32(f32x16_t &c00, f32x16_t &c01, f32x16_
 #define MMRAG_QSW_S16_ACC(MNEMONIC, QC)                                                                       \
     MMRAG_QSW_S16(MNEMONIC, QC, "%[d0]", "%[d1]", "%[d2]", "%[d3]", "%[d4]", "%[d5]", "%[d6]", "%[d7]", "+v")
 #define MMRAG_QSW_S16_FIRST(MNEMONIC, QC) MMRAG_QSW_S16(MNEMONIC, QC, "0", "0", "0", "0", "0", "0", "0", "0", "=&v")
+
+// The same statement with the read-back of the parked Q fragments in its free gaps (gaps 3 .. 7: one instruction each
+// rides under the MFMA in front of it).  PARK_A makes the lane's address in the parked region (lane id from the
+// hardware, see lane_now below; `pb` = this wave's part of the region) and reads fragments 0 and 1, PARK_B, the
+// statement after it, reads fragments 2 and 3.  Both close with lgkmcnt(2): LDS reads return in order, so the
+// statement's own two A fragments (and everything older) have landed, the two parked reads are covered by the next
+// statement's wait.  The statement after PARK_B is an ordinary one (lgkmcnt(0)) and nothing reads p0 .. p3 before it.
+#define MMRAG_QSW_S16_PARK(MNEMONIC, QC, X3, X4, X5, X6, X7, PA, ...)                                         \
+    asm volatile(MNEMONIC " %[d0], %[a0], %[q0], %[d0]\n\t"                                                   \
+                 "ds_read_b128 %[n0], %[ad] offset:%[o0]\n\t" MNEMONIC " %[d1], %[a0], %[q1], %[d1]\n\t"      \
+                 "ds_read_b128 %[n1], %[ad] offset:%[o1]\n\t" MNEMONIC " %[d2], %[a0], %[q2], %[d2]\n\t"      \
+                 X3 MNEMONIC " %[d3], %[a0], %[q3], %[d3]\n\t" X4 MNEMONIC " %[d4], %[a1], %[q0], %[d4]\n\t"  \
+                 X5 MNEMONIC " %[d5], %[a1], %[q1], %[d5]\n\t" X6 MNEMONIC " %[d6], %[a1], %[q2], %[d6]\n\t"  \
+                 X7 MNEMONIC " %[d7], %[a1], %[q3], %[d7]\n\t"                                                 \
+                 "s_waitcnt lgkmcnt(2)"                                                                       \
+                 : [d0] "+v"(d0), [d1] "+v"(d1), [d2] "+v"(d2), [d3] "+v"(d3), [d4] "+v"(d4), [d5] "+v"(d5),  \
+                   [d6] "+v"(d6), [d7] "+v"(d7), [n0] "=&v"(n0), [n1] "=&v"(n1), [px] "=&v"(px),              \
+                   [py] "=&v"(py), [pa] PA(pa)                                                                \
+                 : [a0] "v"(a0), [a1] "v"(a1), [q0] QC(q0), [q1] QC(q1), [q2] QC(q2), [q3] QC(q3),            \
+                   [ad] "v"(adr), [o0] "i"(OFF0), [o1] "i"(OFF1), [ox] "i"(POFF), [oy] "i"(POFF + PSTRIDE),   \
+                   ##__VA_ARGS__)
+#define MMRAG_QSW_S16_PARK_A(MNEMONIC, QC)                                                                    \
+    MMRAG_QSW_S16_PARK(MNEMONIC, QC, "v_mbcnt_lo_u32_b32 %[pa], -1, 0\n\t", "v_mbcnt_hi_u32_b32 %[pa], -1, %[pa]\n\t", \
+                       "v_lshl_add_u32 %[pa], %[pa], 4, %[pb]\n\t", "ds_read_b128 %[px], %[pa] offset:%[ox]\n\t", \
+                       "ds_read_b128 %[py], %[pa] offset:%[oy]\n\t", "=&v", [pb] "s"(pb))
+#define MMRAG_QSW_S16_PARK_B(MNEMONIC, QC)                                                                    \
+    MMRAG_QSW_S16_PARK(MNEMONIC, QC, "ds_read_b128 %[px], %[pa] offset:%[ox]\n\t",                             \
+                       "ds_read_b128 %[py], %[pa] offset:%[oy]\n\t", "", "", "", "+v")
+
+// SECOND = false: PARK_A (fragments 0, 1 -> px, py; pa is made), true: PARK_B (fragments 2, 3; pa is read)
+template <int DT, bool QA, bool SECOND, int OFF0, int OFF1, int PSTRIDE, typename FT>
+__device__ __forceinline__ void qsw_stmt16_park(f32x4_t &d0, f32x4_t &d1, f32x4_t &d2, f32x4_t &d3, f32x4_t &d4,
+                                                f32x4_t &d5, f32x4_t &d6, f32x4_t &d7, const FT a0, const FT a1,
+                                                const FT q0, const FT q1, const FT q2, const FT q3, FT &n0, FT &n1,
+                                                const unsigned adr, FT &px, FT &py, unsigned &pa, const unsigned pb) {
+    constexpr int POFF = SECOND ? 2 * PSTRIDE : 0;
+    if constexpr (!SECOND) {
+        if constexpr (DT == MMRAG_F16) {
+            if constexpr (QA) MMRAG_QSW_S16_PARK_A("v_mfma_f32_16x16x32_f16", "a");
+            else MMRAG_QSW_S16_PARK_A("v_mfma_f32_16x16x32_f16", "v");
+        } else {
+            if constexpr (QA) MMRAG_QSW_S16_PARK_A("v_mfma_f32_16x16x32_bf16", "a");
+            else MMRAG_QSW_S16_PARK_A("v_mfma_f32_16x16x32_bf16", "v");
+        }
+    } else {
+        (void)pb;
+        if constexpr (DT == MMRAG_F16) {
+            if constexpr (QA) MMRAG_QSW_S16_PARK_B("v_mfma_f32_16x16x32_f16", "a");
+            else MMRAG_QSW_S16_PARK_B("v_mfma_f32_16x16x32_f16", "v");
+        } else {
+            if constexpr (QA) MMRAG_QSW_S16_PARK_B("v_mfma_f32_16x16x32_bf16", "a");
+            else MMRAG_QSW_S16_PARK_B("v_mfma_f32_16x16x32_bf16", "v");
+        }
+    }
+}
 
 template <int DT, bool QA, bool FIRST, int OFF0, int OFF1, typename FT>
 __device__ __forceinline__ void qsw_stmt16(f32x4_t &d0, f32x4_t &d1, f32x4_t &d2, f32x4_t &d3, f32x4_t &d4,
@@ -184,9 +247,17 @@ __global__ __launch_bounds__(256, 1) void cosine_topk_walk_kernel(const KParams 
     constexpr int KST = MS == 32 ? NK * 4 : NK * 2;   // Q k-steps (16- or 32-deep), NQB fragments each
     constexpr int QA_STEPS = 64 / NQB;     // k-steps whose Q fragments live in the accumulator file (256 registers)
     constexpr int LISTS = qsw_lists_bytes(K, MS);
+    constexpr int PARK = qsw_park_bytes(MS);   // the last k-step's Q fragments, [fragment][thread]
+    constexpr int PARK_OFF = NST * STAGE + LISTS + QSW_XCH;
+    constexpr int PARK_STRIDE = QS_QROWS * 16;
+    constexpr int NSTMT = NK * 4;              // statements per tile
     // a ticket for position P must be in LDS one barrier before the fill pipeline first asks for it
     constexpr int LOOK = (NST + 1 + SPT - 1) / SPT + 1;
-    static_assert(NST >= 3 && NST * STAGE + LISTS + QSW_XCH <= 160 * 1024, "LDS");
+    static_assert(NST >= 3 && NST * STAGE + LISTS + QSW_XCH + PARK <= 160 * 1024, "LDS");
+    static_assert(PARK_OFF % 16 == 0 && PARK_OFF + 3 * PARK_STRIDE < 65536 * 4, "parked fragments: aligned b128 reads");
+    // the read-back sits in statements NSTMT - 6 and NSTMT - 5: never a stage's last two (hand-over, next stage's
+    // addresses), with one ordinary statement (lgkmcnt(0)) between them and the two that use the fragments
+    static_assert(PARK == 0 || (KSTG >= 8 && NSTMT >= 8), "parked read-back placement");
     static_assert((NST - 1) * PPS <= 56, "vmcnt range");
     static_assert((G - 1) * SLABB + 48 * SLAB + 2048 < 65536, "ds_read immediate offset");
     static_assert(2 * PPS == KSTG, "one piece after every other statement");
@@ -199,7 +270,7 @@ __global__ __launch_bounds__(256, 1) void cosine_topk_walk_kernel(const KParams 
     static_assert(LANDT >= 1 && LANDT * SPT * PPS - 1 >= (NST - 2) * PPS, "exchange pieces land before they are used");
     static_assert(LOOK <= 6, "ticket slots");
 
-    __shared__ __attribute__((aligned(1024))) char smem[NST * STAGE + LISTS + QSW_XCH];
+    __shared__ __attribute__((aligned(1024))) char smem[NST * STAGE + LISTS + QSW_XCH + PARK];
     // per-lane top-K lists: entry e of thread t at [e][t], e = qb * 2K + i (scores) / qb * 2K + K + i (rows):
     // ONE base address register per lane, everything else in the instruction's immediate offset
     float *lists = (float *)(smem + NST * STAGE);
@@ -319,6 +390,15 @@ __global__ __launch_bounds__(256, 1) void cosine_topk_walk_kernel(const KParams 
         // padding query slot: its all-zero scores must never open the insertion path
         thr[qb] = !live ? INFINITY : NEG_INF;
     });
+    if constexpr (PARK != 0) {
+        // park the last k-step (padding query slots park their zeroed fragments); a lane reads back only what it wrote,
+        // and LDS keeps a wave's accesses in order: no barrier.  (The read-back is asm: keep the stores in front of it.)
+        static_for<NQB>([&](auto qb_c) {
+            constexpr int qb = decltype(qb_c)::value;
+            *(FT *)(smem + PARK_OFF + qb * PARK_STRIDE + tid * 16) = qf[qb][KST - 1];
+        });
+        asm volatile("" ::: "memory");
+    }
     float *const my_lists = lists + tid;
     auto lst_v = [&](int qb, int i) -> float & { return my_lists[(qb * 2 * K + i) * QS_QROWS]; };
     auto lst_r = [&](int qb, int i) -> int & { return *(int *)&my_lists[(qb * 2 * K + K + i) * QS_QROWS]; };
@@ -355,7 +435,6 @@ __global__ __launch_bounds__(256, 1) void cosine_topk_walk_kernel(const KParams 
         if constexpr (MS == 32) return c32[(gi >> 2) * 2 + qb][4 * (gi & 3) + i];
         else return c16[gi * 4 + qb][i];
     };
-    auto grp_row = [](int gi) -> int { return MS == 32 ? (gi >> 2) * 32 + 8 * (gi & 3) : gi * 16; };
     // rows past the end of the shard and dead rows (tombstones, `where` filters) are struck out of the finished
     // tile, not out of the accumulator init: the common tile (full, no mask) pays nothing
     auto strike = [&](unsigned m0, unsigned m1, const int sub) {
@@ -378,13 +457,10 @@ __global__ __launch_bounds__(256, 1) void cosine_topk_walk_kernel(const KParams 
         });
     };
 
-    // ---- selection: lane-local, lists in LDS, entered only when some lane's score reaches its threshold ---
-    auto select = [&](auto qb_c, const int row_base, float *const my_lists) {
-        auto lst_v = [&](int qb, int i) -> float & { return my_lists[(qb * 2 * K + i) * QS_QROWS]; };
-        auto lst_r = [&](int qb, int i) -> int & { return *(int *)&my_lists[(qb * 2 * K + K + i) * QS_QROWS]; };
-        constexpr int qb = decltype(qb_c)::value;
-        // (the common case ends here: a wave alone on its SIMD pays every instruction of this test in matrix-pipe idle
-        // time -- v_max3 on the raw accumulators in one statement, not fmaxf, which quiets each MFMA result first: 9 instructions instead of 21)
+    // the largest of this lane's scores of query block qb in the finished tile
+    // (a wave alone on its SIMD pays every instruction of this in matrix-pipe idle time -- v_max3 on the raw
+    // accumulators in one statement, not fmaxf, which quiets each MFMA result first: 9 instructions instead of 21)
+    auto blk_max = [&](auto qb_c) -> float {
         auto max16 = [&](auto g0_c) -> float {   // groups g0 .. g0 + 3
             constexpr int g0 = decltype(g0_c)::value;
             using G0 = std::integral_constant<int, g0>;
@@ -398,48 +474,104 @@ __global__ __launch_bounds__(256, 1) void cosine_topk_walk_kernel(const KParams 
         };
         float mx = max16(std::integral_constant<int, 0>{});
         if constexpr (NGRP == 8) mx = fmaxf(mx, max16(std::integral_constant<int, 4>{}));
+        return mx;
+    };
+
+    // ---- selection: lane-local, lists in LDS, entered only when some lane's score reaches its threshold ---
+    auto select = [&](auto qb_c, const int row_base, float *const my_lists, const bool first_tile) {
+        auto lst_v = [&](int qb, int i) -> float & { return my_lists[(qb * 2 * K + i) * QS_QROWS]; };
+        auto lst_r = [&](int qb, int i) -> int & { return *(int *)&my_lists[(qb * 2 * K + K + i) * QS_QROWS]; };
+        constexpr int qb = decltype(qb_c)::value;
+        const float mx = blk_max(qb_c);   // (the common case ends with this test)
         float t = thr[qb];
         if (__builtin_amdgcn_ballot_w64(mx >= t) == 0ull) return;
-        // Which of this lane's NE scores reach its threshold.  While the thresholds are cold almost every element has
-        // SOME lane of the wave above its threshold, but a lane has only a few: walking the elements (below, `dense`)
-        // pays an insertion per element, walking each lane's own hits pays one per round of the slowest lane.
+        // Which of this lane's NE scores reach its threshold.
         constexpr int NE = NGRP * 4;
-        // A lane that has no threshold yet (the first tiles of the walk) would pass every score.  Only its K best of
-        // this tile can enter its list: raise the bar to (a lower bound of) the K-th largest of the lane's NE scores --
-        // K rounds of "largest score below the last one" (equal scores count once: the bar only gets lower), trees of
-        // independent max operations: issue-bound, where insertions are latency-bound, and three live registers (a
-        // sorting network on copies was faster still but took sixteen, and hipcc then spilled a Q fragment).
-        // Scores equal to the bar still pass and are settled in row order by the insertions.
-        float bar = t;
-        if (__builtin_amdgcn_ballot_w64(t == NEG_INF) != 0ull) {
-            float prev = INFINITY;
+        auto hits = [&](const float bar) -> unsigned {
+            unsigned m = 0;
+            static_for<NE>([&](auto e_c) {
+                constexpr int e = decltype(e_c)::value;
+                m |= score(qb_c, std::integral_constant<int, e / 4>{}, e % 4) >= bar ? (1u << e) : 0u;
+            });
+            return m;
+        };
+        // this lane's NE scores sorted, largest first: an odd-even merge sort on copies, of which only the comparators
+        // that v[0 .. K) depend on survive.  The sixteen registers it takes are the ones the parked k-step leaves free
+        // at a tile's end.
+        auto sorted_scores = [&](float (&v)[NE]) {
+            static_for<NE>([&](auto e_c) {
+                constexpr int e = decltype(e_c)::value;
+                v[e] = score(qb_c, std::integral_constant<int, e / 4>{}, e % 4);
+            });
+#pragma unroll
+            for (int pw = 1; pw < NE; pw *= 2)
+#pragma unroll
+                for (int kk = pw; kk >= 1; kk /= 2)
+#pragma unroll
+                    for (int j = kk % pw; j <= NE - 1 - kk; j += 2 * kk)
+#pragma unroll
+                        for (int i = 0; i <= (kk - 1 < NE - j - kk - 1 ? kk - 1 : NE - j - kk - 1); ++i)
+                            if ((i + j) / (2 * pw) == (i + j + kk) / (2 * pw)) {
+                                const float hi = fmaxf(v[i + j], v[i + j + kk]), lo = fminf(v[i + j], v[i + j + kk]);
+                                v[i + j] = hi;        // descending
+                                v[i + j + kk] = lo;
+                            }
+        };
+        // A lane walks ITS OWN hits (below): an insertion -- a latency-bound chain of ~60 instructions with the score
+        // picked by a tree of selects -- per round of the slowest lane.  While the thresholds are cold that lane has
+        // many: all NE in the first tile of the walk, about K in the next one (its threshold is its own K-th best so
+        // far).  From MANY hits on, the lane's K best scores of the tile are taken from the sorted scores instead, rank
+        // by rank with their rows (the lowest row not taken yet among the scores equal to rank r's: ties go to the lower
+        // row, as the walk has it), and go into the list in that order: issue-bound work without a branch.  Only a
+        // lane's K best of a tile can enter its list, whatever its threshold; -inf (struck rows) never does.
+        constexpr int MANY = 4;
+        const unsigned mask0 = hits(t);
+        TopList<K> L;
+        if (first_tile || __builtin_amdgcn_ballot_w64(__builtin_popcount(mask0) >= MANY) != 0ull) {
+            float v[NE];
+            sorted_scores(v);
+            float cv[K];
+            int cr[K];
+            unsigned used = 0;
 #pragma unroll
             for (int r = 0; r < K; ++r) {
-                float m = NEG_INF;
-                static_for<NGRP>([&](auto gi_c) {
-                    const float x0 = score(qb_c, gi_c, 0), x1 = score(qb_c, gi_c, 1);
-                    const float x2 = score(qb_c, gi_c, 2), x3 = score(qb_c, gi_c, 3);
-                    const float y0 = x0 < prev ? x0 : NEG_INF, y1 = x1 < prev ? x1 : NEG_INF;
-                    const float y2 = x2 < prev ? x2 : NEG_INF, y3 = x3 < prev ? x3 : NEG_INF;
-                    m = fmaxf(m, fmaxf(fmaxf(y0, y1), fmaxf(y2, y3)));
+                unsigned m = 0;
+                static_for<NE>([&](auto e_c) {
+                    constexpr int e = decltype(e_c)::value;
+                    m |= score(qb_c, std::integral_constant<int, e / 4>{}, e % 4) == v[r] ? (1u << e) : 0u;
                 });
-                prev = m;
+                m &= ~used;
+                const unsigned e = (unsigned)__builtin_ctz(m | (1u << (NE - 1)));
+                used |= 1u << e;
+                const int row = MS == 32 ? (int)(((e >> 4) << 5) + (((e >> 2) & 3u) << 3) + (e & 3u))
+                                         : (int)(((e >> 2) << 4) + (e & 3u));
+                const bool ok = v[r] >= t && v[r] > NEG_INF;
+                cv[r] = ok ? v[r] : NEG_INF;
+                cr[r] = ok ? row_base + row : INT_MAX;
             }
-            bar = fmaxf(t, prev);
-        }
-        unsigned mask = 0;
-        static_for<NE>([&](auto e_c) {
-            constexpr int e = decltype(e_c)::value;
-            mask |= score(qb_c, std::integral_constant<int, e / 4>{}, e % 4) >= bar ? (1u << e) : 0u;
-        });
-        TopList<K> L;   // (loaded only now: the network above wants the registers)
+            if (first_tile) {   // (the lists are empty: nothing to load, nothing to compare with)
 #pragma unroll
-        for (int i = 0; i < K; ++i) {
-            L.v[i] = lst_v(qb, i);
-            L.r[i] = lst_r(qb, i);
-        }
-        constexpr int DENSE_AT = NE == 16 ? 8 : 12;
-        if (__builtin_amdgcn_ballot_w64(__builtin_popcount(mask) > DENSE_AT) == 0ull) {
+                for (int r = 0; r < K; ++r) {
+                    L.v[r] = cv[r];
+                    L.r[r] = cr[r];
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < K; ++i) {
+                    L.v[i] = lst_v(qb, i);
+                    L.r[i] = lst_r(qb, i);
+                }
+#pragma unroll
+                for (int r = 0; r < K; ++r) L.insert_strict_flat(cv[r], cr[r]);   // (-inf changes nothing)
+            }
+            t = fmaxf(t, L.v[K - 1]);
+        } else {
+            unsigned mask = mask0;
+#pragma unroll
+            for (int i = 0; i < K; ++i) {
+                L.v[i] = lst_v(qb, i);
+                L.r[i] = lst_r(qb, i);
+            }
             while (__builtin_amdgcn_ballot_w64(mask != 0u) != 0ull) {
                 const bool valid = mask != 0u;
                 const unsigned e = (unsigned)__builtin_ctz(mask | (1u << (NE - 1)));   // lowest row first
@@ -461,23 +593,6 @@ __global__ __launch_bounds__(256, 1) void cosine_topk_walk_kernel(const KParams 
                 L.insert_strict_flat(valid && sc >= t ? sc : NEG_INF, row_base + row);
                 t = fmaxf(t, L.v[K - 1]);
             }
-        } else {
-            static_for<NGRP>([&](auto gi_c) {
-                constexpr int gi = decltype(gi_c)::value;
-                const float a0 = score(qb_c, gi_c, 0), a1 = score(qb_c, gi_c, 1);
-                const float a2 = score(qb_c, gi_c, 2), a3 = score(qb_c, gi_c, 3);
-                if (__builtin_amdgcn_ballot_w64(fmaxf(fmaxf(a0, a1), fmaxf(a2, a3)) >= t) != 0ull) {
-#pragma clang loop unroll(disable)
-                    for (int i = 0; i < 4; ++i) {
-                        const float s = i == 0 ? a0 : (i == 1 ? a1 : (i == 2 ? a2 : a3));
-                        const bool pass = s >= t;
-                        if (__builtin_amdgcn_ballot_w64(pass) != 0ull) {
-                            L.insert_strict(pass ? s : NEG_INF, row_base + grp_row(gi) + i);
-                            t = fmaxf(t, L.v[K - 1]);
-                        }
-                    }
-                }
-            });
         }
         // k-th best of the union of this lane's list and its neighbour's (the lanes that share the query hold
         // different rows): a lower bound of the final k-th score; with four lanes per query, the better of the two pairs
@@ -503,6 +618,18 @@ __global__ __launch_bounds__(256, 1) void cosine_topk_walk_kernel(const KParams 
         static_for<NQB>([&](auto qb_c) {
             constexpr int qb = decltype(qb_c)::value;
             float v = lst_v(qb, 0);   // the workgroup's best row of a query is in one of its lanes' lists
+            v = fmaxf(v, __shfl_xor(v, QW));
+            if constexpr (NSUB == 4) v = fmaxf(v, __shfl_xor(v, 32));
+            if (sub == 0) __hip_atomic_store(dst + qb * QW, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        });
+    };
+    // The first round's bests are the per-query maxima of tile 0, published BEFORE that tile's selection (the longest of
+    // the walk: every lane is cold): what the selection would leave at the head of the lane's list, a tile end earlier.
+    auto publish_tile_max = [&](const int ql, const int sub) {
+        float *dst = p.pub_best + ((size_t)by * walkers + bx) * QS_QROWS + wave * 64 + ql;
+        static_for<NQB>([&](auto qb_c) {
+            constexpr int qb = decltype(qb_c)::value;
+            float v = thr[qb] == INFINITY ? NEG_INF : blk_max(qb_c);   // (a padding query slot has no list)
             v = fmaxf(v, __shfl_xor(v, QW));
             if constexpr (NSUB == 4) v = fmaxf(v, __shfl_xor(v, 32));
             if (sub == 0) __hip_atomic_store(dst + qb * QW, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -537,14 +664,21 @@ __global__ __launch_bounds__(256, 1) void cosine_topk_walk_kernel(const KParams 
             thr[qb] = fmaxf(thr[qb], poll_lds[wave * 64 + qb * QW + ql]);
         });
     };
-    // Two rounds: bests after the first tile (a 64-row sample per workgroup) and again after tile pub1 (stragglers, and
-    // lists that have seen several tiles).  The responsible wave fetches the bests of its j-th query STEP tiles apart,
-    // starting the tile after the publication, and reduces them LANDT tiles later; thresholds are polled every tile
-    // while the rounds are fresh, every fourth tile afterwards.
+    // Two rounds: the maxima of the first tile (a 64-row sample per workgroup) and the bests after tile pub1 (stragglers,
+    // and lists that have seen several tiles).  The responsible wave fetches the bests of its j-th query STEP tiles apart
+    // and reduces them LANDT tiles later; thresholds are polled every tile while the rounds are fresh, every fourth tile
+    // afterwards.  Where in a tile's end the steps sit:
+    //   before the selection: tile 0's publication, the reduction (so that the threshold is out while this and the
+    //     other workgroups still select: their polls at the end of the SAME tile find it) and the pick-up of what a poll
+    //     brought (so that this tile's selection already runs on it);
+    //   after it: pub1's publication (it needs the lists), the fetches and the poll.
+    // Round 1: published in tile 0, query j fetched at tile j STEP (after tile 0's selection, ~10 us after everybody
+    // published), reduced at j STEP + LANDT; round 2: published at pub1, fetched from pub1 + 1.  With one responsible
+    // query and LANDT = 1 (768-d rows, 256 walkers) the first thresholds steer the selection of tile 2.
     constexpr int STEP = LANDT;
-    const int span = n_resp * STEP + LANDT + 1;     // tiles a round keeps the gather buffer busy
-    const int pub1 = span + 1 > 5 ? span + 1 : 5;
-    auto polled_at = [&](int t) -> bool { return t >= 1 + LANDT && (t < pub1 + span + 4 || (t & 3) == 3); };
+    const int span = n_resp * STEP + LANDT + 1;     // tiles a round keeps the gather buffer busy (round 1: one fewer)
+    const int pub1 = span + 1 > 5 ? span + 1 : 5;   // (round 1's last reduction is at tile span - 2 < pub1 + 1)
+    auto polled_at = [&](int t) -> bool { return t >= LANDT && (t < pub1 + span + 4 || (t & 3) == 3); };
     const int quiet = pub1 + span + 4 + LANDT;      // from this tile on nothing but the periodic poll happens
 
     // ---- main loop.  One continuous software pipeline over statements: statement s issues the LDS reads of
@@ -558,6 +692,8 @@ __global__ __launch_bounds__(256, 1) void cosine_topk_walk_kernel(const KParams 
     }
     if (any_tile) {
         FT fa0, fa1, fb0, fb1;  // A fragments of the current / next statement
+        FT pq0, pq1, pq2, pq3;  // the parked k-step's Q fragments: read back late in a tile, dead at its end
+        unsigned park_adr;      // (lives from the first read-back statement to the second)
         wait_vmcnt<(NST - 1) * PPS>();
         __builtin_amdgcn_s_barrier();
         {
@@ -617,10 +753,26 @@ __global__ __launch_bounds__(256, 1) void cosine_topk_walk_kernel(const KParams 
                         constexpr int ks = slab * 2 + (m >> 1), rp = m & 1;
                         constexpr int o0 = ng * SLABB + (nm & 1) * (32 * SLAB);
                         if constexpr (last) qsw_stage_addr(adr_lo, adr_hi, lane_off0, st_nxt);
-                        qsw_stmt16<DT, (ks < QA_STEPS), ks == 0, o0, o0 + 16 * SLAB, FT>(
-                            c16[rp * 8 + 0], c16[rp * 8 + 1], c16[rp * 8 + 2], c16[rp * 8 + 3], c16[rp * 8 + 4],
-                            c16[rp * 8 + 5], c16[rp * 8 + 6], c16[rp * 8 + 7], x0, x1, qf[0][ks], qf[1][ks], qf[2][ks],
-                            qf[3][ks], y0, y1, (nm >> 1) ? adr_hi : adr_lo);
+                        constexpr int tix = slab * 4 + m;           // statement of the tile
+                        if constexpr (PARK != 0 && (tix == NSTMT - 6 || tix == NSTMT - 5)) {
+                            static_assert(j < KSTG - 2 && ks < KST - 1, "read-back statement");
+                            constexpr bool second = tix == NSTMT - 5;
+                            qsw_stmt16_park<DT, (ks < QA_STEPS), second, o0, o0 + 16 * SLAB, PARK_STRIDE, FT>(
+                                c16[rp * 8 + 0], c16[rp * 8 + 1], c16[rp * 8 + 2], c16[rp * 8 + 3], c16[rp * 8 + 4],
+                                c16[rp * 8 + 5], c16[rp * 8 + 6], c16[rp * 8 + 7], x0, x1, qf[0][ks], qf[1][ks],
+                                qf[2][ks], qf[3][ks], y0, y1, (nm >> 1) ? adr_hi : adr_lo, second ? pq2 : pq0,
+                                second ? pq3 : pq1, park_adr, smem_base + (unsigned)(PARK_OFF + wave * 1024));
+                        } else if constexpr (PARK != 0 && ks == KST - 1) {
+                            qsw_stmt16<DT, false, false, o0, o0 + 16 * SLAB, FT>(
+                                c16[rp * 8 + 0], c16[rp * 8 + 1], c16[rp * 8 + 2], c16[rp * 8 + 3], c16[rp * 8 + 4],
+                                c16[rp * 8 + 5], c16[rp * 8 + 6], c16[rp * 8 + 7], x0, x1, pq0, pq1, pq2, pq3, y0, y1,
+                                (nm >> 1) ? adr_hi : adr_lo);
+                        } else {
+                            qsw_stmt16<DT, (ks < QA_STEPS), ks == 0, o0, o0 + 16 * SLAB, FT>(
+                                c16[rp * 8 + 0], c16[rp * 8 + 1], c16[rp * 8 + 2], c16[rp * 8 + 3], c16[rp * 8 + 4],
+                                c16[rp * 8 + 5], c16[rp * 8 + 6], c16[rp * 8 + 7], x0, x1, qf[0][ks], qf[1][ks],
+                                qf[2][ks], qf[3][ks], y0, y1, (nm >> 1) ? adr_hi : adr_lo);
+                        }
                     }
                     if constexpr (j == KSTG - 2) {
                         // every read of this stage is back: hand the ring over.  The stage just drained is
@@ -659,8 +811,25 @@ __global__ __launch_bounds__(256, 1) void cosine_topk_walk_kernel(const KParams 
             const int ql_t = ln & (QW - 1), sub_t = ln / QW;
             float *const lists_t = lists + wave * 64 + ln;
             const int row_base = (int)row0 + 4 * sub_t;
+            if (seeding && ti >= quiet) {
+                // both rounds are over: what is left is the poll every fourth tile (a workgroup that ran late publishes
+                // late) -- the same schedule as below, spelled out because the tests below cost a dozen scalar
+                // instructions per tile
+                if (((ti - LANDT) & 3) == 3) poll_consume(ql_t);
+            } else if (seeding) {
+                if (ti >= LANDT && polled_at(ti - LANDT)) poll_consume(ql_t);
+                if (ti == 0) publish_tile_max(ql_t, sub_t);
+                if (wave == 0) {
+                    // responsible query j of a round: fetched at tile (round's first fetch) + j STEP, reduced LANDT
+                    // tiles later (STEP = LANDT: the reduction of query j and the fetch of query j + 1 share a tile end,
+                    // reduction first)
+                    const int jc = (ti > pub1 ? ti - (pub1 + 1) : ti) - LANDT;
+                    if (jc >= 0 && jc % STEP == 0 && jc / STEP < n_resp && bx + (jc / STEP) * walkers < QS_QROWS)
+                        compute_thr(bx + (jc / STEP) * walkers);
+                }
+            }
             if (!(p.dbg & DBG_QS_NO_SELECT)) {
-                static_for<NQB>([&](auto qb_c) { select(qb_c, row_base, lists_t); });
+                static_for<NQB>([&](auto qb_c) { select(qb_c, row_base, lists_t, ti == 0); });
             } else {
                 if constexpr (MS == 32) asm volatile("" ::"v"(c32[0]), "v"(c32[1]), "v"(c32[2]), "v"(c32[3]));
                 else {
@@ -669,23 +838,12 @@ __global__ __launch_bounds__(256, 1) void cosine_topk_walk_kernel(const KParams 
                 }
             }
             if (seeding && ti >= quiet) {
-                // both rounds are over: what is left is the poll every fourth tile (a workgroup that ran late publishes
-                // late) -- the same schedule as below, spelled out because the tests below cost a dozen scalar
-                // instructions per tile
-                if (((ti - LANDT) & 3) == 3) poll_consume(ql_t);
                 if ((ti & 3) == 3 && wave == 0) poll_issue();
             } else if (seeding) {
-                if (ti >= LANDT && polled_at(ti - LANDT)) poll_consume(ql_t);
-                if (ti == 0 || ti == pub1) publish_bests(ql_t, sub_t, lists_t);
+                if (ti == pub1) publish_bests(ql_t, sub_t, lists_t);
                 if (wave == 0) {
-                    // responsible query j of a round: fetched at tile (round's publication) + 1 + j STEP, reduced LANDT
-                    // tiles later (STEP = LANDT: the reduction of query j and the fetch of query j + 1 share a tile end,
-                    // reduction first)
-                    const int rel = ti > pub1 ? ti - (pub1 + 1) : ti - 1;
-                    const int jc = rel - LANDT, jg = rel;
-                    if (jc >= 0 && jc % STEP == 0 && jc / STEP < n_resp && bx + (jc / STEP) * walkers < QS_QROWS)
-                        compute_thr(bx + (jc / STEP) * walkers);
-                    if (jg >= 0 && jg % STEP == 0 && jg / STEP < n_resp && bx + (jg / STEP) * walkers < QS_QROWS)
+                    const int jg = ti > pub1 ? ti - (pub1 + 1) : ti;
+                    if (jg % STEP == 0 && jg / STEP < n_resp && bx + (jg / STEP) * walkers < QS_QROWS)
                         gather_issue(bx + (jg / STEP) * walkers);
                     if (polled_at(ti)) poll_issue();
                 }
