@@ -705,6 +705,78 @@ int mmrag_related_groups(const void *set_rows, int M, const int32_t *set_off, in
                          int32_t *out_covered, float *out_best, int64_t *out_best_row, void *workspace,
                          size_t workspace_bytes, void *stream);
 
+/* Filtered retrieval (csrc/filtered.hip): metadata filters evaluated on the device into row bitmaps, and a batch of
+ * queries answered in ONE masked scan, each query seeing only the rows of its own filter's bitmap.
+ * VectorIndex.filtered_search; the filter compiler is multimodal_rag_amd/filters.py.
+ *
+ * A bitmap of n rows holds W = mmrag_filter_words(n) = 4 * ceil(n / 128) words (a 128-row tile is one 16-byte group):
+ * bit r & 31 of word r >> 5 is row r.
+ *
+ * Program.  A filter is a postfix program over a boolean stack of at most 32 entries; every row runs the same
+ * instructions on its own column values.  A column is MMRAG_FILTER_NUMBER (dev float64 [n], NaN = missing) or
+ * MMRAG_FILTER_STRING (dev int32 [n] ordinals into the caller's dictionary, -1 = missing, read as NaN); a row's operand
+ * is its column value as a double.
+ *   TRUE, FALSE          push the constant
+ *   AND, OR              pop two, push the result
+ *   EQ NE GT GE LT LE    push (column[row] OP value), the IEEE comparison: false against NaN, NE true
+ *   IN, NIN              push whether column[row] equals any / none of set_values[set_off .. set_off + set_len),
+ *                        set_len in 0..MMRAG_MAX_FILTER_SET
+ * The answer is the top of the stack after the last instruction.  A program holds 1..MMRAG_MAX_FILTER_OPS instructions;
+ * program f is ops[prog_off[f] .. prog_off[f + 1]).
+ *
+ * mmrag_filter_eval: out_bits[f][w] for F programs, ANDed with alive_bits when given; bits at and past n are zero.  A
+ * pure function of its inputs.  One launch, no host synchronisation, no atomics.
+ *   ops, prog_off, set_values   dev; n_ops, n_set their lengths (prog_off holds F + 1 ascending offsets)
+ *   columns, kinds              HOST arrays of n_columns <= MMRAG_MAX_FILTER_COLUMNS device pointers and their kinds
+ *   alive_bits                  dev, optional, at least ceil(n / 32) words
+ *   out_bits                    dev [F, W]
+ * MMRAG_EINVAL before the launch: a null pointer, F < 1, n_ops < 1, n outside 0..2^31-1, n_columns out of range, a kind
+ * that is neither.  The tables live on the device and are not read by the host: a program outside ops or longer than
+ * MMRAG_MAX_FILTER_OPS matches nothing, a column index out of range reads as missing, a set out of range as empty (the
+ * Python wrapper checks the host copies it holds).
+ *
+ * mmrag_filtered_topk: query b sees row r iff r < n and bit r of vis_bits[filter_of_query[b]] is set (the bitmaps may
+ * come from mmrag_filter_eval or from anywhere else; bits at and past n are ignored).
+ * Contract
+ *   - out_scores / out_rows [B, k] as mmrag_cosine_topk_deep's: score descending, ties to the lower row,
+ *     row + row_offset, (-inf, -1) padded;
+ *   - a score's bits depend on the query row, the stored row and d alone (the pair-tile body's fixed K order) and equal
+ *     mmrag_scoped_topk's for the same two rows: not on the batch, the filters, the grid or whether bound passes ran;
+ *   - a 128-row tile in which no query of a 128-query tile sees a row is not fetched for that query tile;
+ *   - exact under ANY bitmap: when n exceeds the candidate slots of a query (32 k, at least 16384) a sampled lower bound
+ *     on each query's k-th score is staged first, from the VISIBLE rows of a strided sample of whole tiles (the k-th
+ *     best of any subset of a query's visible rows is at most its true k-th), and only scores at or above it are kept;
+ *   - at most one stream synchronisation per call, and only when n exceeds the candidate slots.
+ *   q, rows          as mmrag_scoped_topk's; MMRAG_F8E4M3 returns MMRAG_EUNSUPPORTED
+ *   k                1..MMRAG_MAX_K_DEEP
+ *   filter_of_query  dev [B] int32 in 0..F-1 (anything else sees nothing; the Python wrapper checks its host copy)
+ *   vis_bits         dev [F, W]
+ *   workspace        dev, >= mmrag_filtered_topk_workspace_bytes(B, n, k) bytes (0 for arguments out of range), 16-byte
+ *                    aligned; short or misaligned: MMRAG_EWORKSPACE
+ * MMRAG_EINVAL before anything is launched: a null pointer, B < 1, F < 1, n < 0 or >= 2^31, k out of range, d <= 0,
+ * ld < d or not whole slabs. */
+#define MMRAG_MAX_FILTER_OPS 32
+#define MMRAG_MAX_FILTER_SET 64
+#define MMRAG_MAX_FILTER_COLUMNS 16
+#define MMRAG_FILTER_NUMBER 0
+#define MMRAG_FILTER_STRING 1
+enum {
+    MMRAG_FILTER_TRUE = 0, MMRAG_FILTER_FALSE, MMRAG_FILTER_AND, MMRAG_FILTER_OR, MMRAG_FILTER_EQ, MMRAG_FILTER_NE,
+    MMRAG_FILTER_GT, MMRAG_FILTER_GE, MMRAG_FILTER_LT, MMRAG_FILTER_LE, MMRAG_FILTER_IN, MMRAG_FILTER_NIN
+};
+typedef struct {
+    int32_t code, column, set_off, set_len;
+    double value;
+} mmrag_filter_op; /* 24 bytes */
+int64_t mmrag_filter_words(int64_t n);
+int mmrag_filter_eval(const mmrag_filter_op *ops, int n_ops, const int32_t *prog_off, int F, const double *set_values,
+                      int n_set, const void *const *columns, const int32_t *kinds, int n_columns, int64_t n,
+                      const uint32_t *alive_bits, uint32_t *out_bits, void *stream);
+size_t mmrag_filtered_topk_workspace_bytes(int B, int64_t n, int k);
+int mmrag_filtered_topk(const void *q, const void *rows, int B, int64_t n, int d, int64_t ld, int dtype, int k,
+                        int64_t row_offset, const int32_t *filter_of_query, int F, const uint32_t *vis_bits,
+                        float *out_scores, int64_t *out_rows, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Late-interaction re-ranking (ColBERT's MaxSim) with the bi-encoder alone.  The reference has no counterpart: its
  * EmbeddingManager.rerank_results is a placeholder (app/utils/embedder.py:834-859).  The encoder's per-token outputs are

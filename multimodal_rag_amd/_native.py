@@ -31,6 +31,8 @@ FUSE_METHODS = {"rrf": 0, "max": 1}
 MAX_JOIN_PAIRS = 1 << 26   # mmrag_sim_join (MMRAG_MAX_JOIN_PAIRS)
 MAX_CLUSTERS = 4096   # mmrag_kmeans_assign / mmrag_cluster_sums (MMRAG_MAX_CLUSTERS)
 MAX_SCOPE_GROUPS = 64   # mmrag_scoped_topk (MMRAG_MAX_SCOPE_GROUPS)
+# mmrag_filter_eval (MMRAG_MAX_FILTER_OPS, MMRAG_MAX_FILTER_SET, MMRAG_MAX_FILTER_COLUMNS)
+MAX_FILTER_OPS, MAX_FILTER_SET, MAX_FILTER_COLUMNS = 32, 64, 16
 MAX_RELATED_ROWS, MAX_RELATED_SETS = 8192, 64   # mmrag_related_groups (MMRAG_MAX_RELATED_ROWS, MMRAG_MAX_RELATED_SETS)
 MAX_RECOMMEND_EXAMPLES = 16  # mmrag_recommend_topk (MMRAG_MAX_RECOMMEND_EXAMPLES)
 # mmrag_maxsim_scores (MMRAG_MAX_LATE_QUERY_TOKENS, MMRAG_MAX_LATE_DOC_TOKENS)
@@ -231,6 +233,20 @@ def _declare(lib):
                                       c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.mmrag_internal_scoped_topk_ex.restype = c_int
     lib.mmrag_internal_scoped_topk_ex.argtypes = lib.mmrag_scoped_topk.argtypes + [c_int64]
+    # filtered retrieval (csrc/filtered.hip); the _ex entry adds a candidate capacity, debug switches and the counter of
+    # issued items (tests and tools, not in include/mmrag.h)
+    lib.mmrag_filter_words.restype = c_int64
+    lib.mmrag_filter_words.argtypes = [c_int64]
+    lib.mmrag_filter_eval.restype = c_int
+    lib.mmrag_filter_eval.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                      c_int64, c_void_p, c_void_p, c_void_p]
+    lib.mmrag_filtered_topk_workspace_bytes.restype = c_size_t
+    lib.mmrag_filtered_topk_workspace_bytes.argtypes = [c_int, c_int64, c_int]
+    lib.mmrag_filtered_topk.restype = c_int
+    lib.mmrag_filtered_topk.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int64, c_int, c_int, c_int64,
+                                        c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.mmrag_internal_filtered_topk_ex.restype = c_int
+    lib.mmrag_internal_filtered_topk_ex.argtypes = lib.mmrag_filtered_topk.argtypes + [c_int64, ctypes.c_uint, c_void_p]
     # related groups (csrc/related.hip); the _ex entry adds the scan's grid (tests, not in include/mmrag.h)
     lib.mmrag_related_groups_workspace_bytes.restype = c_size_t
     lib.mmrag_related_groups_workspace_bytes.argtypes = [c_int, c_int, c_int64, c_int, c_int]
@@ -752,6 +768,157 @@ def scoped_topk(q: torch.Tensor, rows: torch.Tensor, n: int, d: int, k: int, gro
             workspace.data_ptr(), _nbytes(workspace), _stream_ptr(dev), int(cap))
     _check(st, "mmrag_scoped_topk")
     return out_s, out_r
+
+
+def filter_words(n: int) -> int:
+    """words of a row bitmap of n rows (mmrag_filter_words): 4 per 128-row tile; 0 for n outside 0..2^31-1"""
+    return int(lib().mmrag_filter_words(int(n)))
+
+
+def filtered_topk_workspace_bytes(B: int, n: int, k: int) -> int:
+    return int(lib().mmrag_filtered_topk_workspace_bytes(int(B), int(n), int(k)))
+
+
+def check_filter_programs(ops: np.ndarray, prog_off, set_values, n_columns: int) -> int:
+    """The program tables of filter_eval as HOST arrays (filters.pack_programs), checked the way the device cannot
+    report: returns F.  Raises MMRagNativeError for offsets that do not ascend from 0 to len(ops), a program of 0 or
+    more than MAX_FILTER_OPS instructions, an unknown code, a column index outside 0..n_columns-1, a set range outside
+    set_values or longer than MAX_FILTER_SET, a constant that is not finite, and a program that does not leave exactly
+    one value on a stack that never underflows."""
+    off = [int(v) for v in np.asarray(prog_off).reshape(-1)]
+    F, n_ops, n_set = len(off) - 1, len(ops), len(set_values)
+    if F < 1 or off[0] != 0 or off[-1] != n_ops or any(b < a for a, b in zip(off, off[1:])):
+        raise MMRagNativeError("filter_eval: prog_off must hold F + 1 >= 2 ascending offsets from 0 to len(ops)")
+    if n_set and not np.isfinite(np.asarray(set_values, dtype=np.float64)).all():
+        raise MMRagNativeError("filter_eval: set_values must be finite")
+    for f in range(F):
+        lo, hi = off[f], off[f + 1]
+        if not 1 <= hi - lo <= MAX_FILTER_OPS:
+            raise MMRagNativeError(f"filter_eval: program {f} holds {hi - lo} instructions, 1..{MAX_FILTER_OPS}")
+        depth = 0
+        for i in range(lo, hi):
+            code, column, set_off, set_len, value = (ops[i][name].item() for name in
+                                                     ("code", "column", "set_off", "set_len", "value"))
+            if not 0 <= code <= 11:
+                raise MMRagNativeError(f"filter_eval: instruction {i} has the unknown code {code}")
+            if code in (2, 3):
+                depth -= 1
+                if depth < 1:
+                    raise MMRagNativeError(f"filter_eval: program {f} pops an empty stack")
+                continue
+            depth += 1
+            if code >= 4 and not 0 <= column < n_columns:
+                raise MMRagNativeError(f"filter_eval: instruction {i} reads column {column} outside 0..{n_columns - 1}")
+            if code >= 10 and not (0 <= set_len <= MAX_FILTER_SET and 0 <= set_off <= n_set - set_len):
+                raise MMRagNativeError(f"filter_eval: instruction {i} reads a set outside set_values "
+                                       f"(offset {set_off}, length {set_len}, at most {MAX_FILTER_SET})")
+            if 4 <= code <= 9 and not np.isfinite(value):
+                raise MMRagNativeError(f"filter_eval: instruction {i} compares with {value}")
+        if depth != 1:
+            raise MMRagNativeError(f"filter_eval: program {f} leaves {depth} values on the stack")
+    return F
+
+
+def filter_eval(ops: np.ndarray, prog_off, set_values, columns, n: int, alive_bits: Optional[torch.Tensor] = None,
+                device=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """F filter programs over n rows -> bitmaps [F, filter_words(n)] int32 on the device (include/mmrag.h
+    mmrag_filter_eval, csrc/filtered.hip), ANDed with alive_bits when given; bits at and past n are zero.  `ops`
+    (filters.OP_DTYPE), `prog_off` and `set_values` are HOST arrays (filters.pack_programs): checked here
+    (check_filter_programs) and uploaded in one transfer.  `columns`: at most MAX_FILTER_COLUMNS device tensors of at
+    least n values, float64 (numbers, NaN = missing) or int32 (string ordinals, -1 = missing).  `out`: a contiguous
+    device int32 [F, filter_words(n)] to write instead of a new tensor.  One launch on the current stream, no host
+    synchronisation."""
+    columns = list(columns)
+    n = int(n)
+    if len(columns) > MAX_FILTER_COLUMNS:
+        raise MMRagNativeError(f"filter_eval: {len(columns)} columns, at most {MAX_FILTER_COLUMNS}")
+    _dev_check(alive_bits, *columns)
+    dev = columns[0].device if columns else (alive_bits.device if alive_bits is not None else torch.device(device))
+    for c in columns:
+        if (c.dim() != 1 or c.dtype not in (torch.float64, torch.int32) or not c.is_contiguous() or c.numel() < n
+                or c.device != dev):
+            raise MMRagNativeError("filter_eval: a column must be a contiguous float64 or int32 tensor of at least n "
+                                   "values on one device")
+    if alive_bits is not None and (alive_bits.dim() != 1 or alive_bits.dtype != torch.int32
+                                   or not alive_bits.is_contiguous() or alive_bits.numel() * 32 < n
+                                   or alive_bits.device != dev):
+        raise MMRagNativeError("filter_eval: alive must be a contiguous int32 bitmap of at least n bits on the columns' "
+                               "device")
+    ops = np.ascontiguousarray(ops)
+    if ops.dtype.itemsize != 24:
+        raise MMRagNativeError("filter_eval: ops must be an array of filters.OP_DTYPE (24-byte instructions)")
+    off = np.ascontiguousarray(prog_off, dtype=np.int32).reshape(-1)
+    sets = np.ascontiguousarray(set_values, dtype=np.float64).reshape(-1)
+    F = check_filter_programs(ops, off, sets, len(columns))
+    W = filter_words(n)
+    if n < 0 or (W == 0 and n != 0):
+        raise MMRagNativeError(f"filter_eval: n={n} outside 0..2^31-1")
+    # one pinned copy: [ops | set_values (8-byte aligned: 24 n_ops is) | prog_off]; a spare double keeps the pointer real
+    blob = np.concatenate([ops.view(np.uint8).reshape(-1), np.append(sets, 0.0).view(np.uint8), off.view(np.uint8)])
+    packed = _pinned_to_device(torch.from_numpy(blob), dev)
+    at_sets = ops.nbytes
+    at_off = at_sets + (sets.size + 1) * 8
+    if out is None:
+        out = torch.empty((F, W), dtype=torch.int32, device=dev)
+    elif (not out.is_cuda or out.dtype != torch.int32 or not out.is_contiguous() or tuple(out.shape) != (F, W)
+          or out.device != dev):
+        raise MMRagNativeError(f"filter_eval: out must be a contiguous int32 [{F}, {W}] tensor on the columns' device")
+    if W == 0:
+        return out
+    ptrs = (c_void_p * MAX_FILTER_COLUMNS)(*[c.data_ptr() for c in columns])
+    kinds = (c_int32 * MAX_FILTER_COLUMNS)(*[0 if c.dtype == torch.float64 else 1 for c in columns])
+    with torch.cuda.device(dev):
+        st = lib().mmrag_filter_eval(packed.data_ptr(), len(ops), packed.data_ptr() + at_off, F,
+                                     packed.data_ptr() + at_sets, sets.size, ptrs, kinds, len(columns), n,
+                                     alive_bits.data_ptr() if alive_bits is not None else None, out.data_ptr(),
+                                     _stream_ptr(dev))
+    _check(st, "mmrag_filter_eval")
+    return out
+
+
+def filtered_topk(q: torch.Tensor, rows: torch.Tensor, n: int, d: int, k: int, filter_of_query, vis_bits: torch.Tensor,
+                  workspace: Optional[torch.Tensor] = None, row_offset: int = 0, cap: int = 0, dbg: int = 0,
+                  count_items: bool = False):
+    """Top-k of each query of q [B, ld] over the rows ITS bitmap holds among the first n of `rows` [cap, ld]
+    (include/mmrag.h mmrag_filtered_topk): query b sees row r iff bit r of vis_bits[filter_of_query[b]] is set.
+    `vis_bits`: a contiguous device int32 [F, filter_words(n)], from filter_eval or from anywhere else.
+    `filter_of_query`: B HOST integers in 0..F-1, checked here (the device cannot report them) and uploaded.  Returns
+    (scores [B, k] float32 descending, rows [B, k] int64 + row_offset), (-inf, -1) padded.  No host synchronisation
+    unless n exceeds the candidate slots of a query.  `cap`, `dbg`, `count_items` (tests and tools): fewer slots;
+    dbg & 1 = no bound passes; a third result, the device int64 count of (row tile, query tile) items the main pass
+    issued."""
+    _dev_check(q, rows, vis_bits)
+    _check_q_rows("filtered_topk", q, rows, n, other="rows")
+    _check_stored_rows("filtered_topk", rows)
+    B, ld = q.shape
+    n, k = int(n), int(k)
+    if not 1 <= k <= MAX_K_DEEP:
+        raise ValueError(f"filtered_topk: k={k} outside 1..{MAX_K_DEEP}")
+    dev = q.device
+    W = filter_words(n)
+    if (vis_bits.dim() != 2 or vis_bits.dtype != torch.int32 or not vis_bits.is_contiguous() or vis_bits.shape[0] < 1
+            or vis_bits.shape[1] != W or vis_bits.device != dev):
+        raise MMRagNativeError(f"filtered_topk: vis_bits must be a contiguous int32 [F, {W}] tensor on the rows' device")
+    F = vis_bits.shape[0]
+    foq = torch.as_tensor(filter_of_query, dtype=torch.int32).reshape(-1).cpu()
+    if foq.numel() != B:
+        raise MMRagNativeError(f"filtered_topk: filter_of_query holds {foq.numel()} entries for {B} queries")
+    if B and (int(foq.min()) < 0 or int(foq.max()) >= F):
+        raise MMRagNativeError(f"filtered_topk: filter_of_query outside 0..{F - 1}")
+    foq_dev = _pinned_to_device(foq, dev)
+    need = filtered_topk_workspace_bytes(B, n, k)
+    if workspace is None or _nbytes(workspace) < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    out_s, out_r = _topk_out(B, k, dev)
+    items = torch.zeros(1, dtype=torch.int64, device=dev) if count_items else None
+    with torch.cuda.device(dev):
+        st = lib().mmrag_internal_filtered_topk_ex(
+            q.data_ptr(), rows.data_ptr(), B, n, int(d), ld, _TORCH2DT[q.dtype], k, int(row_offset), foq_dev.data_ptr(),
+            F, vis_bits.data_ptr() if vis_bits.numel() else None, out_s.data_ptr(), out_r.data_ptr(),
+            workspace.data_ptr(), _nbytes(workspace), _stream_ptr(dev), int(cap), int(dbg),
+            items.data_ptr() if items is not None else None)
+    _check(st, "mmrag_filtered_topk")
+    return (out_s, out_r, items) if count_items else (out_s, out_r)
 
 
 def related_groups_workspace_bytes(M: int, S: int, n: int, n_groups: int, k: int) -> int:

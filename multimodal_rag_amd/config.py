@@ -95,6 +95,15 @@ class Settings:
     # min(max(MMRAG_GROUP_CANDIDATES, 4 * n_groups * group_size), 4096) dense hits; queries that neither found
     # n_groups groups nor exhausted their list are searched again 4 x deeper, up to 4096
     MMRAG_GROUP_CANDIDATES: int = field(default_factory=lambda: int(os.getenv("MMRAG_GROUP_CANDIDATES", "64")))
+    # metadata filters on the device (multimodal_rag_amd/filters.py, csrc/filtered.hip).  "true": a `where` the compiler
+    # covers becomes its row bitmap with one kernel launch over typed metadata columns instead of on the host (the words
+    # are identical, so every retrieval mode returns what it returned), and the dispatcher batches requests with
+    # different filters into one filtered_query.  VectorIndex.filtered_search evaluates at most
+    # MMRAG_FILTER_BITMAP_BYTES of bitmaps (distinct filters x 4 * ceil(n / 128) words) per launch; more are served in
+    # slices
+    MMRAG_DEVICE_FILTERS: bool = field(default_factory=lambda: _b("MMRAG_DEVICE_FILTERS", "false"))
+    MMRAG_FILTER_BITMAP_BYTES: int = field(default_factory=lambda: int(os.getenv("MMRAG_FILTER_BITMAP_BYTES",
+                                                                                 str(256 << 20))))
     # multi-query retrieval (VectorIndex.fused_query, csrc/fuse.hip): every phrasing of a question returns
     # max(n_results, MMRAG_FUSE_CANDIDATES) hits (at most 256); the lists are fused by MMRAG_FUSE_METHOD: "rrf" = sum of
     # weight / (MMRAG_FUSE_RRF_K + rank), "max" = largest weight * cosine

@@ -19,14 +19,18 @@ ScopedFn = Callable[[List[str], int, List[List[str]]], Awaitable[List[Dict[str, 
 BoostedFn = Callable[[List[str], int, Optional[Dict], Any], Awaitable[List[Dict[str, Any]]]]
 # (requests, k, filter): ONE encode of every request's texts and ONE recommend search (csrc/recommend.hip).  An 'error'
 # dict it returns is the request's own fault (a ValueError for its caller); anything else it raises
+# (texts, k, each text's filter or None): ONE batched encode and ONE filtered search whatever the filters
+# (csrc/filtered.hip)
+FilteredFn = Callable[[List[str], int, List[Optional[Dict]]], Awaitable[List[Dict[str, Any]]]]
 RecommendFn = Callable[[List[Dict[str, Any]], int, Optional[Dict]], Awaitable[List[Dict[str, Any]]]]
 
 
 class QueryDispatcher:
     def __init__(self, batch_fn: BatchFn, max_batch: int = 256, max_wait_ms: float = 2.0, idle_ms: float = 0.25,
                  scoped_fn: Optional[ScopedFn] = None, boosted_fn: Optional[BoostedFn] = None,
-                 recommend_fn: Optional[RecommendFn] = None):
+                 recommend_fn: Optional[RecommendFn] = None, filtered_fn: Optional[FilteredFn] = None):
         self.batch_fn = batch_fn
+        self.filtered_fn = filtered_fn
         self.scoped_fn = scoped_fn
         self.boosted_fn = boosted_fn
         self.recommend_fn = recommend_fn
@@ -64,7 +68,9 @@ class QueryDispatcher:
         that score prior, and requests of one k, filter and spec key share one batch.
         `doc_ids`: answer from these documents only.  With a `scoped_fn`, requests that carry doc_ids and no
         filter_dict share one batch per k whatever their documents; without one (or next to a filter_dict) the
-        restriction becomes part of the filter and the request is grouped by it like any other."""
+        restriction becomes part of the filter and the request is grouped by it like any other.
+        With a `filtered_fn`, requests that carry a filter_dict (doc_ids folded into it included) and neither a boost
+        nor a recommend request share one batch per k whatever their filters."""
         if boost is not None and (self.boosted_fn is None or doc_ids is not None):
             raise ValueError("a boosted request needs a boosted_fn and takes no doc_ids")
         if recommend is not None and (self.recommend_fn is None or doc_ids is not None or boost is not None):
@@ -95,7 +101,8 @@ class QueryDispatcher:
                     batch.append(await asyncio.wait_for(self._queue.get(), timeout))
                 except asyncio.TimeoutError:
                     break
-            # one kernel batch per (k, filter) group; the requests with doc_ids are one group per k, the boosted ones
+            # one kernel batch per (k, filter) group (per k alone with a filtered_fn, for the requests that carry a
+            # filter); the requests with doc_ids are one group per k, the boosted ones
             # one per (k, filter, spec key), the recommend ones one per (k, filter)
             groups: Dict[Any, List[int]] = {}
             for i, (_, k, flt, _, docs, boost, rec) in enumerate(batch):
@@ -105,6 +112,8 @@ class QueryDispatcher:
                     key = ("boosted", k, repr(flt), boost.batch_key())
                 elif docs is not None:
                     key = ("scoped", k)
+                elif flt is not None and self.filtered_fn is not None:
+                    key = ("filtered", k)
                 else:
                     key = ("plain", k, repr(flt))
                 groups.setdefault(key, []).append(i)
@@ -117,6 +126,8 @@ class QueryDispatcher:
                         results = await self.boosted_fn([batch[i][0] for i in idxs], k, flt, batch[idxs[0]][5])
                     elif key[0] == "scoped":
                         results = await self.scoped_fn([batch[i][0] for i in idxs], k, [batch[i][4] for i in idxs])
+                    elif key[0] == "filtered":
+                        results = await self.filtered_fn([batch[i][0] for i in idxs], k, [batch[i][2] for i in idxs])
                     else:
                         results = await self.batch_fn([batch[i][0] for i in idxs], k, flt)
                     for i, res in zip(idxs, results):

@@ -330,6 +330,9 @@ class EmbeddingManager:
         def scoped(texts, n_results, doc_ids_per_query):      # the dispatcher's (texts, k, documents) order
             return self.batch_scoped_query(texts, doc_ids_per_query, n_results=n_results)
 
+        def filtered(texts, n_results, filters):              # the dispatcher's (texts, k, filters) order
+            return self.batch_filtered_query(texts, filters, n_results=n_results)
+
         def boosted(texts, n_results, filter_dict, spec):
             return self.batch_boosted_query(texts, n_results=n_results, filter_dict=filter_dict, boost=spec)
 
@@ -340,7 +343,9 @@ class EmbeddingManager:
         self._dispatcher = QueryDispatcher(self.batch_query, max_batch=max_batch, max_wait_ms=max_wait_ms,
                                            scoped_fn=scoped if self.supports_scoped() else None,
                                            boosted_fn=boosted if self.supports_boost() else None,
-                                           recommend_fn=recommend if self.supports_recommend() else None)
+                                           recommend_fn=recommend if self.supports_recommend() else None,
+                                           filtered_fn=filtered if (settings.MMRAG_DEVICE_FILTERS
+                                                                    and self.supports_device_filters()) else None)
         return self._dispatcher
 
     _INCLUDE = ["metadatas", "documents", "distances"]
@@ -488,6 +493,41 @@ class EmbeddingManager:
             raise ValueError(f"{len(doc_ids_per_query)} document lists for {len(queries)} queries")
         live = [list(ids) for q, ids in zip(queries, doc_ids_per_query) if q and q.strip()]    # as _batch picks them
         return await self._batch("Batch scoped query", None, _EMPTY, self._answer_scoped, queries, n_results, live)
+
+    def supports_device_filters(self) -> bool:
+        """True when ONE search serves a batch whose queries each carry their own metadata filter, evaluated on the
+        device (VectorIndex.filtered_query; a float8_e4m3fn collection needs its re-scoring plane).  Any other
+        collection still answers batch_filtered_query, by one filtered search per distinct filter."""
+        return self.collection is None or (hasattr(self.collection, "filtered_query") and self._has_full_rows())
+
+    def _answer_filtered(self, texts: Sequence[str], n_results: int,
+                         filters: Sequence[Optional[Dict]]) -> List[Dict[str, Any]]:
+        """blocking, one worker thread: cached or fresh embeddings (ONE encoder pass for the misses), then ONE
+        collection.filtered_query for all of them; a collection without it is asked once per distinct filter"""
+        emb = self._embed(texts)
+        if hasattr(self.collection, "filtered_query") and self._has_full_rows():
+            res = self.collection.filtered_query(emb, n_results=n_results, wheres=list(filters), include=self._INCLUDE)
+            return self._split(res, len(texts))
+        by_filter: Dict[str, List[int]] = {}
+        for at, flt in enumerate(filters):
+            by_filter.setdefault(repr(flt), []).append(at)
+        out: List[Optional[Dict[str, Any]]] = [None] * len(texts)
+        for mine in by_filter.values():
+            res = self.collection.query(query_embeddings=emb[mine], n_results=n_results, where=filters[mine[0]],
+                                        include=self._INCLUDE)
+            for at, hit in zip(mine, self._split(res, len(mine))):
+                out[at] = hit
+        return out  # type: ignore[return-value]
+
+    async def batch_filtered_query(self, queries: List[str], filters: Sequence[Optional[Dict]],
+                                   n_results: int = 5) -> List[Dict[str, Any]]:
+        """batch_scoped_query's twin for metadata filters: query i is answered from the rows that match filters[i] (None
+        = every row); one batched encode and one search for all of them whatever the filters; a query that cannot be
+        answered gets a dict with empty lists and an 'error' message."""
+        if len(filters) != len(queries):
+            raise ValueError(f"{len(filters)} filters for {len(queries)} queries")
+        live = [flt for q, flt in zip(queries, filters) if q and q.strip()]    # as _batch picks them
+        return await self._batch("Batch filtered query", None, _EMPTY, self._answer_filtered, queries, n_results, live)
 
     def supports_boost(self) -> bool:
         """True when the collection can rank with a score prior (a single-GPU VectorIndex with full-precision rows; not

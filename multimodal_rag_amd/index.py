@@ -29,6 +29,7 @@ import torch
 
 from . import _native
 from .boost import BoostSpec, check_prior_values
+from .filters import ColumnRegistry, names_added_at, pack_programs, try_compile
 from .hostutil import load_hostrows
 from .tracing import stage
 
@@ -237,6 +238,10 @@ class VectorIndex:
         # spec columns by (canonical JSON of the spec, floored now) -> {"spec", "now", "col"}; at most MAX_SPEC_COLUMNS
         self._spec_cols: "OrderedDict[Tuple[str, float], Dict[str, Any]]" = OrderedDict()
         self.f32_exact = bool(settings.MMRAG_F32_EXACT_SEARCH)   # float32 collections only (see config.py)
+        # typed metadata columns of the device filters (filters.py): built per key on first use, derived, not persisted
+        self._filter_cols = ColumnRegistry(lambda: (self._metadatas, self._n, self._added_at))
+        self._filtered_ws: Optional[torch.Tensor] = None   # workspace of the filtered search, reused
+        self.device_filters = bool(settings.MMRAG_DEVICE_FILTERS)   # _where_bits builds its bitmap on the device
 
     def _new_rows(self, rows: int, zero: bool) -> torch.Tensor:
         """[rows, ld] in the storage dtype; FP8 codes are allocated as bytes and viewed as float8_e4m3fn"""
@@ -729,6 +734,7 @@ class VectorIndex:
             new = st["spec"].column(times, self._metadatas[lo:hi], st["now"])
             st["col"][lo:hi].copy_(_native._pinned_to_device(torch.from_numpy(new), self.device))
         self._meta_index.append(self._metadatas[lo:hi])
+        self._filter_cols.appended(self._metadatas[lo:hi], lo)
         self._set_alive(lo, hi)
         if self._lex is not None:
             self._lex.append(self._documents[lo:hi])
@@ -763,6 +769,10 @@ class VectorIndex:
         """device alive bitmap for one search: tombstones AND `where` (ANDed on the device), or None = every row"""
         if not where:
             return self._alive_dev if self._n_dead else None
+        if self.device_filters:
+            words = self._where_bits_device(where)
+            if words is not None:
+                return words
         flags = np.zeros(self._alive_host.size * 32, dtype=bool)
         flags[self._rows_where(where)] = True
         words = torch.from_numpy(np.packbits(flags, bitorder="little").view(np.int32)).to(self.device)
@@ -1058,6 +1068,7 @@ class VectorIndex:
             times = np.full(cap, np.nan, dtype=np.float64)
             times[: self._n] = self._added_at[keep]
             self._added_at = times
+            self._filter_cols.compacted(keep)
             self._map_prior_columns(lambda col: self._compacted(col, cap, keep_dev, 0))
 
     def reset(self):
@@ -1072,6 +1083,7 @@ class VectorIndex:
                 self._lex.reset()
             self._groups = {}
             self._added_at[:] = np.nan
+            self._filter_cols.reset()
             self._priors = {}
             self._spec_cols.clear()
 
@@ -1370,6 +1382,147 @@ class VectorIndex:
         from the rows whose `key` is in scopes[b] only."""
         with self._lock, stage("search"):
             scores, rows = self._launch_scoped(query_embeddings, n_results, scopes, key, where, check_norm)
+            tables = self._tables()
+            emb_src = self._full if "embeddings" in include else None
+        with stage("collect"):
+            return self._collect(scores, rows, include, *tables, emb_src)
+
+    # ------------------------------------------------------------------ per-query metadata filters ----
+    def _compiled(self, where):
+        """(program or None, reason) of one filter (caller holds the lock).  A filter that names "$added_at" exists on
+        the device path only: where that path does not cover it, ValueError."""
+        prog, why = try_compile(where, self._filter_cols)
+        if prog is None and names_added_at(where):
+            raise ValueError(f'a filter on "$added_at" must run on the device, and this one cannot: {why}')
+        return prog, why
+
+    def _eval_programs(self, programs, out: torch.Tensor, alive: Optional[torch.Tensor]):
+        """out[f, :W] = the bitmap of programs[f] over the rows in use (caller holds the lock): one mmrag_filter_eval
+        launch per run of programs that read at most MAX_FILTER_COLUMNS columns between them"""
+        cap = self._matrix.shape[0]
+        lo = 0
+        while lo < len(programs):
+            keys: List[str] = []
+            hi = lo
+            while hi < len(programs):
+                more = [k for k in programs[hi].keys if k not in keys]
+                if hi > lo and len(keys) + len(more) > _native.MAX_FILTER_COLUMNS:
+                    break
+                keys += more
+                hi += 1
+            ops, off, sets, keys = pack_programs(programs[lo:hi])
+            cols = [self._filter_cols.device(k, cap, self.device) for k in keys]
+            _native.filter_eval(ops, off, sets, cols, self._n, alive_bits=alive, device=self.device, out=out[lo:hi])
+            lo = hi
+
+    def _where_bits_device(self, where) -> Optional[torch.Tensor]:
+        """_where_bits on the device (MMRAG_DEVICE_FILTERS): the same words the host builds, or None when the compiler
+        does not cover `where` (an unknown operator included: the host path raises it where match_where does)"""
+        try:
+            prog, _ = self._compiled(where)
+        except ValueError:
+            if names_added_at(where):
+                raise
+            return None
+        if prog is None:
+            return None
+        words = torch.zeros(self._alive_host.size, dtype=torch.int32, device=self.device)
+        if self._n:
+            self._eval_programs([prog], words[: _native.filter_words(self._n)].unsqueeze(0),
+                                self._alive_dev if self._n_dead else None)
+        return words
+
+    def filter_plan(self, where: Optional[Dict[str, Any]]) -> Dict[str, Any]:
+        """How `where` would run: {"device": bool, "reason": why not, "columns": the metadata keys whose columns the
+        program reads}.  Builds those columns if this is their first use.  An unknown operator raises ValueError."""
+        with self._lock:
+            return self._filter_cols.plan(where)
+
+    def _launch_filtered(self, query_embeddings, n_results: int, wheres, check_norm: bool = True):
+        """enqueue the filtered search (caller holds the lock): device (scores, rows) [B, n_results]"""
+        from .config import settings
+
+        self._need_plane("filtered_query")
+        k = int(n_results)
+        if not 1 <= k <= _native.MAX_K_DEEP:
+            raise ValueError(f"n_results must be in 1..{_native.MAX_K_DEEP} for a filtered search")
+        qf = self._to_device_f32(query_embeddings, "query", check_norm)     # converted and norm-checked once
+        B = qf.shape[0]
+        wheres = [wheres] * B if wheres is None or isinstance(wheres, dict) else list(wheres)
+        if len(wheres) != B:
+            raise ValueError(f"wheres holds {len(wheres)} entries for {B} queries")
+        # equal filters are one program and one bitmap; what does not compile is grouped by the filter as written
+        seen: Dict[int, Any] = {}
+        programs: Dict[Any, int] = {}
+        of_query: List[int] = [-1] * B
+        slow: Dict[str, Tuple[Any, List[int]]] = {}
+        for b, w in enumerate(wheres):
+            if id(w) not in seen:
+                seen[id(w)] = self._compiled(w)[0]
+            prog = seen[id(w)]
+            if prog is None:
+                slow.setdefault(repr(w), (w, []))[1].append(b)
+            else:
+                of_query[b] = programs.setdefault(prog, len(programs))
+        scores = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        rows_o = torch.empty((B, k), dtype=torch.int64, device=self.device)
+        if programs:
+            # equal filters next to each other: a query tile's union bitmap then holds few filters
+            order = sorted((b for b in range(B) if of_query[b] >= 0), key=lambda b: of_query[b])
+            rows = self._full
+            q = self._pack_plane_queries(qf) if self._plane is not None else self._pack_queries(qf, check_norm=False)
+            plist = list(programs)
+            W = _native.filter_words(self._n)
+            per_launch = max(1, int(settings.MMRAG_FILTER_BITMAP_BYTES) // max(4 * W, 1))
+            alive = self._alive_dev if self._n_dead else None
+            at = 0
+            for f0 in range(0, len(plist), per_launch):
+                f1 = min(f0 + per_launch, len(plist))
+                mine = []
+                while at < len(order) and of_query[order[at]] < f1:
+                    mine.append(order[at])
+                    at += 1
+                vis = torch.empty((f1 - f0, W), dtype=torch.int32, device=self.device)
+                if self._n:
+                    self._eval_programs(plist[f0:f1], vis, alive)
+                whole = len(mine) == B and mine == list(range(B))
+                pick = None if whole else torch.tensor(mine, device=self.device)
+                need = _native.filtered_topk_workspace_bytes(len(mine), self._n, k)
+                ss, rr = _native.filtered_topk(q if whole else q[pick].contiguous(), rows, self._n, self.dim, k,
+                                               [of_query[b] - f0 for b in mine], vis,
+                                               workspace=self._workspace("_filtered_ws", need))
+                if whole:
+                    return ss, rr
+                scores[pick], rows_o[pick] = ss, rr
+        # not covered by the compiler: the filtered search of today, one per distinct filter, joined in query order
+        for w, mine in slow.values():
+            pick = torch.tensor(mine, device=self.device)
+            scores[pick], rows_o[pick] = self._launch_search(qf[pick].contiguous(), k, w, check_norm=False)
+        return scores, rows_o
+
+    def filtered_search(self, query_embeddings, n_results: int, wheres):
+        """Raw device search with a metadata filter PER QUERY (csrc/filtered.hip, include/mmrag.h mmrag_filter_eval and
+        mmrag_filtered_topk): query b is answered from the live rows whose metadata matches wheres[b] -- match_where's
+        semantics, what search(where=wheres[b]) returns for each query -- in ONE batch: the distinct filters are compiled
+        to small programs (filters.py), one kernel evaluates them over typed metadata columns into row bitmaps, and one
+        masked scan answers every query from its own bitmap, skipping the row tiles no query of a tile can see.
+        `wheres`: one filter per query (None = every live row), or one dict for all.  Returns (scores [B, k] float32
+        desc, rows [B, k] int64, -1 = none), n_results up to MAX_K_DEEP.
+
+        The reserved key "$added_at" filters on the time a row was added (UNIX seconds; see row_times()); it exists on
+        the device path only (ValueError where the filter cannot run there).  A filter the compiler does not cover (see
+        filter_plan) takes search(where=...) inside the same call, one search per distinct filter; the result is in
+        query order either way.  A float8_e4m3fn collection is searched on its re-scoring plane (exact scores; capacity
+        mode raises ValueError).  At most MMRAG_FILTER_BITMAP_BYTES of bitmaps are evaluated per launch."""
+        with self._lock:
+            return self._launch_filtered(query_embeddings, n_results, wheres)
+
+    def filtered_query(self, query_embeddings, n_results: int = 10, wheres=None,
+                       include: Sequence[str] = ("metadatas", "documents", "distances"),
+                       check_norm: bool = True) -> Dict[str, Any]:
+        """query() with a filter per query (see filtered_search): the Chroma-shaped dict of query()"""
+        with self._lock, stage("search"):
+            scores, rows = self._launch_filtered(query_embeddings, n_results, wheres, check_norm)
             tables = self._tables()
             emb_src = self._full if "embeddings" in include else None
         with stage("collect"):

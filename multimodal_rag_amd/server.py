@@ -15,7 +15,7 @@ import time
 import uuid
 from contextlib import asynccontextmanager
 from datetime import datetime
-from typing import Annotated, Any, Dict, List, Literal, Optional, Union
+from typing import Annotated, Any, Dict, List, Literal, Optional, Tuple, Union
 
 from fastapi import FastAPI, HTTPException, Request, status
 from pydantic import BaseModel, Field, StrictBool
@@ -104,6 +104,46 @@ class QueryRequest(BaseModel):  # api.py:161-164
     unlike: Optional[ExampleIds] = None
     not_: Optional[ExampleTexts] = Field(None, alias="not")
     negative_weight: Optional[float] = Field(None, ge=0.0, le=1000.0)
+    # not in the reference: a metadata filter in the `where` grammar of the collection ({"type": "table"},
+    # {"page": {"$gte": 10, "$lte": 40}}, "$and" / "$or" lists; at most 32 leaves, nested at most 8 deep).  A plain or
+    # re-ranked query passes it on as its filter; every other mode gets it AND-ed into its restriction, next to
+    # `doc_ids`.  The reserved key "$added_at" (UNIX seconds a row was added) needs device filters
+    # (MMRAG_DEVICE_FILTERS)
+    filter: Optional[Dict[str, Any]] = None
+
+
+FILTER_MAX_LEAVES, FILTER_MAX_DEPTH = 32, 8
+
+
+def check_filter(where: Any, depth: int = 1) -> Tuple[int, bool]:
+    """(leaves, whether "$added_at" is named) of a request's filter; ValueError for one that is not a dict, an operator
+    match_where does not know (its message), more than FILTER_MAX_LEAVES leaves or nesting beyond FILTER_MAX_DEPTH"""
+    from .index import _CMP
+
+    if not isinstance(where, dict):
+        raise ValueError("a filter must be an object")
+    if depth > FILTER_MAX_DEPTH:
+        raise ValueError(f"a filter nests at most {FILTER_MAX_DEPTH} deep")
+    leaves, timed = 0, False
+    for key, cond in where.items():
+        if key in ("$and", "$or"):
+            if not isinstance(cond, list):
+                raise ValueError(f"{key} takes a list of filters")
+            for sub in cond:
+                n, t = check_filter(sub, depth + 1)
+                leaves, timed = leaves + n, timed or t
+            continue
+        timed = timed or key == "$added_at"
+        if isinstance(cond, dict):
+            for op in cond:
+                if op not in _CMP:
+                    raise ValueError(f"unsupported where operator {op!r}")
+            leaves += len(cond)
+        else:
+            leaves += 1
+    if depth == 1 and leaves > FILTER_MAX_LEAVES:
+        raise ValueError(f"a filter holds at most {FILTER_MAX_LEAVES} leaves (this one: {leaves})")
+    return leaves, timed
 
 
 class RecommendRequest(BaseModel):
@@ -348,7 +388,8 @@ class Pipeline:
                      variants: Optional[List[str]] = None, variant_weight: Optional[float] = None,
                      fusion: Optional[str] = None, doc_ids: Optional[List[str]] = None,
                      rerank_method: Optional[str] = None, explain: bool = False, boost: Any = None,
-                     recommend: Optional[Dict[str, Any]] = None) -> Optional[dict]:
+                     recommend: Optional[Dict[str, Any]] = None,
+                     filter_dict: Optional[Dict[str, Any]] = None) -> Optional[dict]:
         """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
         max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the re-ranker's best top_k (`rerank_method` "cross" or "late",
         default MMRAG_RERANK_METHOD; `explain`: late interaction's per-token matches on every source).  `hybrid`: from
@@ -361,10 +402,14 @@ class Pipeline:
         only -- a plain (or re-ranked) query through EmbeddingManager.scoped_query, every other mode through its
         filter.  `boost` (a BoostSpec; alone or with `rerank`): the hits are ranked by cosine + the spec's score prior
         (EmbeddingManager.boosted_query).  `recommend` ({"like", "unlike", "unlike_texts", "negative_weight"}; alone or
-        with `rerank`): the question is one positive example next to these (EmbeddingManager.recommend)"""
+        with `rerank`): the question is one positive example next to these (EmbeddingManager.recommend).
+        `filter_dict`: a metadata filter every mode gets as (part of) its filter; a plain or re-ranked query with one
+        goes through EmbeddingManager.query, `doc_ids` AND-ed into it"""
         multi = variants is not None
         # the restriction as the filter the embedder's methods take (nothing is passed when there is none)
-        only = {} if doc_ids is None else {"filter_dict": {"doc_id": {"$in": list(doc_ids)}}}
+        docs_only = None if doc_ids is None else {"doc_id": {"$in": list(doc_ids)}}
+        both = {"$and": [filter_dict, docs_only]} if filter_dict and docs_only else (filter_dict or docs_only)
+        only = {} if both is None else {"filter_dict": both}
         if multi:
             weights = None if variant_weight is None else [1.0] + [float(variant_weight)] * len(variants)
 
@@ -372,14 +417,14 @@ class Pipeline:
                 return self.embedder.multi_query([text] + list(variants), n_results=n_results, weights=weights,
                                                  method=fusion, **only)
         elif boost is not None:
-            search = functools.partial(self.embedder.boosted_query, boost=boost)
+            search = functools.partial(self.embedder.boosted_query, boost=boost, **only)
         elif recommend is not None:
-            search = functools.partial(self.embedder.recommend, **recommend)
+            search = functools.partial(self.embedder.recommend, **recommend, **only)
         elif mmr:
             search = functools.partial(self.embedder.mmr_query, lambda_mult=mmr_lambda, **only)
         elif hybrid:
             search = functools.partial(self.embedder.hybrid_query, **only)
-        elif doc_ids is not None and hasattr(self.embedder, "scoped_query"):
+        elif doc_ids is not None and not filter_dict and hasattr(self.embedder, "scoped_query"):
             search = functools.partial(self.embedder.scoped_query, doc_ids=list(doc_ids))
         else:
             search = functools.partial(self.embedder.query, **only)
@@ -563,6 +608,16 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
         elif request.rerank and not (hasattr(pipe.embedder, "has_reranker") and pipe.embedder.has_reranker()):
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="Re-ranking is not configured: set MMRAG_RERANKER_DIR to a local cross-encoder")
+        if request.filter is not None:
+            try:
+                _, timed = check_filter(request.filter)
+            except ValueError as e:
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
+            if timed and not (settings.MMRAG_DEVICE_FILTERS
+                              and getattr(pipe.embedder, "supports_device_filters", lambda: False)()):
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                    detail='A filter on "$added_at" needs device filters: set MMRAG_DEVICE_FILTERS=1 '
+                                           "with a single-GPU collection (EmbeddingManager.supports_device_filters)")
         spec = None
         if request.boost is not None and request.boost is not False:
             if multi or request.mmr or request.hybrid or request.group_by_document or request.doc_ids is not None:
@@ -628,7 +683,8 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
                                     doc_ids=request.doc_ids,
                                     rerank_method="late" if late else request.rerank_method, explain=request.explain,
                                     **({} if spec is None else {"boost": spec}),
-                                    **({} if recommend is None else {"recommend": recommend}))
+                                    **({} if recommend is None else {"recommend": recommend}),
+                                    **({} if not request.filter else {"filter_dict": request.filter}))
         except ValueError as e:
             if recommend is None:
                 raise
