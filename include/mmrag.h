@@ -846,6 +846,61 @@ int mmrag_maxsim_scores(const void *q_tok, int64_t q_rows, int64_t q_ld, const v
                         const int32_t *pair_d, int P, float *out_sum, float *out_best_sim, int32_t *out_best_idx,
                         void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Token store: exact MaxSim retrieval over stored token rows (csrc/maxsim_scan.hip).  The token rows of stored items
+ * stay on the device in one plane, item i owning rows item_off[i] .. item_off[i + 1]; a batch of questions is answered
+ * with each question's exact MaxSim top-k over ALL items in one scan of the plane, no pooled-vector search before it.
+ * multimodal_rag_amd/late_store.py, VectorIndex.late_search.
+ *
+ * mmrag_maxsim_topk
+ * Contract
+ *   Sequences
+ *   - Question q is rows q_start[q] .. q_start[q] + q_len[q] of q_tok, as in mmrag_maxsim_scores.
+ *   - Item i is rows item_off[i] .. item_off[i + 1] of tok (item_off ascending).  An item is a CANDIDATE iff its length
+ *     is in 1..MMRAG_MAX_LATE_DOC_TOKENS and, when alive_bits is given, bit i & 31 of word i >> 5 is set.  Length 0
+ *     marks "no tokens stored"; such an item never appears in an output.
+ *   Per question q and candidate item, i over the question's tokens, j over the item's rows
+ *   - best[q][i][item] = max over j of <q_i, d_j>: float32 accumulation of the fp16 rows in the tile body's fixed K
+ *     order.  Rows outside the item never take part: a zero row is not a token and a neighbour's token is not this
+ *     item's;
+ *   - score[q][item] = the float32 sum of best[q][0 .. q_len) in ascending i starting from 0.0f: for every
+ *     (question, item) the bits equal mmrag_maxsim_scores' out_sum of the same pair;
+ *   - out_scores / out_items [Q, k]: the k candidates of highest score, descending, ties to the LOWER item,
+ *     (-inf, -1) padded.
+ *   Guarantees
+ *   - every output is a pure function of the inputs: not of the grid, the batch, how the plane is cut into chunks or
+ *     whether a bound pass ran;
+ *   - the per-item maxima are reduced inside one workgroup (registers, lane shuffles, LDS): no atomics, no
+ *     [Q, n_items] score matrix in memory;
+ *   - exact for any n_items: when n_items exceeds a question's candidate slots (32 k, at least 16384) a lower bound on
+ *     its k-th score is staged first from a strided sample of whole chunks (the k-th best of any subset is at most the
+ *     true k-th) and only scores at or above it are kept; a question whose survivors still overflow is produced again
+ *     alone into n_items slots;
+ *   - at most one stream synchronisation per call, and only when n_items exceeds the candidate slots.
+ *
+ *   q_tok            dev [q_rows, q_ld] fp16, pad columns zero, 16-byte aligned
+ *   q_start, q_len   dev [Q] int32, lengths 1..MMRAG_MAX_LATE_QUERY_TOKENS; Q in 1..MMRAG_MAX_LATE_QUESTIONS
+ *   tok              dev [T, ld] fp16, 16-byte aligned, T < 2^31
+ *   q_ld, ld         mmrag_padded_dim(dim, MMRAG_F16) or a larger width of whole 128-byte slabs
+ *   item_off         dev [n_items + 1] int32, ascending, inside 0..T
+ *   alive_bits       dev, optional, at least ceil(n_items / 32) words (the index's alive bitmap or any `where` bitmap)
+ *   dim              a multiple of 64, at most 1024
+ *   k                1..MMRAG_MAX_K_DEEP
+ *   out_scores       dev [Q, k] float32        out_items  dev [Q, k] int64
+ *   workspace        dev, >= mmrag_maxsim_topk_workspace_bytes(Q, n_items, k) bytes (0 for arguments out of range),
+ *                    16-byte aligned; short or misaligned: MMRAG_EWORKSPACE
+ * MMRAG_EINVAL before anything is launched: a null pointer (alive_bits aside), Q out of range, n_items < 0 or >= 2^31,
+ * T < 0 or >= 2^31, q_rows < 1, k out of range, dim out of range, ld < dim or not whole slabs.  n_items == 0 or T == 0
+ * gives padding only.  The tables live on the device and are not read by the host: a question whose length is out of
+ * range or whose rows do not lie inside q_rows gets padding only; an item whose rows do not lie inside the plane is no
+ * candidate. */
+#define MMRAG_MAX_LATE_QUESTIONS 4096
+size_t mmrag_maxsim_topk_workspace_bytes(int Q, int64_t n_items, int k);
+int mmrag_maxsim_topk(const void *q_tok, int64_t q_rows, int64_t q_ld, const int32_t *q_start, const int32_t *q_len,
+                      int Q, const void *tok, int64_t T, int64_t ld, const int32_t *item_off, int64_t n_items,
+                      const uint32_t *alive_bits, int dim, int k, float *out_scores, int64_t *out_items,
+                      void *workspace, size_t workspace_bytes, void *stream);
+
 /* CLIP byte-level BPE (the text tower's tokenizer, BASELINE config 4; the reference only names CLIP in config.py:106).
  * Host code, multi-threaded; equals multimodal_rag_amd/tokenizer.py:ClipBpeTokenizer, which tests pin to
  * transformers.CLIPTokenizer.  The caller passes text already NFC-normalised, whitespace-collapsed and lower-cased.

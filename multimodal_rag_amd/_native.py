@@ -38,6 +38,7 @@ MAX_RECOMMEND_EXAMPLES = 16  # mmrag_recommend_topk (MMRAG_MAX_RECOMMEND_EXAMPLE
 # mmrag_maxsim_scores (MMRAG_MAX_LATE_QUERY_TOKENS, MMRAG_MAX_LATE_DOC_TOKENS)
 MAX_LATE_QUERY_TOKENS, MAX_LATE_DOC_TOKENS = 128, 512
 MAX_LATE_PAIRS = 65535
+MAX_LATE_QUESTIONS = 4096   # mmrag_maxsim_topk (MMRAG_MAX_LATE_QUESTIONS)
 _DT2TORCH = {F32: torch.float32, F16: torch.float16, BF16: torch.bfloat16, F8E4M3: torch.float8_e4m3fn}
 _TORCH2DT = {v: k for k, v in _DT2TORCH.items()}
 
@@ -287,6 +288,17 @@ def _declare(lib):
     lib.mmrag_maxsim_scores.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
                                         c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                         c_void_p, c_void_p]
+    # token store (csrc/maxsim_scan.hip)
+    lib.mmrag_maxsim_topk_workspace_bytes.restype = c_size_t
+    lib.mmrag_maxsim_topk_workspace_bytes.argtypes = [c_int, c_int64, c_int]
+    lib.mmrag_maxsim_topk.restype = c_int
+    lib.mmrag_maxsim_topk.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64,
+                                      c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]
+    lib.mmrag_internal_maxsim_topk_ex.restype = c_int
+    lib.mmrag_internal_maxsim_topk_ex.argtypes = lib.mmrag_maxsim_topk.argtypes + [c_int, c_int64, ctypes.c_uint, c_int]
+    lib.mmrag_internal_maxsim_topk_workspace_bytes_ex.restype = c_size_t
+    lib.mmrag_internal_maxsim_topk_workspace_bytes_ex.argtypes = [c_int, c_int64, c_int, c_int, c_int]
     from .lexical import declare as declare_lexical   # BM25 analyzer, device index and search (csrc/lexical.hip)
 
     declare_lexical(lib)
@@ -1279,6 +1291,89 @@ def maxsim_scores(q_tok: torch.Tensor, d_tok: torch.Tensor, dim: int, q_start, q
                                        sums.data_ptr(), _ptr(best_sim), _ptr(best_idx), _stream_ptr(dev))
     _check(st, "mmrag_maxsim_scores")
     return sums, best_sim, best_idx
+
+
+def maxsim_topk_workspace_bytes(Q: int, n_items: int, k: int, dim: int = 0, max_tiles: int = 0) -> int:
+    """the public bound (any dim, a tile per question), or with `dim` what a call at that dim with at most `max_tiles`
+    question tiles (0: Q) needs"""
+    if not dim:
+        return int(lib().mmrag_maxsim_topk_workspace_bytes(int(Q), int(n_items), int(k)))
+    return int(lib().mmrag_internal_maxsim_topk_workspace_bytes_ex(int(Q), int(n_items), int(k), int(dim), int(max_tiles)))
+
+
+def late_question_tiles(q_start, q_len, q_rows: int) -> int:
+    """the 128-row tiles the scan packs these questions into (whole questions, greedily, in order; a question the
+    device would refuse is in none): the kernel's own rule on the host copies, at least 1"""
+    tiles, used = 0, MAX_LATE_QUERY_TOKENS + 1
+    for a, n in zip(q_start, q_len):
+        if not 1 <= n <= MAX_LATE_QUERY_TOKENS or a < 0 or a + n > q_rows:
+            continue
+        if used + n > MAX_LATE_QUERY_TOKENS:
+            tiles, used = tiles + 1, 0
+        used += n
+    return max(tiles, 1)
+
+
+def maxsim_topk(q_tok: torch.Tensor, q_start, q_len, tok: torch.Tensor, n_rows: int, item_off: torch.Tensor,
+                n_items: int, dim: int, k: int, alive_bits: Optional[torch.Tensor] = None,
+                workspace: Optional[torch.Tensor] = None, chunk_rows: int = 0, cap: int = 0, dbg: int = 0,
+                check_tables: bool = True):
+    """Each question's exact MaxSim top-k over the items of a token plane (include/mmrag.h mmrag_maxsim_topk).
+    `q_tok` [q_rows, ld] and `tok` [>= n_rows, ld] are contiguous device float16 tensors; question s is rows
+    q_start[s] .. q_start[s] + q_len[s] (HOST integer sequences, checked here unless `check_tables` is false -- then a
+    bad question only gets padding -- and uploaded in one transfer).  `item_off`: a device int32 tensor of at least
+    n_items + 1 ascending offsets into the first n_rows rows of `tok`; `alive_bits`: an optional device int32 bitmap
+    over items.  Returns (scores [Q, k] float32 descending, items [Q, k] int64), (-inf, -1) padded.  No host
+    synchronisation unless n_items exceeds the candidate slots of a question.  `chunk_rows`, `cap`, `dbg` (tests and
+    tools): the plane rows per chunk, fewer candidate slots, dbg & 1 = no bound passes."""
+    _dev_check(q_tok, tok, item_off)
+    for name, t in (("q_tok", q_tok), ("tok", tok)):
+        if t.dim() != 2 or not t.is_contiguous() or t.dtype != torch.float16:
+            raise MMRagNativeError(f"maxsim_topk: {name} must be a contiguous 2-D float16 tensor")
+    dev = q_tok.device
+    n_rows, n_items, k = int(n_rows), int(n_items), int(k)
+    if not 1 <= k <= MAX_K_DEEP:
+        raise ValueError(f"maxsim_topk: k={k} outside 1..{MAX_K_DEEP}")
+    if tok.device != dev or item_off.device != dev or (alive_bits is not None and alive_bits.device != dev):
+        raise MMRagNativeError("maxsim_topk: q_tok, tok, item_off and alive_bits must be on one device")
+    if not 0 <= n_rows <= tok.shape[0]:
+        raise MMRagNativeError(f"maxsim_topk: n_rows={n_rows} outside the {tok.shape[0]} rows of tok")
+    if (item_off.dim() != 1 or item_off.dtype != torch.int32 or not item_off.is_contiguous() or n_items < 0
+            or item_off.numel() < n_items + 1):
+        raise MMRagNativeError(f"maxsim_topk: item_off must be a contiguous int32 tensor of at least n_items + 1 = "
+                               f"{n_items + 1} offsets")
+    if alive_bits is not None and (alive_bits.dtype != torch.int32 or not alive_bits.is_contiguous()
+                                   or alive_bits.numel() * 32 < n_items):
+        raise MMRagNativeError(f"maxsim_topk: alive_bits must be a contiguous int32 bitmap over {n_items} items")
+    tables = [torch.as_tensor(t, dtype=torch.int32).reshape(-1).cpu() for t in (q_start, q_len)]
+    Q = tables[0].numel()
+    if tables[1].numel() != Q or not 1 <= Q <= MAX_LATE_QUESTIONS:
+        raise MMRagNativeError(f"maxsim_topk: q_start and q_len must hold the same 1..{MAX_LATE_QUESTIONS} questions "
+                               f"(got {Q} and {tables[1].numel()})")
+    if check_tables:
+        for s, (a, n) in enumerate(zip(tables[0].tolist(), tables[1].tolist())):
+            if not 1 <= n <= MAX_LATE_QUERY_TOKENS:
+                raise MMRagNativeError(f"maxsim_topk: question {s} has {n} tokens, outside 1..{MAX_LATE_QUERY_TOKENS}")
+            if a < 0 or a + n > q_tok.shape[0]:
+                raise MMRagNativeError(f"maxsim_topk: question {s} (rows {a}..{a + n}) is outside the "
+                                       f"{q_tok.shape[0]} rows given")
+    packed = _pinned_to_device(torch.cat(tables), dev)
+    # the host tables say how many question tiles there are: the grid and the packed tiles are sized by that, not by Q
+    tiles = late_question_tiles(tables[0].tolist(), tables[1].tolist(), q_tok.shape[0])
+    need = maxsim_topk_workspace_bytes(Q, n_items, k, int(dim), tiles)
+    if need == 0:
+        raise MMRagNativeError(f"maxsim_topk: dim must be a multiple of 64, at most 1024 (dim={dim})")
+    if workspace is None or _nbytes(workspace) < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    out_s, out_r = _topk_out(Q, k, dev)
+    with torch.cuda.device(dev):
+        st = lib().mmrag_internal_maxsim_topk_ex(
+            q_tok.data_ptr(), q_tok.shape[0], q_tok.shape[1], packed.data_ptr(), packed[Q:].data_ptr(), Q,
+            tok.data_ptr(), n_rows, tok.shape[1], item_off.data_ptr(), n_items, _ptr(alive_bits), int(dim), k,
+            out_s.data_ptr(), out_r.data_ptr(), workspace.data_ptr(), _nbytes(workspace), _stream_ptr(dev),
+            int(chunk_rows), int(cap), int(dbg), tiles)
+    _check(st, "mmrag_maxsim_topk")
+    return out_s, out_r
 
 
 def join_tile(T: int, at: int, slot_order: bool = False) -> Tuple[int, int]:

@@ -78,6 +78,13 @@ class Settings:
     # second model).  MMRAG_LATE_MAX_DOC_TOKENS: passage tokens "late" scores (0 = the encoder's length; at most 512)
     MMRAG_RERANK_METHOD: str = field(default_factory=lambda: os.getenv("MMRAG_RERANK_METHOD", "cross"))
     MMRAG_LATE_MAX_DOC_TOKENS: int = field(default_factory=lambda: int(os.getenv("MMRAG_LATE_MAX_DOC_TOKENS", "0")))
+    # token store (late_store.py, csrc/maxsim_scan.hip): with MMRAG_LATE_STORE=1 an upload also keeps the token rows
+    # of the stored texts on the device (768 bytes per MiniLM token), so a late re-rank encodes only the question and
+    # late_query / POST /query {"late": true} retrieve by exact MaxSim over all of them.  MMRAG_LATE_STORE_MAX_BYTES
+    # caps the plane (0 = no cap): past it new rows keep no tokens and are re-encoded by a re-rank
+    MMRAG_LATE_STORE: bool = field(default_factory=lambda: os.getenv("MMRAG_LATE_STORE", "0") == "1")
+    MMRAG_LATE_STORE_MAX_BYTES: int = field(
+        default_factory=lambda: int(os.getenv("MMRAG_LATE_STORE_MAX_BYTES", "0")))
     # BM25 lexical leg (VectorIndex.lexical_query / hybrid_query, csrc/lexical.hip): term-frequency saturation k1 and
     # length normalisation b of the score, the same for every query
     MMRAG_BM25_K1: float = field(default_factory=lambda: float(os.getenv("MMRAG_BM25_K1", "1.2")))

@@ -42,6 +42,7 @@ ITEM_KINDS = ("text", "table", "image")           # the kinds embed_and_store co
 RESULT_KEYS = ("ids", "distances", "metadatas", "documents")
 HYBRID_KEYS = RESULT_KEYS + ("hybrid_scores", "lexical_scores")
 MMR_KEYS = RESULT_KEYS + ("mmr_scores",)
+LATE_KEYS = RESULT_KEYS + ("late_scores",)
 FUSED_KEYS = RESULT_KEYS + ("fused_scores", "matched_queries", "best_query")
 BOOST_KEYS = RESULT_KEYS + ("scores", "boosts")
 RECOMMEND_KEYS = RESULT_KEYS + ("scores", "penalties", "matched", "repelled_by")
@@ -61,11 +62,14 @@ _NEEDS_RECOMMEND = ("recommend_query", "recommend retrieval needs a single-GPU c
                                         "full-precision rows")
 _NEEDS_RELATED = ("related_query", "related-document retrieval needs a single-GPU collection (VectorIndex) with "
                                    "full-precision rows")
+_NEEDS_LATE = ("late_query", "late retrieval needs a single-GPU collection (VectorIndex) with a token store")
+_late_store_warned = False   # "MMRAG_LATE_STORE is set but this embedder cannot keep token rows": once per process
 _boost_warned = False   # "this collection cannot boost": once per process
 _dedup_warned = False    # "MMRAG_DEDUP_THRESHOLD is set but this collection cannot de-duplicate": once per process
 # the answer of a batch's query that could not be answered, before its 'error' (copied for every such query)
 _EMPTY = {key: [] for key in RESULT_KEYS}
 _EMPTY_MMR = {key: [] for key in MMR_KEYS}
+_EMPTY_LATE = {key: [] for key in LATE_KEYS}
 _EMPTY_FUSED = {key: [] for key in FUSED_KEYS}
 _EMPTY_BOOST = {key: [] for key in BOOST_KEYS}
 _EMPTY_RECOMMEND = {key: [] for key in RECOMMEND_KEYS}
@@ -296,6 +300,15 @@ class EmbeddingManager:
                 counts["duplicates_skipped"] = skipped     # the per-kind counts keep counting items processed
             else:
                 await self._store_with_retry(embeddings=matrix, documents=texts, metadatas=metas, ids=ids, **extra)
+        if settings.MMRAG_LATE_STORE:
+            if self.supports_late_store():
+                await asyncio.to_thread(self._store_tokens, ids, texts)
+            else:
+                global _late_store_warned
+                if not _late_store_warned:
+                    _late_store_warned = True
+                    logger.warning("MMRAG_LATE_STORE=1 is ignored: the token store needs a single BERT-family fp16 HIP "
+                                   "engine with a tokenizer and a single-GPU collection")
         if skipped:
             logger.info("Skipped %d near-duplicate items of doc %s (cosine >= %s)", skipped, doc_id, dedup)
         self.stats["total_items_stored"] += len(summaries)
@@ -1081,6 +1094,128 @@ class EmbeddingManager:
                 self._late = LateInteractionScorer(self._engine.encoder, self._engine.tokenizer)
             return self._late
 
+    # ---- the token store (late_store.py, csrc/maxsim_scan.hip): stored token rows, late retrieval ----
+    def supports_late_store(self) -> bool:
+        """True when the collection can keep token rows: has_late_reranker's rules (not the CLIP engine, not the fp32
+        encoder mode) and a single-GPU VectorIndex (not a sharded collection)"""
+        return self.has_late_reranker() and (self.collection is None or hasattr(self.collection, "enable_token_store"))
+
+    def late_store_enabled(self) -> bool:
+        return getattr(self.collection, "token_store", None) is not None
+
+    def supports_late_query(self) -> bool:
+        """True when late_query can run: a token store is attached (MMRAG_LATE_STORE=1 or enable_late_store())"""
+        return self.supports_late_store() and self.late_store_enabled()
+
+    def _token_store(self):
+        """the collection's token store, attached on first use with the scorer's dim and passage length"""
+        scorer = self._get_late()
+        dim = int(scorer.projection.shape[0]) if scorer.projection is not None else int(scorer.encoder.cfg.hidden)
+        return self.collection.enable_token_store(dim, scorer.max_doc_tokens)
+
+    def _store_tokens(self, ids: Sequence[str], texts: Sequence[Optional[str]], batch: int = 64):
+        """blocking: encode_tokens over `texts` in batches and keep the trimmed rows under the rows of `ids`.  Only ids
+        whose live row keeps no tokens yet are encoded (an id add() ignored because it exists keeps the tokens of the
+        document stored under it; a skipped duplicate has no row), and each batch is written by id under the index's
+        lock (VectorIndex.set_tokens_for_ids): a delete, compaction or reset while the forward ran cannot misplace it."""
+        self._token_store()
+        scorer = self._get_late()
+        text_of = dict(zip(ids, texts))
+        todo = self.collection.ids_without_tokens(list(ids))
+        for lo in range(0, len(todo), batch):
+            part = todo[lo: lo + batch]
+            tok, lens, tok_ids = scorer.encode_documents([text_of[i] for i in part], batch)
+            self.collection.set_tokens_for_ids(part, tok, lens, tok_ids)
+
+    def _enable_late_store_sync(self) -> Dict[str, Any]:
+        if not self.supports_late_store():
+            raise ValueError("the token store needs a single BERT-family fp16 HIP engine with a tokenizer and a "
+                             "single-GPU collection (VectorIndex)")
+        store = self._token_store()
+        got = self.collection.get(include=("documents",))
+        todo = set(self.collection.ids_without_tokens(got["ids"]))      # get() lists the live rows in row order
+        ids = [i for i in got["ids"] if i in todo]
+        text_of = dict(zip(got["ids"], got["documents"]))
+        # Rows behind the last one that keeps tokens are appended batch by batch.  Rows before it are holes (the cap, or
+        # uploads while the store was off): a fill rebuilds the plane, so all of them are encoded first and written in
+        # ONE rebuild.  What that holds at once is the holes' token rows, not the plane's.
+        rows = self.collection.rows_of_ids(ids)
+        frontier = store.frontier()
+        holes = [i for i, r in zip(ids, rows) if 0 <= r < frontier]
+        self._store_tokens([i for i, r in zip(ids, rows) if r >= frontier], [text_of[i] for i, r in zip(ids, rows)
+                                                                              if r >= frontier])
+        if holes:
+            import torch
+
+            scorer, parts, lens, tok_ids = self._get_late(), [], [], []
+            for lo in range(0, len(holes), 64):
+                tok, n, t_ids = scorer.encode_documents([text_of[i] for i in holes[lo: lo + 64]], 64)
+                parts.append(tok)
+                lens.extend(int(x) for x in n)
+                tok_ids.extend(t_ids)
+            self.collection.set_tokens_for_ids(holes, torch.cat(parts), lens, tok_ids)
+        return self.collection.token_stats()
+
+    async def enable_late_store(self) -> Dict[str, Any]:
+        """Attach the token store and fill it from the stored documents, in batches (the pattern of enable_lexical);
+        rows that already keep tokens are left alone.  From then on late_rerank scores stored passages from the plane
+        and late_query is available; uploads keep filling it only with MMRAG_LATE_STORE=1.  The plane is not persisted:
+        after a restore, call this again.  Returns the store's statistics."""
+        await self._ready()
+        return await asyncio.to_thread(self._enable_late_store_sync)
+
+    def _stored_spans(self, scorer, results_list: List[Dict[str, Any]], with_ids: bool):
+        """(spans, plane) for _late_rerank_sync: per hit, in order, (first plane row, length, token ids) of the rows the
+        token store keeps under the hit's id, or None -- no store, a store built for another passage length, an id the
+        collection does not have, or a row that keeps no tokens.  One snapshot under the index's lock
+        (VectorIndex.token_spans).  The token ids are read only `with_ids` (explain)"""
+        if not hasattr(self.collection, "token_spans"):
+            return None, None
+        spans, plane, max_doc = self.collection.token_spans([r["ids"] for r in results_list], with_ids)
+        if spans is None or max_doc != scorer.max_doc_tokens:
+            return None, None
+        return spans, plane
+
+    def _answer_late(self, texts: Sequence[str], n_results: int, filter_dict: Optional[Dict]) -> List[Dict[str, Any]]:
+        """blocking, one worker thread: ONE forward over the questions (token rows, not pooled), ONE scan of the token
+        plane for all of them"""
+        scorer = self._get_late()
+        tokens, q_start, q_len, _ = scorer.encode_questions(list(texts))
+        res = self.collection.late_query(tokens, q_start, q_len, n_results=n_results, where=filter_dict,
+                                         include=self._INCLUDE)
+        return [{key: res[key][at] for key in LATE_KEYS} for at in range(len(texts))]
+
+    def _late_query_problem(self) -> Optional[str]:
+        """why late_query cannot run on a collection that has the method, or None (checked before the engine call: a
+        missing store is the caller's to fix, not a failure to retry)"""
+        if hasattr(self.collection, "late_query") and not self.supports_late_query():
+            return ("Late retrieval needs the token store: set MMRAG_LATE_STORE=1 before uploading, or call "
+                    "EmbeddingManager.enable_late_store()")
+        return None
+
+    async def late_query(self, query_text: str, n_results: int = 5, filter_dict: Optional[Dict] = None) -> Dict[str, Any]:
+        """First-stage late-interaction retrieval (VectorIndex.late_query, csrc/maxsim_scan.hip): the n_results stored
+        items of highest MaxSim against the question's tokens, over ALL stored items that keep token rows -- a passage
+        whose pooled cosine is middling but three of whose tokens answer the question is found.  One result dict with
+        the keys of query() plus `late_scores` (the mean over the question's tokens of each token's best cosine;
+        `distances` is 1 - that).  Needs the token store."""
+        await self._ready()
+        problem = self._late_query_problem()
+        if problem:
+            raise ValueError(problem)
+        return await self._single("Late query", _NEEDS_LATE, self._answer_late, query_text, n_results, filter_dict)
+
+    async def batch_late_query(self, queries: List[str], n_results: int = 5,
+                               filter_dict: Optional[Dict] = None) -> List[Dict[str, Any]]:
+        """batch_query's twin for late_query: one question forward and one scan for all the queries; a query that cannot
+        be answered gets a dict with empty lists and an 'error' message."""
+        await self._ready()
+        problem = self._late_query_problem()
+        if problem:
+            return [{**copy.deepcopy(_EMPTY_LATE), "error": problem} for _ in queries]
+        return await self._batch("Batch late query", _NEEDS_LATE, _EMPTY_LATE, self._answer_late, queries, n_results,
+                                 filter_dict)
+
     def _late_rerank_sync(self, queries: List[str], results_list: List[Dict[str, Any]], top_k: Optional[int],
                           explain: bool) -> List[Dict[str, Any]]:
         scorer = self._get_late()
@@ -1093,10 +1228,14 @@ class EmbeddingManager:
         scores: Any = []
         records: List[Any] = []
         if pairs:
+            # hits whose token rows the store keeps are scored from the plane; the rest are encoded as before
+            # (without a store, or when it keeps none of them, the scorer is called exactly as before)
+            spans, plane = self._stored_spans(scorer, results_list, explain)
+            stored = {"spans": spans, "plane": plane} if spans and any(s is not None for s in spans) else {}
             if explain:
-                scores, records = scorer.explain_pairs(list(queries), docs, pairs)
+                scores, records = scorer.explain_pairs(list(queries), docs, pairs, **stored)
             else:
-                scores = scorer.score_pairs(list(queries), docs, pairs)
+                scores = scorer.score_pairs(list(queries), docs, pairs, **stored)
         out, lo = [], 0
         for results in results_list:
             n = len(results["documents"])
@@ -1202,6 +1341,8 @@ class EmbeddingManager:
         if hasattr(self.collection, "bytes_per_row"):   # a VectorIndex: how its rows are stored
             report["index_dtype"] = str(self.collection.dtype).split(".")[-1]
             report["bytes_per_row"] = self.collection.bytes_per_row()
+        if getattr(self.collection, "token_store", None) is not None:     # tokens and bytes of the late store
+            report["late_store"] = self.collection.token_stats()
         if self.cache:
             report["cache"] = self.cache.get_stats()
         return report

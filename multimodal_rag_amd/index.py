@@ -242,6 +242,8 @@ class VectorIndex:
         self._filter_cols = ColumnRegistry(lambda: (self._metadatas, self._n, self._added_at))
         self._filtered_ws: Optional[torch.Tensor] = None   # workspace of the filtered search, reused
         self.device_filters = bool(settings.MMRAG_DEVICE_FILTERS)   # _where_bits builds its bitmap on the device
+        self._tokens = None    # late_store.TokenStore once enable_token_store() ran: token rows of the items, item = row
+        self._late_ws: Optional[torch.Tensor] = None      # workspace of the late search, reused
 
     def _new_rows(self, rows: int, zero: bool) -> torch.Tensor:
         """[rows, ld] in the storage dtype; FP8 codes are allocated as bytes and viewed as float8_e4m3fn"""
@@ -1070,6 +1072,8 @@ class VectorIndex:
             self._added_at = times
             self._filter_cols.compacted(keep)
             self._map_prior_columns(lambda col: self._compacted(col, cap, keep_dev, 0))
+            if self._tokens is not None:
+                self._tokens.compact(keep)     # the same kept rows, in order: item stays row
 
     def reset(self):
         with self._lock:
@@ -1086,6 +1090,8 @@ class VectorIndex:
             self._filter_cols.reset()
             self._priors = {}
             self._spec_cols.clear()
+            if self._tokens is not None:
+                self._tokens.reset()
 
     # ------------------------------------------------------------------ diversified (MMR) ----
     def _launch_mmr(self, query_embeddings, n_results: int, fetch_k, lambda_mult, where, check_norm: bool = True):
@@ -1965,6 +1971,153 @@ class VectorIndex:
             out = self._collect(best, rows, include, *tables, emb_src)
             for key, t in (("fused_scores", fused), ("matched_queries", count), ("best_query", best_list)):
                 out[key] = [vals[: len(ids)] for vals, ids in zip(t.cpu().tolist(), out["ids"])]
+            return out
+
+    # ------------------------------------------------------------------ token store / late retrieval ----
+    def enable_token_store(self, dim: int, max_doc_tokens: int, max_bytes: Optional[int] = None):
+        """Attach the token store (late_store.TokenStore): a device fp16 plane [tokens, dim] of the stored chunks' token
+        rows, item i being row i, with the `max_doc_tokens` its rows were trimmed to.  Rows keep no tokens until
+        set_tokens names them.  delete needs nothing (the alive bitmap is over rows, i.e. items); compact and reset keep
+        the store in step.  `max_bytes` (default MMRAG_LATE_STORE_MAX_BYTES; 0 = no cap): past it new rows keep no
+        tokens.  Idempotent for the same (dim, max_doc_tokens)."""
+        from .config import settings
+        from .late_store import TokenStore
+
+        with self._lock:
+            if self._tokens is not None:
+                if (self._tokens.dim, self._tokens.max_doc_tokens) != (int(dim), int(max_doc_tokens)):
+                    raise ValueError(f"this collection's token store holds dim {self._tokens.dim}, max_doc_tokens "
+                                     f"{self._tokens.max_doc_tokens}; reset it before changing them")
+                return self._tokens
+            cap = settings.MMRAG_LATE_STORE_MAX_BYTES if max_bytes is None else int(max_bytes)
+            self._tokens = TokenStore(dim, max_doc_tokens, device=self.device, max_bytes=cap)
+            return self._tokens
+
+    @property
+    def token_store(self):
+        """the late_store.TokenStore, or None before enable_token_store()"""
+        return self._tokens
+
+    def _need_tokens(self, what: str):
+        if self._tokens is None:
+            raise ValueError(f"{what} needs the token store: call enable_token_store() (EmbeddingManager: "
+                             f"MMRAG_LATE_STORE=1 or enable_late_store())")
+        return self._tokens
+
+    def rows_of_ids(self, ids: Sequence[str]) -> List[int]:
+        """the live row of each id, -1 for an id no live row has"""
+        with self._lock:
+            return [self._row_of.get(i, -1) for i in ids]
+
+    def set_tokens(self, rows: Sequence[int], token_rows, lens: Sequence[int], token_ids=None):
+        """Store the token rows of index rows `rows` (TokenStore.set_tokens): row rows[j] gets the next lens[j] rows of
+        `token_rows` [sum(lens), dim] (a device or host fp16 array), `token_ids[j]` its token ids for `explain`."""
+        with self._lock:
+            st = self._need_tokens("set_tokens")
+            rows = [int(r) for r in rows]
+            if any(not 0 <= r < self._n for r in rows):
+                raise ValueError(f"set_tokens: a row outside the {self._n} rows in use")
+            st.set_tokens(rows, token_rows, lens, token_ids)
+
+    def ids_without_tokens(self, ids: Sequence[str]) -> List[str]:
+        """the ids, in order, that have a live row which keeps no tokens (what an ingest still has to encode)"""
+        with self._lock:
+            st = self._need_tokens("ids_without_tokens")
+            return [i for i in ids if i in self._row_of and st.length(self._row_of[i]) == 0]
+
+    def set_tokens_for_ids(self, ids: Sequence[str], token_rows, lens: Sequence[int], token_ids=None,
+                           only_empty: bool = True) -> int:
+        """set_tokens by id, resolved and written under ONE lock: rows are renumbered by a compaction, so a row number
+        looked up before an encoder forward may name another document after it.  ids[j] owns the next lens[j] rows of
+        `token_rows`.  An id without a live row by now (deleted, the collection reset) is dropped with its rows, and --
+        `only_empty` -- so is one whose row already keeps tokens: the tokens under a row are those of the document
+        under it (add() ignores an id that exists, so its new text is not what is stored).  Returns the ids written."""
+        with self._lock:
+            st = self._need_tokens("set_tokens_for_ids")
+            lens = [int(n) for n in lens]
+            if len(lens) != len(ids) or (token_ids is not None and len(token_ids) != len(ids)):
+                raise ValueError(f"set_tokens_for_ids: {len(ids)} ids for {len(lens)} lengths")
+            rows = [self._row_of.get(i, -1) for i in ids]
+            keep, seen = [], set()
+            for j, r in enumerate(rows):
+                if r >= 0 and r not in seen and not (only_empty and st.length(r) > 0):
+                    seen.add(r)
+                    keep.append(j)
+            if not keep:
+                return 0
+            if len(keep) != len(ids):
+                starts = np.concatenate([[0], np.cumsum(lens)])
+                pick = np.concatenate([np.arange(starts[j], starts[j + 1]) for j in keep]).astype(np.int64)
+                token_rows = st._take(st._as_rows(token_rows), pick)
+            st.set_tokens([rows[j] for j in keep], token_rows, [lens[j] for j in keep],
+                          None if token_ids is None else [token_ids[j] for j in keep])
+            return len(keep)
+
+    def token_spans(self, ids_lists: Sequence[Sequence[str]], with_ids: bool = False):
+        """One snapshot, under the lock, of where the token rows of these ids lie: (spans, plane, max_doc_tokens) with,
+        per id in order, (first plane row, length, token ids if `with_ids` else None), or None for an id without a live
+        row or whose row keeps no tokens.  `plane` is the tensor those rows are in: a later fill or compaction swaps a
+        new one in and appends write past the rows a snapshot names, so the snapshot stays valid for a launch that
+        follows.  (None, None, None) without a token store."""
+        with self._lock:
+            st = self._tokens
+            if st is None:
+                return None, None, None
+            off = st.offsets()
+            spans: List[Any] = []
+            for ids in ids_lists:
+                for i in ids:
+                    r = self._row_of.get(i, -1)
+                    n = st.length(r) if r >= 0 else 0
+                    spans.append((int(off[r]), n, st.token_ids(r) if with_ids else None) if n > 0 else None)
+            return spans, st.plane, st.max_doc_tokens
+
+    def token_stats(self) -> Optional[Dict[str, Any]]:
+        with self._lock:
+            return None if self._tokens is None else self._tokens.stats()
+
+    def late_search(self, q_tokens: torch.Tensor, q_start, q_len, n_results: int,
+                    where: Optional[Dict[str, Any]] = None):
+        """First-stage late-interaction retrieval (csrc/maxsim_scan.hip, include/mmrag.h mmrag_maxsim_topk): each
+        question's exact MaxSim top-k over the token rows of ALL live stored rows that match `where` -- no pooled-vector
+        search before it.  Question s is rows q_start[s] .. q_start[s] + q_len[s] of the device fp16 tensor `q_tokens`
+        [rows, dim] (unit rows of the encoder that filled the store).  Returns device (scores [Q, k] float32 -- the
+        SUM over the question's tokens, descending, ties to the lower row -- and rows [Q, k] int64, -1 = none); a row
+        without stored tokens is never returned.  No host synchronisation unless rows_in_use exceeds a question's
+        candidate slots."""
+        k = int(n_results)
+        if not 1 <= k <= _native.MAX_K_DEEP:
+            raise ValueError(f"n_results must be in 1..{_native.MAX_K_DEEP} for a late search")
+        with self._lock:
+            st = self._need_tokens("late_search")
+            if q_tokens.dim() != 2 or q_tokens.shape[1] != st.dim:
+                raise ValueError(f"late_search: question token rows must be [rows, {st.dim}]")
+            bits = self._where_bits(where)
+            q_start, q_len = [int(v) for v in q_start], [int(v) for v in q_len]
+            tiles = _native.late_question_tiles(q_start, q_len, q_tokens.shape[0])
+            need = _native.maxsim_topk_workspace_bytes(len(q_start), self._n, k, st.dim, tiles)
+            if self._late_ws is None or _native._nbytes(self._late_ws) < need:
+                self._late_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+            return _native.maxsim_topk(q_tokens, q_start, q_len, st.plane, st.n_rows, st.device_offsets(self._n),
+                                       self._n, st.dim, k, alive_bits=bits, workspace=self._late_ws)
+
+    def late_query(self, q_tokens: torch.Tensor, q_start, q_len, n_results: int = 10,
+                   where: Optional[Dict[str, Any]] = None,
+                   include: Sequence[str] = ("metadatas", "documents", "distances")) -> Dict[str, Any]:
+        """late_search as a Chroma-shaped result (the shared result builder): `late_scores` is score / q_len, the mean
+        over the question's tokens of each token's best cosine, so it reads like a cosine; `distances` is 1 - that
+        (there is no pooled cosine: no pooled search ran)."""
+        with self._lock, stage("search"):
+            scores, rows = self.late_search(q_tokens, q_start, q_len, n_results, where)
+            tables = self._tables()
+            emb_src = self._full if "embeddings" in include else None
+            q_len_dev = _native._pinned_to_device(torch.as_tensor(q_len, dtype=torch.float32).reshape(-1, 1).cpu(),
+                                                  self.device)
+            mean = scores / q_len_dev
+        with stage("collect"):
+            mean_h, rows_h = mean.cpu(), rows.cpu()
+            out = self._collect(mean_h, rows_h, include, *tables, emb_src)
+            out["late_scores"] = [srow[: len(found)] for srow, found in zip(mean_h.tolist(), out["ids"])]
             return out
 
     # ------------------------------------------------------------------ lexical / hybrid ----

@@ -64,11 +64,14 @@ class LateInteractionScorer:
             ids[i, : len(r)] = r
         return ids, np.array([len(r) for r in rows], np.int32)
 
-    def plan(self, queries: Sequence[str], docs: Sequence[str], pairs: Sequence[Tuple[int, int]]):
+    def plan(self, queries: Sequence[str], docs: Sequence[str], pairs: Sequence[Tuple[int, int]],
+             stored: Optional[Sequence[bool]] = None):
         """The host half of score_pairs: tokenise the distinct texts that some pair uses and lay out one encoder batch.
         Returns a dict: ids [B, W] / lens [B] (queries first, then passages), the six tables of mmrag_maxsim_scores
         relative to the packed token rows (q_start, q_len, d_start, d_len, pair_q, pair_d; [CLS] and the final [SEP]
-        trimmed through start / len), and q_ids / d_ids, the scored token ids of each sequence."""
+        trimmed through start / len), and q_ids / d_ids, the scored token ids of each sequence.
+        `stored` (one flag per passage; the token store): a flagged passage is neither tokenised nor encoded -- its
+        pairs get pair_d = -1 and the caller scores them from the stored rows."""
         pairs = [(int(a), int(b)) for a, b in pairs]
         if not pairs:
             raise ValueError("score_pairs: no pairs")
@@ -83,11 +86,14 @@ class LateInteractionScorer:
             qt = queries[a] if queries[a] is not None else ""
             dt = docs[b] if docs[b] is not None else ""
             pair_q.append(q_slot.setdefault(qt, len(q_slot)))
-            pair_d.append(d_slot.setdefault(dt, len(d_slot)))
+            pair_d.append(-1 if stored is not None and stored[b] else d_slot.setdefault(dt, len(d_slot)))
         q_texts, d_texts = list(q_slot), list(d_slot)
         q_max, d_max = self.max_query_tokens + 2, self.max_doc_tokens + 2
         q_ids, q_lens = self._tokenize(q_texts, q_max)
-        d_ids, d_lens = self._tokenize(d_texts, d_max)
+        if d_texts:
+            d_ids, d_lens = self._tokenize(d_texts, d_max)
+        else:       # every passage is stored: the batch is the queries alone
+            d_ids, d_lens = np.zeros((0, 1), np.int32), np.zeros(0, np.int32)
         q_lens, d_lens = np.minimum(q_lens, q_max), np.minimum(d_lens, d_max)
         W = max(q_ids.shape[1], d_ids.shape[1])
         ids = np.zeros((len(q_texts) + len(d_texts), W), np.int32)
@@ -109,17 +115,134 @@ class LateInteractionScorer:
                 "pair_q": np.asarray(pair_q, np.int32), "pair_d": np.asarray(pair_d, np.int32),
                 "q_ids": seq_ids[:nq], "d_ids": seq_ids[nq:]}
 
+    # A forward of at most this many tokens takes the encoder's single-query GEMM kernels (csrc/encoder.hip
+    # takes_small16_kernel: M <= 64), which split K over the waves of a workgroup: the same sequence then gets other
+    # low bits than in any larger batch, where every tile kernel adds a row's K products in one order.
+    SMALL_FORWARD_TOKENS = 64
+
+    def _encode_stable(self, ids: np.ndarray, lens: np.ndarray):
+        """encode_tokens whose rows' bits depend on each sequence alone: a forward that would hold at most
+        SMALL_FORWARD_TOKENS tokens is filled up past them with filler sequences (copies of the first id), whose rows
+        are dropped.  What the token store keeps and what is scored against it go through here, so a stored row equals
+        the row any re-encoding forward of more than SMALL_FORWARD_TOKENS tokens computes.  Returns (tokens, cu) of the
+        real sequences."""
+        lens = np.asarray(lens, np.int32)
+        total, n = int(lens.sum()), len(lens)
+        if total > self.SMALL_FORWARD_TOKENS:
+            return self.encoder.encode_tokens(ids, lens, self.projection)
+        fill, most = [], self.encoder_max_length
+        short = self.SMALL_FORWARD_TOKENS + 1 - total
+        while short > 0:
+            fill.append(min(short, most))
+            short -= fill[-1]
+        W = max(ids.shape[1], max(fill))
+        padded = np.full((n + len(fill), W), int(ids[0, 0]), np.int32)
+        padded[:n, : ids.shape[1]] = ids
+        tokens, cu = self.encoder.encode_tokens(padded, np.concatenate([lens, np.asarray(fill, np.int32)]),
+                                                self.projection)
+        return tokens[:total], cu[: n + 1]
+
+    def trimmed(self, lens: np.ndarray):
+        """(first scored token, scored tokens) of sequences [CLS] t_1 .. t_m [SEP] of `lens` ids, relative to each
+        sequence's first id -- plan()'s rule: t_1 .. t_m, or the [CLS] row alone for a text without a single token"""
+        inner = np.maximum(np.asarray(lens, np.int64) - 2, 0)
+        return np.where(inner > 0, 1, 0), np.where(inner > 0, inner, 1)
+
+    def encode_documents(self, texts: Sequence[Optional[str]], batch: int = 64):
+        """What the token store keeps of `texts`: (token rows [sum(lens), dim] device fp16, lens [n], token ids per
+        text) -- each text tokenised and truncated as plan() does a passage, encoded `batch` texts per forward, [CLS]
+        and the final [SEP] trimmed as plan() trims them.  A token row's bits depend on its own sequence alone, so these
+        are the rows a re-rank would compute again (_encode_stable says for which forwards that holds)."""
+        import torch
+
+        texts = [t if t is not None else "" for t in texts]
+        parts, lens_out, ids_out = [], [], []
+        for lo in range(0, len(texts), batch):
+            ids, lens = self._tokenize(texts[lo: lo + batch], self.max_doc_tokens + 2)
+            lens = np.minimum(lens, self.max_doc_tokens + 2).astype(np.int32)
+            tokens, _ = self._encode_stable(ids, lens)
+            cu = np.zeros(len(lens) + 1, np.int64)
+            np.cumsum(lens, out=cu[1:])
+            first, count = self.trimmed(lens)
+            pick = np.concatenate([np.arange(cu[s] + first[s], cu[s] + first[s] + count[s]) for s in range(len(lens))])
+            parts.append(tokens.index_select(0, torch.from_numpy(pick).to(tokens.device)))
+            lens_out.extend(int(c) for c in count)
+            ids_out.extend(ids[s, first[s]: first[s] + count[s]].tolist() for s in range(len(lens)))
+        dim = int(self.projection.shape[0]) if self.projection is not None else int(self.encoder.cfg.hidden)
+        rows = torch.cat(parts) if parts else torch.zeros((0, dim), dtype=torch.float16)
+        return rows, np.asarray(lens_out, np.int32), ids_out
+
+    def encode_questions(self, texts: Sequence[str]):
+        """(token rows device fp16, q_start, q_len, token ids per question) of questions alone: ONE forward, trimmed as
+        plan() trims a query"""
+        ids, lens = self._tokenize([t if t is not None else "" for t in texts], self.max_query_tokens + 2)
+        lens = np.minimum(lens, self.max_query_tokens + 2).astype(np.int32)
+        tokens, _ = self._encode_stable(ids, lens)
+        cu = np.zeros(len(lens) + 1, np.int64)
+        np.cumsum(lens, out=cu[1:])
+        first, count = self.trimmed(lens)
+        q_ids = [ids[s, first[s]: first[s] + count[s]].tolist() for s in range(len(lens))]
+        return tokens, (cu[:-1] + first).astype(np.int32), count.astype(np.int32), q_ids
+
+    def _run_stored(self, queries, docs, pairs, spans, plane, want_best: bool):
+        """_run with a token store: `spans[b]` is (first plane row, length, token ids) of passage b's stored rows, or
+        None.  ONE forward over the queries and the passages that are not stored, then one MaxSim launch for the
+        stored passages' pairs (against `plane`) and one for the others.  Returns _run's tuple; the plan's d_ids /
+        pair_d are rewritten so that pair p's passage ids are plan["d_ids"][plan["pair_d"][p]] as in _run."""
+        import torch
+
+        stored = [s is not None for s in spans]
+        plan = self.plan(queries, docs, pairs, stored=stored)
+        tokens, _ = self._encode_stable(plan["ids"], plan["lens"])
+        dim = int(self.projection.shape[0]) if self.projection is not None else int(self.encoder.cfg.hidden)
+        P, W = len(plan["pair_q"]), _native.MAX_LATE_QUERY_TOKENS
+        from_store = np.array([stored[int(b)] for _, b in pairs], bool)
+        packed = np.zeros((P, 1 + 2 * W if want_best else 1), np.int32)
+        d_ids = list(plan["d_ids"])
+        pair_d = plan["pair_d"].copy()
+        for mask, d_tok in ((from_store, plane), (~from_store, tokens)):
+            at = np.nonzero(mask)[0]
+            if at.size == 0:
+                continue
+            if d_tok is plane:
+                used = sorted({int(pairs[p][1]) for p in at})
+                slot = {b: i for i, b in enumerate(used)}
+                d_start = np.array([spans[b][0] for b in used], np.int32)
+                d_len = np.array([spans[b][1] for b in used], np.int32)
+                pd = np.array([slot[int(pairs[p][1])] for p in at], np.int32)
+                for b in used:
+                    pair_of = len(d_ids)
+                    d_ids.append(list(spans[b][2]) if spans[b][2] is not None else [0] * int(spans[b][1]))
+                    pair_d[[p for p in at if int(pairs[p][1]) == b]] = pair_of
+            else:
+                d_start, d_len, pd = plan["d_start"], plan["d_len"], plan["pair_d"][at]
+            sums, best_sim, best_idx = _native.maxsim_scores(tokens, d_tok, dim, plan["q_start"], plan["q_len"], d_start,
+                                                             d_len, plan["pair_q"][at], pd, want_best=want_best)
+            cols = [sums.view(torch.int32).reshape(-1, 1)]
+            if want_best:
+                cols += [best_sim.view(torch.int32), best_idx]
+            packed[at] = torch.cat(cols, dim=1).cpu().numpy()
+        plan["d_ids"], plan["pair_d"] = d_ids, pair_d
+        q_len = plan["q_len"][plan["pair_q"]].astype(np.float32)
+        scores = packed[:, 0].copy().view(np.float32) / q_len
+        if not want_best:
+            return scores, None, None, plan
+        sims = np.ascontiguousarray(packed[:, 1: 1 + W]).view(np.float32)
+        return scores, sims, np.ascontiguousarray(packed[:, 1 + W:]), plan
+
     def _token(self, token_id: int) -> Any:
         if self._id2tok is None:
             return int(token_id)
         return self._id2tok.get(int(token_id), int(token_id))
 
     # ------------------------------------------------------------------ scoring -------------
-    def _run(self, queries, docs, pairs, want_best: bool):
+    def _run(self, queries, docs, pairs, want_best: bool, spans=None, plane=None):
         """(scores [P] float32, best_sim [P, 128] float32 | None, best_idx [P, 128] int32 | None, plan): one tokenise
         of the distinct texts, ONE encoder forward over queries and passages together, ONE MaxSim launch, one copy back"""
         import torch
 
+        if spans is not None and any(s is not None for s in spans):
+            return self._run_stored(queries, docs, pairs, spans, plane, want_best)
         plan = self.plan(queries, docs, pairs)
         tokens, _ = self.encoder.encode_tokens(plan["ids"], plan["lens"], self.projection)
         dim = int(self.projection.shape[0]) if self.projection is not None else int(self.encoder.cfg.hidden)
@@ -138,20 +261,23 @@ class LateInteractionScorer:
         sims = np.ascontiguousarray(packed[:, 1: 1 + W]).view(np.float32)
         return scores, sims, np.ascontiguousarray(packed[:, 1 + W:]), plan
 
-    def score_pairs(self, queries: List[str], docs: List[str], pairs: List[Tuple[int, int]], explain: bool = False):
+    def score_pairs(self, queries: List[str], docs: List[str], pairs: List[Tuple[int, int]], explain: bool = False,
+                    spans=None, plane=None):
         """MaxSim score of every pair (i, j) = (queries[i], docs[j]): float32 [len(pairs)], out_sum / q_len -- the mean
         over the query's tokens of each token's best cosine against the passage's tokens, so it reads like a cosine.
         `explain`: returns (scores, matches) with, per pair, [(query_token, doc_token, sim)] in query-token order:
-        token strings from the tokenizer's `vocab` where it has one, ids otherwise."""
+        token strings from the tokenizer's `vocab` where it has one, ids otherwise.
+        `spans`, `plane` (the token store): spans[b] = (first row, length, token ids) of passage b's rows in the device
+        plane, or None -- such a passage is scored from those rows instead of being encoded again, with the same bits."""
         if not explain:
-            return self._run(queries, docs, pairs, False)[0]
-        scores, records = self.explain_pairs(queries, docs, pairs)
+            return self._run(queries, docs, pairs, False, spans, plane)[0]
+        scores, records = self.explain_pairs(queries, docs, pairs, spans, plane)
         return scores, [[(m["query_token"], m["doc_token"], m["similarity"]) for m in rec] for rec in records]
 
-    def explain_pairs(self, queries: List[str], docs: List[str], pairs: List[Tuple[int, int]]):
+    def explain_pairs(self, queries: List[str], docs: List[str], pairs: List[Tuple[int, int]], spans=None, plane=None):
         """(scores, records): per pair one dict per query token -- query_token, doc_token (as score_pairs names them),
         doc_index (the matched token's 0-based position among the passage's scored tokens) and similarity"""
-        scores, sims, idx, plan = self._run(queries, docs, pairs, True)
+        scores, sims, idx, plan = self._run(queries, docs, pairs, True, spans, plane)
         records = []
         for p in range(len(scores)):
             qi, di = plan["q_ids"][plan["pair_q"][p]], plan["d_ids"][plan["pair_d"][p]]

@@ -110,6 +110,15 @@ class QueryRequest(BaseModel):  # api.py:161-164
     # `doc_ids`.  The reserved key "$added_at" (UNIX seconds a row was added) needs device filters
     # (MMRAG_DEVICE_FILTERS)
     filter: Optional[Dict[str, Any]] = None
+    # not in the reference: first-stage late-interaction retrieval (EmbeddingManager.late_query): the hits are the
+    # stored items of highest MaxSim against the question's tokens, from one scan of the token store -- no pooled-vector
+    # search before it.  Each source carries its `late_score` (the mean over the question's tokens of each token's
+    # best cosine).  `relevance_score` stays the pooled cosine wherever a pooled search produced the hit; this mode
+    # runs none, so here it is the late score too.  Needs the token store (MMRAG_LATE_STORE=1 or
+    # EmbeddingManager.enable_late_store()); `doc_ids` and `filter` restrict it, `rerank` re-ranks its hits.  Not
+    # combined with `hybrid`, `mmr`, `group_by_document`, `boost`, `variants` / `expand` or `like` / `unlike` / `not`
+    # yet
+    late: bool = Field(False)
 
 
 FILTER_MAX_LEAVES, FILTER_MAX_DEPTH = 32, 8
@@ -207,6 +216,13 @@ RECOMMEND_COLUMNS = (("scores", "score"), ("penalties", "penalty"), ("matched", 
 LATE_NEEDS = ("late_rerank", "has_late_reranker",
               "Late-interaction re-ranking is not available with this embedder: it needs a single BERT-family HIP "
               "engine in fp16 mode with a tokenizer (EmbeddingManager.late_rerank)")
+
+
+# first-stage late retrieval (`late`): the same
+LATE_QUERY_NEEDS = ("late_query", "supports_late_query",
+                    "Late retrieval is not available with this embedder: it needs a single BERT-family HIP engine in "
+                    "fp16 mode, a single-GPU collection and the token store (MMRAG_LATE_STORE=1 or "
+                    "EmbeddingManager.enable_late_store())")
 
 
 # /duplicates: what it needs of the embedder and the 400 detail when that is missing (worded like MODE_NEEDS)
@@ -389,7 +405,7 @@ class Pipeline:
                      fusion: Optional[str] = None, doc_ids: Optional[List[str]] = None,
                      rerank_method: Optional[str] = None, explain: bool = False, boost: Any = None,
                      recommend: Optional[Dict[str, Any]] = None,
-                     filter_dict: Optional[Dict[str, Any]] = None) -> Optional[dict]:
+                     filter_dict: Optional[Dict[str, Any]] = None, late: bool = False) -> Optional[dict]:
         """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
         max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the re-ranker's best top_k (`rerank_method` "cross" or "late",
         default MMRAG_RERANK_METHOD; `explain`: late interaction's per-token matches on every source).  `hybrid`: from
@@ -404,7 +420,8 @@ class Pipeline:
         (EmbeddingManager.boosted_query).  `recommend` ({"like", "unlike", "unlike_texts", "negative_weight"}; alone or
         with `rerank`): the question is one positive example next to these (EmbeddingManager.recommend).
         `filter_dict`: a metadata filter every mode gets as (part of) its filter; a plain or re-ranked query with one
-        goes through EmbeddingManager.query, `doc_ids` AND-ed into it"""
+        goes through EmbeddingManager.query, `doc_ids` AND-ed into it.  `late` (alone or with `rerank`): the hits are
+        the exact MaxSim top_k over the token store (EmbeddingManager.late_query)"""
         multi = variants is not None
         # the restriction as the filter the embedder's methods take (nothing is passed when there is none)
         docs_only = None if doc_ids is None else {"doc_id": {"$in": list(doc_ids)}}
@@ -424,13 +441,16 @@ class Pipeline:
             search = functools.partial(self.embedder.mmr_query, lambda_mult=mmr_lambda, **only)
         elif hybrid:
             search = functools.partial(self.embedder.hybrid_query, **only)
+        elif late:
+            search = functools.partial(self.embedder.late_query, **only)
         elif doc_ids is not None and not filter_dict and hasattr(self.embedder, "scoped_query"):
             search = functools.partial(self.embedder.scoped_query, doc_ids=list(doc_ids))
         else:
             search = functools.partial(self.embedder.query, **only)
         # per-hit columns re-ranking carries along
         extra = ("fused_scores", "matched_queries") if multi else ("mmr_scores",) if mmr else \
-            ("hybrid_scores",) if hybrid else ("scores", "boosts") if boost is not None else \
+            ("hybrid_scores",) if hybrid else ("late_scores",) if late else \
+            ("scores", "boosts") if boost is not None else \
             tuple(column for column, _ in RECOMMEND_COLUMNS) if recommend is not None else ()
         if group_by_document:
             hits = await self.embedder.grouped_query(question, n_groups=top_k, group_size=per_document, **only)
@@ -461,7 +481,8 @@ class Pipeline:
                                                 max_tokens=1000, temperature=0.7)
         ranked = self._sources(hits)
         for on, column, key in ((rerank, "rerank_scores", "rerank_score"), (hybrid, "hybrid_scores", "hybrid_score"),
-                                (mmr, "mmr_scores", "mmr_score"), (multi, "fused_scores", "fused_score"),
+                                (mmr, "mmr_scores", "mmr_score"), (late, "late_scores", "late_score"),
+                                (multi, "fused_scores", "fused_score"),
                                 (multi, "matched_queries", "matched_queries"), (boost is not None, "scores", "score"),
                                 (boost is not None, "boosts", "boost"),
                                 *((recommend is not None, column, key) for column, key in RECOMMEND_COLUMNS)):
@@ -653,6 +674,15 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
         if request.mmr and request.hybrid:
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="MMR and hybrid retrieval are not combined yet: send `mmr` or `hybrid`, not both")
+        if request.late:
+            if (multi or request.mmr or request.hybrid or request.group_by_document or spec is not None
+                    or recommend is not None):
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                    detail="Late retrieval is not combined with hybrid retrieval, MMR, grouping by "
+                                           "document, boosted retrieval, multi-query retrieval or recommend retrieval "
+                                           "yet: send `late` without `hybrid`, `mmr`, `group_by_document`, `boost`, "
+                                           "`variants` / `expand` and `like` / `unlike` / `not`")
+            pipe._need(LATE_QUERY_NEEDS)
         for flag, method, supports, detail in MODE_NEEDS:
             if getattr(request, flag) and not (hasattr(pipe.embedder, method)
                                                and getattr(pipe.embedder, supports, lambda: True)()):
@@ -684,7 +714,8 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
                                     rerank_method="late" if late else request.rerank_method, explain=request.explain,
                                     **({} if spec is None else {"boost": spec}),
                                     **({} if recommend is None else {"recommend": recommend}),
-                                    **({} if not request.filter else {"filter_dict": request.filter}))
+                                    **({} if not request.filter else {"filter_dict": request.filter}),
+                                    **({} if not request.late else {"late": True}))
         except ValueError as e:
             if recommend is None:
                 raise
