@@ -901,6 +901,43 @@ int mmrag_maxsim_topk(const void *q_tok, int64_t q_rows, int64_t q_ld, const int
                       const uint32_t *alive_bits, int dim, int k, float *out_scores, int64_t *out_items,
                       void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * FP8 token rows: the token store at one byte per element, MaxSim on the block-scaled FP8 matrix instruction
+ * (v_mfma_scale_f32_16x16x128_f8f6f4, E4M3 x E4M3, scales 1.0).  TokenStore(dtype="float8_e4m3fn").
+ *
+ * Definition
+ *   - An FP8 token row is a row of MMRAG_F8E4M3 codes as stored by FP8 collections: the OCP E4M3 code of x * 256
+ *     rounded to nearest even, subnormals kept, magnitudes above 448 saturate to 448, NaN stores +0; pad columns are
+ *     code 0.  The row pitch is mmrag_padded_dim(dim, MMRAG_F8E4M3) or a larger width of whole 128-byte slabs.
+ *   - BOTH operands are code rows, the questions included (there is no mixed-precision matrix instruction): the caller
+ *     quantises the question's fp16 rows first, with mmrag_f8_encode_rows.
+ *   - sim(q_i, d_j) = the float32 accumulator of the decoded values' dot product in the tile body's fixed K order,
+ *     times 2^-16 (exact).  The scores are the quantised rows' own; nothing is re-scored at a higher precision.
+ *   - Everything else is mmrag_maxsim_scores' and mmrag_maxsim_topk's contract word for word: maxima over the item's
+ *     or passage's own rows only, masked by index; best_idx the LOWEST j; the sum in ascending i from 0.0f; top-k
+ *     descending, ties to the lower item, (-inf, -1) padding; every output a pure function of the inputs; the scan's
+ *     score of a (question, item) has the bits of mmrag_maxsim_scores_f8's out_sum of the same pair.
+ *
+ * mmrag_f8_encode_rows   dst[r, c] = the code of src[r, c] for c < d, code 0 for d <= c < dst_ld.
+ *   src        dev [m, src_ld] of src_dtype MMRAG_F16 or MMRAG_F32 (any other: MMRAG_EINVAL), src_ld >= d
+ *   dst        dev [m, dst_ld] bytes, 16-byte aligned, dst_ld >= d of whole 128-byte slabs
+ * mmrag_maxsim_scores_f8 / mmrag_maxsim_topk_f8   the arguments of mmrag_maxsim_scores / mmrag_maxsim_topk with code
+ *   rows for q_tok, d_tok and tok and the FP8 pitch rule for q_ld, d_ld and ld; the same refusals, reported under
+ *   their own names.  mmrag_maxsim_topk_f8_workspace_bytes is the FP8 scan's bound (its packed question tiles are
+ *   half the fp16 scan's). */
+int mmrag_f8_encode_rows(const void *src, int src_dtype, int64_t m, int d, int64_t src_ld, void *dst, int64_t dst_ld,
+                         void *stream);
+int mmrag_maxsim_scores_f8(const void *q_codes, int64_t q_rows, int64_t q_ld, const void *d_codes, int64_t d_rows,
+                           int64_t d_ld, int dim, const int32_t *q_start, const int32_t *q_len, int n_q,
+                           const int32_t *d_start, const int32_t *d_len, int n_d, const int32_t *pair_q,
+                           const int32_t *pair_d, int P, float *out_sum, float *out_best_sim, int32_t *out_best_idx,
+                           void *stream);
+size_t mmrag_maxsim_topk_f8_workspace_bytes(int Q, int64_t n_items, int k);
+int mmrag_maxsim_topk_f8(const void *q_codes, int64_t q_rows, int64_t q_ld, const int32_t *q_start,
+                         const int32_t *q_len, int Q, const void *codes, int64_t T, int64_t ld,
+                         const int32_t *item_off, int64_t n_items, const uint32_t *alive_bits, int dim, int k,
+                         float *out_scores, int64_t *out_items, void *workspace, size_t workspace_bytes, void *stream);
+
 /* CLIP byte-level BPE (the text tower's tokenizer, BASELINE config 4; the reference only names CLIP in config.py:106).
  * Host code, multi-threaded; equals multimodal_rag_amd/tokenizer.py:ClipBpeTokenizer, which tests pin to
  * transformers.CLIPTokenizer.  The caller passes text already NFC-normalised, whitespace-collapsed and lower-cased.

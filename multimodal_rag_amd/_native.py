@@ -299,6 +299,19 @@ def _declare(lib):
     lib.mmrag_internal_maxsim_topk_ex.argtypes = lib.mmrag_maxsim_topk.argtypes + [c_int, c_int64, ctypes.c_uint, c_int]
     lib.mmrag_internal_maxsim_topk_workspace_bytes_ex.restype = c_size_t
     lib.mmrag_internal_maxsim_topk_workspace_bytes_ex.argtypes = [c_int, c_int64, c_int, c_int, c_int]
+    # FP8 token rows: the same entries over E4M3 code rows, and the row encoder (csrc/maxsim.hip, csrc/maxsim_scan.hip)
+    lib.mmrag_f8_encode_rows.restype = c_int
+    lib.mmrag_f8_encode_rows.argtypes = [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int64, c_void_p]
+    lib.mmrag_maxsim_scores_f8.restype = c_int
+    lib.mmrag_maxsim_scores_f8.argtypes = lib.mmrag_maxsim_scores.argtypes
+    lib.mmrag_maxsim_topk_f8_workspace_bytes.restype = c_size_t
+    lib.mmrag_maxsim_topk_f8_workspace_bytes.argtypes = [c_int, c_int64, c_int]
+    lib.mmrag_maxsim_topk_f8.restype = c_int
+    lib.mmrag_maxsim_topk_f8.argtypes = lib.mmrag_maxsim_topk.argtypes
+    lib.mmrag_internal_maxsim_topk_f8_ex.restype = c_int
+    lib.mmrag_internal_maxsim_topk_f8_ex.argtypes = lib.mmrag_internal_maxsim_topk_ex.argtypes
+    lib.mmrag_internal_maxsim_topk_f8_workspace_bytes_ex.restype = c_size_t
+    lib.mmrag_internal_maxsim_topk_f8_workspace_bytes_ex.argtypes = [c_int, c_int64, c_int, c_int, c_int]
     from .lexical import declare as declare_lexical   # BM25 analyzer, device index and search (csrc/lexical.hip)
 
     declare_lexical(lib)
@@ -1231,6 +1244,9 @@ def recommend_topk(examples: torch.Tensor, sign, neg_weight, rows: torch.Tensor,
     return (out_s, out_r, *expl)
 
 
+_DT_NAME = {torch.float16: "float16", torch.uint8: "uint8"}     # what the MaxSim wrappers call their row tensors
+
+
 def check_late_tables(q_rows: int, d_rows: int, q_start, q_len, d_start, d_len, pair_q, pair_d) -> Tuple[int, int, int]:
     """The sequence and pair tables of maxsim_scores as HOST integer sequences, checked the way the device cannot
     report (there a bad pair only gets a NaN): returns (n_q, n_d, P).  Raises MMRagNativeError for tables of unequal
@@ -1260,20 +1276,21 @@ def check_late_tables(q_rows: int, d_rows: int, q_start, q_len, d_start, d_len, 
 
 
 def maxsim_scores(q_tok: torch.Tensor, d_tok: torch.Tensor, dim: int, q_start, q_len, d_start, d_len, pair_q, pair_d,
-                  want_best: bool = True):
+                  want_best: bool = True, _f8: bool = False):
     """Late-interaction (MaxSim) scores of (query, passage) pairs over fp16 token rows (include/mmrag.h
     mmrag_maxsim_scores).  `q_tok` [q_rows, ld] and `d_tok` [d_rows, ld] are device tensors of unit rows (they may be the
     same tensor); sequence s of a side is rows start[s] .. start[s] + len[s].  The six tables are HOST integer tensors
     or sequences: they are checked here (check_late_tables) and copied to the device in one transfer.  Returns device
     tensors (sums [P] float32, best_sim [P, MAX_LATE_QUERY_TOKENS] float32, best_idx [P, MAX_LATE_QUERY_TOKENS] int32),
     the last two None unless `want_best`; slots i >= q_len of a pair are not written.  One launch on the current
-    stream, no host synchronisation."""
+    stream, no host synchronisation.  (`_f8`: maxsim_scores_f8's switch.)"""
+    who, row_dtype = ("maxsim_scores_f8", torch.uint8) if _f8 else ("maxsim_scores", torch.float16)
     _dev_check(q_tok, d_tok)
     for name, t in (("q_tok", q_tok), ("d_tok", d_tok)):
-        if t.dim() != 2 or not t.is_contiguous() or t.dtype != torch.float16:
-            raise MMRagNativeError(f"maxsim_scores: {name} must be a contiguous 2-D float16 tensor")
+        if t.dim() != 2 or not t.is_contiguous() or t.dtype != row_dtype:
+            raise MMRagNativeError(f"{who}: {name} must be a contiguous 2-D {_DT_NAME[row_dtype]} tensor")
     if q_tok.device != d_tok.device:
-        raise MMRagNativeError("maxsim_scores: q_tok and d_tok must be on one device")
+        raise MMRagNativeError(f"{who}: q_tok and d_tok must be on one device")
     tables = [torch.as_tensor(t, dtype=torch.int32).reshape(-1).cpu()
               for t in (q_start, q_len, d_start, d_len, pair_q, pair_d)]
     n_q, n_d, P = check_late_tables(q_tok.shape[0], d_tok.shape[0], *(t.tolist() for t in tables))
@@ -1285,20 +1302,60 @@ def maxsim_scores(q_tok: torch.Tensor, d_tok: torch.Tensor, dim: int, q_start, q
     best_sim = torch.empty((P, MAX_LATE_QUERY_TOKENS), dtype=torch.float32, device=dev) if want_best else None
     best_idx = torch.empty((P, MAX_LATE_QUERY_TOKENS), dtype=torch.int32, device=dev) if want_best else None
     with torch.cuda.device(dev):
-        st = lib().mmrag_maxsim_scores(q_tok.data_ptr(), q_tok.shape[0], q_tok.shape[1], d_tok.data_ptr(),
-                                       d_tok.shape[0], d_tok.shape[1], int(dim), qs.data_ptr(), ql.data_ptr(), n_q,
-                                       ds.data_ptr(), dl.data_ptr(), n_d, pq.data_ptr(), pd.data_ptr(), P,
-                                       sums.data_ptr(), _ptr(best_sim), _ptr(best_idx), _stream_ptr(dev))
-    _check(st, "mmrag_maxsim_scores")
+        fn = lib().mmrag_maxsim_scores_f8 if _f8 else lib().mmrag_maxsim_scores
+        st = fn(q_tok.data_ptr(), q_tok.shape[0], q_tok.shape[1], d_tok.data_ptr(), d_tok.shape[0], d_tok.shape[1],
+                int(dim), qs.data_ptr(), ql.data_ptr(), n_q, ds.data_ptr(), dl.data_ptr(), n_d, pq.data_ptr(),
+                pd.data_ptr(), P, sums.data_ptr(), _ptr(best_sim), _ptr(best_idx), _stream_ptr(dev))
+    _check(st, "mmrag_" + who)
     return sums, best_sim, best_idx
 
 
-def maxsim_topk_workspace_bytes(Q: int, n_items: int, k: int, dim: int = 0, max_tiles: int = 0) -> int:
+def maxsim_scores_f8(q_codes: torch.Tensor, d_codes: torch.Tensor, dim: int, q_start, q_len, d_start, d_len, pair_q,
+                     pair_d, want_best: bool = True):
+    """maxsim_scores over rows of E4M3 codes on BOTH sides (include/mmrag.h mmrag_maxsim_scores_f8): contiguous uint8
+    tensors [rows, ld], ld = padded_dim(dim, torch.float8_e4m3fn) or more whole slabs, as f8_encode_rows writes them.
+    A similarity is the decoded rows' float32 dot product times 2^-16; everything else is maxsim_scores'."""
+    return maxsim_scores(q_codes, d_codes, dim, q_start, q_len, d_start, d_len, pair_q, pair_d, want_best, _f8=True)
+
+
+def f8_encode_rows(src: torch.Tensor, d: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The E4M3 code rows of `src` [m, >= d] (a device float16 or float32 tensor whose rows are contiguous; d defaults
+    to its width): uint8 [m, padded_dim(d, torch.float8_e4m3fn)], pad columns code 0 (include/mmrag.h
+    mmrag_f8_encode_rows).  One launch on the current stream."""
+    _dev_check(src)
+    if (src.dim() != 2 or src.dtype not in (torch.float16, torch.float32) or src.stride(1) != 1
+            or (src.shape[0] > 1 and src.stride(0) < src.shape[1])):
+        raise MMRagNativeError("f8_encode_rows: src must be a 2-D float16 or float32 tensor with contiguous rows")
+    m, d = int(src.shape[0]), int(src.shape[1] if d is None else d)
+    if not 0 < d <= src.shape[1]:
+        raise MMRagNativeError(f"f8_encode_rows: d={d} outside 1..{src.shape[1]}")
+    ld = padded_dim(d, torch.float8_e4m3fn)
+    if out is None:
+        out = torch.empty((m, ld), dtype=torch.uint8, device=src.device)
+    elif (out.dim() != 2 or out.dtype != torch.uint8 or not out.is_contiguous() or out.shape[0] < m
+          or out.shape[1] < ld or out.device != src.device):
+        raise MMRagNativeError(f"f8_encode_rows: out must be a contiguous uint8 tensor of at least [{m}, {ld}] on "
+                               f"src's device")
+    src_ld = int(src.stride(0)) if m > 1 else int(src.shape[1])
+    with torch.cuda.device(src.device):
+        st = lib().mmrag_f8_encode_rows(src.data_ptr(), _TORCH2DT[src.dtype], m, d, src_ld, out.data_ptr(),
+                                        out.shape[1], _stream_ptr(src.device))
+    _check(st, "mmrag_f8_encode_rows")
+    return out[:m]
+
+
+def maxsim_topk_workspace_bytes(Q: int, n_items: int, k: int, dim: int = 0, max_tiles: int = 0,
+                                dtype: torch.dtype = torch.float16) -> int:
     """the public bound (any dim, a tile per question), or with `dim` what a call at that dim with at most `max_tiles`
-    question tiles (0: Q) needs"""
+    question tiles (0: Q) needs; `dtype`: torch.float16 (mmrag_maxsim_topk) or torch.float8_e4m3fn (the FP8 scan)"""
+    if dtype not in (torch.float16, torch.float8_e4m3fn):
+        raise ValueError(f"maxsim_topk_workspace_bytes: dtype must be float16 or float8_e4m3fn (got {dtype})")
+    L, f8 = lib(), dtype == torch.float8_e4m3fn
     if not dim:
-        return int(lib().mmrag_maxsim_topk_workspace_bytes(int(Q), int(n_items), int(k)))
-    return int(lib().mmrag_internal_maxsim_topk_workspace_bytes_ex(int(Q), int(n_items), int(k), int(dim), int(max_tiles)))
+        fn = L.mmrag_maxsim_topk_f8_workspace_bytes if f8 else L.mmrag_maxsim_topk_workspace_bytes
+        return int(fn(int(Q), int(n_items), int(k)))
+    fn = L.mmrag_internal_maxsim_topk_f8_workspace_bytes_ex if f8 else L.mmrag_internal_maxsim_topk_workspace_bytes_ex
+    return int(fn(int(Q), int(n_items), int(k), int(dim), int(max_tiles)))
 
 
 def late_question_tiles(q_start, q_len, q_rows: int) -> int:
@@ -1317,7 +1374,7 @@ def late_question_tiles(q_start, q_len, q_rows: int) -> int:
 def maxsim_topk(q_tok: torch.Tensor, q_start, q_len, tok: torch.Tensor, n_rows: int, item_off: torch.Tensor,
                 n_items: int, dim: int, k: int, alive_bits: Optional[torch.Tensor] = None,
                 workspace: Optional[torch.Tensor] = None, chunk_rows: int = 0, cap: int = 0, dbg: int = 0,
-                check_tables: bool = True):
+                check_tables: bool = True, _f8: bool = False):
     """Each question's exact MaxSim top-k over the items of a token plane (include/mmrag.h mmrag_maxsim_topk).
     `q_tok` [q_rows, ld] and `tok` [>= n_rows, ld] are contiguous device float16 tensors; question s is rows
     q_start[s] .. q_start[s] + q_len[s] (HOST integer sequences, checked here unless `check_tables` is false -- then a
@@ -1325,55 +1382,69 @@ def maxsim_topk(q_tok: torch.Tensor, q_start, q_len, tok: torch.Tensor, n_rows: 
     n_items + 1 ascending offsets into the first n_rows rows of `tok`; `alive_bits`: an optional device int32 bitmap
     over items.  Returns (scores [Q, k] float32 descending, items [Q, k] int64), (-inf, -1) padded.  No host
     synchronisation unless n_items exceeds the candidate slots of a question.  `chunk_rows`, `cap`, `dbg` (tests and
-    tools): the plane rows per chunk, fewer candidate slots, dbg & 1 = no bound passes."""
+    tools): the plane rows per chunk, fewer candidate slots, dbg & 1 = no bound passes.  (`_f8`: maxsim_topk_f8's
+    switch.)"""
+    who, row_dtype = ("maxsim_topk_f8", torch.uint8) if _f8 else ("maxsim_topk", torch.float16)
     _dev_check(q_tok, tok, item_off)
     for name, t in (("q_tok", q_tok), ("tok", tok)):
-        if t.dim() != 2 or not t.is_contiguous() or t.dtype != torch.float16:
-            raise MMRagNativeError(f"maxsim_topk: {name} must be a contiguous 2-D float16 tensor")
+        if t.dim() != 2 or not t.is_contiguous() or t.dtype != row_dtype:
+            raise MMRagNativeError(f"{who}: {name} must be a contiguous 2-D {_DT_NAME[row_dtype]} tensor")
     dev = q_tok.device
     n_rows, n_items, k = int(n_rows), int(n_items), int(k)
     if not 1 <= k <= MAX_K_DEEP:
-        raise ValueError(f"maxsim_topk: k={k} outside 1..{MAX_K_DEEP}")
+        raise ValueError(f"{who}: k={k} outside 1..{MAX_K_DEEP}")
     if tok.device != dev or item_off.device != dev or (alive_bits is not None and alive_bits.device != dev):
-        raise MMRagNativeError("maxsim_topk: q_tok, tok, item_off and alive_bits must be on one device")
+        raise MMRagNativeError(f"{who}: q_tok, tok, item_off and alive_bits must be on one device")
     if not 0 <= n_rows <= tok.shape[0]:
-        raise MMRagNativeError(f"maxsim_topk: n_rows={n_rows} outside the {tok.shape[0]} rows of tok")
+        raise MMRagNativeError(f"{who}: n_rows={n_rows} outside the {tok.shape[0]} rows of tok")
     if (item_off.dim() != 1 or item_off.dtype != torch.int32 or not item_off.is_contiguous() or n_items < 0
             or item_off.numel() < n_items + 1):
-        raise MMRagNativeError(f"maxsim_topk: item_off must be a contiguous int32 tensor of at least n_items + 1 = "
+        raise MMRagNativeError(f"{who}: item_off must be a contiguous int32 tensor of at least n_items + 1 = "
                                f"{n_items + 1} offsets")
     if alive_bits is not None and (alive_bits.dtype != torch.int32 or not alive_bits.is_contiguous()
                                    or alive_bits.numel() * 32 < n_items):
-        raise MMRagNativeError(f"maxsim_topk: alive_bits must be a contiguous int32 bitmap over {n_items} items")
+        raise MMRagNativeError(f"{who}: alive_bits must be a contiguous int32 bitmap over {n_items} items")
     tables = [torch.as_tensor(t, dtype=torch.int32).reshape(-1).cpu() for t in (q_start, q_len)]
     Q = tables[0].numel()
     if tables[1].numel() != Q or not 1 <= Q <= MAX_LATE_QUESTIONS:
-        raise MMRagNativeError(f"maxsim_topk: q_start and q_len must hold the same 1..{MAX_LATE_QUESTIONS} questions "
+        raise MMRagNativeError(f"{who}: q_start and q_len must hold the same 1..{MAX_LATE_QUESTIONS} questions "
                                f"(got {Q} and {tables[1].numel()})")
     if check_tables:
         for s, (a, n) in enumerate(zip(tables[0].tolist(), tables[1].tolist())):
             if not 1 <= n <= MAX_LATE_QUERY_TOKENS:
-                raise MMRagNativeError(f"maxsim_topk: question {s} has {n} tokens, outside 1..{MAX_LATE_QUERY_TOKENS}")
+                raise MMRagNativeError(f"{who}: question {s} has {n} tokens, outside 1..{MAX_LATE_QUERY_TOKENS}")
             if a < 0 or a + n > q_tok.shape[0]:
-                raise MMRagNativeError(f"maxsim_topk: question {s} (rows {a}..{a + n}) is outside the "
+                raise MMRagNativeError(f"{who}: question {s} (rows {a}..{a + n}) is outside the "
                                        f"{q_tok.shape[0]} rows given")
     packed = _pinned_to_device(torch.cat(tables), dev)
     # the host tables say how many question tiles there are: the grid and the packed tiles are sized by that, not by Q
     tiles = late_question_tiles(tables[0].tolist(), tables[1].tolist(), q_tok.shape[0])
-    need = maxsim_topk_workspace_bytes(Q, n_items, k, int(dim), tiles)
+    need = maxsim_topk_workspace_bytes(Q, n_items, k, int(dim), tiles, torch.float8_e4m3fn if _f8 else torch.float16)
     if need == 0:
-        raise MMRagNativeError(f"maxsim_topk: dim must be a multiple of 64, at most 1024 (dim={dim})")
+        raise MMRagNativeError(f"{who}: dim must be a multiple of 64, at most 1024 (dim={dim})")
     if workspace is None or _nbytes(workspace) < need:
         workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
     out_s, out_r = _topk_out(Q, k, dev)
     with torch.cuda.device(dev):
-        st = lib().mmrag_internal_maxsim_topk_ex(
+        fn = lib().mmrag_internal_maxsim_topk_f8_ex if _f8 else lib().mmrag_internal_maxsim_topk_ex
+        st = fn(
             q_tok.data_ptr(), q_tok.shape[0], q_tok.shape[1], packed.data_ptr(), packed[Q:].data_ptr(), Q,
             tok.data_ptr(), n_rows, tok.shape[1], item_off.data_ptr(), n_items, _ptr(alive_bits), int(dim), k,
             out_s.data_ptr(), out_r.data_ptr(), workspace.data_ptr(), _nbytes(workspace), _stream_ptr(dev),
             int(chunk_rows), int(cap), int(dbg), tiles)
-    _check(st, "mmrag_maxsim_topk")
+    _check(st, "mmrag_" + who)
     return out_s, out_r
+
+
+def maxsim_topk_f8(q_codes: torch.Tensor, q_start, q_len, codes: torch.Tensor, n_rows: int, item_off: torch.Tensor,
+                   n_items: int, dim: int, k: int, alive_bits: Optional[torch.Tensor] = None,
+                   workspace: Optional[torch.Tensor] = None, chunk_rows: int = 0, cap: int = 0, dbg: int = 0,
+                   check_tables: bool = True):
+    """maxsim_topk over a plane of E4M3 code rows and code rows of the questions (include/mmrag.h mmrag_maxsim_topk_f8):
+    contiguous uint8 tensors [rows, ld], ld = padded_dim(dim, torch.float8_e4m3fn) or more whole slabs.  Scores are
+    the quantised rows' own (decoded dot products times 2^-16); everything else is maxsim_topk's."""
+    return maxsim_topk(q_codes, q_start, q_len, codes, n_rows, item_off, n_items, dim, k, alive_bits, workspace,
+                       chunk_rows, cap, dbg, check_tables, _f8=True)
 
 
 def join_tile(T: int, at: int, slot_order: bool = False) -> Tuple[int, int]:

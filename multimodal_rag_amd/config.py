@@ -85,6 +85,9 @@ class Settings:
     MMRAG_LATE_STORE: bool = field(default_factory=lambda: os.getenv("MMRAG_LATE_STORE", "0") == "1")
     MMRAG_LATE_STORE_MAX_BYTES: int = field(
         default_factory=lambda: int(os.getenv("MMRAG_LATE_STORE_MAX_BYTES", "0")))
+    # the plane's element type: "float16" (default) or "float8_e4m3fn" -- E4M3 codes, half the bytes per token (384 per
+    # MiniLM token), scored by the FP8 MaxSim kernels; scores are then the quantised rows' own
+    MMRAG_LATE_STORE_DTYPE: str = field(default_factory=lambda: os.getenv("MMRAG_LATE_STORE_DTYPE", "float16"))
     # BM25 lexical leg (VectorIndex.lexical_query / hybrid_query, csrc/lexical.hip): term-frequency saturation k1 and
     # length normalisation b of the score, the same for every query
     MMRAG_BM25_K1: float = field(default_factory=lambda: float(os.getenv("MMRAG_BM25_K1", "1.2")))
@@ -153,6 +156,7 @@ class Settings:
         self.dedup_threshold()
         self.topics()
         self.rerank_method()
+        self.late_store_dtype()
 
     def dedup_threshold(self) -> float:
         """MMRAG_DEDUP_THRESHOLD checked: 0 (off) or a cosine in (0, 1]"""
@@ -166,6 +170,13 @@ class Settings:
         if self.MMRAG_RERANK_METHOD not in ("cross", "late"):
             raise ValueError(f"MMRAG_RERANK_METHOD must be 'cross' or 'late' (got {self.MMRAG_RERANK_METHOD!r})")
         return self.MMRAG_RERANK_METHOD
+
+    def late_store_dtype(self) -> str:
+        """MMRAG_LATE_STORE_DTYPE checked: 'float16' or 'float8_e4m3fn'"""
+        if self.MMRAG_LATE_STORE_DTYPE not in ("float16", "float8_e4m3fn"):
+            raise ValueError("MMRAG_LATE_STORE_DTYPE must be 'float16' or 'float8_e4m3fn' "
+                             f"(got {self.MMRAG_LATE_STORE_DTYPE!r})")
+        return self.MMRAG_LATE_STORE_DTYPE
 
     def topics(self) -> int:
         """MMRAG_TOPICS checked: 0 (automatic) or a cluster count in 1 .. 4096"""

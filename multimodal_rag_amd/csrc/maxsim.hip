@@ -16,6 +16,7 @@
 // Query rows i >= q_len are computed (they are zero rows) and dropped: never written, never summed.
 #include <math.h>
 
+#include "f8_codec.h"
 #include "pair_tile.h"
 
 namespace mmrag_impl {
@@ -40,6 +41,9 @@ __device__ inline void ms_better(float &v, int &i, float ov, int oi) {
     }
 }
 
+// DT: MMRAG_F16 (unit rows) or MMRAG_F8E4M3 (code rows of both sides: the accumulators hold 2^16 times the similarity,
+// maxima are compared there and scaled, exactly, where they leave for `best` and the outputs)
+template <int DT>
 __global__ __launch_bounds__(256, 2) void maxsim_kernel(const MaxSimParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     static_assert(PT == MMRAG_MAX_LATE_QUERY_TOKENS, "the query is one A tile");
@@ -106,8 +110,9 @@ __global__ __launch_bounds__(256, 2) void maxsim_kernel(const MaxSimParams p) {
         wait_vmcnt<0>();     // two stages: item `it` is the only one in flight
         __builtin_amdgcn_s_barrier();
         if (issued < total) issue();
-        slab_step<MMRAG_F16>(smem + (it % PT_NSTAGE) * PT_STAGE, c, acc);
+        slab_step<DT>(smem + (it % PT_NSTAGE) * PT_STAGE, c, acc);
         if (++ks == nk) {
+            pair_tile_settle<DT>();
             // ---- the passage tile is complete: acc[a][b][r] = <query row wm*64 + 16a + 4 g4 + r, passage col0 + 16b>
             ks = 0;
             const int col0 = ct * PT + wn * 64 + c16;
@@ -154,6 +159,7 @@ __global__ __launch_bounds__(256, 2) void maxsim_kernel(const MaxSimParams p) {
         float v = red_v[0][t];
         int arg = red_a[0][t];
         ms_better(v, arg, red_v[1][t], red_a[1][t]);
+        if constexpr (DT == MMRAG_F8E4M3) v *= PT_ACC_SCALE<DT>;
         best[t] = v;
         if (p.out_best_sim != nullptr) p.out_best_sim[(size_t)pair * PT + t] = v;
         if (p.out_best_idx != nullptr) p.out_best_idx[(size_t)pair * PT + t] = arg;
@@ -169,6 +175,62 @@ __global__ __launch_bounds__(256, 2) void maxsim_kernel(const MaxSimParams p) {
 
 }  // namespace mmrag_impl
 
+namespace mmrag_impl {
+
+// csrc/f8_codec.h's encoder over rows: dst[r, c] = code of src[r, c] for c < d, code 0 for d <= c < dst_ld
+template <typename T>
+__global__ __launch_bounds__(256) void f8_encode_rows_kernel(const T *__restrict__ src, int64_t src_ld,
+                                                             unsigned char *__restrict__ dst, int64_t dst_ld,
+                                                             int64_t m, int d) {
+    const int64_t per_row = dst_ld / 4, total = m * per_row;      // four codes (one 32-bit store) per thread and step
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / per_row;
+        const int c0 = (int)(i - r * per_row) * 4;
+        unsigned w = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (c0 + e < d) w |= (unsigned)f8_encode((float)src[r * src_ld + c0 + e]) << (8 * e);
+        *(unsigned *)(dst + r * dst_ld + c0) = w;
+    }
+}
+
+template <int DT>
+static int maxsim_scores_impl(const char *who, const void *q_tok, int64_t q_rows, int64_t q_ld, const void *d_tok,
+                              int64_t d_rows, int64_t d_ld, int dim, const int32_t *q_start, const int32_t *q_len,
+                              int n_q, const int32_t *d_start, const int32_t *d_len, int n_d, const int32_t *pair_q,
+                              const int32_t *pair_d, int P, float *out_sum, float *out_best_sim,
+                              int32_t *out_best_idx, void *stream) {
+    MMRAG_CHECK_ARG(q_tok && d_tok && q_start && q_len && d_start && d_len && pair_q && pair_d && out_sum,
+                    "%s: null pointer", who);
+    MMRAG_CHECK_ARG(dim > 0 && dim % 64 == 0 && dim <= 1024,
+                    "%s: dim must be a multiple of 64, at most 1024 (dim=%d)", who, dim);
+    for (const int64_t ld : {q_ld, d_ld}) {
+        const int st = DT == MMRAG_F8E4M3 ? check_code_rows(who, ld, dim)
+                                          : check_stored_rows(who, "scored", "score", ld, DT, dim);
+        if (st != MMRAG_OK) return st;
+    }
+    MMRAG_CHECK_ARG(P >= 1 && P <= 65535, "%s: P=%d outside 1..65535", who, P);
+    MMRAG_CHECK_ARG(n_q >= 1 && n_d >= 1 && q_rows >= 1 && d_rows >= 1 && q_rows < (1LL << 31) && d_rows < (1LL << 31),
+                    "%s: need at least one sequence and one row on each side, fewer than 2^31 rows "
+                    "(n_q=%d n_d=%d q_rows=%lld d_rows=%lld)", who, n_q, n_d, (long long)q_rows, (long long)d_rows);
+    MMRAG_CHECK_ARG(((uintptr_t)q_tok % 16) == 0 && ((uintptr_t)d_tok % 16) == 0,
+                    "%s: token rows must be 16-byte aligned", who);
+    MaxSimParams p;
+    p.q_tok = (const char *)q_tok, p.d_tok = (const char *)d_tok;
+    p.q_rb = stored_row_bytes(q_ld, DT), p.d_rb = stored_row_bytes(d_ld, DT);
+    p.q_rows = q_rows, p.d_rows = d_rows;
+    p.nk = stored_k_slabs(dim, DT);
+    p.q_start = q_start, p.q_len = q_len, p.d_start = d_start, p.d_len = d_len;
+    p.n_q = n_q, p.n_d = n_d;
+    p.pair_q = pair_q, p.pair_d = pair_d;
+    p.out_sum = out_sum, p.out_best_sim = out_best_sim, p.out_best_idx = out_best_idx;
+    hipLaunchKernelGGL(maxsim_kernel<DT>, dim3((unsigned)P), dim3(256), 0, (hipStream_t)stream, p);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    return MMRAG_OK;
+}
+
+}  // namespace mmrag_impl
+
 extern "C" {
 
 int mmrag_maxsim_scores(const void *q_tok, int64_t q_rows, int64_t q_ld, const void *d_tok, int64_t d_rows,
@@ -176,31 +238,44 @@ int mmrag_maxsim_scores(const void *q_tok, int64_t q_rows, int64_t q_ld, const v
                         const int32_t *d_start, const int32_t *d_len, int n_d, const int32_t *pair_q,
                         const int32_t *pair_d, int P, float *out_sum, float *out_best_sim, int32_t *out_best_idx,
                         void *stream) {
+    return mmrag_impl::maxsim_scores_impl<MMRAG_F16>("maxsim_scores", q_tok, q_rows, q_ld, d_tok, d_rows, d_ld, dim,
+                                                     q_start, q_len, n_q, d_start, d_len, n_d, pair_q, pair_d, P,
+                                                     out_sum, out_best_sim, out_best_idx, stream);
+}
+
+int mmrag_maxsim_scores_f8(const void *q_codes, int64_t q_rows, int64_t q_ld, const void *d_codes, int64_t d_rows,
+                           int64_t d_ld, int dim, const int32_t *q_start, const int32_t *q_len, int n_q,
+                           const int32_t *d_start, const int32_t *d_len, int n_d, const int32_t *pair_q,
+                           const int32_t *pair_d, int P, float *out_sum, float *out_best_sim, int32_t *out_best_idx,
+                           void *stream) {
+    return mmrag_impl::maxsim_scores_impl<MMRAG_F8E4M3>("maxsim_scores_f8", q_codes, q_rows, q_ld, d_codes, d_rows,
+                                                        d_ld, dim, q_start, q_len, n_q, d_start, d_len, n_d, pair_q,
+                                                        pair_d, P, out_sum, out_best_sim, out_best_idx, stream);
+}
+
+int mmrag_f8_encode_rows(const void *src, int src_dtype, int64_t m, int d, int64_t src_ld, void *dst, int64_t dst_ld,
+                         void *stream) {
     using namespace mmrag_impl;
-    MMRAG_CHECK_ARG(q_tok && d_tok && q_start && q_len && d_start && d_len && pair_q && pair_d && out_sum,
-                    "maxsim_scores: null pointer");
-    MMRAG_CHECK_ARG(dim > 0 && dim % 64 == 0 && dim <= 1024,
-                    "maxsim_scores: dim must be a multiple of 64, at most 1024 (dim=%d)", dim);
-    int st = check_stored_rows("maxsim_scores", "scored", "score", q_ld, MMRAG_F16, dim);
-    if (st != MMRAG_OK) return st;
-    st = check_stored_rows("maxsim_scores", "scored", "score", d_ld, MMRAG_F16, dim);
-    if (st != MMRAG_OK) return st;
-    MMRAG_CHECK_ARG(P >= 1 && P <= 65535, "maxsim_scores: P=%d outside 1..65535", P);
-    MMRAG_CHECK_ARG(n_q >= 1 && n_d >= 1 && q_rows >= 1 && d_rows >= 1 && q_rows < (1LL << 31) && d_rows < (1LL << 31),
-                    "maxsim_scores: need at least one sequence and one row on each side, fewer than 2^31 rows "
-                    "(n_q=%d n_d=%d q_rows=%lld d_rows=%lld)", n_q, n_d, (long long)q_rows, (long long)d_rows);
-    MMRAG_CHECK_ARG(((uintptr_t)q_tok % 16) == 0 && ((uintptr_t)d_tok % 16) == 0,
-                    "maxsim_scores: token rows must be 16-byte aligned");
-    MaxSimParams p;
-    p.q_tok = (const char *)q_tok, p.d_tok = (const char *)d_tok;
-    p.q_rb = stored_row_bytes(q_ld, MMRAG_F16), p.d_rb = stored_row_bytes(d_ld, MMRAG_F16);
-    p.q_rows = q_rows, p.d_rows = d_rows;
-    p.nk = stored_k_slabs(dim, MMRAG_F16);
-    p.q_start = q_start, p.q_len = q_len, p.d_start = d_start, p.d_len = d_len;
-    p.n_q = n_q, p.n_d = n_d;
-    p.pair_q = pair_q, p.pair_d = pair_d;
-    p.out_sum = out_sum, p.out_best_sim = out_best_sim, p.out_best_idx = out_best_idx;
-    hipLaunchKernelGGL(maxsim_kernel, dim3((unsigned)P), dim3(256), 0, (hipStream_t)stream, p);
+    MMRAG_CHECK_ARG(src && dst, "f8_encode_rows: null pointer");
+    MMRAG_CHECK_ARG(src_dtype == MMRAG_F16 || src_dtype == MMRAG_F32,
+                    "f8_encode_rows: the source must be MMRAG_F16 or MMRAG_F32 (src_dtype=%d)", src_dtype);
+    MMRAG_CHECK_ARG(m >= 0 && d > 0 && src_ld >= d && dst_ld >= d,
+                    "f8_encode_rows: need m >= 0 and 0 < d <= src_ld, dst_ld (m=%lld d=%d src_ld=%lld dst_ld=%lld)",
+                    (long long)m, d, (long long)src_ld, (long long)dst_ld);
+    if (int st = check_code_rows("f8_encode_rows", dst_ld, d)) return st;
+    MMRAG_CHECK_ARG(((uintptr_t)dst % 16) == 0, "f8_encode_rows: dst must be 16-byte aligned");
+    if (m == 0) return MMRAG_OK;
+    const int64_t total = m * (dst_ld / 4);
+    int64_t grid = (total + 255) / 256;
+    const int64_t most = (int64_t)mmrag::num_cus() * 8;
+    grid = grid > most ? most : grid;
+    hipStream_t s = (hipStream_t)stream;
+    if (src_dtype == MMRAG_F16)
+        hipLaunchKernelGGL(f8_encode_rows_kernel<_Float16>, dim3((unsigned)grid), dim3(256), 0, s,
+                           (const _Float16 *)src, src_ld, (unsigned char *)dst, dst_ld, m, d);
+    else
+        hipLaunchKernelGGL(f8_encode_rows_kernel<float>, dim3((unsigned)grid), dim3(256), 0, s, (const float *)src,
+                           src_ld, (unsigned char *)dst, dst_ld, m, d);
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
 }

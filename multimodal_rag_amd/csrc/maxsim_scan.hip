@@ -146,6 +146,9 @@ __device__ inline int ms_lower_bound(const int *off, int n, long long v) {
     return lo;
 }
 
+// DT: MMRAG_F16, or MMRAG_F8E4M3 (code rows on both sides: maxima are taken in the accumulator domain and scaled by
+// 2^-16, exactly, before the ascending sum, so sums and tau are similarities as in the fp16 instantiation)
+template <int DT>
 __global__ __launch_bounds__(256, 2) void maxsim_scan_kernel(const MsScanParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     static_assert(PT == MMRAG_MAX_LATE_QUERY_TOKENS, "a question fits one A tile");
@@ -256,8 +259,9 @@ __global__ __launch_bounds__(256, 2) void maxsim_scan_kernel(const MsScanParams 
         wait_vmcnt<0>();     // two stages: item `it` is the only one in flight
         __builtin_amdgcn_s_barrier();
         if (issued < total) issue();
-        slab_step<MMRAG_F16>(smem + (it % PT_NSTAGE) * PT_STAGE, c, acc);
+        slab_step<DT>(smem + (it % PT_NSTAGE) * PT_STAGE, c, acc);
         if (++ks < nk) continue;
+        pair_tile_settle<DT>();
         // ---- the B tile is complete: acc[a][b][r] = <question row wm*64 + 16a + 4 g4 + r, plane row r0 + wn*64 + 16b + c16>
         ks = 0;
         // columns are counted from the tile's first row r0 (r0 + 128 may not fit an int): the tile holds n_in rows
@@ -312,7 +316,8 @@ __global__ __launch_bounds__(256, 2) void maxsim_scan_kernel(const MsScanParams 
                     float sum = 0.0f;
                     for (int i = 0; i < my_len; ++i) {      // ascending i: the sum's bits are defined
                         const float v0 = red[0][tid + i], v1 = red[1][tid + i];
-                        sum += v1 > v0 ? v1 : v0;
+                        if constexpr (DT == MMRAG_F8E4M3) sum += (v1 > v0 ? v1 : v0) * PT_ACC_SCALE<DT>;
+                        else sum += v1 > v0 ? v1 : v0;
                     }
                     if (sum >= my_tau) {
                         // the counter keeps the true count; slots at or past cap are not written
@@ -371,8 +376,9 @@ struct MsWs {
 };
 
 // [candidate_select's blocks | n_tiles | q_tile [Q] | row_src [Q, 128] | row_q [Q, 128] | packed A tiles]: `tiles` packed
-// tiles of 128 rows of 2 dim bytes.  The public size is that of tiles = Q at dim 1024, an upper bound of every call's
-inline MsWs ms_ws_layout(int Q, long long cap, long long n_items, int tiles, int dim) {
+// tiles of 128 rows of `pack_rb` bytes (2 dim for fp16 rows, dim for codes).  The public sizes are those of tiles = Q
+// at dim 1024, an upper bound of every call's
+inline MsWs ms_ws_layout(int Q, long long cap, long long n_items, int tiles, int pack_rb) {
     MsWs w;
     w.cand = candidate_ws_layout(Q, cap, n_items, true);
     w.off_ntiles = w.cand.total;
@@ -380,57 +386,39 @@ inline MsWs ms_ws_layout(int Q, long long cap, long long n_items, int tiles, int
     w.off_rowsrc = align_up(w.off_qtile + (size_t)Q * sizeof(int), 256);
     w.off_rowq = w.off_rowsrc + (size_t)Q * PT * sizeof(int);
     w.off_pack = align_up(w.off_rowq + (size_t)Q * PT * sizeof(int), 1024);
-    w.total = w.off_pack + (size_t)tiles * PT * 2 * (size_t)dim;
+    w.total = w.off_pack + (size_t)tiles * PT * (size_t)pack_rb;
     return w;
 }
 
-}  // namespace
+// bytes of a packed question row: the slabs that hold the dim columns (fp16: 2 dim, dim % 64 == 0; codes: the padded dim)
+inline int ms_pack_rb(int dim, int dtype) { return stored_k_slabs(dim, dtype) * SLAB; }
 
-}  // namespace mmrag_impl
-using namespace mmrag_impl;
-
-extern "C" {
-
-size_t mmrag_maxsim_topk_workspace_bytes(int Q, int64_t n_items, int k) {
-    if (Q < 1 || Q > MMRAG_MAX_LATE_QUESTIONS || n_items < 0 || n_items >= (1LL << 31) || k < 1 || k > MMRAG_MAX_K_DEEP)
-        return 0;
-    return ms_ws_layout(Q, candidate_capacity(k), n_items, Q, 1024).total + 1024;   // + the slack that aligns the tiles
-}
-
-// what a call with this dim and at most max_tiles question tiles (0: Q) needs: the wrapper, which holds the host tables
-size_t mmrag_internal_maxsim_topk_workspace_bytes_ex(int Q, int64_t n_items, int k, int dim, int max_tiles) {
-    if (mmrag_maxsim_topk_workspace_bytes(Q, n_items, k) == 0 || dim <= 0 || dim % 64 != 0 || dim > 1024) return 0;
-    const int tiles = max_tiles > 0 && max_tiles < Q ? max_tiles : Q;
-    return ms_ws_layout(Q, candidate_capacity(k), n_items, tiles, dim).total + 1024;
-}
-
-// mmrag_maxsim_topk with a chunk size (chunk_rows > 0), a smaller candidate capacity (cap_override > 0), debug
-// switches (MS_DBG_*) and an upper bound of the question tiles (max_tiles > 0; a caller that holds the host tables
-// knows it: the grid and the packed tiles are then sized by it instead of by Q, and a question the bound leaves no tile
-// for gets padding only): the tests that pin chunk independence, the overflow re-run and the unbounded scan, and the bench.
-// Exported for them, deliberately absent from include/mmrag.h.
-int mmrag_internal_maxsim_topk_ex(const void *q_tok, int64_t q_rows, int64_t q_ld, const int32_t *q_start,
-                                  const int32_t *q_len, int Q, const void *tok, int64_t T, int64_t ld,
-                                  const int32_t *item_off, int64_t n_items, const uint32_t *alive_bits, int dim, int k,
-                                  float *out_scores, int64_t *out_items, void *workspace, size_t workspace_bytes,
-                                  void *stream, int chunk_rows, int64_t cap_override, unsigned dbg, int max_tiles) {
-    MMRAG_CHECK_ARG(q_tok && q_start && q_len && item_off, "maxsim_topk: null pointer");
-    MMRAG_CHECK_ARG(out_scores && out_items, "maxsim_topk: null output");
+// mmrag_maxsim_topk (DT = MMRAG_F16) and mmrag_maxsim_topk_f8 (MMRAG_F8E4M3) behind their _ex entries
+template <int DT>
+int maxsim_topk_impl(const char *who, const void *q_tok, int64_t q_rows, int64_t q_ld, const int32_t *q_start,
+                     const int32_t *q_len, int Q, const void *tok, int64_t T, int64_t ld, const int32_t *item_off,
+                     int64_t n_items, const uint32_t *alive_bits, int dim, int k, float *out_scores,
+                     int64_t *out_items, void *workspace, size_t workspace_bytes, void *stream, int chunk_rows,
+                     int64_t cap_override, unsigned dbg, int max_tiles) {
+    MMRAG_CHECK_ARG(q_tok && q_start && q_len && item_off, "%s: null pointer", who);
+    MMRAG_CHECK_ARG(out_scores && out_items, "%s: null output", who);
     MMRAG_CHECK_ARG(dim > 0 && dim % 64 == 0 && dim <= 1024,
-                    "maxsim_topk: dim must be a multiple of 64, at most 1024 (dim=%d)", dim);
-    if (int st = check_stored_rows("maxsim_topk", "scanned", "scan", q_ld, MMRAG_F16, dim)) return st;
-    if (int st = check_stored_rows("maxsim_topk", "scanned", "scan", ld, MMRAG_F16, dim)) return st;
-    MMRAG_CHECK_ARG(Q >= 1 && Q <= MMRAG_MAX_LATE_QUESTIONS, "maxsim_topk: Q=%d outside 1..%d", Q,
+                    "%s: dim must be a multiple of 64, at most 1024 (dim=%d)", who, dim);
+    for (const int64_t w : {q_ld, ld})
+        if (int st = DT == MMRAG_F8E4M3 ? check_code_rows(who, w, dim)
+                                        : check_stored_rows(who, "scanned", "scan", w, DT, dim))
+            return st;
+    MMRAG_CHECK_ARG(Q >= 1 && Q <= MMRAG_MAX_LATE_QUESTIONS, "%s: Q=%d outside 1..%d", who, Q,
                     MMRAG_MAX_LATE_QUESTIONS);
     MMRAG_CHECK_ARG(n_items >= 0 && n_items < (1LL << 31) && T >= 0 && T < (1LL << 31) && q_rows >= 1 &&
                         q_rows < (1LL << 31),
-                    "maxsim_topk: need 0 <= n_items < 2^31, 0 <= T < 2^31 and 1 <= q_rows < 2^31 (n_items=%lld T=%lld "
-                    "q_rows=%lld)", (long long)n_items, (long long)T, (long long)q_rows);
-    MMRAG_CHECK_ARG(tok || T == 0, "maxsim_topk: null token plane");
-    MMRAG_CHECK_ARG(k >= 1 && k <= MMRAG_MAX_K_DEEP, "maxsim_topk: k=%d outside 1..%d", k, MMRAG_MAX_K_DEEP);
+                    "%s: need 0 <= n_items < 2^31, 0 <= T < 2^31 and 1 <= q_rows < 2^31 (n_items=%lld T=%lld "
+                    "q_rows=%lld)", who, (long long)n_items, (long long)T, (long long)q_rows);
+    MMRAG_CHECK_ARG(tok || T == 0, "%s: null token plane", who);
+    MMRAG_CHECK_ARG(k >= 1 && k <= MMRAG_MAX_K_DEEP, "%s: k=%d outside 1..%d", who, k, MMRAG_MAX_K_DEEP);
     MMRAG_CHECK_ARG(((uintptr_t)q_tok % 16) == 0 && ((uintptr_t)tok % 16) == 0,
-                    "maxsim_topk: token rows must be 16-byte aligned");
-    MMRAG_CHECK_ARG(chunk_rows >= 0 && max_tiles >= 0, "maxsim_topk: chunk_rows=%d or max_tiles=%d is negative",
+                    "%s: token rows must be 16-byte aligned", who);
+    MMRAG_CHECK_ARG(chunk_rows >= 0 && max_tiles >= 0, "%s: chunk_rows=%d or max_tiles=%d is negative", who,
                     chunk_rows, max_tiles);
     const int tiles = max_tiles > 0 && max_tiles < Q ? max_tiles : Q;
     hipStream_t s = (hipStream_t)stream;
@@ -439,14 +427,14 @@ int mmrag_internal_maxsim_topk_ex(const void *q_tok, int64_t q_rows, int64_t q_l
     const int R = chunk_rows > 0 ? chunk_rows : MS_CHUNK_ROWS;
     const long long n_chunks = (T + R - 1) / R;
     const MsPlan pl = make_ms_plan(n_items, n_chunks, k, cap_override, dbg);
-    const MsWs wl = ms_ws_layout(Q, pl.cap, n_items, tiles, dim);
+    const MsWs wl = ms_ws_layout(Q, pl.cap, n_items, tiles, ms_pack_rb(dim, DT));
     const size_t need = wl.total + 1024;
     if (!workspace || workspace_bytes < need) {
-        set_error("maxsim_topk: workspace %zu bytes < required %zu", workspace_bytes, need);
+        set_error("%s: workspace %zu bytes < required %zu", who, workspace_bytes, need);
         return MMRAG_EWORKSPACE;
     }
     if (((uintptr_t)workspace % 16) != 0) {
-        set_error("maxsim_topk: workspace must be 16-byte aligned");
+        set_error("%s: workspace must be 16-byte aligned", who);
         return MMRAG_EWORKSPACE;
     }
 
@@ -465,19 +453,19 @@ int mmrag_internal_maxsim_topk_ex(const void *q_tok, int64_t q_rows, int64_t q_l
     MMRAG_CHECK_HIP(hipMemsetAsync(pp.row_src, 0xff, 2 * (size_t)Q * PT * sizeof(int), s));
     hipLaunchKernelGGL(maxsim_plan_kernel, dim3(1), dim3(MS_PLAN_THREADS), 0, s, pp);
     MMRAG_CHECK_HIP(hipGetLastError());
-    const unsigned q_rb = stored_row_bytes(q_ld, MMRAG_F16);
-    const unsigned pack_rb = (unsigned)dim * 2;      // dim % 64 == 0: whole slabs
+    const unsigned q_rb = stored_row_bytes(q_ld, DT);
+    const unsigned pack_rb = ms_pack_rb(dim, DT);
     hipLaunchKernelGGL(maxsim_pack_kernel, dim3((unsigned)tiles), dim3(256), 0, s, (const char *)q_tok, q_rb,
                        (const int *)pp.n_tiles, (const int *)pp.row_src, qpack, pack_rb);
     MMRAG_CHECK_HIP(hipGetLastError());
 
     MsScanParams p;
     p.tok = (const char *)tok;
-    p.rb = stored_row_bytes(ld, MMRAG_F16);
+    p.rb = stored_row_bytes(ld, DT);
     p.T = T;
     p.qpack = qpack;
     p.q_rb = pack_rb;
-    p.nk = stored_k_slabs(dim, MMRAG_F16);
+    p.nk = stored_k_slabs(dim, DT);
     p.item_off = item_off;
     p.n_items = (int)n_items;
     p.alive = alive_bits;
@@ -501,7 +489,7 @@ int mmrag_internal_maxsim_topk_ex(const void *q_tok, int64_t q_rows, int64_t q_l
         pc.walk = walk;
         pc.cand_s = cand_s, pc.cand_r = cand_r, pc.cnt = counts;
         pc.cap = (unsigned)slots;
-        hipLaunchKernelGGL(maxsim_scan_kernel, dim3((unsigned)walk, only_q >= 0 ? 1u : (unsigned)tiles), dim3(256), 0, s, pc);
+        hipLaunchKernelGGL(maxsim_scan_kernel<DT>, dim3((unsigned)walk, only_q >= 0 ? 1u : (unsigned)tiles), dim3(256), 0, s, pc);
         MMRAG_CHECK_HIP(hipGetLastError());
         return MMRAG_OK;
     };
@@ -519,13 +507,80 @@ int mmrag_internal_maxsim_topk_ex(const void *q_tok, int64_t q_rows, int64_t q_l
     }
     // 3. main pass over every chunk, select, and each question with more survivors than slots alone, same tau_q
     return candidate_select(
-        "maxsim_topk", Q, n_items, pl.cap, k, 0, out_scores, (long long *)out_items, ws, wl.cand, s,
+        who, Q, n_items, pl.cap, k, 0, out_scores, (long long *)out_items, ws, wl.cand, s,
         [&](float *cand_s, int *cand_r, unsigned *counts, long long slots) {
             return produce(-1, n_chunks, cand_s, cand_r, counts, slots);
         },
         [&](int qi, float *cand_s, int *cand_r, unsigned *counts, long long slots) {
             return produce(qi, n_chunks, cand_s, cand_r, counts, slots);
         });
+}
+
+}  // namespace
+}  // namespace mmrag_impl
+
+using namespace mmrag_impl;
+
+extern "C" {
+
+size_t mmrag_maxsim_topk_workspace_bytes(int Q, int64_t n_items, int k) {
+    if (Q < 1 || Q > MMRAG_MAX_LATE_QUESTIONS || n_items < 0 || n_items >= (1LL << 31) || k < 1 || k > MMRAG_MAX_K_DEEP)
+        return 0;
+    return ms_ws_layout(Q, candidate_capacity(k), n_items, Q, 2 * 1024).total + 1024;   // + the slack that aligns the tiles
+}
+
+size_t mmrag_maxsim_topk_f8_workspace_bytes(int Q, int64_t n_items, int k) {
+    if (mmrag_maxsim_topk_workspace_bytes(Q, n_items, k) == 0) return 0;
+    return ms_ws_layout(Q, candidate_capacity(k), n_items, Q, 1024).total + 1024;
+}
+
+// what a call with this dim and at most max_tiles question tiles (0: Q) needs: the wrapper, which holds the host tables
+size_t mmrag_internal_maxsim_topk_workspace_bytes_ex(int Q, int64_t n_items, int k, int dim, int max_tiles) {
+    if (mmrag_maxsim_topk_workspace_bytes(Q, n_items, k) == 0 || dim <= 0 || dim % 64 != 0 || dim > 1024) return 0;
+    const int tiles = max_tiles > 0 && max_tiles < Q ? max_tiles : Q;
+    return ms_ws_layout(Q, candidate_capacity(k), n_items, tiles, ms_pack_rb(dim, MMRAG_F16)).total + 1024;
+}
+
+size_t mmrag_internal_maxsim_topk_f8_workspace_bytes_ex(int Q, int64_t n_items, int k, int dim, int max_tiles) {
+    if (mmrag_maxsim_topk_workspace_bytes(Q, n_items, k) == 0 || dim <= 0 || dim % 64 != 0 || dim > 1024) return 0;
+    const int tiles = max_tiles > 0 && max_tiles < Q ? max_tiles : Q;
+    return ms_ws_layout(Q, candidate_capacity(k), n_items, tiles, ms_pack_rb(dim, MMRAG_F8E4M3)).total + 1024;
+}
+
+// mmrag_maxsim_topk with a chunk size (chunk_rows > 0), a smaller candidate capacity (cap_override > 0), debug
+// switches (MS_DBG_*) and an upper bound of the question tiles (max_tiles > 0; a caller that holds the host tables
+// knows it: the grid and the packed tiles are then sized by it instead of by Q, and a question the bound leaves no tile
+// for gets padding only): the tests that pin chunk independence, the overflow re-run and the unbounded scan, and the bench.
+// Exported for them, deliberately absent from include/mmrag.h.
+int mmrag_internal_maxsim_topk_ex(const void *q_tok, int64_t q_rows, int64_t q_ld, const int32_t *q_start,
+                                  const int32_t *q_len, int Q, const void *tok, int64_t T, int64_t ld,
+                                  const int32_t *item_off, int64_t n_items, const uint32_t *alive_bits, int dim, int k,
+                                  float *out_scores, int64_t *out_items, void *workspace, size_t workspace_bytes,
+                                  void *stream, int chunk_rows, int64_t cap_override, unsigned dbg, int max_tiles) {
+    return maxsim_topk_impl<MMRAG_F16>("maxsim_topk", q_tok, q_rows, q_ld, q_start, q_len, Q, tok, T, ld, item_off,
+                                       n_items, alive_bits, dim, k, out_scores, out_items, workspace, workspace_bytes,
+                                       stream, chunk_rows, cap_override, dbg, max_tiles);
+}
+
+// the same for code rows
+int mmrag_internal_maxsim_topk_f8_ex(const void *q_codes, int64_t q_rows, int64_t q_ld, const int32_t *q_start,
+                                     const int32_t *q_len, int Q, const void *codes, int64_t T, int64_t ld,
+                                     const int32_t *item_off, int64_t n_items, const uint32_t *alive_bits, int dim,
+                                     int k, float *out_scores, int64_t *out_items, void *workspace,
+                                     size_t workspace_bytes, void *stream, int chunk_rows, int64_t cap_override,
+                                     unsigned dbg, int max_tiles) {
+    return maxsim_topk_impl<MMRAG_F8E4M3>("maxsim_topk_f8", q_codes, q_rows, q_ld, q_start, q_len, Q, codes, T, ld,
+                                          item_off, n_items, alive_bits, dim, k, out_scores, out_items, workspace,
+                                          workspace_bytes, stream, chunk_rows, cap_override, dbg, max_tiles);
+}
+
+int mmrag_maxsim_topk_f8(const void *q_codes, int64_t q_rows, int64_t q_ld, const int32_t *q_start,
+                         const int32_t *q_len, int Q, const void *codes, int64_t T, int64_t ld,
+                         const int32_t *item_off, int64_t n_items, const uint32_t *alive_bits, int dim, int k,
+                         float *out_scores, int64_t *out_items, void *workspace, size_t workspace_bytes, void *stream) {
+    return mmrag_internal_maxsim_topk_f8_ex(q_codes, q_rows, q_ld, q_start, q_len, Q, codes, T, ld, item_off, n_items,
+                                            alive_bits, dim, k, out_scores, out_items, workspace, workspace_bytes,
+                                            stream, 0, 0, 0u, 0);
 }
 
 int mmrag_maxsim_topk(const void *q_tok, int64_t q_rows, int64_t q_ld, const int32_t *q_start, const int32_t *q_len,

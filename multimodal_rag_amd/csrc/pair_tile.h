@@ -68,11 +68,14 @@ __device__ __forceinline__ void pair_tile_clear(f32x4_t (&acc)[4][4]) {
 }
 
 // acc[a][b][r] += <A row wm*64 + 16a + 4 g4 + r, B row wn*64 + 16b + c16> over the K-slab in `stage`.
-// A 128-byte slab is two k-steps; lane (c16, g4) reads chunk 4 s + g4 of row c16 of every 16-row block.  One fixed K
-// order for every pair of rows: the score bits depend on the two rows and d alone, not on the tile, the grid or the
+// A 128-byte slab is two k-steps (one for E4M3 codes); lane (c16, g4) reads chunk 4 s + g4 of row c16 of every 16-row
+// block.  One fixed K order for every pair of rows: the score bits depend on the two rows and d alone, not on the tile, the grid or the
 // kernel.
+__device__ __forceinline__ void slab_step_codes(const char *stage, const PairTileCtx &c, f32x4_t (&acc)[4][4]);
 template <int DT>
 __device__ __forceinline__ void slab_step(const char *stage, const PairTileCtx &c, f32x4_t (&acc)[4][4]) {
+    if constexpr (DT == MMRAG_F8E4M3) slab_step_codes(stage, c, acc);
+    else
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         const int off = ((4 * s + c.g4) ^ c.sw) * 16;
@@ -106,6 +109,54 @@ __device__ __forceinline__ void slab_step(const char *stage, const PairTileCtx &
     }
 }
 
+// The same for rows of E4M3 codes: a 128-byte slab is 128 K-elements of a row, ONE block-scaled
+// v_mfma_scale_f32_16x16x128_f8f6f4 per (a, b) block pair (format 0 = E4M3 on both sides, every scale byte 127 = 1.0).
+// A lane supplies 32 bytes of its row per block: chunks g4 and 4 + g4, i.e. the two reads of slab_step's 16-bit branch
+// (t for s), so the LDS reads and their banks are that branch's, conflict-free under the same swizzle.  (Chunks 2 g4,
+// 2 g4 + 1 would put lanes g4 = 0 and g4 = 1 of one ds_read_b128 lane group on the same bank slots.)  A and B use the
+// same lane-to-k map, so which 32 of the 128 k a lane holds is the hardware's business.  The C/D layout is the 16 x 16
+// one of the other forms: acc holds 2^16 times the similarity.
+__device__ __forceinline__ void slab_step_codes(const char *stage, const PairTileCtx &c, f32x4_t (&acc)[4][4]) {
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    typedef int i32x8 __attribute__((ext_vector_type(8)));
+    const int o0 = (c.g4 ^ c.sw) * 16, o1 = ((4 + c.g4) ^ c.sw) * 16;
+    i32x8 fa[4], fb[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const i32x4 lo = *(const i32x4 *)(stage + c.a_base + a * (16 * SLAB) + o0);
+        const i32x4 hi = *(const i32x4 *)(stage + c.a_base + a * (16 * SLAB) + o1);
+        fa[a] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const i32x4 lo = *(const i32x4 *)(stage + c.b_base + b * (16 * SLAB) + o0);
+        const i32x4 hi = *(const i32x4 *)(stage + c.b_base + b * (16 * SLAB) + o1);
+        fb[b] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+            acc[a][b] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fa[a], fb[b], acc[a][b], 0, 0, 0,
+                                                                         0x7f7f7f7f, 0, 0x7f7f7f7f);
+}
+
+// Between a tile's last slab_step and the first read of its accumulators.  For E4M3 codes: slab_ring_body.inc's
+// stop-gap for the suspected wait-state shortfall after a block-scaled MFMA (the account is there), once per B tile;
+// nothing for the other types.
+template <int DT>
+__device__ __forceinline__ void pair_tile_settle() {
+    if constexpr (DT == MMRAG_F8E4M3) {
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_sleep(1);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// what an accumulator of DT operands is worth: E4M3 codes hold x * 256 on both sides
+template <int DT>
+constexpr float PT_ACC_SCALE = DT == MMRAG_F8E4M3 ? 0x1p-16f : 1.0f;
+
 // ---- host side ---------------------------------------------------------------------------------------------------
 inline unsigned stored_row_bytes(int64_t ld, int dtype) { return (unsigned)(ld * mmrag::esize(dtype)); }
 // K-slabs that hold the d logical columns
@@ -128,6 +179,16 @@ inline int check_stored_rows(const char *who, const char *done, const char *verb
     MMRAG_CHECK_ARG(ld * mmrag::esize(dtype) % SLAB == 0 && ld * mmrag::esize(dtype) <= (1LL << 24),
                     "%s: ld must cover whole 128-byte slabs (mmrag_padded_dim), rows of at most 16 MiB (ld=%lld)", who,
                     (long long)ld);
+    return MMRAG_OK;
+}
+
+// Rows of E4M3 codes that slab_step<MMRAG_F8E4M3> reads (the FP8 MaxSim entries alone): 0 < d <= ld, ld bytes of
+// whole 128-byte slabs (mmrag_padded_dim(d, MMRAG_F8E4M3) or larger), rows of at most 16 MiB.
+inline int check_code_rows(const char *who, int64_t ld, int d) {
+    MMRAG_CHECK_ARG(d > 0 && ld >= d, "%s: need 0 < d <= ld (d=%d ld=%lld)", who, d, (long long)ld);
+    MMRAG_CHECK_ARG(ld % SLAB == 0 && ld <= (1LL << 24),
+                    "%s: ld must cover whole 128-byte slabs of codes (mmrag_padded_dim(d, MMRAG_F8E4M3)), rows of at "
+                    "most 16 MiB (ld=%lld)", who, (long long)ld);
     return MMRAG_OK;
 }
 

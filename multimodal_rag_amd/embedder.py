@@ -1229,9 +1229,17 @@ class EmbeddingManager:
         records: List[Any] = []
         if pairs:
             # hits whose token rows the store keeps are scored from the plane; the rest are encoded as before
-            # (without a store, or when it keeps none of them, the scorer is called exactly as before)
+            # (without a store, or when it keeps none of them, the scorer is called exactly as before).  An FP8 store's
+            # plane is passed even when it keeps none of the hits: the scorer then quantises what it encodes, so a
+            # passage scores the same whether or not its tokens are stored
             spans, plane = self._stored_spans(scorer, results_list, explain)
-            stored = {"spans": spans, "plane": plane} if spans and any(s is not None for s in spans) else {}
+            store = getattr(self.collection, "token_store", None)
+            plane_f8 = bool(spans) and store is not None and store.f8
+            stored = {}
+            if spans and (plane_f8 or any(s is not None for s in spans)):
+                stored = {"spans": spans, "plane": plane}
+                if plane_f8:
+                    stored["plane_f8"] = True
             if explain:
                 scores, records = scorer.explain_pairs(list(queries), docs, pairs, **stored)
             else:

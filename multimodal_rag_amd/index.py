@@ -1974,12 +1974,14 @@ class VectorIndex:
             return out
 
     # ------------------------------------------------------------------ token store / late retrieval ----
-    def enable_token_store(self, dim: int, max_doc_tokens: int, max_bytes: Optional[int] = None):
+    def enable_token_store(self, dim: int, max_doc_tokens: int, max_bytes: Optional[int] = None,
+                           dtype: Optional[str] = None):
         """Attach the token store (late_store.TokenStore): a device fp16 plane [tokens, dim] of the stored chunks' token
         rows, item i being row i, with the `max_doc_tokens` its rows were trimmed to.  Rows keep no tokens until
         set_tokens names them.  delete needs nothing (the alive bitmap is over rows, i.e. items); compact and reset keep
         the store in step.  `max_bytes` (default MMRAG_LATE_STORE_MAX_BYTES; 0 = no cap): past it new rows keep no
-        tokens.  Idempotent for the same (dim, max_doc_tokens)."""
+        tokens.  `dtype` (default MMRAG_LATE_STORE_DTYPE): "float16", or "float8_e4m3fn" for a plane of E4M3 codes,
+        one byte per element, scored by the FP8 MaxSim kernels.  Idempotent for the same (dim, max_doc_tokens, dtype)."""
         from .config import settings
         from .late_store import TokenStore
 
@@ -1988,9 +1990,13 @@ class VectorIndex:
                 if (self._tokens.dim, self._tokens.max_doc_tokens) != (int(dim), int(max_doc_tokens)):
                     raise ValueError(f"this collection's token store holds dim {self._tokens.dim}, max_doc_tokens "
                                      f"{self._tokens.max_doc_tokens}; reset it before changing them")
+                if dtype is not None and dtype != self._tokens.dtype:
+                    raise ValueError(f"this collection's token store holds {self._tokens.dtype} rows; reset it before "
+                                     f"changing the dtype to {dtype}")
                 return self._tokens
             cap = settings.MMRAG_LATE_STORE_MAX_BYTES if max_bytes is None else int(max_bytes)
-            self._tokens = TokenStore(dim, max_doc_tokens, device=self.device, max_bytes=cap)
+            self._tokens = TokenStore(dim, max_doc_tokens, device=self.device, max_bytes=cap,
+                                      dtype=settings.late_store_dtype() if dtype is None else dtype)
             return self._tokens
 
     @property
@@ -2045,12 +2051,14 @@ class VectorIndex:
                     keep.append(j)
             if not keep:
                 return 0
+            as_codes = False
             if len(keep) != len(ids):
                 starts = np.concatenate([[0], np.cumsum(lens)])
                 pick = np.concatenate([np.arange(starts[j], starts[j + 1]) for j in keep]).astype(np.int64)
                 token_rows = st._take(st._as_rows(token_rows), pick)
+                as_codes = st.f8          # an FP8 store: the rows are quantised by now
             st.set_tokens([rows[j] for j in keep], token_rows, [lens[j] for j in keep],
-                          None if token_ids is None else [token_ids[j] for j in keep])
+                          None if token_ids is None else [token_ids[j] for j in keep], _codes=as_codes)
             return len(keep)
 
     def token_spans(self, ids_lists: Sequence[Sequence[str]], with_ids: bool = False):
@@ -2058,7 +2066,8 @@ class VectorIndex:
         per id in order, (first plane row, length, token ids if `with_ids` else None), or None for an id without a live
         row or whose row keeps no tokens.  `plane` is the tensor those rows are in: a later fill or compaction swaps a
         new one in and appends write past the rows a snapshot names, so the snapshot stays valid for a launch that
-        follows.  (None, None, None) without a token store."""
+        follows; its dtype says what the rows are (torch.float16, or torch.uint8 for an FP8 store's code rows).
+        (None, None, None) without a token store."""
         with self._lock:
             st = self._tokens
             if st is None:
@@ -2095,9 +2104,15 @@ class VectorIndex:
             bits = self._where_bits(where)
             q_start, q_len = [int(v) for v in q_start], [int(v) for v in q_len]
             tiles = _native.late_question_tiles(q_start, q_len, q_tokens.shape[0])
-            need = _native.maxsim_topk_workspace_bytes(len(q_start), self._n, k, st.dim, tiles)
+            need = _native.maxsim_topk_workspace_bytes(len(q_start), self._n, k, st.dim, tiles,
+                                                       torch.float8_e4m3fn if st.f8 else torch.float16)
             if self._late_ws is None or _native._nbytes(self._late_ws) < need:
                 self._late_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+            if st.f8:
+                # both operands are codes: the questions' fp16 / fp32 rows are quantised once, here
+                q_codes = st._as_rows(q_tokens)
+                return _native.maxsim_topk_f8(q_codes, q_start, q_len, st.plane, st.n_rows, st.device_offsets(self._n),
+                                              self._n, st.dim, k, alive_bits=bits, workspace=self._late_ws)
             return _native.maxsim_topk(q_tokens, q_start, q_len, st.plane, st.n_rows, st.device_offsets(self._n),
                                        self._n, st.dim, k, alive_bits=bits, workspace=self._late_ws)
 

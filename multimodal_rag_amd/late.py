@@ -184,11 +184,14 @@ class LateInteractionScorer:
         q_ids = [ids[s, first[s]: first[s] + count[s]].tolist() for s in range(len(lens))]
         return tokens, (cu[:-1] + first).astype(np.int32), count.astype(np.int32), q_ids
 
-    def _run_stored(self, queries, docs, pairs, spans, plane, want_best: bool):
+    def _run_stored(self, queries, docs, pairs, spans, plane, want_best: bool, plane_f8: bool = False):
         """_run with a token store: `spans[b]` is (first plane row, length, token ids) of passage b's stored rows, or
         None.  ONE forward over the queries and the passages that are not stored, then one MaxSim launch for the
         stored passages' pairs (against `plane`) and one for the others.  Returns _run's tuple; the plan's d_ids /
-        pair_d are rewritten so that pair p's passage ids are plan["d_ids"][plan["pair_d"][p]] as in _run."""
+        pair_d are rewritten so that pair p's passage ids are plan["d_ids"][plan["pair_d"][p]] as in _run.
+        An FP8 store (`plane_f8`: `plane` holds E4M3 code rows): the encoded rows -- the questions' AND those of the passages that
+        had to be encoded -- are quantised once and both launches are mmrag_maxsim_scores_f8, so every candidate of the
+        call is scored in the plane's arithmetic and a passage scores the same from the plane as re-encoded."""
         import torch
 
         stored = [s is not None for s in spans]
@@ -196,6 +199,9 @@ class LateInteractionScorer:
         tokens, _ = self._encode_stable(plan["ids"], plan["lens"])
         dim = int(self.projection.shape[0]) if self.projection is not None else int(self.encoder.cfg.hidden)
         P, W = len(plan["pair_q"]), _native.MAX_LATE_QUERY_TOKENS
+        if plane_f8:
+            tokens = _native.f8_encode_rows(tokens, dim)
+        scorer = _native.maxsim_scores_f8 if plane_f8 else _native.maxsim_scores
         from_store = np.array([stored[int(b)] for _, b in pairs], bool)
         packed = np.zeros((P, 1 + 2 * W if want_best else 1), np.int32)
         d_ids = list(plan["d_ids"])
@@ -216,8 +222,8 @@ class LateInteractionScorer:
                     pair_d[[p for p in at if int(pairs[p][1]) == b]] = pair_of
             else:
                 d_start, d_len, pd = plan["d_start"], plan["d_len"], plan["pair_d"][at]
-            sums, best_sim, best_idx = _native.maxsim_scores(tokens, d_tok, dim, plan["q_start"], plan["q_len"], d_start,
-                                                             d_len, plan["pair_q"][at], pd, want_best=want_best)
+            sums, best_sim, best_idx = scorer(tokens, d_tok, dim, plan["q_start"], plan["q_len"], d_start, d_len,
+                                              plan["pair_q"][at], pd, want_best=want_best)
             cols = [sums.view(torch.int32).reshape(-1, 1)]
             if want_best:
                 cols += [best_sim.view(torch.int32), best_idx]
@@ -236,13 +242,13 @@ class LateInteractionScorer:
         return self._id2tok.get(int(token_id), int(token_id))
 
     # ------------------------------------------------------------------ scoring -------------
-    def _run(self, queries, docs, pairs, want_best: bool, spans=None, plane=None):
+    def _run(self, queries, docs, pairs, want_best: bool, spans=None, plane=None, plane_f8: bool = False):
         """(scores [P] float32, best_sim [P, 128] float32 | None, best_idx [P, 128] int32 | None, plan): one tokenise
         of the distinct texts, ONE encoder forward over queries and passages together, ONE MaxSim launch, one copy back"""
         import torch
 
-        if spans is not None and any(s is not None for s in spans):
-            return self._run_stored(queries, docs, pairs, spans, plane, want_best)
+        if spans is not None and (plane_f8 or any(s is not None for s in spans)):     # an FP8 store: always
+            return self._run_stored(queries, docs, pairs, spans, plane, want_best, plane_f8)
         plan = self.plan(queries, docs, pairs)
         tokens, _ = self.encoder.encode_tokens(plan["ids"], plan["lens"], self.projection)
         dim = int(self.projection.shape[0]) if self.projection is not None else int(self.encoder.cfg.hidden)
@@ -262,7 +268,7 @@ class LateInteractionScorer:
         return scores, sims, np.ascontiguousarray(packed[:, 1 + W:]), plan
 
     def score_pairs(self, queries: List[str], docs: List[str], pairs: List[Tuple[int, int]], explain: bool = False,
-                    spans=None, plane=None):
+                    spans=None, plane=None, plane_f8: bool = False):
         """MaxSim score of every pair (i, j) = (queries[i], docs[j]): float32 [len(pairs)], out_sum / q_len -- the mean
         over the query's tokens of each token's best cosine against the passage's tokens, so it reads like a cosine.
         `explain`: returns (scores, matches) with, per pair, [(query_token, doc_token, sim)] in query-token order:
@@ -270,14 +276,15 @@ class LateInteractionScorer:
         `spans`, `plane` (the token store): spans[b] = (first row, length, token ids) of passage b's rows in the device
         plane, or None -- such a passage is scored from those rows instead of being encoded again, with the same bits."""
         if not explain:
-            return self._run(queries, docs, pairs, False, spans, plane)[0]
-        scores, records = self.explain_pairs(queries, docs, pairs, spans, plane)
+            return self._run(queries, docs, pairs, False, spans, plane, plane_f8)[0]
+        scores, records = self.explain_pairs(queries, docs, pairs, spans, plane, plane_f8)
         return scores, [[(m["query_token"], m["doc_token"], m["similarity"]) for m in rec] for rec in records]
 
-    def explain_pairs(self, queries: List[str], docs: List[str], pairs: List[Tuple[int, int]], spans=None, plane=None):
+    def explain_pairs(self, queries: List[str], docs: List[str], pairs: List[Tuple[int, int]], spans=None, plane=None,
+                      plane_f8: bool = False):
         """(scores, records): per pair one dict per query token -- query_token, doc_token (as score_pairs names them),
         doc_index (the matched token's 0-based position among the passage's scored tokens) and similarity"""
-        scores, sims, idx, plan = self._run(queries, docs, pairs, True, spans, plane)
+        scores, sims, idx, plan = self._run(queries, docs, pairs, True, spans, plane, plane_f8)
         records = []
         for p in range(len(scores)):
             qi, di = plan["q_ids"][plan["pair_q"][p]], plan["d_ids"][plan["pair_d"][p]]

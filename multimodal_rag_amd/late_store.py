@@ -8,6 +8,11 @@ question, and mmrag_maxsim_topk (csrc/maxsim_scan.hip) scans the whole plane for
 This module is the bookkeeping: lengths, offsets, the stored token ids (what `explain` names), growth, compaction in the
 index's `keep` order and the byte cap.  Every device step is a copy or a gather of rows; the scoring is the HIP kernels'.
 With `device=None` the plane is a numpy array: the same bookkeeping, testable without a GPU.
+
+`dtype="float8_e4m3fn"` keeps the plane as rows of E4M3 codes (include/mmrag.h MMRAG_F8E4M3, one byte per element, pad
+columns code 0): incoming fp16 / fp32 rows are quantised once, here, and the FP8 kernels (mmrag_maxsim_topk_f8,
+mmrag_maxsim_scores_f8) score the codes.  Half the bytes per token, so twice the chunks under the same cap; the scores
+are the quantised rows' own.
 """
 from __future__ import annotations
 
@@ -19,18 +24,45 @@ import numpy as np
 logger = logging.getLogger(__name__)
 
 MAX_PLANE_ROWS = (1 << 31) - 1     # mmrag_maxsim_topk: T < 2^31
+DTYPES = ("float16", "float8_e4m3fn")
+
+
+def f8_encode_numpy(x) -> np.ndarray:
+    """The E4M3 codes (uint8) of float values x as the storage format defines them: csrc/f8_codec.h's f8_encode
+    restated in numpy float32 / uint32 arithmetic (x * 256 rounded to nearest even, subnormals kept, saturation at 448,
+    NaN -> +0).  The numpy stand-in of mmrag_f8_encode_rows."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        y = np.asarray(x, np.float32) * np.float32(256.0)
+        nan = np.isnan(y)
+        sign = np.where(nan, 0, (y.view(np.uint32) >> 24) & 0x80).astype(np.uint32)
+        a = np.abs(y)
+        u = a.view(np.uint32).astype(np.uint64)
+        normal = (((u + 0x7FFFF + ((u >> 20) & 1)) >> 20) - (120 << 3)).astype(np.int64)
+        sub = np.rint(np.where(a < np.float32(0.015625), a, 0) * np.float32(512.0)).astype(np.int64)   # step 2^-9
+        code = np.where(a < np.float32(0.015625), sub, normal)
+        code = np.where(a > np.float32(448.0), 0x7E, code)
+        code = np.where(nan, 0, code).astype(np.uint32)
+    return (sign | code).astype(np.uint8)
 
 
 class TokenStore:
     """Token rows of items 0 .. n_items.  An item of length 0 has no tokens stored: it is no candidate of the scan and is
     re-encoded by a re-rank."""
 
-    def __init__(self, dim: int, max_doc_tokens: int, device: Any = None, max_bytes: int = 0, capacity: int = 4096):
+    def __init__(self, dim: int, max_doc_tokens: int, device: Any = None, max_bytes: int = 0, capacity: int = 4096,
+                 dtype: str = "float16"):
         if dim <= 0 or dim % 64 or dim > 1024:
             raise ValueError(f"token store: dim must be a multiple of 64, at most 1024 (dim={dim})")
         if not 1 <= int(max_doc_tokens) <= 512:
             raise ValueError(f"token store: max_doc_tokens={max_doc_tokens} outside 1..512")
+        if dtype not in DTYPES:
+            raise ValueError(f"token store: dtype must be one of {DTYPES} (got {dtype!r})")
         self.dim = int(dim)
+        self.dtype = dtype
+        self.f8 = dtype == "float8_e4m3fn"
+        # plane columns and bytes per token row: fp16 rows have no pad (dim % 64 == 0), code rows are whole 128-byte slabs
+        self.width = (self.dim + 127) // 128 * 128 if self.f8 else self.dim
+        self.bytes_per_row = self.width if self.f8 else self.dim * 2
         self.max_doc_tokens = int(max_doc_tokens)
         self.device = device
         self.max_bytes = int(max_bytes)
@@ -46,13 +78,18 @@ class TokenStore:
     # ------------------------------------------------------------------ plane helpers --------
     def _alloc(self, rows: int):
         if self.device is None:
-            return np.zeros((rows, self.dim), np.float16)
+            return np.zeros((rows, self.width), np.uint8 if self.f8 else np.float16)
         import torch
 
-        return torch.zeros((rows, self.dim), dtype=torch.float16, device=self.device)
+        return torch.zeros((rows, self.width), dtype=torch.uint8 if self.f8 else torch.float16, device=self.device)
 
-    def _as_rows(self, token_rows):
-        """`token_rows` as a [m, dim] fp16 array of the plane's kind"""
+    def _as_rows(self, token_rows, codes: bool = False):
+        """`token_rows` as a [m, width] array of the plane's kind: fp16 rows, or (an FP8 store) their code rows --
+        quantised here, on the device by mmrag_f8_encode_rows, in the numpy mode by f8_encode_numpy.  `codes` (internal:
+        a caller that hands back what _as_rows returned): the rows already are code rows of the plane's width.  Without
+        it integer data is refused: a uint8 array is never taken for codes because its width happens to fit."""
+        if self.f8:
+            return self._as_code_rows(token_rows, codes)
         if self.device is None:
             rows = np.ascontiguousarray(np.asarray(token_rows, np.float16))
         else:
@@ -63,6 +100,35 @@ class TokenStore:
         if rows.ndim != 2 or rows.shape[1] != self.dim:
             raise ValueError(f"token store: token rows must be [tokens, {self.dim}] (got {tuple(rows.shape)})")
         return rows
+
+    def _as_code_rows(self, token_rows, codes: bool):
+        bad = ValueError(f"token store: token rows must be floating-point [tokens, {self.dim}] (got "
+                         f"{tuple(getattr(token_rows, 'shape', ()))})")
+        if self.device is None:
+            rows = np.asarray(token_rows)
+            if codes:
+                if rows.dtype != np.uint8 or rows.ndim != 2 or rows.shape[1] != self.width:
+                    raise bad
+                return np.ascontiguousarray(rows)
+            if rows.ndim != 2 or rows.shape[1] != self.dim or rows.dtype.kind != "f":
+                raise bad
+            codes = np.zeros((rows.shape[0], self.width), np.uint8)
+            codes[:, : self.dim] = f8_encode_numpy(rows.astype(np.float32))
+            return codes
+        import torch
+
+        from . import _native
+
+        rows = token_rows if isinstance(token_rows, torch.Tensor) else torch.from_numpy(np.asarray(token_rows))
+        if codes:
+            if rows.dtype != torch.uint8 or rows.dim() != 2 or rows.shape[1] != self.width:
+                raise bad
+            return rows.to(self.device).contiguous()
+        if rows.dim() != 2 or rows.shape[1] != self.dim or not rows.is_floating_point():
+            raise bad
+        if rows.dtype not in (torch.float16, torch.float32):
+            rows = rows.to(torch.float32)
+        return _native.f8_encode_rows(rows.to(self.device).contiguous(), self.dim)
 
     def _take(self, rows, index: np.ndarray):
         if self.device is None:
@@ -160,12 +226,13 @@ class TokenStore:
 
     def stats(self) -> Dict[str, Any]:
         return {"dim": self.dim, "max_doc_tokens": self.max_doc_tokens, "items": int((self._lens > 0).sum()),
-                "tokens": self._T, "bytes": self._T * self.dim * 2, "reserved_bytes": int(self._plane.shape[0]) * self.dim * 2,
-                "max_bytes": self.max_bytes, "dropped_items": self.dropped}
+                "tokens": self._T, "bytes": self._T * self.bytes_per_row,
+                "reserved_bytes": int(self._plane.shape[0]) * self.bytes_per_row, "max_bytes": self.max_bytes,
+                "dropped_items": self.dropped, "dtype": self.dtype, "bytes_per_token": self.bytes_per_row}
 
     # ------------------------------------------------------------------ writing --------------
     def set_tokens(self, rows: Sequence[int], token_rows, lens: Sequence[int],
-                   token_ids: Optional[Sequence[Optional[Sequence[int]]]] = None):
+                   token_ids: Optional[Sequence[Optional[Sequence[int]]]] = None, _codes: bool = False):
         """Store the token rows of items `rows` (distinct): item rows[j] gets the next lens[j] rows of `token_rows`
         [sum(lens), dim].  Items past the last one that has tokens are appended to the plane; any other item (a fill of an
         earlier row, a replacement) rebuilds the plane by one gather.  Past `max_bytes` (0 = no cap) or 2^31 - 1 plane
@@ -182,7 +249,7 @@ class TokenStore:
             raise ValueError("token store: rows must be distinct and non-negative")
         if lens_a.min() < 0 or lens_a.max() > self.max_doc_tokens:
             raise ValueError(f"token store: a length outside 0..{self.max_doc_tokens}")
-        new = self._as_rows(token_rows)
+        new = self._as_rows(token_rows, _codes)      # _codes: VectorIndex.set_tokens_for_ids hands back _as_rows' rows
         if new.shape[0] != int(lens_a.sum()):
             raise ValueError(f"token store: {new.shape[0]} token rows for lengths that sum to {int(lens_a.sum())}")
         src_at = np.zeros(rows_a.size + 1, np.int64)     # where each item's rows start in `new`
@@ -199,7 +266,7 @@ class TokenStore:
         keep = lens_a.copy()
         limit = MAX_PLANE_ROWS
         if self.max_bytes > 0:
-            limit = min(limit, self.max_bytes // (self.dim * 2))
+            limit = min(limit, self.max_bytes // self.bytes_per_row)
         used = self._T - int(old_lens.sum())
         for j in range(rows_a.size):
             if used + keep[j] > limit:

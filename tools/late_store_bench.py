@@ -10,7 +10,11 @@
     in the counters, and `kmeans_assign` (the same tile body, arg-max epilogue) of the same plane against 128 centroids.
     The plane is filled with random unit rows on the device: the scan's cost does not depend on the values.
 
-    python tools/late_store_bench.py [--candidates 20,100] [--chunks 10000,100000] [--reps 30]
+    python tools/late_store_bench.py [--candidates 20,100] [--chunks 10000,100000] [--reps 30] [--dtype float16]
+
+--dtype float8_e4m3fn keeps both stores as E4M3 code rows: the rerank and the scan then run the FP8
+kernels, the questions are quantised per call (counted in the times), and kmeans_assign, which reads fp16 rows only,
+is left out.  `--candidates ""` skips (a).
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/late_store_bench.py --profile      (a run of its own)
 
 --profile runs 10 late_rerank calls per candidate count and 10 late_search calls per case, for the kernel statistics
@@ -84,6 +88,7 @@ def main():
     ap.add_argument("--candidates", default="20,100")
     ap.add_argument("--chunks", default="10000,100000")
     ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--dtype", default="float16", choices=("float16", "float8_e4m3fn"))
     ap.add_argument("--profile", action="store_true")
     a = ap.parse_args()
     reps = 10 if a.profile else a.reps
@@ -98,7 +103,7 @@ def main():
     g = np.random.default_rng(0)
     question = text(g, 32)
     report = {"shape": "all-MiniLM-L6-v2 (6 x 384, 12 heads, I 1536), random weights", "question_tokens": 32,
-              "reps": reps, "rerank": {}, "scan": {}}
+              "reps": reps, "store_dtype": a.dtype, "rerank": {}, "scan": {}}
 
     # ---- (a) late_rerank with and without the store
     for n in [int(x) for x in a.candidates.split(",") if x]:
@@ -106,6 +111,7 @@ def main():
         ids = [f"id{i}" for i in range(n)]
         m.collection = VectorIndex(dim=enc.dim, dtype=torch.float16)
         m.collection.add(unit_plane(n, enc.dim, n).float().cpu().numpy(), documents=docs, ids=ids)
+        m.collection.enable_token_store(enc.dim, m._get_late().max_doc_tokens, dtype=a.dtype)
         m._store_tokens(ids, docs)
         hits = {"ids": ids, "distances": [0.0] * n, "metadatas": [{}] * n, "documents": docs}
         unknown = {**hits, "ids": ["x" + i for i in ids]}            # ids the store does not know: the path before it
@@ -127,16 +133,18 @@ def main():
         for lo in range(0, n, step):
             hi = min(n, lo + step)
             idx.add(unit_plane(hi - lo, dim, lo + 1).float().cpu().numpy(), ids=[f"c{i}" for i in range(lo, hi)])
-        st = idx.enable_token_store(dim, 512)
+        st = idx.enable_token_store(dim, 512, dtype=a.dtype)
         for lo in range(0, n, 4096):
             hi = min(n, lo + 4096)
             st.set_tokens(range(lo, hi), unit_plane(int(lens[lo:hi].sum()), dim, 7 + lo), lens[lo:hi])
         T = st.n_rows
-        case = {"tokens": T, "plane_bytes": T * dim * 2}
-        cent = unit_plane(128, dim, 3)
-        km = device_ms(lambda: _native.kmeans_assign(st.plane, T, dim, cent), reps)
-        case["kmeans_assign_128_ms"] = km
-        case["kmeans_assign_tflops"] = 2.0 * T * 128 * dim / km / 1e9
+        plane_bytes = T * st.bytes_per_row
+        case = {"tokens": T, "plane_bytes": plane_bytes, "bytes_per_token": st.bytes_per_row}
+        if not st.f8:
+            cent = unit_plane(128, dim, 3)
+            km = device_ms(lambda: _native.kmeans_assign(st.plane, T, dim, cent), reps)
+            case["kmeans_assign_128_ms"] = km
+            case["kmeans_assign_tflops"] = 2.0 * T * 128 * dim / km / 1e9
         for Q in (1, 16):
             q_tok = unit_plane(32 * Q, dim, 11 + Q)
             qs, ql = np.arange(Q, dtype=np.int32) * 32, np.full(Q, 32, np.int32)
@@ -146,7 +154,7 @@ def main():
             torch.cuda.synchronize()
             survivors = idx._late_ws[: 4 * Q].view(torch.int32).cpu().numpy()
             tiles = (32 * Q + 127) // 128
-            case[f"Q{Q}"] = {"wall_ms": wall, "device_ms": dev, "plane_gb_per_s": T * dim * 2 / dev / 1e6,
+            case[f"Q{Q}"] = {"wall_ms": wall, "device_ms": dev, "plane_gb_per_s": plane_bytes / dev / 1e6,
                              "tflops_of_128_row_tiles": 2.0 * T * 128 * tiles * dim / dev / 1e9,
                              "survivors_per_question": [int(survivors.min()), int(np.median(survivors)),
                                                         int(survivors.max())]}
