@@ -777,6 +777,52 @@ int mmrag_filtered_topk(const void *q, const void *rows, int B, int64_t n, int d
                         int64_t row_offset, const int32_t *filter_of_query, int F, const uint32_t *vis_bits,
                         float *out_scores, int64_t *out_rows, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Range retrieval (csrc/range.hip): not "the best k" but "everything at or above a score": how many rows pass, how they
+ * spread over the values of metadata columns, and the `limit` best of them, in ONE exact masked scan (the scan of
+ * mmrag_filtered_topk with another epilogue; the [B, n] score matrix is never written).  VectorIndex.range_search.
+ *
+ * Definitions
+ *   - score(b, r) is the float32 accumulator of the pair-tile body for query row b and stored row r: the bits of
+ *     mmrag_filtered_topk / mmrag_scoped_topk, a function of the two rows and d alone.
+ *   - row r PASSES for query b iff r < n, r is visible to b (vis_bits == NULL: every row below n; else bit r of
+ *     vis_bits[filter_of_query[b]] is set, bits at and past n ignored, a filter outside 0..F-1 sees nothing) and
+ *     score(b, r) >= threshold[b].
+ *   - out_count[b] = the number of passing rows.
+ *   - out_facets[b], for column c at offset sum over c' < c of (G_c' + 1): slot g < G_c = the passing rows with
+ *     facet_cols[c][r] == g; slot G_c = the passing rows whose code is outside 0..G_c-1 (the -1 of a row without the
+ *     key).  Every column's slots sum to out_count[b].
+ *   - out_scores / out_rows [B, limit] = the `limit` best passing rows: score descending, ties to the lower row,
+ *     row + row_offset, (-inf, -1) padded (mmrag_cosine_topk_deep's order).
+ *   - n == 0: zero counts, zero facets, padded hits.
+ * Contract
+ *   - counts and facets are integers added by atomics in the full pass alone: they do not depend on the batch, the
+ *     grid, the order of arrival, `limit`, or whether bound passes or an overflow re-run ran;
+ *   - hits are exact under any bitmap and threshold: when n exceeds the candidate slots of a query (32 limit, at least
+ *     16384) a lower bound max(threshold[b], the limit-th best visible sampled score) is staged first, as
+ *     mmrag_filtered_topk does, and only the candidate appends use it;
+ *   - limit == 0: one pass, no select, no stream synchronisation whatever n is; limit > 0: at most one, and only when
+ *     n exceeds the candidate slots;
+ *   - out_count and out_facets are zeroed on `stream` by the call.
+ *   q, rows          as mmrag_filtered_topk's; MMRAG_F8E4M3 returns MMRAG_EUNSUPPORTED
+ *   threshold        dev [B] float32, finite (not read by the host; the Python wrapper checks its copy)
+ *   limit            0..MMRAG_MAX_K_DEEP; 0 = counts and facets only, out_scores / out_rows may be NULL
+ *   filter_of_query, F, vis_bits   as mmrag_filtered_topk's; vis_bits == NULL: no bitmaps, the other two are ignored
+ *   facet_cols       HOST array of n_facets device columns [n] int32;  facet_sizes: HOST [n_facets], G_c >= 0
+ *   n_facets         0..MMRAG_MAX_FACET_COLUMNS
+ *   out_count        dev [B];  out_facets: dev [B, sum_c (G_c + 1)], NULL iff n_facets == 0
+ *   workspace        dev, >= mmrag_range_scan_workspace_bytes(B, n, limit, facet_slots) bytes (0 for arguments out of
+ *                    range; facet_slots = sum_c (G_c + 1), which the size does not depend on today), 16-byte aligned;
+ *                    short or misaligned: MMRAG_EWORKSPACE
+ * MMRAG_EINVAL before anything is launched: a null pointer, B < 1, n < 0 or >= 2^31, limit or n_facets out of range,
+ * vis_bits without filter_of_query or F < 1, a negative G_c, d <= 0, ld < d or not whole slabs. */
+#define MMRAG_MAX_FACET_COLUMNS 4
+size_t mmrag_range_scan_workspace_bytes(int B, int64_t n, int limit, int facet_slots);
+int mmrag_range_scan(const void *q, const void *rows, int B, int64_t n, int d, int64_t ld, int dtype,
+                     const float *threshold, int limit, int64_t row_offset, const int32_t *filter_of_query, int F,
+                     const uint32_t *vis_bits, const int32_t *const *facet_cols, const int32_t *facet_sizes, int n_facets,
+                     uint32_t *out_count, uint32_t *out_facets, float *out_scores, int64_t *out_rows, void *workspace,
+                     size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Late-interaction re-ranking (ColBERT's MaxSim) with the bi-encoder alone.  The reference has no counterpart: its
  * EmbeddingManager.rerank_results is a placeholder (app/utils/embedder.py:834-859).  The encoder's per-token outputs are

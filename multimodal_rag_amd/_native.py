@@ -33,6 +33,7 @@ MAX_CLUSTERS = 4096   # mmrag_kmeans_assign / mmrag_cluster_sums (MMRAG_MAX_CLUS
 MAX_SCOPE_GROUPS = 64   # mmrag_scoped_topk (MMRAG_MAX_SCOPE_GROUPS)
 # mmrag_filter_eval (MMRAG_MAX_FILTER_OPS, MMRAG_MAX_FILTER_SET, MMRAG_MAX_FILTER_COLUMNS)
 MAX_FILTER_OPS, MAX_FILTER_SET, MAX_FILTER_COLUMNS = 32, 64, 16
+MAX_FACET_COLUMNS = 4   # mmrag_range_scan (MMRAG_MAX_FACET_COLUMNS)
 MAX_RELATED_ROWS, MAX_RELATED_SETS = 8192, 64   # mmrag_related_groups (MMRAG_MAX_RELATED_ROWS, MMRAG_MAX_RELATED_SETS)
 MAX_RECOMMEND_EXAMPLES = 16  # mmrag_recommend_topk (MMRAG_MAX_RECOMMEND_EXAMPLES)
 # mmrag_maxsim_scores (MMRAG_MAX_LATE_QUERY_TOKENS, MMRAG_MAX_LATE_DOC_TOKENS)
@@ -248,6 +249,16 @@ def _declare(lib):
                                         c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.mmrag_internal_filtered_topk_ex.restype = c_int
     lib.mmrag_internal_filtered_topk_ex.argtypes = lib.mmrag_filtered_topk.argtypes + [c_int64, ctypes.c_uint, c_void_p]
+    # range scan (csrc/range.hip); the _ex entry adds a candidate capacity and debug switches (tests, not in
+    # include/mmrag.h)
+    lib.mmrag_range_scan_workspace_bytes.restype = c_size_t
+    lib.mmrag_range_scan_workspace_bytes.argtypes = [c_int, c_int64, c_int, c_int]
+    lib.mmrag_range_scan.restype = c_int
+    lib.mmrag_range_scan.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_int, c_int64, c_int, c_void_p, c_int, c_int64,
+                                     c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.mmrag_internal_range_scan_ex.restype = c_int
+    lib.mmrag_internal_range_scan_ex.argtypes = lib.mmrag_range_scan.argtypes + [c_int64, ctypes.c_uint]
     # related groups (csrc/related.hip); the _ex entry adds the scan's grid (tests, not in include/mmrag.h)
     lib.mmrag_related_groups_workspace_bytes.restype = c_size_t
     lib.mmrag_related_groups_workspace_bytes.argtypes = [c_int, c_int, c_int64, c_int, c_int]
@@ -944,6 +955,88 @@ def filtered_topk(q: torch.Tensor, rows: torch.Tensor, n: int, d: int, k: int, f
             items.data_ptr() if items is not None else None)
     _check(st, "mmrag_filtered_topk")
     return (out_s, out_r, items) if count_items else (out_s, out_r)
+
+
+def range_scan_workspace_bytes(B: int, n: int, limit: int, facet_slots: int = 0) -> int:
+    return int(lib().mmrag_range_scan_workspace_bytes(int(B), int(n), int(limit), int(facet_slots)))
+
+
+def range_scan(q: torch.Tensor, rows: torch.Tensor, n: int, d: int, threshold, limit: int, facet_cols=(),
+               facet_sizes=(), filter_of_query=None, vis_bits: Optional[torch.Tensor] = None,
+               workspace: Optional[torch.Tensor] = None, row_offset: int = 0, cap: int = 0, dbg: int = 0):
+    """Everything at or above a score (include/mmrag.h mmrag_range_scan, where the definitions are): for each query of
+    q [B, ld] over the first n of `rows` [cap, ld], the number of rows it sees whose score is >= its threshold, their
+    spread over the codes of up to MAX_FACET_COLUMNS int32 device columns, and the `limit` best of them, in one scan.
+    `threshold`: one finite float, B of them (a HOST sequence, checked here) or a device float32 [B] tensor (taken as it
+    is).  `limit`: 0..MAX_K_DEEP; 0 = counts and facets only.  `facet_cols` / `facet_sizes`: device int32 columns of at
+    least n codes and their G_c; a code outside 0..G_c-1 counts in the column's last slot.  `vis_bits`: a contiguous
+    device int32 [F, filter_words(n)] with `filter_of_query`, B HOST integers (an index outside 0..F-1 sees nothing);
+    None: every row below n is visible.  Returns (counts [B] int32, facets [B, sum(G_c + 1)] int32 or None without
+    columns, scores [B, limit] float32 descending, rows [B, limit] int64 + row_offset, (-inf, -1) padded; both None for
+    limit == 0).  No host synchronisation unless limit > 0 and n exceeds the candidate slots of a query.  `cap`, `dbg`
+    (tests): fewer slots; dbg & 1 = no bound passes."""
+    n, limit = int(n), int(limit)
+    facet_cols, facet_sizes = list(facet_cols), [int(g) for g in facet_sizes]
+    if not 0 <= limit <= MAX_K_DEEP:
+        raise ValueError(f"range_scan: limit={limit} outside 0..{MAX_K_DEEP}")
+    if len(facet_cols) > MAX_FACET_COLUMNS:
+        raise MMRagNativeError(f"range_scan: {len(facet_cols)} facet columns, at most {MAX_FACET_COLUMNS}")
+    if len(facet_sizes) != len(facet_cols) or any(g < 0 for g in facet_sizes):
+        raise MMRagNativeError("range_scan: facet_sizes must hold one G >= 0 per facet column")
+    _dev_check(q, rows, vis_bits, *facet_cols)
+    _check_q_rows("range_scan", q, rows, n, other="rows")
+    _check_stored_rows("range_scan", rows)
+    B, ld = q.shape
+    dev = q.device
+    for c in facet_cols:
+        if c.dim() != 1 or c.dtype != torch.int32 or not c.is_contiguous() or c.numel() < n or c.device != dev:
+            raise MMRagNativeError("range_scan: a facet column must be a contiguous int32 tensor of at least n codes on "
+                                   "the rows' device")
+    if isinstance(threshold, torch.Tensor) and threshold.is_cuda:
+        thr = threshold
+        if thr.dtype != torch.float32 or thr.dim() != 1 or thr.numel() != B or not thr.is_contiguous() or thr.device != dev:
+            raise MMRagNativeError(f"range_scan: a device threshold must be a contiguous float32 [{B}] tensor")
+    else:
+        host = torch.as_tensor(threshold, dtype=torch.float32).reshape(-1)
+        if host.numel() == 1:
+            host = host.expand(B)
+        if host.numel() != B:
+            raise MMRagNativeError(f"range_scan: threshold holds {host.numel()} entries for {B} queries")
+        if not bool(torch.isfinite(host).all()):
+            raise ValueError("range_scan: thresholds must be finite")
+        thr = _pinned_to_device(host, dev)
+    foq_dev, F = None, 0
+    if vis_bits is not None:
+        W = filter_words(n)
+        if (vis_bits.dim() != 2 or vis_bits.dtype != torch.int32 or not vis_bits.is_contiguous()
+                or vis_bits.shape[0] < 1 or vis_bits.shape[1] != W or vis_bits.device != dev):
+            raise MMRagNativeError(f"range_scan: vis_bits must be a contiguous int32 [F, {W}] tensor on the rows' device")
+        F = vis_bits.shape[0]
+        if filter_of_query is None:
+            raise MMRagNativeError("range_scan: vis_bits needs filter_of_query")
+        foq = torch.as_tensor(filter_of_query, dtype=torch.int32).reshape(-1).cpu()
+        if foq.numel() != B:
+            raise MMRagNativeError(f"range_scan: filter_of_query holds {foq.numel()} entries for {B} queries")
+        foq_dev = _pinned_to_device(foq, dev)
+    slots = sum(g + 1 for g in facet_sizes)
+    need = range_scan_workspace_bytes(B, n, limit, slots)
+    if workspace is None or _nbytes(workspace) < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    facets = torch.empty((B, slots), dtype=torch.int32, device=dev) if facet_cols else None
+    out_s, out_r = _topk_out(B, limit, dev) if limit else (None, None)
+    ptrs = (c_void_p * MAX_FACET_COLUMNS)(*[c.data_ptr() for c in facet_cols])
+    sizes = (c_int32 * MAX_FACET_COLUMNS)(*facet_sizes)
+    with torch.cuda.device(dev):
+        st = lib().mmrag_internal_range_scan_ex(
+            q.data_ptr(), rows.data_ptr(), B, n, int(d), ld, _TORCH2DT[q.dtype], thr.data_ptr(), limit, int(row_offset),
+            foq_dev.data_ptr() if foq_dev is not None else None, F,
+            vis_bits.data_ptr() if vis_bits is not None and vis_bits.numel() else None, ptrs, sizes, len(facet_cols),
+            counts.data_ptr(), facets.data_ptr() if facets is not None else None,
+            out_s.data_ptr() if limit else None, out_r.data_ptr() if limit else None, workspace.data_ptr(),
+            _nbytes(workspace), _stream_ptr(dev), int(cap), int(dbg))
+    _check(st, "mmrag_range_scan")
+    return counts, facets, out_s, out_r
 
 
 def related_groups_workspace_bytes(M: int, S: int, n: int, n_groups: int, k: int) -> int:

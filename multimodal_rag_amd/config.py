@@ -146,6 +146,11 @@ class Settings:
     # (exact: sets are independent), a single set that exceeds it alone is refused.  A memory budget, not a measurement
     MMRAG_RELATED_TABLE_BYTES: int = field(
         default_factory=lambda: int(os.getenv("MMRAG_RELATED_TABLE_BYTES", str(1 << 30))))
+    # range retrieval (VectorIndex.range_query, csrc/range.hip): the scan adds into one 4-byte counter per (query, facet
+    # slot: a key's distinct values + 1); a batch whose tables would exceed this many bytes is split by queries (exact:
+    # queries are independent), a single query that exceeds it alone is refused.  A memory budget, not a measurement
+    MMRAG_RANGE_TABLE_BYTES: int = field(
+        default_factory=lambda: int(os.getenv("MMRAG_RANGE_TABLE_BYTES", str(256 << 20))))
     # topic clustering (VectorIndex.cluster, csrc/kmeans.hip): the default number of topics of cluster() / GET /topics;
     # 0 (default) = automatic, auto_topics(live rows); else 1 .. 4096
     MMRAG_TOPICS: int = field(default_factory=lambda: int(os.getenv("MMRAG_TOPICS", "0")))

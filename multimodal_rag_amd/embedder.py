@@ -46,6 +46,7 @@ LATE_KEYS = RESULT_KEYS + ("late_scores",)
 FUSED_KEYS = RESULT_KEYS + ("fused_scores", "matched_queries", "best_query")
 BOOST_KEYS = RESULT_KEYS + ("scores", "boosts")
 RECOMMEND_KEYS = RESULT_KEYS + ("scores", "penalties", "matched", "repelled_by")
+RANGE_KEYS = RESULT_KEYS + ("total", "truncated", "facets")
 _HOSTROWS = load_hostrows()
 _COLLECTION_NOTE = {"description": "Multi-modal RAG embeddings"}
 # what a retrieval mode needs of the collection: (method, the error of a collection that lacks it)
@@ -62,6 +63,7 @@ _NEEDS_RECOMMEND = ("recommend_query", "recommend retrieval needs a single-GPU c
                                         "full-precision rows")
 _NEEDS_RELATED = ("related_query", "related-document retrieval needs a single-GPU collection (VectorIndex) with "
                                    "full-precision rows")
+_NEEDS_RANGE = ("range_query", "range retrieval needs a single-GPU collection (VectorIndex) with full-precision rows")
 _NEEDS_LATE = ("late_query", "late retrieval needs a single-GPU collection (VectorIndex) with a token store")
 _late_store_warned = False   # "MMRAG_LATE_STORE is set but this embedder cannot keep token rows": once per process
 _boost_warned = False   # "this collection cannot boost": once per process
@@ -73,6 +75,7 @@ _EMPTY_LATE = {key: [] for key in LATE_KEYS}
 _EMPTY_FUSED = {key: [] for key in FUSED_KEYS}
 _EMPTY_BOOST = {key: [] for key in BOOST_KEYS}
 _EMPTY_RECOMMEND = {key: [] for key in RECOMMEND_KEYS}
+_EMPTY_RANGE = {**_EMPTY, "total": 0, "truncated": False, "facets": {}}
 _EMPTY_GROUPED = {**_EMPTY, "groups": [], "exhaustive": False, "fetch_k": 0}
 
 
@@ -899,6 +902,47 @@ class EmbeddingManager:
         found = await self._refusing_call("Related documents", self.collection.related_query, sets=[entry],
                                           n_results=n_results, threshold=t, where=filter_dict)
         return {"chunks": m, "threshold": float(t), "related": found[0]}
+
+    # ---- range retrieval: everything above a score, counted and faceted (VectorIndex.range_query, csrc/range.hip) ----
+    def supports_range(self) -> bool:
+        """True when the collection can answer range_query (a single-GPU VectorIndex with full-precision rows; not the
+        sharded serving path, whose counts would have to be added across GPUs)"""
+        return self.collection is None or (hasattr(self.collection, "range_query") and self._has_full_rows())
+
+    def _answer_range(self, texts: Sequence[str], min_scores: Sequence[float], limit: int, facets: Sequence[str],
+                      filter_dict: Optional[Dict]) -> List[Dict[str, Any]]:
+        """blocking, one worker thread: cached or fresh embeddings (ONE encoder pass for the misses), then ONE
+        collection.range_query for all of them (one scan that counts, facets and keeps the best `limit`)"""
+        if not self._has_full_rows():
+            raise ValueError(_NEEDS_RANGE[1])
+        res = self.collection.range_query(self._embed(texts), threshold=list(min_scores), limit=limit, wheres=filter_dict,
+                                          facets=list(facets), include=self._INCLUDE)
+        hits = self._split(res, len(texts))
+        for at, hit in enumerate(hits):
+            hit.update(total=res["total"][at], truncated=res["truncated"][at], facets=res["facets"][at])
+        return hits
+
+    async def range_query(self, query_text: str, min_score: float, limit: int = 20, facets: Sequence[str] = (),
+                          filter_dict: Optional[Dict] = None) -> Dict[str, Any]:
+        """Everything relevant, and how much of it there is (VectorIndex.range_query): the `limit` best stored items
+        whose cosine with the query is at least `min_score`, as the result dict of query(), plus `total` (how many
+        items clear the score), `truncated` (total > limit) and `facets` ({metadata key: [{"value", "count"}, ...]}
+        over ALL of them, for each key in `facets`).  limit 0 = the numbers alone.  Same empty-query error, embedding
+        cache and query count as query(); it calls the collection directly (no dynamic batching)."""
+        return await self._single("Range query", _NEEDS_RANGE, self._answer_range, query_text, [float(min_score)],
+                                  int(limit), list(facets), filter_dict)
+
+    async def batch_range_query(self, queries: List[str], min_score, limit: int = 20, facets: Sequence[str] = (),
+                                filter_dict: Optional[Dict] = None) -> List[Dict[str, Any]]:
+        """batch_query's twin for range_query: one batched encode and one scan for all the queries; `min_score` is one
+        float or one per query; a query that cannot be answered gets a dict with empty lists, zero totals and an
+        'error' message."""
+        scores = [float(min_score)] * len(queries) if isinstance(min_score, (int, float)) else [float(x) for x in min_score]
+        if len(scores) != len(queries):
+            raise ValueError(f"{len(scores)} scores for {len(queries)} queries")
+        live = [t for q, t in zip(queries, scores) if q and q.strip()]    # as _batch picks them
+        return await self._batch("Batch range query", _NEEDS_RANGE, _EMPTY_RANGE, self._answer_range, queries, live,
+                                 int(limit), list(facets), filter_dict)
 
     def supports_grouping(self) -> bool:
         """True when the collection can answer grouped_query (a single-GPU VectorIndex; not the sharded serving path,

@@ -241,6 +241,7 @@ class VectorIndex:
         # typed metadata columns of the device filters (filters.py): built per key on first use, derived, not persisted
         self._filter_cols = ColumnRegistry(lambda: (self._metadatas, self._n, self._added_at))
         self._filtered_ws: Optional[torch.Tensor] = None   # workspace of the filtered search, reused
+        self._range_ws: Optional[torch.Tensor] = None      # workspace of the range search, reused
         self.device_filters = bool(settings.MMRAG_DEVICE_FILTERS)   # _where_bits builds its bitmap on the device
         self._tokens = None    # late_store.TokenStore once enable_token_store() ran: token rows of the items, item = row
         self._late_ws: Optional[torch.Tensor] = None      # workspace of the late search, reused
@@ -1533,6 +1534,187 @@ class VectorIndex:
             emb_src = self._full if "embeddings" in include else None
         with stage("collect"):
             return self._collect(scores, rows, include, *tables, emb_src)
+
+    # ------------------------------------------------------------------ range retrieval (count, facets, hits) ----
+    def _launch_range(self, query_embeddings, threshold, limit: int, wheres, facets, check_norm: bool = True):
+        """enqueue the range scan(s) (caller holds the lock): (counts [B] int64, one [B, G + 1] int64 table per facet
+        key, scores [B, limit], rows [B, limit], the keys' host tables ordinal -> value), all tensors on the device"""
+        from .config import settings
+
+        self._need_plane("range_query")
+        limit = int(limit)
+        if not 0 <= limit <= _native.MAX_K_DEEP:
+            raise ValueError(f"limit must be in 0..{_native.MAX_K_DEEP} for a range search")
+        facets = [facets] if isinstance(facets, str) else list(facets)
+        if len(facets) > _native.MAX_FACET_COLUMNS or len(set(facets)) != len(facets):
+            raise ValueError(f"facets: at most {_native.MAX_FACET_COLUMNS} distinct metadata keys (got {facets!r})")
+        qf = self._to_device_f32(query_embeddings, "query", check_norm)     # converted and norm-checked once
+        B = qf.shape[0]
+        thr = np.asarray(threshold, dtype=np.float32).reshape(-1)
+        if thr.size == 1:
+            thr = np.repeat(thr, B)
+        if thr.size != B:
+            raise ValueError(f"threshold holds {thr.size} entries for {B} queries")
+        if not np.isfinite(thr).all():
+            raise ValueError("threshold must be finite")
+        wheres = [wheres] * B if wheres is None or isinstance(wheres, dict) else list(wheres)
+        if len(wheres) != B:
+            raise ValueError(f"wheres holds {len(wheres)} entries for {B} queries")
+        states = [self.enable_grouping(key) for key in facets]
+        sizes = [len(st["values"]) for st in states]
+        cols = [st["col"] for st in states]
+        values = [list(st["values"]) for st in states]
+        slots = sum(g + 1 for g in sizes)
+        budget = int(settings.MMRAG_RANGE_TABLE_BYTES)
+        if 4 * slots > budget:
+            raise ValueError(f"range search: one query's facet tables take {4 * slots} bytes ({slots} slots), above "
+                             f"MMRAG_RANGE_TABLE_BYTES={budget}")
+        # equal filters are one bitmap: ("all",) = every live row, ("prog", program), ("slow", the filter as written)
+        seen: Dict[int, Any] = {}
+        index: Dict[Any, int] = {}
+        filters: List[Tuple[Any, Any]] = []
+        of_query: List[int] = []
+        for w in wheres:
+            if not w:
+                kind: Any = ("all",)
+            else:
+                if id(w) not in seen:
+                    seen[id(w)] = self._compiled(w)[0]
+                kind = ("prog", seen[id(w)]) if seen[id(w)] is not None else ("slow", repr(w))
+            if kind not in index:
+                index[kind] = len(filters)
+                filters.append((kind, w))
+            of_query.append(index[kind])
+        masked = bool(self._n_dead) or any(kind[0] != "all" for kind, _ in filters)
+        W = _native.filter_words(self._n)
+        alive = self._alive_dev if self._n_dead else None
+
+        def bitmaps(fl: List[int]) -> Tuple[torch.Tensor, Dict[int, int]]:
+            """the [F, W] table of filters fl, compiled programs first (one evaluation), and each filter's row in it"""
+            fl = sorted(fl, key=lambda f: filters[f][0][0] != "prog")
+            vis = torch.zeros((len(fl), W), dtype=torch.int32, device=self.device)
+            n_prog = sum(filters[f][0][0] == "prog" for f in fl)
+            if n_prog and self._n:
+                self._eval_programs([filters[f][0][1] for f in fl[:n_prog]], vis[:n_prog], alive)
+            for at in range(n_prog, len(fl)):
+                kind, w = filters[fl[at]]
+                # a filter the compiler does not cover: the bitmap every other search builds for it, into the table
+                words = self._where_bits(w) if kind[0] == "slow" else alive
+                if words is None:
+                    vis[at].fill_(-1)          # every row; bits at and past n are ignored by the scan
+                else:
+                    m = min(W, words.numel())
+                    vis[at, :m].copy_(words[:m])
+            return vis, {f: at for at, f in enumerate(fl)}
+
+        # chunks of queries, equal filters next to each other: at most the table budget of facet slots and at most
+        # MMRAG_FILTER_BITMAP_BYTES of bitmaps each
+        order = sorted(range(B), key=lambda b: of_query[b])
+        max_q = max(1, budget // (4 * slots)) if slots else B
+        max_f = max(1, int(settings.MMRAG_FILTER_BITMAP_BYTES) // max(4 * W, 1)) if masked else len(filters)
+        chunks: List[List[int]] = []
+        cur: List[int] = []
+        cur_f: set = set()
+        for b in order:
+            if cur and (len(cur) >= max_q or (of_query[b] not in cur_f and len(cur_f) >= max_f)):
+                chunks.append(cur)
+                cur, cur_f = [], set()
+            cur.append(b)
+            cur_f.add(of_query[b])
+        if cur:
+            chunks.append(cur)
+
+        rows = self._full
+        q = self._pack_plane_queries(qf) if self._plane is not None else self._pack_queries(qf, check_norm=False)
+        thr_dev = torch.from_numpy(thr).to(self.device)
+        counts = torch.zeros(B, dtype=torch.int64, device=self.device)
+        tables = torch.zeros((B, slots), dtype=torch.int64, device=self.device)
+        scores = torch.full((B, limit), float("-inf"), dtype=torch.float32, device=self.device)
+        rows_o = torch.full((B, limit), -1, dtype=torch.int64, device=self.device)
+        for mine in chunks:
+            whole = mine == list(range(B))
+            pick = None if whole else torch.tensor(mine, device=self.device)
+            vis, foq = None, None
+            if masked:
+                vis, at = bitmaps(sorted({of_query[b] for b in mine}))
+                foq = [at[of_query[b]] for b in mine]
+            need = _native.range_scan_workspace_bytes(len(mine), self._n, limit, slots)
+            cc, ff, ss, rr = _native.range_scan(
+                q if whole else q[pick].contiguous(), rows, self._n, self.dim,
+                thr_dev if whole else thr_dev[pick].contiguous(), limit, cols, sizes, filter_of_query=foq, vis_bits=vis,
+                workspace=self._workspace("_range_ws", need))
+            if whole:
+                counts = cc.to(torch.int64)
+                if ff is not None:
+                    tables = ff.to(torch.int64)
+                if limit:
+                    scores, rows_o = ss, rr
+                break
+            counts[pick] = cc.to(torch.int64)
+            if ff is not None:
+                tables[pick] = ff.to(torch.int64)
+            if limit:
+                scores[pick], rows_o[pick] = ss, rr
+        per_key, lo = [], 0
+        for g in sizes:
+            per_key.append(tables[:, lo:lo + g + 1])
+            lo += g + 1
+        return counts, per_key, scores, rows_o, values
+
+    def range_search(self, query_embeddings, threshold, limit: int = 100, wheres=None, facets=()):
+        """Raw device range search (csrc/range.hip, include/mmrag.h mmrag_range_scan, where the definitions are): not the
+        best k but EVERYTHING at or above a score.  For query b: how many of the live rows that match wheres[b] score
+        >= threshold[b], how those rows spread over the values of each metadata key in `facets`, and the `limit` best
+        of them -- counted inside one exact scan, the [B, n] scores never written.  `threshold`: one float or one per
+        query (a cosine for unit rows).  `limit`: 0..MAX_K_DEEP; 0 = counts and facets only, with no host
+        synchronisation.  `wheres`: as filtered_search's; a filter the compiler does not cover gets no slow path, its
+        bitmap is built as every other search builds it and copied into the table, so one scan serves every filter.
+        `facets`: at most MAX_FACET_COLUMNS metadata keys, each through enable_grouping(key)'s column and value table
+        (built on first use, kept current by add and compact).
+
+        Returns (counts [B] int64, one [B, G + 1] int64 table per key: slot g = ordinal g, slot G = rows without the key,
+        scores [B, limit] float32 desc, rows [B, limit] int64 with -1 = none, one host table ordinal -> value per key);
+        tensors on the device.  A float8_e4m3fn collection scans its re-scoring plane (capacity mode raises ValueError).
+        A batch whose facet tables (4 bytes per query and slot) exceed MMRAG_RANGE_TABLE_BYTES runs as scans of fewer
+        queries, which is exact; one query that exceeds it alone raises ValueError."""
+        with self._lock:
+            return self._launch_range(query_embeddings, threshold, limit, wheres, facets)
+
+    @staticmethod
+    def _facet_lists(table, values) -> List[List[Dict[str, Any]]]:
+        """a host [B, G + 1] count table as, per query, [{"value", "count"}] of its non-zero slots: count descending,
+        then first appearance; the last slot (rows without the key) has the value None"""
+        out = []
+        for row in np.asarray(table):
+            nz = np.nonzero(row)[0]
+            nz = nz[np.argsort(-row[nz], kind="stable")]
+            out.append([{"value": values[g] if g < len(values) else None, "count": int(row[g])} for g in nz.tolist()])
+        return out
+
+    def range_query(self, query_embeddings, threshold, limit: int = 100, wheres=None, facets=(),
+                    include: Sequence[str] = ("metadatas", "documents", "distances"),
+                    check_norm: bool = True) -> Dict[str, Any]:
+        """query() for a range search (see range_search): the Chroma-shaped dict of query() for the `limit` best rows
+        at or above the cosine `threshold` in [-1, 1], plus per query "total" (how many rows pass), "truncated" (total >
+        limit) and "facets": {key: [{"value": v, "count": c}, ...]} over ALL passing rows, non-zero slots only, count
+        descending then first appearance, rows without the key as "value": None."""
+        t = np.asarray(threshold, dtype=np.float64).reshape(-1)
+        if not t.size or not bool(((t >= -1.0) & (t <= 1.0)).all()):      # false for NaN too
+            raise ValueError(f"threshold must be a cosine in [-1, 1] (got {threshold!r})")
+        facets = [facets] if isinstance(facets, str) else list(facets)
+        with self._lock, stage("search"):
+            counts, per_key, scores, rows, values = self._launch_range(query_embeddings, threshold, limit, wheres,
+                                                                       facets, check_norm)
+            tables = self._tables()
+            emb_src = self._full if "embeddings" in include else None
+        with stage("collect"):
+            out = self._collect(scores, rows, include, *tables, emb_src)
+            totals = counts.cpu().tolist()
+            out["total"] = totals
+            out["truncated"] = [c > int(limit) for c in totals]
+            lists = [self._facet_lists(tab.cpu().numpy(), vals) for tab, vals in zip(per_key, values)]
+            out["facets"] = [{key: lists[i][b] for i, key in enumerate(facets)} for b in range(len(totals))]
+            return out
 
     # ------------------------------------------------------------------ related documents (set-to-document) ----
     def _launch_related(self, sets, n_results: int, key: str, threshold, exclude, where, check_norm: bool = True):

@@ -173,6 +173,18 @@ class RelatedRequest(BaseModel):
     filter: Optional[Dict[str, Any]] = None
 
 
+class ExploreRequest(BaseModel):
+    """POST /explore: everything at or above a score -- how many stored items, how they spread over metadata values,
+    and the best of them; no generator call"""
+    query: str = Field(..., min_length=1, max_length=2000)
+    min_score: float = Field(..., gt=-1.0, le=1.0)      # a cosine
+    limit: int = Field(20, ge=0, le=100)                 # hits returned; 0 = the numbers alone
+    facets: List[Annotated[str, Field(min_length=1, max_length=200)]] = Field(default_factory=list, max_length=4)
+    filter: Optional[Dict[str, Any]] = None
+    doc_ids: Optional[Annotated[List[Annotated[str, Field(min_length=1, max_length=200)]],
+                                Field(min_length=1, max_length=64)]] = None
+
+
 # request flag -> what it needs of the embedder (method, `supports_*` check) and the 400 detail when that is missing;
 # /query checks them in this order
 MODE_NEEDS = (
@@ -245,6 +257,13 @@ RELATED_NEEDS = ("related_documents", "supports_related",
                  "(EmbeddingManager.related_documents); a float8_e4m3fn collection also needs its re-scoring plane "
                  "(MMRAG_F8_RESCORE=float16)")
 RELATED_PAIRS = 5     # the best pairs of a related document that a response carries
+
+
+# /explore: the same for range retrieval
+RANGE_NEEDS = ("range_query", "supports_range",
+               "Range retrieval is not available with this embedder: it needs a single-GPU collection "
+               "(EmbeddingManager.range_query); a float8_e4m3fn collection also needs its re-scoring plane "
+               "(MMRAG_F8_RESCORE=float16)")
 
 
 class QueryResponse(BaseModel):  # api.py:167-170
@@ -517,6 +536,21 @@ class Pipeline:
                 src[key] = value
         return {"sources": ranked}
 
+    async def explore(self, question: str, min_score: float, limit: int, facets: List[str],
+                      filter_dict: Optional[Dict], doc_ids: Optional[List[str]]) -> dict:
+        """POST /explore: how many stored items clear `min_score` for the question, their spread over the `facets`
+        keys, and the `limit` best as sources (EmbeddingManager.range_query); no generator call"""
+        self._need(RANGE_NEEDS)
+        docs_only = None if doc_ids is None else {"doc_id": {"$in": list(doc_ids)}}
+        both = {"$and": [filter_dict, docs_only]} if filter_dict and docs_only else (filter_dict or docs_only)
+        try:
+            hits = await self.embedder.range_query(question, min_score, limit=limit, facets=list(facets),
+                                                   filter_dict=both)
+        except ValueError as e:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
+        return {"total": hits["total"], "truncated": hits["truncated"], "hits": self._sources(hits),
+                "facets": hits["facets"]}
+
     async def health(self) -> dict:
         parts = {"llm_adapter": await self.llm.health_check(),
                  "embedder": {"status": "healthy",
@@ -741,6 +775,21 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
     async def related_to_texts(request: RelatedRequest):
         t0 = time.time()
         out = await pipe.related(None, request.texts, request.top_k, request.threshold, request.filter)
+        return {**out, "processing_time": time.time() - t0}
+
+    @app.post("/explore")
+    @_as_http_500
+    async def explore(request: ExploreRequest):
+        t0 = time.time()
+        if len(set(request.facets)) != len(request.facets):
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail="`facets` names a key twice")
+        if request.filter is not None:
+            try:
+                check_filter(request.filter)
+            except ValueError as e:
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
+        out = await pipe.explore(request.query, request.min_score, request.limit, request.facets, request.filter,
+                                 request.doc_ids)
         return {**out, "processing_time": time.time() - t0}
 
     @app.get("/documents/{doc_id}/related")
