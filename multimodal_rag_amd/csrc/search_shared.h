@@ -41,11 +41,15 @@ struct TopList {
             xr = nxr;
         }
     }
-    // insertion order == row order inside a lane, so "strictly greater" keeps the lower row on ties
+    // insertion order == row order inside a lane, so "strictly greater" keeps the lower row on ties.  Every slot is
+    // compared with the NEW score: the list is sorted, so from the slot that takes it on every entry moves down one.
+    // (Comparing the entry carried down instead dropped it at the first slot it ties with: a score above a run of equal
+    // scores that reached the list's end pushed out the run's lowest row, not its highest.)
     __device__ inline void insert_strict(float x, int xr) {
+        const float x_new = x;
 #pragma unroll
         for (int j = 0; j < K; ++j) {
-            const bool b = x > v[j];
+            const bool b = x_new > v[j];
             const float nv = b ? x : v[j];
             const float nx = b ? v[j] : x;
             const int nr = b ? xr : r[j];
