@@ -270,6 +270,8 @@ def _declare(lib):
     lib.mmrag_internal_related_groups_ex.argtypes = lib.mmrag_related_groups.argtypes + [c_int64]
     lib.mmrag_internal_candidate_capacity.restype = c_int64
     lib.mmrag_internal_candidate_capacity.argtypes = [c_int]
+    lib.mmrag_internal_bound_plan.restype = c_int
+    lib.mmrag_internal_bound_plan.argtypes = [c_int64, c_int, c_int64, ctypes.c_uint, c_void_p, c_void_p]
     # boosted top-k (csrc/boosted.hip); the _ex entry adds a candidate capacity and debug switches (tests, not in
     # include/mmrag.h)
     lib.mmrag_boosted_topk_workspace_bytes.restype = c_size_t
@@ -735,6 +737,17 @@ def candidate_capacity(k: int) -> int:
     """candidate slots a query of scoped_topk has for a top-k of k (csrc/candidate_select.h): with max_candidates at or
     below it the call cannot overflow and does not synchronise"""
     return int(lib().mmrag_internal_candidate_capacity(int(k)))
+
+
+def bound_plan(n: int, k: int, cap: int = 0, dbg: int = 0) -> Tuple[int, list]:
+    """(candidate slots per query, 128-row tiles of each bound stage) of boosted_topk, filtered_topk, range_scan
+    (k = limit) and recommend_topk at n rows (csrc/candidate_select.h make_bound_plan); `cap`, `dbg` as those take them"""
+    slots = ctypes.c_int64(0)
+    stages = (ctypes.c_int64 * 8)()
+    m = int(lib().mmrag_internal_bound_plan(int(n), int(k), int(cap), int(dbg), ctypes.byref(slots), stages))
+    if m < 0:
+        raise MMRagNativeError(f"bound_plan: n={n}, k={k} outside the range of the scans")
+    return int(slots.value), [int(stages[i]) for i in range(m)]
 
 
 def check_scopes(B: int, n_groups: int, scope_of_query, scope_off, scope_groups) -> int:

@@ -31,8 +31,6 @@ namespace mmrag_impl {
 namespace {
 
 constexpr int BO_MAX_QT = 64;            // query tiles of one scan launch, as scoped.hip cuts its batches
-constexpr int BO_SAMPLE0_TILES = 96;     // first bound sample: 12288 rows, the select's LDS key cache
-constexpr int BO_MAX_STAGES = 8;
 
 // debug switches of mmrag_internal_boosted_topk_ex (tests only)
 constexpr unsigned BO_DBG_NO_BOUND = 1u;  // no bound passes: tau = -inf, every live row survives the main pass
@@ -57,37 +55,7 @@ struct BoostedParams {
     long long walk;         // tiles this launch visits: tile i * T / walk for i in 0 .. walk (walk == T: every tile)
 };
 
-struct BoostedPlan {
-    long long cap;          // candidate slots per query
-    int n_stages;
-    long long stage_tiles[BO_MAX_STAGES];
-};
-
-// search_deep.hip's make_deep_plan in 128-row tiles.  The stages are planned against the capacity of k itself: a
-// smaller cap_override (tests) only makes the slots fewer, so that queries overflow.
-BoostedPlan make_boosted_plan(long long n, int k, long long cap_override, unsigned dbg) {
-    BoostedPlan pl;
-    const long long C = candidate_capacity(k);
-    pl.cap = cap_override > 0 && cap_override < C ? cap_override : C;
-    pl.n_stages = 0;
-    if (n <= C || (dbg & BO_DBG_NO_BOUND)) return pl;   // every live row fits: no bound needed
-    const long long n_tiles = (n + PT - 1) / PT;
-    // main-pass survivors ~ k * n / m for a bound from m sampled rows: aim at C / 4
-    const long long target_rows = (4LL * k * n + C - 1) / C;
-    const long long target = (target_rows + PT - 1) / PT;
-    long long t = BO_SAMPLE0_TILES < n_tiles ? BO_SAMPLE0_TILES : n_tiles;
-    for (;;) {
-        pl.stage_tiles[pl.n_stages++] = t;
-        if (t >= target || pl.n_stages == BO_MAX_STAGES) break;
-        // the next sample's survivors ~ k * m' / m must fit C / 4 as well
-        long long nt = t * C / (4LL * k);
-        if (nt > target) nt = target;
-        if (nt > n_tiles) nt = n_tiles;
-        if (nt <= t) break;
-        t = nt;
-    }
-    return pl;
-}
+static_assert(BOUND_TILE_ROWS == PT, "the bound stages are planned in this scan's tiles");
 
 template <int DT>
 __global__ __launch_bounds__(256, 2) void boosted_scan_kernel(const BoostedParams p) {
@@ -269,10 +237,13 @@ int mmrag_internal_boosted_topk_ex(const void *q, const void *rows, int B, int64
         return candidate_fill_empty(out_scores, (long long *)out_rows, B, k, s);
     }
 
-    const BoostedPlan pl = make_boosted_plan(n, k, cap_override, dbg);
+    const BoundPlan pl = make_bound_plan(n, k, cap_override, (dbg & BO_DBG_NO_BOUND) != 0u);
     const CandWs wl = candidate_ws_layout(B, pl.cap, n, true);
-    if (!workspace || workspace_bytes < wl.total) {
-        set_error("boosted_topk: workspace %zu bytes < required %zu", workspace_bytes, wl.total);
+    size_t ws_need = wl.total;
+    const CandWs wst = pl.n_stages > 0 ? bound_stage_layout(B, k, n, wl, &ws_need) : wl;
+    const long long stage_cap = pl.n_stages > 0 ? candidate_capacity(k) : pl.cap;
+    if (!workspace || workspace_bytes < ws_need) {
+        set_error("boosted_topk: workspace %zu bytes < required %zu", workspace_bytes, ws_need);
         return MMRAG_EWORKSPACE;
     }
     if (((uintptr_t)workspace % 16) != 0) {
@@ -333,8 +304,10 @@ int mmrag_internal_boosted_topk_ex(const void *q, const void *rows, int B, int64
     }
     for (int st = 0; st < pl.n_stages; ++st) {
         MMRAG_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)B * sizeof(unsigned), s));
-        if (int e = produce(0, B, pl.stage_tiles[st], p.cand_s, p.cand_r, cnt, pl.cap)) return e;
-        deep_select_kernel<<<B, SEL_THREADS, 0, s>>>(p.cand_s, p.cand_r, cnt, pl.cap, k, 0, 1, nullptr, nullptr, tau);
+        float *st_s = (float *)(ws + wst.off_bs);
+        int *st_r = (int *)(ws + wst.off_br);
+        if (int e = produce(0, B, pl.stage_tiles[st], st_s, st_r, cnt, stage_cap)) return e;
+        deep_select_kernel<<<B, SEL_THREADS, 0, s>>>(st_s, st_r, cnt, stage_cap, k, 0, 1, nullptr, nullptr, tau);
         MMRAG_CHECK_HIP(hipGetLastError());
     }
     // 2. main pass over every tile, 3. select, 4. each query with more survivors than slots alone, same tau_q
@@ -353,6 +326,20 @@ int mmrag_internal_boosted_topk_ex(const void *q, const void *rows, int B, int64
         MMRAG_CHECK_HIP(hipGetLastError());
     }
     return MMRAG_OK;
+}
+
+// The bound plan of mmrag_boosted_topk, mmrag_filtered_topk, mmrag_range_scan (k = limit) and mmrag_recommend_topk
+// (candidate_select.h's make_bound_plan; dbg & 1 = no bound passes): *slots = the candidate slots per query,
+// stage_tiles[0 .. return value) = the 128-row tiles of each bound stage.  The tests restate it and compare.  Exported
+// for them, deliberately absent from include/mmrag.h.
+int mmrag_internal_bound_plan(int64_t n, int k, int64_t cap_override, unsigned dbg, int64_t *slots,
+                              int64_t stage_tiles[8]) {
+    static_assert(BOUND_MAX_STAGES == 8, "the signature's array");
+    if (n < 0 || k < 1 || k > MMRAG_MAX_K_DEEP || !slots || !stage_tiles) return -1;
+    const BoundPlan pl = make_bound_plan(n, k, cap_override, (dbg & BO_DBG_NO_BOUND) != 0u);
+    *slots = pl.cap;
+    for (int i = 0; i < pl.n_stages; ++i) stage_tiles[i] = pl.stage_tiles[i];
+    return pl.n_stages;
 }
 
 int mmrag_boosted_topk(const void *q, const void *rows, int B, int64_t n, int d, int64_t ld, int dtype, int k,

@@ -16,6 +16,46 @@ inline long long candidate_capacity(int k) {
     return (long long)mmrag::align_up((size_t)(32LL * k > 16384 ? 32LL * k : 16384), 256);
 }
 
+// ---- the bound stages of a scan over 128-row tiles (boosted.hip, filtered.hip, range.hip, recommend.hip) -------------
+constexpr int BOUND_TILE_ROWS = 128;     // pair_tile.h's PT
+constexpr int BOUND_SAMPLE0_TILES = 96;  // first bound sample: 12288 rows, the select's LDS key cache
+constexpr int BOUND_MAX_STAGES = 8;
+
+struct BoundPlan {
+    long long cap;          // candidate slots per query
+    int n_stages;
+    long long stage_tiles[BOUND_MAX_STAGES];
+};
+
+// search_deep.hip's make_deep_plan in 128-row tiles: a scan first runs over a strided sample of whole tiles (stage i
+// visits stage_tiles[i] of them) and deep_select_kernel's bound mode raises tau_q to the k-th best sampled score; the
+// k-th best of ANY subset of a query's candidates is at most its true k-th, whatever a prior, a filter or a score
+// function does, so the plan is the same for all of them.  The stages are planned against the capacity of k itself: a
+// smaller cap_override (tests) only makes the slots fewer, so that queries overflow.  `no_bound`: no stages (tests).
+inline BoundPlan make_bound_plan(long long n, int k, long long cap_override, bool no_bound) {
+    BoundPlan pl;
+    const long long C = candidate_capacity(k);
+    pl.cap = cap_override > 0 && cap_override < C ? cap_override : C;
+    pl.n_stages = 0;
+    if (n <= C || no_bound) return pl;   // every row fits: no bound needed
+    const long long n_tiles = (n + BOUND_TILE_ROWS - 1) / BOUND_TILE_ROWS;
+    // main-pass survivors ~ k * n / m for a bound from m sampled rows: aim at C / 4
+    const long long target_rows = (4LL * k * n + C - 1) / C;
+    const long long target = (target_rows + BOUND_TILE_ROWS - 1) / BOUND_TILE_ROWS;
+    long long t = BOUND_SAMPLE0_TILES < n_tiles ? BOUND_SAMPLE0_TILES : n_tiles;
+    for (;;) {
+        pl.stage_tiles[pl.n_stages++] = t;
+        if (t >= target || pl.n_stages == BOUND_MAX_STAGES) break;
+        // the next sample's survivors ~ k * m' / m must fit C / 4 as well
+        long long nt = t * C / (4LL * k);
+        if (nt > target) nt = target;
+        if (nt > n_tiles) nt = n_tiles;
+        if (nt <= t) break;
+        t = nt;
+    }
+    return pl;
+}
+
 struct CandWs {
     size_t off_cnt, off_one_cnt, off_floats, off_bs, off_br, off_os, off_or, total;
 };
@@ -35,6 +75,18 @@ inline CandWs candidate_ws_layout(int B, long long cap, long long n, bool per_qu
     w.off_os = mmrag::align_up(w.off_br + (size_t)B * cap * sizeof(int), 256);
     w.off_or = mmrag::align_up(w.off_os + (size_t)n * sizeof(float), 256);
     w.total = mmrag::align_up(w.off_or + (size_t)n * sizeof(int), 256);
+    return w;
+}
+
+// The buffers of a bound stage: candidate_capacity(k) slots per query, what the stages were planned against, whatever
+// cap_override says.  The override (tests) makes the MAIN pass's slots fewer, so that queries overflow and are produced
+// again under the tau the stages found; a stage that appended into fewer than k slots could never hold k candidates
+// and would leave tau where it started.  Counters and per-query floats lie where the main pass's layout has them (they
+// do not depend on the slots), the scores start at the same offset, and a stage is over before the main pass begins:
+// a call with stages needs the larger of the two layouts, which is what the *_workspace_bytes functions return.
+inline CandWs bound_stage_layout(int B, int k, long long n, const CandWs &main_layout, size_t *total) {
+    const CandWs w = candidate_ws_layout(B, candidate_capacity(k), n, true);
+    *total = w.total > main_layout.total ? w.total : main_layout.total;
     return w;
 }
 

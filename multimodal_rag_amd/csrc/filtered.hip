@@ -22,11 +22,12 @@
 //      A filter can pass most of the collection, so when n exceeds the candidate slots the scan first runs over a
 //      strided sample of whole tiles and deep_select_kernel's bound mode sets tau_q to the k-th best of the VISIBLE
 //      sampled rows: the k-th best of any subset of a query's visible rows is at most its true k-th, whatever the
-//      filter (tau_q stays -inf while fewer than k visible rows were sampled).  Stages as boosted.hip plans them.
+//      filter (tau_q stays -inf while fewer than k visible rows were sampled).  Stages: candidate_select.h's
+//      make_bound_plan.
 //   3. select and overflow: candidate_select.h's driver, unchanged.
 // The K order is slab_step's, so a score's bits depend on the query row, the stored row and d alone and equal
 // mmrag_scoped_topk's: not on the batch, the filters, the grid, tau or whether bound passes ran.
-// The scan body, the union kernel, the plan and the split into launches are masked_scan.h's, shared with range.hip.
+// The scan body, the union kernel and the split into launches are masked_scan.h's, shared with range.hip.
 #include "masked_scan.h"
 
 using namespace mmrag;
@@ -226,9 +227,12 @@ int mmrag_internal_filtered_topk_ex(const void *q, const void *rows, int B, int6
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) return candidate_fill_empty(out_scores, (long long *)out_rows, B, k, s);
 
-    const FilteredPlan pl = make_filtered_plan(n, k, cap_override, dbg);
+    const BoundPlan pl = make_bound_plan(n, k, cap_override, (dbg & FI_DBG_NO_BOUND) != 0u);
     const CandWs wl = candidate_ws_layout(B, pl.cap, n, true);
-    const size_t need = wl.total + filtered_union_bytes(B, n);
+    size_t sel_total = wl.total;
+    const CandWs wst = pl.n_stages > 0 ? bound_stage_layout(B, k, n, wl, &sel_total) : wl;
+    const long long stage_cap = pl.n_stages > 0 ? candidate_capacity(k) : pl.cap;
+    const size_t need = sel_total + filtered_union_bytes(B, n);
     if (!workspace || workspace_bytes < need) {
         set_error("filtered_topk: workspace %zu bytes < required %zu", workspace_bytes, need);
         return MMRAG_EWORKSPACE;
@@ -241,7 +245,7 @@ int mmrag_internal_filtered_topk_ex(const void *q, const void *rows, int B, int6
     char *ws = (char *)workspace;
     unsigned *cnt = (unsigned *)(ws + wl.off_cnt);
     float *tau = (float *)(ws + wl.off_floats);
-    unsigned *uni = (unsigned *)(ws + wl.total);
+    unsigned *uni = (unsigned *)(ws + sel_total);      // behind the stages' buffers too: the unions serve every pass
     FilteredParams p;
     p.rows = (const char *)rows;
     p.q = (const char *)q;
@@ -301,8 +305,10 @@ int mmrag_internal_filtered_topk_ex(const void *q, const void *rows, int B, int6
     }
     for (int st = 0; st < pl.n_stages; ++st) {
         MMRAG_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)B * sizeof(unsigned), s));
-        if (int e = produce(0, B, pl.stage_tiles[st], uni, p.cand_s, p.cand_r, cnt, pl.cap, nullptr)) return e;
-        deep_select_kernel<<<B, SEL_THREADS, 0, s>>>(p.cand_s, p.cand_r, cnt, pl.cap, k, 0, 1, nullptr, nullptr, tau);
+        float *st_s = (float *)(ws + wst.off_bs);
+        int *st_r = (int *)(ws + wst.off_br);
+        if (int e = produce(0, B, pl.stage_tiles[st], uni, st_s, st_r, cnt, stage_cap, nullptr)) return e;
+        deep_select_kernel<<<B, SEL_THREADS, 0, s>>>(st_s, st_r, cnt, stage_cap, k, 0, 1, nullptr, nullptr, tau);
         MMRAG_CHECK_HIP(hipGetLastError());
     }
     if (items_issued) MMRAG_CHECK_HIP(hipMemsetAsync(items_issued, 0, sizeof(uint64_t), s));

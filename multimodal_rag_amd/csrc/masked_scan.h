@@ -1,7 +1,7 @@
 // The masked scan shared by the filtered top-k (filtered.hip) and the range scan (range.hip): Q . X^T with pair_tile.h's
 // body over persistent workgroups, each query seeing only the rows of ITS bitmap, and what surrounds it on the host --
-// the bitmap geometry, the union bitmaps of a query tile, the plan of the bound passes and the split of a batch into
-// launches of at most FI_MAX_QT query tiles.  The kernels keep what differs: the epilogue.  Internal, gfx950 only.
+// the bitmap geometry, the union bitmaps of a query tile and the split of a batch into launches of at most FI_MAX_QT
+// query tiles.  The kernels keep what differs: the epilogue.  Internal, gfx950 only.
 //
 // The scan: a 128-row tile of stored rows as A and a 128-query tile as B; rows past n and queries past B read as zero
 // through the buffer descriptor.  Before anything is fetched all four waves read the tile's four words of every query
@@ -21,8 +21,6 @@ namespace mmrag_impl {
 namespace {
 
 constexpr int FI_MAX_QT = 64;            // query tiles of one scan launch: their "wanted" flags are one 64-bit mask
-constexpr int FI_SAMPLE0_TILES = 96;     // first bound sample: 12288 rows, the select's LDS key cache
-constexpr int FI_MAX_STAGES = 8;
 
 // debug switches of the _ex entry points (tests only)
 constexpr unsigned FI_DBG_NO_BOUND = 1u;  // no bound passes: tau stays at its start, every survivor of it is a candidate
@@ -47,35 +45,7 @@ struct MaskedScanParams {
     unsigned long long *items;   // optional: += the (row tile, query tile) items this launch issues
 };
 
-struct FilteredPlan {
-    long long cap;          // candidate slots per query
-    int n_stages;
-    long long stage_tiles[FI_MAX_STAGES];
-};
-
-// boosted.hip's make_boosted_plan: the argument there (survivors ~ k n / m for a bound from m sampled rows) holds for the
-// visible rows of any filter, with fewer survivors the fewer rows a filter passes.
-inline FilteredPlan make_filtered_plan(long long n, int k, long long cap_override, unsigned dbg) {
-    FilteredPlan pl;
-    const long long C = candidate_capacity(k);
-    pl.cap = cap_override > 0 && cap_override < C ? cap_override : C;
-    pl.n_stages = 0;
-    if (n <= C || (dbg & FI_DBG_NO_BOUND)) return pl;   // every row fits: no bound needed
-    const long long n_tiles = (n + PT - 1) / PT;
-    const long long target_rows = (4LL * k * n + C - 1) / C;
-    const long long target = (target_rows + PT - 1) / PT;
-    long long t = FI_SAMPLE0_TILES < n_tiles ? FI_SAMPLE0_TILES : n_tiles;
-    for (;;) {
-        pl.stage_tiles[pl.n_stages++] = t;
-        if (t >= target || pl.n_stages == FI_MAX_STAGES) break;
-        long long nt = t * C / (4LL * k);
-        if (nt > target) nt = target;
-        if (nt > n_tiles) nt = n_tiles;
-        if (nt <= t) break;
-        t = nt;
-    }
-    return pl;
-}
+static_assert(BOUND_TILE_ROWS == PT, "the bound stages are planned in this scan's tiles");
 
 // uni[qt, :] = OR of vis[f, :] over the filters f of queries 128 qt .. 128 qt + 127 (a run of equal filters is read
 // once; a filter outside 0..F-1 sees nothing, here and in the scan).  Grid (words / 256, query tiles).

@@ -343,9 +343,9 @@ struct MsPlan {
     long long stage_chunks[MS_MAX_STAGES];
 };
 
-// boosted.hip's make_boosted_plan counted in items (survivors ~ k n / m for a bound from m sampled items), then turned
-// into whole chunks under the assumption that items are spread evenly over the plane.  The bound is valid whatever the
-// sample holds; only the number of survivors depends on it.
+// candidate_select.h's make_bound_plan counted in items (survivors ~ k n / m for a bound from m sampled items), then
+// turned into whole chunks under the assumption that items are spread evenly over the plane.  The bound is valid
+// whatever the sample holds; only the number of survivors depends on it.
 MsPlan make_ms_plan(long long n_items, long long n_chunks, int k, long long cap_override, unsigned dbg) {
     MsPlan pl;
     const long long C = candidate_capacity(k);

@@ -152,11 +152,15 @@ int mmrag_internal_range_scan_ex(const void *q, const void *rows, int B, int64_t
     if (n_facets > 0) MMRAG_CHECK_HIP(hipMemsetAsync(out_facets, 0, (size_t)B * (size_t)stride * sizeof(unsigned), s));
     if (n == 0) return limit > 0 ? candidate_fill_empty(out_scores, (long long *)out_rows, B, limit, s) : MMRAG_OK;
 
-    FilteredPlan pl;
+    BoundPlan pl;
     pl.cap = 0;
     pl.n_stages = 0;
-    if (limit > 0) pl = make_filtered_plan(n, limit, cap_override, dbg);
-    const size_t sel_bytes = range_select_bytes(B, n, limit, pl.cap);
+    if (limit > 0) pl = make_bound_plan(n, limit, cap_override, (dbg & FI_DBG_NO_BOUND) != 0u);
+    size_t sel_bytes = range_select_bytes(B, n, limit, pl.cap);
+    // the bound stages append into the slots of `limit` itself (candidate_select.h bound_stage_layout)
+    const long long stage_cap = pl.n_stages > 0 ? candidate_capacity(limit) : pl.cap;
+    CandWs wst = {};
+    if (pl.n_stages > 0) wst = bound_stage_layout(B, limit, n, candidate_ws_layout(B, pl.cap, n, true), &sel_bytes);
     const size_t need = sel_bytes + (vis_bits != nullptr ? filtered_union_bytes(B, n) : 0);
     if (need > 0 && (!workspace || workspace_bytes < need)) {
         set_error("range_scan: workspace %zu bytes < required %zu", workspace_bytes, need);
@@ -245,8 +249,10 @@ int mmrag_internal_range_scan_ex(const void *q, const void *rows, int B, int64_t
     }
     for (int st = 0; st < pl.n_stages; ++st) {
         MMRAG_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)B * sizeof(unsigned), s));
-        if (int e = produce(0, B, pl.stage_tiles[st], uni, false, cand_s, cand_r, cnt, pl.cap)) return e;
-        deep_select_kernel<<<B, SEL_THREADS, 0, s>>>(cand_s, cand_r, cnt, pl.cap, limit, 0, 1, nullptr, nullptr, tau);
+        float *st_s = (float *)(ws + wst.off_bs);
+        int *st_r = (int *)(ws + wst.off_br);
+        if (int e = produce(0, B, pl.stage_tiles[st], uni, false, st_s, st_r, cnt, stage_cap)) return e;
+        deep_select_kernel<<<B, SEL_THREADS, 0, s>>>(st_s, st_r, cnt, stage_cap, limit, 0, 1, nullptr, nullptr, tau);
         MMRAG_CHECK_HIP(hipGetLastError());
     }
     // 3. main pass over every tile (the one that counts), select, and each query with more survivors than slots alone

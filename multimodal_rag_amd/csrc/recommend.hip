@@ -5,7 +5,7 @@
 // formed INSIDE one exact scan.  With negatives the winners are often far down the positive ranking -- everything near
 // the top sits next to a negative -- so the penalty cannot be applied to a finished list.
 //
-//   1. bound passes, only when n exceeds the candidate capacity: boosted.hip's plan unchanged (whole 128-row tiles spread
+//   1. bound passes, only when n exceeds the candidate capacity: candidate_select.h's plan (whole 128-row tiles spread
 //      evenly over the collection, stages growing), every live final >= tau_g appended; deep_select_kernel in its bound
 //      mode then sets tau_g = max(tau_g, the k-th best of those).  The k-th best final of ANY subset of live rows is at
 //      most the true k-th final whatever the score function is, so the argument boosted.hip gives for its prior carries
@@ -43,8 +43,6 @@ namespace {
 constexpr int RC_E = MMRAG_MAX_RECOMMEND_EXAMPLES;   // example slots of a request
 constexpr int RC_REQ_TILE = PT / RC_E;               // requests of a 128-example tile
 constexpr int RC_MAX_ET = 64;            // example tiles of one scan launch (512 requests), as boosted.hip cuts its batches
-constexpr int RC_SAMPLE0_TILES = 96;     // first bound sample: 12288 rows, the select's LDS key cache
-constexpr int RC_MAX_STAGES = 8;
 static_assert(RC_E == 16 && RC_REQ_TILE == 8, "a request is one 16-row MFMA block");
 
 // debug switches of mmrag_internal_recommend_topk_ex (tests only)
@@ -70,37 +68,7 @@ struct RecommendParams {
     long long walk;         // tiles this launch visits: tile i * T / walk for i in 0 .. walk (walk == T: every tile)
 };
 
-struct RecommendPlan {
-    long long cap;          // candidate slots per request
-    int n_stages;
-    long long stage_tiles[RC_MAX_STAGES];
-};
-
-// boosted.hip's make_boosted_plan: the stages are planned against the capacity of k itself, a smaller cap_override
-// (tests) only makes the slots fewer, so that requests overflow
-RecommendPlan make_recommend_plan(long long n, int k, long long cap_override, unsigned dbg) {
-    RecommendPlan pl;
-    const long long C = candidate_capacity(k);
-    pl.cap = cap_override > 0 && cap_override < C ? cap_override : C;
-    pl.n_stages = 0;
-    if (n <= C || (dbg & RC_DBG_NO_BOUND)) return pl;   // every live row fits: no bound needed
-    const long long n_tiles = (n + PT - 1) / PT;
-    // main-pass survivors ~ k * n / m for a bound from m sampled rows: aim at C / 4
-    const long long target_rows = (4LL * k * n + C - 1) / C;
-    const long long target = (target_rows + PT - 1) / PT;
-    long long t = RC_SAMPLE0_TILES < n_tiles ? RC_SAMPLE0_TILES : n_tiles;
-    for (;;) {
-        pl.stage_tiles[pl.n_stages++] = t;
-        if (t >= target || pl.n_stages == RC_MAX_STAGES) break;
-        // the next sample's survivors ~ k * m' / m must fit C / 4 as well
-        long long nt = t * C / (4LL * k);
-        if (nt > target) nt = target;
-        if (nt > n_tiles) nt = n_tiles;
-        if (nt <= t) break;
-        t = nt;
-    }
-    return pl;
-}
+static_assert(BOUND_TILE_ROWS == PT, "the bound stages are planned in this scan's tiles");
 
 // x in the lanes below 32 and y in the lanes from 32 on, each joined with the same value of the lane 32 away:
 // v_permlane32_swap trades the upper half of x with the lower half of y, so max of the pair is, in a lower lane l,
@@ -391,10 +359,13 @@ int mmrag_internal_recommend_topk_ex(const void *examples, const int8_t *sign, c
         return finish();     // every row is -1: all padding
     }
 
-    const RecommendPlan pl = make_recommend_plan(n, k, cap_override, dbg);
+    const BoundPlan pl = make_bound_plan(n, k, cap_override, (dbg & RC_DBG_NO_BOUND) != 0u);
     const CandWs wl = candidate_ws_layout(R, pl.cap, n, true);
-    if (!workspace || workspace_bytes < wl.total) {
-        set_error("recommend_topk: workspace %zu bytes < required %zu", workspace_bytes, wl.total);
+    size_t ws_need = wl.total;
+    const CandWs wst = pl.n_stages > 0 ? bound_stage_layout(R, k, n, wl, &ws_need) : wl;
+    const long long stage_cap = pl.n_stages > 0 ? candidate_capacity(k) : pl.cap;
+    if (!workspace || workspace_bytes < ws_need) {
+        set_error("recommend_topk: workspace %zu bytes < required %zu", workspace_bytes, ws_need);
         return MMRAG_EWORKSPACE;
     }
     if (((uintptr_t)workspace % 16) != 0) {
@@ -457,8 +428,10 @@ int mmrag_internal_recommend_topk_ex(const void *examples, const int8_t *sign, c
     }
     for (int st = 0; st < pl.n_stages; ++st) {
         MMRAG_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)R * sizeof(unsigned), s));
-        if (int e = produce(0, R, pl.stage_tiles[st], p.cand_s, p.cand_r, cnt, pl.cap)) return e;
-        deep_select_kernel<<<R, SEL_THREADS, 0, s>>>(p.cand_s, p.cand_r, cnt, pl.cap, k, 0, 1, nullptr, nullptr, tau);
+        float *st_s = (float *)(ws + wst.off_bs);
+        int *st_r = (int *)(ws + wst.off_br);
+        if (int e = produce(0, R, pl.stage_tiles[st], st_s, st_r, cnt, stage_cap)) return e;
+        deep_select_kernel<<<R, SEL_THREADS, 0, s>>>(st_s, st_r, cnt, stage_cap, k, 0, 1, nullptr, nullptr, tau);
         MMRAG_CHECK_HIP(hipGetLastError());
     }
     // 2. main pass over every tile, 3. select, 4. each request with more survivors than slots alone, same tau_g

@@ -9,7 +9,11 @@ oracle.search_oracle.cosine_topk on the support columns (`expected`), compared w
 
 C is the CU count the library plans with (the sample pre-pass covers the first 256 * C rows, a walk workgroup's static
 tiles are 64 * C rows apart); k the requested depth.  Row layouts (`zero_rows_layout`, `plateau_high_rows`,
-`planted_layout`) are functions of (n, k, C) alone, so a test can name the rows it expects without the data."""
+`planted_layout`) are functions of (n, k, C) alone, so a test can name the rows it expects without the data.
+
+The scan family (tests/test_scan_regimes_*.py: the kernels that run pair_tile.h's body over 128-row tiles) has a part of
+its own below: the bound plan restated (`bound_plan`, `sample_tiles`), planted layouts that are functions of
+(n, k, the plan's stages) alone (`planted_tile_layout`), and two generators with integer priors for the boosted scan."""
 import numpy as np
 
 from oracle import search_oracle as O
@@ -211,6 +215,146 @@ def planted(where, n, B, k, C, f8=False):
     return q, c
 
 
+# ---- the scan family (tests/test_scan_regimes_*.py): 128-row tiles, strided bound samples -----------------------------
+P_TILE = 128             # rows per tile of pair_tile.h's body
+SAMPLE0_TILES = 96       # tiles of the first bound stage (csrc/candidate_select.h)
+MAX_STAGES = 8
+
+
+def candidate_capacity(k):
+    """csrc/candidate_select.h: candidate slots per query for a top-k of k"""
+    return -(-max(32 * k, 16384) // 256) * 256
+
+
+def bound_plan(n, k, cap=0, no_bound=False):
+    """csrc/candidate_select.h make_bound_plan restated: (candidate slots per query, tiles of each bound stage)"""
+    C = candidate_capacity(k)
+    slots = cap if 0 < cap < C else C
+    stages = []
+    if n <= C or no_bound:
+        return slots, stages
+    n_tiles = -(-n // P_TILE)
+    target = -(-(-(-4 * k * n // C)) // P_TILE)
+    t = min(SAMPLE0_TILES, n_tiles)
+    while True:
+        stages.append(t)
+        if t >= target or len(stages) == MAX_STAGES:
+            break
+        nt = min(t * C // (4 * k), target, n_tiles)
+        if nt <= t:
+            break
+        t = nt
+    return slots, stages
+
+
+def sample_tiles(n, stages):
+    """the 128-row tiles the bound stages visit: a stage of w tiles visits tile i * T // w for i in 0 .. w - 1
+    (boosted_scan_kernel, masked_scan_body)"""
+    T = -(-n // P_TILE)
+    return {i * T // w for w in stages for i in range(w)}
+
+
+def layout_stages(n, stages):
+    """the stages a tile layout is planted against: the plan's, or, for a collection short enough to have none, one
+    nominal stage over every other tile, so that the same rows are placed at every n"""
+    return list(stages) or [(-(-n // P_TILE) + 1) // 2]
+
+
+PLANTED_TILES = ("unsampled", "sampled", "one_lane", "one_pair_tile")
+ONE_LANE_MAX_K = 13      # k + 3 winners in the 16 rows of one lane
+
+
+def lane_rows(tile, wm, g4):
+    """the 16 rows of a tile that one lane of pair_tile.h's body holds for each of its query columns"""
+    return np.array([tile * P_TILE + 64 * wm + 16 * a + 4 * g4 + r for a in range(4) for r in range(4)], dtype=np.int64)
+
+
+def planted_tile_layout(where, n, k, stages):
+    """(rows ascending, level of each row) on 128-row tiles, a function of (n, k, stages) alone; k + 3 rows (one_pair_tile:
+    at most the rows of its tile).  Levels as in planted_layout; `sampled` has two rows on the k-th level."""
+    T = -(-n // P_TILE)
+    st = layout_stages(n, stages)
+    every, first = sample_tiles(n, st), sample_tiles(n, st[:1])
+    g = np.random.default_rng(k + len(where))
+    m = k + 3
+    levels = None
+    if where == "unsampled":           # no stage sees a winner: tau stays at what the background gives
+        free = sorted(set(range(T)) - every)
+        assert T - 1 in free and m <= n - (T - len(free)) * P_TILE
+        after = next(t for t in free if t - 1 in every)
+        must = {n - 1, (T - 1) * P_TILE, after * P_TILE}
+        pool = np.concatenate([np.arange(t * P_TILE, min((t + 1) * P_TILE, n)) for t in free])
+        pick = pool[(np.arange(2 * m) * 2 + 1) * pool.size // (4 * m)]
+        rows = set(must)
+        for r in list(pick[::2]) + list(pick[1::2]) + list(pool):
+            if len(rows) == m:
+                break
+            rows.add(int(r))
+        rows = np.array(sorted(rows), dtype=np.int64)
+    elif where == "sampled":           # stage 1 sees the whole top-k; the k-th level ties with a row of the last tile
+        assert T - 1 not in every and k >= 2
+        pool = np.concatenate([np.arange(t * P_TILE, min((t + 1) * P_TILE, n)) for t in sorted(first)])
+        assert m - 1 <= pool.size
+        inner = np.unique(pool[(np.arange(m - 1) * 2 + 1) * pool.size // (2 * (m - 1))])
+        inner = np.array(sorted(set(inner.tolist()) | set(pool[: m - 1 - inner.size + 8].tolist()))[: m - 1], dtype=np.int64)
+        assert inner.size == m - 1
+        high = (T - 1) * P_TILE + (n - 1 - (T - 1) * P_TILE) // 2
+        rows = np.concatenate([inner, [high]])
+        # ranks: k - 1 distinct levels above, two rows on level 3 (the k-th), levels 2 and 1 below
+        lv = g.permutation(np.array([1, 2] + list(range(4, k + 3))))
+        tied = int(g.integers(0, m - 1))
+        levels = np.concatenate([lv[:tied], [3], lv[tied:], [3]])
+    elif where == "one_lane":
+        assert k <= ONE_LANE_MAX_K
+        tile = T // 2
+        wm = 1 if n - tile * P_TILE >= P_TILE else 0
+        lane = lane_rows(tile, wm, 2)
+        assert lane.max() < n
+        rows = np.sort(lane[g.permutation(16)[:m]])
+    elif where == "one_pair_tile":
+        tile = T // 2
+        width = min(P_TILE, n - tile * P_TILE)
+        m = min(m, width)
+        off = {min(63, width - 2), min(64, width - 1)} if width > 64 else {0, width - 1}   # both wm halves
+        for o in g.permutation(width):
+            if len(off) == m:
+                break
+            off.add(int(o))
+        rows = tile * P_TILE + np.array(sorted(off), dtype=np.int64)
+    else:
+        raise ValueError(where)
+    rows = np.asarray(rows, dtype=np.int64)
+    if levels is None:
+        levels = g.permutation(rows.size) + 1
+    assert rows.size == m and np.unique(rows).size == m and rows.min() >= 0 and rows.max() < n
+    assert np.all(np.diff(rows) > 0) and levels.size == m
+    return rows, np.asarray(levels, dtype=np.int64)
+
+
+def planted_tiles(where, n, B, k, stages):
+    q, c = negative(n, B)
+    rows, levels = planted_tile_layout(where, n, k, stages)
+    c[rows] = staircase(levels)
+    return q, c
+
+
+# ---- boosted only: integer priors, weights from {-1, 0, 1, 2}: the fmaf is exact ---------------------------------------
+def cancelled(n, B):
+    """(q, c, prior, weight): the `rising` corpus with prior = -block and weight = the query's multiplier: every final is
+    0, a plateau that only the epilogue makes"""
+    q, c = rising(n, B)
+    prior = -(np.arange(n) // 32).astype(np.float32)
+    return q, c, prior, np.ascontiguousarray(q[:, 0])
+
+
+def prior_only(n, B):
+    """(q, c, prior, weight): the `plateau` corpus (every dot of a query equal) with a prior that rises in steps of 32
+    rows; weight -1 makes the final fall with the row number, 0 leaves the plateau, 1 and 2 make it rise"""
+    q, c = plateau(n, B)
+    prior = (np.arange(n) // 32).astype(np.float32)
+    return q, c, prior, ((np.arange(B) % 4) - 1).astype(np.float32)
+
+
 # ---- band: unit rows around one direction, the only generator that is not a lattice -------------------------------------
 BAND = (0.55, 0.98)     # all cosines, about
 SIGMA2 = 0.2
@@ -231,14 +375,16 @@ def band(n, B, ncols, seed=5):
 
 
 # ---- one entry point ---------------------------------------------------------------------------------------------------
-LATTICE = ("negative", "negative_with_zero_rows", "plateau", "plateau_two_level", "rising", "falling") + tuple(
-    "planted:" + w for w in PLANTED)
+BASE = ("negative", "negative_with_zero_rows", "plateau", "plateau_two_level", "rising", "falling")
+LATTICE = BASE + tuple("planted:" + w for w in PLANTED)
+SCAN_LATTICE = BASE + tuple("planted:" + w for w in PLANTED_TILES)     # the scan family's exact regimes
 REGIMES = LATTICE + ("band",)
 NEEDS_LONG_SHARD = ("planted:one_walker", "planted:tail", "planted:sample_edge")   # no meaning below 256 * C rows
 
 
-def make(regime, n, B, k, C, f8=False, ncols=NSUP):
-    """(q, c, alive or None) of a regime"""
+def make(regime, n, B, k, C, f8=False, ncols=NSUP, stages=None):
+    """(q, c, alive or None) of a regime; `stages` (a bound_plan's) selects the scan family's planted layouts, which
+    take the place of C"""
     if regime == "negative":
         return negative(n, B) + (None,)
     if regime == "negative_with_zero_rows":
@@ -249,6 +395,8 @@ def make(regime, n, B, k, C, f8=False, ncols=NSUP):
         return plateau(n, B, k, C, two_level=True) + (None,)
     if regime in ("rising", "falling"):
         return rising(n, B, falling=regime == "falling", f8=f8) + (None,)
+    if regime.startswith("planted:") and regime.split(":")[1] in PLANTED_TILES:
+        return planted_tiles(regime.split(":")[1], n, B, k, stages or []) + (None,)
     if regime.startswith("planted:"):
         return planted(regime.split(":")[1], n, B, k, C, f8) + (None,)
     if regime == "band":
