@@ -10,8 +10,9 @@
 //      final, whatever the prior looks like, so tau_q stays a valid lower bound (-inf while fewer than k rows were seen).
 //      The stages grow as search_deep.hip's do.
 //   2. main pass: every tile, every live final >= tau_q appended as (final, local row) through the query's counter.
-//   3. select and overflow: candidate_select.h's driver, unchanged; an overflowed query is produced again alone with the
-//      same tau_q into n slots.
+//   3. select and overflow: an overflowed query is produced again alone with the same tau_q into n slots.
+// The sequence itself -- plan, workspace, stages, main pass, select, re-runs -- is candidate_select.h's
+// bounded_scan_select; this file supplies the producer.
 //
 // scan kernel: scoped.hip's scan without the scope test.  Q . X^T with pair_tile.h's body, a 128-row tile of stored rows
 // as A and a 128-query tile as B; rows past n and queries past B read as zero through the buffer descriptor.  Workgroups
@@ -30,8 +31,6 @@ namespace mmrag_impl {
 
 namespace {
 
-constexpr int BO_MAX_QT = 64;            // query tiles of one scan launch, as scoped.hip cuts its batches
-
 // debug switches of mmrag_internal_boosted_topk_ex (tests only)
 constexpr unsigned BO_DBG_NO_BOUND = 1u;  // no bound passes: tau = -inf, every live row survives the main pass
 
@@ -42,7 +41,7 @@ struct BoostedParams {
     int B;
     unsigned row_bytes;     // ld * element size, of the rows and of the queries
     int nk;                 // K-slabs that hold the d logical columns
-    int nqt;                // query tiles, <= BO_MAX_QT
+    int nqt;                // query tiles, <= SCAN_MAX_TILES
     const unsigned *alive;
     const float *prior;     // [n]
     const float *weight;    // [B]
@@ -65,65 +64,35 @@ __global__ __launch_bounds__(256, 2) void boosted_scan_kernel(const BoostedParam
     const unsigned RB = p.row_bytes;
     const PairTileCtx c = pair_tile_ctx(threadIdx.x, RB, smem);
     const int lane = c.lane, wave = c.wave, wm = c.wm, wn = c.wn, c16 = c.c16, g4 = c.g4;
-    const int nk = p.nk, nqt = p.nqt;
-    const int total = nk * nqt;
 
     for (long long i = blockIdx.x; i < p.walk; i += gridDim.x) {
-        const long long tile = i * p.T / p.walk;      // < T
-        const long long row0 = tile * PT;
-        const long long left = p.n - row0;            // >= 1
-        const int in_tile = left < PT ? (int)left : PT;
-
-        // priors of rows `lane` and `lane + 64` of the tile, and whether they are candidates (below n, alive)
+        const PairRowTile rt = pair_row_tile(i, p.T, p.walk, p.n);
+        const long long row0 = rt.row0;
+        unsigned long long m0, m1;
+        pair_tile_live_rows(row0, lane, p.n, p.alive, m0, m1);
+        // uniform: the whole workgroup takes this path; nothing was fetched, no LDS is touched
+        if ((m0 | m1) == 0ull) continue;
+        // priors of rows `lane` and `lane + 64` of the tile
         float pr[2];
-        bool live[2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const long long r = row0 + lane + 64 * h;
-            pr[h] = 0.0f;
-            live[h] = false;
-            if (r < p.n) {
-                pr[h] = p.prior[r];
-                live[h] = p.alive == nullptr || ((p.alive[r >> 5] >> (r & 31)) & 1u) != 0u;
-            }
+            pr[h] = r < p.n ? p.prior[r] : 0.0f;
         }
-        // bit i of m0 = row i is live, of m1 = row 64 + i: the same two scalars in all four waves
-        const unsigned long long m0 = __builtin_amdgcn_ballot_w64(live[0]);
-        const unsigned long long m1 = __builtin_amdgcn_ballot_w64(live[1]);
-        // uniform: the whole workgroup takes this path; nothing was fetched, no LDS is touched
-        if ((m0 | m1) == 0ull) continue;
 
-        const char *const rows_base = p.rows + (size_t)row0 * RB;
-        const unsigned rows_bytes = (unsigned)in_tile * RB;
-        int issued = 0, i_ks = 0, i_qt = 0;
-        auto issue = [&]() {
-            // ring item `issued` = K-slab i_ks of (this row tile, query tile i_qt)
-            const int q_left = p.B - i_qt * PT;
-            const char *base = wave < 2 ? rows_base : p.q + (size_t)i_qt * PT * RB;
-            const unsigned bytes = wave < 2 ? rows_bytes : (unsigned)(q_left < PT ? q_left : PT) * RB;
-            pair_tile_issue(c, make_rsrc(base, bytes), issued % PT_NSTAGE, i_ks);
-            ++issued;
-            if (++i_ks == nk) {
-                i_ks = 0;
-                ++i_qt;
-            }
-        };
-
+        const PairTileSrc rows_src = {p.rows + (size_t)row0 * RB, (unsigned)rt.rows * RB};
         const unsigned long long mw = wm ? m1 : m0;      // this wave's 64 rows
         const float pw = wm ? pr[1] : pr[0];
-        f32x4_t acc[4][4];
-        pair_tile_clear(acc);
-        issue();
-        int ks = 0, qt = 0;
-        for (int it = 0; it < total; ++it) {
-            wait_vmcnt<0>();     // two stages: item `it` is the only one in flight
-            __builtin_amdgcn_s_barrier();
-            if (issued < total) issue();
-            slab_step<DT>(smem + (it % PT_NSTAGE) * PT_STAGE, c, acc);
-            if (++ks < nk) continue;
-            // ---- the query tile is complete: acc[a][b][r] = <row wm*64 + 16a + 4 g4 + r, query col0 + 16b>
-            ks = 0;
-            if (mw != 0ull) {
+        pair_tile_ring<DT>(
+            c, smem, p.nk, p.nqt,
+            [&](int qt) {      // (this row tile, query tile qt)
+                const int q_left = p.B - qt * PT;
+                const PairTileSrc q_src = {p.q + (size_t)qt * PT * RB, (unsigned)(q_left < PT ? q_left : PT) * RB};
+                return wave < 2 ? rows_src : q_src;
+            },
+            [&](int qt, const f32x4_t (&acc)[4][4]) {
+                // ---- acc[a][b][r] = <row wm*64 + 16a + 4 g4 + r, query qt * 128 + wn*64 + 16b + c16>
+                if (mw == 0ull) return;
                 // this lane's 16 rows: bit 4a + r of `vis` = row 16a + 4 g4 + r of the wave's 64 is live
                 float my_p[16];
                 unsigned vis = 0;
@@ -169,11 +138,8 @@ __global__ __launch_bounds__(256, 2) void boosted_scan_kernel(const BoostedParam
                             ++at;
                         }
                 }
-            }
-            ++qt;
-            pair_tile_clear(acc);
-        }
-        __syncthreads();   // every wave is done with the ring before the next tile's first slab lands
+            });
+        __syncthreads();   // the ring's contract: every wave is done with it before the next tile's first slab lands
     }
 #endif
 }
@@ -197,9 +163,7 @@ __global__ __launch_bounds__(256) void boosted_finish_kernel(const long long *__
 
 template <int DT>
 int launch_scan(const BoostedParams &p, hipStream_t s) {
-    long long g = 2LL * num_cus();    // persistent grid: two workgroups per CU (the LDS allows two)
-    if (g > p.walk) g = p.walk;
-    hipLaunchKernelGGL(boosted_scan_kernel<DT>, dim3((unsigned)g), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(boosted_scan_kernel<DT>, dim3(scan_grid(p.walk)), dim3(256), 0, s, p);
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
 }
@@ -213,7 +177,7 @@ extern "C" {
 
 size_t mmrag_boosted_topk_workspace_bytes(int B, int64_t n, int k) {
     if (B <= 0 || n < 0 || n >= (1LL << 31) || k < 1 || k > MMRAG_MAX_K_DEEP) return 0;
-    return candidate_ws_layout(B, candidate_capacity(k), n, true).total;
+    return bounded_scan_layout(B, n, k, 0, false).select_bytes;
 }
 
 // mmrag_boosted_topk with a smaller candidate capacity (cap_override > 0) and debug switches (BO_DBG_*): the tests that
@@ -237,88 +201,36 @@ int mmrag_internal_boosted_topk_ex(const void *q, const void *rows, int B, int64
         return candidate_fill_empty(out_scores, (long long *)out_rows, B, k, s);
     }
 
-    const BoundPlan pl = make_bound_plan(n, k, cap_override, (dbg & BO_DBG_NO_BOUND) != 0u);
-    const CandWs wl = candidate_ws_layout(B, pl.cap, n, true);
-    size_t ws_need = wl.total;
-    const CandWs wst = pl.n_stages > 0 ? bound_stage_layout(B, k, n, wl, &ws_need) : wl;
-    const long long stage_cap = pl.n_stages > 0 ? candidate_capacity(k) : pl.cap;
-    if (!workspace || workspace_bytes < ws_need) {
-        set_error("boosted_topk: workspace %zu bytes < required %zu", workspace_bytes, ws_need);
-        return MMRAG_EWORKSPACE;
-    }
-    if (((uintptr_t)workspace % 16) != 0) {
-        set_error("boosted_topk: workspace must be 16-byte aligned");
-        return MMRAG_EWORKSPACE;
-    }
-
-    char *ws = (char *)workspace;
-    unsigned *cnt = (unsigned *)(ws + wl.off_cnt);
-    float *tau = (float *)(ws + wl.off_floats);
     BoostedParams p;
     p.rows = (const char *)rows;
-    p.q = (const char *)q;
     p.n = n;
-    p.B = B;
     p.row_bytes = stored_row_bytes(ld, dtype);
     p.nk = stored_k_slabs(d, dtype);
-    p.nqt = 0;
     p.alive = alive_bits;
     p.prior = prior;
-    p.weight = weight;
-    p.tau = nullptr;
-    p.cand_s = (float *)(ws + wl.off_bs);
-    p.cand_r = (int *)(ws + wl.off_br);
-    p.cnt = cnt;
-    p.cap = (unsigned)pl.cap;
     p.T = (n + PT - 1) / PT;
-    p.walk = p.T;
-
-    // queries q0 .. q0 + Bq of the caller's batch over `walk` tiles into their slots: scans of at most BO_MAX_QT query
-    // tiles each
-    const auto produce = [&](int q0, int Bq, long long walk, float *cand_s, int *cand_r, unsigned *counts,
-                             long long slots) -> int {
-        const int tiles = (Bq + PT - 1) / PT;
-        for (int t0 = 0; t0 < tiles; t0 += BO_MAX_QT) {
+    // queries q0 .. q0 + Bq of the caller's batch over `walk` tiles into their slots
+    const auto produce = [&](ScanPass, int q0, int Bq, long long walk, const float *tau, float *cand_s, int *cand_r,
+                             unsigned *counts, long long slots) -> int {
+        return for_scan_chunks(Bq, PT, [&](int first, int Bc, int nqt, int) -> int {
             BoostedParams pc = p;
-            const int c0 = q0 + t0 * PT;
-            pc.q = p.q + (size_t)c0 * p.row_bytes;
+            const int c0 = q0 + first;
+            pc.q = (const char *)q + (size_t)c0 * p.row_bytes;
             pc.weight = weight + c0;
-            pc.tau = p.tau != nullptr ? p.tau + c0 : nullptr;
-            pc.B = Bq - t0 * PT < BO_MAX_QT * PT ? Bq - t0 * PT : BO_MAX_QT * PT;
-            pc.nqt = (pc.B + PT - 1) / PT;
+            pc.tau = tau != nullptr ? tau + c0 : nullptr;
+            pc.B = Bc;
+            pc.nqt = nqt;
             pc.walk = walk;
             pc.cap = (unsigned)slots;
-            pc.cand_s = cand_s + (size_t)(t0 * PT) * slots;
-            pc.cand_r = cand_r + (size_t)(t0 * PT) * slots;
-            pc.cnt = counts + t0 * PT;
-            if (int st = with_elem_type(dtype, [&](auto tag) { return launch_scan<decltype(tag)::value>(pc, s); }))
-                return st;
-        }
-        return MMRAG_OK;
+            pc.cand_s = cand_s + (size_t)first * slots;
+            pc.cand_r = cand_r + (size_t)first * slots;
+            pc.cnt = counts + first;
+            return with_elem_type(dtype, [&](auto tag) { return launch_scan<decltype(tag)::value>(pc, s); });
+        });
     };
-
-    // 1. bound passes (tau starts at -inf: the bit pattern 0xff800000)
-    if (pl.n_stages > 0) {
-        MMRAG_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)tau, (int)0xff800000u, (size_t)B, s));
-        p.tau = tau;
-    }
-    for (int st = 0; st < pl.n_stages; ++st) {
-        MMRAG_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)B * sizeof(unsigned), s));
-        float *st_s = (float *)(ws + wst.off_bs);
-        int *st_r = (int *)(ws + wst.off_br);
-        if (int e = produce(0, B, pl.stage_tiles[st], st_s, st_r, cnt, stage_cap)) return e;
-        deep_select_kernel<<<B, SEL_THREADS, 0, s>>>(st_s, st_r, cnt, stage_cap, k, 0, 1, nullptr, nullptr, tau);
-        MMRAG_CHECK_HIP(hipGetLastError());
-    }
-    // 2. main pass over every tile, 3. select, 4. each query with more survivors than slots alone, same tau_q
-    if (int st = candidate_select(
-            "boosted_topk", B, n, pl.cap, k, row_offset, out_scores, (long long *)out_rows, ws, wl, s,
-            [&](float *cand_s, int *cand_r, unsigned *counts, long long slots) {
-                return produce(0, B, p.T, cand_s, cand_r, counts, slots);
-            },
-            [&](int qi, float *cand_s, int *cand_r, unsigned *counts, long long slots) {
-                return produce(qi, 1, p.T, cand_s, cand_r, counts, slots);
-            }))
+    if (int st = bounded_scan_select("boosted_topk", B, n, k, cap_override, (dbg & BO_DBG_NO_BOUND) != 0u, row_offset,
+                                     nullptr, out_scores, (long long *)out_rows, workspace, workspace_bytes, 0, s,
+                                     [](char *) { return MMRAG_OK; }, produce))
         return st;
     if (out_boost) {
         boosted_finish_kernel<<<(unsigned)((total_out + 255) / 256), 256, 0, s>>>(

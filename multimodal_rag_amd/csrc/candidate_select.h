@@ -1,7 +1,12 @@
 // The host sequence around deep_select.h's select, shared by the deep top-k (search_deep.hip) and the BM25 search
 // (lexical.hip): a producer appends (score, local row) candidates to B x cap slots and counts them per query, the select
 // turns each query's slots into its sorted top-k, and a query whose candidates overflowed its slots is produced again
-// alone into n slots.  The callers supply the two producer launches.  Internal, gfx950 only.
+// alone into n slots.  The callers supply the two producer launches.
+// For the scans over 128-row tiles (boosted.hip, filtered.hip, range.hip, recommend.hip) the whole bounded sequence is
+// here as well, once: bounded_scan_select owns the plan, the workspace layout and its checks, the tau start, the bound
+// stages and the call of candidate_select, and takes ONE producer; the *_workspace_bytes functions size themselves by
+// its bounded_scan_layout.  for_scan_chunks cuts a batch into launches of at most SCAN_MAX_TILES column tiles for every
+// scan that has such a limit.  Internal, gfx950 only.
 #pragma once
 #include "deep_select.h"
 
@@ -147,6 +152,105 @@ int candidate_select(const char *name, int B, long long n, long long cap, int k,
         }
     }
     return MMRAG_OK;
+}
+
+// ---- the launches of a scan over 128-row tiles ----------------------------------------------------------------------
+// Column tiles (128 rows of the batch side) of one scan launch: a kernel keeps their "wanted" flags in one 64-bit mask
+constexpr int SCAN_MAX_TILES = 64;
+
+// Bq batch entries, `per_tile` of them to a column tile (128 queries; 8 recommend requests of 16 example rows), as
+// launches of at most SCAN_MAX_TILES column tiles: launch(first entry of the chunk, its entries, its column tiles, its
+// first column tile) returns a status
+template <typename Launch>
+inline int for_scan_chunks(int Bq, int per_tile, Launch &&launch) {
+    const int tiles = (Bq + per_tile - 1) / per_tile;
+    for (int t0 = 0; t0 < tiles; t0 += SCAN_MAX_TILES) {
+        const int first = t0 * per_tile;
+        const int Bc = Bq - first < SCAN_MAX_TILES * per_tile ? Bq - first : SCAN_MAX_TILES * per_tile;
+        if (int st = launch(first, Bc, (Bc + per_tile - 1) / per_tile, t0)) return st;
+    }
+    return MMRAG_OK;
+}
+
+// ---- the bounded scan: plan, workspace, bound stages, main pass, select, overflow re-runs ---------------------------
+struct BoundedScanWs {
+    BoundPlan pl;
+    CandWs main, stage;     // the main pass's blocks (pl.cap slots) and a bound stage's (stage_cap slots)
+    long long stage_cap;
+    size_t select_bytes;    // what the two need; the caller's extra bytes lie behind them
+};
+
+// cap_override == 0 and !no_bound give the public size: candidate_capacity(k) slots, which no call exceeds
+inline BoundedScanWs bounded_scan_layout(int B, long long n, int k, long long cap_override, bool no_bound) {
+    BoundedScanWs l;
+    l.pl = make_bound_plan(n, k, cap_override, no_bound);
+    l.main = candidate_ws_layout(B, l.pl.cap, n, true);
+    l.select_bytes = l.main.total;
+    l.stage = l.pl.n_stages > 0 ? bound_stage_layout(B, k, n, l.main, &l.select_bytes) : l.main;
+    l.stage_cap = l.pl.n_stages > 0 ? candidate_capacity(k) : l.pl.cap;
+    return l;
+}
+
+enum ScanPass { SCAN_PASS_BOUND, SCAN_PASS_MAIN, SCAN_PASS_RERUN };
+
+// Everything of a bounded top-k scan between "arguments checked, n > 0" and the caller's finish kernel (boosted.hip,
+// filtered.hip, range.hip, recommend.hip): out_s / out_r [B, k] = each query's top-k of what `produce` appends.
+//   1. the plan (make_bound_plan) and the workspace [select_bytes | extra_bytes of the caller's], checked: too small or
+//      not 16-byte aligned is MMRAG_EWORKSPACE under `name`;
+//   2. prepare(the caller's extra bytes) -> status, once, before any pass (union bitmaps; nothing for most);
+//   3. with stages: tau_q starts at tau_init[q] (null: -inf), and each stage zeroes the counters, produces over its
+//      sample of tiles into the stage's slots and raises tau_q to the k-th best of them (deep_select_kernel's bound mode);
+//   4. candidate_select: the main pass over all T tiles, the select, and each overflowed query alone into n slots.
+//   produce(pass, q0, Bq, walk, tau, cand_s, cand_r, counts, slots) -> status
+// appends, for queries q0 .. q0 + Bq of the batch over `walk` tiles, every (score, local row) at or above tau[q]
+// (`tau`: the B floats of the whole batch, null without stages: the caller's own floor) to query q's slots
+// cand_s / cand_r [(q - q0) * slots ..), counting in counts[q - q0].  `pass` says which of the three callers it is: what
+// only the main pass may do (count, tabulate) and what a re-run needs (its own unions) hang on it.
+template <typename Prepare, typename Produce>
+int bounded_scan_select(const char *name, int B, long long n, int k, long long cap_override, bool no_bound,
+                        long long row_offset, const float *tau_init, float *out_s, long long *out_r, void *workspace,
+                        size_t workspace_bytes, size_t extra_bytes, hipStream_t s, Prepare &&prepare,
+                        Produce &&produce) {
+    const BoundedScanWs l = bounded_scan_layout(B, n, k, cap_override, no_bound);
+    const size_t need = l.select_bytes + extra_bytes;
+    if (!workspace || workspace_bytes < need) {
+        mmrag::set_error("%s: workspace %zu bytes < required %zu", name, workspace_bytes, need);
+        return MMRAG_EWORKSPACE;
+    }
+    if (((uintptr_t)workspace % 16) != 0) {
+        mmrag::set_error("%s: workspace must be 16-byte aligned", name);
+        return MMRAG_EWORKSPACE;
+    }
+    char *ws = (char *)workspace;
+    unsigned *cnt = (unsigned *)(ws + l.main.off_cnt);
+    float *tau = nullptr;
+    if (int e = prepare(ws + l.select_bytes)) return e;
+
+    if (l.pl.n_stages > 0) {
+        tau = (float *)(ws + l.main.off_floats);
+        if (tau_init != nullptr)
+            MMRAG_CHECK_HIP(hipMemcpyAsync(tau, tau_init, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
+        else      // -inf: the bit pattern 0xff800000
+            MMRAG_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)tau, (int)0xff800000u, (size_t)B, s));
+    }
+    float *st_s = (float *)(ws + l.stage.off_bs);
+    int *st_r = (int *)(ws + l.stage.off_br);
+    for (int st = 0; st < l.pl.n_stages; ++st) {
+        MMRAG_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)B * sizeof(unsigned), s));
+        if (int e = produce(SCAN_PASS_BOUND, 0, B, l.pl.stage_tiles[st], (const float *)tau, st_s, st_r, cnt, l.stage_cap))
+            return e;
+        deep_select_kernel<<<B, SEL_THREADS, 0, s>>>(st_s, st_r, cnt, l.stage_cap, k, 0, 1, nullptr, nullptr, tau);
+        MMRAG_CHECK_HIP(hipGetLastError());
+    }
+    const long long T = (n + BOUND_TILE_ROWS - 1) / BOUND_TILE_ROWS;
+    return candidate_select(
+        name, B, n, l.pl.cap, k, row_offset, out_s, out_r, ws, l.main, s,
+        [&](float *cand_s, int *cand_r, unsigned *counts, long long slots) {
+            return produce(SCAN_PASS_MAIN, 0, B, T, (const float *)tau, cand_s, cand_r, counts, slots);
+        },
+        [&](int qi, float *cand_s, int *cand_r, unsigned *counts, long long slots) {
+            return produce(SCAN_PASS_RERUN, qi, 1, T, (const float *)tau, cand_s, cand_r, counts, slots);
+        });
 }
 
 }  // namespace

@@ -22,12 +22,12 @@
 //      A filter can pass most of the collection, so when n exceeds the candidate slots the scan first runs over a
 //      strided sample of whole tiles and deep_select_kernel's bound mode sets tau_q to the k-th best of the VISIBLE
 //      sampled rows: the k-th best of any subset of a query's visible rows is at most its true k-th, whatever the
-//      filter (tau_q stays -inf while fewer than k visible rows were sampled).  Stages: candidate_select.h's
-//      make_bound_plan.
-//   3. select and overflow: candidate_select.h's driver, unchanged.
+//      filter (tau_q stays -inf while fewer than k visible rows were sampled).
+//   3. select and overflow.  Steps 2 and 3 run under candidate_select.h's bounded_scan_select (plan, workspace,
+//      stages, main pass, select, re-runs); this file supplies the unions and the producer.
 // The K order is slab_step's, so a score's bits depend on the query row, the stored row and d alone and equal
 // mmrag_scoped_topk's: not on the batch, the filters, the grid, tau or whether bound passes ran.
-// The scan body, the union kernel and the split into launches are masked_scan.h's, shared with range.hip.
+// The scan body and the union kernel are masked_scan.h's, shared with range.hip.
 #include "masked_scan.h"
 
 using namespace mmrag;
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256, 2) void filtered_scan_kernel(const FilteredPar
 
 template <int DT>
 int launch_scan(const FilteredParams &p, hipStream_t s) {
-    hipLaunchKernelGGL(filtered_scan_kernel<DT>, dim3(masked_scan_grid(p.walk)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(filtered_scan_kernel<DT>, dim3(scan_grid(p.walk)), dim3(256), 0, s, p);
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
 }
@@ -206,7 +206,7 @@ int mmrag_filter_eval(const mmrag_filter_op *ops, int n_ops, const int32_t *prog
 
 size_t mmrag_filtered_topk_workspace_bytes(int B, int64_t n, int k) {
     if (B <= 0 || n < 0 || n >= (1LL << 31) || k < 1 || k > MMRAG_MAX_K_DEEP) return 0;
-    return candidate_ws_layout(B, candidate_capacity(k), n, true).total + filtered_union_bytes(B, n);
+    return bounded_scan_layout(B, n, k, 0, false).select_bytes + filtered_union_bytes(B, n);
 }
 
 // mmrag_filtered_topk with a smaller candidate capacity (cap_override > 0), debug switches (FI_DBG_*) and an optional
@@ -227,62 +227,34 @@ int mmrag_internal_filtered_topk_ex(const void *q, const void *rows, int B, int6
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) return candidate_fill_empty(out_scores, (long long *)out_rows, B, k, s);
 
-    const BoundPlan pl = make_bound_plan(n, k, cap_override, (dbg & FI_DBG_NO_BOUND) != 0u);
-    const CandWs wl = candidate_ws_layout(B, pl.cap, n, true);
-    size_t sel_total = wl.total;
-    const CandWs wst = pl.n_stages > 0 ? bound_stage_layout(B, k, n, wl, &sel_total) : wl;
-    const long long stage_cap = pl.n_stages > 0 ? candidate_capacity(k) : pl.cap;
-    const size_t need = sel_total + filtered_union_bytes(B, n);
-    if (!workspace || workspace_bytes < need) {
-        set_error("filtered_topk: workspace %zu bytes < required %zu", workspace_bytes, need);
-        return MMRAG_EWORKSPACE;
-    }
-    if (((uintptr_t)workspace % 16) != 0) {
-        set_error("filtered_topk: workspace must be 16-byte aligned");
-        return MMRAG_EWORKSPACE;
-    }
-
-    char *ws = (char *)workspace;
-    unsigned *cnt = (unsigned *)(ws + wl.off_cnt);
-    float *tau = (float *)(ws + wl.off_floats);
-    unsigned *uni = (unsigned *)(ws + sel_total);      // behind the stages' buffers too: the unions serve every pass
     FilteredParams p;
     p.rows = (const char *)rows;
-    p.q = (const char *)q;
     p.n = n;
-    p.B = B;
     p.row_bytes = stored_row_bytes(ld, dtype);
     p.nk = stored_k_slabs(d, dtype);
-    p.nqt = 0;
-    p.uni = uni;
     p.vis = vis_bits;
-    p.filter_of_query = filter_of_query;
     p.F = F;
     p.W = filter_words(n);
-    p.tau = nullptr;
-    p.cand_s = (float *)(ws + wl.off_bs);
-    p.cand_r = (int *)(ws + wl.off_br);
-    p.cnt = cnt;
-    p.cap = (unsigned)pl.cap;
     p.T = (n + PT - 1) / PT;
-    p.walk = p.T;
-    p.items = nullptr;
+    unsigned *uni = nullptr;      // the caller's extra bytes: the batch's unions, then one query tile's for a re-run
     const int nqt_all = (B + PT - 1) / PT;
 
-    // the unions of queries q0 .. q0 + Bq of the caller's batch into um[0 .. ceil(Bq / 128))
-    const auto unions = [&](int q0, int Bq, unsigned *um) -> int {
-        return launch_unions(filter_of_query + q0, Bq, F, vis_bits, p.W, um, s);
-    };
-    // queries q0 .. q0 + Bq over `walk` tiles into their slots, their unions in um: scans of at most FI_MAX_QT query
-    // tiles each
-    const auto produce = [&](int q0, int Bq, long long walk, const unsigned *um, float *cand_s, int *cand_r,
-                             unsigned *counts, long long slots, unsigned long long *items) -> int {
-        return for_scan_chunks(Bq, [&](int first, int Bc, int nqt, int t0) -> int {
+    // queries q0 .. q0 + Bq over `walk` tiles into their slots.  The batch's unions serve every pass of it; a query
+    // produced again alone gets its own.  The main pass counts the items it issues.
+    const auto produce = [&](ScanPass pass, int q0, int Bq, long long walk, const float *tau, float *cand_s, int *cand_r,
+                             unsigned *counts, long long slots) -> int {
+        const unsigned *um = uni;
+        if (pass == SCAN_PASS_RERUN) {
+            unsigned *own = uni + (size_t)nqt_all * p.W;
+            if (int e = launch_unions(filter_of_query + q0, Bq, F, vis_bits, p.W, own, s)) return e;
+            um = own;
+        }
+        return for_scan_chunks(Bq, PT, [&](int first, int Bc, int nqt, int t0) -> int {
             FilteredParams pc = p;
             const int c0 = q0 + first;
-            pc.q = p.q + (size_t)c0 * p.row_bytes;
+            pc.q = (const char *)q + (size_t)c0 * p.row_bytes;
             pc.filter_of_query = filter_of_query + c0;
-            pc.tau = p.tau != nullptr ? p.tau + c0 : nullptr;
+            pc.tau = tau != nullptr ? tau + c0 : nullptr;
             pc.B = Bc;
             pc.nqt = nqt;
             pc.uni = um + (size_t)t0 * p.W;
@@ -291,38 +263,19 @@ int mmrag_internal_filtered_topk_ex(const void *q, const void *rows, int B, int6
             pc.cand_s = cand_s + (size_t)first * slots;
             pc.cand_r = cand_r + (size_t)first * slots;
             pc.cnt = counts + first;
-            pc.items = items;
+            pc.items = pass == SCAN_PASS_MAIN ? (unsigned long long *)items_issued : nullptr;
             return with_elem_type(dtype, [&](auto tag) { return launch_scan<decltype(tag)::value>(pc, s); });
         });
     };
-
-    // 1. the unions of the batch, once for every pass
-    if (int e = unions(0, B, uni)) return e;
-    // 2. bound passes (tau starts at -inf: the bit pattern 0xff800000)
-    if (pl.n_stages > 0) {
-        MMRAG_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)tau, (int)0xff800000u, (size_t)B, s));
-        p.tau = tau;
-    }
-    for (int st = 0; st < pl.n_stages; ++st) {
-        MMRAG_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)B * sizeof(unsigned), s));
-        float *st_s = (float *)(ws + wst.off_bs);
-        int *st_r = (int *)(ws + wst.off_br);
-        if (int e = produce(0, B, pl.stage_tiles[st], uni, st_s, st_r, cnt, stage_cap, nullptr)) return e;
-        deep_select_kernel<<<B, SEL_THREADS, 0, s>>>(st_s, st_r, cnt, stage_cap, k, 0, 1, nullptr, nullptr, tau);
-        MMRAG_CHECK_HIP(hipGetLastError());
-    }
     if (items_issued) MMRAG_CHECK_HIP(hipMemsetAsync(items_issued, 0, sizeof(uint64_t), s));
-    // 3. main pass over every tile, select, and each query with more survivors than slots alone, same tau_q
-    return candidate_select(
-        "filtered_topk", B, n, pl.cap, k, row_offset, out_scores, (long long *)out_rows, ws, wl, s,
-        [&](float *cand_s, int *cand_r, unsigned *counts, long long slots) {
-            return produce(0, B, p.T, uni, cand_s, cand_r, counts, slots, (unsigned long long *)items_issued);
+    return bounded_scan_select(
+        "filtered_topk", B, n, k, cap_override, (dbg & FI_DBG_NO_BOUND) != 0u, row_offset, nullptr, out_scores,
+        (long long *)out_rows, workspace, workspace_bytes, filtered_union_bytes(B, n), s,
+        [&](char *extra) {      // the unions of the batch, once for every pass
+            uni = (unsigned *)extra;
+            return launch_unions(filter_of_query, B, F, vis_bits, p.W, uni, s);
         },
-        [&](int qi, float *cand_s, int *cand_r, unsigned *counts, long long slots) {
-            unsigned *um = uni + (size_t)nqt_all * p.W;
-            if (int e = unions(qi, 1, um)) return e;
-            return produce(qi, 1, p.T, um, cand_s, cand_r, counts, slots, nullptr);
-        });
+        produce);
 }
 
 int mmrag_filtered_topk(const void *q, const void *rows, int B, int64_t n, int d, int64_t ld, int dtype, int k,

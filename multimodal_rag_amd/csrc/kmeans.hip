@@ -56,14 +56,12 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_kernel(const AssignParam
     const unsigned RB = p.row_bytes;
     const PairTileCtx c = pair_tile_ctx(threadIdx.x, RB, smem);
     const int wave = c.wave, wm = c.wm, wn = c.wn, c16 = c.c16, g4 = c.g4;
-    const int nk = p.nk, nct = p.nct;
-    const int total = nk * nct;
     const float NEG_INF = -__builtin_inff();
 
     for (long long tile = blockIdx.x; tile < p.T; tile += gridDim.x) {
-        const long long row0 = tile * PT;
-        const long long left = p.n - row0;            // >= 1
-        const int in_tile = left < PT ? (int)left : PT;
+        const PairRowTile rt = pair_row_tile(tile, p.T, p.T, p.n);
+        const long long row0 = rt.row0;
+        const int in_tile = rt.rows;
 
         unsigned any = 1u;
         if (p.alive != nullptr) {
@@ -81,27 +79,9 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_kernel(const AssignParam
             continue;
         }
 
-        const char *const rows_base = p.rows + (size_t)row0 * RB;
-        const unsigned rows_bytes = (unsigned)in_tile * RB;
-        int issued = 0, i_ct = 0, i_ks = 0;
-        auto issue = [&]() {
-            // ring item `issued` = K-slab i_ks of (this row tile, centroid tile i_ct)
-            const int c_left = p.k - i_ct * PT;
-            const char *base = wave < 2 ? rows_base : p.centroids + (size_t)i_ct * PT * RB;
-            const unsigned bytes = wave < 2 ? rows_bytes : (unsigned)(c_left < PT ? c_left : PT) * RB;
-            pair_tile_issue(c, make_rsrc(base, bytes), issued % PT_NSTAGE, i_ks);
-            ++issued;
-            if (++i_ks == nk) {
-                i_ks = 0;
-                ++i_ct;
-            }
-        };
-
         // running best of this lane's rows wm * 64 + 16 a + 4 g4 + r over the columns it has seen
         float bv[4][4];
         int ba[4][4];
-        f32x4_t acc[4][4];
-        pair_tile_clear(acc);
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -110,16 +90,16 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_kernel(const AssignParam
                 ba[a][r] = 0;
             }
 
-        issue();
-        int ks = 0, ct = 0;
-        for (int it = 0; it < total; ++it) {
-            wait_vmcnt<0>();     // two stages: item `it` is the only one in flight
-            __builtin_amdgcn_s_barrier();
-            if (issued < total) issue();
-            slab_step<DT>(smem + (it % PT_NSTAGE) * PT_STAGE, c, acc);
-            if (++ks == nk) {
-                // ---- the centroid tile is complete: acc[a][b][r] = <row wm*64 + 16a + 4 g4 + r, centroid col0 + 16b>
-                ks = 0;
+        const PairTileSrc rows_src = {p.rows + (size_t)row0 * RB, (unsigned)in_tile * RB};
+        pair_tile_ring<DT>(
+            c, smem, p.nk, p.nct,
+            [&](int ct) {      // (this row tile, centroid tile ct)
+                const int c_left = p.k - ct * PT;
+                const PairTileSrc c_src = {p.centroids + (size_t)ct * PT * RB, (unsigned)(c_left < PT ? c_left : PT) * RB};
+                return wave < 2 ? rows_src : c_src;
+            },
+            [&](int ct, const f32x4_t (&acc)[4][4]) {
+                // ---- acc[a][b][r] = <row wm*64 + 16a + 4 g4 + r, centroid ct * 128 + wn*64 + 16b + c16>
                 const int col0 = ct * PT + wn * 64 + c16;
                 const bool ragged = (ct + 1) * PT > p.k;     // uniform: only the last centroid tile can hold columns >= k
 #pragma unroll
@@ -135,12 +115,9 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_kernel(const AssignParam
                                 bv[a][r] = v;
                                 ba[a][r] = col;
                             }
-                            acc[a][b][r] = 0.0f;
                         }
                 }
-                ++ct;
-            }
-        }
+            });
 
         // ---- fold the 16 lanes that hold other columns of the same rows, then the two waves wn = 0, 1
 #pragma unroll
@@ -158,7 +135,7 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_kernel(const AssignParam
                     red_a[wn][wm * 64 + 16 * a + 4 * g4 + r] = ba[a][r];
                 }
             }
-        __syncthreads();   // also: every wave is done with the ring before the next tile's first slab lands
+        __syncthreads();   // also the ring's: every wave is done with it before the next tile's first slab lands
         if ((int)threadIdx.x < in_tile) {
             const int t = threadIdx.x;
             float v = red_v[0][t];
@@ -179,9 +156,7 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_kernel(const AssignParam
 
 template <int DT>
 static int launch_assign(const AssignParams &p, hipStream_t s) {
-    long long g = 2LL * mmrag::num_cus();    // persistent grid: two workgroups per CU (the LDS allows two)
-    if (g > p.T) g = p.T;
-    hipLaunchKernelGGL(kmeans_assign_kernel<DT>, dim3((unsigned)g), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(kmeans_assign_kernel<DT>, dim3(scan_grid(p.T)), dim3(256), 0, s, p);
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
 }

@@ -1,7 +1,8 @@
 // The masked scan shared by the filtered top-k (filtered.hip) and the range scan (range.hip): Q . X^T with pair_tile.h's
 // body over persistent workgroups, each query seeing only the rows of ITS bitmap, and what surrounds it on the host --
-// the bitmap geometry, the union bitmaps of a query tile and the split of a batch into launches of at most FI_MAX_QT
-// query tiles.  The kernels keep what differs: the epilogue.  Internal, gfx950 only.
+// the bitmap geometry and the union bitmaps of a query tile.  The ring is pair_tile.h's pair_tile_ring; the split of a
+// batch into launches (for_scan_chunks), the grid (scan_grid) and the bounded sequence around the scan
+// (bounded_scan_select) are candidate_select.h's.  The kernels keep what differs: the epilogue.  Internal, gfx950 only.
 //
 // The scan: a 128-row tile of stored rows as A and a 128-query tile as B; rows past n and queries past B read as zero
 // through the buffer descriptor.  Before anything is fetched all four waves read the tile's four words of every query
@@ -20,8 +21,6 @@ namespace mmrag_impl {
 
 namespace {
 
-constexpr int FI_MAX_QT = 64;            // query tiles of one scan launch: their "wanted" flags are one 64-bit mask
-
 // debug switches of the _ex entry points (tests only)
 constexpr unsigned FI_DBG_NO_BOUND = 1u;  // no bound passes: tau stays at its start, every survivor of it is a candidate
 
@@ -34,7 +33,7 @@ struct MaskedScanParams {
     int B;
     unsigned row_bytes;     // ld * element size, of the rows and of the queries
     int nk;                 // K-slabs that hold the d logical columns
-    int nqt;                // query tiles, <= FI_MAX_QT
+    int nqt;                // query tiles, <= SCAN_MAX_TILES
     const unsigned *uni;    // [nqt, W]: the union bitmaps of this launch's query tiles; null: every item is wanted
     const unsigned *vis;    // [F, W]; null: every row below n is visible to every query
     const int *filter_of_query;
@@ -83,33 +82,12 @@ inline size_t filtered_union_bytes(int B, long long n) {
 inline int launch_unions(const int *filter_of_query, int Bq, int F, const unsigned *vis, long long W, unsigned *um,
                          hipStream_t s) {
     const unsigned wblocks = (unsigned)((W + 255) / 256);
-    const int tiles = (Bq + PT - 1) / PT;
-    for (int t0 = 0; t0 < tiles; t0 += FI_MAX_QT) {
-        const int nt = tiles - t0 < FI_MAX_QT ? tiles - t0 : FI_MAX_QT;
-        hipLaunchKernelGGL(filtered_union_kernel, dim3(wblocks, (unsigned)nt), dim3(256), 0, s, filter_of_query + t0 * PT,
-                           Bq - t0 * PT, F, vis, W, um + (size_t)t0 * W);
+    return for_scan_chunks(Bq, PT, [&](int first, int Bc, int nt, int t0) -> int {
+        hipLaunchKernelGGL(filtered_union_kernel, dim3(wblocks, (unsigned)nt), dim3(256), 0, s, filter_of_query + first, Bc,
+                           F, vis, W, um + (size_t)t0 * W);
         MMRAG_CHECK_HIP(hipGetLastError());
-    }
-    return MMRAG_OK;
-}
-
-// Bq queries as scans of at most FI_MAX_QT query tiles: launch(first query of the chunk, its queries, its query tiles,
-// its first query tile) returns a status
-template <typename Launch>
-inline int for_scan_chunks(int Bq, Launch &&launch) {
-    const int tiles = (Bq + PT - 1) / PT;
-    for (int t0 = 0; t0 < tiles; t0 += FI_MAX_QT) {
-        const int Bc = Bq - t0 * PT < FI_MAX_QT * PT ? Bq - t0 * PT : FI_MAX_QT * PT;
-        if (int st = launch(t0 * PT, Bc, (Bc + PT - 1) / PT, t0)) return st;
-    }
-    return MMRAG_OK;
-}
-
-// persistent grid: two workgroups per CU (the LDS allows two), at most one per visited tile
-inline unsigned masked_scan_grid(long long walk) {
-    long long g = 2LL * mmrag::num_cus();
-    if (g > walk) g = walk;
-    return (unsigned)g;
+        return MMRAG_OK;
+    });
 }
 
 // The scan of one launch.  `smem`: PT_LDS bytes, 1 KiB aligned.  For every complete (row tile, query tile) and each of
@@ -122,15 +100,14 @@ __device__ __forceinline__ void masked_scan_body(const MaskedScanParams &p, char
     const unsigned RB = p.row_bytes;
     const PairTileCtx c = pair_tile_ctx(threadIdx.x, RB, smem);
     const int wave = c.wave, wm = c.wm, wn = c.wn, c16 = c.c16, g4 = c.g4;
-    const int nk = p.nk, nqt = p.nqt;
+    const int nqt = p.nqt;
     const long long W = p.W;
     const bool masked = p.uni != nullptr;      // uniform
 
     for (long long i = blockIdx.x; i < p.walk; i += gridDim.x) {
-        const long long tile = i * p.T / p.walk;      // < T
-        const long long row0 = tile * PT;
-        const long long left = p.n - row0;            // >= 1
-        const int in_tile = left < PT ? (int)left : PT;
+        const PairRowTile rt = pair_row_tile(i, p.T, p.walk, p.n);
+        const long long tile = rt.tile, row0 = rt.row0;
+        const int in_tile = rt.rows;
         // the tile's rows below n, per bitmap word: a bitmap from elsewhere may hold bits at and past n
         unsigned vm[4];
 #pragma unroll
@@ -156,41 +133,20 @@ __device__ __forceinline__ void masked_scan_body(const MaskedScanParams &p, char
         if (active == 0ull) continue;
         if (p.items != nullptr && threadIdx.x == 0) atomicAdd(p.items, (unsigned long long)__popcll(active));
 
-        const char *const rows_base = p.rows + (size_t)row0 * RB;
-        const unsigned rows_bytes = (unsigned)in_tile * RB;
-        const int total = nk * __popcll(active);
-        unsigned long long i_left = active;
-        int issued = 0, i_ks = 0;
-        auto issue = [&]() {
-            // ring item `issued` = K-slab i_ks of (this row tile, the lowest query tile left in i_left)
-            const int qt = __builtin_ctzll(i_left);
-            const int q_left = p.B - qt * PT;
-            const char *base = wave < 2 ? rows_base : p.q + (size_t)qt * PT * RB;
-            const unsigned bytes = wave < 2 ? rows_bytes : (unsigned)(q_left < PT ? q_left : PT) * RB;
-            pair_tile_issue(c, make_rsrc(base, bytes), issued % PT_NSTAGE, i_ks);
-            ++issued;
-            if (++i_ks == nk) {
-                i_ks = 0;
-                i_left &= i_left - 1;
-            }
-        };
-
+        const PairTileSrc rows_src = {p.rows + (size_t)row0 * RB, (unsigned)in_tile * RB};
         // this wave's 64 rows below n
         const unsigned long long valid = ((unsigned long long)vm[2 * wm + 1] << 32) | vm[2 * wm];
-        f32x4_t acc[4][4];
-        pair_tile_clear(acc);
-        unsigned long long c_left = active;
-        issue();
-        int ks = 0;
-        for (int it = 0; it < total; ++it) {
-            wait_vmcnt<0>();     // two stages: item `it` is the only one in flight
-            __builtin_amdgcn_s_barrier();
-            if (issued < total) issue();
-            slab_step<DT>(smem + (it % PT_NSTAGE) * PT_STAGE, c, acc);
-            if (++ks < nk) continue;
-            // ---- the query tile is complete: acc[a][b][r] = <row wm*64 + 16a + 4 g4 + r, query col0 + 16b>
-            ks = 0;
-            pair_tile_settle<DT>();
+        // the ring runs over the wanted query tiles, lowest first: each callback pops its own copy of the mask
+        unsigned long long i_left = active, c_left = active;
+        const auto tile_src = [&](int) {
+            const int qt = __builtin_ctzll(i_left);
+            i_left &= i_left - 1;
+            const int q_left = p.B - qt * PT;
+            const PairTileSrc q_src = {p.q + (size_t)qt * PT * RB, (unsigned)(q_left < PT ? q_left : PT) * RB};
+            return wave < 2 ? rows_src : q_src;
+        };
+        // ---- acc[a][b][r] = <row wm*64 + 16a + 4 g4 + r, query qt * 128 + wn*64 + 16b + c16>
+        const auto tile_done = [&](int, const f32x4_t (&acc)[4][4]) {
             const int qt = __builtin_ctzll(c_left);
             c_left &= c_left - 1;
             unsigned long long mw = valid;
@@ -218,9 +174,9 @@ __device__ __forceinline__ void masked_scan_body(const MaskedScanParams &p, char
                     epilogue(col, vis, acc, b, lrow0);
                 }
             }
-            pair_tile_clear(acc);
-        }
-        __syncthreads();   // every wave is done with the ring before the next tile's first slab lands
+        };
+        pair_tile_ring<DT>(c, smem, p.nk, __popcll(active), tile_src, tile_done);
+        __syncthreads();   // the ring's contract: every wave is done with it before the next tile's first slab lands
     }
 }
 

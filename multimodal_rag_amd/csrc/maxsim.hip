@@ -72,30 +72,13 @@ __global__ __launch_bounds__(256, 2) void maxsim_kernel(const MaxSimParams p) {
     const int wave_id = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const PairTileCtx c = pair_tile_ctx(threadIdx.x, wave_id < 2 ? p.q_rb : p.d_rb, smem);
     const int wave = c.wave, wm = c.wm, wn = c.wn, c16 = c.c16, g4 = c.g4;
-    const int nk = p.nk, nct = (dl + PT - 1) / PT;
-    const int total = nk * nct;
-    const char *const q_base = p.q_tok + (size_t)qs * p.q_rb;
+    const int nct = (dl + PT - 1) / PT;
+    const PairTileSrc q_src = {p.q_tok + (size_t)qs * p.q_rb, (unsigned)ql * p.q_rb};
     const char *const d_base = p.d_tok + (size_t)ds * p.d_rb;
-
-    int issued = 0, i_ct = 0, i_ks = 0;
-    auto issue = [&]() {
-        // ring item `issued` = K-slab i_ks of (the query tile, passage tile i_ct)
-        const int d_left = dl - i_ct * PT;
-        const char *base = wave < 2 ? q_base : d_base + (size_t)i_ct * PT * p.d_rb;
-        const unsigned bytes = wave < 2 ? (unsigned)ql * p.q_rb : (unsigned)(d_left < PT ? d_left : PT) * p.d_rb;
-        pair_tile_issue(c, make_rsrc(base, bytes), issued % PT_NSTAGE, i_ks);
-        ++issued;
-        if (++i_ks == nk) {
-            i_ks = 0;
-            ++i_ct;
-        }
-    };
 
     // running best of this lane's query rows wm * 64 + 16 a + 4 g4 + r over the passage columns it has seen
     float bv[4][4];
     int ba[4][4];
-    f32x4_t acc[4][4];
-    pair_tile_clear(acc);
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -104,17 +87,15 @@ __global__ __launch_bounds__(256, 2) void maxsim_kernel(const MaxSimParams p) {
             ba[a][r] = 0;
         }
 
-    issue();
-    int ks = 0, ct = 0;
-    for (int it = 0; it < total; ++it) {
-        wait_vmcnt<0>();     // two stages: item `it` is the only one in flight
-        __builtin_amdgcn_s_barrier();
-        if (issued < total) issue();
-        slab_step<DT>(smem + (it % PT_NSTAGE) * PT_STAGE, c, acc);
-        if (++ks == nk) {
-            pair_tile_settle<DT>();
-            // ---- the passage tile is complete: acc[a][b][r] = <query row wm*64 + 16a + 4 g4 + r, passage col0 + 16b>
-            ks = 0;
+    pair_tile_ring<DT>(
+        c, smem, p.nk, nct,
+        [&](int ct) {      // (the query tile, passage tile ct): the B side is the one that moves
+            const int d_left = dl - ct * PT;
+            const PairTileSrc d_src = {d_base + (size_t)ct * PT * p.d_rb, (unsigned)(d_left < PT ? d_left : PT) * p.d_rb};
+            return wave < 2 ? q_src : d_src;
+        },
+        [&](int ct, const f32x4_t (&acc)[4][4]) {
+            // ---- acc[a][b][r] = <query row wm*64 + 16a + 4 g4 + r, passage token ct * 128 + wn*64 + 16b + c16>
             const int col0 = ct * PT + wn * 64 + c16;
             const bool ragged = (ct + 1) * PT > dl;     // uniform: only the last passage tile can hold columns >= d_len
 #pragma unroll
@@ -130,12 +111,10 @@ __global__ __launch_bounds__(256, 2) void maxsim_kernel(const MaxSimParams p) {
                             bv[a][r] = v;
                             ba[a][r] = col;
                         }
-                        acc[a][b][r] = 0.0f;
                     }
             }
-            ++ct;
-        }
-    }
+        });
+    // one ring per workgroup: the barrier below is the fold's, the ring needs none
 
     // ---- fold the 16 lanes that hold other columns of the same rows, then the two waves wn = 0, 1
 #pragma unroll

@@ -224,51 +224,30 @@ __global__ __launch_bounds__(256, 2) void maxsim_scan_kernel(const MsScanParams 
     const int wave_id = __builtin_amdgcn_readfirstlane(tid >> 6);
     const PairTileCtx c = pair_tile_ctx(tid, wave_id < 2 ? p.q_rb : p.rb, smem);
     const int wave = c.wave, wm = c.wm, wn = c.wn, c16 = c.c16, g4 = c.g4;
-    const int nk = p.nk, nct = (int)(((long long)re - rs + PT - 1) / PT);
-    const int total = nk * nct;
-    const char *const a_base = p.qpack + (size_t)tile * PT * p.q_rb;
+    const int nct = (int)(((long long)re - rs + PT - 1) / PT);
+    const PairTileSrc a_src = {p.qpack + (size_t)tile * PT * p.q_rb, (unsigned)PT * p.q_rb};
     const char *const b_base = p.tok + (size_t)rs * p.rb;
-
-    int issued = 0, i_ct = 0, i_ks = 0;
-    auto issue = [&]() {
-        // ring item `issued` = K-slab i_ks of (the question tile, B tile i_ct of the walk)
-        const int b_left = re - rs - i_ct * PT;
-        const char *base = wave < 2 ? a_base : b_base + (size_t)i_ct * PT * p.rb;
-        const unsigned bytes = wave < 2 ? (unsigned)PT * p.q_rb : (unsigned)(b_left < PT ? b_left : PT) * p.rb;
-        pair_tile_issue(c, make_rsrc(base, bytes), issued % PT_NSTAGE, i_ks);
-        ++issued;
-        if (++i_ks == nk) {
-            i_ks = 0;
-            ++i_ct;
-        }
+    // (the question tile, B tile ct of the walk): the B side is the one that moves
+    const auto tile_src = [&](int ct) {
+        const int b_left = re - rs - ct * PT;
+        const PairTileSrc b_src = {b_base + (size_t)ct * PT * p.rb, (unsigned)(b_left < PT ? b_left : PT) * p.rb};
+        return wave < 2 ? a_src : b_src;
     };
 
     // running maxima of this lane's question rows wm * 64 + 16 a + 4 g4 + r over the open item's columns it has seen
     float bv[4][4];
-    f32x4_t acc[4][4];
-    pair_tile_clear(acc);
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
         for (int r = 0; r < 4; ++r) bv[a][r] = NEG_INF;
 
     int ci = i0;     // the first item not yet closed
-    issue();
-    int ks = 0, ct = 0;
-    for (int it = 0; it < total; ++it) {
-        wait_vmcnt<0>();     // two stages: item `it` is the only one in flight
-        __builtin_amdgcn_s_barrier();
-        if (issued < total) issue();
-        slab_step<DT>(smem + (it % PT_NSTAGE) * PT_STAGE, c, acc);
-        if (++ks < nk) continue;
-        pair_tile_settle<DT>();
-        // ---- the B tile is complete: acc[a][b][r] = <question row wm*64 + 16a + 4 g4 + r, plane row r0 + wn*64 + 16b + c16>
-        ks = 0;
+    // ---- acc[a][b][r] = <question row wm*64 + 16a + 4 g4 + r, plane row r0 + wn*64 + 16b + c16>
+    const auto tile_done = [&](int ct, const f32x4_t (&acc)[4][4]) {
         // columns are counted from the tile's first row r0 (r0 + 128 may not fit an int): the tile holds n_in rows
         const int r0 = rs + ct * PT;
         const int n_in = re - r0 < PT ? re - r0 : PT;
         const int col0 = wn * 64 + c16;
-        ++ct;
         while (ci < i1) {
             const int s = __builtin_amdgcn_readfirstlane(p.item_off[ci]);
             if (s >= re || s - r0 >= n_in) break;
@@ -332,8 +311,9 @@ __global__ __launch_bounds__(256, 2) void maxsim_scan_kernel(const MsScanParams 
             }
             ++ci;
         }
-        pair_tile_clear(acc);
-    }
+    };
+    // one ring per workgroup: no barrier after it
+    pair_tile_ring<DT>(c, smem, p.nk, nct, tile_src, tile_done);
 #endif
 }
 

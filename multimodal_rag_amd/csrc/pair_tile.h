@@ -1,12 +1,22 @@
-// The 128 x 128 "rows against rows" tile body of the similarity join (simjoin.hip) and of the k-means assign step
-// (kmeans.hip): A . B^T of a 128-row A tile and a 128-row B tile of stored rows, float32 accumulators in registers.
+// The 128 x 128 "rows against rows" tile body of every kernel that scores stored rows against a batch of rows: the
+// similarity join (simjoin.hip), the k-means assign step (kmeans.hip), the scoped, filtered, range, boosted, recommend
+// and related scans (scoped.hip, masked_scan.h, boosted.hip, recommend.hip, related.hip) and the two MaxSim kernels
+// (maxsim.hip, maxsim_scan.hip): A . B^T of a 128-row A tile and a 128-row B tile, float32 accumulators in registers.
 //
 // A workgroup is 4 waves in a 2 x 2 grid, 64 x 64 outputs per wave as 4 x 4 MFMA tiles of 16 x 16
 // (v_mfma_f32_16x16x32_f16 / _bf16; float32 rows: v_mfma_f32_16x16x4_f32, the exact float32 matrix instruction).  Both
 // operand tiles arrive by the tile_dma.h ring in 128-byte K-slabs: a stage is the A tile's slab then the B tile's
 // (2 x 16 KiB), two stages, so two workgroups share a CU.  Waves 0, 1 fetch the A tile, waves 2, 3 the B tile; rows
-// past the buffer descriptor's range read as zero.  The kernels keep what differs: which tiles, the ring loop, the
-// descriptors (the caller builds them) and the epilogue.
+// past the buffer descriptor's range read as zero.
+//
+// The ring loop is here too, once: pair_tile_ring runs a sequence of (A tile, B tile) pairs through the two stages
+// without draining between them and hands each finished pair's accumulators to the kernel.  Every kernel named above
+// but one calls it and has no wait, barrier or stage index of its own; they keep what differs: which tiles (the `src`
+// callback) and the epilogue (`done`).  The deliberate exception is sim_join_kernel, whose ring is one pair long: as
+// `done` its epilogue (64 accumulators tested and packed at once, 204 VGPRs) would sit inside the slab loop, and the
+// compiler then spills (256 VGPRs, 792 bytes of scratch per lane).  It keeps the one-pair loop it had.
+// The prologue the row-walking scans repeat -- a tile's geometry, which of its 128 rows are live, their group ordinals
+// -- is pair_row_tile / pair_tile_live_rows / pair_tile_row_ordinals.
 #pragma once
 #include "mmrag_internal.h"
 #include "tile_dma.h"
@@ -153,11 +163,122 @@ __device__ __forceinline__ void pair_tile_settle() {
     }
 }
 
+// The calling wave's operand of one (A tile, B tile) pair: waves 0, 1 name the A tile, waves 2, 3 the B tile.  `bytes`
+// end the buffer descriptor: rows at and past it read as zero.
+struct PairTileSrc {
+    const char *base;
+    unsigned bytes;
+};
+
+// The ring: `n_tiles` pairs of `nk` K-slabs each through the two stages, no drain between pairs.  `smem` and `c` are
+// pair_tile_ctx's.  For pair j = 0 .. n_tiles - 1
+//   src(j)         -> PairTileSrc, wave-uniform; called exactly once per pair, in order, before done(j) -- but a whole
+//                     slab ahead of the MFMAs, so src(j + 1) may be (with nk == 1: is) called before done(j);
+//   done(j, acc)   after pair j's last slab_step and pair_tile_settle: acc[a][b][r] = <A row wm*64 + 16a + 4 g4 + r,
+//                     B row wn*64 + 16b + c16> of pair j; the ring clears acc afterwards.
+// Either side may be the one that moves from pair to pair; the tile that stays is fetched again for each pair (L2).
+// Callbacks may keep state (a bitmask of wanted tiles popped once in each, a prefetch of pair j + 1 in done(j)) and may
+// diverge inside, but every wave of the workgroup must call the ring with the same nk and n_tiles: its barriers are
+// reached by all four waves or by none.  n_tiles == 0 does nothing.
+// THE CALLER'S: one workgroup barrier (__syncthreads) between the return and the next call's first slab, which would
+// otherwise land on a stage another wave is still reading.  A kernel that ends, or that has a barrier of its own on
+// that path, needs no second one.
+template <int DT, typename Src, typename Done>
+__device__ __forceinline__ void pair_tile_ring(const PairTileCtx &c, const char *smem, int nk, int n_tiles, Src &&src,
+                                               Done &&done) {
+    const int total = nk * n_tiles;
+    if (total <= 0) return;
+    int issued = 0, i_ks = 0, i_j = 0;
+    PairTileSrc from = {nullptr, 0u};
+    auto issue = [&]() {
+        // ring item `issued` = K-slab i_ks of pair i_j
+        if (i_ks == 0) from = src(i_j);
+        pair_tile_issue(c, make_rsrc(from.base, from.bytes), issued % PT_NSTAGE, i_ks);
+        ++issued;
+        if (++i_ks == nk) {
+            i_ks = 0;
+            ++i_j;
+        }
+    };
+
+    f32x4_t acc[4][4];
+    pair_tile_clear(acc);
+    issue();
+    int ks = 0, j = 0;
+    for (int it = 0; it < total; ++it) {
+        wait_vmcnt<0>();     // two stages: item `it` is the only one in flight
+        __builtin_amdgcn_s_barrier();
+        if (issued < total) issue();
+        slab_step<DT>(smem + (it % PT_NSTAGE) * PT_STAGE, c, acc);
+        if (++ks < nk) continue;
+        ks = 0;
+        pair_tile_settle<DT>();
+        done(j, acc);
+        ++j;
+        pair_tile_clear(acc);
+    }
+}
+
+// ---- the prologue of the kernels that walk 128-row tiles of the stored rows ----------------------------------------
+struct PairRowTile {
+    long long tile, row0;   // the tile and its first row
+    int rows;               // its rows below n: 1 .. 128
+};
+// step i of a walk over `walk` of the collection's T tiles, spread evenly: tile i * T / walk (walk == T: tile i)
+__device__ __forceinline__ PairRowTile pair_row_tile(long long i, long long T, long long walk, long long n) {
+    PairRowTile t;
+    t.tile = i * T / walk;           // < T
+    t.row0 = t.tile * PT;
+    const long long left = n - t.row0;      // >= 1
+    t.rows = left < PT ? (int)left : PT;
+    return t;
+}
+
+// Which of the tile's 128 rows are candidates (below n, alive; `alive` null: every row): each lane looks at rows
+// `lane` and `lane + 64`.  Bit i of m0 = row row0 + i is live, of m1 = row row0 + 64 + i: the same two scalars in
+// all four waves, so a branch on them is the workgroup's.
+__device__ __forceinline__ void pair_tile_live_rows(long long row0, int lane, long long n, const unsigned *alive,
+                                                    unsigned long long &m0, unsigned long long &m1) {
+    bool live[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const long long r = row0 + lane + 64 * h;
+        live[h] = r < n && (alive == nullptr || ((alive[r >> 5] >> (r & 31)) & 1u) != 0u);
+    }
+    m0 = __builtin_amdgcn_ballot_w64(live[0]);
+    m1 = __builtin_amdgcn_ballot_w64(live[1]);
+}
+
+// The ordinal-flavoured twin: ord[h] = the group ordinal of row row0 + lane + 64 h, -1 for a row past n, a dead row
+// and a row in no group (an ordinal outside 0 .. n_groups - 1)
+__device__ __forceinline__ void pair_tile_row_ordinals(long long row0, int lane, long long n, const unsigned *alive,
+                                                       const int *group_of_row, int n_groups, int (&ord)[2]) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const long long r = row0 + lane + 64 * h;
+        int o = -1;
+        if (r < n) {
+            o = group_of_row[r];
+            if (alive != nullptr && ((alive[r >> 5] >> (r & 31)) & 1u) == 0u) o = -1;
+            if ((unsigned)o >= (unsigned)n_groups) o = -1;
+        }
+        ord[h] = o;
+    }
+}
+
 // what an accumulator of DT operands is worth: E4M3 codes hold x * 256 on both sides
 template <int DT>
 constexpr float PT_ACC_SCALE = DT == MMRAG_F8E4M3 ? 0x1p-16f : 1.0f;
 
 // ---- host side ---------------------------------------------------------------------------------------------------
+// the persistent grid of a kernel that walks `walk` tiles: two workgroups per CU (PT_LDS allows two), at most one per
+// visited tile
+inline unsigned scan_grid(long long walk) {
+    long long g = 2LL * mmrag::num_cus();
+    if (g > walk) g = walk;
+    return (unsigned)g;
+}
+
 inline unsigned stored_row_bytes(int64_t ld, int dtype) { return (unsigned)(ld * mmrag::esize(dtype)); }
 // K-slabs that hold the d logical columns
 inline int stored_k_slabs(int d, int dtype) { return (int)(((long long)d * mmrag::esize(dtype) + SLAB - 1) / SLAB); }

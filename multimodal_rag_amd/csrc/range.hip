@@ -83,14 +83,9 @@ __global__ __launch_bounds__(256, 2) void range_scan_kernel(const RangeParams p)
 
 template <int DT>
 int launch_range_scan(const RangeParams &p, hipStream_t s) {
-    hipLaunchKernelGGL(range_scan_kernel<DT>, dim3(masked_scan_grid(p.walk)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(range_scan_kernel<DT>, dim3(scan_grid(p.walk)), dim3(256), 0, s, p);
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
-}
-
-// [the candidate select's blocks, limit > 0 only | the union bitmaps]
-inline size_t range_select_bytes(int B, long long n, int limit, long long cap) {
-    return limit > 0 ? candidate_ws_layout(B, cap, n, true).total : 0;
 }
 
 }  // namespace
@@ -104,7 +99,8 @@ extern "C" {
 // today the tables are the caller's outputs and the size does not depend on it.
 size_t mmrag_range_scan_workspace_bytes(int B, int64_t n, int limit, int facet_slots) {
     if (B <= 0 || n < 0 || n >= (1LL << 31) || limit < 0 || limit > MMRAG_MAX_K_DEEP || facet_slots < 0) return 0;
-    return range_select_bytes(B, n, limit, limit > 0 ? candidate_capacity(limit) : 0) + filtered_union_bytes(B, n) + 256;
+    // [the bounded scan's blocks, limit > 0 only | the union bitmaps]
+    return (limit > 0 ? bounded_scan_layout(B, n, limit, 0, false).select_bytes : 0) + filtered_union_bytes(B, n) + 256;
 }
 
 // mmrag_range_scan with a smaller candidate capacity (cap_override > 0) and debug switches (FI_DBG_NO_BOUND: no bound
@@ -152,121 +148,76 @@ int mmrag_internal_range_scan_ex(const void *q, const void *rows, int B, int64_t
     if (n_facets > 0) MMRAG_CHECK_HIP(hipMemsetAsync(out_facets, 0, (size_t)B * (size_t)stride * sizeof(unsigned), s));
     if (n == 0) return limit > 0 ? candidate_fill_empty(out_scores, (long long *)out_rows, B, limit, s) : MMRAG_OK;
 
-    BoundPlan pl;
-    pl.cap = 0;
-    pl.n_stages = 0;
-    if (limit > 0) pl = make_bound_plan(n, limit, cap_override, (dbg & FI_DBG_NO_BOUND) != 0u);
-    size_t sel_bytes = range_select_bytes(B, n, limit, pl.cap);
-    // the bound stages append into the slots of `limit` itself (candidate_select.h bound_stage_layout)
-    const long long stage_cap = pl.n_stages > 0 ? candidate_capacity(limit) : pl.cap;
-    CandWs wst = {};
-    if (pl.n_stages > 0) wst = bound_stage_layout(B, limit, n, candidate_ws_layout(B, pl.cap, n, true), &sel_bytes);
-    const size_t need = sel_bytes + (vis_bits != nullptr ? filtered_union_bytes(B, n) : 0);
-    if (need > 0 && (!workspace || workspace_bytes < need)) {
-        set_error("range_scan: workspace %zu bytes < required %zu", workspace_bytes, need);
-        return MMRAG_EWORKSPACE;
-    }
-    if (need > 0 && ((uintptr_t)workspace % 16) != 0) {
-        set_error("range_scan: workspace must be 16-byte aligned");
-        return MMRAG_EWORKSPACE;
-    }
-
-    char *ws = (char *)workspace;
-    unsigned *uni = vis_bits != nullptr ? (unsigned *)(ws + sel_bytes) : nullptr;
     p.rows = (const char *)rows;
-    p.q = (const char *)q;
     p.n = n;
-    p.B = B;
     p.row_bytes = stored_row_bytes(ld, dtype);
     p.nk = stored_k_slabs(d, dtype);
-    p.nqt = 0;
-    p.uni = uni;
     p.vis = vis_bits;
-    p.filter_of_query = filter_of_query;
     p.F = F;
     p.W = filter_words(n);
     p.T = (n + PT - 1) / PT;
-    p.walk = p.T;
     p.items = nullptr;
-    p.thr = threshold;
-    p.tau = nullptr;
-    p.out_count = nullptr;
-    p.out_facets = nullptr;
     p.n_facets = n_facets;
     p.facet_stride = stride;
-    p.cand_s = nullptr;
-    p.cand_r = nullptr;
-    p.cnt = nullptr;
-    p.cap = 0;
+    unsigned *uni = nullptr;      // with bitmaps: the batch's unions, then one query tile's for a re-run
+    const size_t union_bytes = vis_bits != nullptr ? filtered_union_bytes(B, n) : 0;
     const int nqt_all = (B + PT - 1) / PT;
-
-    // the unions of queries q0 .. q0 + Bq of the caller's batch into um[0 .. ceil(Bq / 128)); none without bitmaps
-    const auto unions = [&](int q0, int Bq, unsigned *um) -> int {
+    // the unions of the batch, once for every pass; none without bitmaps
+    const auto prepare = [&](char *extra) -> int {
         if (vis_bits == nullptr) return MMRAG_OK;
-        return launch_unions(filter_of_query + q0, Bq, F, vis_bits, p.W, um, s);
+        uni = (unsigned *)extra;
+        return launch_unions(filter_of_query, B, F, vis_bits, p.W, uni, s);
     };
-    // queries q0 .. q0 + Bq over `walk` tiles, their unions in um: scans of at most FI_MAX_QT query tiles each.
-    // `tables`: this is the main pass, the one that counts.  cand_s == null: no candidates are collected.
-    const auto produce = [&](int q0, int Bq, long long walk, const unsigned *um, bool tables, float *cand_s, int *cand_r,
+    // queries q0 .. q0 + Bq over `walk` tiles.  The main pass is the one that counts and tabulates; a query produced
+    // again alone gets its own unions.  cand_s == null: no candidates are collected.
+    const auto produce = [&](ScanPass pass, int q0, int Bq, long long walk, const float *tau, float *cand_s, int *cand_r,
                              unsigned *counts, long long slots) -> int {
-        return for_scan_chunks(Bq, [&](int first, int Bc, int nqt, int t0) -> int {
+        const unsigned *um = uni;
+        if (pass == SCAN_PASS_RERUN && uni != nullptr) {
+            unsigned *own = uni + (size_t)nqt_all * p.W;
+            if (int e = launch_unions(filter_of_query + q0, Bq, F, vis_bits, p.W, own, s)) return e;
+            um = own;
+        }
+        const bool tables = pass == SCAN_PASS_MAIN;
+        return for_scan_chunks(Bq, PT, [&](int first, int Bc, int nqt, int t0) -> int {
             RangeParams pc = p;
             const int c0 = q0 + first;
-            pc.q = p.q + (size_t)c0 * p.row_bytes;
+            pc.q = (const char *)q + (size_t)c0 * p.row_bytes;
             pc.filter_of_query = filter_of_query != nullptr ? filter_of_query + c0 : nullptr;
             pc.thr = threshold + c0;
-            pc.tau = p.tau != nullptr ? p.tau + c0 : nullptr;
+            pc.tau = tau != nullptr ? tau + c0 : nullptr;
             pc.B = Bc;
             pc.nqt = nqt;
             pc.uni = um != nullptr ? um + (size_t)t0 * p.W : nullptr;
             pc.walk = walk;
             pc.out_count = tables ? out_count + c0 : nullptr;
             pc.out_facets = tables && n_facets > 0 ? out_facets + (size_t)c0 * (size_t)stride : nullptr;
-            if (cand_s != nullptr) {
-                pc.cap = (unsigned)slots;
-                pc.cand_s = cand_s + (size_t)first * slots;
-                pc.cand_r = cand_r + (size_t)first * slots;
-                pc.cnt = counts + first;
-            }
+            pc.cap = (unsigned)slots;
+            pc.cand_s = cand_s != nullptr ? cand_s + (size_t)first * slots : nullptr;
+            pc.cand_r = cand_s != nullptr ? cand_r + (size_t)first * slots : nullptr;
+            pc.cnt = cand_s != nullptr ? counts + first : nullptr;
             return with_elem_type(dtype, [&](auto tag) { return launch_range_scan<decltype(tag)::value>(pc, s); });
         });
     };
 
-    // 1. the unions of the batch, once for every pass
-    if (int e = unions(0, B, uni)) return e;
-    // counts and facets only: one pass, nothing to select, nothing read back
-    if (limit == 0) return produce(0, B, p.T, uni, true, nullptr, nullptr, nullptr, 0);
-
-    const CandWs wl = candidate_ws_layout(B, pl.cap, n, true);
-    unsigned *cnt = (unsigned *)(ws + wl.off_cnt);
-    float *tau = (float *)(ws + wl.off_floats);
-    float *cand_s = (float *)(ws + wl.off_bs);
-    int *cand_r = (int *)(ws + wl.off_br);
-    // 2. bound passes: tau starts at the threshold and rises to the limit-th best visible sampled score above it
-    if (pl.n_stages > 0) {
-        MMRAG_CHECK_HIP(hipMemcpyAsync(tau, threshold, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
-        p.tau = tau;
+    if (limit == 0) {
+        // counts and facets only: one pass, nothing to select, nothing read back; the workspace holds the unions alone
+        if (union_bytes > 0 && (!workspace || workspace_bytes < union_bytes)) {
+            set_error("range_scan: workspace %zu bytes < required %zu", workspace_bytes, union_bytes);
+            return MMRAG_EWORKSPACE;
+        }
+        if (union_bytes > 0 && ((uintptr_t)workspace % 16) != 0) {
+            set_error("range_scan: workspace must be 16-byte aligned");
+            return MMRAG_EWORKSPACE;
+        }
+        if (int e = prepare((char *)workspace)) return e;
+        return produce(SCAN_PASS_MAIN, 0, B, p.T, nullptr, nullptr, nullptr, nullptr, 0);
     }
-    for (int st = 0; st < pl.n_stages; ++st) {
-        MMRAG_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)B * sizeof(unsigned), s));
-        float *st_s = (float *)(ws + wst.off_bs);
-        int *st_r = (int *)(ws + wst.off_br);
-        if (int e = produce(0, B, pl.stage_tiles[st], uni, false, st_s, st_r, cnt, stage_cap)) return e;
-        deep_select_kernel<<<B, SEL_THREADS, 0, s>>>(st_s, st_r, cnt, stage_cap, limit, 0, 1, nullptr, nullptr, tau);
-        MMRAG_CHECK_HIP(hipGetLastError());
-    }
-    // 3. main pass over every tile (the one that counts), select, and each query with more survivors than slots alone
-    //    with the same tau_q and no tables
-    return candidate_select(
-        "range_scan", B, n, pl.cap, limit, row_offset, out_scores, (long long *)out_rows, ws, wl, s,
-        [&](float *bs, int *br, unsigned *counts, long long slots) {
-            return produce(0, B, p.T, uni, true, bs, br, counts, slots);
-        },
-        [&](int qi, float *bs, int *br, unsigned *counts, long long slots) {
-            unsigned *um = uni != nullptr ? uni + (size_t)nqt_all * p.W : nullptr;
-            if (int e = unions(qi, 1, um)) return e;
-            return produce(qi, 1, p.T, um, false, bs, br, counts, slots);
-        });
+    // Hits are a top-`limit`: the bounded sequence with tau starting at the threshold.  Bound passes raise tau_q to the
+    // limit-th best visible sampled score above it; re-runs keep tau_q and touch no table.
+    return bounded_scan_select("range_scan", B, n, limit, cap_override, (dbg & FI_DBG_NO_BOUND) != 0u, row_offset,
+                               threshold, out_scores, (long long *)out_rows, workspace, workspace_bytes, union_bytes, s,
+                               prepare, produce);
 }
 
 int mmrag_range_scan(const void *q, const void *rows, int B, int64_t n, int d, int64_t ld, int dtype,

@@ -11,8 +11,9 @@
 //      most the true k-th final whatever the score function is, so the argument boosted.hip gives for its prior carries
 //      over to this score unchanged: tau_g stays a valid lower bound (-inf while fewer than k rows were seen).
 //   2. main pass: every tile, every live final >= tau_g appended as (final, local row) through the request's counter.
-//   3. select and overflow: candidate_select.h's driver, unchanged; an overflowed request is produced again alone (its
-//      16 example rows as a batch of one) with the same tau_g into n slots.
+//   3. select and overflow: an overflowed request is produced again alone (its 16 example rows as a batch of one)
+//      with the same tau_g into n slots.  Steps 1 to 3 are candidate_select.h's bounded_scan_select; this file
+//      supplies the producer.
 //   4. finish: pos, neg and the slots that gave them, recomputed per winner with row_dot.h's wave_row_dot.
 //
 // scan kernel: boosted_scan_kernel's structure with the operands swapped.  E . X^T with pair_tile.h's body, a
@@ -42,7 +43,6 @@ namespace {
 
 constexpr int RC_E = MMRAG_MAX_RECOMMEND_EXAMPLES;   // example slots of a request
 constexpr int RC_REQ_TILE = PT / RC_E;               // requests of a 128-example tile
-constexpr int RC_MAX_ET = 64;            // example tiles of one scan launch (512 requests), as boosted.hip cuts its batches
 static_assert(RC_E == 16 && RC_REQ_TILE == 8, "a request is one 16-row MFMA block");
 
 // debug switches of mmrag_internal_recommend_topk_ex (tests only)
@@ -57,7 +57,7 @@ struct RecommendParams {
     int R;
     unsigned row_bytes;     // ld * element size, of the rows and of the examples
     int nk;                 // K-slabs that hold the d logical columns
-    int net;                // example tiles, <= RC_MAX_ET
+    int net;                // example tiles, <= SCAN_MAX_TILES (512 requests)
     const unsigned *alive;
     const float *tau;       // [R], or null: -inf
     float *cand_s;
@@ -92,45 +92,18 @@ __global__ __launch_bounds__(256, 2) void recommend_scan_kernel(const RecommendP
     const unsigned RB = p.row_bytes;
     const PairTileCtx c = pair_tile_ctx(threadIdx.x, RB, smem);
     const int lane = c.lane, wave = c.wave, wm = c.wm, wn = c.wn, c16 = c.c16, g4 = c.g4;
-    const int nk = p.nk, net = p.net;
-    const int total = nk * net;
+    const int net = p.net;
     const long long n_ex = (long long)p.R * RC_E;
 
     for (long long i = blockIdx.x; i < p.walk; i += gridDim.x) {
-        const long long tile = i * p.T / p.walk;      // < T
-        const long long row0 = tile * PT;
-        const long long left = p.n - row0;            // >= 1
-        const int in_tile = left < PT ? (int)left : PT;
-
-        // whether rows `lane` and `lane + 64` of the tile are candidates (below n, alive)
-        bool live[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const long long r = row0 + lane + 64 * h;
-            live[h] = r < p.n && (p.alive == nullptr || ((p.alive[r >> 5] >> (r & 31)) & 1u) != 0u);
-        }
-        // bit i of m0 = row i is live, of m1 = row 64 + i: the same two scalars in all four waves
-        const unsigned long long m0 = __builtin_amdgcn_ballot_w64(live[0]);
-        const unsigned long long m1 = __builtin_amdgcn_ballot_w64(live[1]);
+        const PairRowTile rt = pair_row_tile(i, p.T, p.walk, p.n);
+        const long long row0 = rt.row0;
+        unsigned long long m0, m1;
+        pair_tile_live_rows(row0, lane, p.n, p.alive, m0, m1);
         // uniform: the whole workgroup takes this path; nothing was fetched, no LDS is touched
         if ((m0 | m1) == 0ull) continue;
 
-        const char *const rows_base = p.rows + (size_t)row0 * RB;
-        const unsigned rows_bytes = (unsigned)in_tile * RB;
-        int issued = 0, i_ks = 0, i_et = 0;
-        auto issue = [&]() {
-            // ring item `issued` = K-slab i_ks of (example tile i_et, this row tile); waves 0, 1 fetch the A tile
-            const long long e_left = n_ex - (long long)i_et * PT;
-            const char *base = wave < 2 ? p.ex + (size_t)i_et * PT * RB : rows_base;
-            const unsigned bytes = wave < 2 ? (unsigned)(e_left < PT ? e_left : PT) * RB : rows_bytes;
-            pair_tile_issue(c, make_rsrc(base, bytes), issued % PT_NSTAGE, i_ks);
-            ++issued;
-            if (++i_ks == nk) {
-                i_ks = 0;
-                ++i_et;
-            }
-        };
-
+        const PairTileSrc rows_src = {p.rows + (size_t)row0 * RB, (unsigned)rt.rows * RB};
         const unsigned long long mw = wn ? m1 : m0;      // this wave's 64 stored-row columns
         // bit b of `vis` = column 16 b + c16 of the wave's 64 is live
         unsigned vis = 0;
@@ -154,19 +127,14 @@ __global__ __launch_bounds__(256, 2) void recommend_scan_kernel(const RecommendP
             }
         };
 
-        f32x4_t acc[4][4];
-        pair_tile_clear(acc);
-        issue();
-        fetch_requests(0);
-        int ks = 0, et = 0;
-        for (int it = 0; it < total; ++it) {
-            wait_vmcnt<0>();     // two stages: item `it` is the only one in flight
-            __builtin_amdgcn_s_barrier();
-            if (issued < total) issue();
-            slab_step<DT>(smem + (it % PT_NSTAGE) * PT_STAGE, c, acc);
-            if (++ks < nk) continue;
-            // ---- the example tile is complete: acc[a][b][r] = <example wm*64 + 16a + 4 g4 + r, row col 16b + c16>
-            ks = 0;
+        // (example tile et, this row tile): the A side is the one that moves
+        const auto tile_src = [&](int et) {
+            const long long e_left = n_ex - (long long)et * PT;
+            const PairTileSrc ex_src = {p.ex + (size_t)et * PT * RB, (unsigned)(e_left < PT ? e_left : PT) * RB};
+            return wave < 2 ? ex_src : rows_src;
+        };
+        // ---- acc[a][b][r] = <example et * 128 + wm*64 + 16a + 4 g4 + r, row col 16b + c16>
+        const auto tile_done = [&](int et, const f32x4_t (&acc)[4][4]) {
             if (mw != 0ull) {       // wave-uniform: every lane takes part in the shuffles below
                 const int req_w = et * RC_REQ_TILE + wm * 4;    // request of this wave's block a = 0
                 // in-lane: the sign-masked maxima over this lane's four slots 4 g4 .. 4 g4 + 3 of request a, column b
@@ -251,10 +219,12 @@ __global__ __launch_bounds__(256, 2) void recommend_scan_kernel(const RecommendP
                     }
                 }
             }
-            if (++et < net) fetch_requests(et);
-            pair_tile_clear(acc);
-        }
-        __syncthreads();   // every wave is done with the ring before the next tile's first slab lands
+            // the next example tile's request words, a whole tile of K-slabs ahead of their use
+            if (et + 1 < net) fetch_requests(et + 1);
+        };
+        fetch_requests(0);
+        pair_tile_ring<DT>(c, smem, p.nk, net, tile_src, tile_done);
+        __syncthreads();   // the ring's contract: every wave is done with it before the next tile's first slab lands
     }
 #endif
 }
@@ -304,9 +274,7 @@ __global__ __launch_bounds__(256) void recommend_finish_kernel(const long long *
 
 template <int DT>
 int launch_scan(const RecommendParams &p, hipStream_t s) {
-    long long g = 2LL * num_cus();    // persistent grid: two workgroups per CU (the LDS allows two)
-    if (g > p.walk) g = p.walk;
-    hipLaunchKernelGGL(recommend_scan_kernel<DT>, dim3((unsigned)g), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(recommend_scan_kernel<DT>, dim3(scan_grid(p.walk)), dim3(256), 0, s, p);
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
 }
@@ -320,7 +288,7 @@ extern "C" {
 
 size_t mmrag_recommend_topk_workspace_bytes(int R, int64_t n, int k) {
     if (R <= 0 || R > (1 << 20) || n < 0 || n >= (1LL << 31) || k < 1 || k > MMRAG_MAX_K_DEEP) return 0;
-    return candidate_ws_layout(R, candidate_capacity(k), n, true).total;
+    return bounded_scan_layout(R, n, k, 0, false).select_bytes;
 }
 
 // mmrag_recommend_topk with a smaller candidate capacity (cap_override > 0) and debug switches (RC_DBG_*): the tests
@@ -359,90 +327,37 @@ int mmrag_internal_recommend_topk_ex(const void *examples, const int8_t *sign, c
         return finish();     // every row is -1: all padding
     }
 
-    const BoundPlan pl = make_bound_plan(n, k, cap_override, (dbg & RC_DBG_NO_BOUND) != 0u);
-    const CandWs wl = candidate_ws_layout(R, pl.cap, n, true);
-    size_t ws_need = wl.total;
-    const CandWs wst = pl.n_stages > 0 ? bound_stage_layout(R, k, n, wl, &ws_need) : wl;
-    const long long stage_cap = pl.n_stages > 0 ? candidate_capacity(k) : pl.cap;
-    if (!workspace || workspace_bytes < ws_need) {
-        set_error("recommend_topk: workspace %zu bytes < required %zu", workspace_bytes, ws_need);
-        return MMRAG_EWORKSPACE;
-    }
-    if (((uintptr_t)workspace % 16) != 0) {
-        set_error("recommend_topk: workspace must be 16-byte aligned");
-        return MMRAG_EWORKSPACE;
-    }
-
-    char *ws = (char *)workspace;
-    unsigned *cnt = (unsigned *)(ws + wl.off_cnt);
-    float *tau = (float *)(ws + wl.off_floats);
     RecommendParams p;
     p.rows = (const char *)rows;
-    p.ex = (const char *)examples;
-    p.sign = (const signed char *)sign;
-    p.negw = neg_weight;
     p.n = n;
-    p.R = R;
     p.row_bytes = stored_row_bytes(ld, dtype);
     p.nk = stored_k_slabs(d, dtype);
-    p.net = 0;
     p.alive = alive_bits;
-    p.tau = nullptr;
-    p.cand_s = (float *)(ws + wl.off_bs);
-    p.cand_r = (int *)(ws + wl.off_br);
-    p.cnt = cnt;
-    p.cap = (unsigned)pl.cap;
     p.T = (n + PT - 1) / PT;
-    p.walk = p.T;
-
-    // requests g0 .. g0 + Rq of the caller's batch over `walk` tiles into their slots: scans of at most RC_MAX_ET
-    // example tiles each.  A request alone is its 16 example rows as a batch of one.
-    const auto produce = [&](int g0, int Rq, long long walk, float *cand_s, int *cand_r, unsigned *counts,
-                             long long slots) -> int {
-        const int tiles = (Rq + RC_REQ_TILE - 1) / RC_REQ_TILE;
-        for (int t0 = 0; t0 < tiles; t0 += RC_MAX_ET) {
+    // requests g0 .. g0 + Rq of the caller's batch over `walk` tiles into their slots.  A request alone is its 16
+    // example rows as a batch of one.
+    const auto produce = [&](ScanPass, int g0, int Rq, long long walk, const float *tau, float *cand_s, int *cand_r,
+                             unsigned *counts, long long slots) -> int {
+        return for_scan_chunks(Rq, RC_REQ_TILE, [&](int first, int Rc, int net, int) -> int {
             RecommendParams pc = p;
-            const int done = t0 * RC_REQ_TILE;      // requests of the earlier launches
-            const int c0 = g0 + done;
-            pc.ex = p.ex + (size_t)c0 * RC_E * p.row_bytes;
-            pc.sign = p.sign + (size_t)c0 * RC_E;
+            const int c0 = g0 + first;
+            pc.ex = (const char *)examples + (size_t)c0 * RC_E * p.row_bytes;
+            pc.sign = (const signed char *)sign + (size_t)c0 * RC_E;
             pc.negw = neg_weight + c0;
-            pc.tau = p.tau != nullptr ? p.tau + c0 : nullptr;
-            pc.R = Rq - done < RC_MAX_ET * RC_REQ_TILE ? Rq - done : RC_MAX_ET * RC_REQ_TILE;
-            pc.net = (pc.R + RC_REQ_TILE - 1) / RC_REQ_TILE;
+            pc.tau = tau != nullptr ? tau + c0 : nullptr;
+            pc.R = Rc;
+            pc.net = net;
             pc.walk = walk;
             pc.cap = (unsigned)slots;
-            pc.cand_s = cand_s + (size_t)done * slots;
-            pc.cand_r = cand_r + (size_t)done * slots;
-            pc.cnt = counts + done;
-            if (int st = with_elem_type(dtype, [&](auto tag) { return launch_scan<decltype(tag)::value>(pc, s); }))
-                return st;
-        }
-        return MMRAG_OK;
+            pc.cand_s = cand_s + (size_t)first * slots;
+            pc.cand_r = cand_r + (size_t)first * slots;
+            pc.cnt = counts + first;
+            return with_elem_type(dtype, [&](auto tag) { return launch_scan<decltype(tag)::value>(pc, s); });
+        });
     };
-
-    // 1. bound passes (tau starts at -inf: the bit pattern 0xff800000)
-    if (pl.n_stages > 0) {
-        MMRAG_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)tau, (int)0xff800000u, (size_t)R, s));
-        p.tau = tau;
-    }
-    for (int st = 0; st < pl.n_stages; ++st) {
-        MMRAG_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)R * sizeof(unsigned), s));
-        float *st_s = (float *)(ws + wst.off_bs);
-        int *st_r = (int *)(ws + wst.off_br);
-        if (int e = produce(0, R, pl.stage_tiles[st], st_s, st_r, cnt, stage_cap)) return e;
-        deep_select_kernel<<<R, SEL_THREADS, 0, s>>>(st_s, st_r, cnt, stage_cap, k, 0, 1, nullptr, nullptr, tau);
-        MMRAG_CHECK_HIP(hipGetLastError());
-    }
-    // 2. main pass over every tile, 3. select, 4. each request with more survivors than slots alone, same tau_g
-    if (int st = candidate_select(
-            "recommend_topk", R, n, pl.cap, k, row_offset, out_scores, (long long *)out_rows, ws, wl, s,
-            [&](float *cand_s, int *cand_r, unsigned *counts, long long slots) {
-                return produce(0, R, p.T, cand_s, cand_r, counts, slots);
-            },
-            [&](int gi, float *cand_s, int *cand_r, unsigned *counts, long long slots) {
-                return produce(gi, 1, p.T, cand_s, cand_r, counts, slots);
-            }))
+    if (int st = bounded_scan_select("recommend_topk", R, n, k, cap_override, (dbg & RC_DBG_NO_BOUND) != 0u, row_offset,
+                                     nullptr, out_scores, (long long *)out_rows, workspace, workspace_bytes, 0, s,
+                                     [](char *) { return MMRAG_OK; }, produce))
         return st;
     return finish();
 }

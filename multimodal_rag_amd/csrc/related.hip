@@ -35,10 +35,9 @@ namespace mmrag_impl {
 
 namespace {
 
-constexpr int RL_MAX_QT = 64;       // column tiles of one scan launch (scoped.hip's SC_MAX_QT)
 constexpr int RL_MAX_ROWS = MMRAG_MAX_RELATED_ROWS;
 constexpr int RL_MAX_SETS = MMRAG_MAX_RELATED_SETS;
-static_assert(RL_MAX_ROWS == RL_MAX_QT * PT, "one scan launch holds every column tile");
+static_assert(RL_MAX_ROWS == SCAN_MAX_TILES * PT, "one scan launch holds every column tile");
 
 struct RelatedParams {
     const char *rows;
@@ -47,7 +46,7 @@ struct RelatedParams {
     int M;
     unsigned row_bytes;     // ld * element size, of the rows and of the columns
     int nk;                 // K-slabs that hold the d logical columns
-    int nqt;                // column tiles, <= RL_MAX_QT
+    int nqt;                // column tiles, <= SCAN_MAX_TILES
     const unsigned *alive;
     const int *group_of_row;
     int n_groups;
@@ -69,61 +68,28 @@ __global__ __launch_bounds__(256, 2) void related_scan_kernel(const RelatedParam
     const unsigned RB = p.row_bytes;
     const PairTileCtx c = pair_tile_ctx(threadIdx.x, RB, smem);
     const int lane = c.lane, wave = c.wave, wm = c.wm, wn = c.wn, c16 = c.c16, g4 = c.g4;
-    const int nk = p.nk, nqt = p.nqt;
     const size_t NG = (size_t)p.n_groups;
 
     for (long long tile = blockIdx.x; tile < p.T; tile += gridDim.x) {
-        const long long row0 = tile * PT;
-        const long long left = p.n - row0;            // >= 1
-        const int in_tile = left < PT ? (int)left : PT;
-
+        const PairRowTile rt = pair_row_tile(tile, p.T, p.T, p.n);
+        const long long row0 = rt.row0;
         // ordinals of rows `lane` and `lane + 64` of the tile: -1 = past n, dead, in no group
         int ord[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const long long r = row0 + lane + 64 * h;
-            int o = -1;
-            if (r < p.n) {
-                o = p.group_of_row[r];
-                if (p.alive != nullptr && ((p.alive[r >> 5] >> (r & 31)) & 1u) == 0u) o = -1;
-                if ((unsigned)o >= (unsigned)p.n_groups) o = -1;
-            }
-            ord[h] = o;
-        }
+        pair_tile_row_ordinals(row0, lane, p.n, p.alive, p.group_of_row, p.n_groups, ord);
         // uniform (the same two ballots in all four waves): no candidate row, nothing is fetched, no LDS is touched
         const unsigned long long m0 = __builtin_amdgcn_ballot_w64(ord[0] >= 0);
         const unsigned long long m1 = __builtin_amdgcn_ballot_w64(ord[1] >= 0);
         if ((m0 | m1) == 0ull) continue;
 
-        const char *const rows_base = p.rows + (size_t)row0 * RB;
-        const unsigned rows_bytes = (unsigned)in_tile * RB;
-        const int total = nk * nqt;
-        int issued = 0, i_ks = 0, i_qt = 0;
-        auto issue = [&]() {
-            // ring item `issued` = K-slab i_ks of (this row tile, column tile i_qt)
-            const int q_left = p.M - i_qt * PT;
-            const char *base = wave < 2 ? rows_base : p.q + (size_t)i_qt * PT * RB;
-            const unsigned bytes = wave < 2 ? rows_bytes : (unsigned)(q_left < PT ? q_left : PT) * RB;
-            pair_tile_issue(c, make_rsrc(base, bytes), issued % PT_NSTAGE, i_ks);
-            ++issued;
-            if (++i_ks == nk) {
-                i_ks = 0;
-                ++i_qt;
-            }
+        const PairTileSrc rows_src = {p.rows + (size_t)row0 * RB, (unsigned)rt.rows * RB};
+        // (this row tile, column tile qt)
+        const auto tile_src = [&](int qt) {
+            const int q_left = p.M - qt * PT;
+            const PairTileSrc q_src = {p.q + (size_t)qt * PT * RB, (unsigned)(q_left < PT ? q_left : PT) * RB};
+            return wave < 2 ? rows_src : q_src;
         };
-
-        f32x4_t acc[4][4];
-        pair_tile_clear(acc);
-        issue();
-        int ks = 0, qt = 0;
-        for (int it = 0; it < total; ++it) {
-            wait_vmcnt<0>();     // two stages: item `it` is the only one in flight
-            __builtin_amdgcn_s_barrier();
-            if (issued < total) issue();
-            slab_step<DT>(smem + (it % PT_NSTAGE) * PT_STAGE, c, acc);
-            if (++ks < nk) continue;
-            // ---- the column tile is complete: acc[a][b][r] = <row wm*64 + 16a + 4 g4 + r, column col0 + 16b>
-            ks = 0;
+        // ---- acc[a][b][r] = <row wm*64 + 16a + 4 g4 + r, column qt * 128 + wn*64 + 16b + c16>
+        const auto tile_done = [&](int qt, const f32x4_t (&acc)[4][4]) {
             const unsigned long long mw = wm ? m1 : m0;      // this wave's 64 rows
             const int ow = wm ? ord[1] : ord[0];
             if (mw != 0ull) {
@@ -159,19 +125,17 @@ __global__ __launch_bounds__(256, 2) void related_scan_kernel(const RelatedParam
                     if (run >= 0) atomicMax(cell + run, best);
                 }
             }
-            ++qt;
-            pair_tile_clear(acc);
-        }
-        __syncthreads();   // every wave is done with the ring before the next tile's first slab lands
+        };
+        pair_tile_ring<DT>(c, smem, p.nk, p.nqt, tile_src, tile_done);
+        __syncthreads();   // the ring's contract: every wave is done with it before the next tile's first slab lands
     }
 #endif
 }
 
 template <int DT>
 int launch_scan(const RelatedParams &p, long long grid, hipStream_t s) {
-    long long g = grid > 0 ? grid : 2LL * num_cus();    // persistent grid: two workgroups per CU (the LDS allows two)
-    if (g > p.T) g = p.T;
-    hipLaunchKernelGGL(related_scan_kernel<DT>, dim3((unsigned)g), dim3(256), 0, s, p);
+    const unsigned g = grid > 0 ? (unsigned)(grid < p.T ? grid : p.T) : scan_grid(p.T);   // `grid`: the test's
+    hipLaunchKernelGGL(related_scan_kernel<DT>, dim3(g), dim3(256), 0, s, p);
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
 }

@@ -27,8 +27,6 @@ namespace mmrag_impl {
 
 namespace {
 
-constexpr int SC_MAX_QT = 64;    // query tiles of one scan launch: their "wanted" flags are one 64-bit mask
-
 struct ScopedParams {
     const char *rows;
     const char *q;
@@ -36,7 +34,7 @@ struct ScopedParams {
     int B;
     unsigned row_bytes;     // ld * element size, of the rows and of the queries
     int nk;                 // K-slabs that hold the d logical columns
-    int nqt;                // query tiles, <= SC_MAX_QT
+    int nqt;                // query tiles, <= SCAN_MAX_TILES
     const unsigned *alive;
     const int *group_of_row;
     int n_groups;
@@ -78,26 +76,14 @@ __global__ __launch_bounds__(256, 2) void scoped_scan_kernel(const ScopedParams 
     const unsigned RB = p.row_bytes;
     const PairTileCtx c = pair_tile_ctx(threadIdx.x, RB, smem);
     const int lane = c.lane, wave = c.wave, wm = c.wm, wn = c.wn, c16 = c.c16, g4 = c.g4;
-    const int nk = p.nk, nqt = p.nqt, W = p.W;
+    const int nqt = p.nqt, W = p.W;
 
     for (long long tile = blockIdx.x; tile < p.T; tile += gridDim.x) {
-        const long long row0 = tile * PT;
-        const long long left = p.n - row0;            // >= 1
-        const int in_tile = left < PT ? (int)left : PT;
-
+        const PairRowTile rt = pair_row_tile(tile, p.T, p.T, p.n);
+        const long long row0 = rt.row0;
         // ordinals of rows `lane` and `lane + 64` of the tile: -1 = past n, dead, in no group
         int ord[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const long long r = row0 + lane + 64 * h;
-            int o = -1;
-            if (r < p.n) {
-                o = p.group_of_row[r];
-                if (p.alive != nullptr && ((p.alive[r >> 5] >> (r & 31)) & 1u) == 0u) o = -1;
-                if ((unsigned)o >= (unsigned)p.n_groups) o = -1;
-            }
-            ord[h] = o;
-        }
+        pair_tile_row_ordinals(row0, lane, p.n, p.alive, p.group_of_row, p.n_groups, ord);
         // rows of the tile that query tile qt's union bitmap holds: bit i of m0 = row i, of m1 = row 64 + i.  The same
         // two scalars in all four waves.
         auto wanted = [&](int qt, unsigned long long &m0, unsigned long long &m1) {
@@ -118,38 +104,18 @@ __global__ __launch_bounds__(256, 2) void scoped_scan_kernel(const ScopedParams 
         // uniform: the whole workgroup takes this path; nothing was fetched, no LDS is touched
         if (active == 0ull) continue;
 
-        const char *const rows_base = p.rows + (size_t)row0 * RB;
-        const unsigned rows_bytes = (unsigned)in_tile * RB;
-        const int total = nk * __popcll(active);
-        unsigned long long i_left = active;
-        int issued = 0, i_ks = 0;
-        auto issue = [&]() {
-            // ring item `issued` = K-slab i_ks of (this row tile, the lowest query tile left in i_left)
+        const PairTileSrc rows_src = {p.rows + (size_t)row0 * RB, (unsigned)rt.rows * RB};
+        // the ring runs over the wanted query tiles, lowest first: each callback pops its own copy of the mask
+        unsigned long long i_left = active, c_left = active;
+        const auto tile_src = [&](int) {
             const int qt = __builtin_ctzll(i_left);
+            i_left &= i_left - 1;
             const int q_left = p.B - qt * PT;
-            const char *base = wave < 2 ? rows_base : p.q + (size_t)qt * PT * RB;
-            const unsigned bytes = wave < 2 ? rows_bytes : (unsigned)(q_left < PT ? q_left : PT) * RB;
-            pair_tile_issue(c, make_rsrc(base, bytes), issued % PT_NSTAGE, i_ks);
-            ++issued;
-            if (++i_ks == nk) {
-                i_ks = 0;
-                i_left &= i_left - 1;
-            }
+            const PairTileSrc q_src = {p.q + (size_t)qt * PT * RB, (unsigned)(q_left < PT ? q_left : PT) * RB};
+            return wave < 2 ? rows_src : q_src;
         };
-
-        f32x4_t acc[4][4];
-        pair_tile_clear(acc);
-        unsigned long long c_left = active;
-        issue();
-        int ks = 0;
-        for (int it = 0; it < total; ++it) {
-            wait_vmcnt<0>();     // two stages: item `it` is the only one in flight
-            __builtin_amdgcn_s_barrier();
-            if (issued < total) issue();
-            slab_step<DT>(smem + (it % PT_NSTAGE) * PT_STAGE, c, acc);
-            if (++ks < nk) continue;
-            // ---- the query tile is complete: acc[a][b][r] = <row wm*64 + 16a + 4 g4 + r, query col0 + 16b>
-            ks = 0;
+        // ---- acc[a][b][r] = <row wm*64 + 16a + 4 g4 + r, query qt * 128 + wn*64 + 16b + c16>
+        const auto tile_done = [&](int, const f32x4_t (&acc)[4][4]) {
             const int qt = __builtin_ctzll(c_left);
             c_left &= c_left - 1;
             unsigned long long m0, m1;
@@ -220,18 +186,16 @@ __global__ __launch_bounds__(256, 2) void scoped_scan_kernel(const ScopedParams 
                             }
                 }
             }
-            pair_tile_clear(acc);
-        }
-        __syncthreads();   // every wave is done with the ring before the next tile's first slab lands
+        };
+        pair_tile_ring<DT>(c, smem, p.nk, __popcll(active), tile_src, tile_done);
+        __syncthreads();   // the ring's contract: every wave is done with it before the next tile's first slab lands
     }
 #endif
 }
 
 template <int DT>
 int launch_scan(const ScopedParams &p, hipStream_t s) {
-    long long g = 2LL * num_cus();    // persistent grid: two workgroups per CU (the LDS allows two)
-    if (g > p.T) g = p.T;
-    hipLaunchKernelGGL(scoped_scan_kernel<DT>, dim3((unsigned)g), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(scoped_scan_kernel<DT>, dim3(scan_grid(p.T)), dim3(256), 0, s, p);
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
 }
@@ -313,8 +277,7 @@ int mmrag_internal_scoped_topk_ex(const void *q, const void *rows, int B, int64_
     p.T = (n + PT - 1) / PT;
     const int nqt_all = (B + PT - 1) / PT;
 
-    // queries q0 .. q0 + Bq of the caller's batch into their slots: the unions into `bm`, then scans of at most
-    // SC_MAX_QT query tiles each
+    // queries q0 .. q0 + Bq of the caller's batch into their slots: the unions into `bm`, then the scans
     const auto produce = [&](int q0, int Bq, unsigned *bm, float *cand_s, int *cand_r, unsigned *counts,
                              long long slots) -> int {
         ScopedParams pq = p;
@@ -326,21 +289,18 @@ int mmrag_internal_scoped_topk_ex(const void *q, const void *rows, int B, int64_
         MMRAG_CHECK_HIP(hipMemsetAsync(bm, 0, (size_t)tiles * p.W * sizeof(unsigned), s));
         hipLaunchKernelGGL(scoped_union_kernel, dim3((unsigned)tiles), dim3(PT), 0, s, pq, bm);
         MMRAG_CHECK_HIP(hipGetLastError());
-        for (int t0 = 0; t0 < tiles; t0 += SC_MAX_QT) {
+        return for_scan_chunks(Bq, PT, [&](int first, int Bc, int nqt, int t0) -> int {
             ScopedParams pc = pq;
-            const int c0 = t0 * PT;
-            pc.q = pq.q + (size_t)c0 * p.row_bytes;
-            pc.scope_of_query = pq.scope_of_query + c0;
-            pc.B = Bq - c0 < SC_MAX_QT * PT ? Bq - c0 : SC_MAX_QT * PT;
-            pc.nqt = (pc.B + PT - 1) / PT;
+            pc.q = pq.q + (size_t)first * p.row_bytes;
+            pc.scope_of_query = pq.scope_of_query + first;
+            pc.B = Bc;
+            pc.nqt = nqt;
             pc.bitmap = bm + (size_t)t0 * p.W;
-            pc.cand_s = cand_s + (size_t)c0 * slots;
-            pc.cand_r = cand_r + (size_t)c0 * slots;
-            pc.cnt = counts + c0;
-            if (int st = with_elem_type(dtype, [&](auto tag) { return launch_scan<decltype(tag)::value>(pc, s); }))
-                return st;
-        }
-        return MMRAG_OK;
+            pc.cand_s = cand_s + (size_t)first * slots;
+            pc.cand_r = cand_r + (size_t)first * slots;
+            pc.cnt = counts + first;
+            return with_elem_type(dtype, [&](auto tag) { return launch_scan<decltype(tag)::value>(pc, s); });
+        });
     };
     // the driver's n: no scope holds more rows than this, so a re-run of one query fits max_candidates slots
     const long long n_sel = max_candidates < n ? max_candidates : n;

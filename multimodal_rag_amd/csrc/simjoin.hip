@@ -112,6 +112,8 @@ __global__ __launch_bounds__(256, 2) void sim_join_kernel(const JoinParams p) {
             make_rsrc(p.rows + (size_t)my_row0 * RB, (unsigned)((left < PT ? left : (long long)PT) * (long long)RB));
         auto issue = [&](int item) { pair_tile_issue(c, rsrc, item % PT_NSTAGE, item); };   // ring item = K-slab
 
+        // the one-pair ring, kept here and not pair_tile_ring's: the epilogue below must stay outside the slab loop
+        // (pair_tile.h's header has the figures)
         f32x4_t acc[4][4];
         pair_tile_clear(acc);
 
@@ -216,10 +218,8 @@ __global__ __launch_bounds__(256, 2) void sim_join_kernel(const JoinParams p) {
 template <int DT>
 static int launch_join(const JoinParams &p, hipStream_t s) {
     // persistent grid: two workgroups per CU (the LDS allows two), a multiple of 8 so every XCD runs whole slot runs
-    long long g = 2LL * mmrag::num_cus();
-    if (g > p.total) g = p.total;
-    g = (g + 7) / 8 * 8;
-    hipLaunchKernelGGL(sim_join_kernel<DT>, dim3((unsigned)g), dim3(256), 0, s, p);
+    const unsigned g = (scan_grid(p.total) + 7) / 8 * 8;
+    hipLaunchKernelGGL(sim_join_kernel<DT>, dim3(g), dim3(256), 0, s, p);
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
 }
