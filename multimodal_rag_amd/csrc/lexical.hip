@@ -34,6 +34,7 @@ constexpr int SCORE_R = 2048;           // rows per scoring workgroup (8 KiB LDS
 constexpr int SCORE_TERMS = 128;        // query terms whose postings ranges are looked up together
 constexpr int SORT_LDS = 8192;          // postings a term sorts in LDS (32 KiB); longer lists use the row bitmap
 constexpr int SORT_GRID = 256;          // workgroups of the per-term sort (each owns one row bitmap)
+constexpr int SCAN_TERMS = 1024;        // terms the one-workgroup scan takes per step (one per thread)
 
 __device__ inline long long lower_bound_rows(const int *__restrict__ rows, long long lo, long long hi, int x) {
     while (lo < hi) {
@@ -64,16 +65,16 @@ __global__ __launch_bounds__(LEX_THREADS) void csr_hist_kernel(const int *__rest
         atomicAdd(&cnt[fwd_term[p]], 1u);
 }
 
-// term_off = exclusive scan of cnt (term_off[V] = P), cursor = term_off[0 .. V): one workgroup of 1024 threads
-__global__ __launch_bounds__(1024) void csr_scan_kernel(const unsigned *__restrict__ cnt, int V,
-                                                        long long *__restrict__ term_off,
-                                                        unsigned long long *__restrict__ cursor) {
-    __shared__ long long wsum[16];
+// term_off = exclusive scan of cnt (term_off[V] = P), cursor = term_off[0 .. V): one workgroup of SCAN_TERMS threads
+__global__ __launch_bounds__(SCAN_TERMS) void csr_scan_kernel(const unsigned *__restrict__ cnt, int V,
+                                                              long long *__restrict__ term_off,
+                                                              unsigned long long *__restrict__ cursor) {
+    __shared__ long long wsum[SCAN_TERMS / 64];
     __shared__ long long carry;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     if (tid == 0) carry = 0;
     __syncthreads();
-    for (int base = 0; base < V; base += 1024) {
+    for (int base = 0; base < V; base += SCAN_TERMS) {
         const int t = base + tid;
         const long long v = t < V ? cnt[t] : 0;
         long long incl = v;
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(1024) void csr_scan_kernel(const unsigned *__restri
             cursor[t] = (unsigned long long)(before + incl - v);
         }
         __syncthreads();
-        if (tid == 1023) carry = before + incl;
+        if (tid == SCAN_TERMS - 1) carry = before + incl;
         __syncthreads();
     }
     if (tid == 0) term_off[V] = carry;
@@ -366,7 +367,7 @@ int mmrag_lexical_csr_build(const int64_t *fwd_off, const int32_t *fwd_term, con
         csr_hist_kernel<<<(unsigned)(g < 8192 ? g : 8192), LEX_THREADS, 0, s>>>(fwd_term, n_postings, cnt);
         MMRAG_CHECK_HIP(hipGetLastError());
     }
-    csr_scan_kernel<<<1, 1024, 0, s>>>(cnt, n_terms, (long long *)term_off, cursor);
+    csr_scan_kernel<<<1, SCAN_TERMS, 0, s>>>(cnt, n_terms, (long long *)term_off, cursor);
     MMRAG_CHECK_HIP(hipGetLastError());
     if (n_postings == 0) return MMRAG_OK;
     const long long per = LEX_THREADS / 64;
@@ -459,6 +460,20 @@ int mmrag_rows_dot(const void *q, const void *corpus, int64_t ld, int dtype, int
     });
     MMRAG_CHECK_HIP(hipGetLastError());
     return MMRAG_OK;
+}
+
+// The sizes at which the kernels above change path: rows per scoring workgroup, query terms per lookup chunk, the longest
+// postings list sorted in LDS, the sort's grid and the scan's terms per step.  The tests restate them to place their
+// cases on the edges and compare (candidate_select.h's capacity has mmrag_internal_candidate_capacity).  Exported for
+// them, deliberately absent from include/mmrag.h.  Host code, no device needed.
+int mmrag_internal_lexical_limits(int *score_rows, int *score_terms, int *sort_lds, int *sort_grid, int *scan_terms) {
+    if (!score_rows || !score_terms || !sort_lds || !sort_grid || !scan_terms) return -1;
+    *score_rows = SCORE_R;
+    *score_terms = SCORE_TERMS;
+    *sort_lds = SORT_LDS;
+    *sort_grid = SORT_GRID;
+    *scan_terms = SCAN_TERMS;
+    return 0;
 }
 
 }  // extern "C"

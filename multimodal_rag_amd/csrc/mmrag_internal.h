@@ -71,6 +71,12 @@ int mmrag_internal_join_tile(int64_t T, int64_t id, int64_t *ti, int64_t *tj);
 int mmrag_internal_join_slot_tile(int64_t T, int64_t slot, int64_t *ti, int64_t *tj);
 }
 
+// test-only export of the lexical leg's path thresholds (lexical.hip): SCORE_R, SCORE_TERMS, SORT_LDS, SORT_GRID and the
+// scan's terms per step.  Host code, no device needed.
+extern "C" {
+int mmrag_internal_lexical_limits(int *score_rows, int *score_terms, int *sort_lds, int *sort_grid, int *scan_terms);
+}
+
 // the cross-encoder's classification head (cross_head.hip), shared by the fp16 and fp32 forwards
 namespace mmrag_impl {
 size_t cls_head_workspace_bytes(int B, int H, int NL);

@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import os
 import unicodedata
-from ctypes import c_float, c_int, c_int64, c_size_t, c_void_p
+from ctypes import byref, c_float, c_int, c_int64, c_size_t, c_void_p
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -327,6 +327,13 @@ def csr_build_workspace_bytes(n: int, n_terms: int) -> int:
     return int(_native.lib().mmrag_lexical_csr_build_workspace_bytes(n, n_terms))
 
 
+def lexical_limits() -> Dict[str, int]:
+    """csrc/lexical.hip's path thresholds (mmrag_internal_lexical_limits; tests restate them and compare)"""
+    v = [c_int(0) for _ in range(5)]
+    _native._check(_native.lib().mmrag_internal_lexical_limits(*[byref(x) for x in v]), "mmrag_internal_lexical_limits")
+    return dict(zip(("score_rows", "score_terms", "sort_lds", "sort_grid", "scan_terms"), (int(x.value) for x in v)))
+
+
 def declare(lib):
     """ctypes signatures of the lexical entry points (called from _native._declare)"""
     lib.mmrag_lexicon_create.restype = c_void_p
@@ -351,6 +358,9 @@ def declare(lib):
     lib.mmrag_bm25_topk.argtypes = [c_void_p] * 5 + [c_int, c_int64, c_void_p, c_void_p, c_int, c_int64, c_int64,
                                                      c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                                      c_size_t, c_void_p]
+    # test-only export (not in include/mmrag.h): the sizes at which the kernels change path
+    lib.mmrag_internal_lexical_limits.restype = c_int
+    lib.mmrag_internal_lexical_limits.argtypes = [c_void_p] * 5
     lib.mmrag_rows_dot.restype = c_int
     lib.mmrag_rows_dot.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p,
                                    c_void_p]

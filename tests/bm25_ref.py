@@ -118,6 +118,24 @@ def assert_topk(got_s, got_r, acc, matched, allowed, k, rtol=1e-5):
         assert abs(acc[gr[i]] - acc[want[i]]) <= rtol * abs(acc[want[i]]), i
 
 
+def assert_topk_strict(got_s, got_r, acc, matched, allowed, k, group, rtol=1e-5):
+    """device top-k vs the reference where the order is fully determined (tests/lexical_regimes.py): rows of one
+    `group` (an int per row) have bit-identical device scores by construction and groups are far apart in score, so
+    the rows must EQUAL the reference's (score descending, ties to the lower row), the scores are within rtol of
+    float64 and bit-equal inside each group, and the padding is (-inf, -1) past the matching allowed rows"""
+    got_s, got_r = np.asarray(got_s), np.asarray(got_r)
+    assert got_s.dtype == np.float32 and got_s.shape == (k,) and got_r.shape == (k,)
+    want = topk(acc, matched, allowed, k)
+    m = want.size
+    assert np.array_equal(got_r[:m], want), (got_r[:m][got_r[:m] != want][:8], want[got_r[:m] != want][:8])
+    assert np.all(got_r[m:] == -1) and np.all(np.isneginf(got_s[m:])), (m, got_r[m:][:8], got_s[m:][:8])
+    np.testing.assert_allclose(got_s[:m].astype(np.float64), acc[want], rtol=rtol, atol=0)
+    bits, g = got_s[:m].view(np.int32), np.asarray(group)[want]
+    for v in np.unique(g):
+        inside = bits[g == v]
+        assert np.all(inside == inside[0]), (int(v), want[g == v][inside != inside[0]][:8])
+
+
 def rrf(dense_rows, lexical_rows, k=60):
     ranks = {}
     for leg, rows in enumerate((dense_rows, lexical_rows)):
