@@ -984,6 +984,60 @@ int mmrag_maxsim_topk_f8(const void *q_codes, int64_t q_rows, int64_t q_ld, cons
                          const int32_t *item_off, int64_t n_items, const uint32_t *alive_bits, int dim, int k,
                          float *out_scores, int64_t *out_items, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Answer passages: windowed MaxSim (csrc/maxsim_windows.hip).  For a (question, passage) pair: which contiguous window
+ * of the passage has the highest MaxSim against the question, and how much of the whole passage's score it keeps.
+ * LateInteractionScorer.best_passages, EmbeddingManager.extract_passages, POST /query "passages".
+ *
+ * mmrag_maxsim_windows
+ * Contract
+ *   A pair p = (question sequence, passage sequence) as in mmrag_maxsim_scores; i over the question's q_len tokens,
+ *   j over the passage's d_len tokens; S[i][j] = <q_i, d_j>, the tile body's float32 accumulator: the bits of
+ *   mmrag_maxsim_scores' candidates.
+ *   Blocks
+ *   - Block g of the passage is tokens 16 g .. min(16 g + 16, d_len) (MMRAG_LATE_WINDOW_TOKENS); nb = ceil(d_len / 16),
+ *     at most MMRAG_MAX_LATE_WINDOWS.  bm[i][g] = max over j in block g of S[i][j].  Columns j >= d_len are excluded
+ *     by index (-inf), never by value: a zero row is not a token and a neighbour's token in the same buffer is not
+ *     this passage's.
+ *   Windows, given window_blocks = w in 1..MMRAG_MAX_LATE_WINDOWS
+ *   - Window s covers blocks s .. min(s + w, nb) - 1, for s = 0 .. max(nb - w, 0).
+ *   - win[s] = the float32 sum, in ascending i starting from 0.0f, of max over g in window s of bm[i][g].
+ *   Outputs per pair
+ *   - out_sum[p]       exactly mmrag_maxsim_scores' out_sum, same bits;
+ *   - out_win[p][s]    win[s] for the valid s, -inf in the other slots of the MMRAG_MAX_LATE_WINDOWS;
+ *   - out_best[p][3]   (start, first, last): start = the LOWEST s that attains the largest win; first, last = the
+ *     tight span inside that window: for each i the lowest block g of the window with bm[i][g] equal to the window's
+ *     maximum for i, first the minimum over i and last the maximum.
+ *   - When w >= nb there is one window and out_win[p][0] has the bits of out_sum[p].
+ *   Guarantees
+ *   - one launch, no workspace, no atomics, no host synchronisation (the call can be captured into a graph);
+ *   - every output is a pure function of the two sequences, dim and w.
+ *
+ *   q_tok .. pair_d, P   as for mmrag_maxsim_scores
+ *   window_blocks        1..MMRAG_MAX_LATE_WINDOWS
+ *   out_sum              dev [P] float32
+ *   out_win              dev [P, MMRAG_MAX_LATE_WINDOWS] float32
+ *   out_best             dev [P, 3] int32
+ * MMRAG_EINVAL before anything is launched: mmrag_maxsim_scores' refusals, window_blocks out of range, a null output.
+ * A pair whose table entries are out of range (mmrag_maxsim_scores' rule) reads no row and gets out_sum[p] = NaN and
+ * out_best[p] = (-1, -1, -1); its out_win row is not written.  Other pairs are unaffected.
+ *
+ * mmrag_maxsim_windows_f8   the same over E4M3 code rows on both sides, mmrag_maxsim_scores_f8's rule word for word:
+ *   maxima are compared in the accumulator domain and values are scaled, exactly, by 2^-16 where they leave;
+ *   out_sum has the bits of mmrag_maxsim_scores_f8's. */
+#define MMRAG_LATE_WINDOW_TOKENS 16
+#define MMRAG_MAX_LATE_WINDOWS 32
+int mmrag_maxsim_windows(const void *q_tok, int64_t q_rows, int64_t q_ld, const void *d_tok, int64_t d_rows,
+                         int64_t d_ld, int dim, const int32_t *q_start, const int32_t *q_len, int n_q,
+                         const int32_t *d_start, const int32_t *d_len, int n_d, const int32_t *pair_q,
+                         const int32_t *pair_d, int P, int window_blocks, float *out_sum, float *out_win,
+                         int32_t *out_best, void *stream);
+int mmrag_maxsim_windows_f8(const void *q_codes, int64_t q_rows, int64_t q_ld, const void *d_codes, int64_t d_rows,
+                            int64_t d_ld, int dim, const int32_t *q_start, const int32_t *q_len, int n_q,
+                            const int32_t *d_start, const int32_t *d_len, int n_d, const int32_t *pair_q,
+                            const int32_t *pair_d, int P, int window_blocks, float *out_sum, float *out_win,
+                            int32_t *out_best, void *stream);
+
 /* CLIP byte-level BPE (the text tower's tokenizer, BASELINE config 4; the reference only names CLIP in config.py:106).
  * Host code, multi-threaded; equals multimodal_rag_amd/tokenizer.py:ClipBpeTokenizer, which tests pin to
  * transformers.CLIPTokenizer.  The caller passes text already NFC-normalised, whitespace-collapsed and lower-cased.

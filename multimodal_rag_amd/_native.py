@@ -40,6 +40,8 @@ MAX_RECOMMEND_EXAMPLES = 16  # mmrag_recommend_topk (MMRAG_MAX_RECOMMEND_EXAMPLE
 MAX_LATE_QUERY_TOKENS, MAX_LATE_DOC_TOKENS = 128, 512
 MAX_LATE_PAIRS = 65535
 MAX_LATE_QUESTIONS = 4096   # mmrag_maxsim_topk (MMRAG_MAX_LATE_QUESTIONS)
+# mmrag_maxsim_windows (MMRAG_LATE_WINDOW_TOKENS, MMRAG_MAX_LATE_WINDOWS)
+LATE_WINDOW_TOKENS, MAX_LATE_WINDOWS = 16, 32
 _DT2TORCH = {F32: torch.float32, F16: torch.float16, BF16: torch.bfloat16, F8E4M3: torch.float8_e4m3fn}
 _TORCH2DT = {v: k for k, v in _DT2TORCH.items()}
 
@@ -325,6 +327,12 @@ def _declare(lib):
     lib.mmrag_internal_maxsim_topk_f8_ex.argtypes = lib.mmrag_internal_maxsim_topk_ex.argtypes
     lib.mmrag_internal_maxsim_topk_f8_workspace_bytes_ex.restype = c_size_t
     lib.mmrag_internal_maxsim_topk_f8_workspace_bytes_ex.argtypes = [c_int, c_int64, c_int, c_int, c_int]
+    # answer passages: windowed MaxSim (csrc/maxsim_windows.hip)
+    lib.mmrag_maxsim_windows.restype = c_int
+    lib.mmrag_maxsim_windows.argtypes = lib.mmrag_maxsim_scores.argtypes[:16] + [c_int, c_void_p, c_void_p, c_void_p,
+                                                                                 c_void_p]
+    lib.mmrag_maxsim_windows_f8.restype = c_int
+    lib.mmrag_maxsim_windows_f8.argtypes = lib.mmrag_maxsim_windows.argtypes
     from .lexical import declare as declare_lexical   # BM25 analyzer, device index and search (csrc/lexical.hip)
 
     declare_lexical(lib)
@@ -1422,6 +1430,51 @@ def maxsim_scores_f8(q_codes: torch.Tensor, d_codes: torch.Tensor, dim: int, q_s
     tensors [rows, ld], ld = padded_dim(dim, torch.float8_e4m3fn) or more whole slabs, as f8_encode_rows writes them.
     A similarity is the decoded rows' float32 dot product times 2^-16; everything else is maxsim_scores'."""
     return maxsim_scores(q_codes, d_codes, dim, q_start, q_len, d_start, d_len, pair_q, pair_d, want_best, _f8=True)
+
+
+def maxsim_windows(q_tok: torch.Tensor, d_tok: torch.Tensor, dim: int, q_start, q_len, d_start, d_len, pair_q, pair_d,
+                   window_blocks: int, _f8: bool = False):
+    """The best window of each (query, passage) pair by windowed MaxSim (include/mmrag.h mmrag_maxsim_windows).  The
+    arguments are maxsim_scores' (the same host table checks, one transfer) plus `window_blocks`, the window width in
+    blocks of LATE_WINDOW_TOKENS passage tokens, 1..MAX_LATE_WINDOWS.  Returns device tensors (sums [P] float32, the
+    bits of maxsim_scores'; win [P, MAX_LATE_WINDOWS] float32, -inf past a pair's last window; best [P, 3] int32:
+    start, first, last in blocks).  One launch on the current stream, no host synchronisation.  (`_f8`:
+    maxsim_windows_f8's switch.)"""
+    who, row_dtype = ("maxsim_windows_f8", torch.uint8) if _f8 else ("maxsim_windows", torch.float16)
+    _dev_check(q_tok, d_tok)
+    for name, t in (("q_tok", q_tok), ("d_tok", d_tok)):
+        if t.dim() != 2 or not t.is_contiguous() or t.dtype != row_dtype:
+            raise MMRagNativeError(f"{who}: {name} must be a contiguous 2-D {_DT_NAME[row_dtype]} tensor")
+    if q_tok.device != d_tok.device:
+        raise MMRagNativeError(f"{who}: q_tok and d_tok must be on one device")
+    if not 1 <= int(window_blocks) <= MAX_LATE_WINDOWS:
+        raise MMRagNativeError(f"{who}: window_blocks={window_blocks} outside 1..{MAX_LATE_WINDOWS}")
+    tables = [torch.as_tensor(t, dtype=torch.int32).reshape(-1).cpu()
+              for t in (q_start, q_len, d_start, d_len, pair_q, pair_d)]
+    n_q, n_d, P = check_late_tables(q_tok.shape[0], d_tok.shape[0], *(t.tolist() for t in tables))
+    dev = q_tok.device
+    packed = _pinned_to_device(torch.cat(tables), dev)
+    at = [0, n_q, 2 * n_q, 2 * n_q + n_d, 2 * n_q + 2 * n_d, 2 * n_q + 2 * n_d + P]
+    qs, ql, ds, dl, pq, pd = (packed[lo:] for lo in at)
+    sums = torch.empty(P, dtype=torch.float32, device=dev)
+    win = torch.empty((P, MAX_LATE_WINDOWS), dtype=torch.float32, device=dev)
+    best = torch.empty((P, 3), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        fn = lib().mmrag_maxsim_windows_f8 if _f8 else lib().mmrag_maxsim_windows
+        st = fn(q_tok.data_ptr(), q_tok.shape[0], q_tok.shape[1], d_tok.data_ptr(), d_tok.shape[0], d_tok.shape[1],
+                int(dim), qs.data_ptr(), ql.data_ptr(), n_q, ds.data_ptr(), dl.data_ptr(), n_d, pq.data_ptr(),
+                pd.data_ptr(), P, int(window_blocks), sums.data_ptr(), win.data_ptr(), best.data_ptr(),
+                _stream_ptr(dev))
+    _check(st, "mmrag_" + who)
+    return sums, win, best
+
+
+def maxsim_windows_f8(q_codes: torch.Tensor, d_codes: torch.Tensor, dim: int, q_start, q_len, d_start, d_len, pair_q,
+                      pair_d, window_blocks: int):
+    """maxsim_windows over rows of E4M3 codes on BOTH sides (include/mmrag.h mmrag_maxsim_windows_f8), the operands of
+    maxsim_scores_f8; sums has the bits of maxsim_scores_f8's."""
+    return maxsim_windows(q_codes, d_codes, dim, q_start, q_len, d_start, d_len, pair_q, pair_d, window_blocks,
+                          _f8=True)
 
 
 def f8_encode_rows(src: torch.Tensor, d: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -78,6 +78,9 @@ class Settings:
     # second model).  MMRAG_LATE_MAX_DOC_TOKENS: passage tokens "late" scores (0 = the encoder's length; at most 512)
     MMRAG_RERANK_METHOD: str = field(default_factory=lambda: os.getenv("MMRAG_RERANK_METHOD", "cross"))
     MMRAG_LATE_MAX_DOC_TOKENS: int = field(default_factory=lambda: int(os.getenv("MMRAG_LATE_MAX_DOC_TOKENS", "0")))
+    # answer passages (EmbeddingManager.extract_passages, csrc/maxsim_windows.hip): the window, in passage tokens, whose
+    # MaxSim against the question picks the part of a hit that answers it -- a multiple of 16 in 16..512
+    MMRAG_PASSAGE_TOKENS: int = field(default_factory=lambda: int(os.getenv("MMRAG_PASSAGE_TOKENS", "64")))
     # token store (late_store.py, csrc/maxsim_scan.hip): with MMRAG_LATE_STORE=1 an upload also keeps the token rows
     # of the stored texts on the device (768 bytes per MiniLM token), so a late re-rank encodes only the question and
     # late_query / POST /query {"late": true} retrieve by exact MaxSim over all of them.  MMRAG_LATE_STORE_MAX_BYTES
@@ -162,6 +165,7 @@ class Settings:
         self.topics()
         self.rerank_method()
         self.late_store_dtype()
+        self.passage_tokens()
 
     def dedup_threshold(self) -> float:
         """MMRAG_DEDUP_THRESHOLD checked: 0 (off) or a cosine in (0, 1]"""
@@ -175,6 +179,13 @@ class Settings:
         if self.MMRAG_RERANK_METHOD not in ("cross", "late"):
             raise ValueError(f"MMRAG_RERANK_METHOD must be 'cross' or 'late' (got {self.MMRAG_RERANK_METHOD!r})")
         return self.MMRAG_RERANK_METHOD
+
+    def passage_tokens(self) -> int:
+        """MMRAG_PASSAGE_TOKENS checked: a multiple of 16 in 16..512"""
+        n = int(self.MMRAG_PASSAGE_TOKENS)
+        if not 16 <= n <= 512 or n % 16:
+            raise ValueError(f"MMRAG_PASSAGE_TOKENS must be a multiple of 16 in 16..512 (got {n})")
+        return n
 
     def late_store_dtype(self) -> str:
         """MMRAG_LATE_STORE_DTYPE checked: 'float16' or 'float8_e4m3fn'"""

@@ -1260,8 +1260,12 @@ class EmbeddingManager:
         return await self._batch("Batch late query", _NEEDS_LATE, _EMPTY_LATE, self._answer_late, queries, n_results,
                                  filter_dict)
 
-    def _late_rerank_sync(self, queries: List[str], results_list: List[Dict[str, Any]], top_k: Optional[int],
-                          explain: bool) -> List[Dict[str, Any]]:
+    def _late_score_sync(self, queries: List[str], results_list: List[Dict[str, Any]], explain: bool,
+                         passages: Optional[int] = None):
+        """ONE scoring call for every (queries[i], document of results_list[i]) pair, flat in that order: (scores,
+        explain records | [], passages entries | []).  `passages` (a window size in tokens): the windows launch in place
+        of the scores launch -- its out_sum is the score, so a re-rank orders as it does without; with `explain` as
+        well, best_idx comes from a second launch."""
         scorer = self._get_late()
         docs: List[str] = []
         pairs: List[Tuple[int, int]] = []
@@ -1271,12 +1275,14 @@ class EmbeddingManager:
                 docs.append(d if d is not None else "")
         scores: Any = []
         records: List[Any] = []
+        found: List[Any] = []
         if pairs:
             # hits whose token rows the store keeps are scored from the plane; the rest are encoded as before
             # (without a store, or when it keeps none of them, the scorer is called exactly as before).  An FP8 store's
             # plane is passed even when it keeps none of the hits: the scorer then quantises what it encodes, so a
-            # passage scores the same whether or not its tokens are stored
-            spans, plane = self._stored_spans(scorer, results_list, explain)
+            # passage scores the same whether or not its tokens are stored.  (Passages read the stored token ids too:
+            # a passage's text is given only for the ids that were scored.)
+            spans, plane = self._stored_spans(scorer, results_list, explain or passages is not None)
             store = getattr(self.collection, "token_store", None)
             plane_f8 = bool(spans) and store is not None and store.f8
             stored = {}
@@ -1286,8 +1292,18 @@ class EmbeddingManager:
                     stored["plane_f8"] = True
             if explain:
                 scores, records = scorer.explain_pairs(list(queries), docs, pairs, **stored)
-            else:
+            if passages is not None:
+                windows = scorer.best_passages(list(queries), docs, pairs, int(passages), **stored)
+                scores = [w["score"] for w in windows]
+                given = [d for results in results_list for d in results["documents"]]
+                found = [self._passage_of(scorer, d, w) for d, w in zip(given, windows)]
+            elif not explain:
                 scores = scorer.score_pairs(list(queries), docs, pairs, **stored)
+        return scores, records, found
+
+    def _late_rerank_sync(self, queries: List[str], results_list: List[Dict[str, Any]], top_k: Optional[int],
+                          explain: bool, passages: Optional[int] = None) -> List[Dict[str, Any]]:
+        scores, records, found = self._late_score_sync(queries, results_list, explain, passages)
         out, lo = [], 0
         for results in results_list:
             n = len(results["documents"])
@@ -1299,33 +1315,107 @@ class EmbeddingManager:
             hit["rerank_scores"] = [mine[i] for i in order]
             if explain:
                 hit["late_matches"] = [records[lo + i] for i in order]
+            if passages is not None:
+                hit["passages"] = [found[lo + i] for i in order]
             out.append(hit)
             lo += n
         return out
 
+    # ---- answer passages: the best window of each hit by windowed MaxSim (late.py, csrc/maxsim_windows.hip) ----
+    def supports_passages(self) -> bool:
+        """True when extract_passages can run: where late_rerank works (has_late_reranker: ONE BERT-family HIP engine in
+        fp16 mode with a tokenizer -- not the CLIP towers, not the fp32 encoder mode) and the collection is not sharded"""
+        return self.has_late_reranker() and not hasattr(self.collection, "load")     # serving.ShardedCollection
+
+    @staticmethod
+    def _passage_of(scorer, document: Optional[str], window: Dict[str, Any]) -> Dict[str, Any]:
+        """One hit's `passages` entry from best_passages' record: where the tight span lies in the document's
+        characters.  The document is tokenised again with character spans; the text is given only when that yields the
+        very ids that were scored (for a stored passage: the ids the store keeps) -- a document that changed since it
+        was stored, or a tokenizer without encode_with_spans, gives text None, as does a None document."""
+        share = window["window_sum"] / window["sum"] if window["sum"] > 0 else None
+        entry = {"text": None, "char_start": None, "char_end": None, "token_start": window["token_start"],
+                 "token_end": window["token_end"], "score": window["window_score"], "share": share}
+        encode = getattr(scorer.tokenizer, "encode_with_spans", None)
+        if document is None or encode is None:
+            return entry
+        ids, spans = encode(document, scorer.max_doc_tokens + 2)
+        first, count = (int(v[0]) for v in scorer.trimmed(np.array([len(ids)])))
+        if [int(i) for i in ids[first: first + count]] != [int(i) for i in window["doc_ids"]]:
+            return entry
+        inside = spans[first + window["token_start"]: first + window["token_end"]]
+        if not inside or first == 0:        # (a text without a single token: its [CLS] row stood in)
+            return entry
+        lo, hi = inside[0][0], max(e for _, e in inside)
+        entry.update(text=document[lo:hi], char_start=lo, char_end=hi)
+        return entry
+
+    def _extract_passages_sync(self, queries: List[str], results_list: List[Dict[str, Any]],
+                               window_tokens: Optional[int]) -> List[Dict[str, Any]]:
+        if not self.supports_passages():
+            raise ValueError("answer passages need a single BERT-family fp16 HIP engine with a tokenizer and a "
+                             "collection that is not sharded")
+        window = settings.passage_tokens() if window_tokens is None else int(window_tokens)
+        _, _, found = self._late_score_sync(queries, results_list, False, passages=window)
+        out, lo = [], 0
+        for results in results_list:
+            n = len(results["documents"])
+            out.append({**results, "passages": found[lo: lo + n]})
+            lo += n
+        return out
+
+    async def extract_passages(self, query_text: str, results: Dict[str, Any],
+                               window_tokens: Optional[int] = None) -> Dict[str, Any]:
+        """The answer passage of every hit of `results` (any retrieval mode's answer: only its `documents` and `ids` are
+        read): the window of `window_tokens` tokens (default MMRAG_PASSAGE_TOKENS; whole blocks of 16) of the document
+        that keeps the most of its MaxSim against `query_text`, narrowed to the blocks that hold some query token's best
+        match (mmrag_maxsim_windows).  Returns `results` plus `passages`, one entry per hit, in the hits' order:
+          text                     the document's characters from the first token's start to the last token's end; None
+                                   for a None document and when tokenising the document does not give the ids that
+                                   were scored (a stored passage: the ids the token store keeps)
+          char_start, char_end     where that text lies in the document (None with it)
+          token_start, token_end   the same span in scored tokens
+          score                    the window's MaxSim mean, to be read next to a late re-rank score
+          share                    window sum / whole passage's sum, None when the latter is not positive
+        Hits whose token rows the store keeps are scored from the plane.  One encoder forward, one launch."""
+        await self._ready()
+        return (await asyncio.to_thread(self._extract_passages_sync, [query_text], [results], window_tokens))[0]
+
+    async def batch_extract_passages(self, queries: List[str], results_list: List[Dict[str, Any]],
+                                     window_tokens: Optional[int] = None) -> List[Dict[str, Any]]:
+        """extract_passages of results_list[i] against queries[i], ONE scoring call for all"""
+        if len(queries) != len(results_list):
+            raise ValueError(f"{len(results_list)} result dicts for {len(queries)} queries")
+        await self._ready()
+        return await asyncio.to_thread(self._extract_passages_sync, list(queries), list(results_list), window_tokens)
+
     async def late_rerank(self, query_text: str, results: Dict[str, Any], top_k: Optional[int] = None,
-                          explain: bool = False) -> Dict[str, Any]:
+                          explain: bool = False, passages: Optional[int] = None) -> Dict[str, Any]:
         """Re-rank `results` (any retrieval mode's answer: only its `documents` are read) by late interaction with the
         bi-encoder itself: every (query_text, document) pair scores the mean over the query's tokens of each token's
         best cosine against the document's tokens.  Output as the cross-encoder path's: reordered by descending score
         (stable), truncated to top_k, with `rerank_scores`; `explain` adds `late_matches`, per hit one dict per query
-        token (query_token, doc_token, doc_index, similarity).  One encoder forward and one MaxSim launch."""
+        token (query_token, doc_token, doc_index, similarity).  One encoder forward and one MaxSim launch.
+        `passages` (a window size in tokens): the hits also carry `passages`, extract_passages' entries in the new
+        order, from the same call -- the windows launch stands in for the scores launch and its sum is the score."""
         await self._ready()
-        return (await asyncio.to_thread(self._late_rerank_sync, [query_text], [results], top_k, explain))[0]
+        return (await asyncio.to_thread(self._late_rerank_sync, [query_text], [results], top_k, explain, passages))[0]
 
     async def batch_late_rerank(self, queries: List[str], results_list: List[Dict[str, Any]],
-                                top_k: Optional[int] = None) -> List[Dict[str, Any]]:
+                                top_k: Optional[int] = None, passages: Optional[int] = None) -> List[Dict[str, Any]]:
         """late_rerank of results_list[i] against queries[i], ONE scoring call (one forward, one launch) for all"""
         if len(queries) != len(results_list):
             raise ValueError(f"{len(results_list)} result dicts for {len(queries)} queries")
         await self._ready()
-        return await asyncio.to_thread(self._late_rerank_sync, list(queries), list(results_list), top_k, False)
+        return await asyncio.to_thread(self._late_rerank_sync, list(queries), list(results_list), top_k, False,
+                                       passages)
 
     async def rerank_results(self, query_text: str, results: Dict[str, Any],
                              top_k: Optional[int] = None, method: Optional[str] = None,
-                             explain: bool = False) -> Dict[str, Any]:
+                             explain: bool = False, passages: Optional[int] = None) -> Dict[str, Any]:
         """embedder.py:834-859.  `method`: "cross" or "late" (default MMRAG_RERANK_METHOD, whose default is "cross").
-        "late": late_rerank (the bi-encoder's token rows; `explain` adds `late_matches`).  "cross", without a
+        "late": late_rerank (the bi-encoder's token rows; `explain` adds `late_matches`, `passages` -- a window size in
+        tokens, late only -- adds `passages`).  "cross", without a
         cross-encoder (MMRAG_RERANKER_DIR empty): the reference's placeholder -- no
         re-ranking, only truncation to top_k.  With one: every (query_text, document) pair is scored (a None document
         as ""), the results are reordered by descending score (stable: ties keep the search order), truncated to top_k
@@ -1333,8 +1423,12 @@ class EmbeddingManager:
         method = method or settings.rerank_method()
         if method not in ("cross", "late"):
             raise ValueError(f"rerank method must be 'cross' or 'late', not {method!r}")
+        if passages is not None and method != "late":
+            raise ValueError("`passages` rides on late-interaction re-ranking: use method 'late', or extract_passages "
+                             "on the re-ranked hits")
         if method == "late":
-            return await self.late_rerank(query_text, results, top_k=top_k, explain=explain)
+            more = {} if passages is None else {"passages": passages}
+            return await self.late_rerank(query_text, results, top_k=top_k, explain=explain, **more)
         if not self.has_reranker():
             logger.warning("Re-ranking not implemented yet")
             if top_k and top_k < len(results["ids"]):

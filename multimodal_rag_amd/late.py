@@ -184,7 +184,33 @@ class LateInteractionScorer:
         q_ids = [ids[s, first[s]: first[s] + count[s]].tolist() for s in range(len(lens))]
         return tokens, (cu[:-1] + first).astype(np.int32), count.astype(np.int32), q_ids
 
-    def _run_stored(self, queries, docs, pairs, spans, plane, want_best: bool, plane_f8: bool = False):
+    def _launch(self, q_tok, d_tok, dim, tables, want_best: bool, f8: bool, window_blocks: int):
+        """One MaxSim launch; its outputs side by side as raw 32-bit words, a device int32 tensor [P, width]: the sums,
+        then best_sim | best_idx (`want_best`) -- or, with `window_blocks`, the windows launch in place of the scores
+        launch (mmrag_maxsim_windows): the sums, then the 32 window sums | (start, first, last)."""
+        import torch
+
+        if window_blocks:
+            fn = _native.maxsim_windows_f8 if f8 else _native.maxsim_windows
+            sums, win, best = fn(q_tok, d_tok, dim, *tables, window_blocks)
+            cols = [sums.view(torch.int32).reshape(-1, 1), win.view(torch.int32), best]
+        else:
+            fn = _native.maxsim_scores_f8 if f8 else _native.maxsim_scores
+            sums, best_sim, best_idx = fn(q_tok, d_tok, dim, *tables, want_best=want_best)
+            cols = [sums.view(torch.int32).reshape(-1, 1)]
+            if want_best:
+                cols += [best_sim.view(torch.int32), best_idx]
+        return cols[0] if len(cols) == 1 else torch.cat(cols, dim=1)
+
+    @staticmethod
+    def _width(want_best: bool, window_blocks: int) -> int:
+        """columns of _launch's tensor"""
+        if window_blocks:
+            return 1 + _native.MAX_LATE_WINDOWS + 3
+        return 1 + 2 * _native.MAX_LATE_QUERY_TOKENS if want_best else 1
+
+    def _run_stored(self, queries, docs, pairs, spans, plane, want_best: bool, plane_f8: bool = False,
+                    window_blocks: int = 0):
         """_run with a token store: `spans[b]` is (first plane row, length, token ids) of passage b's stored rows, or
         None.  ONE forward over the queries and the passages that are not stored, then one MaxSim launch for the
         stored passages' pairs (against `plane`) and one for the others.  Returns _run's tuple; the plan's d_ids /
@@ -192,18 +218,15 @@ class LateInteractionScorer:
         An FP8 store (`plane_f8`: `plane` holds E4M3 code rows): the encoded rows -- the questions' AND those of the passages that
         had to be encoded -- are quantised once and both launches are mmrag_maxsim_scores_f8, so every candidate of the
         call is scored in the plane's arithmetic and a passage scores the same from the plane as re-encoded."""
-        import torch
-
         stored = [s is not None for s in spans]
         plan = self.plan(queries, docs, pairs, stored=stored)
         tokens, _ = self._encode_stable(plan["ids"], plan["lens"])
         dim = int(self.projection.shape[0]) if self.projection is not None else int(self.encoder.cfg.hidden)
-        P, W = len(plan["pair_q"]), _native.MAX_LATE_QUERY_TOKENS
+        P = len(plan["pair_q"])
         if plane_f8:
             tokens = _native.f8_encode_rows(tokens, dim)
-        scorer = _native.maxsim_scores_f8 if plane_f8 else _native.maxsim_scores
         from_store = np.array([stored[int(b)] for _, b in pairs], bool)
-        packed = np.zeros((P, 1 + 2 * W if want_best else 1), np.int32)
+        packed = np.zeros((P, self._width(want_best, window_blocks)), np.int32)
         d_ids = list(plan["d_ids"])
         pair_d = plan["pair_d"].copy()
         for mask, d_tok in ((from_store, plane), (~from_store, tokens)):
@@ -222,16 +245,24 @@ class LateInteractionScorer:
                     pair_d[[p for p in at if int(pairs[p][1]) == b]] = pair_of
             else:
                 d_start, d_len, pd = plan["d_start"], plan["d_len"], plan["pair_d"][at]
-            sums, best_sim, best_idx = scorer(tokens, d_tok, dim, plan["q_start"], plan["q_len"], d_start, d_len,
-                                              plan["pair_q"][at], pd, want_best=want_best)
-            cols = [sums.view(torch.int32).reshape(-1, 1)]
-            if want_best:
-                cols += [best_sim.view(torch.int32), best_idx]
-            packed[at] = torch.cat(cols, dim=1).cpu().numpy()
+            out = self._launch(tokens, d_tok, dim, (plan["q_start"], plan["q_len"], d_start, d_len, plan["pair_q"][at],
+                                                    pd), want_best, plane_f8, window_blocks)
+            packed[at] = out.cpu().numpy()
         plan["d_ids"], plan["pair_d"] = d_ids, pair_d
+        if window_blocks:
+            plan["d_len_of_pair"] = np.array([spans[int(b)][1] if stored[int(b)] else plan["d_len"][plan["pair_d"][p]]
+                                              for p, (_, b) in enumerate(pairs)], np.int32)
+        return self._unpack(packed, plan, want_best, window_blocks)
+
+    @staticmethod
+    def _unpack(packed: np.ndarray, plan, want_best: bool, window_blocks: int):
+        """_run's tuple from the host copy of _launch's columns"""
+        W = _native.MAX_LATE_WINDOWS if window_blocks else _native.MAX_LATE_QUERY_TOKENS
         q_len = plan["q_len"][plan["pair_q"]].astype(np.float32)
         scores = packed[:, 0].copy().view(np.float32) / q_len
-        if not want_best:
+        if window_blocks:
+            plan["sums"] = packed[:, 0].copy().view(np.float32)
+        elif not want_best:
             return scores, None, None, plan
         sims = np.ascontiguousarray(packed[:, 1: 1 + W]).view(np.float32)
         return scores, sims, np.ascontiguousarray(packed[:, 1 + W:]), plan
@@ -242,30 +273,25 @@ class LateInteractionScorer:
         return self._id2tok.get(int(token_id), int(token_id))
 
     # ------------------------------------------------------------------ scoring -------------
-    def _run(self, queries, docs, pairs, want_best: bool, spans=None, plane=None, plane_f8: bool = False):
+    def _run(self, queries, docs, pairs, want_best: bool, spans=None, plane=None, plane_f8: bool = False,
+             window_blocks: int = 0):
         """(scores [P] float32, best_sim [P, 128] float32 | None, best_idx [P, 128] int32 | None, plan): one tokenise
-        of the distinct texts, ONE encoder forward over queries and passages together, ONE MaxSim launch, one copy back"""
-        import torch
-
+        of the distinct texts, ONE encoder forward over queries and passages together, ONE MaxSim launch, one copy back.
+        `window_blocks` (best_passages): the windows launch in place of the scores launch -- the tuple is then (scores,
+        window sums [P, 32] float32, (start, first, last) [P, 3] int32, plan) and plan["d_len_of_pair"] [P] holds each
+        pair's passage length."""
         if spans is not None and (plane_f8 or any(s is not None for s in spans)):     # an FP8 store: always
-            return self._run_stored(queries, docs, pairs, spans, plane, want_best, plane_f8)
+            return self._run_stored(queries, docs, pairs, spans, plane, want_best, plane_f8, window_blocks)
         plan = self.plan(queries, docs, pairs)
         tokens, _ = self.encoder.encode_tokens(plan["ids"], plan["lens"], self.projection)
         dim = int(self.projection.shape[0]) if self.projection is not None else int(self.encoder.cfg.hidden)
-        sums, best_sim, best_idx = _native.maxsim_scores(
-            tokens, tokens, dim, plan["q_start"], plan["q_len"], plan["d_start"], plan["d_len"], plan["pair_q"],
-            plan["pair_d"], want_best=want_best)
-        P = len(plan["pair_q"])
-        q_len = plan["q_len"][plan["pair_q"]].astype(np.float32)
-        if not want_best:
-            return sums.cpu().numpy() / q_len, None, None, plan
-        # one copy back: the three outputs side by side as raw 32-bit words
-        W = _native.MAX_LATE_QUERY_TOKENS
-        packed = torch.cat([sums.view(torch.int32).reshape(P, 1), best_sim.view(torch.int32), best_idx],
-                           dim=1).cpu().numpy()
-        scores = packed[:, 0].copy().view(np.float32) / q_len
-        sims = np.ascontiguousarray(packed[:, 1: 1 + W]).view(np.float32)
-        return scores, sims, np.ascontiguousarray(packed[:, 1 + W:]), plan
+        # one copy back: the outputs side by side as raw 32-bit words
+        packed = self._launch(tokens, tokens, dim, (plan["q_start"], plan["q_len"], plan["d_start"], plan["d_len"],
+                                                    plan["pair_q"], plan["pair_d"]), want_best, False,
+                              window_blocks).cpu().numpy()
+        if window_blocks:
+            plan["d_len_of_pair"] = plan["d_len"][plan["pair_d"]].astype(np.int32)
+        return self._unpack(packed, plan, want_best, window_blocks)
 
     def score_pairs(self, queries: List[str], docs: List[str], pairs: List[Tuple[int, int]], explain: bool = False,
                     spans=None, plane=None, plane_f8: bool = False):
@@ -279,6 +305,41 @@ class LateInteractionScorer:
             return self._run(queries, docs, pairs, False, spans, plane, plane_f8)[0]
         scores, records = self.explain_pairs(queries, docs, pairs, spans, plane, plane_f8)
         return scores, [[(m["query_token"], m["doc_token"], m["similarity"]) for m in rec] for rec in records]
+
+    @staticmethod
+    def window_blocks(window_tokens: int) -> int:
+        """a window width in tokens as whole blocks: rounded up to a multiple of LATE_WINDOW_TOKENS, clamped to
+        16..512 tokens"""
+        blocks = -(-int(window_tokens) // _native.LATE_WINDOW_TOKENS)
+        return max(1, min(blocks, _native.MAX_LATE_WINDOWS))
+
+    def best_passages(self, queries: List[str], docs: List[str], pairs: List[Tuple[int, int]], window_tokens: int,
+                      spans=None, plane=None, plane_f8: bool = False):
+        """The best window of each pair's passage by windowed MaxSim (mmrag_maxsim_windows): plan, forward and stored
+        spans exactly as score_pairs, with the windows launch in place of the scores launch.  One dict per pair:
+          score          out_sum / q_len, the number score_pairs gives
+          window_score   the best window's sum / q_len
+          sum, window_sum   the two float32 sums themselves
+          window_start, window_end   the best window in scored tokens of the passage: whole blocks, the end clipped
+          token_start, token_end     the tight span inside it: the blocks that hold some query token's best match
+          window_scores  every window's sum / q_len, by start block
+          doc_ids        the passage's scored token ids (plan()'s d_ids; a stored passage's are the store's)
+        `window_tokens` is rounded up to whole blocks of 16 and clamped to 16..512."""
+        w = self.window_blocks(window_tokens)
+        scores, win, best, plan = self._run(queries, docs, pairs, False, spans, plane, plane_f8, window_blocks=w)
+        block = _native.LATE_WINDOW_TOKENS
+        out = []
+        for p in range(len(scores)):
+            d_len, q_len = int(plan["d_len_of_pair"][p]), float(plan["q_len"][plan["pair_q"][p]])
+            start, first, last = (int(v) for v in best[p])
+            valid = win[p, : max(-(-d_len // block) - w, 0) + 1]
+            out.append({"score": float(scores[p]), "window_score": float(win[p, start] / np.float32(q_len)),
+                        "sum": float(plan["sums"][p]), "window_sum": float(win[p, start]),
+                        "window_start": block * start, "window_end": min(block * (start + w), d_len),
+                        "token_start": block * first, "token_end": min(block * (last + 1), d_len),
+                        "window_scores": [float(v / np.float32(q_len)) for v in valid],
+                        "doc_ids": plan["d_ids"][plan["pair_d"][p]]})
+        return out
 
     def explain_pairs(self, queries: List[str], docs: List[str], pairs: List[Tuple[int, int]], spans=None, plane=None,
                       plane_f8: bool = False):

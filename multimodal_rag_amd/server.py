@@ -119,6 +119,14 @@ class QueryRequest(BaseModel):  # api.py:161-164
     # combined with `hybrid`, `mmr`, `group_by_document`, `boost`, `variants` / `expand` or `like` / `unlike` / `not`
     # yet
     late: bool = Field(False)
+    # not in the reference: answer passages (EmbeddingManager.extract_passages).  Each source also carries `passage`:
+    # the part of the hit that answers the question -- the window of `passage_tokens` tokens (default
+    # MMRAG_PASSAGE_TOKENS; whole blocks of 16, 16..512) with the highest MaxSim against the question, narrowed to the
+    # blocks that hold a match -- as {text, char_start, char_end, score, share}; `share` is the part of the hit's
+    # whole late-interaction score the window keeps.  Works with every mode: it reads the final hits.  With `rerank`
+    # and the method "late" it comes out of the re-rank call itself.  The generator's context is unchanged
+    passages: bool = Field(False)
+    passage_tokens: Optional[int] = Field(None, ge=16, le=512)
 
 
 FILTER_MAX_LEAVES, FILTER_MAX_DEPTH = 32, 8
@@ -228,6 +236,13 @@ RECOMMEND_COLUMNS = (("scores", "score"), ("penalties", "penalty"), ("matched", 
 LATE_NEEDS = ("late_rerank", "has_late_reranker",
               "Late-interaction re-ranking is not available with this embedder: it needs a single BERT-family HIP "
               "engine in fp16 mode with a tokenizer (EmbeddingManager.late_rerank)")
+
+
+# `passages`: the same
+PASSAGES_NEEDS = ("extract_passages", "supports_passages",
+                  "Answer passages are not available with this embedder: they need a single BERT-family HIP engine in "
+                  "fp16 mode with a tokenizer and a collection that is not sharded (EmbeddingManager.extract_passages)")
+PASSAGE_KEYS = ("text", "char_start", "char_end", "score", "share")
 
 
 # first-stage late retrieval (`late`): the same
@@ -424,7 +439,8 @@ class Pipeline:
                      fusion: Optional[str] = None, doc_ids: Optional[List[str]] = None,
                      rerank_method: Optional[str] = None, explain: bool = False, boost: Any = None,
                      recommend: Optional[Dict[str, Any]] = None,
-                     filter_dict: Optional[Dict[str, Any]] = None, late: bool = False) -> Optional[dict]:
+                     filter_dict: Optional[Dict[str, Any]] = None, late: bool = False,
+                     passage_tokens: Optional[int] = None) -> Optional[dict]:
         """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
         max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the re-ranker's best top_k (`rerank_method` "cross" or "late",
         default MMRAG_RERANK_METHOD; `explain`: late interaction's per-token matches on every source).  `hybrid`: from
@@ -440,8 +456,12 @@ class Pipeline:
         with `rerank`): the question is one positive example next to these (EmbeddingManager.recommend).
         `filter_dict`: a metadata filter every mode gets as (part of) its filter; a plain or re-ranked query with one
         goes through EmbeddingManager.query, `doc_ids` AND-ed into it.  `late` (alone or with `rerank`): the hits are
-        the exact MaxSim top_k over the token store (EmbeddingManager.late_query)"""
+        the exact MaxSim top_k over the token store (EmbeddingManager.late_query).  `passage_tokens` (a window size;
+        with any mode): every source carries its answer `passage` -- from the re-rank call when that is late
+        interaction's, else from EmbeddingManager.extract_passages over the final hits.  The generator's context is
+        built from the retriever's raw documents either way"""
         multi = variants is not None
+        riding = passage_tokens is not None and rerank and rerank_method == "late"
         # the restriction as the filter the embedder's methods take (nothing is passed when there is none)
         docs_only = None if doc_ids is None else {"doc_id": {"$in": list(doc_ids)}}
         both = {"$and": [filter_dict, docs_only]} if filter_dict and docs_only else (filter_dict or docs_only)
@@ -480,6 +500,8 @@ class Pipeline:
                 # (the method is passed on only when one was chosen: an embedder without late interaction keeps its
                 # two-argument rerank_results)
                 chosen = {} if rerank_method is None and not explain else {"method": rerank_method, "explain": explain}
+                if riding:
+                    chosen["passages"] = passage_tokens
                 hits = await self.embedder.rerank_results(question, hits, top_k=top_k, **chosen)
                 for column, of_id in carried.items():
                     hits[column] = [of_id[found] for found in hits["ids"]]
@@ -487,6 +509,8 @@ class Pipeline:
             hits = await search(question, n_results=top_k)
         if not hits["ids"]:
             return None
+        if passage_tokens is not None and "passages" not in hits:
+            hits = await self.embedder.extract_passages(question, hits, window_tokens=passage_tokens)
         raw = await self.retriever.retrieve_raw_documents(hits["ids"])
         passages, tables, images = (raw[k] for k in self.CONTEXT_KINDS)
         body = "\n\n".join(passages) if passages else ""
@@ -511,6 +535,9 @@ class Pipeline:
         if rerank and "late_matches" in hits:
             for src, found in zip(ranked, hits["late_matches"]):
                 src["matches"] = found
+        if passage_tokens is not None:
+            for src, found in zip(ranked, hits["passages"]):
+                src["passage"] = {key: found[key] for key in PASSAGE_KEYS}
         if group_by_document:
             at = 0
             for document_rank, group in enumerate(hits["groups"], 1):
@@ -663,6 +690,16 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
         elif request.rerank and not (hasattr(pipe.embedder, "has_reranker") and pipe.embedder.has_reranker()):
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="Re-ranking is not configured: set MMRAG_RERANKER_DIR to a local cross-encoder")
+        if request.passage_tokens is not None and not request.passages:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                detail="`passage_tokens` belongs to answer passages: send it with `passages`")
+        window = None
+        if request.passages:
+            pipe._need(PASSAGES_NEEDS)
+            try:
+                window = request.passage_tokens if request.passage_tokens is not None else settings.passage_tokens()
+            except ValueError as e:      # a setting changed out of range after start-up
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
         if request.filter is not None:
             try:
                 _, timed = check_filter(request.filter)
@@ -749,7 +786,8 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
                                     **({} if spec is None else {"boost": spec}),
                                     **({} if recommend is None else {"recommend": recommend}),
                                     **({} if not request.filter else {"filter_dict": request.filter}),
-                                    **({} if not request.late else {"late": True}))
+                                    **({} if not request.late else {"late": True}),
+                                    **({} if window is None else {"passage_tokens": window}))
         except ValueError as e:
             if recommend is None:
                 raise

@@ -61,6 +61,72 @@ def basic_tokenize(text: str, lower: bool = True) -> List[str]:
     return tokens
 
 
+def _basic_tokens(text: str, lower: bool):
+    """basic_tokenize's tokens with where they come from: a list of (token, start, end, offsets).  `offsets[k]` is the
+    index in `text` of the character that token[k] was made from, start = offsets[0] and end = offsets[-1] + 1.  Lower-
+    casing, NFD and dropping `Mn` marks are done on the WORD, as basic_tokenize does them; when doing them per character
+    does not give the same word (a word-final sigma, marks reordered across characters), or when one character becomes
+    several (a Hangul syllable's jamo), the word's characters cannot be told apart: `offsets` is None and every token
+    of the word carries the whole word's (start, end)."""
+    words, cur = [], []         # words of (character, index)
+    for i, ch in enumerate(text):
+        cp = ord(ch)
+        if cp == 0 or cp == 0xFFFD or (unicodedata.category(ch) in ("Cc", "Cf") and ch not in "\t\n\r"):
+            continue
+        space = ch in " \t\n\r" or unicodedata.category(ch) == "Zs" or ch.isspace()   # str.split() splits at isspace
+        if space or _is_cjk(cp):
+            if cur:
+                words.append(cur)
+                cur = []
+            if not space:
+                words.append([(ch, i)])
+        else:
+            cur.append((ch, i))
+    if cur:
+        words.append(cur)
+    out = []
+    for word in words:
+        w = "".join(ch for ch, _ in word)
+        w_start, w_end = word[0][1], word[-1][1] + 1
+        offs = [i for _, i in word]
+        if lower:
+            w = "".join(c for c in unicodedata.normalize("NFD", w.lower()) if unicodedata.category(c) != "Mn")
+            each = ["".join(c for c in unicodedata.normalize("NFD", ch.lower()) if unicodedata.category(c) != "Mn")
+                    for ch, _ in word]
+            if "".join(each) == w and all(len(e) <= 1 for e in each):
+                offs = [i for e, (_, i) in zip(each, word) if e]
+            else:
+                offs = None
+        tok, at = "", []
+
+        def flush():
+            if tok:
+                if offs is None:
+                    out.append((tok, w_start, w_end, None))
+                else:
+                    out.append((tok, at[0], at[-1] + 1, list(at)))
+
+        for k, ch in enumerate(w):
+            if _is_punct(ch):
+                flush()
+                tok, at = ch, [offs[k]] if offs is not None else []
+                flush()
+                tok, at = "", []
+            else:
+                tok += ch
+                if offs is not None:
+                    at.append(offs[k])
+        flush()
+    return out
+
+
+def basic_tokenize_spans(text: str, lower: bool = True):
+    """basic_tokenize's words, each with its (start, end) character offsets into `text`: [(word, (start, end)), ...].
+    text[start:end], normalised the same way, is the word -- except for the words _basic_tokens names, whose tokens all
+    carry the span of the whole whitespace-delimited word."""
+    return [(tok, (start, end)) for tok, start, end, _ in _basic_tokens(text, lower)]
+
+
 class WordPieceTokenizer:
     def __init__(self, vocab: Dict[str, int], lower: bool = True, max_chars_per_word: int = 100):
         self.vocab = vocab
@@ -102,6 +168,38 @@ class WordPieceTokenizer:
             if len(ids) >= max_length - 1:
                 break
         return ids[: max_length - 1] + [self.sep]
+
+    def _wordpiece_cuts(self, word: str):
+        """_wordpiece's ids with each piece's (start, end) in `word`; an [UNK] word is one piece over all of it"""
+        if len(word) > self.max_chars:
+            return [(self.unk, 0, len(word))]
+        out, start = [], 0
+        while start < len(word):
+            end, cur = len(word), None
+            while start < end:
+                piece = word[start:end] if start == 0 else "##" + word[start:end]
+                if piece in self.vocab:
+                    cur = self.vocab[piece]
+                    break
+                end -= 1
+            if cur is None:
+                return [(self.unk, 0, len(word))]
+            out.append((cur, start, end))
+            start = end
+        return out
+
+    def encode_with_spans(self, text: str, max_length: int):
+        """(ids, spans): ids == encode(text, max_length); spans[k] = the (start, end) character offsets into `text` that
+        ids[k] was made from, (0, 0) for [CLS] and [SEP].  Starts never decrease.  Every piece of an [UNK] word, and of
+        a word whose characters cannot be told apart after normalisation (_basic_tokens), has the whole word's span."""
+        ids, spans = [self.cls], [(0, 0)]
+        for tok, start, end, offs in _basic_tokens(text, self.lower):
+            for pid, a, b in self._wordpiece_cuts(tok):
+                ids.append(pid)
+                spans.append((start, end) if offs is None or pid == self.unk else (offs[a], offs[b - 1] + 1))
+            if len(ids) >= max_length - 1:
+                break
+        return ids[: max_length - 1] + [self.sep], spans[: max_length - 1] + [(0, 0)]
 
     def pieces(self, text: str) -> List[int]:
         """every WordPiece id of `text` (no special tokens, no truncation)"""
@@ -174,6 +272,8 @@ class NativeWordPieceTokenizer:
         if not self._h:
             raise RuntimeError(self._lib.mmrag_last_error().decode())
         self.vocab = vocab                   # (late.py names matched tokens with it)
+        self.lower = lower
+        self._py = None                      # encode_with_spans' WordPieceTokenizer, built on first use
         self.vocab_size = n
         self.cls = vocab.get("[CLS]", CLS)
         self.sep = vocab.get("[SEP]", SEP)
@@ -235,6 +335,13 @@ class NativeWordPieceTokenizer:
     def encode(self, text: str, max_length: int) -> List[int]:
         return self.encode_batch([text], max_length)[0]
 
+    def encode_with_spans(self, text: str, max_length: int):
+        """WordPieceTokenizer.encode_with_spans over the same vocabulary, in Python: the character spans are wanted for
+        the few hit documents of a request, not for ingest"""
+        if self._py is None:
+            self._py = WordPieceTokenizer(self.vocab, self.lower)
+        return self._py.encode_with_spans(text, max_length)
+
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         lib = getattr(self, "_lib", None)
@@ -260,6 +367,12 @@ class HashTokenizer:
         for w in basic_tokenize(text, self.lower)[: max_length - 2]:
             ids.append(1000 + int.from_bytes(hashlib.md5(w.encode("utf-8")).digest()[:8], "little") % span)
         return ids + [self.sep]
+
+    def encode_with_spans(self, text: str, max_length: int):
+        """(ids, spans) as WordPieceTokenizer.encode_with_spans: one id per word, each with the word's span"""
+        toks = _basic_tokens(text, self.lower)[: max_length - 2]
+        ids = self.encode(text, max_length)
+        return ids, [(0, 0)] + [(start, end) for _, start, end, _ in toks] + [(0, 0)]
 
 
 # ---------------------------------------------------------------------------------------------
