@@ -1065,6 +1065,94 @@ int mmrag_resize_crop_u8(const uint8_t *src, int H, int W, int64_t src_row_bytes
                          const int32_t *kx, int ksx, const int32_t *by, const int32_t *ky, int ksy, int out_h,
                          int out_w, int y_lo, int y_hi, uint8_t *tmp, uint8_t *dst, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Learned sparse retrieval (SPLADE-style term expansion): a fourth kind of evidence beside dense cosine, BM25 and
+ * MaxSim.  A masked-LM head turns a chunk into a sparse vector over the vocabulary, w_v = log1p(relu(max over the
+ * chunk's tokens of logit_v)); vectors are stored as 8-bit impacts in the inverted index the BM25 leg builds
+ * (mmrag_lexical_csr_build, the impact in the place of tf) and a query scores a row by the integer dot product of the
+ * two vectors.  multimodal_rag_amd/sparse.py DeviceSparseEncoder, ImpactIndex.
+ *
+ * mmrag_sparse_expand_forward (csrc/encoder.hip): the blocks of mmrag_encoder_forward, then the head's transform
+ * (cls.predictions.transform: dense H x H + erf GELU + LayerNorm, on mmrag_linear_f16 and mmrag_layernorm_f16), ending
+ * in UN-normalised token rows.  fp16 encoder mode, MMRAG_ARCH_BERT only (else MMRAG_EUNSUPPORTED); desc.pool and
+ * desc.normalize are ignored; mmrag_encoder_forward_tokens is unchanged.
+ *   desc, w, ids, pos_ids, cu_seqlens, T, B, max_len   as for mmrag_encoder_forward
+ *   head_w       dev [H, H] fp16 (transform.dense.weight)     head_b  dev [H] float32
+ *   head_ln_g, head_ln_b   dev [H] float32 (transform.LayerNorm), eps = desc.ln_eps
+ *   out_tokens   dev [T, H] fp16, 16-byte aligned; H a multiple of 64, at most 1024
+ *   workspace    >= mmrag_sparse_expand_forward_workspace_bytes(desc, T, B)
+ *
+ * mmrag_sparse_pool (csrc/sparse_expand.hip): the vocabulary projection and the per-chunk max in one kernel.
+ * Contract
+ *   - pooled[c][v] = max over the rows t of chunk c of <tok_t, E_v>, chunk c owning rows cu[c] .. cu[c + 1] of tok;
+ *     float32 accumulation of the fp16 rows in the tile body's fixed K order, so the bits of every entry depend on the
+ *     two rows and dim alone: not on the grid, the batch, or where a chunk falls against a tile edge;
+ *   - rows of a neighbouring chunk, rows past T and decoder rows past V are never part of a maximum (they are excluded
+ *     by index): a chunk whose true maximum is negative comes out negative;
+ *   - the only output is pooled; nothing of size T x V is written anywhere.  No workspace, no host synchronisation (the
+ *     call can be captured into a graph): chunks that span several 128-row tiles are merged in `pooled` itself by an
+ *     integer atomic max on the order-preserving key of the float, which does not depend on arrival order.
+ *   tok         dev [T, tok_ld] fp16, pad columns zero, 16-byte aligned       T 1..2^31 - 129
+ *   cu          dev [n_chunks + 1] int32 ascending; chunk lengths 1..MMRAG_MAX_SPARSE_CHUNK_TOKENS
+ *   n_chunks    1..MMRAG_MAX_SPARSE_CHUNKS
+ *   E           dev [V, e_ld] fp16 decoder rows, pad columns zero, 16-byte aligned     V 1..MMRAG_MAX_SPARSE_VOCAB
+ *   tok_ld, e_ld  mmrag_padded_dim(dim, MMRAG_F16) or a larger width of whole 128-byte slabs
+ *   dim         a multiple of 64, at most 1024
+ *   pooled      dev [n_chunks, V] float32
+ *   workspace   unused (mmrag_sparse_pool_workspace_bytes is 0); may be NULL
+ * MMRAG_EINVAL before anything is launched: a null pointer, dim, V, n_chunks or T out of range, a bad pitch.  The table
+ * lives on the device and is not read by the host: a chunk whose rows do not lie in 0..T or whose length is outside
+ * 1..MMRAG_MAX_SPARSE_CHUNK_TOKENS gets a row of -inf.
+ *
+ * mmrag_sparse_select (same file): activation, quantisation and the top m terms of every chunk.
+ *   - w = log1pf(fmaxf(pooled[c][v] + bias[v], 0)); impact = min(255, (int)rintf(w * scale));
+ *   - terms whose bit is set in skip_bits are dropped (special and [unused*] ids);
+ *   - kept: the m terms of highest impact >= 1, ties to the LOWER term id; out_cnt[c] of them, written as
+ *     (out_terms, out_imp)[c][0 .. out_cnt[c]) in ascending term id -- a row of the forward log
+ *     mmrag_lexical_csr_build takes; the slots behind them hold (-1, 0).
+ *   pooled      dev [n_chunks, V] float32     bias  dev [V] float32     skip_bits  dev [ceil(V / 32)] uint32 or NULL
+ *   scale       in (0, 1024]                  m     1..MMRAG_MAX_SPARSE_TERMS
+ *   out_cnt     dev [n_chunks] int32          out_terms, out_imp  dev [n_chunks, m] int32
+ * MMRAG_EINVAL before anything is launched: a null pointer (skip_bits aside), V, n_chunks, m or scale out of range.
+ *
+ * mmrag_impact_topk (csrc/sparse_score.hip): exact top-k by integer impact score over the inverted index.
+ *   - the index: term t's postings (row, impact 1..255) at term_off[t] .. term_off[t + 1), sorted by row --
+ *     mmrag_lexical_csr_build's output for a forward log of (term, impact) pairs, n_terms = V;
+ *   - query b: DISTINCT terms q_terms[q_off[b] .. q_off[b + 1]) with impacts q_imp 1..255, at most
+ *     MMRAG_MAX_SPARSE_QUERY_TERMS of them (a query with more, or with none, matches nothing; a term outside
+ *     0..n_terms or an impact outside 1..255 is skipped);
+ *   - score(row) = sum over the query's terms of q_imp * impact(row, term) in int32: at most 255 * 255 * 64 < 2^24,
+ *     exact, order-free and converted to float32 without rounding;
+ *   - rows compete when their score is above 0 and their bit is set in alive_bits (NULL: every row);
+ *   - out_scores / out_rows [B, k]: the score descending, ties to the lower row, padded with (-inf, -1);
+ *   - exact in every regime: when n exceeds the candidate slots a lower bound of each query's k-th score is first
+ *     taken from a strided sample of 2048-row blocks and only scores at or above it are appended; a query whose
+ *     survivors still overflow is scored again alone.  At most one synchronisation of `stream` per call (to read the
+ *     survivor counts), none when n fits the slots.
+ *   B 1..65535     k 1..MMRAG_MAX_K_DEEP     n 0..2^31 - 2050     n_terms 0..MMRAG_MAX_SPARSE_VOCAB
+ *   workspace   >= mmrag_impact_topk_workspace_bytes(B, n, k) bytes (0 for arguments out of range), 16-byte aligned */
+#define MMRAG_MAX_SPARSE_CHUNK_TOKENS 512
+#define MMRAG_MAX_SPARSE_CHUNKS 65536
+#define MMRAG_MAX_SPARSE_VOCAB 65536
+#define MMRAG_MAX_SPARSE_TERMS 256
+#define MMRAG_MAX_SPARSE_QUERY_TERMS 64
+size_t mmrag_sparse_expand_forward_workspace_bytes(const mmrag_encoder_desc *desc, int64_t T, int B);
+int mmrag_sparse_expand_forward(const mmrag_encoder_desc *desc, const void *const *w, const int32_t *ids,
+                                const int32_t *pos_ids, const int32_t *cu_seqlens, int64_t T, int B, int max_len,
+                                const void *head_w, const float *head_b, const float *head_ln_g,
+                                const float *head_ln_b, void *out_tokens, void *workspace, size_t workspace_bytes,
+                                void *stream);
+size_t mmrag_sparse_pool_workspace_bytes(int64_t T, int n_chunks, int V);
+int mmrag_sparse_pool(const void *tok, int64_t T, int64_t tok_ld, const int32_t *cu, int n_chunks, const void *E, int V,
+                      int64_t e_ld, int dim, float *pooled, void *workspace, size_t workspace_bytes, void *stream);
+int mmrag_sparse_select(const float *pooled, const float *bias, const uint32_t *skip_bits, int n_chunks, int V,
+                        float scale, int m, int32_t *out_cnt, int32_t *out_terms, int32_t *out_imp, void *stream);
+size_t mmrag_impact_topk_workspace_bytes(int B, int64_t n, int k);
+int mmrag_impact_topk(const int64_t *term_off, const int32_t *post_row, const int32_t *post_imp, int n_terms, int64_t n,
+                      const int32_t *q_off, const int32_t *q_terms, const int32_t *q_imp, int B, int k,
+                      const uint32_t *alive_bits, float *out_scores, int64_t *out_rows, void *workspace,
+                      size_t workspace_bytes, void *stream);
+
 /* Measured peaks for the roofline report ("a measured stream-copy bandwidth and a measured MFMA
  * micro-benchmark peak, fractions against both the vendor and the measured peaks").  Not on the product path.
  *   mmrag_device_info        CU count, maximum shader clock (MHz), HBM bytes of the current device

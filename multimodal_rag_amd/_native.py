@@ -333,6 +333,33 @@ def _declare(lib):
                                                                                  c_void_p]
     lib.mmrag_maxsim_windows_f8.restype = c_int
     lib.mmrag_maxsim_windows_f8.argtypes = lib.mmrag_maxsim_windows.argtypes
+    # learned sparse retrieval (csrc/encoder.hip, csrc/sparse_expand.hip, csrc/sparse_score.hip)
+    lib.mmrag_sparse_expand_forward_workspace_bytes.restype = c_size_t
+    lib.mmrag_sparse_expand_forward_workspace_bytes.argtypes = [c_void_p, c_int64, c_int]
+    lib.mmrag_sparse_expand_forward.restype = c_int
+    lib.mmrag_sparse_expand_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                c_void_p]
+    lib.mmrag_sparse_pool_workspace_bytes.restype = c_size_t
+    lib.mmrag_sparse_pool_workspace_bytes.argtypes = [c_int64, c_int, c_int]
+    lib.mmrag_sparse_pool.restype = c_int
+    lib.mmrag_sparse_pool.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int, c_int64, c_int,
+                                      c_void_p, c_void_p, c_size_t, c_void_p]
+    # debug form (not in include/mmrag.h): the run of vocabulary tiles per workgroup
+    lib.mmrag_internal_sparse_pool_ex.restype = c_int
+    lib.mmrag_internal_sparse_pool_ex.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int, c_int64,
+                                                  c_int, c_void_p, c_void_p, c_int]
+    lib.mmrag_sparse_select.restype = c_int
+    lib.mmrag_sparse_select.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]
+    lib.mmrag_impact_topk_workspace_bytes.restype = c_size_t
+    lib.mmrag_impact_topk_workspace_bytes.argtypes = [c_int, c_int64, c_int]
+    lib.mmrag_impact_topk.restype = c_int
+    lib.mmrag_impact_topk.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int,
+                                      c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    # debug form (not in include/mmrag.h): candidate capacity, switches (1 = no bound stages)
+    lib.mmrag_internal_impact_topk_ex.restype = c_int
+    lib.mmrag_internal_impact_topk_ex.argtypes = lib.mmrag_impact_topk.argtypes + [c_int64, ctypes.c_uint]
     from .lexical import declare as declare_lexical   # BM25 analyzer, device index and search (csrc/lexical.hip)
 
     declare_lexical(lib)
@@ -2002,6 +2029,127 @@ def encoder_forward_tokens(desc: EncoderDesc, weight_ptrs, ids: torch.Tensor, po
                                                 _stream_ptr(ids.device))
     _check(st, "mmrag_encoder_forward_tokens")
     return out
+
+
+# ---- learned sparse retrieval (include/mmrag.h: mmrag_sparse_expand_forward, _pool, _select, mmrag_impact_topk) ----
+MAX_SPARSE_CHUNK_TOKENS, MAX_SPARSE_CHUNKS, MAX_SPARSE_VOCAB = 512, 65536, 65536
+MAX_SPARSE_TERMS, MAX_SPARSE_QUERY_TERMS = 256, 64
+
+
+def sparse_expand_forward_workspace_bytes(desc: EncoderDesc, T: int, B: int) -> int:
+    return int(lib().mmrag_sparse_expand_forward_workspace_bytes(ctypes.byref(desc), T, B))
+
+
+def sparse_expand_forward(desc: EncoderDesc, weight_ptrs, ids: torch.Tensor, pos_ids: torch.Tensor,
+                          cu_seqlens: torch.Tensor, max_len: int, head_w: torch.Tensor, head_b: torch.Tensor,
+                          head_ln_g: torch.Tensor, head_ln_b: torch.Tensor, workspace: Optional[torch.Tensor] = None,
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One encoder pass, then a masked-LM head's transform (dense + erf GELU + LayerNorm) -> token rows [T, hidden]
+    float16, NOT normalised: the plane sparse_pool reads."""
+    _dev_check(ids, pos_ids, cu_seqlens, head_w, head_b, head_ln_g, head_ln_b, workspace, out)
+    T, B, H = ids.numel(), cu_seqlens.numel() - 1, desc.hidden
+    if head_w.dtype != torch.float16 or tuple(head_w.shape) != (H, H) or not head_w.is_contiguous():
+        raise MMRagNativeError("sparse_expand_forward: head_w must be a contiguous [hidden, hidden] float16 tensor")
+    for t in (head_b, head_ln_g, head_ln_b):
+        if t.dtype != torch.float32 or t.numel() != H or not t.is_contiguous():
+            raise MMRagNativeError("sparse_expand_forward: head bias / LayerNorm vectors must be [hidden] float32")
+    need = sparse_expand_forward_workspace_bytes(desc, T, B)
+    if workspace is None or _nbytes(workspace) < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=ids.device)
+    if out is None:
+        out = torch.empty((max(T, 1), H), dtype=torch.float16, device=ids.device)
+    with torch.cuda.device(ids.device):
+        st = lib().mmrag_sparse_expand_forward(ctypes.byref(desc), weight_ptrs, ids.data_ptr(), pos_ids.data_ptr(),
+                                               cu_seqlens.data_ptr(), T, B, max_len, head_w.data_ptr(),
+                                               head_b.data_ptr(), head_ln_g.data_ptr(), head_ln_b.data_ptr(),
+                                               out.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
+                                               _stream_ptr(ids.device))
+    _check(st, "mmrag_sparse_expand_forward")
+    return out
+
+
+def sparse_pool(tok: torch.Tensor, cu: torch.Tensor, E: torch.Tensor, dim: int, n_rows: Optional[int] = None,
+                V: Optional[int] = None, vrun: int = 0) -> torch.Tensor:
+    """pooled [n_chunks, V] float32 = per chunk (rows cu[c] .. cu[c + 1] of `tok`) the maximum over its rows of the
+    dot products with the decoder rows `E` [V, ld] (mmrag_sparse_pool).  `tok`, `E`: contiguous 2-D float16, widths of
+    whole 128-byte slabs; `cu` int32 on the device.  `vrun` > 0: the vocabulary tiles a workgroup takes
+    (mmrag_internal_sparse_pool_ex; the output does not depend on it)."""
+    _dev_check(tok, cu, E)
+    for name, t in (("tok", tok), ("E", E)):
+        if t.dim() != 2 or t.dtype != torch.float16 or not t.is_contiguous():
+            raise MMRagNativeError(f"sparse_pool: {name} must be a contiguous 2-D float16 tensor")
+    if cu.dtype != torch.int32 or cu.dim() != 1 or not cu.is_contiguous() or cu.numel() < 2:
+        raise MMRagNativeError("sparse_pool: cu must be a contiguous int32 vector of n_chunks + 1 offsets")
+    T = tok.shape[0] if n_rows is None else int(n_rows)
+    V = E.shape[0] if V is None else int(V)
+    if T > tok.shape[0] or V > E.shape[0]:
+        raise MMRagNativeError("sparse_pool: n_rows / V exceed the tensors")
+    n_chunks = cu.numel() - 1
+    pooled = torch.empty((max(n_chunks, 1), max(V, 1)), dtype=torch.float32, device=tok.device)
+    with torch.cuda.device(tok.device):
+        args = (tok.data_ptr(), T, tok.shape[1], cu.data_ptr(), n_chunks, E.data_ptr(), V, E.shape[1], int(dim),
+                pooled.data_ptr())
+        if vrun:
+            st = lib().mmrag_internal_sparse_pool_ex(*args, _stream_ptr(tok.device), int(vrun))
+        else:
+            st = lib().mmrag_sparse_pool(*args, None, 0, _stream_ptr(tok.device))
+    _check(st, "mmrag_sparse_pool")
+    return pooled
+
+
+def sparse_select(pooled: torch.Tensor, bias: torch.Tensor, scale: float, m: int,
+                  skip_bits: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(count [n_chunks], terms [n_chunks, m], impacts [n_chunks, m]) int32 on the device: per chunk the m terms of
+    highest 8-bit impact min(255, rint(log1p(relu(pooled + bias)) * scale)) >= 1, ties to the lower term id, written
+    in ascending term id; (-1, 0) behind them (mmrag_sparse_select)."""
+    _dev_check(pooled, bias, skip_bits)
+    if pooled.dim() != 2 or pooled.dtype != torch.float32 or not pooled.is_contiguous():
+        raise MMRagNativeError("sparse_select: pooled must be a contiguous [n_chunks, V] float32 tensor")
+    n_chunks, V = pooled.shape
+    if bias.dtype != torch.float32 or bias.numel() != V or not bias.is_contiguous():
+        raise MMRagNativeError("sparse_select: bias must be a contiguous [V] float32 tensor")
+    if skip_bits is not None and (skip_bits.dtype != torch.int32 or skip_bits.numel() < (V + 31) // 32
+                                  or not skip_bits.is_contiguous()):
+        raise MMRagNativeError("sparse_select: skip_bits must be ceil(V / 32) int32 words")
+    dev = pooled.device
+    cnt = torch.empty(max(n_chunks, 1), dtype=torch.int32, device=dev)
+    terms = torch.empty((max(n_chunks, 1), max(int(m), 1)), dtype=torch.int32, device=dev)
+    imps = torch.empty_like(terms)
+    with torch.cuda.device(dev):
+        st = lib().mmrag_sparse_select(pooled.data_ptr(), bias.data_ptr(), _ptr(skip_bits), n_chunks, V, float(scale),
+                                       int(m), cnt.data_ptr(), terms.data_ptr(), imps.data_ptr(), _stream_ptr(dev))
+    _check(st, "mmrag_sparse_select")
+    return cnt, terms, imps
+
+
+def impact_topk_workspace_bytes(B: int, n: int, k: int) -> int:
+    return int(lib().mmrag_impact_topk_workspace_bytes(B, n, k))
+
+
+def impact_topk(term_off: torch.Tensor, post_row: torch.Tensor, post_imp: torch.Tensor, n_terms: int, n: int,
+                q_off: torch.Tensor, q_terms: torch.Tensor, q_imp: torch.Tensor, k: int,
+                alive_bits: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                cap: int = 0, dbg: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(scores [B, k] float32 desc, rows [B, k] int64; (-inf, -1) padding) on the device: the exact top-k by integer
+    impact score over the inverted CSR (mmrag_impact_topk).  `cap` / `dbg`: the test hook's candidate capacity and
+    switches (mmrag_internal_impact_topk_ex)."""
+    _dev_check(term_off, post_row, post_imp, q_off, q_terms, q_imp, alive_bits, workspace)
+    B = q_off.numel() - 1
+    dev = q_off.device
+    need = impact_topk_workspace_bytes(B, n, k)
+    if workspace is None or _nbytes(workspace) < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    out_s, out_r = _topk_out(max(B, 1), max(k, 1), dev)
+    args = (term_off.data_ptr(), post_row.data_ptr(), post_imp.data_ptr(), int(n_terms), int(n), q_off.data_ptr(),
+            q_terms.data_ptr(), q_imp.data_ptr(), B, int(k), _ptr(alive_bits), out_s.data_ptr(), out_r.data_ptr(),
+            workspace.data_ptr(), _nbytes(workspace), _stream_ptr(dev))
+    with torch.cuda.device(dev):
+        if cap or dbg:
+            st = lib().mmrag_internal_impact_topk_ex(*args, int(cap), int(dbg))
+        else:
+            st = lib().mmrag_impact_topk(*args)
+    _check(st, "mmrag_impact_topk")
+    return out_s, out_r
 
 
 def cross_encoder_workspace_bytes(desc: EncoderDesc, T: int, B: int, f32: bool = False) -> int:

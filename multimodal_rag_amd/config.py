@@ -99,6 +99,17 @@ class Settings:
     # reciprocal rank with sum 1 / (MMRAG_HYBRID_RRF_K + rank)
     MMRAG_HYBRID_CANDIDATES: int = field(default_factory=lambda: int(os.getenv("MMRAG_HYBRID_CANDIDATES", "50")))
     MMRAG_HYBRID_RRF_K: int = field(default_factory=lambda: int(os.getenv("MMRAG_HYBRID_RRF_K", "60")))
+    # learned sparse retrieval (sparse.py, csrc/sparse_expand.hip, csrc/sparse_score.hip): a LOCAL BertForMaskedLM
+    # directory (config.json + model.safetensors + vocab.txt, e.g. a SPLADE checkpoint); empty = nothing is built,
+    # stored or loaded.  Documents keep MMRAG_SPARSE_DOC_TERMS terms, questions MMRAG_SPARSE_QUERY_TERMS (at most 64);
+    # impacts are min(255, rint(log1p(relu(logit)) * MMRAG_SPARSE_IMPACT_SCALE)).  MMRAG_SPARSE_QUERY_MODE: "expand"
+    # (a forward pass on the question) or "tokens" (the question's own word pieces at impact scale: no model forward
+    # on the query path)
+    MMRAG_SPARSE_ENCODER_DIR: str = field(default_factory=lambda: os.getenv("MMRAG_SPARSE_ENCODER_DIR", ""))
+    MMRAG_SPARSE_DOC_TERMS: int = field(default_factory=lambda: int(os.getenv("MMRAG_SPARSE_DOC_TERMS", "128")))
+    MMRAG_SPARSE_QUERY_TERMS: int = field(default_factory=lambda: int(os.getenv("MMRAG_SPARSE_QUERY_TERMS", "32")))
+    MMRAG_SPARSE_IMPACT_SCALE: float = field(default_factory=lambda: float(os.getenv("MMRAG_SPARSE_IMPACT_SCALE", "64")))
+    MMRAG_SPARSE_QUERY_MODE: str = field(default_factory=lambda: os.getenv("MMRAG_SPARSE_QUERY_MODE", "expand"))
     # diversified retrieval (VectorIndex.mmr_query, csrc/mmr.hip): maximal marginal relevance picks n_results of
     # max(n_results, MMRAG_MMR_CANDIDATES) dense hits (at most 1024) with v = lambda rel - (1 - lambda) max sim to the
     # picks so far; lambda = 1 is the plain dense order, 0 pure diversity

@@ -1725,10 +1725,21 @@ struct TokenTail {
     int out_dim;
     void *projected;        // [T, out_dim] fp16 scratch (proj only)
     void *out;              // [T, out_dim] fp16
+    // a masked-LM head's transform instead (mmrag_sparse_expand_forward): out = LayerNorm(gelu(hidden . mlm_w^T +
+    // mlm_b)), rows left un-normalised; `projected` [T, H] holds the dense layer's output
+    const void *mlm_w = nullptr;     // [H, H] fp16, or null: the tail above
+    const float *mlm_b = nullptr, *mlm_g = nullptr, *mlm_beta = nullptr;
+    float mlm_eps = 0.0f;
 };
 
 // `hidden` [T, H]: the final hidden states -> (projection) -> L2-normalised fp16 rows
 static int token_tail(const TokenTail &tk, const void *hidden, int64_t T, int H, void *stream) {
+    if (tk.mlm_w != nullptr) {
+        const int st = mmrag_linear_f16(hidden, T, H, tk.mlm_w, H, tk.mlm_b, MMRAG_ACT_GELU, nullptr, tk.projected,
+                                        stream);
+        if (st != MMRAG_OK) return st;
+        return mmrag_layernorm_f16(tk.projected, tk.out, tk.mlm_g, tk.mlm_beta, T, H, tk.mlm_eps, stream);
+    }
     const void *rows = hidden;
     if (tk.proj != nullptr) {
         const int st = mmrag_linear_f16(hidden, T, H, tk.proj, tk.out_dim, nullptr, MMRAG_ACT_NONE, nullptr,
@@ -1901,6 +1912,56 @@ int mmrag_encoder_forward_tokens(const mmrag_encoder_desc *d, const void *const 
     // the tail: carve() aligned the workspace start up to 256 bytes inside its own 256-byte slack
     tk.projected = (char *)(((uintptr_t)workspace + 255) / 256 * 256) + (body - 256);
     tk.out = out_tokens;
+    RUN(mmrag_embed_ln_f16(ids, pos_ids, w[0], w[1], w[2], (const float *)w[3], (const float *)w[4], b.x, T,
+                           dc.hidden, dc.vocab, dc.max_pos, dc.ln_eps, stream));
+    return encoder_body(&dc, w + 5, b, cu_seqlens, nullptr, T, B, max_len, nullptr, stream, &tk);
+}
+
+// ---------------------------------------------------------------------------------------------
+// learned sparse expansion: the same embedding and blocks, then a masked-LM head's transform (cls.predictions.transform:
+// dense H x H + erf GELU + LayerNorm) into un-normalised token rows -- the plane mmrag_sparse_pool reads
+// ---------------------------------------------------------------------------------------------
+size_t mmrag_sparse_expand_forward_workspace_bytes(const mmrag_encoder_desc *d, int64_t T, int B) {
+    if (d == nullptr) return 0;
+    return mmrag_encoder_tokens_workspace_bytes(d, T, B, d->hidden);
+}
+
+int mmrag_sparse_expand_forward(const mmrag_encoder_desc *d, const void *const *w, const int32_t *ids,
+                                const int32_t *pos_ids, const int32_t *cu_seqlens, int64_t T, int B, int max_len,
+                                const void *head_w, const float *head_b, const float *head_ln_g,
+                                const float *head_ln_b, void *out_tokens, void *workspace, size_t workspace_bytes,
+                                void *stream) {
+    MMRAG_CHECK_ARG(d && w && ids && pos_ids && cu_seqlens && out_tokens, "sparse_expand_forward: null pointer");
+    MMRAG_CHECK_ARG(head_w && head_b && head_ln_g && head_ln_b, "sparse_expand_forward: null head weight");
+    MMRAG_CHECK_ARG(T > 0 && T < INT_MAX && B > 0 && max_len > 0, "sparse_expand_forward: bad shape T=%lld B=%d",
+                    (long long)T, B);
+    if (d->arch != MMRAG_ARCH_BERT) {
+        set_error("sparse_expand_forward: BERT family only (arch %d)", d->arch);
+        return MMRAG_EUNSUPPORTED;
+    }
+    mmrag_encoder_desc dc = *d;   // pool / normalize of the caller's desc are ignored
+    dc.pool = MMRAG_POOL_FIRST, dc.normalize = 0, dc.out_dim = d->hidden;
+    int st;
+    RUN(check_desc(&dc));
+    MMRAG_CHECK_ARG(tokens_dim_ok(&dc, dc.hidden), "sparse_expand_forward: hidden must be a multiple of 64, at most "
+                    "1024 (hidden=%d)", dc.hidden);
+    MMRAG_CHECK_ARG(((uintptr_t)head_w % 16) == 0 && ((uintptr_t)out_tokens % 16) == 0 && ((uintptr_t)head_b % 16) == 0 &&
+                        ((uintptr_t)head_ln_g % 16) == 0 && ((uintptr_t)head_ln_b % 16) == 0,
+                    "sparse_expand_forward: head weights and out_tokens must be 16-byte aligned");
+    const size_t body = mmrag_encoder_workspace_bytes(&dc, T, B), need = body + align256((size_t)T * (size_t)dc.hidden * 2);
+    if (!workspace || workspace_bytes < need) {
+        set_error("sparse_expand_forward: workspace %zu bytes < required %zu", workspace_bytes, need);
+        return MMRAG_EWORKSPACE;
+    }
+    EncBuffers b;
+    RUN(carve(&dc, T, B, workspace, body, &b));
+    TokenTail tk;
+    tk.proj = nullptr;
+    tk.out_dim = dc.hidden;
+    // the tail: carve() aligned the workspace start up to 256 bytes inside its own 256-byte slack
+    tk.projected = (char *)(((uintptr_t)workspace + 255) / 256 * 256) + (body - 256);
+    tk.out = out_tokens;
+    tk.mlm_w = head_w, tk.mlm_b = head_b, tk.mlm_g = head_ln_g, tk.mlm_beta = head_ln_b, tk.mlm_eps = dc.ln_eps;
     RUN(mmrag_embed_ln_f16(ids, pos_ids, w[0], w[1], w[2], (const float *)w[3], (const float *)w[4], b.x, T,
                            dc.hidden, dc.vocab, dc.max_pos, dc.ln_eps, stream));
     return encoder_body(&dc, w + 5, b, cu_seqlens, nullptr, T, B, max_len, nullptr, stream, &tk);

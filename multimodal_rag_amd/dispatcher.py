@@ -23,13 +23,17 @@ BoostedFn = Callable[[List[str], int, Optional[Dict], Any], Awaitable[List[Dict[
 # (csrc/filtered.hip)
 FilteredFn = Callable[[List[str], int, List[Optional[Dict]]], Awaitable[List[Dict[str, Any]]]]
 RecommendFn = Callable[[List[Dict[str, Any]], int, Optional[Dict]], Awaitable[List[Dict[str, Any]]]]
+# (texts, k, filter): ONE expansion of the questions and ONE impact search (csrc/sparse_expand.hip, csrc/sparse_score.hip)
+SparseFn = Callable[[List[str], int, Optional[Dict]], Awaitable[List[Dict[str, Any]]]]
 
 
 class QueryDispatcher:
     def __init__(self, batch_fn: BatchFn, max_batch: int = 256, max_wait_ms: float = 2.0, idle_ms: float = 0.25,
                  scoped_fn: Optional[ScopedFn] = None, boosted_fn: Optional[BoostedFn] = None,
-                 recommend_fn: Optional[RecommendFn] = None, filtered_fn: Optional[FilteredFn] = None):
+                 recommend_fn: Optional[RecommendFn] = None, filtered_fn: Optional[FilteredFn] = None,
+                 sparse_fn: Optional[SparseFn] = None):
         self.batch_fn = batch_fn
+        self.sparse_fn = sparse_fn
         self.filtered_fn = filtered_fn
         self.scoped_fn = scoped_fn
         self.boosted_fn = boosted_fn
@@ -39,8 +43,8 @@ class QueryDispatcher:
         # a batch also closes when nothing new has arrived for `idle_ms`: with a fixed set of callers that all come back
         # right after their answers, waiting out the whole window for requests that cannot exist is a quarter of the cycle
         self.idle = idle_ms / 1e3
-        # (text, k, filter, the caller's future, doc_ids, boost spec, recommend request)
-        self._queue: "asyncio.Queue[Tuple[str, int, Optional[Dict], asyncio.Future, Optional[List[str]], Any, Any]]" = \
+        # (text, k, filter, the caller's future, doc_ids, boost spec, recommend request, learned sparse?)
+        self._queue: "asyncio.Queue[Tuple[str, int, Optional[Dict], asyncio.Future, Optional[List[str]], Any, Any, bool]]" = \
             asyncio.Queue()
         self._task: Optional[asyncio.Task] = None
         self.stats = {"requests": 0, "batches": 0, "max_batch_seen": 0}
@@ -60,8 +64,10 @@ class QueryDispatcher:
 
     async def submit(self, text: str, n_results: int = 5, filter_dict: Optional[Dict] = None,
                      doc_ids: Optional[List[str]] = None, boost: Any = None,
-                     recommend: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
-        """`recommend`: a request of positive and negative examples (EmbeddingManager.recommend's dict; needs a
+                     recommend: Optional[Dict[str, Any]] = None, sparse: bool = False) -> Dict[str, Any]:
+        """`sparse`: answer by learned sparse retrieval (needs a `sparse_fn`; takes no doc_ids, boost or recommend
+        request): requests of one k and one filter share one batch -- one expansion forward, one impact search.
+        `recommend`: a request of positive and negative examples (EmbeddingManager.recommend's dict; needs a
         `recommend_fn`; `text` is not read): requests of one k -- and one filter, which is one alive bitmap per scan --
         share one batch whatever their examples.
         `boost`: a boost spec (an object with a canonical `batch_key()`; needs a `boosted_fn`): the request is ranked with
@@ -75,12 +81,14 @@ class QueryDispatcher:
             raise ValueError("a boosted request needs a boosted_fn and takes no doc_ids")
         if recommend is not None and (self.recommend_fn is None or doc_ids is not None or boost is not None):
             raise ValueError("a recommend request needs a recommend_fn and takes neither doc_ids nor a boost")
+        if sparse and (self.sparse_fn is None or doc_ids is not None or boost is not None or recommend is not None):
+            raise ValueError("a sparse request needs a sparse_fn and takes no doc_ids, boost or recommend request")
         self.start()
         if doc_ids is not None and (self.scoped_fn is None or filter_dict is not None):
             only = {"doc_id": {"$in": list(doc_ids)}}
             filter_dict, doc_ids = ({"$and": [filter_dict, only]} if filter_dict else only), None
         fut: asyncio.Future = asyncio.get_running_loop().create_future()
-        await self._queue.put((text, n_results, filter_dict, fut, doc_ids, boost, recommend))
+        await self._queue.put((text, n_results, filter_dict, fut, doc_ids, boost, recommend, bool(sparse)))
         return await fut
 
     async def _run(self):
@@ -105,8 +113,10 @@ class QueryDispatcher:
             # filter); the requests with doc_ids are one group per k, the boosted ones
             # one per (k, filter, spec key), the recommend ones one per (k, filter)
             groups: Dict[Any, List[int]] = {}
-            for i, (_, k, flt, _, docs, boost, rec) in enumerate(batch):
-                if rec is not None:
+            for i, (_, k, flt, _, docs, boost, rec, sparse) in enumerate(batch):
+                if sparse:
+                    key = ("sparse", k, repr(flt))
+                elif rec is not None:
                     key = ("recommend", k, repr(flt))
                 elif boost is not None:
                     key = ("boosted", k, repr(flt), boost.batch_key())
@@ -120,7 +130,9 @@ class QueryDispatcher:
             for key, idxs in groups.items():
                 k, flt = batch[idxs[0]][1], batch[idxs[0]][2]
                 try:
-                    if key[0] == "recommend":
+                    if key[0] == "sparse":
+                        results = await self.sparse_fn([batch[i][0] for i in idxs], k, flt)
+                    elif key[0] == "recommend":
                         results = await self.recommend_fn([batch[i][6] for i in idxs], k, flt)
                     elif key[0] == "boosted":
                         results = await self.boosted_fn([batch[i][0] for i in idxs], k, flt, batch[idxs[0]][5])

@@ -43,6 +43,8 @@ RESULT_KEYS = ("ids", "distances", "metadatas", "documents")
 HYBRID_KEYS = RESULT_KEYS + ("hybrid_scores", "lexical_scores")
 MMR_KEYS = RESULT_KEYS + ("mmr_scores",)
 LATE_KEYS = RESULT_KEYS + ("late_scores",)
+SPARSE_KEYS = RESULT_KEYS + ("sparse_scores",)
+SPARSE_HYBRID_KEYS = RESULT_KEYS + ("hybrid_scores", "sparse_scores")
 FUSED_KEYS = RESULT_KEYS + ("fused_scores", "matched_queries", "best_query")
 BOOST_KEYS = RESULT_KEYS + ("scores", "boosts")
 RECOMMEND_KEYS = RESULT_KEYS + ("scores", "penalties", "matched", "repelled_by")
@@ -64,6 +66,9 @@ _NEEDS_RECOMMEND = ("recommend_query", "recommend retrieval needs a single-GPU c
 _NEEDS_RELATED = ("related_query", "related-document retrieval needs a single-GPU collection (VectorIndex) with "
                                    "full-precision rows")
 _NEEDS_RANGE = ("range_query", "range retrieval needs a single-GPU collection (VectorIndex) with full-precision rows")
+_NEEDS_SPARSE = ("sparse_query", "learned sparse retrieval needs a single-GPU collection (VectorIndex) and a sparse "
+                                  "encoder (MMRAG_SPARSE_ENCODER_DIR, or EmbeddingManager.enable_sparse)")
+_sparse_warned = False   # "MMRAG_SPARSE_ENCODER_DIR is set but this collection cannot keep sparse vectors": once per process
 _NEEDS_LATE = ("late_query", "late retrieval needs a single-GPU collection (VectorIndex) with a token store")
 _late_store_warned = False   # "MMRAG_LATE_STORE is set but this embedder cannot keep token rows": once per process
 _boost_warned = False   # "this collection cannot boost": once per process
@@ -72,6 +77,7 @@ _dedup_warned = False    # "MMRAG_DEDUP_THRESHOLD is set but this collection can
 _EMPTY = {key: [] for key in RESULT_KEYS}
 _EMPTY_MMR = {key: [] for key in MMR_KEYS}
 _EMPTY_LATE = {key: [] for key in LATE_KEYS}
+_EMPTY_SPARSE = {key: [] for key in SPARSE_KEYS}
 _EMPTY_FUSED = {key: [] for key in FUSED_KEYS}
 _EMPTY_BOOST = {key: [] for key in BOOST_KEYS}
 _EMPTY_RECOMMEND = {key: [] for key in RECOMMEND_KEYS}
@@ -111,6 +117,8 @@ class EmbeddingManager:
         self._reranker = None                    # cross-encoder (MMRAG_RERANKER_DIR), loaded on first use
         self._reranker_lock = threading.Lock()
         self._late = None                        # late.LateInteractionScorer over the engine's own encoder, on first use
+        self._sparse = None                      # sparse.DeviceSparseEncoder (MMRAG_SPARSE_ENCODER_DIR), on first use
+        self._sparse_lock = threading.Lock()
 
     # ------------------------------------------------------------------ lifecycle -----------
     async def initialize(self):
@@ -312,6 +320,14 @@ class EmbeddingManager:
                     _late_store_warned = True
                     logger.warning("MMRAG_LATE_STORE=1 is ignored: the token store needs a single BERT-family fp16 HIP "
                                    "engine with a tokenizer and a single-GPU collection")
+        if self.has_sparse_encoder():
+            if self.supports_sparse():
+                await asyncio.to_thread(self._store_sparse, ids, texts)
+            else:
+                global _sparse_warned
+                if not _sparse_warned:
+                    _sparse_warned = True
+                    logger.warning("MMRAG_SPARSE_ENCODER_DIR is ignored: %s", _NEEDS_SPARSE[1])
         if skipped:
             logger.info("Skipped %d near-duplicate items of doc %s (cosine >= %s)", skipped, doc_id, dedup)
         self.stats["total_items_stored"] += len(summaries)
@@ -352,6 +368,9 @@ class EmbeddingManager:
         def boosted(texts, n_results, filter_dict, spec):
             return self.batch_boosted_query(texts, n_results=n_results, filter_dict=filter_dict, boost=spec)
 
+        def sparse(texts, n_results, filter_dict):
+            return self.batch_sparse_query(texts, n_results=n_results, filter_dict=filter_dict)
+
         def recommend(requests, n_results, filter_dict):      # a failing engine raises: only a request's own fault
             return self.batch_recommend(requests, n_results=n_results, filter_dict=filter_dict,     # is an 'error'
                                         raise_engine_errors=True)
@@ -360,6 +379,8 @@ class EmbeddingManager:
                                            scoped_fn=scoped if self.supports_scoped() else None,
                                            boosted_fn=boosted if self.supports_boost() else None,
                                            recommend_fn=recommend if self.supports_recommend() else None,
+                                           sparse_fn=sparse if self.has_sparse_encoder() and self.supports_sparse()
+                                           else None,
                                            filtered_fn=filtered if (settings.MMRAG_DEVICE_FILTERS
                                                                     and self.supports_device_filters()) else None)
         return self._dispatcher
@@ -764,12 +785,153 @@ class EmbeddingManager:
         return [{key: res[key][at] for key in HYBRID_KEYS} for at in range(len(texts))]
 
     async def hybrid_query(self, query_text: str, n_results: int = 5,
-                           filter_dict: Optional[Dict] = None) -> Dict[str, Any]:
+                           filter_dict: Optional[Dict] = None, leg: str = "lexical") -> Dict[str, Any]:
         """Dense + BM25 retrieval fused by reciprocal rank (VectorIndex.hybrid_query): one result dict with `ids`,
         `distances`, `metadatas`, `documents`, `hybrid_scores` and `lexical_scores`, in hybrid-score order (distances
         are therefore not ascending).  Same empty-query error, embedding cache and query count as query(); it calls
-        the collection directly (no dynamic batching)."""
+        the collection directly (no dynamic batching).  `leg` = "sparse": the second leg is learned sparse retrieval
+        instead of BM25 (VectorIndex.sparse_hybrid_query) and the dict carries `sparse_scores` in place of
+        `lexical_scores`."""
+        if leg == "sparse":
+            await self._ready()
+            if not (self.has_sparse_encoder() and self.supports_sparse()):
+                raise ValueError(_NEEDS_SPARSE[1])
+            return await self._single("Sparse hybrid query", _NEEDS_SPARSE, self._answer_sparse_hybrid, query_text,
+                                      n_results, filter_dict)
+        if leg != "lexical":
+            raise ValueError(f"hybrid leg must be 'lexical' or 'sparse', not {leg!r}")
         return await self._single("Hybrid query", _NEEDS_HYBRID, self._answer_hybrid, query_text, n_results, filter_dict)
+
+    # ------------------------------------------------------------------ learned sparse ------
+    def has_sparse_encoder(self) -> bool:
+        """True when a sparse encoder is configured (MMRAG_SPARSE_ENCODER_DIR) or was attached (enable_sparse)"""
+        return self._sparse is not None or bool(settings.MMRAG_SPARSE_ENCODER_DIR)
+
+    def supports_sparse(self) -> bool:
+        """True when the collection can keep and search learned sparse vectors: a single-GPU VectorIndex (not the
+        sharded serving path) behind a BERT-family fp16 HIP engine (not the CLIP engine, not the fp32 encoder mode)"""
+        if self.collection is not None and not hasattr(self.collection, "sparse_query"):
+            return False
+        eng = self._engine
+        if eng is None:
+            return True
+        return not hasattr(eng, "encode_images") and getattr(getattr(eng, "encoder", None), "_f32", False) is False
+
+    def _get_sparse(self):
+        """the sparse encoder of MMRAG_SPARSE_ENCODER_DIR, loaded once on the embedder's device"""
+        with self._sparse_lock:
+            if self._sparse is None:
+                from .sparse import DeviceSparseEncoder
+
+                if not settings.MMRAG_SPARSE_ENCODER_DIR:
+                    raise ValueError(_NEEDS_SPARSE[1])
+                device = str(getattr(self.collection, "device", None) or "cuda:0")
+                self._sparse = DeviceSparseEncoder.from_local_dir(settings.MMRAG_SPARSE_ENCODER_DIR, device)
+            return self._sparse
+
+    def _doc_terms(self) -> int:
+        return max(1, min(int(settings.MMRAG_SPARSE_DOC_TERMS), 256))
+
+    def _query_terms(self) -> int:
+        return max(1, min(int(settings.MMRAG_SPARSE_QUERY_TERMS), 64))
+
+    def _store_sparse(self, ids: Sequence[str], texts: Sequence[Optional[str]], batch: int = 256):
+        """blocking: expand the texts and give the stored rows their sparse vectors (rows that were skipped as
+        duplicates have no row and are passed over)"""
+        enc = self._get_sparse()
+        self.collection.enable_sparse(enc.cfg.vocab)
+        rows = self.collection.rows_of_ids(list(ids))
+        have = [at for at, r in enumerate(rows) if r >= 0]
+        for s in range(0, len(have), batch):
+            part = have[s: s + batch]
+            off, terms, imps = enc.expand_texts([texts[at] or "" for at in part], self._doc_terms())
+            self.collection.set_sparse([rows[at] for at in part], off, terms, imps)
+
+    def _enable_sparse_sync(self, encoder) -> Dict[str, Any]:
+        if encoder is not None:
+            self._sparse = encoder
+        if not self.supports_sparse():
+            raise ValueError(_NEEDS_SPARSE[1])
+        enc = self._get_sparse()
+        c = self.collection
+        c.enable_sparse(enc.cfg.vocab)
+        got = c.get(include=["documents"])
+        self._store_sparse(got["ids"], got["documents"])
+        return {"items": len(got["ids"]), "vocab": enc.cfg.vocab}
+
+    async def enable_sparse(self, encoder=None) -> Dict[str, Any]:
+        """Attach a sparse encoder (`encoder`: a DeviceSparseEncoder; None: the one of MMRAG_SPARSE_ENCODER_DIR) and
+        expand the documents already stored, in batches -- the sparse state is not persisted, so this is also what
+        brings it back after a restore.  From then on embed_and_store expands what it stores."""
+        await self._ready()
+        return await asyncio.to_thread(self._enable_sparse_sync, encoder)
+
+    def _sparse_queries(self, texts: Sequence[str]):
+        enc = self._get_sparse()
+        if settings.MMRAG_SPARSE_QUERY_MODE == "tokens":
+            return enc.token_terms(list(texts), self._query_terms())
+        return enc.expand_texts(list(texts), self._query_terms())
+
+    @staticmethod
+    def _sparse_distances(res: Dict[str, Any]) -> List[List[float]]:
+        # there is no cosine: a source's relevance reads the sparse score itself, cut to 0..1
+        return [[max(0.0, 1.0 - s) for s in row] for row in res["sparse_scores"]]
+
+    def _answer_sparse(self, texts: Sequence[str], n_results: int, filter_dict: Optional[Dict],
+                       explain: bool = False) -> List[Dict[str, Any]]:
+        """blocking, one worker thread: ONE expansion of the questions (or their word pieces), ONE impact search"""
+        queries = self._sparse_queries(texts)
+        enc = self._get_sparse()
+        self.collection.enable_sparse(enc.cfg.vocab)
+        scales = (enc.scale, enc.scale)
+        res = self.collection.sparse_query(queries, n_results=n_results, where=filter_dict,
+                                           include=("metadatas", "documents"), scales=scales)
+        res["distances"] = self._sparse_distances(res)
+        out = [{key: res[key][at] for key in SPARSE_KEYS} for at in range(len(texts))]
+        if explain:
+            off, terms, imps = queries
+            for at, hit in enumerate(out):
+                qt, qi = terms[off[at]: off[at + 1]], imps[off[at]: off[at + 1]]
+                hit["matched_terms"] = []
+                for row in res["rows"][at]:
+                    pairs = self.collection.sparse_explain(qt, qi, row, scales)
+                    names = enc.terms_to_strings([t for t, _ in pairs])
+                    hit["matched_terms"].append([{"term": n, "score": c} for n, (_, c) in zip(names, pairs)])
+        return out
+
+    def _answer_sparse_hybrid(self, texts: Sequence[str], n_results: int,
+                              filter_dict: Optional[Dict]) -> List[Dict[str, Any]]:
+        enc = self._get_sparse()
+        self.collection.enable_sparse(enc.cfg.vocab)
+        res = self.collection.sparse_hybrid_query(self._embed(texts), self._sparse_queries(texts), n_results=n_results,
+                                                  where=filter_dict, include=self._INCLUDE,
+                                                  scales=(enc.scale, enc.scale))
+        return [{key: res[key][at] for key in SPARSE_HYBRID_KEYS} for at in range(len(texts))]
+
+    async def sparse_query(self, query_text: str, n_results: int = 5, filter_dict: Optional[Dict] = None,
+                           explain: bool = False) -> Dict[str, Any]:
+        """Learned sparse retrieval (VectorIndex.sparse_query): the question is expanded by the sparse encoder
+        (MMRAG_SPARSE_QUERY_MODE=tokens: its own word pieces, no forward pass) and scored exactly against the stored
+        sparse vectors.  One result dict with `ids`, `metadatas`, `documents`, `sparse_scores` (descending) and
+        `distances` = max(0, 1 - sparse score) (there is no cosine).  `explain`: `matched_terms`, per hit the shared
+        vocabulary strings with their contribution to the score, best first.  Same empty-query error and query
+        count as query(); with dynamic batching on, concurrent callers of one n_results and filter share one batch."""
+        if not self.has_sparse_encoder():
+            raise ValueError(_NEEDS_SPARSE[1])
+        if explain or self._dispatcher is None or getattr(self._dispatcher, "sparse_fn", None) is None:
+            return await self._single("Sparse query", _NEEDS_SPARSE, self._answer_sparse, query_text, n_results,
+                                      filter_dict, explain)
+        await self._ready()
+        if not query_text or not query_text.strip():
+            raise ValueError("Query text cannot be empty")
+        return await self._dispatcher.submit(query_text, n_results, filter_dict, sparse=True)
+
+    async def batch_sparse_query(self, queries: List[str], n_results: int = 5,
+                                 filter_dict: Optional[Dict] = None) -> List[Dict[str, Any]]:
+        """batch_query's twin for sparse_query: one expansion forward and one impact search for all the queries; a
+        query that cannot be answered gets a dict with empty lists and an 'error' message."""
+        return await self._batch("Batch sparse query", _NEEDS_SPARSE, _EMPTY_SPARSE, self._answer_sparse, queries,
+                                 n_results, filter_dict)
 
     def supports_mmr(self) -> bool:
         """True when the collection can answer mmr_query (a single-GPU VectorIndex; not the sharded serving path, whose

@@ -230,6 +230,8 @@ class VectorIndex:
         self._deep_ws: Optional[torch.Tensor] = None      # workspace of the deep search (n_results > 20), reused
         self._scoped_ws: Optional[torch.Tensor] = None    # workspace of the scoped search, reused
         self._lex = None   # lexical.LexicalIndex once enable_lexical() ran (lazily: first lexical / hybrid query)
+        self._sparse = None          # sparse.ImpactIndex once enable_sparse() ran (opt-in: learned sparse vectors)
+        self._pending_sparse = None  # the vectors of the rows add() is appending, consumed by _appended()
         self._groups: Dict[str, Dict[str, Any]] = {}   # metadata key -> group column state once enable_grouping(key) ran
         self._boosted_ws: Optional[torch.Tensor] = None   # workspace of the boosted search, reused
         self._recommend_ws: Optional[torch.Tensor] = None   # workspace of the recommend search, reused
@@ -401,8 +403,9 @@ class VectorIndex:
     # ------------------------------------------------------------------ collection API ----
     def add(self, embeddings, documents: Optional[Sequence[Optional[str]]] = None,
             metadatas: Optional[Sequence[Dict[str, Any]]] = None, ids: Optional[Sequence[str]] = None,
-            dedup_threshold: Optional[float] = None, timestamps=None):
-        """Append rows (collection.add).  `timestamps`: when each row was added, a UNIX time or one per row (NaN =
+            dedup_threshold: Optional[float] = None, timestamps=None, sparse=None):
+        """Append rows (collection.add).  `sparse`: the rows' learned sparse vectors (off, terms, impacts) as
+        `DeviceSparseEncoder.expand_ids` returns them (needs enable_sparse(); without it the rows get empty vectors).  `timestamps`: when each row was added, a UNIX time or one per row (NaN =
         unknown; default: now) -- what a recency prior reads (set_prior), stored beside the rows and never in their
         metadata.  `dedup_threshold` (None: off, returns None): a cosine t in (0, 1]; a row whose
         best stored row scores >= t, or that pairs (>= t) with an earlier row of this batch that is itself kept, is
@@ -422,6 +425,12 @@ class VectorIndex:
         if len(documents) != m or len(metadatas) != m:
             raise ValueError("documents / metadatas length mismatch")
         times = self._row_times(timestamps, m)
+        if sparse is not None:
+            from .sparse import check_sparse_rows
+
+            if self._sparse is None:
+                raise ValueError("add(sparse=...) needs enable_sparse(vocab_size) first")
+            sparse = check_sparse_rows(*sparse, self._sparse.n_terms, m, _native.MAX_SPARSE_TERMS, "add(sparse=...)")
         with self._lock:
             fresh = [i for i, s in enumerate(ids) if s not in self._row_of]
             seen = set()
@@ -452,6 +461,12 @@ class VectorIndex:
                 self._ids.append(ids[i])
                 self._documents.append(documents[i])
                 self._metadatas.append(metadatas[i])
+            if sparse is not None:      # the vectors of the kept rows, in their order
+                off, terms, imps = sparse
+                lens = np.diff(off)[keep]
+                src = np.repeat(off[keep], lens) + (np.arange(int(lens.sum()), dtype=np.int64)
+                                                    - np.repeat(np.cumsum(lens) - lens, lens))
+                self._pending_sparse = (np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), terms[src], imps[src])
             self._appended(len(keep), times[keep])
             return None if dedup_threshold is None else {"added": [ids[i] for i in keep], "skipped": skipped}
 
@@ -741,6 +756,12 @@ class VectorIndex:
         self._set_alive(lo, hi)
         if self._lex is not None:
             self._lex.append(self._documents[lo:hi])
+        if self._sparse is not None:
+            pending, self._pending_sparse = self._pending_sparse, None
+            if pending is not None:
+                self._sparse.append(*pending)
+            else:
+                self._sparse.append_empty(m)
         if self._groups:
             self._groups_appended(lo, hi)
         self._n = hi
@@ -1064,6 +1085,8 @@ class VectorIndex:
                 self._set_alive(0, self._n)
             if self._lex is not None:
                 self._lex.compact(keep)
+            if self._sparse is not None:
+                self._sparse.compact(keep)
             for st in self._groups.values():      # the same kept rows, in order; ordinals keep their values
                 st["col"] = self._compacted(st["col"], cap, keep_dev, -1)
                 live = st["col"][: self._n]
@@ -1086,6 +1109,8 @@ class VectorIndex:
             self._alive_dev.zero_()
             if self._lex is not None:
                 self._lex.reset()
+            if self._sparse is not None:
+                self._sparse.reset()
             self._groups = {}
             self._added_at[:] = np.nan
             self._filter_cols.reset()
@@ -2420,5 +2445,150 @@ class VectorIndex:
             self._append_hits(out, tables, rows, include)
             out["hybrid_scores"].append([s for _, s in top])
             out["lexical_scores"].append([lex.get(r, 0.0) for r in rows])
+            out["distances"].append([dist_dense[b][dpos[r]] if r in dpos else extra[(b, r)] for r in rows])
+        return out
+
+    # ------------------------------------------------------------------ learned sparse ----
+    def enable_sparse(self, vocab_size: int):
+        """Attach the learned sparse state (sparse.ImpactIndex over a vocabulary of `vocab_size` terms); the rows already
+        stored get empty vectors until set_sparse() gives them theirs.  From then on add(sparse=...), compact and
+        reset keep it current; a delete needs nothing (the alive bits filter dead rows).  Opt-in: without this call
+        the collection does no sparse work."""
+        with self._lock:
+            if self._sparse is None:
+                from .sparse import ImpactIndex
+
+                sp = ImpactIndex(self.device, vocab_size)
+                sp.append_empty(self._n)
+                self._sparse = sp
+            elif self._sparse.n_terms != int(vocab_size):
+                raise ValueError(f"the sparse state has {self._sparse.n_terms} terms, not {vocab_size}")
+            return self._sparse
+
+    @property
+    def sparse_enabled(self) -> bool:
+        return self._sparse is not None
+
+    def _need_sparse(self, who: str):
+        if self._sparse is None:
+            raise RuntimeError(f"{who} needs enable_sparse(vocab_size) first")
+        return self._sparse
+
+    def set_sparse(self, rows, off, terms, impacts):
+        """Replace the sparse vectors of stored rows `rows` (row numbers; see rows_of_ids) by (off, terms, impacts):
+        vector i = terms[off[i] .. off[i + 1]) ascending and distinct, impacts 1..255."""
+        with self._lock:
+            sp = self._need_sparse("set_sparse")
+            rows = np.ascontiguousarray(rows, np.int64)
+            if rows.size and (rows.min() < 0 or rows.max() >= self._n):
+                raise ValueError("set_sparse: row outside the collection")
+            from .sparse import check_sparse_rows
+
+            check_sparse_rows(off, terms, impacts, sp.n_terms, rows.size, _native.MAX_SPARSE_TERMS, "set_sparse")
+            sp.set_rows(rows, off, terms, impacts)
+
+    def sparse_search(self, sparse_queries, n_results: int = 10, where: Optional[Dict[str, Any]] = None,
+                      cap: int = 0, dbg: int = 0):
+        """enqueue the impact search (csrc/sparse_score.hip): device (scores [B, k] float32 = the exact integer score,
+        rows [B, k] int64), descending, ties to the lower row, (-inf, -1) padded.  `sparse_queries` = (off, terms,
+        impacts): query i's distinct terms[off[i] .. off[i + 1]), at most 64, impacts 1..255.  `cap`, `dbg`: the
+        kernel's test hook."""
+        with self._lock:
+            sp = self._need_sparse("sparse_search")
+            return sp.topk(*sparse_queries, n_results, self._where_bits(where), cap, dbg)
+
+    @staticmethod
+    def _sparse_norm(scales) -> float:
+        from .config import settings
+
+        if scales is None:
+            scales = (settings.MMRAG_SPARSE_IMPACT_SCALE, settings.MMRAG_SPARSE_IMPACT_SCALE)
+        return float(scales[0]) * float(scales[1])
+
+    def sparse_query(self, sparse_queries, n_results: int = 10, where: Optional[Dict[str, Any]] = None,
+                     include: Sequence[str] = ("metadatas", "documents"), scales=None) -> Dict[str, Any]:
+        """Learned sparse search as Chroma-shaped lists of lists `ids`, `documents`, `metadatas` and `sparse_scores` =
+        integer score / (query scale x document scale), i.e. the dot product of the two un-quantised vectors up to
+        rounding (`scales`: the two impact scales, default MMRAG_SPARSE_IMPACT_SCALE for both).  Only rows sharing a
+        term with the query are returned, so a list may be shorter than n_results."""
+        norm = self._sparse_norm(scales)
+        with self._lock:
+            scores, rows = self.sparse_search(sparse_queries, n_results, where)
+            tables = self._tables()
+        scores_h, rows_h = scores.cpu(), rows.cpu()
+        out: Dict[str, Any] = {"ids": [], "documents": [] if "documents" in include else None,
+                               "metadatas": [] if "metadatas" in include else None, "sparse_scores": [], "rows": []}
+        for srow, rrow in zip(scores_h.tolist(), rows_h.tolist()):
+            hit = [r for r in rrow if r >= 0]
+            self._append_hits(out, tables, hit, include)
+            out["sparse_scores"].append([s / norm for s in srow[: len(hit)]])
+            out["rows"].append(hit)
+        return out
+
+    def sparse_explain(self, q_terms, q_impacts, row: int, scales=None) -> List[Tuple[int, float]]:
+        """[(term id, contribution)] of one query against one stored row, best first (ties to the lower term): the
+        overlapping terms and their share of sparse_scores, from the host copy of the forward log"""
+        norm = self._sparse_norm(scales)
+        with self._lock:
+            d_terms, d_imp = self._need_sparse("sparse_explain").row_vector(int(row))
+        qw = {int(t): int(w) for t, w in zip(q_terms, q_impacts)}
+        both = [(int(t), qw[int(t)] * int(w) / norm) for t, w in zip(d_terms, d_imp) if int(t) in qw]
+        return sorted(both, key=lambda x: (-x[1], x[0]))
+
+    def sparse_hybrid_query(self, query_embeddings, sparse_queries, n_results: int = 10,
+                            where: Optional[Dict[str, Any]] = None,
+                            include: Sequence[str] = ("metadatas", "documents", "distances"),
+                            check_norm: bool = True, scales=None) -> Dict[str, Any]:
+        """Dense + learned sparse retrieval fused by reciprocal rank (lexical.rrf_fuse), as hybrid_query fuses dense +
+        BM25: each leg takes C = max(n_results, MMRAG_HYBRID_CANDIDATES) hits (at most 4096) under the same `where`.
+        Returns `ids`, `documents`, `metadatas`, `distances`, `hybrid_scores` and `sparse_scores` (0.0 for rows the
+        sparse leg did not return), ordered by hybrid score."""
+        from .config import settings
+        from .lexical import rows_dot, rrf_fuse
+
+        self._need_plane("sparse_hybrid_query")
+        if n_results < 1:
+            raise ValueError("n_results must be >= 1")
+        norm = self._sparse_norm(scales)
+        C = min(max(n_results, settings.MMRAG_HYBRID_CANDIDATES), _native.MAX_K_DEEP)
+        n_q = len(sparse_queries[0]) - 1
+        with self._lock:
+            if self._plane is not None:
+                query_embeddings = self._to_device_f32(query_embeddings, "query", check_norm)
+                check_norm = False
+                q = self._pack_plane_queries(query_embeddings)
+            else:
+                q = self._pack_queries(query_embeddings, check_norm)
+            if q.shape[0] != n_q:
+                raise ValueError(f"{q.shape[0]} query embeddings for {n_q} sparse queries")
+            d_scores, d_rows = self._launch_search(query_embeddings, C, where, check_norm)
+            s_scores, s_rows = self.sparse_search(sparse_queries, C, where)
+            tables = self._tables()
+            d_s, d_r = d_scores.cpu(), d_rows.cpu()
+            s_s, s_r = s_scores.cpu().tolist(), s_rows.cpu().tolist()
+            dist_dense = (1.0 - d_s).tolist()
+            fused, need = [], []
+            for b in range(n_q):
+                drow = [r for r in d_r[b].tolist() if r >= 0]
+                srow = [r for r in s_r[b] if r >= 0]
+                top = rrf_fuse(drow, srow, settings.MMRAG_HYBRID_RRF_K)[:n_results]
+                dpos = {r: i for i, r in enumerate(drow)}
+                fused.append((top, dpos, {r: s_s[b][i] / norm for i, r in enumerate(srow)}))
+                need.extend((b, r) for r, _ in top if r not in dpos)
+            if need:
+                dots = rows_dot(q, self._full, self.dim, torch.tensor([b for b, _ in need], device=self.device),
+                                torch.tensor([r for _, r in need], device=self.device))
+                extra = dict(zip(need, (1.0 - dots.cpu()).tolist()))
+            else:
+                extra = {}
+        out: Dict[str, Any] = {"ids": [], "distances": [], "hybrid_scores": [], "sparse_scores": [], "rows": [],
+                               "documents": [] if "documents" in include else None,
+                               "metadatas": [] if "metadatas" in include else None}
+        for b, (top, dpos, sp) in enumerate(fused):
+            rows = [r for r, _ in top]
+            self._append_hits(out, tables, rows, include)
+            out["hybrid_scores"].append([s for _, s in top])
+            out["sparse_scores"].append([sp.get(r, 0.0) for r in rows])
+            out["rows"].append(rows)
             out["distances"].append([dist_dense[b][dpos[r]] if r in dpos else extra[(b, r)] for r in rows])
         return out

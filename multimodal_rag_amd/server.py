@@ -54,6 +54,14 @@ class QueryRequest(BaseModel):  # api.py:161-164
     # .hybrid_query); each source then carries its `hybrid_score`.  With `rerank`, max(top_k, MMRAG_RERANK_CANDIDATES)
     # hybrid hits are re-ranked
     hybrid: bool = Field(False)
+    # with `hybrid`: the second leg, "lexical" (BM25, the default) or "sparse" (learned sparse retrieval: each source
+    # then carries its `sparse_score` too)
+    hybrid_leg: Optional[Literal["lexical", "sparse"]] = None
+    # not in the reference: hits by learned sparse retrieval alone (EmbeddingManager.sparse_query: the question expanded
+    # by the masked-LM of MMRAG_SPARSE_ENCODER_DIR, scored exactly against the stored sparse vectors); each source
+    # carries its `sparse_score` and, with `explain`, `matched_terms`: the shared vocabulary strings with their
+    # contribution, best first.  Takes `filter` and `doc_ids`; not combined with the other modes or `rerank` yet
+    sparse: bool = Field(False)
     # not in the reference: diversified hits (EmbeddingManager.mmr_query: maximal marginal relevance over
     # MMRAG_MMR_CANDIDATES dense hits); each source then carries its `mmr_score`.  `mmr_lambda` (default
     # MMRAG_MMR_LAMBDA): 1 = plain relevance, 0 = pure diversity.  With `rerank`, max(top_k, MMRAG_RERANK_CANDIDATES)
@@ -208,6 +216,12 @@ MODE_NEEDS = (
      "(EmbeddingManager.mmr_query); a float8_e4m3fn collection also needs its re-scoring plane "
      "(MMRAG_F8_RESCORE=float16)"),
 )
+
+
+# learned sparse retrieval (`sparse`, `hybrid_leg`: "sparse"): the same
+SPARSE_NEEDS = ("sparse_query", "supports_sparse",
+                "Learned sparse retrieval is not available with this embedder: it needs a single-GPU collection, the "
+                "fp16 BERT engine and a sparse encoder (MMRAG_SPARSE_ENCODER_DIR, EmbeddingManager.enable_sparse)")
 
 
 # multi-query retrieval (`variants` / `expand`): the same
@@ -440,7 +454,8 @@ class Pipeline:
                      rerank_method: Optional[str] = None, explain: bool = False, boost: Any = None,
                      recommend: Optional[Dict[str, Any]] = None,
                      filter_dict: Optional[Dict[str, Any]] = None, late: bool = False,
-                     passage_tokens: Optional[int] = None) -> Optional[dict]:
+                     passage_tokens: Optional[int] = None, sparse: bool = False,
+                     hybrid_leg: Optional[str] = None) -> Optional[dict]:
         """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
         max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the re-ranker's best top_k (`rerank_method` "cross" or "late",
         default MMRAG_RERANK_METHOD; `explain`: late interaction's per-token matches on every source).  `hybrid`: from
@@ -459,8 +474,11 @@ class Pipeline:
         the exact MaxSim top_k over the token store (EmbeddingManager.late_query).  `passage_tokens` (a window size;
         with any mode): every source carries its answer `passage` -- from the re-rank call when that is late
         interaction's, else from EmbeddingManager.extract_passages over the final hits.  The generator's context is
-        built from the retriever's raw documents either way"""
+        built from the retriever's raw documents either way.  `sparse` (alone): the hits are the learned sparse top_k
+        (EmbeddingManager.sparse_query; `explain`: every source carries its `matched_terms`).  `hybrid_leg` "sparse"
+        (with `hybrid`): the dense hits are fused with the learned sparse leg instead of BM25"""
         multi = variants is not None
+        sparse_leg = hybrid and hybrid_leg == "sparse"
         riding = passage_tokens is not None and rerank and rerank_method == "late"
         # the restriction as the filter the embedder's methods take (nothing is passed when there is none)
         docs_only = None if doc_ids is None else {"doc_id": {"$in": list(doc_ids)}}
@@ -478,6 +496,10 @@ class Pipeline:
             search = functools.partial(self.embedder.recommend, **recommend, **only)
         elif mmr:
             search = functools.partial(self.embedder.mmr_query, lambda_mult=mmr_lambda, **only)
+        elif sparse:
+            search = functools.partial(self.embedder.sparse_query, explain=explain, **only)
+        elif sparse_leg:
+            search = functools.partial(self.embedder.hybrid_query, leg="sparse", **only)
         elif hybrid:
             search = functools.partial(self.embedder.hybrid_query, **only)
         elif late:
@@ -488,6 +510,7 @@ class Pipeline:
             search = functools.partial(self.embedder.query, **only)
         # per-hit columns re-ranking carries along
         extra = ("fused_scores", "matched_queries") if multi else ("mmr_scores",) if mmr else \
+            ("hybrid_scores", "sparse_scores") if sparse_leg else \
             ("hybrid_scores",) if hybrid else ("late_scores",) if late else \
             ("scores", "boosts") if boost is not None else \
             tuple(column for column, _ in RECOMMEND_COLUMNS) if recommend is not None else ()
@@ -525,6 +548,8 @@ class Pipeline:
         ranked = self._sources(hits)
         for on, column, key in ((rerank, "rerank_scores", "rerank_score"), (hybrid, "hybrid_scores", "hybrid_score"),
                                 (mmr, "mmr_scores", "mmr_score"), (late, "late_scores", "late_score"),
+                                (sparse or sparse_leg, "sparse_scores", "sparse_score"),
+                                (sparse and explain, "matched_terms", "matched_terms"),
                                 (multi, "fused_scores", "fused_score"),
                                 (multi, "matched_queries", "matched_queries"), (boost is not None, "scores", "score"),
                                 (boost is not None, "boosts", "boost"),
@@ -673,14 +698,29 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="Grouping by document is not combined with MMR, hybrid retrieval or re-ranking "
                                        "yet: send `group_by_document` without `mmr`, `hybrid` and `rerank`")
-        if (request.rerank_method is not None or request.explain) and not request.rerank:
+        if request.hybrid_leg is not None and not request.hybrid:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                detail="`hybrid_leg` belongs to hybrid retrieval: send it with `hybrid`")
+        if request.sparse:
+            if (multi or request.mmr or request.hybrid or request.group_by_document or request.rerank or request.late
+                    or (request.boost is not None and request.boost is not False) or request.like is not None
+                    or request.unlike is not None or request.not_ is not None or request.passages):
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                    detail="Learned sparse retrieval is not combined with the other retrieval modes, "
+                                           "re-ranking or answer passages yet: send `sparse` alone, with `filter`, "
+                                           "`doc_ids` or `explain`")
+        if request.sparse or request.hybrid_leg == "sparse":
+            pipe._need(SPARSE_NEEDS)
+            if not getattr(pipe.embedder, "has_sparse_encoder", lambda: False)():
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=SPARSE_NEEDS[2])
+        if (request.rerank_method is not None or request.explain) and not request.rerank and not request.sparse:
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="`rerank_method` and `explain` belong to re-ranking: send them with `rerank`")
         try:
             late = request.rerank and (request.rerank_method or settings.rerank_method()) == "late"
         except ValueError as e:      # a setting changed to neither method after start-up
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
-        if request.explain and not late:
+        if request.explain and not late and not request.sparse:
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="`explain` needs late-interaction re-ranking: send `rerank_method`: \"late\"")
         if late:
@@ -787,6 +827,8 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
                                     **({} if recommend is None else {"recommend": recommend}),
                                     **({} if not request.filter else {"filter_dict": request.filter}),
                                     **({} if not request.late else {"late": True}),
+                                    **({} if not request.sparse else {"sparse": True}),
+                                    **({} if request.hybrid_leg is None else {"hybrid_leg": request.hybrid_leg}),
                                     **({} if window is None else {"passage_tokens": window}))
         except ValueError as e:
             if recommend is None:
