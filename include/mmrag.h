@@ -1153,6 +1153,49 @@ int mmrag_impact_topk(const int64_t *term_off, const int32_t *post_row, const in
                       const uint32_t *alive_bits, float *out_scores, int64_t *out_rows, void *workspace,
                       size_t workspace_bytes, void *stream);
 
+/* Extractive selection by sentence centrality (csrc/summarize.hip): LexRank centrality over
+ * the sentences of a unit (a chunk, or an answer's context), then a budgeted MMR selection.  One workgroup per unit.
+ *
+ * Definition, for unit u with rows x_0 .. x_{n-1} = rows[unit_start[u] .. + unit_len[u]), 1 <= n <= 128:
+ *   - S_ij = <x_i, x_j>, float32 as the 128 x 128 tile body forms it; with a bias row q = bias_rows[unit_bias[u]],
+ *     s_i = <x_i, q> in the same arithmetic;
+ *   - W_ij = S_ij if i != j and S_ij >= edge_threshold, else 0; deg_j = sum_i W_ij; inv_j = 1 / deg_j if deg_j > 0,
+ *     else 0 (an isolated sentence's mass is dropped, not redistributed);
+ *   - prior b_i = 1 / n; with a bias row r_i = max(s_i, 0) and b_i = r_i / sum(r), 1 / n when sum(r) = 0;
+ *   - p = b, then EXACTLY `iterations` steps of p'_i = alpha b_i + (1 - alpha) sum_j W_ij (p_j inv_j) (no convergence
+ *     test); rel_i = p_i / max_j p_j;
+ *   - selection: remaining = budget[u], red_i = 0; until k picks are made or no free i has cost_i <= remaining, take
+ *     the free i with cost_i <= remaining of largest v_i = lambda rel_i - (1 - lambda) red_i (ties: the lower i;
+ *     lambda and 1 - lambda are float32 and each product is rounded, as in mmrag_mmr_select); then remaining -= cost_i
+ *     and red_j = max(red_j, max(S_ij, 0)) for every j;
+ *   - every float32 sum runs over ascending index in one thread's accumulator: a unit's output bits do not depend on
+ *     the batch, the grid or its place in the plane; identical calls give identical bits;
+ *   - one launch, no workspace, no host synchronisation, no atomics (the call can be captured into a graph).
+ *
+ *   rows        dev [n_rows, ld] of `dtype` MMRAG_F32 / F16 / BF16, pad columns zero, 16-byte aligned; MMRAG_F8E4M3
+ *               returns MMRAG_EUNSUPPORTED.  ld = mmrag_padded_dim(d, dtype) or a larger width of whole 128-byte slabs
+ *   unit_start, unit_len, budget   dev [n_units] int32      cost  dev [n_rows] int32, >= 1 (indexed like rows)
+ *   bias_rows   dev [n_bias, ld] of the same dtype and ld, with unit_bias dev [n_units] int32 (-1: no bias row for that
+ *               unit); or NULL, 0, NULL
+ *   edge_threshold >= 0     alpha in (0, 1]     iterations 0..MMRAG_MAX_SUMMARY_ITERATIONS     lambda in [0, 1]
+ *   k           1..MMRAG_MAX_SUMMARY_SENTENCES
+ *   out_pos     dev [n_units, k] int32: the position inside the unit, in pick order, -1 padded
+ *   out_val     dev [n_units, k] float32: v at the pick, -inf padded
+ *   out_rel     dev [n_rows] float32 or NULL: rel of every row of a valid unit; other rows are not written
+ *   out_used    dev [n_units] int32: the cost spent
+ * MMRAG_EINVAL before anything is launched: a null pointer, a bad shape or pitch, n_rows outside 1..2^31 - 1, n_units
+ * outside 1..2^24, a parameter out of range, a bias triple given in part.  The tables live on the device and are not
+ * read by the host: a unit whose entry is out of range (unit_len outside 1..128, rows outside 0..n_rows, unit_bias
+ * outside -1..n_bias - 1) gets NaN in out_val[u, 0], -1 in all of out_pos[u], 0 in out_used[u], and its out_rel rows
+ * are not written (mmrag_maxsim_scores' rule). */
+#define MMRAG_MAX_SUMMARY_SENTENCES 128
+#define MMRAG_MAX_SUMMARY_ITERATIONS 64
+int mmrag_summary_select(const void *rows, int64_t ld, int dtype, int d, int64_t n_rows, const int32_t *unit_start,
+                         const int32_t *unit_len, int n_units, const int32_t *cost, const int32_t *budget,
+                         const void *bias_rows, int64_t n_bias, const int32_t *unit_bias, float edge_threshold,
+                         float alpha, int iterations, float lambda, int k, int32_t *out_pos, float *out_val,
+                         float *out_rel, int32_t *out_used, void *stream);
+
 /* Measured peaks for the roofline report ("a measured stream-copy bandwidth and a measured MFMA
  * micro-benchmark peak, fractions against both the vendor and the measured peaks").  Not on the product path.
  *   mmrag_device_info        CU count, maximum shader clock (MHz), HBM bytes of the current device

@@ -42,6 +42,8 @@ MAX_LATE_PAIRS = 65535
 MAX_LATE_QUESTIONS = 4096   # mmrag_maxsim_topk (MMRAG_MAX_LATE_QUESTIONS)
 # mmrag_maxsim_windows (MMRAG_LATE_WINDOW_TOKENS, MMRAG_MAX_LATE_WINDOWS)
 LATE_WINDOW_TOKENS, MAX_LATE_WINDOWS = 16, 32
+# mmrag_summary_select (MMRAG_MAX_SUMMARY_SENTENCES, MMRAG_MAX_SUMMARY_ITERATIONS)
+MAX_SUMMARY_SENTENCES, MAX_SUMMARY_ITERATIONS = 128, 64
 _DT2TORCH = {F32: torch.float32, F16: torch.float16, BF16: torch.bfloat16, F8E4M3: torch.float8_e4m3fn}
 _TORCH2DT = {v: k for k, v in _DT2TORCH.items()}
 
@@ -360,7 +362,11 @@ def _declare(lib):
     # debug form (not in include/mmrag.h): candidate capacity, switches (1 = no bound stages)
     lib.mmrag_internal_impact_topk_ex.restype = c_int
     lib.mmrag_internal_impact_topk_ex.argtypes = lib.mmrag_impact_topk.argtypes + [c_int64, ctypes.c_uint]
-    from .lexical import declare as declare_lexical   # BM25 analyzer, device index and search (csrc/lexical.hip)
+    lib.mmrag_summary_select.restype = c_int
+    lib.mmrag_summary_select.argtypes = [c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p,
+                                         c_void_p, c_void_p, c_int64, c_void_p, c_float, c_float, c_int, c_float, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    from .lexical import declare as declare_lexical  # BM25 analyzer, device index and search (csrc/lexical.hip)
 
     declare_lexical(lib)
 
@@ -1502,6 +1508,55 @@ def maxsim_windows_f8(q_codes: torch.Tensor, d_codes: torch.Tensor, dim: int, q_
     maxsim_scores_f8; sums has the bits of maxsim_scores_f8's."""
     return maxsim_windows(q_codes, d_codes, dim, q_start, q_len, d_start, d_len, pair_q, pair_d, window_blocks,
                           _f8=True)
+
+
+def summary_select(rows: torch.Tensor, d: int, unit_start: torch.Tensor, unit_len: torch.Tensor, cost: torch.Tensor,
+                   budget: torch.Tensor, k: int, edge_threshold: float, alpha: float, iterations: int, lam: float,
+                   bias_rows: Optional[torch.Tensor] = None, unit_bias: Optional[torch.Tensor] = None,
+                   want_rel: bool = True, out=None):
+    """Extractive selection by sentence centrality (include/mmrag.h mmrag_summary_select): unit u is the sentences
+    rows[unit_start[u] : unit_start[u] + unit_len[u]] (1..MAX_SUMMARY_SENTENCES of them) with costs cost[...] and the
+    budget budget[u]; LexRank centrality over the unit's similarity graph, then at most k picks by budgeted MMR.
+    `rows` [n_rows, ld] is a device tensor of a storage dtype (float32 / float16 / bfloat16), pad columns zero; the
+    four tables are DEVICE int32 tensors (unit_start, unit_len, budget [n_units]; cost [n_rows]) and are not read by
+    the host: a unit whose entry is out of range gets NaN in val[u, 0].  `bias_rows` [n_bias, ld] with `unit_bias`
+    [n_units] (device int32, -1 = none for that unit) bias units toward a row, e.g. an encoded question.  Returns
+    device tensors (pos [n_units, k] int32, -1 padded; val [n_units, k] float32, -inf padded; rel [n_rows] float32 or
+    None unless `want_rel`, rows of no valid unit not written; used [n_units] int32).  `out`: the four to write into
+    (a caller that replays a captured graph).  One launch on the current stream, no host synchronisation."""
+    who = "summary_select"
+    tables = (unit_start, unit_len, cost, budget)
+    _dev_check(rows, bias_rows, unit_bias, *tables)
+    _check_stored_rows(who, rows)
+    for t in tables + ((unit_bias,) if unit_bias is not None else ()):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != rows.device:
+            raise MMRagNativeError(f"{who}: the tables must be contiguous 1-D int32 tensors on the rows' device")
+    n_rows, n_units = int(rows.shape[0]), int(unit_start.shape[0])
+    if unit_len.shape[0] != n_units or budget.shape[0] != n_units or cost.shape[0] != n_rows:
+        raise MMRagNativeError(f"{who}: unit_start, unit_len and budget need one entry per unit, cost one per row")
+    if (bias_rows is None) != (unit_bias is None):
+        raise MMRagNativeError(f"{who}: bias_rows and unit_bias go together")
+    if bias_rows is not None:
+        _check_q_rows(who, bias_rows, rows, other="rows")
+        if unit_bias.shape[0] != n_units or bias_rows.device != rows.device:
+            raise MMRagNativeError(f"{who}: unit_bias needs one entry per unit, bias_rows the rows' device")
+    dev = rows.device
+    if out is None:
+        k_alloc = max(int(k), 1)
+        out = (torch.empty((n_units, k_alloc), dtype=torch.int32, device=dev),
+               torch.empty((n_units, k_alloc), dtype=torch.float32, device=dev),
+               torch.empty(n_rows, dtype=torch.float32, device=dev) if want_rel else None,
+               torch.empty(n_units, dtype=torch.int32, device=dev))
+    pos, val, rel, used = out
+    with torch.cuda.device(dev):
+        st = lib().mmrag_summary_select(rows.data_ptr(), rows.shape[1], _TORCH2DT[rows.dtype], int(d), n_rows,
+                                        unit_start.data_ptr(), unit_len.data_ptr(), n_units, cost.data_ptr(),
+                                        budget.data_ptr(), _ptr(bias_rows),
+                                        int(bias_rows.shape[0]) if bias_rows is not None else 0, _ptr(unit_bias),
+                                        float(edge_threshold), float(alpha), int(iterations), float(lam), int(k),
+                                        pos.data_ptr(), val.data_ptr(), _ptr(rel), used.data_ptr(), _stream_ptr(dev))
+    _check(st, "mmrag_summary_select")
+    return pos, val, rel, used
 
 
 def f8_encode_rows(src: torch.Tensor, d: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:

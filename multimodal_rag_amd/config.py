@@ -168,6 +168,18 @@ class Settings:
     # topic clustering (VectorIndex.cluster, csrc/kmeans.hip): the default number of topics of cluster() / GET /topics;
     # 0 (default) = automatic, auto_topics(live rows); else 1 .. 4096
     MMRAG_TOPICS: int = field(default_factory=lambda: int(os.getenv("MMRAG_TOPICS", "0")))
+    # the summary an upload embeds (summarize.py, csrc/summarize.hip).  MMRAG_SUMMARIZER: "fallback" (default: the
+    # chunk's first 300 characters) or "extractive": the chunk's most central sentences -- LexRank centrality over the
+    # sentence embeddings, a non-redundant set under the length budget by MMR.  An edge of the sentence graph needs a
+    # cosine of at least MMRAG_SUMMARY_EDGE_THRESHOLD; MMRAG_SUMMARY_ALPHA in (0, 1] is the weight of the prior in each
+    # of the MMRAG_SUMMARY_ITERATIONS (0..64) steps; MMRAG_SUMMARY_LAMBDA in [0, 1] trades centrality (1) against
+    # redundancy (0).  The same settings serve EmbeddingManager.extract_answer (POST /query "extractive_answer")
+    MMRAG_SUMMARIZER: str = field(default_factory=lambda: os.getenv("MMRAG_SUMMARIZER", "fallback"))
+    MMRAG_SUMMARY_EDGE_THRESHOLD: float = field(
+        default_factory=lambda: float(os.getenv("MMRAG_SUMMARY_EDGE_THRESHOLD", "0.1")))
+    MMRAG_SUMMARY_ALPHA: float = field(default_factory=lambda: float(os.getenv("MMRAG_SUMMARY_ALPHA", "0.15")))
+    MMRAG_SUMMARY_ITERATIONS: int = field(default_factory=lambda: int(os.getenv("MMRAG_SUMMARY_ITERATIONS", "32")))
+    MMRAG_SUMMARY_LAMBDA: float = field(default_factory=lambda: float(os.getenv("MMRAG_SUMMARY_LAMBDA", "0.7")))
     # CLIP engines only: embed image items from their pixels (vision tower) instead of their summary text
     MMRAG_EMBED_IMAGE_PIXELS: bool = field(default_factory=lambda: _b("MMRAG_EMBED_IMAGE_PIXELS", "true"))
 
@@ -177,6 +189,14 @@ class Settings:
         self.rerank_method()
         self.late_store_dtype()
         self.passage_tokens()
+        self.summarizer()
+
+    def summarizer(self) -> str:
+        """MMRAG_SUMMARIZER checked: 'fallback' or 'extractive' (tests set the attribute after start-up, so users call
+        this)"""
+        if self.MMRAG_SUMMARIZER not in ("fallback", "extractive"):
+            raise ValueError(f"MMRAG_SUMMARIZER must be 'fallback' or 'extractive' (got {self.MMRAG_SUMMARIZER!r})")
+        return self.MMRAG_SUMMARIZER
 
     def dedup_threshold(self) -> float:
         """MMRAG_DEDUP_THRESHOLD checked: 0 (off) or a cosine in (0, 1]"""

@@ -1551,6 +1551,43 @@ class EmbeddingManager:
         await self._ready()
         return await asyncio.to_thread(self._extract_passages_sync, list(queries), list(results_list), window_tokens)
 
+    # ---- extractive summaries and answers: sentence centrality + MMR (summarize.py, csrc/summarize.hip) ----
+    def supports_summaries(self) -> bool:
+        """True when summarize_texts / extract_answer can run: the engine leaves its embeddings on the device
+        (encode_device: the HIP engine; not the CLIP towers, not a sharded engine without it)"""
+        return hasattr(self._engine, "encode_device")
+
+    def _summarizer(self):
+        from .summarize import DeviceSummarizer
+
+        if not self.supports_summaries():
+            raise ValueError("extractive summaries need an engine with encode_device (the single-GPU HIP engine)")
+        dtype = getattr(self.collection, "dtype", None)
+        return DeviceSummarizer(self._engine, dtype if dtype is not None else settings.index_dtype())
+
+    async def summarize_texts(self, texts: List[str], max_length: int = 300, by_lines: bool = False,
+                              questions: Optional[Sequence[Optional[str]]] = None) -> List[Dict[str, Any]]:
+        """An extractive summary of every text, at most `max_length` characters: its most central sentences
+        (`by_lines`: lines, for tables) in document order -- summarize.DeviceSummarizer.summarize.  One encoder call
+        over all sentences of all texts, one mmrag_summary_select launch, one copy back.  Per text {"summary", "spans",
+        "scores"}; `questions` (one per text, None allowed) bias a text's selection toward a question."""
+        await self._ready()
+        worker = self._summarizer()
+        async with self._encode_lock:
+            return await asyncio.to_thread(worker.summarize, list(texts), max_length, questions, by_lines)
+
+    async def extract_answer(self, question: str, passages: Sequence[str], max_chars: int = 600,
+                             top_sentences: int = 8) -> Dict[str, Any]:
+        """A query-focused extract of `passages` (the hits' raw texts, in rank order): at most `top_sentences` of their
+        sentences, `max_chars` characters in all, central to the passages AND close to `question`, none repeating
+        another (summarize.DeviceSummarizer.answer).  {"answer", "quotes": [{"passage", "start", "end", "text",
+        "score"} ...] ordered by (passage, start), "considered": the number of sentences that took part (at most
+        128)}."""
+        await self._ready()
+        worker = self._summarizer()
+        async with self._encode_lock:
+            return await asyncio.to_thread(worker.answer, question, list(passages), max_chars, top_sentences)
+
     async def late_rerank(self, query_text: str, results: Dict[str, Any], top_k: Optional[int] = None,
                           explain: bool = False, passages: Optional[int] = None) -> Dict[str, Any]:
         """Re-rank `results` (any retrieval mode's answer: only its `documents` are read) by late interaction with the

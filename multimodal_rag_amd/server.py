@@ -26,6 +26,7 @@ from .embedder import EmbeddingManager
 from .index import DuplicateReportTruncated
 from .ingest import ExtractiveAnswerer, PassthroughSummarizer, TextDocumentParser
 from .retriever import MultiVectorRetriever
+from .summarize import make_summarizer
 
 logger = logging.getLogger(__name__)
 
@@ -135,6 +136,12 @@ class QueryRequest(BaseModel):  # api.py:161-164
     # and the method "late" it comes out of the re-rank call itself.  The generator's context is unchanged
     passages: bool = Field(False)
     passage_tokens: Optional[int] = Field(None, ge=16, le=512)
+    # not in the reference: an extractive answer (EmbeddingManager.extract_answer).  `answer` is then a handful of
+    # sentences QUOTED from the hits' raw text passages -- central to them, close to the question, none repeating
+    # another (sentence centrality with MMR selection, csrc/summarize.hip) -- instead of the generator's text, and every
+    # source that was quoted carries `quotes`: [{start, end, text, score}] in the passage's characters.  Works with every
+    # mode: it reads the final hits
+    extractive_answer: bool = Field(False)
 
 
 FILTER_MAX_LEAVES, FILTER_MAX_DEPTH = 32, 8
@@ -259,6 +266,13 @@ PASSAGES_NEEDS = ("extract_passages", "supports_passages",
 PASSAGE_KEYS = ("text", "char_start", "char_end", "score", "share")
 
 
+# `extractive_answer`: the same
+EXTRACT_NEEDS = ("extract_answer", "supports_summaries",
+                 "Extractive answers are not available with this embedder: they need an engine that leaves its "
+                 "embeddings on the device (the single-GPU HIP engine; EmbeddingManager.extract_answer)")
+QUOTE_KEYS = ("start", "end", "text", "score")
+
+
 # first-stage late retrieval (`late`): the same
 LATE_QUERY_NEEDS = ("late_query", "supports_late_query",
                     "Late retrieval is not available with this embedder: it needs a single BERT-family HIP engine in "
@@ -353,7 +367,8 @@ class Pipeline:
         p["llm"] = p["llm"] or ExtractiveAnswerer()
         p["mllm"] = p["mllm"] or p["llm"]
         await p["llm"].initialize()
-        p["summarizer"] = p["summarizer"] or PassthroughSummarizer(p["mllm"])
+        # (MMRAG_SUMMARIZER=extractive: the summariser finds the embedder, which is created below, at its first document)
+        p["summarizer"] = p["summarizer"] or make_summarizer(lambda: p["embedder"]) or PassthroughSummarizer(p["mllm"])
         p["embedder"] = p["embedder"] or EmbeddingManager(batch_size=32, enable_cache=True)
         p["retriever"] = p["retriever"] or MultiVectorRetriever(enable_compression=True, enable_cache=True)
         for name in ("embedder", "retriever"):
@@ -446,6 +461,19 @@ class Pipeline:
                  "type": meta.get("type", "unknown")}
                 for at, (found, dist, meta) in enumerate(zip(hits["ids"], hits["distances"], hits["metadatas"]), 1)]
 
+    async def _generate(self, question: str, ids: List[str], multimodal: bool) -> str:
+        """the generator's answer from the raw items of the hits (api.py:355-388)"""
+        raw = await self.retriever.retrieve_raw_documents(ids)
+        passages, tables, images = (raw[k] for k in self.CONTEXT_KINDS)
+        body = "\n\n".join(passages) if passages else ""
+        if multimodal and (images or tables):
+            return await self.mllm.generate_multimodal(text=body, tables=tables, images=images, max_tokens=1000,
+                                                       temperature=0.7)
+        if tables:
+            body += "\n\nBảng:\n" + "\n\n".join(tables)
+        return await self.llm.generate_text(f"Context:\n{body}\n\nCâu hỏi: {question}\n\nTrả lời:", max_tokens=1000,
+                                            temperature=0.7)
+
     async def answer(self, question: str, top_k: int, multimodal: bool, rerank: bool = False,
                      hybrid: bool = False, mmr: bool = False, mmr_lambda: Optional[float] = None,
                      group_by_document: bool = False, per_document: int = 1,
@@ -455,7 +483,7 @@ class Pipeline:
                      recommend: Optional[Dict[str, Any]] = None,
                      filter_dict: Optional[Dict[str, Any]] = None, late: bool = False,
                      passage_tokens: Optional[int] = None, sparse: bool = False,
-                     hybrid_leg: Optional[str] = None) -> Optional[dict]:
+                     hybrid_leg: Optional[str] = None, extractive: bool = False) -> Optional[dict]:
         """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
         max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the re-ranker's best top_k (`rerank_method` "cross" or "late",
         default MMRAG_RERANK_METHOD; `explain`: late interaction's per-token matches on every source).  `hybrid`: from
@@ -476,7 +504,9 @@ class Pipeline:
         interaction's, else from EmbeddingManager.extract_passages over the final hits.  The generator's context is
         built from the retriever's raw documents either way.  `sparse` (alone): the hits are the learned sparse top_k
         (EmbeddingManager.sparse_query; `explain`: every source carries its `matched_terms`).  `hybrid_leg` "sparse"
-        (with `hybrid`): the dense hits are fused with the learned sparse leg instead of BM25"""
+        (with `hybrid`): the dense hits are fused with the learned sparse leg instead of BM25.  `extractive` (with any
+        mode): the answer is EmbeddingManager.extract_answer's over the hits' raw text passages, no generator call, and
+        every quoted source carries its `quotes`"""
         multi = variants is not None
         sparse_leg = hybrid and hybrid_leg == "sparse"
         riding = passage_tokens is not None and rerank and rerank_method == "late"
@@ -534,17 +564,18 @@ class Pipeline:
             return None
         if passage_tokens is not None and "passages" not in hits:
             hits = await self.embedder.extract_passages(question, hits, window_tokens=passage_tokens)
-        raw = await self.retriever.retrieve_raw_documents(hits["ids"])
-        passages, tables, images = (raw[k] for k in self.CONTEXT_KINDS)
-        body = "\n\n".join(passages) if passages else ""
-        if multimodal and (images or tables):
-            text = await self.mllm.generate_multimodal(text=body, tables=tables, images=images, max_tokens=1000,
-                                                       temperature=0.7)
+        quoted = None
+        if extractive:
+            # hit by hit: which source a raw text passage belongs to (the buckets of one call do not say)
+            texts, owner = [], []
+            for at, found in enumerate(hits["ids"]):
+                for passage in (await self.retriever.retrieve_raw_documents([found]))[self.CONTEXT_KINDS[0]]:
+                    texts.append(passage)
+                    owner.append(at)
+            quoted = await self.embedder.extract_answer(question, texts)
+            text = quoted["answer"]
         else:
-            if tables:
-                body += "\n\nBảng:\n" + "\n\n".join(tables)
-            text = await self.llm.generate_text(f"Context:\n{body}\n\nCâu hỏi: {question}\n\nTrả lời:",
-                                                max_tokens=1000, temperature=0.7)
+            text = await self._generate(question, hits["ids"], multimodal)
         ranked = self._sources(hits)
         for on, column, key in ((rerank, "rerank_scores", "rerank_score"), (hybrid, "hybrid_scores", "hybrid_score"),
                                 (mmr, "mmr_scores", "mmr_score"), (late, "late_scores", "late_score"),
@@ -563,6 +594,9 @@ class Pipeline:
         if passage_tokens is not None:
             for src, found in zip(ranked, hits["passages"]):
                 src["passage"] = {key: found[key] for key in PASSAGE_KEYS}
+        if quoted is not None:
+            for quote in quoted["quotes"]:
+                ranked[owner[quote["passage"]]].setdefault("quotes", []).append({key: quote[key] for key in QUOTE_KEYS})
         if group_by_document:
             at = 0
             for document_rank, group in enumerate(hits["groups"], 1):
@@ -740,6 +774,8 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
                 window = request.passage_tokens if request.passage_tokens is not None else settings.passage_tokens()
             except ValueError as e:      # a setting changed out of range after start-up
                 raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
+        if request.extractive_answer:
+            pipe._need(EXTRACT_NEEDS)
         if request.filter is not None:
             try:
                 _, timed = check_filter(request.filter)
@@ -829,7 +865,8 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
                                     **({} if not request.late else {"late": True}),
                                     **({} if not request.sparse else {"sparse": True}),
                                     **({} if request.hybrid_leg is None else {"hybrid_leg": request.hybrid_leg}),
-                                    **({} if window is None else {"passage_tokens": window}))
+                                    **({} if window is None else {"passage_tokens": window}),
+                                    **({} if not request.extractive_answer else {"extractive": True}))
         except ValueError as e:
             if recommend is None:
                 raise
