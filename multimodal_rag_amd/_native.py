@@ -362,6 +362,9 @@ def _declare(lib):
     # debug form (not in include/mmrag.h): candidate capacity, switches (1 = no bound stages)
     lib.mmrag_internal_impact_topk_ex.restype = c_int
     lib.mmrag_internal_impact_topk_ex.argtypes = lib.mmrag_impact_topk.argtypes + [c_int64, ctypes.c_uint]
+    # test-only export (not in include/mmrag.h): the sizes at which the sparse kernels change path
+    lib.mmrag_internal_sparse_limits.restype = c_int
+    lib.mmrag_internal_sparse_limits.argtypes = [c_void_p] * 5
     lib.mmrag_summary_select.restype = c_int
     lib.mmrag_summary_select.argtypes = [c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p,
                                          c_void_p, c_void_p, c_int64, c_void_p, c_float, c_float, c_int, c_float, c_int,
@@ -2089,6 +2092,14 @@ def encoder_forward_tokens(desc: EncoderDesc, weight_ptrs, ids: torch.Tensor, po
 # ---- learned sparse retrieval (include/mmrag.h: mmrag_sparse_expand_forward, _pool, _select, mmrag_impact_topk) ----
 MAX_SPARSE_CHUNK_TOKENS, MAX_SPARSE_CHUNKS, MAX_SPARSE_VOCAB = 512, 65536, 65536
 MAX_SPARSE_TERMS, MAX_SPARSE_QUERY_TERMS = 256, 64
+
+
+def sparse_limits() -> dict:
+    """csrc/sparse_score.hip's and csrc/sparse_expand.hip's path sizes (mmrag_internal_sparse_limits; tests restate them
+    and compare)"""
+    v = [ctypes.c_int(0) for _ in range(5)]
+    _check(lib().mmrag_internal_sparse_limits(*[ctypes.byref(x) for x in v]), "mmrag_internal_sparse_limits")
+    return dict(zip(("impact_rows", "pool_batch", "pool_vrun", "select_terms", "tile_rows"), (int(x.value) for x in v)))
 
 
 def sparse_expand_forward_workspace_bytes(desc: EncoderDesc, T: int, B: int) -> int:

@@ -77,6 +77,16 @@ extern "C" {
 int mmrag_internal_lexical_limits(int *score_rows, int *score_terms, int *sort_lds, int *sort_grid, int *scan_terms);
 }
 
+// test-only export of the learned sparse leg's path sizes (sparse_expand.hip): rows per impact scoring workgroup
+// (sparse_score.hip), chunk pieces the pool folds per pair of barriers, the longest run of vocabulary tiles a pool
+// workgroup takes, threads (terms per step) of a select workgroup and the pair tile's rows.  Host code, no device needed.
+extern "C" {
+int mmrag_internal_sparse_limits(int *impact_rows, int *pool_batch, int *pool_vrun, int *select_terms, int *tile_rows);
+}
+namespace mmrag_impl {
+int impact_block_rows();   // sparse_score.hip's IMP_R
+}
+
 // the cross-encoder's classification head (cross_head.hip), shared by the fp16 and fp32 forwards
 namespace mmrag_impl {
 size_t cls_head_workspace_bytes(int B, int H, int NL);

@@ -361,4 +361,18 @@ int mmrag_sparse_select(const float *pooled, const float *bias, const uint32_t *
     return MMRAG_OK;
 }
 
+// The sizes at which the sparse kernels change path: rows per impact scoring workgroup, chunk pieces per pair of
+// barriers and the longest run of vocabulary tiles in the pool, terms per step of the select, rows of the pair tile.
+// The tests restate them to place their cases on the edges and compare.  Exported for them, deliberately absent from
+// include/mmrag.h.  Host code, no device needed.
+int mmrag_internal_sparse_limits(int *impact_rows, int *pool_batch, int *pool_vrun, int *select_terms, int *tile_rows) {
+    if (!impact_rows || !pool_batch || !pool_vrun || !select_terms || !tile_rows) return -1;
+    *impact_rows = impact_block_rows();
+    *pool_batch = SP_BATCH;
+    *pool_vrun = SP_VRUN;
+    *select_terms = SEL_T;
+    *tile_rows = PT;
+    return 0;
+}
+
 }  // extern "C"

@@ -164,6 +164,8 @@ int impact_topk_impl(const int64_t *term_off, const int32_t *post_row, const int
 
 }  // namespace
 
+int impact_block_rows() { return IMP_R; }
+
 }  // namespace mmrag_impl
 using namespace mmrag_impl;
 

@@ -155,18 +155,24 @@ class DeviceSparseEncoder(DeviceEncoder):
     # ---------------------------------------------------------------- forward ---------------
     MAX_BATCH_TOKENS = 1 << 16      # tokens of one forward: 256 chunks of 256
 
-    def _expand_batch(self, ids2d: np.ndarray, lens: np.ndarray, max_terms: int):
+    def _token_rows(self, ids2d: np.ndarray, lens: np.ndarray):
+        """(token rows [T, hidden] float16 of the packed sequences, un-normalised; cu int32 [B + 1]) on the device: the
+        plane mmrag_sparse_pool reads.  The caller holds _launch_lock."""
         ids, pos, cu = self._pack_rows(ids2d, lens)
         d_ids, d_pos, d_cu = self._upload(ids, pos, cu)
         T, B = int(ids.size), len(lens)
         need = _native.sparse_expand_forward_workspace_bytes(self.desc, T, B)
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        tok = _native.sparse_expand_forward(self.desc, self._ptrs, d_ids, d_pos, d_cu, int(lens.max()),
+                                            self._head_w, self._head_b, self._head_g, self._head_beta,
+                                            workspace=self._workspace)
+        return tok, d_cu
+
+    def _expand_batch(self, ids2d: np.ndarray, lens: np.ndarray, max_terms: int):
         with self._launch_lock:
-            if self._workspace is None or self._workspace.numel() < need:
-                self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-            tok = _native.sparse_expand_forward(self.desc, self._ptrs, d_ids, d_pos, d_cu, int(lens.max()),
-                                                self._head_w, self._head_b, self._head_g, self._head_beta,
-                                                workspace=self._workspace)
-            pooled = _native.sparse_pool(tok, d_cu, self._decoder, self.cfg.hidden, n_rows=T)
+            tok, d_cu = self._token_rows(ids2d, lens)
+            pooled = _native.sparse_pool(tok, d_cu, self._decoder, self.cfg.hidden, n_rows=int(tok.shape[0]))
             cnt, terms, imps = _native.sparse_select(pooled, self.vocab_bias, self.scale, max_terms, self._skip_bits)
         return cnt.cpu().numpy(), terms.cpu().numpy(), imps.cpu().numpy()
 

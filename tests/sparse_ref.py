@@ -113,8 +113,9 @@ def expand(w: dict, sequences, n_layers: int, n_heads: int, eps: float) -> np.nd
 
 # ---- activation, quantisation, select -----------------------------------------------------------------------------------
 def weights(pooled: np.ndarray, bias: np.ndarray, scale: float) -> np.ndarray:
-    """w * scale, float64: log1p(max(pooled + bias, 0)) * scale"""
-    x = np.maximum(np.asarray(pooled, np.float64) + np.asarray(bias, np.float64), 0.0)
+    """w * scale, float64: log1p(max(pooled + bias, 0)) * scale.  The maximum is fmaxf's: a NaN logit gives
+    fmax(NaN, 0) = 0, weight 0 and impact 0; +inf gives an infinite weight and the clamped impact 255; -inf gives 0"""
+    x = np.fmax(np.asarray(pooled, np.float64) + np.asarray(bias, np.float64), 0.0)
     return np.log1p(x) * float(scale)
 
 
