@@ -247,6 +247,54 @@ int mmrag_cross_encoder_forward_f32(const mmrag_encoder_desc *desc, const void *
                                     const int32_t *cu_seqlens, int64_t T, int B, int max_len, float *out_logits,
                                     void *workspace, size_t workspace_bytes, void *stream);
 
+/* Extractive reader (not in the reference): answer spans from a BertForQuestionAnswering head.  Each (question,
+ * passage) pair is ONE packed sequence [CLS] question [SEP] passage [SEP] of at most MMRAG_MAX_READER_TOKENS tokens.
+ *
+ * mmrag_span_select (csrc/span_head.hip): ONE launch, one workgroup per sequence, over caller-supplied final hidden
+ * states.  Start / end logits ls[t] = <hidden[t], qa_w[0]> + qa_b[0], le[t] = <hidden[t], qa_w[1]> + qa_b[1] (float32
+ * accumulation, kept on chip), then per sequence b:
+ *   out_lse[b][0], [1]  log-sum-exp of the start / of the end logits over position 0 ([CLS]) and the passage tokens
+ *   out_null[b]         ls[0] + le[0], the score of "no answer in this passage"
+ *   out_span[b][r], out_score[b][r], r < n_best: the candidates are all (i, j) with ctx_start <= i <= j <
+ *       ctx_start + ctx_len and j - i < max_answer_tokens, scored ls[i] + le[j] (a float32 sum; a candidate must score
+ *       above -inf).  Round r takes the best candidate that shares no token with a span of an earlier round: higher
+ *       score first, then lower i, then lower j.  Spans are inclusive token offsets from the sequence's first token.
+ *       A round without an eligible candidate gives (-1, -1) and -inf.
+ *   hidden      dev [T, ld] fp16, 16-byte aligned; ld a multiple of 8, >= hidden_dim; hidden_dim a multiple of 64,
+ *               at most 1024
+ *   qa_w, qa_b  dev [2, hidden_dim], [2] float32 (qa_outputs.weight / .bias: row 0 start, row 1 end)
+ *   cu_seqlens  dev [B + 1] int32; ctx_start, ctx_len dev [B] int32: the passage's tokens inside sequence b, counted
+ *               from its first token ([CLS], the question and both [SEP]s excluded: ctx_start >= 1)
+ *   max_answer_tokens  1..MMRAG_MAX_ANSWER_TOKENS;  n_best  1..MMRAG_MAX_READER_SPANS
+ *   out_span    dev [B, n_best, 2] int32;  out_score dev [B, n_best];  out_null dev [B];  out_lse dev [B, 2] float32
+ *   out_logits  dev [T, 2] float32 (start, end) or NULL: the logits are then never written to memory
+ * Bad arguments return MMRAG_EINVAL before anything is launched; the device tables are not read by the host.  A sequence
+ * that is empty, longer than MMRAG_MAX_READER_TOKENS or outside [0, T], or whose ctx_start / ctx_len fall outside it,
+ * reads nothing and gets out_null = out_lse = NaN, spans (-1, -1) and scores -inf.  No atomics and no workspace: the
+ * launch can be captured into a graph, identical calls give identical bits, and a sequence gives the same bits alone
+ * or inside any batch.
+ *
+ * mmrag_reader_forward (csrc/encoder.hip): embedding with segment ids -> the encoder blocks of mmrag_encoder_forward
+ * -> the span launch on the final hidden rows.  fp16 mode, MMRAG_ARCH_BERT only; desc.pool / normalize are IGNORED.
+ *   w           the weight table of mmrag_cross_encoder_forward (w[2] = the two-row token-type table); after the
+ *               layers, at w[5 + 12 L ...]: qa_w [2, H], qa_b [2], float32
+ *   ids, type_ids, pos_ids   dev [T] int32, as for mmrag_cross_encoder_forward
+ *   workspace   >= mmrag_reader_workspace_bytes(desc, T, B)
+ * Bad arguments return MMRAG_EINVAL, a short workspace MMRAG_EWORKSPACE. */
+#define MMRAG_MAX_READER_TOKENS 512
+#define MMRAG_MAX_ANSWER_TOKENS 64
+#define MMRAG_MAX_READER_SPANS 8
+int mmrag_span_select(const void *hidden, int ld, int hidden_dim, const float *qa_w, const float *qa_b,
+                      const int32_t *cu_seqlens, const int32_t *ctx_start, const int32_t *ctx_len, int64_t T, int B,
+                      int max_answer_tokens, int n_best, int32_t *out_span, float *out_score, float *out_null,
+                      float *out_lse, float *out_logits, void *stream);
+size_t mmrag_reader_workspace_bytes(const mmrag_encoder_desc *desc, int64_t T, int B);
+int mmrag_reader_forward(const mmrag_encoder_desc *desc, const void *const *w, const int32_t *ids,
+                         const int32_t *type_ids, const int32_t *pos_ids, const int32_t *cu_seqlens,
+                         const int32_t *ctx_start, const int32_t *ctx_len, int64_t T, int B, int max_len,
+                         int max_answer_tokens, int n_best, int32_t *out_span, float *out_score, float *out_null,
+                         float *out_lse, float *out_logits, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Vision tower (CLIP ViT-B/32 shape; BASELINE config 4 -- no reference behaviour):
  * patchify (+ fused uint8 -> normalised fp16 preprocessing) -> patch-embedding GEMM -> class token +
  * positions -> pre-LN -> the same pre-LN blocks / final LN / projection / L2 normalise as the text tower.

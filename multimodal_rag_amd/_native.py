@@ -44,6 +44,8 @@ MAX_LATE_QUESTIONS = 4096   # mmrag_maxsim_topk (MMRAG_MAX_LATE_QUESTIONS)
 LATE_WINDOW_TOKENS, MAX_LATE_WINDOWS = 16, 32
 # mmrag_summary_select (MMRAG_MAX_SUMMARY_SENTENCES, MMRAG_MAX_SUMMARY_ITERATIONS)
 MAX_SUMMARY_SENTENCES, MAX_SUMMARY_ITERATIONS = 128, 64
+# mmrag_span_select / mmrag_reader_forward (MMRAG_MAX_READER_TOKENS, MMRAG_MAX_ANSWER_TOKENS, MMRAG_MAX_READER_SPANS)
+MAX_READER_TOKENS, MAX_ANSWER_TOKENS, MAX_READER_SPANS = 512, 64, 8
 _DT2TORCH = {F32: torch.float32, F16: torch.float16, BF16: torch.bfloat16, F8E4M3: torch.float8_e4m3fn}
 _TORCH2DT = {v: k for k, v in _DT2TORCH.items()}
 
@@ -189,6 +191,14 @@ def _declare(lib):
                                                 c_int64, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.mmrag_cross_encoder_forward_f32.restype = c_int
     lib.mmrag_cross_encoder_forward_f32.argtypes = lib.mmrag_cross_encoder_forward.argtypes
+    lib.mmrag_span_select.restype = c_int
+    lib.mmrag_span_select.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                      c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.mmrag_reader_workspace_bytes.restype = c_size_t
+    lib.mmrag_reader_workspace_bytes.argtypes = [c_void_p, c_int64, c_int]
+    lib.mmrag_reader_forward.restype = c_int
+    lib.mmrag_reader_forward.argtypes = [c_void_p] * 8 + [c_int64, c_int, c_int, c_int, c_int] + [c_void_p] * 6 + \
+        [c_size_t, c_void_p]
     lib.mmrag_wordpiece_encode_pairs.restype = c_int
     lib.mmrag_wordpiece_encode_pairs.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                                  c_void_p, c_void_p, c_int]
@@ -2243,6 +2253,76 @@ def cross_encoder_forward(desc: EncoderDesc, weight_ptrs, n_labels: int, ids: to
                 _nbytes(workspace), _stream_ptr(ids.device))
     _check(st, "mmrag_cross_encoder_forward")
     return out
+
+
+# ---- extractive reader (include/mmrag.h: mmrag_span_select, mmrag_reader_forward) ----
+def _reader_outs(B: int, T: int, n_best: int, logits: bool, dev):
+    n = max(int(n_best), 1)
+    return (torch.empty((B, n, 2), dtype=torch.int32, device=dev), torch.empty((B, n), dtype=torch.float32, device=dev),
+            torch.empty(B, dtype=torch.float32, device=dev), torch.empty((B, 2), dtype=torch.float32, device=dev),
+            torch.empty((T, 2), dtype=torch.float32, device=dev) if logits else None)
+
+
+def _reader_tables(cu_seqlens, ctx_start, ctx_len):
+    B = cu_seqlens.numel() - 1
+    for t in (cu_seqlens, ctx_start, ctx_len):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+            raise MMRagNativeError("reader: cu_seqlens / ctx_start / ctx_len must be contiguous int32 vectors")
+    if B < 1 or ctx_start.numel() != B or ctx_len.numel() != B:
+        raise MMRagNativeError("reader: ctx_start / ctx_len need one entry per sequence")
+    return B
+
+
+def span_select(hidden: torch.Tensor, qa_w: torch.Tensor, qa_b: torch.Tensor, cu_seqlens: torch.Tensor,
+                ctx_start: torch.Tensor, ctx_len: torch.Tensor, max_answer_tokens: int, n_best: int,
+                logits: bool = False, hidden_dim: Optional[int] = None):
+    """(spans [B, n_best, 2] int32, scores [B, n_best], null [B], lse [B, 2], logits [T, 2] or None) on the device:
+    the reader's span head on final hidden states `hidden` [T, ld] float16 (mmrag_span_select).  `hidden_dim`: the
+    columns that are the hidden state (default: all of them)."""
+    _dev_check(hidden, qa_w, qa_b, cu_seqlens, ctx_start, ctx_len)
+    if hidden.dim() != 2 or hidden.dtype != torch.float16 or not hidden.is_contiguous():
+        raise MMRagNativeError("span_select: hidden must be a contiguous [T, ld] float16 tensor")
+    T, ld = hidden.shape
+    H = ld if hidden_dim is None else int(hidden_dim)
+    if qa_w.dtype != torch.float32 or tuple(qa_w.shape) != (2, H) or not qa_w.is_contiguous() \
+            or qa_b.dtype != torch.float32 or qa_b.numel() != 2 or not qa_b.is_contiguous():
+        raise MMRagNativeError("span_select: qa_w must be [2, hidden] and qa_b [2], contiguous float32")
+    B = _reader_tables(cu_seqlens, ctx_start, ctx_len)
+    span, score, null, lse, lg = _reader_outs(B, T, n_best, logits, hidden.device)
+    with torch.cuda.device(hidden.device):
+        st = lib().mmrag_span_select(hidden.data_ptr(), ld, H, qa_w.data_ptr(), qa_b.data_ptr(), cu_seqlens.data_ptr(),
+                                     ctx_start.data_ptr(), ctx_len.data_ptr(), T, B, int(max_answer_tokens),
+                                     int(n_best), span.data_ptr(), score.data_ptr(), null.data_ptr(), lse.data_ptr(),
+                                     _ptr(lg), _stream_ptr(hidden.device))
+    _check(st, "mmrag_span_select")
+    return span, score, null, lse, lg
+
+
+def reader_workspace_bytes(desc: EncoderDesc, T: int, B: int) -> int:
+    return int(lib().mmrag_reader_workspace_bytes(ctypes.byref(desc), T, B))
+
+
+def reader_forward(desc: EncoderDesc, weight_ptrs, ids: torch.Tensor, type_ids: torch.Tensor, pos_ids: torch.Tensor,
+                   cu_seqlens: torch.Tensor, ctx_start: torch.Tensor, ctx_len: torch.Tensor, max_len: int,
+                   max_answer_tokens: int, n_best: int, logits: bool = False,
+                   workspace: Optional[torch.Tensor] = None):
+    """One reader pass over packed (question, passage) sequences -> span_select's outputs.  `weight_ptrs` in the order
+    include/mmrag.h documents for mmrag_reader_forward (see reader.DeviceReader)."""
+    _dev_check(ids, type_ids, pos_ids, cu_seqlens, ctx_start, ctx_len, workspace)
+    T = ids.numel()
+    B = _reader_tables(cu_seqlens, ctx_start, ctx_len)
+    need = reader_workspace_bytes(desc, T, B)
+    if workspace is None or _nbytes(workspace) < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=ids.device)
+    span, score, null, lse, lg = _reader_outs(B, T, n_best, logits, ids.device)
+    with torch.cuda.device(ids.device):
+        st = lib().mmrag_reader_forward(ctypes.byref(desc), weight_ptrs, ids.data_ptr(), type_ids.data_ptr(),
+                                        pos_ids.data_ptr(), cu_seqlens.data_ptr(), ctx_start.data_ptr(),
+                                        ctx_len.data_ptr(), T, B, int(max_len), int(max_answer_tokens), int(n_best),
+                                        span.data_ptr(), score.data_ptr(), null.data_ptr(), lse.data_ptr(), _ptr(lg),
+                                        workspace.data_ptr(), _nbytes(workspace), _stream_ptr(ids.device))
+    _check(st, "mmrag_reader_forward")
+    return span, score, null, lse, lg
 
 
 def embed_types_ln(ids, type_ids, pos_ids, tok, pos, type_tab, gamma, beta, eps: float) -> torch.Tensor:

@@ -73,6 +73,17 @@ class Settings:
     # reference's placeholder (truncation only).  /query re-ranks max(top_k, MMRAG_RERANK_CANDIDATES) search hits
     MMRAG_RERANKER_DIR: str = field(default_factory=lambda: os.getenv("MMRAG_RERANKER_DIR", ""))
     MMRAG_RERANK_CANDIDATES: int = field(default_factory=lambda: int(os.getenv("MMRAG_RERANK_CANDIDATES", "20")))
+    # extractive reader (EmbeddingManager.read_answers, POST /query with "reader": true; reader.py, csrc/span_head.hip):
+    # a local BertForQuestionAnswering directory (config.json + model.safetensors + vocab.txt, e.g. a SQuAD2-trained
+    # BERT); empty = the feature is off.  MMRAG_READER_MAX_ANSWER_TOKENS: the longest answer span, in tokens (1..64).
+    # MMRAG_READER_NULL_THRESHOLD: the hits answer the question when best span score - lowest null score exceeds it.
+    # MMRAG_READER_DOC_STRIDE: tokens two consecutive windows of a long passage share
+    MMRAG_READER_DIR: str = field(default_factory=lambda: os.getenv("MMRAG_READER_DIR", ""))
+    MMRAG_READER_MAX_ANSWER_TOKENS: int = field(
+        default_factory=lambda: int(os.getenv("MMRAG_READER_MAX_ANSWER_TOKENS", "30")))
+    MMRAG_READER_NULL_THRESHOLD: float = field(
+        default_factory=lambda: float(os.getenv("MMRAG_READER_NULL_THRESHOLD", "0.0")))
+    MMRAG_READER_DOC_STRIDE: int = field(default_factory=lambda: int(os.getenv("MMRAG_READER_DOC_STRIDE", "128")))
     # which re-ranker rerank_results uses when its caller names none: "cross" (the cross-encoder above; without one the
     # placeholder) or "late" (late interaction: token-level MaxSim with the bi-encoder itself, late.py -- needs no
     # second model).  MMRAG_LATE_MAX_DOC_TOKENS: passage tokens "late" scores (0 = the encoder's length; at most 512)

@@ -1730,10 +1730,17 @@ struct TokenTail {
     const void *mlm_w = nullptr;     // [H, H] fp16, or null: the tail above
     const float *mlm_b = nullptr, *mlm_g = nullptr, *mlm_beta = nullptr;
     float mlm_eps = 0.0f;
+    // no tail at all (mmrag_reader_forward): *raw_hidden = the buffer [T, H] that holds the final hidden states; the
+    // caller launches its own head on it.  Nothing else of this struct is read
+    const void **raw_hidden = nullptr;
 };
 
 // `hidden` [T, H]: the final hidden states -> (projection) -> L2-normalised fp16 rows
 static int token_tail(const TokenTail &tk, const void *hidden, int64_t T, int H, void *stream) {
+    if (tk.raw_hidden != nullptr) {
+        *tk.raw_hidden = hidden;
+        return MMRAG_OK;
+    }
     if (tk.mlm_w != nullptr) {
         const int st = mmrag_linear_f16(hidden, T, H, tk.mlm_w, H, tk.mlm_b, MMRAG_ACT_GELU, nullptr, tk.projected,
                                         stream);
@@ -2119,6 +2126,58 @@ int mmrag_cross_encoder_forward(const mmrag_encoder_desc *d, const void *const *
     const void *const *hw = w + 5 + 12 * dc.n_layers;
     return launch_cls_head_f32(cls, (const float *)hw[0], (const float *)hw[1], (const float *)hw[2],
                                (const float *)hw[3], out_logits, B, H, n_labels, head_ws, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// extractive reader (BertForQuestionAnswering): embed with segment ids, the unchanged encoder body ending in its raw
+// final hidden rows (TokenTail::raw_hidden; the folded-LayerNorm path leaves them in y, the general path in x), then the
+// span head's one launch on them (span_head.hip)
+// ---------------------------------------------------------------------------------------------
+size_t mmrag_reader_workspace_bytes(const mmrag_encoder_desc *d, int64_t T, int B) {
+    if (!d || T <= 0 || B <= 0 || d->hidden <= 0) return 0;
+    mmrag_encoder_desc dc = *d;
+    dc.out_dim = d->hidden;
+    return mmrag_encoder_workspace_bytes(&dc, T, B);
+}
+
+int mmrag_reader_forward(const mmrag_encoder_desc *d, const void *const *w, const int32_t *ids, const int32_t *type_ids,
+                         const int32_t *pos_ids, const int32_t *cu_seqlens, const int32_t *ctx_start,
+                         const int32_t *ctx_len, int64_t T, int B, int max_len, int max_answer_tokens, int n_best,
+                         int32_t *out_span, float *out_score, float *out_null, float *out_lse, float *out_logits,
+                         void *workspace, size_t workspace_bytes, void *stream) {
+    MMRAG_CHECK_ARG(d && w && ids && type_ids && pos_ids && cu_seqlens && ctx_start && ctx_len && out_span && out_score &&
+                        out_null && out_lse, "reader_forward: null pointer");
+    MMRAG_CHECK_ARG(T > 0 && T < INT_MAX && B > 0 && max_len > 0, "reader_forward: bad shape T=%lld B=%d", (long long)T, B);
+    MMRAG_CHECK_ARG(d->arch == MMRAG_ARCH_BERT, "reader_forward: BERT family only (arch %d)", d->arch);
+    MMRAG_CHECK_ARG(max_answer_tokens >= 1 && max_answer_tokens <= MMRAG_MAX_ANSWER_TOKENS,
+                    "reader_forward: max_answer_tokens = %d (1..%d)", max_answer_tokens, MMRAG_MAX_ANSWER_TOKENS);
+    MMRAG_CHECK_ARG(n_best >= 1 && n_best <= MMRAG_MAX_READER_SPANS, "reader_forward: n_best = %d (1..%d)", n_best,
+                    MMRAG_MAX_READER_SPANS);
+    MMRAG_CHECK_ARG(d->n_layers > 0 && d->vocab > 0 && d->max_pos > 0 && d->n_heads > 0 && d->hidden % d->n_heads == 0,
+                    "reader_forward: bad encoder shape");
+    MMRAG_CHECK_ARG(d->hidden / d->n_heads == 32 || d->hidden / d->n_heads == 64,
+                    "reader_forward: head dimension %d (32 and 64 are built)", d->hidden / d->n_heads);
+    MMRAG_CHECK_ARG(w[5 + 12 * d->n_layers] && w[6 + 12 * d->n_layers], "reader_forward: null qa_outputs weight");
+    mmrag_encoder_desc dc = *d;   // pool / normalize of the caller's desc are ignored
+    dc.pool = MMRAG_POOL_FIRST, dc.normalize = 0, dc.out_dim = d->hidden;
+    int st;
+    RUN(check_desc(&dc));
+    EncBuffers b;
+    RUN(carve(&dc, T, B, workspace, workspace_bytes, &b));
+    const int H = dc.hidden;
+    embed_types_ln_kernel<<<(unsigned)((T + 3) / 4), 256, 0, (hipStream_t)stream>>>(
+        ids, type_ids, pos_ids, (const _Float16 *)w[0], (const _Float16 *)w[1], (const _Float16 *)w[2],
+        (const float *)w[3], (const float *)w[4], (_Float16 *)b.x, (int)T, H, dc.vocab, dc.max_pos,
+        MMRAG_CROSS_TYPE_VOCAB, dc.ln_eps, nullptr, 0);
+    MMRAG_CHECK_HIP(hipGetLastError());
+    const void *hidden = nullptr;
+    TokenTail tk{};
+    tk.raw_hidden = &hidden;
+    RUN(encoder_body(&dc, w + 5, b, cu_seqlens, nullptr, T, B, max_len, nullptr, stream, &tk));
+    const void *const *hw = w + 5 + 12 * dc.n_layers;
+    return launch_span_select(hidden, H, H, (const float *)hw[0], (const float *)hw[1], cu_seqlens, ctx_start, ctx_len,
+                              T, B, max_answer_tokens, n_best, out_span, out_score, out_null, out_lse, out_logits,
+                              (hipStream_t)stream);
 }
 #undef RUN
 

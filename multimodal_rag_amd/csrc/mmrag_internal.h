@@ -95,3 +95,12 @@ int *cls_head_counter_ptr(void *ws, int B, int H, int NL);
 int launch_cls_head_f32(const float *cls, const float *wp, const float *bp, const float *wc, const float *bc, float *out,
                         int B, int H, int NL, void *ws, hipStream_t s);
 }  // namespace mmrag_impl
+
+// the extractive reader's span head (span_head.hip): mmrag_span_select's checks and launch, also the tail of
+// mmrag_reader_forward (encoder.hip)
+namespace mmrag_impl {
+int launch_span_select(const void *hidden, int ld, int H, const float *qa_w, const float *qa_b, const int32_t *cu_seqlens,
+                       const int32_t *ctx_start, const int32_t *ctx_len, int64_t T, int B, int max_answer_tokens,
+                       int n_best, int32_t *out_span, float *out_score, float *out_null, float *out_lse,
+                       float *out_logits, hipStream_t s);
+}  // namespace mmrag_impl

@@ -116,6 +116,7 @@ class EmbeddingManager:
         self._sleep = asyncio.sleep              # (tests swap the back-off sleep out)
         self._reranker = None                    # cross-encoder (MMRAG_RERANKER_DIR), loaded on first use
         self._reranker_lock = threading.Lock()
+        self._reader = None                      # extractive reader (MMRAG_READER_DIR), loaded on first use
         self._late = None                        # late.LateInteractionScorer over the engine's own encoder, on first use
         self._sparse = None                      # sparse.DeviceSparseEncoder (MMRAG_SPARSE_ENCODER_DIR), on first use
         self._sparse_lock = threading.Lock()
@@ -1280,6 +1281,83 @@ class EmbeddingManager:
                 device = getattr(self._engine, "device", None) or "cuda:0"
                 self._reranker = DeviceCrossEncoder.from_local_dir(settings.MMRAG_RERANKER_DIR, device)
             return self._reranker
+
+    # ---- extractive reader: answer spans from a BertForQuestionAnswering (reader.py, csrc/span_head.hip) ----
+    def has_reader(self) -> bool:
+        """True when read_answers can run (a reader is configured: MMRAG_READER_DIR, or one was set)"""
+        return self._reader is not None or bool(settings.MMRAG_READER_DIR)
+
+    def _get_reader(self):
+        """the reader of MMRAG_READER_DIR, loaded once on the embedder's device"""
+        with self._reranker_lock:
+            if self._reader is None:
+                if not settings.MMRAG_READER_DIR:
+                    raise ValueError("The extractive reader is not configured: set MMRAG_READER_DIR to a local "
+                                     "BertForQuestionAnswering directory")
+                from .reader import DeviceReader
+
+                device = getattr(self._engine, "device", None) or "cuda:0"
+                self._reader = DeviceReader.from_local_dir(settings.MMRAG_READER_DIR, device)
+            return self._reader
+
+    async def batch_read_answers(self, queries: List[str], results_list: List[Dict[str, Any]], n_answers: int = 3,
+                                 texts_list: Optional[Sequence[Optional[Sequence[str]]]] = None,
+                                 owners_list: Optional[Sequence[Optional[Sequence[int]]]] = None,
+                                 max_answer_tokens: Optional[int] = None, doc_stride: Optional[int] = None,
+                                 null_threshold: Optional[float] = None) -> List[Dict[str, Any]]:
+        """read_answers of results_list[i] against queries[i], ONE reader call (one forward per token budget) for all
+        questions' hits"""
+        if len(queries) != len(results_list):
+            raise ValueError(f"{len(results_list)} result dicts for {len(queries)} queries")
+        from .reader import best_answers
+
+        reader = self._reader if self._reader is not None else await asyncio.to_thread(self._get_reader)
+        max_answer_tokens = settings.MMRAG_READER_MAX_ANSWER_TOKENS if max_answer_tokens is None else max_answer_tokens
+        doc_stride = settings.MMRAG_READER_DOC_STRIDE if doc_stride is None else doc_stride
+        null_threshold = settings.MMRAG_READER_NULL_THRESHOLD if null_threshold is None else null_threshold
+        n_best = max(1, min(int(n_answers), 8))
+        questions, passages, owners = [], [], []
+        for at, (query, results) in enumerate(zip(queries, results_list)):
+            texts = texts_list[at] if texts_list is not None and texts_list[at] is not None else None
+            if texts is None:      # the hits' own stored texts, one per hit
+                texts = [d if d is not None else "" for d in results["documents"]]
+                owner = list(range(len(texts)))
+            else:
+                owner = list(owners_list[at]) if owners_list is not None and owners_list[at] is not None \
+                    else list(range(len(texts)))
+                if len(owner) != len(texts):
+                    raise ValueError(f"{len(owner)} owners for {len(texts)} texts")
+            questions += [query] * len(texts)
+            passages += list(texts)
+            owners.append(owner)
+        found = await asyncio.to_thread(reader.read, questions, passages, n_best, max_answer_tokens,
+                                        doc_stride) if passages else []
+        out, at = [], 0
+        for results, owner in zip(results_list, owners):
+            mine = found[at: at + len(owner)]
+            at += len(owner)
+            spans: List[List[Dict[str, Any]]] = [[] for _ in results["ids"]]
+            for at_text, (hit, f) in enumerate(zip(owner, mine)):
+                spans[hit].extend({**s, "passage": at_text} for s in f["spans"])
+            out.append({**results, **best_answers(mine, owner, n_answers, float(null_threshold)),
+                        "answer_spans": spans})
+        return out
+
+    async def read_answers(self, query_text: str, results: Dict[str, Any], n_answers: int = 3,
+                           texts: Optional[Sequence[str]] = None, owner: Optional[Sequence[int]] = None,
+                           max_answer_tokens: Optional[int] = None, doc_stride: Optional[int] = None,
+                           null_threshold: Optional[float] = None) -> Dict[str, Any]:
+        """Answer spans of `query_text` in the hits of `results` (any retrieval mode's answer).  Returns `results` plus
+        `answers`: the best `n_answers` spans over all hits, {"text", "score", "probability", "hit" (index into the
+        hits), "passage" (index into the texts read), "start", "end"}, character-identical texts from different hits
+        merged (the best stays); `answerable`:
+        best span score - the lowest null score over the hits > `null_threshold` (default
+        MMRAG_READER_NULL_THRESHOLD); `null_score`; and `answer_spans`, per hit its own spans.  The texts read are the
+        hits' `documents`, or `texts` (e.g. the retriever's raw passages) with `owner[i]` the hit texts[i] belongs to;
+        start / end are characters of that text.  One reader.DeviceReader.read call."""
+        return (await self.batch_read_answers([query_text], [results], n_answers,
+                                              None if texts is None else [texts], None if owner is None else [owner],
+                                              max_answer_tokens, doc_stride, null_threshold))[0]
 
     # ---- late interaction: re-ranking with the bi-encoder alone (late.py, csrc/maxsim.hip) ----
     def has_late_reranker(self) -> bool:

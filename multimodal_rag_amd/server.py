@@ -142,6 +142,14 @@ class QueryRequest(BaseModel):  # api.py:161-164
     # source that was quoted carries `quotes`: [{start, end, text, score}] in the passage's characters.  Works with every
     # mode: it reads the final hits
     extractive_answer: bool = Field(False)
+    # not in the reference: the extractive reader (EmbeddingManager.read_answers; needs MMRAG_READER_DIR, a local
+    # BertForQuestionAnswering).  The response gains `answers` -- the best answer SPANS over the hits' raw text passages,
+    # {text, score, probability, hit, passage, start, end} -- and `answerable` (best span score - lowest null score >
+    # MMRAG_READER_NULL_THRESHOLD); every source carries its own `answer_spans`.  The generator call is unchanged.
+    # `reader_answer` implies `reader`: `answer` is then the best span's text, or the "nothing found" wording when the
+    # hits do not answer the question, and the generator is not called.  Works with the modes `passages` works with
+    reader: bool = Field(False)
+    reader_answer: bool = Field(False)
 
 
 FILTER_MAX_LEAVES, FILTER_MAX_DEPTH = 32, 8
@@ -273,6 +281,14 @@ EXTRACT_NEEDS = ("extract_answer", "supports_summaries",
 QUOTE_KEYS = ("start", "end", "text", "score")
 
 
+# `reader` / `reader_answer`: the answers a response lists, the keys of an answer and of a source's span, and the
+# answer when the hits hold none
+READER_ANSWERS = 3
+ANSWER_KEYS = ("text", "score", "probability", "hit", "passage", "start", "end")
+SPAN_KEYS = ("text", "passage", "start", "end", "score", "probability")
+NO_ANSWER_FOUND = NO_DOCS_ANSWER
+
+
 # first-stage late retrieval (`late`): the same
 LATE_QUERY_NEEDS = ("late_query", "supports_late_query",
                     "Late retrieval is not available with this embedder: it needs a single BERT-family HIP engine in "
@@ -313,6 +329,9 @@ class QueryResponse(BaseModel):  # api.py:167-170
     answer: str
     sources: List[dict]
     processing_time: float
+    # `reader` only (the route leaves unset fields out of the response)
+    answers: Optional[List[dict]] = None
+    answerable: Optional[bool] = None
 
 
 class UploadResponse(BaseModel):  # api.py:173-179
@@ -483,7 +502,8 @@ class Pipeline:
                      recommend: Optional[Dict[str, Any]] = None,
                      filter_dict: Optional[Dict[str, Any]] = None, late: bool = False,
                      passage_tokens: Optional[int] = None, sparse: bool = False,
-                     hybrid_leg: Optional[str] = None, extractive: bool = False) -> Optional[dict]:
+                     hybrid_leg: Optional[str] = None, extractive: bool = False,
+                     reader: Optional[str] = None) -> Optional[dict]:
         """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
         max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the re-ranker's best top_k (`rerank_method` "cross" or "late",
         default MMRAG_RERANK_METHOD; `explain`: late interaction's per-token matches on every source).  `hybrid`: from
@@ -506,7 +526,10 @@ class Pipeline:
         (EmbeddingManager.sparse_query; `explain`: every source carries its `matched_terms`).  `hybrid_leg` "sparse"
         (with `hybrid`): the dense hits are fused with the learned sparse leg instead of BM25.  `extractive` (with any
         mode): the answer is EmbeddingManager.extract_answer's over the hits' raw text passages, no generator call, and
-        every quoted source carries its `quotes`"""
+        every quoted source carries its `quotes`.  `reader` ("spans" or "answer"; with any mode `passages` works with):
+        EmbeddingManager.read_answers over the hits' raw text passages -- the result gains `answers` and `answerable`,
+        every source its `answer_spans`; "answer": the answer is the best span's text (NO_ANSWER_FOUND when the hits do
+        not answer the question), no generator call"""
         multi = variants is not None
         sparse_leg = hybrid and hybrid_leg == "sparse"
         riding = passage_tokens is not None and rerank and rerank_method == "late"
@@ -564,16 +587,21 @@ class Pipeline:
             return None
         if passage_tokens is not None and "passages" not in hits:
             hits = await self.embedder.extract_passages(question, hits, window_tokens=passage_tokens)
-        quoted = None
-        if extractive:
+        quoted = read = None
+        if extractive or reader is not None:
             # hit by hit: which source a raw text passage belongs to (the buckets of one call do not say)
             texts, owner = [], []
             for at, found in enumerate(hits["ids"]):
                 for passage in (await self.retriever.retrieve_raw_documents([found]))[self.CONTEXT_KINDS[0]]:
                     texts.append(passage)
                     owner.append(at)
+        if reader is not None:
+            read = await self.embedder.read_answers(question, hits, n_answers=READER_ANSWERS, texts=texts, owner=owner)
+        if extractive:
             quoted = await self.embedder.extract_answer(question, texts)
             text = quoted["answer"]
+        elif reader == "answer":
+            text = read["answers"][0]["text"] if read["answerable"] else NO_ANSWER_FOUND
         else:
             text = await self._generate(question, hits["ids"], multimodal)
         ranked = self._sources(hits)
@@ -597,6 +625,9 @@ class Pipeline:
         if quoted is not None:
             for quote in quoted["quotes"]:
                 ranked[owner[quote["passage"]]].setdefault("quotes", []).append({key: quote[key] for key in QUOTE_KEYS})
+        if read is not None:
+            for src, found in zip(ranked, read["answer_spans"]):
+                src["answer_spans"] = [{key: span[key] for key in SPAN_KEYS} for span in found]
         if group_by_document:
             at = 0
             for document_rank, group in enumerate(hits["groups"], 1):
@@ -604,6 +635,9 @@ class Pipeline:
                     src["document"] = group["key"]
                     src["document_rank"] = document_rank
                 at += len(group["ids"])
+        if read is not None:
+            return {"answer": text, "sources": ranked, "answerable": read["answerable"],
+                    "answers": [{key: answer[key] for key in ANSWER_KEYS} for answer in read["answers"]]}
         return {"answer": text, "sources": ranked}
 
     async def recommend(self, like: List[str], unlike: List[str], unlike_texts: List[str], top_k: int,
@@ -718,7 +752,7 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
         note = f", {skipped} duplicates skipped" if skipped > 0 else ""
         return {**out, "message": f"Processed in {took:.2f}s{note}", "processing_time": took}
 
-    @app.post("/query", response_model=QueryResponse)
+    @app.post("/query", response_model=QueryResponse, response_model_exclude_unset=True)
     @_as_http_500
     async def query_documents(request: QueryRequest):  # api.py:325-413
         t0 = time.time()
@@ -738,7 +772,8 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
         if request.sparse:
             if (multi or request.mmr or request.hybrid or request.group_by_document or request.rerank or request.late
                     or (request.boost is not None and request.boost is not False) or request.like is not None
-                    or request.unlike is not None or request.not_ is not None or request.passages):
+                    or request.unlike is not None or request.not_ is not None or request.passages or request.reader
+                    or request.reader_answer):
                 raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                     detail="Learned sparse retrieval is not combined with the other retrieval modes, "
                                            "re-ranking or answer passages yet: send `sparse` alone, with `filter`, "
@@ -776,6 +811,15 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
                 raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
         if request.extractive_answer:
             pipe._need(EXTRACT_NEEDS)
+        if request.reader or request.reader_answer:
+            if not (hasattr(pipe.embedder, "read_answers") and getattr(pipe.embedder, "has_reader", lambda: False)()):
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                    detail="The extractive reader is not configured: set MMRAG_READER_DIR to a local "
+                                           "BertForQuestionAnswering directory")
+            if request.reader_answer and request.extractive_answer:
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                    detail="`reader_answer` and `extractive_answer` both replace the generator's "
+                                           "answer: send one of them")
         if request.filter is not None:
             try:
                 _, timed = check_filter(request.filter)
@@ -866,7 +910,9 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
                                     **({} if not request.sparse else {"sparse": True}),
                                     **({} if request.hybrid_leg is None else {"hybrid_leg": request.hybrid_leg}),
                                     **({} if window is None else {"passage_tokens": window}),
-                                    **({} if not request.extractive_answer else {"extractive": True}))
+                                    **({} if not request.extractive_answer else {"extractive": True}),
+                                    **({} if not (request.reader or request.reader_answer) else
+                                       {"reader": "answer" if request.reader_answer else "spans"}))
         except ValueError as e:
             if recommend is None:
                 raise
