@@ -137,6 +137,9 @@ int mmrag_merge_topk_host_packed(const void *blocks, int G, int B, int k_in, int
  * (app/utils/embedder.py:514-523): cast + copy `m` new float32 rows into the shard matrix
  * at row n_used (the id/metadata/document table stays on the host).
  *   corpus  dev [capacity, ld] dtype   new_rows dev [m, d] float32 (tightly packed)
+ * The cast rounds to nearest even, pad columns [d, ld) of the written rows are set to zero and
+ * nothing else is written.  m = 0 is a no-op with any pointers, null included (an empty device
+ * tensor has none); every other bad argument returns MMRAG_EINVAL and launches nothing.
  * ------------------------------------------------------------------------------------- */
 int mmrag_append_rows(void *corpus, int64_t capacity, int64_t ld, int dtype, int64_t n_used,
                       const float *new_rows, int64_t m, int d, void *stream);

@@ -146,7 +146,8 @@ int64_t mmrag_padded_dim(int d, int dtype) {
 
 int mmrag_append_rows(void *corpus, int64_t capacity, int64_t ld, int dtype, int64_t n_used,
                       const float *new_rows, int64_t m, int d, void *stream) {
-    MMRAG_CHECK_ARG(corpus && new_rows, "append_rows: null pointer");
+    // m == 0 is a no-op whatever the pointers are: an empty device tensor has none
+    MMRAG_CHECK_ARG((corpus && new_rows) || m == 0, "append_rows: null pointer");
     MMRAG_CHECK_ARG(dtype >= 0 && dtype <= MMRAG_F8E4M3, "append_rows: bad dtype %d", dtype);
     MMRAG_CHECK_ARG(d > 0 && ld >= d, "append_rows: need 0 < d <= ld (d=%d ld=%lld)", d, (long long)ld);
     MMRAG_CHECK_ARG(m >= 0 && n_used >= 0 && n_used + m <= capacity,
