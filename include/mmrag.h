@@ -356,6 +356,41 @@ int64_t mmrag_lexicon_size(const void *lexicon);
 int mmrag_lexicon_analyze_batch(void *lexicon, const uint32_t *cps, const int64_t *offsets, int n, int mode,
                                 int64_t *out_offsets, int32_t *term_ids, int32_t *tfs, int32_t *dl, int64_t capacity,
                                 int n_threads);
+/*   export         the code points of terms first_id .. first_id + count (ids are first-seen order, and so is the
+ *                  lexicon's pool): term first_id + i = cps[offsets[i] .. offsets[i+1]), offsets [count+1] from 0.
+ *                  More than `capacity` code points: MMRAG_EWORKSPACE with offsets filled in (offsets[count] is the
+ *                  capacity to call again with).
+ *   analyze_terms  the query mode that drops nothing: every DISTINCT term of text i in order of first occurrence,
+ *                  term_ids[out_offsets[i] .. out_offsets[i+1]) (-1: not in the lexicon); term j of the whole batch is
+ *                  out_cps[cp_offsets[j] .. cp_offsets[j+1]).  needed[0] / needed[1] are always set to the number of
+ *                  terms / code points; more than term_capacity / cp_capacity: MMRAG_EWORKSPACE with out_offsets
+ *                  filled in.  Adds nothing to the lexicon. */
+int mmrag_lexicon_export(const void *lexicon, int32_t first_id, int32_t count, int64_t *offsets, uint32_t *cps,
+                         int64_t capacity);
+int mmrag_lexicon_analyze_terms(const void *lexicon, const uint32_t *cps, const int64_t *offsets, int n,
+                                int64_t *out_offsets, int32_t *term_ids, int64_t *cp_offsets, uint32_t *out_cps,
+                                int64_t term_capacity, int64_t cp_capacity, int64_t *needed, int n_threads);
+
+/* Typo-tolerant term matching (all pointers dev): for each of n_patterns query terms, the max_expansions best lexicon
+ * terms within its edit budget.  Term t = term_cps[term_off[t] .. term_off[t+1]), pattern p likewise.
+ *   distance    optimal string alignment over code points: insert, delete, substitute and the transposition of two
+ *               adjacent code points cost 1, no substring edited twice (osa("ca", "abc") = 3)
+ *   candidates  terms with df[t] >= 1 and 1..MMRAG_FUZZY_MAX_LEN code points, at distance <= pat_edits[p] (0..2);
+ *               a pattern longer than MMRAG_FUZZY_MAX_LEN has none
+ *   order       smaller distance, then larger df, then lower term id: the 64-bit key
+ *               (2 - dist) << 62 | df << 31 | (2^31 - 1 - id), selected by integer maxima (order-independent)
+ *   out_terms, out_edits  [n_patterns, max_expansions] int32, best first, -1 padded
+ *   workspace   mmrag_fuzzy_terms_workspace_bytes(...) bytes, 16-byte aligned; short or misaligned: MMRAG_EWORKSPACE
+ * MMRAG_EINVAL before anything is launched: a null pointer, n_terms or n_patterns negative, max_expansions outside
+ * 1..MMRAG_FUZZY_MAX_EXPANSIONS.  The edit budgets are device data: one outside 0..2 gives its pattern no candidates.
+ * No host synchronisation. */
+#define MMRAG_FUZZY_MAX_LEN 64
+#define MMRAG_FUZZY_MAX_EXPANSIONS 16
+size_t mmrag_fuzzy_terms_workspace_bytes(int n_terms, int n_patterns, int max_expansions);
+int mmrag_fuzzy_terms(const int32_t *term_off, const uint32_t *term_cps, const int32_t *df, int n_terms,
+                      const int32_t *pat_off, const uint32_t *pat_cps, const int32_t *pat_edits, int n_patterns,
+                      int max_expansions, int32_t *out_terms, int32_t *out_edits, void *workspace,
+                      size_t workspace_bytes, void *stream);
 
 /* Device index (all pointers dev).  Forward log: row r's postings are (fwd_term, fwd_tf)[fwd_off[r] .. fwd_off[r+1]),
  * sorted by term id (as MMRAG_LEX_DOCUMENTS produces them).  df [n_terms] counts the LIVE rows holding each term.

@@ -106,6 +106,10 @@ class Settings:
     # length normalisation b of the score, the same for every query
     MMRAG_BM25_K1: float = field(default_factory=lambda: float(os.getenv("MMRAG_BM25_K1", "1.2")))
     MMRAG_BM25_B: float = field(default_factory=lambda: float(os.getenv("MMRAG_BM25_B", "0.75")))
+    # typo tolerance of the lexical leg (csrc/fuzzy.hip): "" (off), "auto" (0 / 1 / 2 edits for terms of 1-2 / 3-5 / 6+
+    # code points) or "0", "1", "2".  A query term no live row holds is replaced by its closest indexed term; what a
+    # request says about `fuzzy` overrides it
+    MMRAG_LEXICAL_FUZZY: str = field(default_factory=lambda: os.getenv("MMRAG_LEXICAL_FUZZY", ""))
     # hybrid retrieval: each leg returns max(n_results, MMRAG_HYBRID_CANDIDATES) hits (at most 4096), fused by
     # reciprocal rank with sum 1 / (MMRAG_HYBRID_RRF_K + rank)
     MMRAG_HYBRID_CANDIDATES: int = field(default_factory=lambda: int(os.getenv("MMRAG_HYBRID_CANDIDATES", "50")))
@@ -201,6 +205,14 @@ class Settings:
         self.late_store_dtype()
         self.passage_tokens()
         self.summarizer()
+        self.lexical_fuzzy()
+
+    def lexical_fuzzy(self) -> str:
+        """MMRAG_LEXICAL_FUZZY checked: '', 'auto', '0', '1' or '2'"""
+        if self.MMRAG_LEXICAL_FUZZY not in ("", "auto", "0", "1", "2"):
+            raise ValueError(f"MMRAG_LEXICAL_FUZZY must be '' (off), 'auto', '0', '1' or '2' "
+                             f"(got {self.MMRAG_LEXICAL_FUZZY!r})")
+        return self.MMRAG_LEXICAL_FUZZY
 
     def summarizer(self) -> str:
         """MMRAG_SUMMARIZER checked: 'fallback' or 'extractive' (tests set the attribute after start-up, so users call

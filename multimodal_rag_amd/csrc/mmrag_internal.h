@@ -77,6 +77,12 @@ extern "C" {
 int mmrag_internal_lexical_limits(int *score_rows, int *score_terms, int *sort_lds, int *sort_grid, int *scan_terms);
 }
 
+// test-only export of the fuzzy term matcher's sizes (fuzzy.hip): terms per workgroup, patterns per LDS tile, the
+// longest matched term, the most expansions and the code points of a term tile kept in LDS.  Host code, no device needed.
+extern "C" {
+int mmrag_internal_fuzzy_limits(int *term_tile, int *pattern_tile, int *max_len, int *max_expansions, int *stage_cps);
+}
+
 // test-only export of the learned sparse leg's path sizes (sparse_expand.hip): rows per impact scoring workgroup
 // (sparse_score.hip), chunk pieces the pool folds per pair of barriers, the longest run of vocabulary tiles a pool
 // workgroup takes, threads (terms per step) of a select workgroup and the pair tile's rows.  Host code, no device needed.

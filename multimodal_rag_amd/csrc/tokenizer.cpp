@@ -384,6 +384,7 @@ struct Lexicon {
         int32_t id;
     };
     u32s pool;
+    std::vector<uint64_t> starts;   // term id's code points are pool[starts[id] .. starts[id + 1]) (the pool's end for the last)
     std::vector<Slot> slots;
     size_t mask;
     int32_t n = 0;
@@ -414,6 +415,7 @@ struct Lexicon {
         size_t i = h & mask;
         while (slots[i].hash) i = (i + 1) & mask;
         slots[i] = Slot{h, (uint64_t)pool.size(), (uint32_t)len, n};
+        starts.push_back((uint64_t)pool.size());
         pool.insert(pool.end(), p, p + len);
         return n++;
     }
@@ -629,6 +631,100 @@ int mmrag_lexicon_analyze_batch(void *lexicon, const uint32_t *cps, const int64_
             for (const auto &p : pairs[i]) {
                 term_ids[at] = p.first;
                 tfs[at++] = p.second;
+            }
+        }
+    });
+    return MMRAG_OK;
+}
+
+// Terms first_id .. first_id + count as code points: the pool is in id order, so the answer is one slice of it.
+int mmrag_lexicon_export(const void *lexicon, int32_t first_id, int32_t count, int64_t *offsets, uint32_t *cps,
+                         int64_t capacity) {
+    MMRAG_CHECK_ARG(lexicon && offsets, "lexicon_export: null pointer");
+    const Lexicon &lx = *(const Lexicon *)lexicon;
+    MMRAG_CHECK_ARG(first_id >= 0 && count >= 0 && (int64_t)first_id + count <= lx.n,
+                    "lexicon_export: terms %d .. %lld outside the lexicon's %d", first_id, (long long)first_id + count, lx.n);
+    MMRAG_CHECK_ARG(capacity >= 0, "lexicon_export: capacity=%lld", (long long)capacity);
+    auto start_of = [&](int64_t id) { return id < lx.n ? lx.starts[(size_t)id] : (uint64_t)lx.pool.size(); };
+    const uint64_t base = start_of(first_id);
+    for (int32_t i = 0; i <= count; ++i) offsets[i] = (int64_t)(start_of((int64_t)first_id + i) - base);
+    if (offsets[count] > capacity) {
+        set_error("lexicon_export: %lld code points > capacity %lld", (long long)offsets[count], (long long)capacity);
+        return MMRAG_EWORKSPACE;
+    }
+    MMRAG_CHECK_ARG(offsets[count] == 0 || cps, "lexicon_export: null output");
+    if (offsets[count]) memcpy(cps, &lx.pool[base], (size_t)offsets[count] * 4);
+    return MMRAG_OK;
+}
+
+// The query mode that keeps unknown terms: every distinct term of each text in order of first occurrence, with its id
+// (-1: not in the lexicon) and its code points.  Threads as mmrag_lexicon_analyze_batch; nothing is inserted.
+int mmrag_lexicon_analyze_terms(const void *lexicon, const uint32_t *cps, const int64_t *offsets, int n,
+                                int64_t *out_offsets, int32_t *term_ids, int64_t *cp_offsets, uint32_t *out_cps,
+                                int64_t term_capacity, int64_t cp_capacity, int64_t *needed, int n_threads) {
+    MMRAG_CHECK_ARG(lexicon && offsets && out_offsets && needed, "lexicon_analyze_terms: null pointer");
+    MMRAG_CHECK_ARG(n >= 0, "lexicon_analyze_terms: n=%d", n);
+    MMRAG_CHECK_ARG(n == 0 || cps || offsets[n] == offsets[0], "lexicon_analyze_terms: null text");
+    MMRAG_CHECK_ARG(term_capacity >= 0 && cp_capacity >= 0 && cp_offsets &&
+                        (term_capacity == 0 || term_ids) && (cp_capacity == 0 || out_cps),
+                    "lexicon_analyze_terms: null output");
+    const Lexicon &lx = *(const Lexicon *)lexicon;
+    if (n_threads < 1) n_threads = 1;
+    if (n > 0) {
+        const int64_t by_work = 1 + (offsets[n] - offsets[0]) / 16384;
+        if (n_threads > by_work) n_threads = (int)by_work;
+    }
+    // per text: the distinct terms as (begin, end) in its own pool, and their ids
+    struct Distinct {
+        Analyzed a;
+        std::vector<std::pair<uint32_t, uint32_t>> spans;
+        std::vector<int32_t> ids;
+        int64_t n_cps = 0;
+    };
+    std::vector<Distinct> docs((size_t)n);
+    parallel_slices(n, n_threads, [&](int lo, int hi) {
+        for (int i = lo; i < hi; ++i) {
+            Distinct &d = docs[i];
+            analyze_text(cps + offsets[i], (size_t)(offsets[i + 1] - offsets[i]), d.a);
+            for (size_t t = 0, b = 0; t < d.a.ends.size(); b = d.a.ends[t++]) {
+                const uint32_t e = d.a.ends[t];
+                bool seen = false;
+                for (const auto &s : d.spans)
+                    if (s.second - s.first == e - b && !memcmp(&d.a.pool[s.first], &d.a.pool[b], (size_t)(e - b) * 4)) {
+                        seen = true;
+                        break;
+                    }
+                if (seen) continue;
+                d.spans.emplace_back((uint32_t)b, e);
+                d.ids.push_back(lx.find(&d.a.pool[b], e - b));
+                d.n_cps += e - b;
+            }
+        }
+    });
+    out_offsets[0] = 0;
+    std::vector<int64_t> cp_at((size_t)n + 1, 0);
+    for (int i = 0; i < n; ++i) {
+        out_offsets[i + 1] = out_offsets[i] + (int64_t)docs[i].ids.size();
+        cp_at[i + 1] = cp_at[i] + docs[i].n_cps;
+    }
+    needed[0] = out_offsets[n];
+    needed[1] = cp_at[n];
+    if (needed[0] > term_capacity || needed[1] > cp_capacity) {
+        set_error("lexicon_analyze_terms: %lld terms, %lld code points > capacity %lld, %lld", (long long)needed[0],
+                  (long long)needed[1], (long long)term_capacity, (long long)cp_capacity);
+        return MMRAG_EWORKSPACE;
+    }
+    cp_offsets[0] = 0;
+    parallel_slices(n, n_threads, [&](int lo, int hi) {
+        for (int i = lo; i < hi; ++i) {
+            const Distinct &d = docs[i];
+            int64_t at = out_offsets[i], cp = cp_at[i];
+            for (size_t t = 0; t < d.ids.size(); ++t, ++at) {
+                const uint32_t len = d.spans[t].second - d.spans[t].first;
+                term_ids[at] = d.ids[t];
+                if (len) memcpy(out_cps + cp, &d.a.pool[d.spans[t].first], (size_t)len * 4);
+                cp += len;
+                cp_offsets[at + 1] = cp;
             }
         }
     });

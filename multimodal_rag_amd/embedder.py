@@ -779,20 +779,37 @@ class EmbeddingManager:
         c = self.collection
         return not (getattr(c, "is_f8", False) and getattr(c, "plane", None) is None)
 
-    def _answer_hybrid(self, texts: Sequence[str], n_results: int, filter_dict: Optional[Dict]) -> List[Dict[str, Any]]:
+    def _answer_hybrid(self, texts: Sequence[str], n_results: int, filter_dict: Optional[Dict],
+                       fuzzy=None) -> List[Dict[str, Any]]:
         """blocking, one worker thread: cached or fresh embeddings, then ONE collection.hybrid_query"""
+        more = {} if fuzzy is None else {"fuzzy": fuzzy}
         res = self.collection.hybrid_query(self._embed(texts), list(texts), n_results=n_results, where=filter_dict,
-                                           include=self._INCLUDE)
-        return [{key: res[key][at] for key in HYBRID_KEYS} for at in range(len(texts))]
+                                           include=self._INCLUDE, **more)
+        keys = HYBRID_KEYS + (("corrections",) if "corrections" in res else ())
+        return [{key: res[key][at] for key in keys} for at in range(len(texts))]
+
+    async def suggest_terms(self, words: Sequence[str], fuzzy="auto", limit: int = 5) -> List[List[Dict[str, Any]]]:
+        """"Did you mean" (VectorIndex.suggest_terms): per word up to `limit` indexed terms within the allowed edits, as
+        {"term", "edits", "df"}, best first"""
+        await self._ready()
+        if not hasattr(self.collection, "suggest_terms"):
+            raise ValueError(_NEEDS_HYBRID[1])
+        return await asyncio.to_thread(self.collection.suggest_terms, list(words), fuzzy, limit)
 
     async def hybrid_query(self, query_text: str, n_results: int = 5,
-                           filter_dict: Optional[Dict] = None, leg: str = "lexical") -> Dict[str, Any]:
+                           filter_dict: Optional[Dict] = None, leg: str = "lexical", fuzzy=None) -> Dict[str, Any]:
         """Dense + BM25 retrieval fused by reciprocal rank (VectorIndex.hybrid_query): one result dict with `ids`,
         `distances`, `metadatas`, `documents`, `hybrid_scores` and `lexical_scores`, in hybrid-score order (distances
         are therefore not ascending).  Same empty-query error, embedding cache and query count as query(); it calls
         the collection directly (no dynamic batching).  `leg` = "sparse": the second leg is learned sparse retrieval
         instead of BM25 (VectorIndex.sparse_hybrid_query) and the dict carries `sparse_scores` in place of
-        `lexical_scores`."""
+        `lexical_scores`.  `fuzzy` ("auto", True or 0..2 edits; None: the MMRAG_LEXICAL_FUZZY setting) makes the BM25 leg
+        typo-tolerant (VectorIndex.lexical_query) and the dict then carries `corrections`; it does not go with the
+        sparse leg."""
+        from .lexical import parse_fuzzy
+
+        if leg == "sparse" and parse_fuzzy(fuzzy) is not None:
+            raise ValueError("fuzzy matching belongs to the lexical leg, not the learned sparse one")
         if leg == "sparse":
             await self._ready()
             if not (self.has_sparse_encoder() and self.supports_sparse()):
@@ -801,7 +818,9 @@ class EmbeddingManager:
                                       n_results, filter_dict)
         if leg != "lexical":
             raise ValueError(f"hybrid leg must be 'lexical' or 'sparse', not {leg!r}")
-        return await self._single("Hybrid query", _NEEDS_HYBRID, self._answer_hybrid, query_text, n_results, filter_dict)
+        fuzzy = parse_fuzzy(settings.MMRAG_LEXICAL_FUZZY if fuzzy is None else fuzzy)
+        return await self._single("Hybrid query", _NEEDS_HYBRID, self._answer_hybrid, query_text, n_results, filter_dict,
+                                  *(() if fuzzy is None else (fuzzy,)))
 
     # ------------------------------------------------------------------ learned sparse ------
     def has_sparse_encoder(self) -> bool:

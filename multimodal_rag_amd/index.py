@@ -2362,23 +2362,53 @@ class VectorIndex:
     def lexical_enabled(self) -> bool:
         return self._lex is not None
 
-    def _lexical_search(self, query_texts: Sequence[str], n_results: int, where):
-        """enqueue the BM25 search (caller holds the lock): device (scores, rows), -1 padded"""
+    def _lexical_search(self, query_texts: Sequence[str], n_results: int, where, fuzzy=None):
+        """enqueue the BM25 search (caller holds the lock): device (scores, rows), -1 padded, and the corrections
+        typo tolerance made (None without `fuzzy`)"""
         if isinstance(query_texts, str):
             raise ValueError("query_texts must be a list of strings")
         if n_results < 1 or n_results > _native.MAX_K_DEEP:
             raise ValueError(f"n_results must be in 1..{_native.MAX_K_DEEP} for lexical search")
         lex = self.enable_lexical()
-        return lex.topk(list(query_texts), n_results, self._where_bits(where))
+        got = lex.topk(list(query_texts), n_results, self._where_bits(where), fuzzy=fuzzy)
+        return got if len(got) == 3 else got + (None,)
+
+    def suggest_terms(self, words: Sequence[str], fuzzy="auto", limit: int = 5) -> List[List[Dict[str, Any]]]:
+        """"Did you mean": for each word (analysed like a query; its first term counts) up to `limit` (at most 16)
+        indexed terms within the edits `fuzzy` allows it, as {"term", "edits", "df"}: fewer edits first, then the
+        larger live df, then the term seen first.  Only terms some live row holds are suggested; an indexed word is
+        its own first suggestion."""
+        from .lexical import FUZZY_MAX_EXPANSIONS, analyze, fuzzy_edits, parse_fuzzy
+
+        if isinstance(words, str):
+            raise ValueError("words must be a list of strings")
+        if not 1 <= limit <= FUZZY_MAX_EXPANSIONS:
+            raise ValueError(f"limit must be in 1..{FUZZY_MAX_EXPANSIONS}")
+        mode = parse_fuzzy(fuzzy)
+        if mode is None:
+            raise ValueError("suggest_terms needs fuzzy: 'auto' or 0..2")
+        terms = [(analyze(w) or [""])[0] for w in words]
+        with self._lock:
+            lex = self.enable_lexical()
+            got_t, got_e = lex.fuzzy_terms(terms, [fuzzy_edits(mode, len(t)) for t in terms], limit)
+            df = lex.df_host()
+            out = []
+            for i, t in enumerate(terms):
+                ids = [int(x) for x in got_t[i] if x >= 0] if t else []
+                out.append([{"term": lex.lexicon.terms(tid, 1)[0], "edits": int(got_e[i, j]), "df": int(df[tid])}
+                            for j, tid in enumerate(ids)])
+        return out
 
     def lexical_query(self, query_texts: Sequence[str], n_results: int = 10, where: Optional[Dict[str, Any]] = None,
-                      include: Sequence[str] = ("metadatas", "documents")) -> Dict[str, Any]:
+                      include: Sequence[str] = ("metadatas", "documents"), fuzzy=None) -> Dict[str, Any]:
         """BM25 search (csrc/lexical.hip): Chroma-shaped lists of lists `ids`, `documents`, `metadatas` and
         `lexical_scores` (descending; ties to the lower row).  Only rows holding at least one query term are returned,
         so a list may be shorter than n_results.  Statistics (N, avgdl, df) are over the live rows; `where` restricts
-        the results only."""
+        the results only.  `fuzzy` ("auto", True or 0..2 edits; csrc/fuzzy.hip): query terms no live row holds are
+        replaced by their closest indexed term before scoring, and the result carries `corrections`, per query a list
+        of {"term", "matched", "edits"}; corrections are collection-wide like the statistics."""
         with self._lock:
-            scores, rows = self._lexical_search(query_texts, n_results, where)
+            scores, rows, corrections = self._lexical_search(query_texts, n_results, where, fuzzy)
             tables = self._tables()
         scores_h, rows_h = scores.cpu(), rows.cpu()
         out: Dict[str, Any] = {"ids": [], "documents": [] if "documents" in include else None,
@@ -2387,18 +2417,21 @@ class VectorIndex:
             hit = [r for r in rrow if r >= 0]
             self._append_hits(out, tables, hit, include)
             out["lexical_scores"].append(srow[: len(hit)])
+        if corrections is not None:
+            out["corrections"] = corrections
         return out
 
     def hybrid_query(self, query_embeddings, query_texts: Sequence[str], n_results: int = 10,
                      where: Optional[Dict[str, Any]] = None,
                      include: Sequence[str] = ("metadatas", "documents", "distances"),
-                     check_norm: bool = True) -> Dict[str, Any]:
+                     check_norm: bool = True, fuzzy=None) -> Dict[str, Any]:
         """Dense + lexical retrieval fused by reciprocal rank (lexical.rrf_fuse).  Each leg takes
         C = max(n_results, MMRAG_HYBRID_CANDIDATES) hits (at most 4096) under the same `where`; a row scores
         sum 1 / (MMRAG_HYBRID_RRF_K + rank) over the legs that returned it.  Returns `ids`, `documents`, `metadatas`,
         `distances`, `hybrid_scores` and `lexical_scores` (0.0 for rows the lexical leg did not return), ordered by
         hybrid score -- so `distances` (1 - cos, the dense leg's own value where it returned the row, else computed on
-        the device from the stored row) are NOT ascending."""
+        the device from the stored row) are NOT ascending.  `fuzzy` makes the lexical leg typo-tolerant as in
+        lexical_query; the result then carries `corrections`."""
         from .config import settings
         from .lexical import rows_dot, rrf_fuse
 
@@ -2418,7 +2451,7 @@ class VectorIndex:
             if q.shape[0] != len(texts):
                 raise ValueError(f"{q.shape[0]} query embeddings for {len(texts)} query texts")
             d_scores, d_rows = self._launch_search(query_embeddings, C, where, check_norm)
-            l_scores, l_rows = self._lexical_search(texts, C, where)
+            l_scores, l_rows, corrections = self._lexical_search(texts, C, where, fuzzy)
             tables = self._tables()
             d_s, d_r = d_scores.cpu(), d_rows.cpu()
             l_s, l_r = l_scores.cpu().tolist(), l_rows.cpu().tolist()
@@ -2446,6 +2479,8 @@ class VectorIndex:
             out["hybrid_scores"].append([s for _, s in top])
             out["lexical_scores"].append([lex.get(r, 0.0) for r in rows])
             out["distances"].append([dist_dense[b][dpos[r]] if r in dpos else extra[(b, r)] for r in rows])
+        if corrections is not None:
+            out["corrections"] = corrections
         return out
 
     # ------------------------------------------------------------------ learned sparse ----

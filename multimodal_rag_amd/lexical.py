@@ -9,6 +9,10 @@ Scoring contract (the tests pin it against tests/bm25_ref.py):
                 idf_t * tf (k1 + 1) / (tf + k1 (1 - b + b dl / avgdl)),   idf_t = ln(1 + (N - df_t + 0.5) / (df_t + 0.5))
   with N, avgdl = sum(dl) / N and df over the LIVE rows (a `where` filter restricts results, not statistics), float32 on
   the device.  Rows with score > 0, alive and passing `where`, ordered by score, ties to the lower row.
+
+Typo tolerance (opt-in, `fuzzy=`; the tests pin it against tests/fuzzy_ref.py): a query term no live row holds is
+replaced by its closest indexed term -- optimal-string-alignment distance within 0..2 edits, then larger live df, then
+lower id -- found on the device over the lexicon's strings (csrc/fuzzy.hip); the list then goes to the same scoring.
 """
 from __future__ import annotations
 
@@ -105,10 +109,105 @@ class Lexicon:
             total = int(out_off[n])
             return out_off, ids[:total], tfs[:total], dl
 
+    def export(self, first_id: int, count: int):
+        """(offsets int64 [count+1] from 0, code points uint32) of terms first_id .. first_id + count"""
+        offs = np.zeros(count + 1, np.int64)
+        cps = np.empty(max(8 * count, 1), np.uint32)
+        while True:
+            st = self._lib.mmrag_lexicon_export(self._h, first_id, count, offs.ctypes.data, cps.ctypes.data, cps.size)
+            if st == 2 and int(offs[count]) > cps.size:        # MMRAG_EWORKSPACE: offsets say how much
+                cps = np.empty(int(offs[count]), np.uint32)
+                continue
+            _native._check(st, "mmrag_lexicon_export")
+            return offs, cps[: int(offs[count])]
+
+    def terms(self, first_id: int, count: int) -> List[str]:
+        """the term strings of ids first_id .. first_id + count"""
+        offs, cps = self.export(first_id, count)
+        return [_str_of(cps[offs[i]: offs[i + 1]]) for i in range(count)]
+
+    def analyze_terms(self, texts: Sequence[Optional[str]]):
+        """(offsets int64 [n+1], term_ids int32, cp_offsets int64 [total+1], cps uint32): every distinct term of each
+        text in order of first occurrence, unknown ones (id -1) included; term j of the batch is
+        cps[cp_offsets[j] .. cp_offsets[j+1])"""
+        cps, offs = _utf32([t or "" for t in texts])
+        n = len(texts)
+        out_off = np.zeros(n + 1, np.int64)
+        needed = np.zeros(2, np.int64)
+        t_cap, c_cap = int(cps.size) + 1, 2 * int(cps.size) + 16
+        while True:
+            ids = np.empty(t_cap, np.int32)
+            cp_off = np.zeros(t_cap + 1, np.int64)
+            out = np.empty(c_cap, np.uint32)
+            st = self._lib.mmrag_lexicon_analyze_terms(self._h, cps.ctypes.data, offs.ctypes.data, n,
+                                                       out_off.ctypes.data, ids.ctypes.data, cp_off.ctypes.data,
+                                                       out.ctypes.data, t_cap, c_cap, needed.ctypes.data,
+                                                       self.n_threads)
+            if st == 2 and (int(needed[0]) > t_cap or int(needed[1]) > c_cap):   # decompositions outgrew the guess
+                t_cap, c_cap = max(t_cap, int(needed[0])), max(c_cap, int(needed[1]))
+                continue
+            _native._check(st, "mmrag_lexicon_analyze_terms")
+            total = int(needed[0])
+            return out_off, ids[:total], cp_off[: total + 1], out[: int(needed[1])]
+
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
             self._lib.mmrag_lexicon_destroy(h)
+
+
+def _str_of(cps: np.ndarray) -> str:
+    return np.ascontiguousarray(cps, np.uint32).tobytes().decode("utf-32-le", "surrogatepass")
+
+
+FUZZY_MAX_LEN = 64          # MMRAG_FUZZY_MAX_LEN: longer terms are neither corrected nor corrected to
+FUZZY_MAX_EXPANSIONS = 16   # MMRAG_FUZZY_MAX_EXPANSIONS
+
+
+def parse_fuzzy(fuzzy):
+    """None (off), "auto" or an int 0..2 from what callers pass: None / "" / False, True / "auto", 0..2 / "0".."2" """
+    if fuzzy is None or fuzzy is False or fuzzy == "":
+        return None
+    if fuzzy is True:
+        return "auto"
+    if isinstance(fuzzy, str):
+        s = fuzzy.strip().lower()
+        if s == "auto":
+            return "auto"
+        if s in ("0", "1", "2"):
+            return int(s)
+    elif isinstance(fuzzy, (int, np.integer)) and 0 <= int(fuzzy) <= 2:
+        return int(fuzzy)
+    raise ValueError(f"fuzzy must be 'auto', True or an integer 0..2, not {fuzzy!r}")
+
+
+def fuzzy_edits(fuzzy, n_code_points: int) -> int:
+    """the edits allowed to a term of n_code_points under `fuzzy` (parse_fuzzy's value, not None).  "auto" is the
+    AUTO:3,6 rule: 0 for 1-2 code points, 1 for 3-5, 2 for 6 or more.  Terms above FUZZY_MAX_LEN get 0."""
+    if n_code_points > FUZZY_MAX_LEN:
+        return 0
+    if fuzzy == "auto":
+        return 0 if n_code_points < 3 else 1 if n_code_points < 6 else 2
+    return int(fuzzy)
+
+
+def rewrite_terms(terms: Sequence[Tuple[int, str]], live: Sequence[bool], best: Dict[str, Tuple[int, int]]):
+    """One query's term list under typo tolerance (pure Python; tests/fuzzy_ref.py restates it).  `terms` are its
+    distinct (id, string) in order of first occurrence, id -1 when unknown; live[i] says the term is in the lexicon with
+    live df >= 1; best maps a term string to its best candidate (term id, edits).  A term that is not live is replaced
+    at the place it stood by its best candidate, or dropped when it has none; of equal ids the first stays.  Returns
+    (ids, corrections) with corrections [(term, matched id, edits)] for every term that found a candidate."""
+    ids: List[int] = []
+    corrections: List[Tuple[str, int, int]] = []
+    for (tid, s), ok in zip(terms, live):
+        if not ok:
+            if s not in best:
+                continue
+            tid, e = best[s]
+            corrections.append((s, int(tid), int(e)))
+        if tid not in ids:
+            ids.append(int(tid))
+    return ids, corrections
 
 
 def _grow(t: torch.Tensor, need: int) -> torch.Tensor:
@@ -149,6 +248,14 @@ class LexicalIndex:
         self.csr_builds = 0               # how many times the CSR was rebuilt (tests, tools)
         self.lexicon = Lexicon()
         self._max_term = -1               # largest term id appended (synthetic postings bypass the lexicon)
+        # the term plane (fuzzy matching): the lexicon's strings on the device, synchronised by the first fuzzy call
+        # after adds.  Terms of synthetic postings have no strings and are not in it.
+        self._tp_off = torch.zeros(1025, dtype=torch.int32, device=dev)    # [_tp_n + 1] code point offsets
+        self._tp_cps = torch.zeros(8192, dtype=torch.int32, device=dev)    # uint32 code points (bit pattern)
+        self._tp_n = 0
+        self._tp_total = 0
+        self._fuzzy_ws = None
+        self.term_plane_syncs = 0         # how many times terms were uploaded (tests, tools)
 
     @property
     def n_terms(self) -> int:
@@ -259,13 +366,114 @@ class LexicalIndex:
         off, ids, _, _ = self.lexicon.analyze_batch(list(query_texts), LEX_QUERIES)
         return off.astype(np.int32), ids
 
+    def _sync_term_plane(self):
+        """upload the terms the lexicon gained since the last fuzzy call (ids are append-only, so this is a suffix)"""
+        V = len(self.lexicon)
+        if V > self._tp_n:
+            offs, cps = self.lexicon.export(self._tp_n, V - self._tp_n)
+            total = self._tp_total + int(cps.size)
+            if total >= 2 ** 31:
+                raise ValueError(f"the lexicon's {total} code points exceed the term plane's 2^31 - 1")
+            self._tp_off = _grow(self._tp_off, V + 1)
+            self._tp_cps = _grow(self._tp_cps, max(total, 1))
+            self._tp_off[self._tp_n: V + 1].copy_(torch.from_numpy((offs + self._tp_total).astype(np.int32)))
+            if cps.size:
+                self._tp_cps[self._tp_total: total].copy_(torch.from_numpy(cps.view(np.int32)))
+            self._tp_n, self._tp_total = V, total
+            self.term_plane_syncs += 1
+        self._df = _grow(self._df, max(V, 1))
+
+    def fuzzy_terms(self, terms: Sequence[str], edits: Sequence[int], max_expansions: int = 1):
+        """For each analysed term string the best lexicon terms within edits[i] (0..2) optimal-string-alignment edits
+        (csrc/fuzzy.hip): (term ids [P, E] int32, edits [P, E] int32) on the host, best first (fewer edits, then
+        larger live df, then lower id), -1 padded.  Candidates have live df >= 1 and at most FUZZY_MAX_LEN code
+        points; a longer term string has none."""
+        P, E = len(terms), int(max_expansions)
+        if not 1 <= E <= FUZZY_MAX_EXPANSIONS:
+            raise ValueError(f"max_expansions must be in 1..{FUZZY_MAX_EXPANSIONS}")
+        if len(edits) != P:
+            raise ValueError(f"{len(edits)} edit budgets for {P} terms")
+        pe = np.ascontiguousarray(edits, np.int32)
+        if P and (pe.min() < 0 or pe.max() > 2):
+            raise ValueError("edits must be 0, 1 or 2")
+        if P == 0:
+            return np.zeros((0, E), np.int32), np.zeros((0, E), np.int32)
+        self._sync_term_plane()
+        cps, offs = _utf32(list(terms))
+        return self.fuzzy_ids(self._tp_off, self._tp_cps, self._df, self._tp_n, offs.astype(np.int32), cps, pe, E)
+
+    def fuzzy_ids(self, term_off: torch.Tensor, term_cps: torch.Tensor, df: torch.Tensor, n_terms: int,
+                  pat_off: np.ndarray, pat_cps: np.ndarray, pat_edits: np.ndarray, max_expansions: int):
+        """mmrag_fuzzy_terms over an explicit term plane (device int32 offsets, code points, df) and host patterns"""
+        P, E = int(pat_off.size) - 1, int(max_expansions)
+        dev = self.device
+        d_off = torch.from_numpy(np.ascontiguousarray(pat_off, np.int32)).to(dev)
+        d_cps = torch.from_numpy(np.concatenate([np.ascontiguousarray(pat_cps, np.uint32).view(np.int32),
+                                                 np.zeros(1, np.int32)])).to(dev)
+        d_ed = torch.from_numpy(np.ascontiguousarray(pat_edits, np.int32)).to(dev)
+        L = _native.lib()
+        need = int(L.mmrag_fuzzy_terms_workspace_bytes(n_terms, P, E))
+        if self._fuzzy_ws is None or self._fuzzy_ws.numel() < need:
+            self._fuzzy_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        out_t = torch.empty((P, E), dtype=torch.int32, device=dev)
+        out_e = torch.empty((P, E), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _native._check(L.mmrag_fuzzy_terms(term_off.data_ptr(), term_cps.data_ptr(), df.data_ptr(), n_terms,
+                                               d_off.data_ptr(), d_cps.data_ptr(), d_ed.data_ptr(), P, E,
+                                               out_t.data_ptr(), out_e.data_ptr(), self._fuzzy_ws.data_ptr(),
+                                               self._fuzzy_ws.numel(), self._stream()), "mmrag_fuzzy_terms")
+        return out_t.cpu().numpy(), out_e.cpu().numpy()
+
+    def analyze_queries_fuzzy(self, query_texts: Sequence[str], fuzzy):
+        """analyze_queries under typo tolerance: (q_off, q_terms, corrections).  Only terms that contribute nothing
+        today -- unknown, or known with live df == 0 -- are corrected, each to its single best candidate
+        (rewrite_terms); corrections[i] lists query i's {"term", "matched", "edits"}.  Collection-wide, like df."""
+        fuzzy = parse_fuzzy(fuzzy)
+        off, ids, cp_off, cps = self.lexicon.analyze_terms(list(query_texts))
+        strings = [_str_of(cps[cp_off[j]: cp_off[j + 1]]) for j in range(int(ids.size))]
+        self._sync_term_plane()
+        live = np.zeros(ids.size, bool)
+        known = ids >= 0
+        if known.any():
+            df = self._df[torch.from_numpy(ids[known].astype(np.int64)).to(self.device)].cpu().numpy()
+            live[known] = df >= 1
+        want: Dict[str, int] = {}
+        for j in np.nonzero(~live)[0]:
+            e = fuzzy_edits(fuzzy, int(cp_off[j + 1] - cp_off[j]))
+            if e > 0 and cp_off[j + 1] - cp_off[j] <= FUZZY_MAX_LEN:
+                want.setdefault(strings[j], e)
+        best: Dict[str, Tuple[int, int]] = {}
+        if want and self._tp_n:
+            pats = list(want)
+            got_t, got_e = self.fuzzy_terms(pats, [want[p] for p in pats], 1)
+            best = {p: (int(got_t[i, 0]), int(got_e[i, 0])) for i, p in enumerate(pats) if got_t[i, 0] >= 0}
+        q_off = np.zeros(off.size, np.int32)
+        q_terms: List[int] = []
+        corrections: List[List[Dict[str, object]]] = []
+        names: Dict[int, str] = {}
+        for i in range(off.size - 1):
+            lo, hi = int(off[i]), int(off[i + 1])
+            kept, made = rewrite_terms([(int(ids[j]), strings[j]) for j in range(lo, hi)], live[lo:hi], best)
+            q_terms.extend(kept)
+            q_off[i + 1] = len(q_terms)
+            for _, tid, _ in made:
+                if tid not in names:
+                    names[tid] = self.lexicon.terms(tid, 1)[0]
+            corrections.append([{"term": s, "matched": names[tid], "edits": e} for s, tid, e in made])
+        return q_off, np.asarray(q_terms, np.int32), corrections
+
     def topk(self, query_texts: Sequence[str], k: int, alive_bits: Optional[torch.Tensor] = None,
-             k1: Optional[float] = None, b: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(scores [B, k] float32 desc, rows [B, k] int64; (-inf, -1) padding) on the device"""
+             k1: Optional[float] = None, b: Optional[float] = None, fuzzy=None):
+        """(scores [B, k] float32 desc, rows [B, k] int64; (-inf, -1) padding) on the device.  With `fuzzy`
+        ("auto", True or 0..2) the query terms BM25 would drop are corrected first (analyze_queries_fuzzy) and the
+        corrections come back as a third value."""
         if len(query_texts) == 0:
             raise ValueError("no query texts")
         if not 1 <= k <= _native.MAX_K_DEEP:
             raise ValueError(f"n_results must be in 1..{_native.MAX_K_DEEP} for lexical search")
+        if parse_fuzzy(fuzzy) is not None:
+            q_off, q_terms, corrections = self.analyze_queries_fuzzy(query_texts, fuzzy)
+            return self.topk_ids(q_off, q_terms, k, alive_bits, k1, b) + (corrections,)
         q_off, q_terms = self.analyze_queries(query_texts)
         return self.topk_ids(q_off, q_terms, k, alive_bits, k1, b)
 
@@ -327,6 +535,13 @@ def csr_build_workspace_bytes(n: int, n_terms: int) -> int:
     return int(_native.lib().mmrag_lexical_csr_build_workspace_bytes(n, n_terms))
 
 
+def fuzzy_limits() -> Dict[str, int]:
+    """csrc/fuzzy.hip's tile sizes (mmrag_internal_fuzzy_limits; tests put their seams on them)"""
+    v = [c_int(0) for _ in range(5)]
+    _native._check(_native.lib().mmrag_internal_fuzzy_limits(*[byref(x) for x in v]), "mmrag_internal_fuzzy_limits")
+    return dict(zip(("term_tile", "pattern_tile", "max_len", "max_expansions", "stage_cps"), (int(x.value) for x in v)))
+
+
 def lexical_limits() -> Dict[str, int]:
     """csrc/lexical.hip's path thresholds (mmrag_internal_lexical_limits; tests restate them and compare)"""
     v = [c_int(0) for _ in range(5)]
@@ -358,6 +573,18 @@ def declare(lib):
     lib.mmrag_bm25_topk.argtypes = [c_void_p] * 5 + [c_int, c_int64, c_void_p, c_void_p, c_int, c_int64, c_int64,
                                                      c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                                      c_size_t, c_void_p]
+    lib.mmrag_lexicon_export.restype = c_int
+    lib.mmrag_lexicon_export.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64]
+    lib.mmrag_lexicon_analyze_terms.restype = c_int
+    lib.mmrag_lexicon_analyze_terms.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_int64, c_int64, c_void_p, c_int]
+    lib.mmrag_fuzzy_terms_workspace_bytes.restype = c_size_t
+    lib.mmrag_fuzzy_terms_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    lib.mmrag_fuzzy_terms.restype = c_int
+    lib.mmrag_fuzzy_terms.argtypes = [c_void_p] * 3 + [c_int] + [c_void_p] * 3 + [c_int, c_int, c_void_p, c_void_p,
+                                                                                  c_void_p, c_size_t, c_void_p]
+    lib.mmrag_internal_fuzzy_limits.restype = c_int
+    lib.mmrag_internal_fuzzy_limits.argtypes = [c_void_p] * 5
     # test-only export (not in include/mmrag.h): the sizes at which the kernels change path
     lib.mmrag_internal_lexical_limits.restype = c_int
     lib.mmrag_internal_lexical_limits.argtypes = [c_void_p] * 5

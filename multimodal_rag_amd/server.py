@@ -58,6 +58,11 @@ class QueryRequest(BaseModel):  # api.py:161-164
     # with `hybrid`: the second leg, "lexical" (BM25, the default) or "sparse" (learned sparse retrieval: each source
     # then carries its `sparse_score` too)
     hybrid_leg: Optional[Literal["lexical", "sparse"]] = None
+    # with `hybrid` and the lexical leg: typo tolerance -- true or "auto" (0 / 1 / 2 edits for terms of 1-2 / 3-5 / 6+
+    # code points) or 0..2 edits for every term.  A query term no stored chunk holds is replaced by its closest
+    # indexed term (csrc/fuzzy.hip) before BM25 scores; the response then carries `corrections`, a list of
+    # {"term", "matched", "edits"}.  Unset: the MMRAG_LEXICAL_FUZZY setting
+    fuzzy: Optional[Any] = None
     # not in the reference: hits by learned sparse retrieval alone (EmbeddingManager.sparse_query: the question expanded
     # by the masked-LM of MMRAG_SPARSE_ENCODER_DIR, scored exactly against the stored sparse vectors); each source
     # carries its `sparse_score` and, with `explain`, `matched_terms`: the shared vocabulary strings with their
@@ -332,6 +337,8 @@ class QueryResponse(BaseModel):  # api.py:167-170
     # `reader` only (the route leaves unset fields out of the response)
     answers: Optional[List[dict]] = None
     answerable: Optional[bool] = None
+    # `fuzzy` only
+    corrections: Optional[List[dict]] = None
 
 
 class UploadResponse(BaseModel):  # api.py:173-179
@@ -503,7 +510,7 @@ class Pipeline:
                      filter_dict: Optional[Dict[str, Any]] = None, late: bool = False,
                      passage_tokens: Optional[int] = None, sparse: bool = False,
                      hybrid_leg: Optional[str] = None, extractive: bool = False,
-                     reader: Optional[str] = None) -> Optional[dict]:
+                     reader: Optional[str] = None, fuzzy: Any = None) -> Optional[dict]:
         """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
         max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the re-ranker's best top_k (`rerank_method` "cross" or "late",
         default MMRAG_RERANK_METHOD; `explain`: late interaction's per-token matches on every source).  `hybrid`: from
@@ -529,7 +536,8 @@ class Pipeline:
         every quoted source carries its `quotes`.  `reader` ("spans" or "answer"; with any mode `passages` works with):
         EmbeddingManager.read_answers over the hits' raw text passages -- the result gains `answers` and `answerable`,
         every source its `answer_spans`; "answer": the answer is the best span's text (NO_ANSWER_FOUND when the hits do
-        not answer the question), no generator call"""
+        not answer the question), no generator call.  `fuzzy` (with `hybrid` and the lexical leg): the BM25 leg is
+        typo-tolerant (EmbeddingManager.hybrid_query) and the result carries the `corrections` it made"""
         multi = variants is not None
         sparse_leg = hybrid and hybrid_leg == "sparse"
         riding = passage_tokens is not None and rerank and rerank_method == "late"
@@ -554,7 +562,7 @@ class Pipeline:
         elif sparse_leg:
             search = functools.partial(self.embedder.hybrid_query, leg="sparse", **only)
         elif hybrid:
-            search = functools.partial(self.embedder.hybrid_query, **only)
+            search = functools.partial(self.embedder.hybrid_query, **only, **({} if fuzzy is None else {"fuzzy": fuzzy}))
         elif late:
             search = functools.partial(self.embedder.late_query, **only)
         elif doc_ids is not None and not filter_dict and hasattr(self.embedder, "scoped_query"):
@@ -571,6 +579,7 @@ class Pipeline:
             hits = await self.embedder.grouped_query(question, n_groups=top_k, group_size=per_document, **only)
         elif rerank:
             hits = await search(question, n_results=max(top_k, settings.MMRAG_RERANK_CANDIDATES))
+            corrections = hits.get("corrections")
             if hits["ids"]:
                 carried = {column: dict(zip(hits["ids"], hits[column])) for column in extra}
                 # (the method is passed on only when one was chosen: an embedder without late interaction keeps its
@@ -581,6 +590,8 @@ class Pipeline:
                 hits = await self.embedder.rerank_results(question, hits, top_k=top_k, **chosen)
                 for column, of_id in carried.items():
                     hits[column] = [of_id[found] for found in hits["ids"]]
+                if corrections is not None:
+                    hits["corrections"] = corrections
         else:
             hits = await search(question, n_results=top_k)
         if not hits["ids"]:
@@ -635,10 +646,11 @@ class Pipeline:
                     src["document"] = group["key"]
                     src["document_rank"] = document_rank
                 at += len(group["ids"])
+        made = {"corrections": hits["corrections"]} if "corrections" in hits else {}
         if read is not None:
             return {"answer": text, "sources": ranked, "answerable": read["answerable"],
-                    "answers": [{key: answer[key] for key in ANSWER_KEYS} for answer in read["answers"]]}
-        return {"answer": text, "sources": ranked}
+                    "answers": [{key: answer[key] for key in ANSWER_KEYS} for answer in read["answers"]], **made}
+        return {"answer": text, "sources": ranked, **made}
 
     async def recommend(self, like: List[str], unlike: List[str], unlike_texts: List[str], top_k: int,
                         filter_dict: Optional[Dict], negative_weight: Optional[float]) -> dict:
@@ -769,6 +781,21 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
         if request.hybrid_leg is not None and not request.hybrid:
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                 detail="`hybrid_leg` belongs to hybrid retrieval: send it with `hybrid`")
+        fuzzy = None
+        if request.fuzzy is not None:
+            from .lexical import parse_fuzzy
+
+            if not request.hybrid:
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                    detail="`fuzzy` belongs to hybrid retrieval's lexical leg: send it with `hybrid`")
+            if request.hybrid_leg == "sparse":
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                    detail="`fuzzy` belongs to the lexical leg: send it without `hybrid_leg`: \"sparse\"")
+            try:
+                fuzzy = parse_fuzzy(request.fuzzy)
+            except ValueError as e:
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
+            fuzzy = "" if fuzzy is None else fuzzy      # an explicit false overrides the setting
         if request.sparse:
             if (multi or request.mmr or request.hybrid or request.group_by_document or request.rerank or request.late
                     or (request.boost is not None and request.boost is not False) or request.like is not None
@@ -909,6 +936,7 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
                                     **({} if not request.late else {"late": True}),
                                     **({} if not request.sparse else {"sparse": True}),
                                     **({} if request.hybrid_leg is None else {"hybrid_leg": request.hybrid_leg}),
+                                    **({} if fuzzy is None else {"fuzzy": fuzzy}),
                                     **({} if window is None else {"passage_tokens": window}),
                                     **({} if not request.extractive_answer else {"extractive": True}),
                                     **({} if not (request.reader or request.reader_answer) else
