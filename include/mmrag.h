@@ -1282,6 +1282,45 @@ int mmrag_summary_select(const void *rows, int64_t ld, int dtype, int d, int64_t
                          float alpha, int iterations, float lambda, int k, int32_t *out_pos, float *out_val,
                          float *out_rel, int32_t *out_used, void *stream);
 
+/* Semantic chunking (csrc/chunk.hip): where to cut a document's sentences into chunks -- the
+ * stage parser.py:1702-1736 `_basic_chunk_text` fills with a sliding character window.  The globally optimal
+ * segmentation under the size limits, by dynamic programming over the similarities at distance < 64.  One workgroup
+ * per document, documents of any length.
+ *
+ * Definition, for document u with rows x_0 .. x_{n-1} = rows[doc_start[u] .. + doc_len[u]), n >= 1, and costs c_i =
+ * cost[doc_start[u] + i] >= 1:
+ *   - S_ij = <x_i, x_j>, float32 as the 128 x 128 tile body forms it (taken with i < j);
+ *   - a chunk [a, b) is admissible if b - a <= W = max_sentences and (b - a == 1 or c_a + .. + c_{b-1} <= max_cost);
+ *     cost sums are exact (64-bit);
+ *   - gain(a, b) = sum_{a <= i < j < b} (S_ij - tau) - penalty;
+ *   - best[0] = 0, best[b] = max over admissible a in [b - W, b) of best[a] + gain(a, b); prev[b] is the arg-max, ties
+ *     to the lowest a;
+ *   - float32 order: R_a(b) = sum_{j = a+1}^{b-1} __fsub_rn(S_aj, tau) over ascending j in one accumulator (R_a(a+1) =
+ *     0); G(b-1, b) = 0, G(a, b) = G(a+1, b) + R_a(b) for descending a; candidate v = best[a] + (G(a, b) - penalty);
+ *   - tau = threshold when auto_scale == 0; else per document auto_scale * (sum_{i=0}^{n-2} S_{i,i+1}) / (n - 1): the
+ *     sum over ascending i in one float32 accumulator, __fdiv_rn by (float)(n - 1), __fmul_rn; 0 when n == 1;
+ *   - a document's output bits do not depend on the batch, the grid or its place in the plane;
+ *   - one launch, no workspace, no host synchronisation, no atomics (the call can be captured into a graph).
+ *
+ *   rows        dev [n_rows, ld] of `dtype` MMRAG_F32 / F16 / BF16, pad columns zero, 16-byte aligned (MMRAG_F8E4M3 is
+ *               refused).  ld = mmrag_padded_dim(d, dtype) or a larger width of whole 128-byte slabs
+ *   doc_start, doc_len   dev [n_docs] int32          cost  dev [n_rows] int32, >= 1 (indexed like rows)
+ *   max_cost >= 1     max_sentences 1..MMRAG_MAX_CHUNK_SENTENCES     threshold finite     auto_scale, penalty finite, >= 0
+ *   out_prev    dev [n_rows] int32: out_prev[doc_start + b - 1] = prev[b], a position inside the document, b = 1..n
+ *   out_best    dev [n_rows] float32: out_best[doc_start + b - 1] = best[b]
+ *   out_tau     dev [n_docs] float32: the tau used
+ *   out_score   dev [n_docs] float32: best[n]
+ * The cuts are read from the end: b = n, then b = prev[b] until 0.
+ * MMRAG_EINVAL before anything is launched: a null pointer, a bad dtype, shape or pitch, FP8 rows, n_rows outside
+ * 1..2^31 - 1, n_docs outside 1..2^24, a parameter out of range.  The tables live on the device and are not read by the
+ * host: a document whose entry is out of range (doc_len < 1, doc_start < 0, rows past n_rows) gets NaN in out_score[u];
+ * its out_tau entry and its rows of out_prev / out_best are not written (mmrag_summary_select's rule). */
+#define MMRAG_MAX_CHUNK_SENTENCES 64
+int mmrag_chunk_boundaries(const void *rows, int64_t ld, int dtype, int d, int64_t n_rows, const int32_t *doc_start,
+                           const int32_t *doc_len, int n_docs, const int32_t *cost, int32_t max_cost,
+                           int max_sentences, float threshold, float auto_scale, float penalty, int32_t *out_prev,
+                           float *out_best, float *out_tau, float *out_score, void *stream);
+
 /* Measured peaks for the roofline report ("a measured stream-copy bandwidth and a measured MFMA
  * micro-benchmark peak, fractions against both the vendor and the measured peaks").  Not on the product path.
  *   mmrag_device_info        CU count, maximum shader clock (MHz), HBM bytes of the current device

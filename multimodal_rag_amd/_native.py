@@ -44,6 +44,7 @@ MAX_LATE_QUESTIONS = 4096   # mmrag_maxsim_topk (MMRAG_MAX_LATE_QUESTIONS)
 LATE_WINDOW_TOKENS, MAX_LATE_WINDOWS = 16, 32
 # mmrag_summary_select (MMRAG_MAX_SUMMARY_SENTENCES, MMRAG_MAX_SUMMARY_ITERATIONS)
 MAX_SUMMARY_SENTENCES, MAX_SUMMARY_ITERATIONS = 128, 64
+MAX_CHUNK_SENTENCES = 64   # mmrag_chunk_boundaries (MMRAG_MAX_CHUNK_SENTENCES)
 # mmrag_span_select / mmrag_reader_forward (MMRAG_MAX_READER_TOKENS, MMRAG_MAX_ANSWER_TOKENS, MMRAG_MAX_READER_SPANS)
 MAX_READER_TOKENS, MAX_ANSWER_TOKENS, MAX_READER_SPANS = 512, 64, 8
 _DT2TORCH = {F32: torch.float32, F16: torch.float16, BF16: torch.bfloat16, F8E4M3: torch.float8_e4m3fn}
@@ -379,6 +380,10 @@ def _declare(lib):
     lib.mmrag_summary_select.argtypes = [c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p,
                                          c_void_p, c_void_p, c_int64, c_void_p, c_float, c_float, c_int, c_float, c_int,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.mmrag_chunk_boundaries.restype = c_int
+    lib.mmrag_chunk_boundaries.argtypes = [c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_int,
+                                           c_void_p, ctypes.c_int32, c_int, c_float, c_float, c_float, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p]
     from .lexical import declare as declare_lexical  # BM25 analyzer, device index and search (csrc/lexical.hip)
 
     declare_lexical(lib)
@@ -1570,6 +1575,48 @@ def summary_select(rows: torch.Tensor, d: int, unit_start: torch.Tensor, unit_le
                                         pos.data_ptr(), val.data_ptr(), _ptr(rel), used.data_ptr(), _stream_ptr(dev))
     _check(st, "mmrag_summary_select")
     return pos, val, rel, used
+
+
+def chunk_boundaries(rows: torch.Tensor, d: int, doc_start: torch.Tensor, doc_len: torch.Tensor, cost: torch.Tensor,
+                     max_cost: int, max_sentences: int, threshold: float = 0.0, auto_scale: float = 0.0,
+                     penalty: float = 0.0, out=None):
+    """Semantic chunking (include/mmrag.h mmrag_chunk_boundaries): document u is the sentences rows[doc_start[u] :
+    doc_start[u] + doc_len[u]] (any number of them) with costs cost[...]; the partition into chunks of at most
+    `max_sentences` (1..MAX_CHUNK_SENTENCES) sentences and at most `max_cost` (a single sentence is always a chunk)
+    with the greatest sum of (S_ij - tau) over the pairs inside a chunk minus `penalty` per chunk.  tau is `threshold`,
+    or with auto_scale > 0 auto_scale times the document's mean adjacent similarity.  `rows` [n_rows, ld] is a device
+    tensor of a storage dtype (float32 / float16 / bfloat16), pad columns zero; the three tables are DEVICE int32
+    tensors (doc_start, doc_len [n_docs]; cost [n_rows]) and are not read by the host: a document whose entry is out
+    of range gets NaN in score[u].  Returns device tensors (prev [n_rows] int32: prev[doc_start + b - 1] = where the
+    chunk that ends before sentence b begins; best [n_rows] float32; tau [n_docs] float32; score [n_docs] float32);
+    rows of no valid document are not written.  `out`: the four to write into (a caller that replays a captured
+    graph).  One launch on the current stream, no host synchronisation."""
+    who = "chunk_boundaries"
+    tables = (doc_start, doc_len, cost)
+    _dev_check(rows, *tables)
+    _check_stored_rows(who, rows)
+    for t in tables:
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != rows.device:
+            raise MMRagNativeError(f"{who}: the tables must be contiguous 1-D int32 tensors on the rows' device")
+    n_rows, n_docs = int(rows.shape[0]), int(doc_start.shape[0])
+    if doc_len.shape[0] != n_docs or cost.shape[0] != n_rows:
+        raise MMRagNativeError(f"{who}: doc_start and doc_len need one entry per document, cost one per row")
+    if not 1 <= int(max_cost) < 2 ** 31:
+        raise MMRagNativeError(f"{who}: max_cost={max_cost} outside 1..2^31 - 1")
+    dev = rows.device
+    if out is None:
+        out = (torch.empty(n_rows, dtype=torch.int32, device=dev), torch.empty(n_rows, dtype=torch.float32, device=dev),
+               torch.empty(n_docs, dtype=torch.float32, device=dev), torch.empty(n_docs, dtype=torch.float32, device=dev))
+    prev, best, tau, score = out
+    _dev_check(*out)
+    with torch.cuda.device(dev):
+        st = lib().mmrag_chunk_boundaries(rows.data_ptr(), rows.shape[1], _TORCH2DT[rows.dtype], int(d), n_rows,
+                                          doc_start.data_ptr(), doc_len.data_ptr(), n_docs, cost.data_ptr(),
+                                          int(max_cost), int(max_sentences), float(threshold), float(auto_scale),
+                                          float(penalty), prev.data_ptr(), best.data_ptr(), tau.data_ptr(),
+                                          score.data_ptr(), _stream_ptr(dev))
+    _check(st, "mmrag_chunk_boundaries")
+    return prev, best, tau, score
 
 
 def f8_encode_rows(src: torch.Tensor, d: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:

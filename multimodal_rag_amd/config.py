@@ -195,6 +195,21 @@ class Settings:
     MMRAG_SUMMARY_ALPHA: float = field(default_factory=lambda: float(os.getenv("MMRAG_SUMMARY_ALPHA", "0.15")))
     MMRAG_SUMMARY_ITERATIONS: int = field(default_factory=lambda: int(os.getenv("MMRAG_SUMMARY_ITERATIONS", "32")))
     MMRAG_SUMMARY_LAMBDA: float = field(default_factory=lambda: float(os.getenv("MMRAG_SUMMARY_LAMBDA", "0.7")))
+    # how an upload's text is cut into chunks (chunking.py, csrc/chunk.hip).  MMRAG_CHUNKER: "basic" (default: the
+    # sliding CHUNK_SIZE-character window of ingest.basic_chunk_text) or "semantic": sentences are embedded and the
+    # text is cut where the topic changes -- the partition of greatest total within-chunk similarity above tau, chunks
+    # of at most CHUNK_SIZE characters and MMRAG_CHUNK_MAX_SENTENCES (1..64) sentences.  MMRAG_CHUNK_THRESHOLD: "" (default)
+    # = tau is MMRAG_CHUNK_AUTO_SCALE (> 0) times the document's mean adjacent-sentence similarity; a float fixes tau.
+    # MMRAG_CHUNK_PENALTY >= 0 is a price per chunk, against slivers.  MMRAG_CHUNK_SEMANTIC_OVERLAP: 1 = each chunk is
+    # prefixed with the trailing whole sentences of its predecessor that fit in CHUNK_OVERLAP characters (default 0:
+    # none).  The defaults 0.5 and 0.0 are untuned starting points
+    MMRAG_CHUNKER: str = field(default_factory=lambda: os.getenv("MMRAG_CHUNKER", "basic"))
+    MMRAG_CHUNK_THRESHOLD: str = field(default_factory=lambda: os.getenv("MMRAG_CHUNK_THRESHOLD", ""))
+    MMRAG_CHUNK_AUTO_SCALE: float = field(default_factory=lambda: float(os.getenv("MMRAG_CHUNK_AUTO_SCALE", "0.5")))
+    MMRAG_CHUNK_PENALTY: float = field(default_factory=lambda: float(os.getenv("MMRAG_CHUNK_PENALTY", "0.0")))
+    MMRAG_CHUNK_MAX_SENTENCES: int = field(default_factory=lambda: int(os.getenv("MMRAG_CHUNK_MAX_SENTENCES", "64")))
+    MMRAG_CHUNK_SEMANTIC_OVERLAP: int = field(
+        default_factory=lambda: int(os.getenv("MMRAG_CHUNK_SEMANTIC_OVERLAP", "0")))
     # CLIP engines only: embed image items from their pixels (vision tower) instead of their summary text
     MMRAG_EMBED_IMAGE_PIXELS: bool = field(default_factory=lambda: _b("MMRAG_EMBED_IMAGE_PIXELS", "true"))
 
@@ -206,6 +221,35 @@ class Settings:
         self.passage_tokens()
         self.summarizer()
         self.lexical_fuzzy()
+        self.chunker()
+
+    def chunker(self) -> str:
+        """MMRAG_CHUNKER checked: 'basic' or 'semantic' (tests set the attribute after start-up, so users call this);
+        under 'semantic' the MMRAG_CHUNK_* parameters are checked with it"""
+        if self.MMRAG_CHUNKER not in ("basic", "semantic"):
+            raise ValueError(f"MMRAG_CHUNKER must be 'basic' or 'semantic' (got {self.MMRAG_CHUNKER!r})")
+        if self.MMRAG_CHUNKER == "semantic":
+            self.chunk_parameters()
+        return self.MMRAG_CHUNKER
+
+    def chunk_parameters(self) -> dict:
+        """the MMRAG_CHUNK_* settings as the segmentation's parameters, checked (the C entry refuses them too, with
+        less to go on): threshold None = tau by auto_scale"""
+        text = str(self.MMRAG_CHUNK_THRESHOLD).strip()
+        try:
+            threshold = float(text) if text else None
+        except ValueError:
+            threshold = math.nan
+        scale, penalty = float(self.MMRAG_CHUNK_AUTO_SCALE), float(self.MMRAG_CHUNK_PENALTY)
+        most, overlap = int(self.MMRAG_CHUNK_MAX_SENTENCES), int(self.MMRAG_CHUNK_SEMANTIC_OVERLAP)
+        if ((threshold is not None and not math.isfinite(threshold)) or not 0.0 < scale < math.inf
+                or not 0.0 <= penalty < math.inf or not 1 <= most <= 64 or overlap not in (0, 1)):
+            raise ValueError("MMRAG_CHUNK_THRESHOLD must be empty (auto) or a finite float, MMRAG_CHUNK_AUTO_SCALE "
+                             "finite and > 0, MMRAG_CHUNK_PENALTY finite and >= 0, MMRAG_CHUNK_MAX_SENTENCES in 1..64, "
+                             f"MMRAG_CHUNK_SEMANTIC_OVERLAP 0 or 1 (got {self.MMRAG_CHUNK_THRESHOLD!r}, {scale}, "
+                             f"{penalty}, {most}, {overlap})")
+        return {"threshold": threshold, "auto_scale": scale, "penalty": penalty, "max_sentences": most,
+                "overlap": self.CHUNK_OVERLAP if overlap else 0}
 
     def lexical_fuzzy(self) -> str:
         """MMRAG_LEXICAL_FUZZY checked: '', 'auto', '0', '1' or '2'"""

@@ -40,6 +40,7 @@ logger = logging.getLogger(__name__)
 
 ITEM_KINDS = ("text", "table", "image")           # the kinds embed_and_store counts (embedder.py:477-479)
 RESULT_KEYS = ("ids", "distances", "metadatas", "documents")
+CHUNK_SPAN_KEYS = ("char_start", "char_end", "sentence_count", "chunker")   # a semantic chunk's stored metadata
 HYBRID_KEYS = RESULT_KEYS + ("hybrid_scores", "lexical_scores")
 MMR_KEYS = RESULT_KEYS + ("mmr_scores",)
 LATE_KEYS = RESULT_KEYS + ("late_scores",)
@@ -274,9 +275,12 @@ class EmbeddingManager:
         texts = [item["summary"] for item in summaries]
         ids = [f"{doc_id}_{item['id']}" for item in summaries]
         metas = [{"doc_id": doc_id, "item_id": item["id"], "type": item["type"]} for item in summaries]
-        for item in summaries:
+        for item, meta in zip(summaries, metas):
             if item["type"] in counts:           # other kinds are stored but not counted (:477-479)
                 counts[item["type"]] += 1
+            found = item.get("metadata") or {}
+            if found.get("chunker"):             # a semantic chunk (chunking.py) is stored with where it lies in its text
+                meta.update({key: found[key] for key in CHUNK_SPAN_KEYS if key in found})
         joint = hasattr(self._engine, "encode_images")
         # when the rows were added (what a recency boost reads): the time of this call, or each item's own UNIX time
         # under MMRAG_BOOST_TIME_KEY; kept beside the rows, never in their metadata
@@ -1684,6 +1688,26 @@ class EmbeddingManager:
         worker = self._summarizer()
         async with self._encode_lock:
             return await asyncio.to_thread(worker.answer, question, list(passages), max_chars, top_sentences)
+
+    # ---- semantic chunking: topic-boundary segmentation (chunking.py, csrc/chunk.hip) ----
+    def supports_chunking(self) -> bool:
+        """True when chunk_texts can run: supports_summaries' requirement (an engine with encode_device)"""
+        return self.supports_summaries()
+
+    async def chunk_texts(self, texts: List[str], chunk_size: Optional[int] = None) -> List[List[Dict[str, Any]]]:
+        """The semantic chunks of every text, none longer than `chunk_size` (default CHUNK_SIZE) characters: the text
+        cut where its topic changes -- chunking.DeviceChunker.chunk_texts.  One encoder call over all sentences of all
+        texts, one mmrag_chunk_boundaries launch, one copy back.  Per text a list of {"content", "start", "end",
+        "sentences", "gain"} in order."""
+        from .chunking import DeviceChunker
+
+        await self._ready()
+        if not self.supports_chunking():
+            raise ValueError("semantic chunking needs an engine with encode_device (the single-GPU HIP engine)")
+        dtype = getattr(self.collection, "dtype", None)
+        worker = DeviceChunker(self._engine, dtype if dtype is not None else settings.index_dtype())
+        async with self._encode_lock:
+            return await asyncio.to_thread(worker.chunk_texts, list(texts), chunk_size)
 
     async def late_rerank(self, query_text: str, results: Dict[str, Any], top_k: Optional[int] = None,
                           explain: bool = False, passages: Optional[int] = None) -> Dict[str, Any]:

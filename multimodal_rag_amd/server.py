@@ -26,6 +26,7 @@ from .embedder import EmbeddingManager
 from .index import DuplicateReportTruncated
 from .ingest import ExtractiveAnswerer, PassthroughSummarizer, TextDocumentParser
 from .retriever import MultiVectorRetriever
+from .chunking import make_parser
 from .summarize import make_summarizer
 
 logger = logging.getLogger(__name__)
@@ -221,6 +222,12 @@ class ExploreRequest(BaseModel):
                                 Field(min_length=1, max_length=64)]] = None
 
 
+class ChunkRequest(BaseModel):
+    """POST /chunk: how a text would be cut under MMRAG_CHUNKER=semantic; nothing is stored"""
+    text: str = Field(..., max_length=4_000_000)
+    chunk_size: Optional[int] = Field(None, ge=1, le=100_000)
+
+
 # request flag -> what it needs of the embedder (method, `supports_*` check) and the 400 detail when that is missing;
 # /query checks them in this order
 MODE_NEEDS = (
@@ -330,6 +337,12 @@ RANGE_NEEDS = ("range_query", "supports_range",
                "(MMRAG_F8_RESCORE=float16)")
 
 
+# /chunk: the same for semantic chunking
+CHUNK_NEEDS = ("chunk_texts", "supports_chunking",
+               "Semantic chunking is not available with this embedder: it needs an engine that leaves its embeddings "
+               "on the device (the single-GPU HIP engine; EmbeddingManager.chunk_texts)")
+
+
 class QueryResponse(BaseModel):  # api.py:167-170
     answer: str
     sources: List[dict]
@@ -389,7 +402,8 @@ class Pipeline:
 
     async def start(self):
         p = self.parts
-        p["parser"] = p["parser"] or TextDocumentParser()
+        # (MMRAG_CHUNKER=semantic: the parser finds the embedder, which is created below, at its first document)
+        p["parser"] = p["parser"] or make_parser(lambda: p["embedder"]) or TextDocumentParser()
         p["llm"] = p["llm"] or ExtractiveAnswerer()
         p["mllm"] = p["mllm"] or p["llm"]
         await p["llm"].initialize()
@@ -967,6 +981,17 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
         t0 = time.time()
         out = await pipe.related(None, request.texts, request.top_k, request.threshold, request.filter)
         return {**out, "processing_time": time.time() - t0}
+
+    @app.post("/chunk")
+    @_as_http_500
+    async def chunk_preview(request: ChunkRequest):
+        t0 = time.time()
+        pipe._need(CHUNK_NEEDS)
+        try:
+            chunks = (await pipe.embedder.chunk_texts([request.text], request.chunk_size))[0]
+        except ValueError as e:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
+        return {"chunks": chunks, "chunker": "semantic", "processing_time": time.time() - t0}
 
     @app.post("/explore")
     @_as_http_500
