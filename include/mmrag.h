@@ -422,6 +422,64 @@ int mmrag_bm25_topk(const int64_t *term_off, const int32_t *post_row, const int3
 int mmrag_rows_dot(const void *q, const void *corpus, int64_t ld, int dtype, int d, const int32_t *qi,
                    const int64_t *rows, int64_t m, float *out, void *stream);
 
+/* Phrase queries: a positional index beside the forward log (csrc/phrase.hip; tests/phrase_ref.py restates it).
+ *
+ * analyze_positions (HOST)  mmrag_lexicon_analyze_batch in MMRAG_LEX_DOCUMENTS mode -- the same pairs, ids, dl and
+ *               lexicon growth -- that also writes every pair's token positions (0-based token indices of the text),
+ *               ascending, concatenated in pair order: sum(dl) ints for the batch.  *pos_needed is always set to that
+ *               number.  More than `capacity` pairs or `pos_capacity` positions: MMRAG_EWORKSPACE with out_offsets, dl
+ *               and *pos_needed filled in (call again with enough of both).
+ *
+ * Positions plane (dev): pos_off [P + 1] int64, the prefix sum of fwd_tf over the P forward postings; forward posting i
+ * stands at the token positions pos[pos_off[i] .. pos_off[i+1]), ascending.
+ *
+ * Phrase tables (dev): phrase p has the terms ph_terms[ph_off[p] .. ph_off[p+1]) (1..MMRAG_MAX_PHRASE_TERMS, repeats
+ * kept) and the DRIVER term ph_driver[p]: the one of its terms with the fewest postings (the caller chooses; any term
+ * of the phrase gives the same result), or -1 for a phrase that occurs nowhere.  Query b holds the phrases
+ * q_ph[q_ph_off[b] .. q_ph_off[b+1]) (distinct, at most MMRAG_MAX_QUERY_PHRASES).  ptf_off [n_phrases + 1] int64: the
+ * prefix sum of the drivers' postings counts (0 for a driver of -1).  The tables are device data: the caller states the
+ * longest phrase (max_terms) and the most phrases of one query (max_phrases), and the kernels read no more than those.
+ *
+ *   phrase_match  the phrase (t_0 .. t_m-1) occurs at start i of a row's token sequence T under `slop` s when
+ *               T[i] = t_0 and positions i = p_0 < p_1 < .. < p_m-1 exist with T[p_j] = t_j and
+ *               p_m-1 - p_0 - (m - 1) <= s; tf_p(row) counts such starts (overlaps count; s = 0 is the contiguous
+ *               phrase).  For posting i of the driver's CSR list (row r = post_row[term_off[driver] + i]):
+ *               ptf[ptf_off[p] + i] = tf_p(r), 0 for a row not set in alive_bits (NULL = every row).  ph_rows[p] = the
+ *               number of rows with tf_p >= 1 (integer atomics: order-free).  With `bitmaps` ([B, mmrag_filter_words(n)]
+ *               uint32, bit r & 31 of word r >> 5): query b's rows holding EVERY one of its phrases; a query without
+ *               phrases gets every row below n.  max_driver_postings: the longest driver list (sizes the grid; postings
+ *               beyond it are not visited).  No host synchronisation.
+ *   bm25_phrase_topk  mmrag_bm25_topk with phrases as further clauses: after query b's loose terms, in q_ph order, each
+ *               phrase adds idf_p * tf_p (k1 + 1) / (tf_p + k1 (1 - b + b dl / avgdl)), idf_p = the sum of its terms'
+ *               idf in phrase order (a repeated term counts each time), tf_p from `ptf` as phrase_match wrote it.
+ *               require != 0: a query that has phrases returns only rows with tf_p >= 1 for every one of them (its loose
+ *               terms only add score); require == 0 and queries without phrases: rows with a score > 0.  Order, padding,
+ *               k, alive_bits, the one synchronisation and the overflow re-run as mmrag_bm25_topk; a batch without
+ *               phrases returns bit for bit what mmrag_bm25_topk returns.
+ * MMRAG_EINVAL before anything is launched: a null pointer, negative counts, B < 1, k outside 1..MMRAG_MAX_K_DEEP, slop
+ * outside 0..MMRAG_MAX_PHRASE_SLOP, max_terms above MMRAG_MAX_PHRASE_TERMS, max_phrases above MMRAG_MAX_QUERY_PHRASES. */
+#define MMRAG_MAX_PHRASE_TERMS 8
+#define MMRAG_MAX_QUERY_PHRASES 4
+#define MMRAG_MAX_PHRASE_SLOP 16
+int mmrag_lexicon_analyze_positions(void *lexicon, const uint32_t *cps, const int64_t *offsets, int n,
+                                    int64_t *out_offsets, int32_t *term_ids, int32_t *tfs, int32_t *dl,
+                                    int64_t capacity, int32_t *positions, int64_t pos_capacity, int64_t *pos_needed,
+                                    int n_threads);
+int mmrag_phrase_match(const int64_t *fwd_off, const int32_t *fwd_term, const int64_t *pos_off, const int32_t *pos,
+                       int64_t n, const int64_t *term_off, const int32_t *post_row, const int32_t *ph_off,
+                       const int32_t *ph_terms, const int32_t *ph_driver, const int64_t *ptf_off, int n_phrases,
+                       int max_terms, int64_t max_driver_postings, int slop, const uint32_t *alive_bits, int32_t *ptf,
+                       int32_t *ph_rows, const int32_t *q_ph_off, const int32_t *q_ph, int B, int max_phrases,
+                       uint32_t *bitmaps, void *stream);
+size_t mmrag_bm25_phrase_topk_workspace_bytes(int B, int64_t n, int k);
+int mmrag_bm25_phrase_topk(const int64_t *term_off, const int32_t *post_row, const int32_t *post_tf, const int32_t *dl,
+                           const int32_t *df, int n_terms, int64_t n, const int32_t *q_off, const int32_t *q_terms,
+                           int B, const int32_t *q_ph_off, const int32_t *q_ph, const int32_t *ph_off,
+                           const int32_t *ph_terms, const int32_t *ph_driver, const int64_t *ptf_off,
+                           const int32_t *ptf, int n_phrases, int max_terms, int max_phrases, int require,
+                           int64_t n_live, int64_t sum_dl, float k1, float b, int k, const uint32_t *alive_bits,
+                           float *out_scores, int64_t *out_rows, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Diversified retrieval: maximal-marginal-relevance (MMR) selection of k of a query's C dense hits (what LangChain's
  * max_marginal_relevance_search(k, fetch_k, lambda_mult) does over a Chroma collection).  The reference has no

@@ -110,6 +110,11 @@ class Settings:
     # code points) or "0", "1", "2".  A query term no live row holds is replaced by its closest indexed term; what a
     # request says about `fuzzy` overrides it
     MMRAG_LEXICAL_FUZZY: str = field(default_factory=lambda: os.getenv("MMRAG_LEXICAL_FUZZY", ""))
+    # phrase queries of the lexical leg (csrc/phrase.hip): with MMRAG_LEXICAL_PHRASES=1 a quoted segment of a hybrid
+    # query is a phrase every returned chunk must hold; MMRAG_LEXICAL_SLOP (0..16) is how many other tokens may stand
+    # between its terms.  What a request says about `phrases` / `slop` overrides them
+    MMRAG_LEXICAL_PHRASES: bool = field(default_factory=lambda: os.getenv("MMRAG_LEXICAL_PHRASES", "0") == "1")
+    MMRAG_LEXICAL_SLOP: int = field(default_factory=lambda: int(os.getenv("MMRAG_LEXICAL_SLOP", "0")))
     # hybrid retrieval: each leg returns max(n_results, MMRAG_HYBRID_CANDIDATES) hits (at most 4096), fused by
     # reciprocal rank with sum 1 / (MMRAG_HYBRID_RRF_K + rank)
     MMRAG_HYBRID_CANDIDATES: int = field(default_factory=lambda: int(os.getenv("MMRAG_HYBRID_CANDIDATES", "50")))
@@ -221,6 +226,7 @@ class Settings:
         self.passage_tokens()
         self.summarizer()
         self.lexical_fuzzy()
+        self.lexical_slop()
         self.chunker()
 
     def chunker(self) -> str:
@@ -257,6 +263,13 @@ class Settings:
             raise ValueError(f"MMRAG_LEXICAL_FUZZY must be '' (off), 'auto', '0', '1' or '2' "
                              f"(got {self.MMRAG_LEXICAL_FUZZY!r})")
         return self.MMRAG_LEXICAL_FUZZY
+
+    def lexical_slop(self) -> int:
+        """MMRAG_LEXICAL_SLOP checked: an integer in 0..16 (MMRAG_MAX_PHRASE_SLOP)"""
+        slop = self.MMRAG_LEXICAL_SLOP
+        if isinstance(slop, bool) or not isinstance(slop, int) or not 0 <= slop <= 16:
+            raise ValueError(f"MMRAG_LEXICAL_SLOP must be an integer in 0..16 (got {slop!r})")
+        return slop
 
     def summarizer(self) -> str:
         """MMRAG_SUMMARIZER checked: 'fallback' or 'extractive' (tests set the attribute after start-up, so users call

@@ -559,14 +559,19 @@ int64_t mmrag_lexicon_size(const void *lexicon) { return lexicon ? ((const Lexic
 
 // Analysis on n_threads threads (a thread per ~16 k code points, as mmrag_wordpiece_encode_batch); only the insertion
 // of unseen terms runs on one thread, in text order, so ids are first-seen whatever the thread count.
-int mmrag_lexicon_analyze_batch(void *lexicon, const uint32_t *cps, const int64_t *offsets, int n, int mode,
-                                int64_t *out_offsets, int32_t *term_ids, int32_t *tfs, int32_t *dl, int64_t capacity,
-                                int n_threads) {
-    MMRAG_CHECK_ARG(lexicon && offsets && out_offsets && dl, "lexicon_analyze_batch: null pointer");
-    MMRAG_CHECK_ARG(n >= 0, "lexicon_analyze_batch: n=%d", n);
-    MMRAG_CHECK_ARG(mode == MMRAG_LEX_DOCUMENTS || mode == MMRAG_LEX_QUERIES, "lexicon_analyze_batch: bad mode %d", mode);
-    MMRAG_CHECK_ARG(n == 0 || cps || offsets[n] == offsets[0], "lexicon_analyze_batch: null text");
-    MMRAG_CHECK_ARG(capacity >= 0 && (capacity == 0 || (term_ids && tfs)), "lexicon_analyze_batch: null output");
+// The body of mmrag_lexicon_analyze_batch and mmrag_lexicon_analyze_positions (`name`, for error texts).  With
+// want_positions every pair's token positions are written too: ascending, concatenated in pair order, sum(dl) ints.
+static int analyze_batch_impl(const char *name, void *lexicon, const uint32_t *cps, const int64_t *offsets, int n,
+                              int mode, int64_t *out_offsets, int32_t *term_ids, int32_t *tfs, int32_t *dl,
+                              int64_t capacity, bool want_positions, int32_t *positions, int64_t pos_capacity,
+                              int64_t *pos_needed, int n_threads) {
+    MMRAG_CHECK_ARG(lexicon && offsets && out_offsets && dl, "%s: null pointer", name);
+    MMRAG_CHECK_ARG(n >= 0, "%s: n=%d", name, n);
+    MMRAG_CHECK_ARG(mode == MMRAG_LEX_DOCUMENTS || mode == MMRAG_LEX_QUERIES, "%s: bad mode %d", name, mode);
+    MMRAG_CHECK_ARG(n == 0 || cps || offsets[n] == offsets[0], "%s: null text", name);
+    MMRAG_CHECK_ARG(capacity >= 0 && (capacity == 0 || (term_ids && tfs)), "%s: null output", name);
+    MMRAG_CHECK_ARG(!want_positions || (pos_needed && pos_capacity >= 0 && (pos_capacity == 0 || positions)),
+                    "%s: null positions", name);
     Lexicon &lx = *(Lexicon *)lexicon;
     if (n_threads < 1) n_threads = 1;
     if (n > 0) {
@@ -591,12 +596,22 @@ int mmrag_lexicon_analyze_batch(void *lexicon, const uint32_t *cps, const int64_
     }
     // 3. (term id, tf) pairs: documents sorted by id, queries in order of first occurrence; unknown terms dropped
     std::vector<std::vector<std::pair<int32_t, int32_t>>> pairs((size_t)n);
+    std::vector<std::vector<int32_t>> where((size_t)(want_positions ? n : 0));   // positions, in pair order
     parallel_slices(n, n_threads, [&](int lo, int hi) {
         std::vector<int32_t> sorted;
+        std::vector<std::pair<int32_t, int32_t>> by_id;
         for (int i = lo; i < hi; ++i) {
             const Analyzed &a = docs[i];
             auto &out = pairs[i];
             dl[i] = (int32_t)a.ids.size();
+            if (want_positions) {   // (id, position) sorted: the positions of each id ascending, ids as the pairs below
+                by_id.clear();
+                for (size_t t = 0; t < a.ids.size(); ++t)
+                    if (a.ids[t] >= 0) by_id.emplace_back(a.ids[t], (int32_t)t);
+                std::sort(by_id.begin(), by_id.end());
+                where[i].reserve(by_id.size());
+                for (const auto &ip : by_id) where[i].push_back(ip.second);
+            }
             sorted.clear();
             for (int32_t id : a.ids)
                 if (id >= 0) sorted.push_back(id);
@@ -621,8 +636,17 @@ int mmrag_lexicon_analyze_batch(void *lexicon, const uint32_t *cps, const int64_
     });
     out_offsets[0] = 0;
     for (int i = 0; i < n; ++i) out_offsets[i + 1] = out_offsets[i] + (int64_t)pairs[i].size();
+    std::vector<int64_t> pos_at((size_t)(want_positions ? n + 1 : 0), 0);
+    if (want_positions) {
+        for (int i = 0; i < n; ++i) pos_at[i + 1] = pos_at[i] + (int64_t)where[i].size();
+        *pos_needed = pos_at[n];
+    }
     if (out_offsets[n] > capacity) {
-        set_error("lexicon_analyze_batch: %lld pairs > capacity %lld", (long long)out_offsets[n], (long long)capacity);
+        set_error("%s: %lld pairs > capacity %lld", name, (long long)out_offsets[n], (long long)capacity);
+        return MMRAG_EWORKSPACE;
+    }
+    if (want_positions && pos_at[n] > pos_capacity) {
+        set_error("%s: %lld positions > capacity %lld", name, (long long)pos_at[n], (long long)pos_capacity);
         return MMRAG_EWORKSPACE;
     }
     parallel_slices(n, n_threads, [&](int lo, int hi) {
@@ -632,9 +656,27 @@ int mmrag_lexicon_analyze_batch(void *lexicon, const uint32_t *cps, const int64_
                 term_ids[at] = p.first;
                 tfs[at++] = p.second;
             }
+            if (want_positions && !where[i].empty())
+                memcpy(positions + pos_at[i], where[i].data(), where[i].size() * sizeof(int32_t));
         }
     });
     return MMRAG_OK;
+}
+
+int mmrag_lexicon_analyze_batch(void *lexicon, const uint32_t *cps, const int64_t *offsets, int n, int mode,
+                                int64_t *out_offsets, int32_t *term_ids, int32_t *tfs, int32_t *dl, int64_t capacity,
+                                int n_threads) {
+    return analyze_batch_impl("lexicon_analyze_batch", lexicon, cps, offsets, n, mode, out_offsets, term_ids, tfs, dl,
+                              capacity, false, nullptr, 0, nullptr, n_threads);
+}
+
+// mmrag_lexicon_analyze_batch in MMRAG_LEX_DOCUMENTS mode plus where in its text every pair's term stands
+int mmrag_lexicon_analyze_positions(void *lexicon, const uint32_t *cps, const int64_t *offsets, int n,
+                                    int64_t *out_offsets, int32_t *term_ids, int32_t *tfs, int32_t *dl,
+                                    int64_t capacity, int32_t *positions, int64_t pos_capacity, int64_t *pos_needed,
+                                    int n_threads) {
+    return analyze_batch_impl("lexicon_analyze_positions", lexicon, cps, offsets, n, MMRAG_LEX_DOCUMENTS, out_offsets,
+                              term_ids, tfs, dl, capacity, true, positions, pos_capacity, pos_needed, n_threads);
 }
 
 // Terms first_id .. first_id + count as code points: the pool is in id order, so the answer is one slice of it.

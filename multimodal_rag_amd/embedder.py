@@ -784,12 +784,15 @@ class EmbeddingManager:
         return not (getattr(c, "is_f8", False) and getattr(c, "plane", None) is None)
 
     def _answer_hybrid(self, texts: Sequence[str], n_results: int, filter_dict: Optional[Dict],
-                       fuzzy=None) -> List[Dict[str, Any]]:
-        """blocking, one worker thread: cached or fresh embeddings, then ONE collection.hybrid_query"""
+                       fuzzy=None, slop: Optional[int] = None) -> List[Dict[str, Any]]:
+        """blocking, one worker thread: cached or fresh embeddings, then ONE collection.hybrid_query.  `slop` not None:
+        phrase queries with that slop (the dict then carries `phrases`)"""
         more = {} if fuzzy is None else {"fuzzy": fuzzy}
+        if slop is not None:
+            more.update(phrases=True, slop=slop)
         res = self.collection.hybrid_query(self._embed(texts), list(texts), n_results=n_results, where=filter_dict,
                                            include=self._INCLUDE, **more)
-        keys = HYBRID_KEYS + (("corrections",) if "corrections" in res else ())
+        keys = HYBRID_KEYS + tuple(key for key in ("corrections", "phrases") if key in res)
         return [{key: res[key][at] for key in keys} for at in range(len(texts))]
 
     async def suggest_terms(self, words: Sequence[str], fuzzy="auto", limit: int = 5) -> List[List[Dict[str, Any]]]:
@@ -801,7 +804,8 @@ class EmbeddingManager:
         return await asyncio.to_thread(self.collection.suggest_terms, list(words), fuzzy, limit)
 
     async def hybrid_query(self, query_text: str, n_results: int = 5,
-                           filter_dict: Optional[Dict] = None, leg: str = "lexical", fuzzy=None) -> Dict[str, Any]:
+                           filter_dict: Optional[Dict] = None, leg: str = "lexical", fuzzy=None,
+                           phrases: Optional[bool] = None, slop: Optional[int] = None) -> Dict[str, Any]:
         """Dense + BM25 retrieval fused by reciprocal rank (VectorIndex.hybrid_query): one result dict with `ids`,
         `distances`, `metadatas`, `documents`, `hybrid_scores` and `lexical_scores`, in hybrid-score order (distances
         are therefore not ascending).  Same empty-query error, embedding cache and query count as query(); it calls
@@ -809,11 +813,15 @@ class EmbeddingManager:
         instead of BM25 (VectorIndex.sparse_hybrid_query) and the dict carries `sparse_scores` in place of
         `lexical_scores`.  `fuzzy` ("auto", True or 0..2 edits; None: the MMRAG_LEXICAL_FUZZY setting) makes the BM25 leg
         typo-tolerant (VectorIndex.lexical_query) and the dict then carries `corrections`; it does not go with the
-        sparse leg."""
-        from .lexical import parse_fuzzy
+        sparse leg.  `phrases` (None: the MMRAG_LEXICAL_PHRASES setting): a quoted segment of the question is a phrase
+        every hit must hold (VectorIndex.hybrid_query, phrase_mode "require"), its terms at most `slop` (0..16; None:
+        MMRAG_LEXICAL_SLOP) other tokens apart; the dict then carries `phrases`.  Not with the sparse leg either."""
+        from .lexical import parse_fuzzy, parse_slop
 
         if leg == "sparse" and parse_fuzzy(fuzzy) is not None:
             raise ValueError("fuzzy matching belongs to the lexical leg, not the learned sparse one")
+        if leg == "sparse" and phrases:
+            raise ValueError("phrase queries belong to the lexical leg, not the learned sparse one")
         if leg == "sparse":
             await self._ready()
             if not (self.has_sparse_encoder() and self.supports_sparse()):
@@ -823,6 +831,10 @@ class EmbeddingManager:
         if leg != "lexical":
             raise ValueError(f"hybrid leg must be 'lexical' or 'sparse', not {leg!r}")
         fuzzy = parse_fuzzy(settings.MMRAG_LEXICAL_FUZZY if fuzzy is None else fuzzy)
+        if settings.MMRAG_LEXICAL_PHRASES if phrases is None else phrases:
+            slop = parse_slop(settings.lexical_slop() if slop is None else slop)
+            return await self._single("Hybrid query", _NEEDS_HYBRID, self._answer_hybrid, query_text, n_results,
+                                      filter_dict, fuzzy, slop)
         return await self._single("Hybrid query", _NEEDS_HYBRID, self._answer_hybrid, query_text, n_results, filter_dict,
                                   *(() if fuzzy is None else (fuzzy,)))
 
@@ -1809,6 +1821,8 @@ class EmbeddingManager:
             report["bytes_per_row"] = self.collection.bytes_per_row()
         if getattr(self.collection, "token_store", None) is not None:     # tokens and bytes of the late store
             report["late_store"] = self.collection.token_stats()
+        if getattr(self.collection, "positions_enabled", False):          # the positions plane, once a phrase query built it
+            report["lexical_positions_bytes"] = self.collection.positions_bytes()
         if self.cache:
             report["cache"] = self.cache.get_stats()
         return report

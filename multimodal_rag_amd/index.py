@@ -2352,6 +2352,7 @@ class VectorIndex:
                 from .lexical import LexicalIndex
 
                 lex = LexicalIndex(self.device)
+                lex.documents_source = lambda: self._documents[: self._n]    # the positions plane is built from them
                 lex.append(self._documents[: self._n])
                 if self._n_dead:
                     lex.delete_rows(np.nonzero(self._is_dead(np.arange(self._n, dtype=np.int64)))[0])
@@ -2362,16 +2363,34 @@ class VectorIndex:
     def lexical_enabled(self) -> bool:
         return self._lex is not None
 
-    def _lexical_search(self, query_texts: Sequence[str], n_results: int, where, fuzzy=None):
+    def _lexical_search(self, query_texts: Sequence[str], n_results: int, where, fuzzy=None, phrases=None,
+                        slop: int = 0, phrase_mode: str = "require", bitmaps: bool = False):
         """enqueue the BM25 search (caller holds the lock): device (scores, rows), -1 padded, and the corrections
-        typo tolerance made (None without `fuzzy`)"""
+        typo tolerance made (None without `fuzzy`).  With `phrases` two more values: the per-query phrase report and
+        (for `bitmaps`, when some query has a phrase) the device bitmaps [B, filter_words(n)] of the rows holding every
+        phrase of each query, else None."""
         if isinstance(query_texts, str):
             raise ValueError("query_texts must be a list of strings")
         if n_results < 1 or n_results > _native.MAX_K_DEEP:
             raise ValueError(f"n_results must be in 1..{_native.MAX_K_DEEP} for lexical search")
         lex = self.enable_lexical()
+        if phrases:
+            scores, rows, corrections, report, info = lex.topk(list(query_texts), n_results, self._where_bits(where),
+                                                               fuzzy=fuzzy, phrases=True, slop=slop,
+                                                               phrase_mode=phrase_mode, bitmaps=bitmaps)
+            return scores, rows, corrections, report, (info["bitmaps"] if info is not None else None)
         got = lex.topk(list(query_texts), n_results, self._where_bits(where), fuzzy=fuzzy)
         return got if len(got) == 3 else got + (None,)
+
+    @property
+    def positions_enabled(self) -> bool:
+        """True once a phrase query built the lexical leg's positions plane"""
+        return self._lex is not None and self._lex.positions_enabled
+
+    def positions_bytes(self) -> int:
+        """device bytes of the positions plane (4 per stored token and 8 per posting, with growth room); 0 until a
+        phrase query builds it"""
+        return self._lex.positions_bytes if self._lex is not None else 0
 
     def suggest_terms(self, words: Sequence[str], fuzzy="auto", limit: int = 5) -> List[List[Dict[str, Any]]]:
         """"Did you mean": for each word (analysed like a query; its first term counts) up to `limit` (at most 16)
@@ -2400,15 +2419,29 @@ class VectorIndex:
         return out
 
     def lexical_query(self, query_texts: Sequence[str], n_results: int = 10, where: Optional[Dict[str, Any]] = None,
-                      include: Sequence[str] = ("metadatas", "documents"), fuzzy=None) -> Dict[str, Any]:
+                      include: Sequence[str] = ("metadatas", "documents"), fuzzy=None, phrases=None, slop: int = 0,
+                      phrase_mode: str = "require") -> Dict[str, Any]:
         """BM25 search (csrc/lexical.hip): Chroma-shaped lists of lists `ids`, `documents`, `metadatas` and
         `lexical_scores` (descending; ties to the lower row).  Only rows holding at least one query term are returned,
         so a list may be shorter than n_results.  Statistics (N, avgdl, df) are over the live rows; `where` restricts
         the results only.  `fuzzy` ("auto", True or 0..2 edits; csrc/fuzzy.hip): query terms no live row holds are
         replaced by their closest indexed term before scoring, and the result carries `corrections`, per query a list
-        of {"term", "matched", "edits"}; corrections are collection-wide like the statistics."""
+        of {"term", "matched", "edits"}; corrections are collection-wide like the statistics.  `phrases` (csrc/phrase.hip):
+        a segment of the query between two '"' (or between U+201C and U+201D) is a phrase of 1..8 terms, at most 4 per
+        query; it occurs in a row where its terms stand in this order with at most `slop` (0..16) other tokens between
+        the first and the last, and scores as one more BM25 clause (idf = the sum of its terms' idf, tf = the number of
+        starts).  phrase_mode "require" (default): only rows holding every phrase of the query are returned, the terms
+        outside the quotes only add score; "prefer": a phrase is an optional clause like a term.  `fuzzy` never rewrites
+        a phrase's terms.  The result then carries `phrases`, per query a list of {"text", "terms", "known", "rows"}
+        (rows: how many rows the search may return hold the phrase).  The first phrase query builds the positions plane
+        (4 bytes per stored token); without `phrases` quotes are punctuation as before."""
+        report = None
         with self._lock:
-            scores, rows, corrections = self._lexical_search(query_texts, n_results, where, fuzzy)
+            if phrases:
+                scores, rows, corrections, report, _ = self._lexical_search(query_texts, n_results, where, fuzzy, True,
+                                                                            slop, phrase_mode)
+            else:
+                scores, rows, corrections = self._lexical_search(query_texts, n_results, where, fuzzy)
             tables = self._tables()
         scores_h, rows_h = scores.cpu(), rows.cpu()
         out: Dict[str, Any] = {"ids": [], "documents": [] if "documents" in include else None,
@@ -2419,21 +2452,31 @@ class VectorIndex:
             out["lexical_scores"].append(srow[: len(hit)])
         if corrections is not None:
             out["corrections"] = corrections
+        if report is not None:
+            out["phrases"] = report
         return out
 
     def hybrid_query(self, query_embeddings, query_texts: Sequence[str], n_results: int = 10,
                      where: Optional[Dict[str, Any]] = None,
                      include: Sequence[str] = ("metadatas", "documents", "distances"),
-                     check_norm: bool = True, fuzzy=None) -> Dict[str, Any]:
+                     check_norm: bool = True, fuzzy=None, phrases=None, slop: int = 0,
+                     phrase_mode: str = "require") -> Dict[str, Any]:
         """Dense + lexical retrieval fused by reciprocal rank (lexical.rrf_fuse).  Each leg takes
         C = max(n_results, MMRAG_HYBRID_CANDIDATES) hits (at most 4096) under the same `where`; a row scores
         sum 1 / (MMRAG_HYBRID_RRF_K + rank) over the legs that returned it.  Returns `ids`, `documents`, `metadatas`,
         `distances`, `hybrid_scores` and `lexical_scores` (0.0 for rows the lexical leg did not return), ordered by
         hybrid score -- so `distances` (1 - cos, the dense leg's own value where it returned the row, else computed on
         the device from the stored row) are NOT ascending.  `fuzzy` makes the lexical leg typo-tolerant as in
-        lexical_query; the result then carries `corrections`."""
+        lexical_query; the result then carries `corrections`.  `phrases`, `slop`, `phrase_mode` as in lexical_query, and
+        the result carries `phrases`: under "require" a query that has phrases takes its DENSE leg from the same rows --
+        those holding every phrase, alive and passing `where` -- by the filtered scan (mmrag_filtered_topk) over the
+        match kernel's bitmaps, so every fused hit holds the phrases; queries without phrases share one bitmap, and the
+        batch is cut to MMRAG_FILTER_BITMAP_BYTES of bitmaps per launch.  Under "prefer" the dense leg is unchanged."""
         from .config import settings
-        from .lexical import rows_dot, rrf_fuse
+        from .lexical import parse_phrase_mode, parse_slop, rows_dot, rrf_fuse
+
+        if phrases:
+            slop, phrase_mode = parse_slop(slop), parse_phrase_mode(phrase_mode)
 
         texts = list(query_texts)
         self._need_plane("hybrid_query")
@@ -2450,8 +2493,18 @@ class VectorIndex:
                 q = self._pack_queries(query_embeddings, check_norm)
             if q.shape[0] != len(texts):
                 raise ValueError(f"{q.shape[0]} query embeddings for {len(texts)} query texts")
-            d_scores, d_rows = self._launch_search(query_embeddings, C, where, check_norm)
-            l_scores, l_rows, corrections = self._lexical_search(texts, C, where, fuzzy)
+            report = None
+            if phrases:
+                want = phrase_mode == "require"
+                l_scores, l_rows, corrections, report, maps = self._lexical_search(texts, C, where, fuzzy, True, slop,
+                                                                                  phrase_mode, bitmaps=want)
+                if want and maps is not None:
+                    d_scores, d_rows = self._launch_phrase_dense(query_embeddings, q, C, where, check_norm, report, maps)
+                else:
+                    d_scores, d_rows = self._launch_search(query_embeddings, C, where, check_norm)
+            else:
+                d_scores, d_rows = self._launch_search(query_embeddings, C, where, check_norm)
+                l_scores, l_rows, corrections = self._lexical_search(texts, C, where, fuzzy)
             tables = self._tables()
             d_s, d_r = d_scores.cpu(), d_rows.cpu()
             l_s, l_r = l_scores.cpu().tolist(), l_rows.cpu().tolist()
@@ -2481,7 +2534,63 @@ class VectorIndex:
             out["distances"].append([dist_dense[b][dpos[r]] if r in dpos else extra[(b, r)] for r in rows])
         if corrections is not None:
             out["corrections"] = corrections
+        if report is not None:
+            out["phrases"] = report
         return out
+
+    def _launch_phrase_dense(self, query_embeddings, q, k: int, where, check_norm: bool, report, maps):
+        """the dense leg of a hybrid query under phrase_mode="require" (caller holds the lock): device (scores, rows)
+        [B, k].  Query b with phrases is answered from the rows of maps[b] (already alive and passing `where`: the match
+        kernel writes no other row); the queries without phrases share ONE bitmap, alive AND `where`.  One filtered scan
+        (mmrag_filtered_topk) per MMRAG_FILTER_BITMAP_BYTES of bitmaps."""
+        from .config import settings
+
+        B = q.shape[0]
+        with_ph = [b for b in range(B) if report[b]]
+        without = [b for b in range(B) if not report[b]]
+        W = _native.filter_words(self._n)
+        per_launch = max(1, int(settings.MMRAG_FILTER_BITMAP_BYTES) // max(4 * W, 1))
+        scores = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        rows_o = torch.empty((B, k), dtype=torch.int64, device=self.device)
+        shared = None
+        if without:
+            bits = self._where_bits(where)
+            if bits is None:
+                shared = torch.full((1, W), -1, dtype=torch.int32, device=self.device)
+                if self._n % 32 and W:      # bits at and past n stay zero, as mmrag_filter_eval leaves them
+                    shared[0, self._n // 32] = (1 << (self._n % 32)) - 1
+                shared[0, (self._n + 31) // 32:] = 0
+            else:
+                shared = torch.zeros((1, W), dtype=torch.int32, device=self.device)
+                m = min(W, bits.numel())
+                shared[0, :m] = bits[:m]
+        # launches: the shared bitmap rides with the first chunk of phrase queries
+        order = without + with_ph
+        at = 0
+        while at < len(order):
+            mine, vis, foq = [], [], []
+            if at < len(without):
+                mine = without[at:]
+                vis.append(shared)
+                foq = [0] * len(mine)
+                at = len(without)
+            room = per_launch - len(vis)
+            take = order[at: at + max(room, 0 if vis else 1)]
+            for b in take:
+                foq.append(len(vis))
+                vis.append(maps[b: b + 1])
+                mine.append(b)
+            at += len(take)
+            vb = torch.cat(vis, 0).contiguous()
+            whole = mine == list(range(B))
+            pick = None if whole else torch.tensor(mine, device=self.device)
+            need = _native.filtered_topk_workspace_bytes(len(mine), self._n, k)
+            ss, rr = _native.filtered_topk(q if whole else q[pick].contiguous(), self._full, self._n, self.dim, k, foq,
+                                           vb, workspace=self._workspace("_filtered_ws", need))
+            if whole:
+                return ss, rr
+            scores[pick], rows_o[pick] = ss, rr
+        return scores, rows_o
 
     # ------------------------------------------------------------------ learned sparse ----
     def enable_sparse(self, vocab_size: int):

@@ -13,6 +13,10 @@ Scoring contract (the tests pin it against tests/bm25_ref.py):
 Typo tolerance (opt-in, `fuzzy=`; the tests pin it against tests/fuzzy_ref.py): a query term no live row holds is
 replaced by its closest indexed term -- optimal-string-alignment distance within 0..2 edits, then larger live df, then
 lower id -- found on the device over the lexicon's strings (csrc/fuzzy.hip); the list then goes to the same scoring.
+
+Phrase queries (opt-in, `phrases=`; the tests pin them against tests/phrase_ref.py): a quoted segment of the query is a
+phrase, matched against the token positions of every row (the positions plane, built by the first phrase query) by
+csrc/phrase.hip and scored as one more BM25 clause; under phrase_mode="require" only rows holding every phrase are hits.
 """
 from __future__ import annotations
 
@@ -108,6 +112,30 @@ class Lexicon:
             _native._check(st, "mmrag_lexicon_analyze_batch")
             total = int(out_off[n])
             return out_off, ids[:total], tfs[:total], dl
+
+    def analyze_positions(self, texts: Sequence[Optional[str]]):
+        """analyze_batch(texts, LEX_DOCUMENTS) and a fifth array: every pair's token positions (0-based token indices),
+        ascending, concatenated in pair order -- sum(dl) int32 (mmrag_lexicon_analyze_positions)"""
+        cps, offs = _utf32([t or "" for t in texts])
+        n = len(texts)
+        out_off = np.zeros(n + 1, np.int64)
+        dl = np.zeros(n, np.int32)
+        needed = c_int64(0)
+        cap = pos_cap = int(cps.size) + 1
+        while True:
+            ids = np.empty(cap, np.int32)
+            tfs = np.empty(cap, np.int32)
+            pos = np.empty(pos_cap, np.int32)
+            st = self._lib.mmrag_lexicon_analyze_positions(self._h, cps.ctypes.data, offs.ctypes.data, n,
+                                                           out_off.ctypes.data, ids.ctypes.data, tfs.ctypes.data,
+                                                           dl.ctypes.data, cap, pos.ctypes.data, pos_cap, byref(needed),
+                                                           self.n_threads)
+            if st == 2 and (int(out_off[n]) > cap or int(needed.value) > pos_cap):   # MMRAG_EWORKSPACE (rare)
+                cap, pos_cap = max(cap, int(out_off[n])), max(pos_cap, int(needed.value))
+                continue
+            _native._check(st, "mmrag_lexicon_analyze_positions")
+            total = int(out_off[n])
+            return out_off, ids[:total], tfs[:total], dl, pos[: int(needed.value)]
 
     def export(self, first_id: int, count: int):
         """(offsets int64 [count+1] from 0, code points uint32) of terms first_id .. first_id + count"""
@@ -210,6 +238,66 @@ def rewrite_terms(terms: Sequence[Tuple[int, str]], live: Sequence[bool], best: 
     return ids, corrections
 
 
+MAX_PHRASE_TERMS = 8       # MMRAG_MAX_PHRASE_TERMS
+MAX_QUERY_PHRASES = 4      # MMRAG_MAX_QUERY_PHRASES
+MAX_PHRASE_SLOP = 16       # MMRAG_MAX_PHRASE_SLOP
+PHRASE_MODES = ("require", "prefer")
+
+
+def split_phrases(text: Optional[str]) -> Tuple[str, List[str]]:
+    """(the text outside the quotes, the quoted segments in order) of a query under `phrases`: a segment between two
+    '"' (U+0022), or between U+201C and U+201D, is a phrase; an opening quote without its closing one is ordinary
+    punctuation.  The scan runs left to right and a segment ends at the first closing quote of its own kind, so quotes
+    do not nest.  Each segment leaves a space in the loose text."""
+    text = text or ""
+    loose: List[str] = []
+    segments: List[str] = []
+    i = 0
+    while i < len(text):
+        ch = text[i]
+        close = '"' if ch == '"' else "\u201d" if ch == "\u201c" else None
+        j = text.find(close, i + 1) if close else -1
+        if j < 0:
+            loose.append(ch)
+            i += 1
+            continue
+        segments.append(text[i + 1: j])
+        loose.append(" ")
+        i = j + 1
+    return "".join(loose), segments
+
+
+def query_phrases(text: Optional[str]) -> Tuple[str, List[Tuple[str, List[str]]]]:
+    """(loose text, [(segment text, its terms)]) of one query under `phrases` (pure Python): the distinct phrases in
+    order of appearance, each segment analysed like a document with repeats kept.  An empty segment is ignored and equal
+    term sequences are one phrase; a segment of more than MAX_PHRASE_TERMS terms or more than MAX_QUERY_PHRASES distinct
+    phrases raise ValueError."""
+    loose, segments = split_phrases(text)
+    mine: List[Tuple[str, List[str]]] = []
+    for seg in segments:
+        terms = analyze(seg)
+        if not terms or any(terms == t for _, t in mine):
+            continue
+        if len(terms) > MAX_PHRASE_TERMS:
+            raise ValueError(f"a phrase holds at most {MAX_PHRASE_TERMS} terms: {seg!r} has {len(terms)}")
+        mine.append((seg, terms))
+    if len(mine) > MAX_QUERY_PHRASES:
+        raise ValueError(f"a query holds at most {MAX_QUERY_PHRASES} distinct phrases, not {len(mine)}")
+    return loose, mine
+
+
+def parse_slop(slop) -> int:
+    if isinstance(slop, bool) or not isinstance(slop, (int, np.integer)) or not 0 <= int(slop) <= MAX_PHRASE_SLOP:
+        raise ValueError(f"slop must be an integer in 0..{MAX_PHRASE_SLOP}, not {slop!r}")
+    return int(slop)
+
+
+def parse_phrase_mode(mode) -> str:
+    if mode not in PHRASE_MODES:
+        raise ValueError(f"phrase_mode must be 'require' or 'prefer', not {mode!r}")
+    return mode
+
+
 def _grow(t: torch.Tensor, need: int) -> torch.Tensor:
     if t.numel() >= need:
         return t
@@ -256,6 +344,14 @@ class LexicalIndex:
         self._tp_total = 0
         self._fuzzy_ws = None
         self.term_plane_syncs = 0         # how many times terms were uploaded (tests, tools)
+        # the positions plane (phrase queries): built by enable_positions(), None until then
+        self._pos_off = None              # int64 [n_postings + 1]: prefix sum of tf over the forward postings
+        self._pos = None                  # int32 [sum(dl)]: each forward posting's token positions, ascending
+        self._pos_total = 0
+        self._counts_host = None          # postings per term of the current CSR (driver choice), read once per build
+        self._counts_build = -1
+        self._phrase_ws = None
+        self.position_builds = 0          # how many times the plane was built from documents (tests, tools)
 
     @property
     def n_terms(self) -> int:
@@ -273,14 +369,24 @@ class LexicalIndex:
         m = len(documents)
         if m == 0:
             return
+        if self.positions_enabled:
+            off, ids, tfs, dl, pos = self.lexicon.analyze_positions(documents)
+            self.append_postings(off, ids, tfs, dl, pos)
+            return
         off, ids, tfs, dl = self.lexicon.analyze_batch(documents, LEX_DOCUMENTS)
         self.append_postings(off, ids, tfs, dl)
 
-    def append_postings(self, off: np.ndarray, ids: np.ndarray, tfs: np.ndarray, dl: np.ndarray):
+    def append_postings(self, off: np.ndarray, ids: np.ndarray, tfs: np.ndarray, dl: np.ndarray,
+                        positions: Optional[np.ndarray] = None):
         """append already analysed rows (offsets [m+1] from 0, term ids sorted within each row, distinct): the form
-        `Lexicon.analyze_batch(..., LEX_DOCUMENTS)` returns; tools feed synthetic corpora through it"""
+        `Lexicon.analyze_batch(..., LEX_DOCUMENTS)` returns; tools feed synthetic corpora through it.  `positions`
+        (the fifth array of `Lexicon.analyze_positions`) is needed once the positions plane exists."""
         m = int(dl.size)
         p0 = self.n_postings
+        if self.positions_enabled:
+            if positions is None:
+                raise ValueError("the positions plane is enabled: rows need their token positions (append_sequences)")
+            self._append_positions(p0, np.asarray(tfs, np.int64), np.ascontiguousarray(positions, np.int32))
         if ids.size:
             self._max_term = max(self._max_term, int(ids.max()))
         new_off = p0 + np.asarray(off, np.int64)
@@ -339,6 +445,17 @@ class LexicalIndex:
             self._fwd_tf[: src.size].copy_(torch.from_numpy(tf[src]))
         if self.n:
             self._dl[: self.n].copy_(torch.from_numpy(self._dl_host))
+        if self.positions_enabled:
+            pos_off = self._pos_off[: P + 1].cpu().numpy()
+            pos = self._pos[: self._pos_total].cpu().numpy()
+            plens = pos_off[src + 1] - pos_off[src]
+            new_pos_off = np.zeros(src.size + 1, np.int64)
+            np.cumsum(plens, out=new_pos_off[1:])
+            psrc = np.repeat(pos_off[src] - new_pos_off[:-1], plens) + np.arange(int(new_pos_off[-1]), dtype=np.int64)
+            self._pos_off[: src.size + 1].copy_(torch.from_numpy(new_pos_off))
+            if psrc.size:
+                self._pos[: psrc.size].copy_(torch.from_numpy(pos[psrc]))
+            self._pos_total = int(new_pos_off[-1])
         self._csr_n = -1
 
     def _ensure_csr(self):
@@ -463,14 +580,19 @@ class LexicalIndex:
         return q_off, np.asarray(q_terms, np.int32), corrections
 
     def topk(self, query_texts: Sequence[str], k: int, alive_bits: Optional[torch.Tensor] = None,
-             k1: Optional[float] = None, b: Optional[float] = None, fuzzy=None):
+             k1: Optional[float] = None, b: Optional[float] = None, fuzzy=None, phrases=None, slop: int = 0,
+             phrase_mode: str = "require", bitmaps: bool = False):
         """(scores [B, k] float32 desc, rows [B, k] int64; (-inf, -1) padding) on the device.  With `fuzzy`
         ("auto", True or 0..2) the query terms BM25 would drop are corrected first (analyze_queries_fuzzy) and the
-        corrections come back as a third value."""
+        corrections come back as a third value.  With `phrases` quoted segments are phrases (parse_phrases) and the
+        call returns topk_phrases' five values: scores, rows, corrections (None without `fuzzy`), the per-query phrase
+        report and, for `bitmaps`, the per-query row bitmaps inside the last value."""
         if len(query_texts) == 0:
             raise ValueError("no query texts")
         if not 1 <= k <= _native.MAX_K_DEEP:
             raise ValueError(f"n_results must be in 1..{_native.MAX_K_DEEP} for lexical search")
+        if phrases:
+            return self.topk_phrases(query_texts, k, alive_bits, k1, b, fuzzy, slop, phrase_mode, bitmaps)
         if parse_fuzzy(fuzzy) is not None:
             q_off, q_terms, corrections = self.analyze_queries_fuzzy(query_texts, fuzzy)
             return self.topk_ids(q_off, q_terms, k, alive_bits, k1, b) + (corrections,)
@@ -512,6 +634,272 @@ class LexicalIndex:
         """live df per term (tests)"""
         return self._df[: self.n_terms].cpu().numpy()
 
+    # ------------------------------------------------------------------ positions plane / phrase queries ----
+    documents_source = None   # set by the owner: a callable returning the stored documents in row order
+
+    @property
+    def positions_enabled(self) -> bool:
+        return self._pos_off is not None
+
+    @property
+    def positions_bytes(self) -> int:
+        """device bytes of the positions plane (0 until it exists)"""
+        if not self.positions_enabled:
+            return 0
+        return self._pos_off.numel() * 8 + self._pos.numel() * 4
+
+    def enable_positions(self):
+        """Build the positions plane: re-analyse the stored documents in row order (dead rows included, so the rows
+        stay aligned with the forward log; the lexicon already holds every term, so the pairs come out as they stand
+        there).  From then on append, compact and reset keep it current; a delete needs nothing.  Runs by itself on
+        the first phrase query; an index that never sees one allocates none of it."""
+        if self.positions_enabled:
+            return
+        dev = self.device
+        self._pos_off = torch.zeros(4097, dtype=torch.int64, device=dev)
+        self._pos = torch.zeros(4096, dtype=torch.int32, device=dev)
+        self._pos_total = 0
+        if self.n == 0:
+            return
+        docs = self.documents_source() if self.documents_source is not None else None
+        if docs is None or len(docs) != self.n:
+            self._pos_off = self._pos = None
+            raise ValueError("the positions plane needs the stored documents of every row: rows appended as bare "
+                             "postings have no positions (use append_sequences from the start)")
+        step = 65536
+        p0 = 0
+        for lo in range(0, self.n, step):
+            off, ids, tfs, dl, pos = self.lexicon.analyze_positions(docs[lo: lo + step])
+            hi = lo + int(dl.size)
+            if (not np.array_equal(off + self._off_host[lo], self._off_host[lo: hi + 1])
+                    or not np.array_equal(dl, self._dl_host[lo:hi])):
+                self._pos_off = self._pos = None
+                raise ValueError("the stored documents do not match the forward log")
+            self._append_positions(p0, tfs.astype(np.int64), pos)
+            p0 += int(ids.size)
+        self.position_builds += 1
+
+    def _append_positions(self, p0: int, tfs: np.ndarray, positions: np.ndarray):
+        """forward postings p0 .. p0 + len(tfs) stand at `positions` (tf each, in posting order)"""
+        if int(tfs.sum()) != int(positions.size):
+            raise ValueError(f"{positions.size} positions for postings with {int(tfs.sum())} occurrences")
+        ends = self._pos_total + np.cumsum(tfs, dtype=np.int64)
+        total = int(ends[-1]) if ends.size else self._pos_total
+        if total >= 2 ** 31:
+            raise ValueError(f"{total} stored tokens exceed the positions plane's 2^31 - 1")
+        self._pos_off = _grow(self._pos_off, p0 + tfs.size + 1)
+        self._pos = _grow(self._pos, max(total, 1))
+        if ends.size:
+            self._pos_off[p0 + 1: p0 + 1 + ends.size].copy_(torch.from_numpy(ends))
+        if positions.size:
+            self._pos[self._pos_total: total].copy_(torch.from_numpy(positions))
+        self._pos_total = total
+
+    def append_sequences(self, seqs: Sequence[Sequence[int]]):
+        """append rows given as raw term-id sequences (token order, repeats kept): postings and positions are derived
+        on the host and the lexicon is bypassed -- append_postings' twin for tests and tools.  Enables the positions
+        plane on an empty index; a non-empty one must have it already."""
+        if not self.positions_enabled:
+            if self.n:
+                raise ValueError("append_sequences needs the positions plane from the first row on")
+            self.enable_positions()
+        lens = np.fromiter((len(s) for s in seqs), np.int64, len(seqs))
+        m = int(lens.size)
+        flat = (np.concatenate([np.asarray(s, np.int64).reshape(-1) for s in seqs]) if m else np.zeros(0, np.int64))
+        if flat.size and (flat.min() < 0 or flat.max() >= 2 ** 31 - 1):
+            raise ValueError("term ids must be in 0..2^31-2")
+        starts = np.zeros(m + 1, np.int64)
+        np.cumsum(lens, out=starts[1:])
+        rows = np.repeat(np.arange(m, dtype=np.int64), lens)
+        where = np.arange(flat.size, dtype=np.int64) - np.repeat(starts[:-1], lens)
+        order = np.lexsort((where, flat, rows))
+        rows_s, terms_s = rows[order], flat[order]
+        first = np.ones(flat.size, bool)
+        first[1:] = (rows_s[1:] != rows_s[:-1]) | (terms_s[1:] != terms_s[:-1])
+        at = np.nonzero(first)[0]
+        tfs = np.diff(np.append(at, flat.size)).astype(np.int32)
+        off = np.zeros(m + 1, np.int64)
+        np.cumsum(np.bincount(rows_s[at], minlength=m), out=off[1:])
+        self.append_postings(off, terms_s[at].astype(np.int32), tfs, lens.astype(np.int32),
+                             where[order].astype(np.int32))
+
+    def _posting_counts(self) -> np.ndarray:
+        """postings per term of the current CSR on the host (read once per CSR build): the driver choice"""
+        term_off, _, _ = self._ensure_csr()
+        if self._counts_build != self.csr_builds:
+            self._counts_host = np.diff(term_off.cpu().numpy())
+            self._counts_build = self.csr_builds
+        return self._counts_host
+
+    def parse_phrases(self, query_texts: Sequence[Optional[str]]):
+        """The query language of `phrases` (query_phrases) with the lexicon's ids: per query (loose text,
+        [(segment text, [term strings], (term ids))]), id -1 for a term the lexicon does not hold.  The string -> id map
+        comes from the native analyzer (mmrag_lexicon_analyze_terms); nothing is added to the lexicon."""
+        split = [query_phrases(t) for t in query_texts]
+        segs = [seg for _, mine in split for seg, _ in mine]
+        ids_of: Dict[str, int] = {}
+        if segs:
+            off, ids, cp_off, cps = self.lexicon.analyze_terms(segs)
+            for j in range(int(ids.size)):
+                ids_of[_str_of(cps[cp_off[j]: cp_off[j + 1]])] = int(ids[j])
+        return [(loose, [(seg, terms, tuple(ids_of.get(t, -1) for t in terms)) for seg, terms in mine])
+                for loose, mine in split]
+
+    def match_phrases(self, phrases: Sequence[Sequence[int]], slop: int = 0,
+                      alive_bits: Optional[torch.Tensor] = None, q_phrases: Optional[Sequence[Sequence[int]]] = None,
+                      bitmaps: bool = False) -> Dict[str, object]:
+        """mmrag_phrase_match for `phrases` (term-id sequences, -1 = unknown term): a dict with
+          known     [NP] bool (host): every term in the lexicon with live df >= 1
+          drivers   [NP] int32 (host): the driver term of each known phrase (fewest postings, ties to the earlier
+                    position), -1 for the others
+          ptf_off   [NP + 1] int64 (host) and ptf (device int32): tf_p per posting of each driver's CSR list
+          rows      [NP] int32 (device): rows with tf_p >= 1
+          bitmaps   with `bitmaps`, device int32 [B, filter_words(n)]: query i's rows holding every phrase of
+                    q_phrases[i] (indices into `phrases`); all rows below n for a query without phrases
+        and the device tables ("tables") that topk_phrase_ids hands to the scoring call."""
+        slop = parse_slop(slop)
+        if not self.positions_enabled:
+            raise ValueError("phrase matching needs the positions plane (enable_positions)")
+        phrases = [tuple(int(t) for t in ph) for ph in phrases]
+        NP = len(phrases)
+        for ph in phrases:
+            if not 1 <= len(ph) <= MAX_PHRASE_TERMS:
+                raise ValueError(f"a phrase holds 1..{MAX_PHRASE_TERMS} terms, not {len(ph)}")
+            if max(ph) >= self.n_terms:
+                raise ValueError("phrase term id outside the lexicon")
+        q_phrases = [list(q) for q in (q_phrases if q_phrases is not None else [])]
+        B = len(q_phrases)
+        for q in q_phrases:
+            if len(q) > MAX_QUERY_PHRASES or len(set(q)) != len(q) or any(not 0 <= i < NP for i in q):
+                raise ValueError(f"a query holds at most {MAX_QUERY_PHRASES} distinct phrases of the batch")
+        counts = self._posting_counts()
+        term_off, post_row, _ = self._csr
+        dev = self.device
+        flat = np.asarray([t for ph in phrases for t in ph], np.int64)
+        known_t = flat >= 0
+        if known_t.any():
+            df = self._df[torch.from_numpy(flat[known_t]).to(dev)].cpu().numpy()
+            known_t[known_t] = df >= 1
+        ph_off = np.zeros(NP + 1, np.int32)
+        np.cumsum([len(ph) for ph in phrases], out=ph_off[1:])
+        known = np.asarray([bool(known_t[ph_off[i]: ph_off[i + 1]].all()) for i in range(NP)], bool)
+        drivers = np.full(NP, -1, np.int32)
+        ptf_off = np.zeros(NP + 1, np.int64)
+        for i, ph in enumerate(phrases):
+            if known[i]:
+                drivers[i] = ph[int(np.argmin([counts[t] for t in ph]))]     # argmin: ties to the earlier position
+            ptf_off[i + 1] = ptf_off[i] + (int(counts[drivers[i]]) if known[i] else 0)
+        longest = int(max((counts[d] for d in drivers if d >= 0), default=0))
+        q_off = np.zeros(B + 1, np.int32)
+        np.cumsum([len(q) for q in q_phrases], out=q_off[1:])
+        blob = np.concatenate([ph_off, np.maximum(flat, 0).astype(np.int32), np.zeros(1, np.int32), drivers, q_off,
+                               np.asarray([i for q in q_phrases for i in q], np.int32), np.zeros(1, np.int32)])
+        d_blob = torch.from_numpy(blob).to(dev)
+        d_ptf_off = torch.from_numpy(ptf_off).to(dev)
+        base = d_blob.data_ptr()
+        at_terms = 4 * (NP + 1)
+        at_drv = at_terms + 4 * (int(flat.size) + 1)
+        at_qoff = at_drv + 4 * NP
+        at_qph = at_qoff + 4 * (B + 1)
+        tables = {"blob": d_blob, "ph_off": base, "ph_terms": base + at_terms, "ph_driver": base + at_drv,
+                  "q_ph_off": base + at_qoff, "q_ph": base + at_qph, "ptf_off": d_ptf_off, "n_phrases": NP,
+                  "max_terms": max((len(ph) for ph in phrases), default=0),
+                  "max_phrases": max((len(q) for q in q_phrases), default=0)}
+        ptf = torch.empty(max(int(ptf_off[-1]), 1), dtype=torch.int32, device=dev)
+        rows = torch.zeros(max(NP, 1), dtype=torch.int32, device=dev)
+        maps = None
+        if bitmaps:
+            maps = torch.zeros((B, _native.filter_words(self.n)), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _native._check(_native.lib().mmrag_phrase_match(
+                self._fwd_off.data_ptr(), self._fwd_term.data_ptr(), self._pos_off.data_ptr(), self._pos.data_ptr(),
+                self.n, term_off.data_ptr(), post_row.data_ptr(), tables["ph_off"], tables["ph_terms"],
+                tables["ph_driver"], d_ptf_off.data_ptr(), NP, tables["max_terms"], longest, slop,
+                alive_bits.data_ptr() if alive_bits is not None else None, ptf.data_ptr(), rows.data_ptr(),
+                tables["q_ph_off"], tables["q_ph"], B if bitmaps else 0, tables["max_phrases"],
+                maps.data_ptr() if maps is not None and maps.numel() else None, self._stream()), "mmrag_phrase_match")
+        return {"known": known, "drivers": drivers, "ptf_off": ptf_off, "ptf": ptf, "rows": rows[:NP], "bitmaps": maps,
+                "tables": tables}
+
+    def topk_phrase_ids(self, q_off: np.ndarray, q_terms: np.ndarray, q_phrases: Sequence[Sequence[Sequence[int]]],
+                        k: int, alive_bits: Optional[torch.Tensor] = None, k1: Optional[float] = None,
+                        b: Optional[float] = None, slop: int = 0, phrase_mode: str = "require",
+                        bitmaps: bool = False):
+        """topk_ids with phrases: q_phrases[i] lists query i's phrases as term-id sequences (repeats kept, -1 = unknown
+        term).  Equal phrases of the batch are matched once.  Returns (scores, rows, info): info is match_phrases'
+        dict plus "phrases" (the distinct id sequences) and "q_phrases" (per query, indices into them)."""
+        from .config import settings
+
+        k1 = settings.MMRAG_BM25_K1 if k1 is None else k1
+        b = settings.MMRAG_BM25_B if b is None else b
+        mode = parse_phrase_mode(phrase_mode)
+        B = int(q_off.size) - 1
+        if len(q_phrases) != B:
+            raise ValueError(f"{len(q_phrases)} phrase lists for {B} queries")
+        if not 1 <= k <= _native.MAX_K_DEEP:
+            raise ValueError(f"n_results must be in 1..{_native.MAX_K_DEEP} for lexical search")
+        q_off = np.ascontiguousarray(q_off, np.int32)
+        q_terms = np.ascontiguousarray(q_terms, np.int32)
+        if q_terms.size and (q_terms.min() < 0 or q_terms.max() >= self.n_terms):
+            raise ValueError("query term id outside the lexicon")
+        index_of: Dict[Tuple[int, ...], int] = {}
+        per_query: List[List[int]] = []
+        for phs in q_phrases:
+            mine: List[int] = []
+            for ph in phs:
+                i = index_of.setdefault(tuple(int(t) for t in ph), len(index_of))
+                if i not in mine:
+                    mine.append(i)
+            per_query.append(mine)
+        info = self.match_phrases(list(index_of), slop, alive_bits, per_query, bitmaps)
+        t = info["tables"]
+        term_off, post_row, post_tf = self._csr
+        dq_off = torch.from_numpy(q_off).to(self.device)
+        dq_terms = torch.from_numpy(np.concatenate([q_terms, np.zeros(1, np.int32)])).to(self.device)
+        L = _native.lib()
+        need = int(L.mmrag_bm25_phrase_topk_workspace_bytes(B, self.n, k))
+        if self._phrase_ws is None or self._phrase_ws.numel() < need:
+            self._phrase_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        out_s = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        out_r = torch.empty((B, k), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _native._check(L.mmrag_bm25_phrase_topk(
+                term_off.data_ptr(), post_row.data_ptr(), post_tf.data_ptr(), self._dl.data_ptr(), self._df.data_ptr(),
+                self.n_terms, self.n, dq_off.data_ptr(), dq_terms.data_ptr(), B, t["q_ph_off"], t["q_ph"], t["ph_off"],
+                t["ph_terms"], t["ph_driver"], t["ptf_off"].data_ptr(), info["ptf"].data_ptr(), t["n_phrases"],
+                t["max_terms"], t["max_phrases"], 1 if mode == "require" else 0, self.n_live, self.sum_dl, float(k1),
+                float(b), k, alive_bits.data_ptr() if alive_bits is not None else None, out_s.data_ptr(),
+                out_r.data_ptr(), self._phrase_ws.data_ptr(), self._phrase_ws.numel(), self._stream()),
+                "mmrag_bm25_phrase_topk")
+        info["phrases"] = list(index_of)
+        info["q_phrases"] = per_query
+        return out_s, out_r, info
+
+    def topk_phrases(self, query_texts: Sequence[str], k: int, alive_bits: Optional[torch.Tensor] = None,
+                     k1: Optional[float] = None, b: Optional[float] = None, fuzzy=None, slop: int = 0,
+                     phrase_mode: str = "require", bitmaps: bool = False):
+        """topk under `phrases` (see topk): (scores, rows, corrections or None, report, info).  report[i] lists query
+        i's phrases as {"text", "terms", "known", "rows"}; info is None when no query of the batch has a phrase (the
+        call is then topk's, and the positions plane is not touched), else topk_phrase_ids' dict."""
+        slop, mode = parse_slop(slop), parse_phrase_mode(phrase_mode)
+        parsed = self.parse_phrases(query_texts)
+        loose = [t for t, _ in parsed]
+        corrections = None
+        if parse_fuzzy(fuzzy) is not None:     # quoting means "exactly this": only the loose terms are rewritten
+            q_off, q_terms, corrections = self.analyze_queries_fuzzy(loose, fuzzy)
+        else:
+            q_off, q_terms = self.analyze_queries(loose)
+        if not any(phs for _, phs in parsed):
+            scores, rows = self.topk_ids(q_off, q_terms, k, alive_bits, k1, b)
+            return scores, rows, corrections, [[] for _ in parsed], None
+        self.enable_positions()
+        scores, rows, info = self.topk_phrase_ids(q_off, q_terms, [[ids for _, _, ids in phs] for _, phs in parsed], k,
+                                                  alive_bits, k1, b, slop, mode, bitmaps)
+        held = info["rows"].cpu().numpy()
+        report = [[{"text": seg, "terms": list(terms), "known": bool(info["known"][i]), "rows": int(held[i])}
+                   for (seg, terms, _), i in zip(phs, mine)] for (_, phs), mine in zip(parsed, info["q_phrases"])]
+        return scores, rows, corrections, report, info
+
 
 def rows_dot(q: torch.Tensor, corpus: torch.Tensor, d: int, qi: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
     """out[i] = <q[qi[i]], corpus[rows[i]]> over the first d columns, float32 (mmrag_rows_dot)"""
@@ -540,6 +928,17 @@ def fuzzy_limits() -> Dict[str, int]:
     v = [c_int(0) for _ in range(5)]
     _native._check(_native.lib().mmrag_internal_fuzzy_limits(*[byref(x) for x in v]), "mmrag_internal_fuzzy_limits")
     return dict(zip(("term_tile", "pattern_tile", "max_len", "max_expansions", "stage_cps"), (int(x.value) for x in v)))
+
+
+def phrase_limits() -> Dict[str, int]:
+    """csrc/phrase.hip's partition sizes (mmrag_internal_phrase_limits; tests put their seams on them)"""
+    v = [c_int(0) for _ in range(4)]
+    _native._check(_native.lib().mmrag_internal_phrase_limits(*[byref(x) for x in v]), "mmrag_internal_phrase_limits")
+    return dict(zip(("match_block", "lane_starts", "wave_lanes", "score_rows"), (int(x.value) for x in v)))
+
+
+def bm25_phrase_workspace_bytes(B: int, n: int, k: int) -> int:
+    return int(_native.lib().mmrag_bm25_phrase_topk_workspace_bytes(B, n, k))
 
 
 def lexical_limits() -> Dict[str, int]:
@@ -588,6 +987,20 @@ def declare(lib):
     # test-only export (not in include/mmrag.h): the sizes at which the kernels change path
     lib.mmrag_internal_lexical_limits.restype = c_int
     lib.mmrag_internal_lexical_limits.argtypes = [c_void_p] * 5
+    lib.mmrag_internal_phrase_limits.restype = c_int
+    lib.mmrag_internal_phrase_limits.argtypes = [c_void_p] * 4
+    lib.mmrag_lexicon_analyze_positions.restype = c_int
+    lib.mmrag_lexicon_analyze_positions.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int]
+    lib.mmrag_phrase_match.restype = c_int
+    lib.mmrag_phrase_match.argtypes = [c_void_p] * 4 + [c_int64] + [c_void_p] * 6 + [c_int, c_int, c_int64, c_int] + \
+        [c_void_p] * 5 + [c_int, c_int, c_void_p, c_void_p]
+    lib.mmrag_bm25_phrase_topk_workspace_bytes.restype = c_size_t
+    lib.mmrag_bm25_phrase_topk_workspace_bytes.argtypes = [c_int, c_int64, c_int]
+    lib.mmrag_bm25_phrase_topk.restype = c_int
+    lib.mmrag_bm25_phrase_topk.argtypes = [c_void_p] * 5 + [c_int, c_int64, c_void_p, c_void_p, c_int] + \
+        [c_void_p] * 7 + [c_int] * 4 + [c_int64, c_int64, c_float, c_float, c_int] + [c_void_p] * 4 + \
+        [c_size_t, c_void_p]
     lib.mmrag_rows_dot.restype = c_int
     lib.mmrag_rows_dot.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p,
                                    c_void_p]

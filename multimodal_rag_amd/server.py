@@ -64,6 +64,12 @@ class QueryRequest(BaseModel):  # api.py:161-164
     # indexed term (csrc/fuzzy.hip) before BM25 scores; the response then carries `corrections`, a list of
     # {"term", "matched", "edits"}.  Unset: the MMRAG_LEXICAL_FUZZY setting
     fuzzy: Optional[Any] = None
+    # with `hybrid` and the lexical leg: phrase queries -- a segment of the question between two '"' (or curly quotes)
+    # is a phrase of 1..8 terms every returned chunk must hold (csrc/phrase.hip), its terms at most `slop` (0..16) other
+    # tokens apart; the response then carries `phrases`, a list of {"text", "terms", "known", "rows"}.  Unset: the
+    # MMRAG_LEXICAL_PHRASES / MMRAG_LEXICAL_SLOP settings
+    phrases: Optional[bool] = None
+    slop: Optional[int] = None
     # not in the reference: hits by learned sparse retrieval alone (EmbeddingManager.sparse_query: the question expanded
     # by the masked-LM of MMRAG_SPARSE_ENCODER_DIR, scored exactly against the stored sparse vectors); each source
     # carries its `sparse_score` and, with `explain`, `matched_terms`: the shared vocabulary strings with their
@@ -352,6 +358,8 @@ class QueryResponse(BaseModel):  # api.py:167-170
     answerable: Optional[bool] = None
     # `fuzzy` only
     corrections: Optional[List[dict]] = None
+    # `phrases` only
+    phrases: Optional[List[dict]] = None
 
 
 class UploadResponse(BaseModel):  # api.py:173-179
@@ -524,7 +532,8 @@ class Pipeline:
                      filter_dict: Optional[Dict[str, Any]] = None, late: bool = False,
                      passage_tokens: Optional[int] = None, sparse: bool = False,
                      hybrid_leg: Optional[str] = None, extractive: bool = False,
-                     reader: Optional[str] = None, fuzzy: Any = None) -> Optional[dict]:
+                     reader: Optional[str] = None, fuzzy: Any = None, phrases: Optional[bool] = None,
+                     slop: Optional[int] = None) -> Optional[dict]:
         """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
         max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the re-ranker's best top_k (`rerank_method` "cross" or "late",
         default MMRAG_RERANK_METHOD; `explain`: late interaction's per-token matches on every source).  `hybrid`: from
@@ -551,7 +560,9 @@ class Pipeline:
         EmbeddingManager.read_answers over the hits' raw text passages -- the result gains `answers` and `answerable`,
         every source its `answer_spans`; "answer": the answer is the best span's text (NO_ANSWER_FOUND when the hits do
         not answer the question), no generator call.  `fuzzy` (with `hybrid` and the lexical leg): the BM25 leg is
-        typo-tolerant (EmbeddingManager.hybrid_query) and the result carries the `corrections` it made"""
+        typo-tolerant (EmbeddingManager.hybrid_query) and the result carries the `corrections` it made.  `phrases` /
+        `slop` (with `hybrid` and the lexical leg): quoted segments of the question are phrases every hit must hold,
+        and the result carries the `phrases` report"""
         multi = variants is not None
         sparse_leg = hybrid and hybrid_leg == "sparse"
         riding = passage_tokens is not None and rerank and rerank_method == "late"
@@ -576,7 +587,9 @@ class Pipeline:
         elif sparse_leg:
             search = functools.partial(self.embedder.hybrid_query, leg="sparse", **only)
         elif hybrid:
-            search = functools.partial(self.embedder.hybrid_query, **only, **({} if fuzzy is None else {"fuzzy": fuzzy}))
+            search = functools.partial(self.embedder.hybrid_query, **only, **({} if fuzzy is None else {"fuzzy": fuzzy}),
+                                       **({} if phrases is None else {"phrases": phrases}),
+                                       **({} if slop is None else {"slop": slop}))
         elif late:
             search = functools.partial(self.embedder.late_query, **only)
         elif doc_ids is not None and not filter_dict and hasattr(self.embedder, "scoped_query"):
@@ -593,7 +606,7 @@ class Pipeline:
             hits = await self.embedder.grouped_query(question, n_groups=top_k, group_size=per_document, **only)
         elif rerank:
             hits = await search(question, n_results=max(top_k, settings.MMRAG_RERANK_CANDIDATES))
-            corrections = hits.get("corrections")
+            corrections, phrase_report = hits.get("corrections"), hits.get("phrases")
             if hits["ids"]:
                 carried = {column: dict(zip(hits["ids"], hits[column])) for column in extra}
                 # (the method is passed on only when one was chosen: an embedder without late interaction keeps its
@@ -606,6 +619,8 @@ class Pipeline:
                     hits[column] = [of_id[found] for found in hits["ids"]]
                 if corrections is not None:
                     hits["corrections"] = corrections
+                if phrase_report is not None:
+                    hits["phrases"] = phrase_report
         else:
             hits = await search(question, n_results=top_k)
         if not hits["ids"]:
@@ -660,7 +675,7 @@ class Pipeline:
                     src["document"] = group["key"]
                     src["document_rank"] = document_rank
                 at += len(group["ids"])
-        made = {"corrections": hits["corrections"]} if "corrections" in hits else {}
+        made = {key: hits[key] for key in ("corrections", "phrases") if key in hits}
         if read is not None:
             return {"answer": text, "sources": ranked, "answerable": read["answerable"],
                     "answers": [{key: answer[key] for key in ANSWER_KEYS} for answer in read["answers"]], **made}
@@ -810,6 +825,22 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
             except ValueError as e:
                 raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
             fuzzy = "" if fuzzy is None else fuzzy      # an explicit false overrides the setting
+        if request.phrases is not None or request.slop is not None:
+            from .lexical import parse_slop, query_phrases
+
+            if not request.hybrid:
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                    detail="`phrases` belongs to hybrid retrieval's lexical leg: send it with `hybrid`")
+            if request.hybrid_leg == "sparse":
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                    detail="`phrases` belongs to the lexical leg: send it without `hybrid_leg`: \"sparse\"")
+            try:
+                if request.slop is not None:
+                    parse_slop(request.slop)
+                if request.phrases:
+                    query_phrases(request.query)      # too long a phrase, too many of them
+            except ValueError as e:
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
         if request.sparse:
             if (multi or request.mmr or request.hybrid or request.group_by_document or request.rerank or request.late
                     or (request.boost is not None and request.boost is not False) or request.like is not None
@@ -951,6 +982,8 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
                                     **({} if not request.sparse else {"sparse": True}),
                                     **({} if request.hybrid_leg is None else {"hybrid_leg": request.hybrid_leg}),
                                     **({} if fuzzy is None else {"fuzzy": fuzzy}),
+                                    **({} if request.phrases is None else {"phrases": request.phrases}),
+                                    **({} if request.slop is None else {"slop": request.slop}),
                                     **({} if window is None else {"passage_tokens": window}),
                                     **({} if not request.extractive_answer else {"extractive": True}),
                                     **({} if not (request.reader or request.reader_answer) else
