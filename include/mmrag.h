@@ -480,6 +480,34 @@ int mmrag_bm25_phrase_topk(const int64_t *term_off, const int32_t *post_row, con
                            int64_t n_live, int64_t sum_dl, float k1, float b, int k, const uint32_t *alive_bits,
                            float *out_scores, int64_t *out_rows, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Significant terms: which terms set a group of rows apart from the collection (csrc/terms.hip; tests/terms_ref.py
+ * restates it).  All pointers dev.  term_off / post_row / df are mmrag_lexical_csr_build's CSR of rows [0, n) and the
+ * live df; group [n] labels every row with its group 0 .. n_groups-1 or -1 for none (dead rows must be -1; a label at
+ * or above n_groups counts for nothing); group_size [n_groups] is the number of rows labelled g; term_bits (NULL: every
+ * term) holds bit t & 31 of word t >> 5 for every term that may be returned.
+ *   group_terms  for group g and term t, with fg = the rows of g holding t (a posting counts once, whatever its tf),
+ *               fgp = (float)fg / (float)group_size[g] and bgp = (float)df[t] / (float)n_live, the pair qualifies when
+ *               group_size[g] > 0, df[t] > 0, fg >= min_count, t is set in term_bits and fgp > bgp; its score is the
+ *               JLH measure (fgp - bgp) * (fgp / bgp), float32, every operation rounded once.  out [n_groups, top]:
+ *               each group's best qualifying terms, score desc, ties to the lower term id, (-inf, -1) padded;
+ *               out_counts holds fg of every returned pair and 0 on padding.  Terms with df < min_count are dropped
+ *               without a visit of their postings (df bounds every fg).  One launch counts MMRAG_TERM_GROUP_WINDOW
+ *               consecutive groups in on-chip histograms; more groups take more launches over the same CSR, and the
+ *               workspace is sized for one launch, not for n_groups.  Synchronises `stream` once per launch to read
+ *               the per-group candidate counts (a group whose qualifying terms overflow its candidate buffer is
+ *               counted again alone into a buffer of n_terms slots); not at all when n_terms fits the buffer.
+ * MMRAG_EINVAL before anything is launched: a null pointer, n_groups outside 1..MMRAG_MAX_TERM_GROUPS, top outside
+ * 1..MMRAG_MAX_K_DEEP, min_count < 1, a negative n, n_terms or n_live, n_live > n.  MMRAG_EWORKSPACE: a workspace below
+ * mmrag_group_terms_workspace_bytes (0 for arguments the call refuses).  n, n_live or n_terms of 0: empty outputs. */
+#define MMRAG_MAX_TERM_GROUPS 4096
+#define MMRAG_TERM_GROUP_WINDOW 256
+size_t mmrag_group_terms_workspace_bytes(int n_groups, int n_terms, int top);
+int mmrag_group_terms(const int64_t *term_off, const int32_t *post_row, const int32_t *df, int n_terms, int64_t n,
+                      const int32_t *group, const int32_t *group_size, int n_groups, int64_t n_live,
+                      const uint32_t *term_bits /* NULL: every term */, int min_count, int top,
+                      float *out_scores, int64_t *out_terms, int32_t *out_counts,
+                      void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Diversified retrieval: maximal-marginal-relevance (MMR) selection of k of a query's C dense hits (what LangChain's
  * max_marginal_relevance_search(k, fetch_k, lambda_mult) does over a Chroma collection).  The reference has no

@@ -384,6 +384,14 @@ def _declare(lib):
     lib.mmrag_chunk_boundaries.argtypes = [c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_int,
                                            c_void_p, ctypes.c_int32, c_int, c_float, c_float, c_float, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.mmrag_group_terms_workspace_bytes.restype = c_size_t
+    lib.mmrag_group_terms_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    lib.mmrag_group_terms.restype = c_int
+    lib.mmrag_group_terms.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_int64,
+                                      c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    # test-only export (not in include/mmrag.h): the sizes at which the significant-terms kernel changes path
+    lib.mmrag_internal_terms_limits.restype = c_int
+    lib.mmrag_internal_terms_limits.argtypes = [c_void_p] * 4
     from .lexical import declare as declare_lexical  # BM25 analyzer, device index and search (csrc/lexical.hip)
 
     declare_lexical(lib)
@@ -2273,6 +2281,47 @@ def impact_topk(term_off: torch.Tensor, post_row: torch.Tensor, post_imp: torch.
             st = lib().mmrag_impact_topk(*args)
     _check(st, "mmrag_impact_topk")
     return out_s, out_r
+
+
+MAX_TERM_GROUPS = 4096   # mmrag_group_terms (MMRAG_MAX_TERM_GROUPS)
+
+
+def terms_limits() -> dict:
+    """csrc/terms.hip's path sizes (mmrag_internal_terms_limits; tests put their cases on them): groups per launch,
+    term ids per workgroup, the longest postings list one wave takes alone, the workgroup's stride over a longer one"""
+    v = [ctypes.c_int(0) for _ in range(4)]
+    _check(lib().mmrag_internal_terms_limits(*[ctypes.byref(x) for x in v]), "mmrag_internal_terms_limits")
+    return dict(zip(("groups", "block_terms", "wave_limit", "block_stride"), (int(x.value) for x in v)))
+
+
+def group_terms_workspace_bytes(n_groups: int, n_terms: int, top: int) -> int:
+    return int(lib().mmrag_group_terms_workspace_bytes(n_groups, n_terms, top))
+
+
+def group_terms(term_off: torch.Tensor, post_row: torch.Tensor, df: torch.Tensor, n_terms: int, n: int,
+                group: torch.Tensor, group_size: torch.Tensor, n_live: int, top: int, min_count: int = 2,
+                term_bits: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """(scores [G, top] float32 desc, terms [G, top] int64, counts [G, top] int32; (-inf, -1, 0) padding) on the device:
+    each group's significant terms by the JLH score over the inverted CSR (mmrag_group_terms).  `group` int32 [>= n]
+    labels the rows (-1: none), `group_size` int32 [G] counts them, `term_bits` int32 words mask the terms."""
+    _dev_check(term_off, post_row, df, group, group_size, term_bits, workspace)
+    G = int(group_size.numel())
+    if group.dtype != torch.int32 or group_size.dtype != torch.int32 or group.numel() < n:
+        raise MMRagNativeError(f"group_terms: group must be int32 [>= {n}] and group_size int32")
+    if term_bits is not None and (term_bits.dtype != torch.int32 or term_bits.numel() * 32 < n_terms):
+        raise MMRagNativeError(f"group_terms: term_bits must hold {n_terms} bits as int32 words")
+    dev = group.device
+    need = group_terms_workspace_bytes(G, n_terms, top)
+    if workspace is None or _nbytes(workspace) < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    out_s, out_t = _topk_out(max(G, 1), max(top, 1), dev)
+    out_c = torch.empty((max(G, 1), max(top, 1)), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().mmrag_group_terms(term_off.data_ptr(), post_row.data_ptr(), df.data_ptr(), int(n_terms), int(n),
+                                       group.data_ptr(), group_size.data_ptr(), G, int(n_live), _ptr(term_bits),
+                                       int(min_count), int(top), out_s.data_ptr(), out_t.data_ptr(), out_c.data_ptr(),
+                                       workspace.data_ptr(), _nbytes(workspace), _stream_ptr(dev)), "mmrag_group_terms")
+    return out_s, out_t, out_c
 
 
 def cross_encoder_workspace_bytes(desc: EncoderDesc, T: int, B: int, f32: bool = False) -> int:

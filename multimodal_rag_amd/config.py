@@ -188,6 +188,12 @@ class Settings:
     # topic clustering (VectorIndex.cluster, csrc/kmeans.hip): the default number of topics of cluster() / GET /topics;
     # 0 (default) = automatic, auto_topics(live rows); else 1 .. 4096
     MMRAG_TOPICS: int = field(default_factory=lambda: int(os.getenv("MMRAG_TOPICS", "0")))
+    # significant terms (VectorIndex.significant_terms, csrc/terms.hip).  MMRAG_TOPIC_TERMS (0..32): the terms each topic
+    # of GET /topics carries when the request does not say; 0 (default) = none, and the response is what it was.
+    # MMRAG_KEYWORD_MIN_LENGTH (>= 1): the fewest code points of a term that may stand in a topic's terms or a
+    # document's keywords
+    MMRAG_TOPIC_TERMS: int = field(default_factory=lambda: int(os.getenv("MMRAG_TOPIC_TERMS", "0")))
+    MMRAG_KEYWORD_MIN_LENGTH: int = field(default_factory=lambda: int(os.getenv("MMRAG_KEYWORD_MIN_LENGTH", "3")))
     # the summary an upload embeds (summarize.py, csrc/summarize.hip).  MMRAG_SUMMARIZER: "fallback" (default: the
     # chunk's first 300 characters) or "extractive": the chunk's most central sentences -- LexRank centrality over the
     # sentence embeddings, a non-redundant set under the length budget by MMR.  An edge of the sentence graph needs a
@@ -228,6 +234,22 @@ class Settings:
         self.lexical_fuzzy()
         self.lexical_slop()
         self.chunker()
+        self.topic_terms()
+        self.keyword_min_length()
+
+    def topic_terms(self) -> int:
+        """MMRAG_TOPIC_TERMS checked: an integer in 0..32"""
+        t = self.MMRAG_TOPIC_TERMS
+        if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t <= 32:
+            raise ValueError(f"MMRAG_TOPIC_TERMS must be an integer in 0..32 (got {t!r})")
+        return t
+
+    def keyword_min_length(self) -> int:
+        """MMRAG_KEYWORD_MIN_LENGTH checked: an integer >= 1"""
+        m = self.MMRAG_KEYWORD_MIN_LENGTH
+        if isinstance(m, bool) or not isinstance(m, int) or m < 1:
+            raise ValueError(f"MMRAG_KEYWORD_MIN_LENGTH must be an integer >= 1 (got {m!r})")
+        return m
 
     def chunker(self) -> str:
         """MMRAG_CHUNKER checked: 'basic' or 'semantic' (tests set the attribute after start-up, so users call this);

@@ -77,6 +77,12 @@ extern "C" {
 int mmrag_internal_lexical_limits(int *score_rows, int *score_terms, int *sort_lds, int *sort_grid, int *scan_terms);
 }
 
+// test-only export of the significant-terms kernel's sizes (terms.hip): groups per launch, term ids per workgroup, the
+// longest postings list one wave takes alone and the workgroup's stride over a longer one.  Host code, no device needed.
+extern "C" {
+int mmrag_internal_terms_limits(int *groups, int *block_terms, int *wave_limit, int *block_stride);
+}
+
 // test-only export of the fuzzy term matcher's sizes (fuzzy.hip): terms per workgroup, patterns per LDS tile, the
 // longest matched term, the most expansions and the code points of a term tile kept in LDS.  Host code, no device needed.
 extern "C" {

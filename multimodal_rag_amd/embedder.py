@@ -60,6 +60,7 @@ _NEEDS_GROUPING = ("grouped_query", "grouped retrieval needs a single-GPU collec
 _NEEDS_DEDUP = ("near_duplicates", "near-duplicate detection needs a single-GPU collection (VectorIndex) with "
                                    "full-precision rows")
 _NEEDS_CLUSTERING = ("cluster", "topic clustering needs a single-GPU collection (VectorIndex) with full-precision rows")
+_NEEDS_TERMS = ("significant_terms", "significant terms need a single-GPU collection (VectorIndex) with stored documents")
 _NEEDS_BOOST = ("boosted_query", "boosted retrieval needs a single-GPU collection (VectorIndex) with full-precision "
                                  "rows")
 _NEEDS_RECOMMEND = ("recommend_query", "recommend retrieval needs a single-GPU collection (VectorIndex) with "
@@ -1044,17 +1045,45 @@ class EmbeddingManager:
         full-precision rows; not the sharded serving path)"""
         return self.collection is None or (hasattr(self.collection, "cluster") and self._has_full_rows())
 
+    def supports_terms(self) -> bool:
+        """True when the collection can report significant terms (a single-GPU VectorIndex, whose lexical leg holds
+        the stored chunks' terms; not the sharded serving path)"""
+        return self.collection is None or hasattr(self.collection, "significant_terms")
+
+    async def document_keywords(self, doc_ids: Sequence[str], top: int = 10, min_count: int = 2) -> List[Dict[str, Any]]:
+        """The keywords of stored documents (VectorIndex.significant_terms over key "doc_id"): per doc_id, in order,
+        {"doc_id", "chunks": its live chunks, "keywords": [{"term", "score", "count", "background"}]} -- the terms of
+        at least MMRAG_KEYWORD_MIN_LENGTH code points that at least `min_count` of its chunks hold and that are more
+        frequent in it than in the collection, best first.  A doc_id nothing is stored under has 0 chunks and no
+        keywords.  ValueError for arguments the collection refuses."""
+        await self._ready()
+        if not self.supports_terms():
+            raise ValueError(_NEEDS_TERMS[1])
+        doc_ids = list(doc_ids)
+        if not doc_ids:
+            return []
+        found = await self._refusing_call("Document keywords", self.collection.significant_terms, key="doc_id",
+                                          values=doc_ids, top=top, min_count=min_count,
+                                          min_length=settings.keyword_min_length())
+        return [{"doc_id": g["group"], "chunks": g["size"], "keywords": g["terms"]} for g in found]
+
     async def cluster_topics(self, n_topics: Optional[int] = None, doc_id: Optional[str] = None,
-                             representatives: int = 3, seed: int = 0) -> Dict[str, Any]:
+                             representatives: int = 3, seed: int = 0, terms: int = 0) -> Dict[str, Any]:
         """The topics of the collection, of one document's chunks with `doc_id` (VectorIndex.cluster): its report
         without the centroid tensor, every representative expanded to {"id", "score", "document", "metadata"}.
-        n_topics None: MMRAG_TOPICS.  ValueError for a cluster count the collection refuses."""
+        n_topics None: MMRAG_TOPICS.  `terms` > 0: every cluster carries its `terms` significant terms (ValueError where
+        supports_terms() is false).  ValueError for a cluster count the collection refuses."""
         await self._ready()
         if not self.supports_clustering():
             raise ValueError(_NEEDS_CLUSTERING[1])
+        more = {}
+        if terms:
+            if not self.supports_terms():
+                raise ValueError(_NEEDS_TERMS[1])
+            more["terms"] = int(terms)
         report = await self._refusing_call("Cluster topics", self.collection.cluster, n_clusters=n_topics,
                                            where={"doc_id": doc_id} if doc_id else None,
-                                           representatives=representatives, seed=seed)
+                                           representatives=representatives, seed=seed, **more)
         report = {key: val for key, val in report.items() if key != "centroids"}
         wanted = [i for c in report["clusters"] for i, _ in c["representatives"]]
         got = self.collection.get(ids=wanted, include=["metadatas", "documents"]) if wanted else {"ids": []}

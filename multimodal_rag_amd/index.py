@@ -591,7 +591,7 @@ class VectorIndex:
 
     def cluster(self, n_clusters: Optional[int] = None, where: Optional[Dict[str, Any]] = None, max_iter: int = 25,
                 tol: float = 1e-3, seed: int = 0, init: Optional[Sequence[str]] = None, representatives: int = 3,
-                return_labels: bool = False) -> Dict[str, Any]:
+                return_labels: bool = False, terms: int = 0) -> Dict[str, Any]:
         """Topics of the collection: spherical k-means over the live rows (matching `where`), on the full-precision rows
         (an FP8 collection's re-scoring plane).  The two hot steps are csrc/kmeans.hip (nearest centroid of every row;
         deterministic per-cluster sums); the rest is torch on [k, d] and a device sort.  It changes no search result.
@@ -610,9 +610,14 @@ class VectorIndex:
         live rows after every assign, "clusters": [{"cluster", "size", "cohesion" (mean cosine to the centroid),
         "representatives": [(id, cosine)] best first, ties to the lower row, "documents": the five most frequent doc_id
         values [(value, count)]}] by size descending then cluster index, "centroids": float32 [k, d] on the device}
-        and, with return_labels, "labels": {id: cluster}.  No matching row: a report without clusters."""
+        and, with return_labels, "labels": {id: cluster}.  No matching row: a report without clusters.
+        `terms` > 0: every cluster also carries "terms", its `terms` significant terms (significant_terms' dicts, under
+        its defaults and MMRAG_KEYWORD_MIN_LENGTH) with the final assign's device labels as the grouping; 0 (default):
+        no such key and no lexical work."""
         if int(max_iter) < 1 or not float(tol) >= 0.0 or int(representatives) < 0:
             raise ValueError("cluster: need max_iter >= 1, tol >= 0 and representatives >= 0")
+        if not 0 <= int(terms) <= _native.MAX_K_DEEP:
+            raise ValueError(f"cluster: terms must be in 0..{_native.MAX_K_DEEP} (got {terms!r})")
         with self._lock:
             self._need_plane("cluster")
             live_rows = self._rows_where(where)
@@ -694,6 +699,13 @@ class VectorIndex:
                     "cohesion": float(score_h[mine].mean()) if mine.size else 0.0,
                     "representatives": [(ids[r], float(score_h[r])) for r in mine[: int(representatives)].tolist()],
                     "documents": sorted(docs.items(), key=lambda kv: -kv[1])[:5]})    # stable: ties by first appearance
+            if int(terms) > 0:
+                from .config import settings
+
+                lists = self._group_term_lists(labels, torch.from_numpy(sizes.astype(np.int32)).to(dev), int(terms), 2,
+                                               settings.keyword_min_length(), ())
+                for c, found in zip(clusters, lists):
+                    c["terms"] = found
             clusters.sort(key=lambda c: (-c["size"], c["cluster"]))
             out = {"n_clusters": k, "iterations": iterations, "converged": converged, "objective": objective,
                    "clusters": clusters, "centroids": cent}
@@ -2417,6 +2429,80 @@ class VectorIndex:
                 out.append([{"term": lex.lexicon.terms(tid, 1)[0], "edits": int(got_e[i, j]), "df": int(df[tid])}
                             for j, tid in enumerate(ids)])
         return out
+
+    # ------------------------------------------------------------------ significant terms ----
+    def _group_term_lists(self, group: torch.Tensor, sizes: torch.Tensor, top: int, min_count: int, min_length: int,
+                          exclude: Sequence[str]) -> List[List[Dict[str, Any]]]:
+        """per group the significant terms of the rows labelled with it (caller holds the lock): LexicalIndex.group_terms
+        under label_mask(min_length, exclude), as [{"term", "score", "count", "background" (the live df)}] best first"""
+        if not 1 <= int(top) <= _native.MAX_K_DEEP:
+            raise ValueError(f"significant terms: top must be in 1..{_native.MAX_K_DEEP} (got {top!r})")
+        if int(min_count) < 1 or int(min_length) < 1:
+            raise ValueError("significant terms: need min_count >= 1 and min_length >= 1")
+        if self._n and not any(self._documents[: self._n]):
+            raise ValueError("significant terms need the stored documents: this collection holds none")
+        lex = self.enable_lexical()
+        scores, terms, counts = lex.group_terms(group, sizes, int(top), int(min_count),
+                                                lex.label_mask(min_length, exclude))
+        scores_h, terms_h, counts_h = scores.cpu().numpy(), terms.cpu().numpy(), counts.cpu().numpy()
+        df = lex.df_host()
+        found = np.unique(terms_h[terms_h >= 0])
+        known = found[found < len(lex.lexicon)]
+        names = {int(t): lex.lexicon.terms(int(t), 1)[0] for t in known.tolist()}
+        return [[{"term": names.get(int(t)), "score": float(s), "count": int(c), "background": int(df[t])}
+                 for s, t, c in zip(scores_h[g], terms_h[g], counts_h[g]) if t >= 0] for g in range(terms_h.shape[0])]
+
+    def significant_terms(self, where: Optional[Dict[str, Any]] = None, key: Optional[str] = None,
+                          values: Optional[Sequence[Any]] = None, labels: Optional[torch.Tensor] = None, top: int = 10,
+                          min_count: int = 2, min_length: int = 3, exclude: Sequence[str] = ()) -> List[Dict[str, Any]]:
+        """The terms that set groups of rows apart from the rest of the collection (csrc/terms.hip): for every group
+        the `top` terms by the JLH score (fgp - bgp) * (fgp / bgp), fgp = the share of the group's rows holding the
+        term, bgp = the share of the live rows holding it, among the terms at least `min_count` rows of the group hold,
+        of at least `min_length` code points, not digits only and not among the `exclude` words.  Exactly one grouping:
+        `where` (one group: the live rows that match), `key` + `values` (one group per value of that metadata key, at
+        most 4096 distinct values; a value no live row has gives size 0 and no terms) or `labels` (a device int32
+        [rows_in_use]: each row's group 0 .. G-1, or -1 for none; dead rows count for nothing).  Statistics are over the
+        live rows.  Builds the lexical index on first use.  Returns [{"group": 0 / the value / the label, "size",
+        "terms": [{"term", "score", "count": rows of the group holding it, "background": live rows holding it}]}]."""
+        given = (where is not None) + (key is not None or values is not None) + (labels is not None)
+        if given != 1 or (key is None) != (values is None):
+            raise ValueError("significant_terms takes exactly one of where, key + values and labels")
+        with self._lock:
+            n, dev = self._n, self.device
+            if labels is not None:
+                if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or labels.numel() != n:
+                    raise ValueError(f"labels must be an int32 device tensor of {n} rows")
+                group = labels.to(dev).contiguous()
+                if self._n_dead:
+                    dead = np.nonzero(self._is_dead(np.arange(n, dtype=np.int64)))[0]
+                    group = group.index_fill(0, torch.from_numpy(dead).to(dev), -1)
+                G = int(group.max().item()) + 1 if n else 0
+                if not 1 <= G <= _native.MAX_TERM_GROUPS:
+                    raise ValueError(f"labels must name 1..{_native.MAX_TERM_GROUPS} groups (found {G})")
+                sizes = torch.bincount(group.long() + 1, minlength=G + 1)[1:].to(torch.int32)
+                names: List[Any] = list(range(G))
+            else:
+                if key is not None:
+                    names = list(values)
+                    if isinstance(values, str) or not 1 <= len(names) <= _native.MAX_TERM_GROUPS:
+                        raise ValueError(f"values must be a list of 1..{_native.MAX_TERM_GROUPS} values")
+                    try:
+                        distinct = len(set(names)) == len(names)
+                    except TypeError:
+                        raise ValueError("values must be hashable") from None
+                    if not distinct:
+                        raise ValueError("values names a value twice")
+                    members = [self._rows_where({key: v}) for v in names]
+                else:
+                    names, members = [0], [self._rows_where(where)]
+                host = np.full(max(n, 1), -1, np.int32)
+                for g, rows in enumerate(members):
+                    host[rows] = g
+                group = torch.from_numpy(host).to(dev)
+                sizes = torch.from_numpy(np.asarray([rows.size for rows in members], np.int32)).to(dev)
+            lists = self._group_term_lists(group, sizes, top, min_count, min_length, exclude)
+            sizes_h = sizes.cpu().tolist()
+        return [{"group": name, "size": int(size), "terms": terms} for name, size, terms in zip(names, sizes_h, lists)]
 
     def lexical_query(self, query_texts: Sequence[str], n_results: int = 10, where: Optional[Dict[str, Any]] = None,
                       include: Sequence[str] = ("metadatas", "documents"), fuzzy=None, phrases=None, slop: int = 0,

@@ -298,6 +298,12 @@ def parse_phrase_mode(mode) -> str:
     return mode
 
 
+def label_allowed(term: str, min_length: int = 3) -> bool:
+    """may an analysed term stand in a topic label or a keyword list (LexicalIndex.label_mask): at least `min_length`
+    code points (as analysed: NFD, so an accent counts as one) and not decimal digits only"""
+    return len(term) >= min_length and not term.isdecimal()
+
+
 def _grow(t: torch.Tensor, need: int) -> torch.Tensor:
     if t.numel() >= need:
         return t
@@ -352,6 +358,9 @@ class LexicalIndex:
         self._counts_build = -1
         self._phrase_ws = None
         self.position_builds = 0          # how many times the plane was built from documents (tests, tools)
+        # significant terms (group_terms / label_mask)
+        self._terms_ws = None
+        self._label_masks: Dict[int, Dict[str, object]] = {}   # min_length -> the rule's verdicts and their bitmap
 
     @property
     def n_terms(self) -> int:
@@ -633,6 +642,62 @@ class LexicalIndex:
     def df_host(self) -> np.ndarray:
         """live df per term (tests)"""
         return self._df[: self.n_terms].cpu().numpy()
+
+    # ------------------------------------------------------------------ significant terms ----
+    def group_terms(self, group: torch.Tensor, group_size, top: int, min_count: int = 2,
+                    term_bits: Optional[torch.Tensor] = None):
+        """Each group's significant terms (csrc/terms.hip; the tests pin it against tests/terms_ref.py): `group` is an
+        int32 device tensor [>= n] labelling every row 0 .. G-1 or -1 (dead rows -1), `group_size` [G] the rows per
+        label.  Returns device (scores [G, top] float32, terms [G, top] int64, counts [G, top] int32): per group the
+        terms with the highest JLH score (fgp - bgp) * (fgp / bgp) among those at least `min_count` of its rows hold,
+        set in `term_bits` (label_mask's bitmap; None: every term) and more frequent in the group than in the live
+        collection; ties to the lower term id, (-inf, -1, 0) padding."""
+        if not isinstance(group, torch.Tensor) or group.dtype != torch.int32 or group.numel() < self.n:
+            raise ValueError(f"group must be an int32 device tensor of at least {self.n} labels")
+        if not isinstance(group_size, torch.Tensor):
+            group_size = torch.from_numpy(np.ascontiguousarray(group_size, np.int32))
+        group_size = group_size.to(device=self.device, dtype=torch.int32).contiguous()
+        G = int(group_size.numel())
+        if not 1 <= G <= _native.MAX_TERM_GROUPS:
+            raise ValueError(f"significant terms take 1..{_native.MAX_TERM_GROUPS} groups, not {G}")
+        if not 1 <= int(top) <= _native.MAX_K_DEEP:
+            raise ValueError(f"top must be in 1..{_native.MAX_K_DEEP}")
+        if int(min_count) < 1:
+            raise ValueError("min_count must be at least 1")
+        term_off, post_row, _ = self._ensure_csr()
+        self._df = _grow(self._df, max(self.n_terms, 1))      # the kernel reads df of every term of the vocabulary
+        need = _native.group_terms_workspace_bytes(G, self.n_terms, int(top))
+        if self._terms_ws is None or self._terms_ws.numel() < need:
+            self._terms_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        return _native.group_terms(term_off, post_row, self._df, self.n_terms, self.n, group.contiguous(), group_size,
+                                   self.n_live, int(top), int(min_count), term_bits, self._terms_ws)
+
+    def label_mask(self, min_length: int = 3, exclude: Sequence[str] = ()) -> torch.Tensor:
+        """The device bitmap (int32 words, bit t & 31 of word t >> 5) of the terms allowed as labels: at least
+        `min_length` code points and not digits only (label_allowed); the terms of the `exclude` words, analysed like
+        a document, are cleared.  Terms of synthetic postings have no strings and are always allowed.  The rule's
+        verdicts are kept per min_length and extended by the terms the lexicon gained, as the term plane is."""
+        min_length = int(min_length)
+        if isinstance(exclude, str):
+            raise ValueError("exclude must be a list of words")
+        V, L = self.n_terms, len(self.lexicon)
+        entry = self._label_masks.setdefault(min_length, {"allowed": np.zeros(0, bool), "dev": None, "terms": -1})
+        known = int(entry["allowed"].size)
+        if L > known:
+            fresh = self.lexicon.terms(known, L - known)
+            entry["allowed"] = np.concatenate([entry["allowed"],
+                                               np.fromiter((label_allowed(s, min_length) for s in fresh), bool, L - known)])
+            entry["dev"] = None
+        drop = [int(t) for t in self.lexicon.analyze_terms(list(exclude))[1] if t >= 0] if len(exclude) else []
+        if not drop and entry["dev"] is not None and entry["terms"] == V:
+            return entry["dev"]
+        bits = np.ones(32 * max((V + 31) // 32, 1), bool)
+        bits[:L] = entry["allowed"]
+        bits[drop] = False
+        dev = torch.from_numpy(np.packbits(bits, bitorder="little").view(np.int32).copy()).to(self.device)
+        if not drop:
+            entry["dev"], entry["terms"] = dev, V
+        return dev
 
     # ------------------------------------------------------------------ positions plane / phrase queries ----
     documents_source = None   # set by the owner: a callable returning the stored documents in row order

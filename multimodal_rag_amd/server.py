@@ -328,6 +328,15 @@ TOPICS_NEEDS = ("cluster_topics", "supports_clustering",
                 "(MMRAG_F8_RESCORE=float16)")
 
 
+# /topics?terms=n and /documents/{doc_id}/keywords: the same for significant terms
+TERMS_NEEDS = ("document_keywords", "supports_terms",
+               "Significant terms are not available with this embedder: they need a single-GPU collection with stored "
+               "documents (EmbeddingManager.document_keywords)")
+MAX_TOPIC_TERMS = 32  # the most terms a topic of /topics carries
+LABEL_TERMS = 3       # the terms a topic's `label` joins
+MAX_KEYWORDS = 100    # the most keywords /documents/{doc_id}/keywords returns
+
+
 # /documents/{doc_id}/related and /related: the same for related-document retrieval
 RELATED_NEEDS = ("related_documents", "supports_related",
                  "Related-document retrieval is not available with this embedder: it needs a single-GPU collection "
@@ -459,22 +468,54 @@ class Pipeline:
                 "pairs": [{"a": a, "b": b, "cosine": c} for a, b, c in report["pairs"][:max(limit, 0)]],
                 "groups": [{"keep": g[0], "duplicates": list(g[1:])} for g in report["groups"]]}
 
-    async def topics(self, n_topics: Optional[int], doc_id: Optional[str], representatives: int, seed: int) -> dict:
-        """the topic report (EmbeddingManager.cluster_topics); `objective` is its last value"""
+    async def topics(self, n_topics: Optional[int], doc_id: Optional[str], representatives: int, seed: int,
+                     terms: Optional[int] = None) -> dict:
+        """the topic report (EmbeddingManager.cluster_topics); `objective` is its last value.  `terms` (None: the
+        MMRAG_TOPIC_TERMS setting) > 0: each topic also carries its significant `terms` and a `label`, the first
+        LABEL_TERMS of them"""
         self._need(TOPICS_NEEDS)
         if not 1 <= representatives <= 10:
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail="representatives must be in 1..10")
+        terms = settings.topic_terms() if terms is None else terms
+        if not 0 <= terms <= MAX_TOPIC_TERMS:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                detail=f"terms must be in 0..{MAX_TOPIC_TERMS}")
+        more = {}
+        if terms:
+            self._need(TERMS_NEEDS)
+            more["terms"] = terms
         try:
             report = await self.embedder.cluster_topics(n_topics=n_topics, doc_id=doc_id,
-                                                        representatives=representatives, seed=seed)
+                                                        representatives=representatives, seed=seed, **more)
         except ValueError as e:
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
+
+        def labelled(c: dict) -> dict:
+            if not terms:
+                return {}
+            found = c.get("terms", [])
+            return {"terms": found, "label": ", ".join(str(t["term"]) for t in found[:LABEL_TERMS])}
+
         return {"n_topics": report["n_clusters"], "iterations": report["iterations"], "converged": report["converged"],
                 "objective": report["objective"][-1] if report["objective"] else None,
                 "topics": [{"topic": c["cluster"], "size": c["size"], "cohesion": c["cohesion"],
                             "representatives": c["representatives"],
-                            "documents": [{"doc_id": v, "count": n} for v, n in c["documents"]]}
+                            "documents": [{"doc_id": v, "count": n} for v, n in c["documents"]], **labelled(c)}
                            for c in report["clusters"]]}
+
+    async def keywords(self, doc_id: str, top: int, min_count: int) -> dict:
+        """a stored document's keywords (EmbeddingManager.document_keywords); 404 when no stored item has `doc_id`"""
+        self._need(TERMS_NEEDS)
+        if not 1 <= top <= MAX_KEYWORDS or min_count < 1:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                detail=f"top must be in 1..{MAX_KEYWORDS} and min_count at least 1")
+        try:
+            found = await self.embedder.document_keywords([doc_id], top=top, min_count=min_count)
+        except ValueError as e:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
+        if not found or not found[0]["chunks"]:
+            raise HTTPException(status_code=status.HTTP_404_NOT_FOUND, detail=f"no stored item has doc_id {doc_id!r}")
+        return found[0]
 
     async def related(self, doc_id: Optional[str], texts: Optional[List[str]], top_k: int,
                       threshold: Optional[float], filter_dict: Optional[Dict] = None) -> dict:
@@ -1050,6 +1091,11 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
         out = await pipe.related(doc_id, None, top_k, threshold)
         return {"doc_id": doc_id, **out, "processing_time": time.time() - t0}
 
+    @app.get("/documents/{doc_id}/keywords")
+    @_as_http_500
+    async def document_keywords(doc_id: str, top: int = 10, min_count: int = 2):
+        return await pipe.keywords(doc_id, top, min_count)
+
     @app.get("/documents")
     @_as_http_500
     async def list_documents():  # api.py:416-429
@@ -1084,8 +1130,8 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
     @app.get("/topics")
     @_as_http_500
     async def topics(n_topics: Optional[int] = None, doc_id: Optional[str] = None, representatives: int = 3,
-                     seed: int = 0):
-        return await pipe.topics(n_topics, doc_id, representatives, seed)
+                     seed: int = 0, terms: Optional[int] = None):
+        return await pipe.topics(n_topics, doc_id, representatives, seed, terms)
 
     @app.get("/stats")
     @_as_http_500
