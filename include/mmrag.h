@@ -1407,6 +1407,46 @@ int mmrag_chunk_boundaries(const void *rows, int64_t ld, int dtype, int d, int64
                            int max_sentences, float threshold, float auto_scale, float penalty, int32_t *out_prev,
                            float *out_best, float *out_tau, float *out_score, void *stream);
 
+/* Answer citations (csrc/attribute.hip): which source stands behind which sentence of an
+ * answer -- similarity-based attribution with the bi-encoder's rows ("this source says something very close to this
+ * sentence"), not entailment.  One workgroup per unit: one answer's sentences (the claims) and its evidence sentences.
+ *
+ * Definition, for unit u with claims x_0 .. x_{C-1} = rows[claim_start[u] .. + claim_len[u]), 1 <= C <= 128, and
+ * evidence e_0 .. e_{E-1} = rows[ev_start[u] .. + ev_len[u]), 0 <= E <= 4096, evidence row j carrying the source ordinal
+ * s_j = ev_source[ev_start[u] + j] (any order; an ordinal outside 0 .. n_sources - 1: the row counts for nothing):
+ *   - S_ij = <x_i, e_j>, float32 as the 128 x 128 tile body forms it (one fixed K order);
+ *   - M_is = max over j with s_j = s of S_ij; J_is = the lowest such j that attains it; a source without evidence in
+ *     the unit has M_is = -inf, J_is = -1;
+ *   - per claim the m best sources with J_is >= 0: M_is descending, ties to the lower s;
+ *   - nothing is summed but S_ij and a maximum is order-free: a unit's output bits do not depend on the batch, the grid
+ *     or its place in the plane; identical calls give identical bits;
+ *   - one launch, no workspace, no host synchronisation, no global atomics; the LDS maxima are over packed (score,
+ *     ~j) keys, so their order cannot show in the output (the call can be captured into a graph).
+ *
+ *   rows        dev [n_rows, ld] of `dtype` MMRAG_F32 / F16 / BF16, pad columns zero, 16-byte aligned; MMRAG_F8E4M3
+ *               returns MMRAG_EUNSUPPORTED.  ld = mmrag_padded_dim(d, dtype) or a larger width of whole 128-byte slabs
+ *   claim_start, claim_len, ev_start, ev_len   dev [n_units] int32 (units may share evidence rows)
+ *   ev_source   dev [n_rows] int32 (indexed like rows)
+ *   n_sources   1..MMRAG_MAX_ATTR_SOURCES      m  1..MMRAG_MAX_CITATIONS      max_claims  1..MMRAG_MAX_CLAIMS
+ *   out_src     dev [n_units, max_claims, m] int32: the source ordinals, best first, -1 padded
+ *   out_ev      dev [n_units, max_claims, m] int32: J_is, a position inside the unit's evidence, -1 padded
+ *   out_score   dev [n_units, max_claims, m] float32: M_is, -inf padded
+ *   out_support dev [n_units, max_claims, n_sources] float32 or NULL: all of M; claims past C are not written
+ * Rows i >= C of a valid unit hold the padding values; E = 0 is valid (every entry is padding).
+ * MMRAG_EINVAL before anything is launched: a null pointer, a bad dtype, shape or pitch, n_rows outside 1..2^31 - 1,
+ * n_units outside 1..2^24, n_sources, m or max_claims out of range.  The tables live on the device and are not read by
+ * the host: a unit whose entry is out of range (claim_len outside 1..min(128, max_claims), ev_len outside 0..4096, rows
+ * outside 0..n_rows) gets NaN in out_score[u, 0, 0], -1 in all of out_src[u] / out_ev[u], and its out_support rows are
+ * not written (mmrag_summary_select's rule). */
+#define MMRAG_MAX_CLAIMS 128
+#define MMRAG_MAX_EVIDENCE 4096
+#define MMRAG_MAX_ATTR_SOURCES 64
+#define MMRAG_MAX_CITATIONS 8
+int mmrag_attribute(const void *rows, int64_t ld, int dtype, int d, int64_t n_rows, const int32_t *claim_start,
+                    const int32_t *claim_len, const int32_t *ev_start, const int32_t *ev_len, int n_units,
+                    const int32_t *ev_source, int n_sources, int m, int max_claims, int32_t *out_src, int32_t *out_ev,
+                    float *out_score, float *out_support, void *stream);
+
 /* Measured peaks for the roofline report ("a measured stream-copy bandwidth and a measured MFMA
  * micro-benchmark peak, fractions against both the vendor and the measured peaks").  Not on the product path.
  *   mmrag_device_info        CU count, maximum shader clock (MHz), HBM bytes of the current device

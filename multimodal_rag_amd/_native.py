@@ -45,6 +45,8 @@ LATE_WINDOW_TOKENS, MAX_LATE_WINDOWS = 16, 32
 # mmrag_summary_select (MMRAG_MAX_SUMMARY_SENTENCES, MMRAG_MAX_SUMMARY_ITERATIONS)
 MAX_SUMMARY_SENTENCES, MAX_SUMMARY_ITERATIONS = 128, 64
 MAX_CHUNK_SENTENCES = 64   # mmrag_chunk_boundaries (MMRAG_MAX_CHUNK_SENTENCES)
+# mmrag_attribute (MMRAG_MAX_CLAIMS, MMRAG_MAX_EVIDENCE, MMRAG_MAX_ATTR_SOURCES, MMRAG_MAX_CITATIONS)
+MAX_CLAIMS, MAX_EVIDENCE, MAX_ATTR_SOURCES, MAX_CITATIONS = 128, 4096, 64, 8
 # mmrag_span_select / mmrag_reader_forward (MMRAG_MAX_READER_TOKENS, MMRAG_MAX_ANSWER_TOKENS, MMRAG_MAX_READER_SPANS)
 MAX_READER_TOKENS, MAX_ANSWER_TOKENS, MAX_READER_SPANS = 512, 64, 8
 _DT2TORCH = {F32: torch.float32, F16: torch.float16, BF16: torch.bfloat16, F8E4M3: torch.float8_e4m3fn}
@@ -384,6 +386,10 @@ def _declare(lib):
     lib.mmrag_chunk_boundaries.argtypes = [c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_int,
                                            c_void_p, ctypes.c_int32, c_int, c_float, c_float, c_float, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.mmrag_attribute.restype = c_int
+    lib.mmrag_attribute.argtypes = [c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]
     lib.mmrag_group_terms_workspace_bytes.restype = c_size_t
     lib.mmrag_group_terms_workspace_bytes.argtypes = [c_int, c_int, c_int]
     lib.mmrag_group_terms.restype = c_int
@@ -1625,6 +1631,48 @@ def chunk_boundaries(rows: torch.Tensor, d: int, doc_start: torch.Tensor, doc_le
                                           score.data_ptr(), _stream_ptr(dev))
     _check(st, "mmrag_chunk_boundaries")
     return prev, best, tau, score
+
+
+def attribute(rows: torch.Tensor, d: int, claim_start: torch.Tensor, claim_len: torch.Tensor, ev_start: torch.Tensor,
+              ev_len: torch.Tensor, ev_source: torch.Tensor, n_sources: int, m: int, max_claims: int,
+              want_support: bool = True, out=None):
+    """Answer citations (include/mmrag.h mmrag_attribute): unit u is the claims rows[claim_start[u] : + claim_len[u]]
+    (1..MAX_CLAIMS) and the evidence rows[ev_start[u] : + ev_len[u]] (0..MAX_EVIDENCE), evidence row j belonging to
+    source ev_source[ev_start[u] + j]; for every claim and source the best-supporting evidence row, then per claim the
+    `m` best sources.  `rows` [n_rows, ld] is a device tensor of a storage dtype (float32 / float16 / bfloat16), pad
+    columns zero; the five tables are DEVICE int32 tensors (the four unit tables [n_units]; ev_source [n_rows]) and are
+    not read by the host: a unit whose entry is out of range gets NaN in score[u, 0, 0].  Returns device tensors (src,
+    ev [n_units, max_claims, m] int32, -1 padded; score [n_units, max_claims, m] float32, -inf padded; support
+    [n_units, max_claims, n_sources] float32 or None unless `want_support`, claims past a unit's not written).  `out`:
+    the four to write into (a caller that replays a captured graph).  One launch on the current stream, no host
+    synchronisation."""
+    who = "attribute"
+    tables = (claim_start, claim_len, ev_start, ev_len, ev_source)
+    _dev_check(rows, *tables)
+    _check_stored_rows(who, rows)
+    for t in tables:
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != rows.device:
+            raise MMRagNativeError(f"{who}: the tables must be contiguous 1-D int32 tensors on the rows' device")
+    n_rows, n_units = int(rows.shape[0]), int(claim_start.shape[0])
+    if any(t.shape[0] != n_units for t in tables[1:4]) or ev_source.shape[0] != n_rows:
+        raise MMRagNativeError(f"{who}: the unit tables need one entry per unit, ev_source one per row")
+    dev = rows.device
+    if out is None:
+        shape = (n_units, max(int(max_claims), 1), max(int(m), 1))
+        out = (torch.empty(shape, dtype=torch.int32, device=dev), torch.empty(shape, dtype=torch.int32, device=dev),
+               torch.empty(shape, dtype=torch.float32, device=dev),
+               torch.empty(shape[:2] + (max(int(n_sources), 1),), dtype=torch.float32, device=dev)
+               if want_support else None)
+    src, ev, score, support = out
+    _dev_check(*out)
+    with torch.cuda.device(dev):
+        st = lib().mmrag_attribute(rows.data_ptr(), rows.shape[1], _TORCH2DT[rows.dtype], int(d), n_rows,
+                                   claim_start.data_ptr(), claim_len.data_ptr(), ev_start.data_ptr(),
+                                   ev_len.data_ptr(), n_units, ev_source.data_ptr(), int(n_sources), int(m),
+                                   int(max_claims), src.data_ptr(), ev.data_ptr(), score.data_ptr(), _ptr(support),
+                                   _stream_ptr(dev))
+    _check(st, "mmrag_attribute")
+    return src, ev, score, support
 
 
 def f8_encode_rows(src: torch.Tensor, d: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -20,7 +20,7 @@ LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libmmrag.so")
 INCLUDE = os.path.join(os.path.dirname(PKG), "include")
 
-SOURCES = ["common.hip", "search.hip", "search_qs.hip", "search_qsw.hip", "search_deep.hip", "search_f8.hip", "rescore.hip", "lexical.hip", "fuzzy.hip", "phrase.hip", "terms.hip", "mmr.hip", "group.hip", "fuse.hip", "simjoin.hip", "kmeans.hip", "scoped.hip", "filtered.hip", "range.hip", "boosted.hip", "recommend.hip", "related.hip", "maxsim.hip", "maxsim_scan.hip", "maxsim_windows.hip", "sparse_expand.hip", "sparse_score.hip", "summarize.hip", "chunk.hip", "encoder.hip", "encoder_f32.hip", "cross_head.hip", "span_head.hip", "image.hip", "microbench.hip", "host_merge.cpp", "tokenizer.cpp", "clip_bpe.cpp"]
+SOURCES = ["common.hip", "search.hip", "search_qs.hip", "search_qsw.hip", "search_deep.hip", "search_f8.hip", "rescore.hip", "lexical.hip", "fuzzy.hip", "phrase.hip", "terms.hip", "mmr.hip", "group.hip", "fuse.hip", "simjoin.hip", "kmeans.hip", "scoped.hip", "filtered.hip", "range.hip", "boosted.hip", "recommend.hip", "related.hip", "maxsim.hip", "maxsim_scan.hip", "maxsim_windows.hip", "sparse_expand.hip", "sparse_score.hip", "summarize.hip", "chunk.hip", "attribute.hip", "encoder.hip", "encoder_f32.hip", "cross_head.hip", "span_head.hip", "image.hip", "microbench.hip", "host_merge.cpp", "tokenizer.cpp", "clip_bpe.cpp"]
 ARCH = "gfx950"
 
 

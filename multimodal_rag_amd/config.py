@@ -221,6 +221,15 @@ class Settings:
     MMRAG_CHUNK_MAX_SENTENCES: int = field(default_factory=lambda: int(os.getenv("MMRAG_CHUNK_MAX_SENTENCES", "64")))
     MMRAG_CHUNK_SEMANTIC_OVERLAP: int = field(
         default_factory=lambda: int(os.getenv("MMRAG_CHUNK_SEMANTIC_OVERLAP", "0")))
+    # answer citations (attribution.py, csrc/attribute.hip): which source stands behind which sentence of an answer, by
+    # the bi-encoder's sentence similarity (not entailment).  MMRAG_CITATIONS: the default of POST /query's `citations`
+    # flag (0: off).  A sentence is supported, and a source cited, at a cosine of at least MMRAG_CITATION_THRESHOLD, in
+    # (-1, 1]; a sentence cites at most MMRAG_CITATION_MAX (1..8) sources.  The default 0.6 is an untuned starting
+    # point: it presumes a trained sentence encoder, and with seeded random weights it means nothing
+    MMRAG_CITATIONS: int = field(default_factory=lambda: int(os.getenv("MMRAG_CITATIONS", "0")))
+    MMRAG_CITATION_THRESHOLD: float = field(
+        default_factory=lambda: float(os.getenv("MMRAG_CITATION_THRESHOLD", "0.6")))
+    MMRAG_CITATION_MAX: int = field(default_factory=lambda: int(os.getenv("MMRAG_CITATION_MAX", "3")))
     # CLIP engines only: embed image items from their pixels (vision tower) instead of their summary text
     MMRAG_EMBED_IMAGE_PIXELS: bool = field(default_factory=lambda: _b("MMRAG_EMBED_IMAGE_PIXELS", "true"))
 
@@ -236,6 +245,17 @@ class Settings:
         self.chunker()
         self.topic_terms()
         self.keyword_min_length()
+        self.citation_parameters()
+
+    def citation_parameters(self) -> dict:
+        """the MMRAG_CITATION* settings as attribution's parameters, checked (the C entry refuses a count out of range
+        too, with less to go on); "default": what a request without the `citations` flag gets"""
+        on, t, most = self.MMRAG_CITATIONS, self.MMRAG_CITATION_THRESHOLD, self.MMRAG_CITATION_MAX
+        if (on not in (0, 1) or isinstance(t, bool) or not isinstance(t, (int, float)) or not -1.0 < float(t) <= 1.0
+                or isinstance(most, bool) or not isinstance(most, int) or not 1 <= most <= 8):
+            raise ValueError("MMRAG_CITATIONS must be 0 or 1, MMRAG_CITATION_THRESHOLD a cosine in (-1, 1], "
+                             f"MMRAG_CITATION_MAX an integer in 1..8 (got {on!r}, {t!r}, {most!r})")
+        return {"default": bool(on), "threshold": float(t), "max_citations": most}
 
     def topic_terms(self) -> int:
         """MMRAG_TOPIC_TERMS checked: an integer in 0..32"""

@@ -1730,6 +1730,43 @@ class EmbeddingManager:
         async with self._encode_lock:
             return await asyncio.to_thread(worker.answer, question, list(passages), max_chars, top_sentences)
 
+    # ---- answer citations: sentence-to-source attribution (attribution.py, csrc/attribute.hip) ----
+    def supports_citations(self) -> bool:
+        """True when attribute_answer can run: supports_summaries' requirement (an engine with encode_device)"""
+        return self.supports_summaries()
+
+    def _attributor(self):
+        from .attribution import DeviceAttributor
+
+        if not self.supports_citations():
+            raise ValueError("answer citations need an engine with encode_device (the single-GPU HIP engine)")
+        dtype = getattr(self.collection, "dtype", None)
+        return DeviceAttributor(self._engine, dtype if dtype is not None else settings.index_dtype())
+
+    async def attribute_answer(self, answer: str, passages: Sequence[str], owner: Optional[Sequence[int]] = None,
+                               threshold: Optional[float] = None, max_citations: Optional[int] = None) -> Dict[str, Any]:
+        """Which source stands behind which sentence of `answer`: `passages` are the sources' raw texts in rank order,
+        owner[i] the source passage i belongs to (default i).  Similarity of sentence embeddings, not entailment
+        (attribution.DeviceAttributor.attribute).  {"citations": per sentence {"start", "end", "text", "score",
+        "supported", "sources": [{"source", "passage", "start", "end", "text", "score"} ...]}, "groundedness",
+        "support": per source, "considered": {"claims", "evidence"}}.  `threshold` (default
+        MMRAG_CITATION_THRESHOLD) is the cosine at which a sentence counts as supported and a source as cited,
+        `max_citations` (default MMRAG_CITATION_MAX, 1..8) the most sources a sentence cites."""
+        return (await self.batch_attribute_answers([answer], [passages], None if owner is None else [owner],
+                                                   threshold, max_citations))[0]
+
+    async def batch_attribute_answers(self, answers: Sequence[str], passages_list: Sequence[Sequence[str]],
+                                      owners: Optional[Sequence[Optional[Sequence[int]]]] = None,
+                                      threshold: Optional[float] = None,
+                                      max_citations: Optional[int] = None) -> List[Dict[str, Any]]:
+        """attribute_answer of answers[i] against passages_list[i]: ONE encoder call and ONE mmrag_attribute launch
+        for all of them"""
+        await self._ready()
+        worker = self._attributor()
+        async with self._encode_lock:
+            return await asyncio.to_thread(worker.attribute, list(answers), [list(p) for p in passages_list], owners,
+                                           None, max_citations, threshold)
+
     # ---- semantic chunking: topic-boundary segmentation (chunking.py, csrc/chunk.hip) ----
     def supports_chunking(self) -> bool:
         """True when chunk_texts can run: supports_summaries' requirement (an engine with encode_device)"""

@@ -162,6 +162,17 @@ class QueryRequest(BaseModel):  # api.py:161-164
     # hits do not answer the question, and the generator is not called.  Works with the modes `passages` works with
     reader: bool = Field(False)
     reader_answer: bool = Field(False)
+    # not in the reference: answer citations (EmbeddingManager.attribute_answer; csrc/attribute.hip).  The response gains
+    # `citations` -- one entry per sentence of `answer`: {start, end, text, score, supported, sources: [{source, passage,
+    # start, end, text, score}]}, `source` an index into `sources`, the span that source's best-supporting sentence in
+    # its raw text passage -- and `groundedness`, the share of the answer's characters in supported sentences; every
+    # source carries `cited_by` (the sentences that cite it) and `support`.  Similarity of sentence embeddings, not
+    # entailment.  A sentence is supported at a cosine of at least `citation_threshold` (default
+    # MMRAG_CITATION_THRESHOLD) and cites at most `max_citations` sources (default MMRAG_CITATION_MAX).  Works with
+    # every mode and every way the answer is made.  Unset: the MMRAG_CITATIONS setting
+    citations: bool = Field(default_factory=lambda: bool(settings.MMRAG_CITATIONS))
+    citation_threshold: Optional[float] = Field(None, gt=-1.0, le=1.0)
+    max_citations: Optional[int] = Field(None, ge=1, le=8)
 
 
 FILTER_MAX_LEAVES, FILTER_MAX_DEPTH = 32, 8
@@ -226,6 +237,17 @@ class ExploreRequest(BaseModel):
     filter: Optional[Dict[str, Any]] = None
     doc_ids: Optional[Annotated[List[Annotated[str, Field(min_length=1, max_length=200)]],
                                 Field(min_length=1, max_length=64)]] = None
+
+
+class AttributeRequest(BaseModel):
+    """POST /attribute: citations for an answer that was generated elsewhere, against `passages` (each its own source)
+    or the raw text passages of stored `ids` (each id a source); no retrieval and no generator call"""
+    answer: str = Field(..., max_length=100_000)
+    passages: Optional[Annotated[List[Annotated[str, Field(max_length=1_000_000)]], Field(max_length=64)]] = None
+    ids: Optional[Annotated[List[Annotated[str, Field(min_length=1, max_length=200)]],
+                            Field(min_length=1, max_length=64)]] = None
+    citation_threshold: Optional[float] = Field(None, gt=-1.0, le=1.0)
+    max_citations: Optional[int] = Field(None, ge=1, le=8)
 
 
 class ChunkRequest(BaseModel):
@@ -358,6 +380,12 @@ CHUNK_NEEDS = ("chunk_texts", "supports_chunking",
                "on the device (the single-GPU HIP engine; EmbeddingManager.chunk_texts)")
 
 
+# `citations` and /attribute: the same for answer citations
+CITATION_NEEDS = ("attribute_answer", "supports_citations",
+                  "Answer citations are not available with this embedder: they need an engine that leaves its "
+                  "embeddings on the device (the single-GPU HIP engine; EmbeddingManager.attribute_answer)")
+
+
 class QueryResponse(BaseModel):  # api.py:167-170
     answer: str
     sources: List[dict]
@@ -369,6 +397,9 @@ class QueryResponse(BaseModel):  # api.py:167-170
     corrections: Optional[List[dict]] = None
     # `phrases` only
     phrases: Optional[List[dict]] = None
+    # `citations` only
+    citations: Optional[List[dict]] = None
+    groundedness: Optional[float] = None
 
 
 class UploadResponse(BaseModel):  # api.py:173-179
@@ -574,7 +605,7 @@ class Pipeline:
                      passage_tokens: Optional[int] = None, sparse: bool = False,
                      hybrid_leg: Optional[str] = None, extractive: bool = False,
                      reader: Optional[str] = None, fuzzy: Any = None, phrases: Optional[bool] = None,
-                     slop: Optional[int] = None) -> Optional[dict]:
+                     slop: Optional[int] = None, citations: Optional[Dict[str, Any]] = None) -> Optional[dict]:
         """vector search -> raw items -> generator (api.py:338-400); None when nothing was retrieved.  `rerank`: search
         max(top_k, MMRAG_RERANK_CANDIDATES) hits, keep the re-ranker's best top_k (`rerank_method` "cross" or "late",
         default MMRAG_RERANK_METHOD; `explain`: late interaction's per-token matches on every source).  `hybrid`: from
@@ -603,7 +634,10 @@ class Pipeline:
         not answer the question), no generator call.  `fuzzy` (with `hybrid` and the lexical leg): the BM25 leg is
         typo-tolerant (EmbeddingManager.hybrid_query) and the result carries the `corrections` it made.  `phrases` /
         `slop` (with `hybrid` and the lexical leg): quoted segments of the question are phrases every hit must hold,
-        and the result carries the `phrases` report"""
+        and the result carries the `phrases` report.  `citations` ({"threshold", "max_citations"}, None where the
+        settings decide; with any mode and any way the answer is made): EmbeddingManager.attribute_answer of the answer
+        against the hits' raw text passages -- the result gains `citations` and `groundedness`, every source its
+        `cited_by` and `support`"""
         multi = variants is not None
         sparse_leg = hybrid and hybrid_leg == "sparse"
         riding = passage_tokens is not None and rerank and rerank_method == "late"
@@ -669,7 +703,7 @@ class Pipeline:
         if passage_tokens is not None and "passages" not in hits:
             hits = await self.embedder.extract_passages(question, hits, window_tokens=passage_tokens)
         quoted = read = None
-        if extractive or reader is not None:
+        if extractive or reader is not None or citations is not None:
             # hit by hit: which source a raw text passage belongs to (the buckets of one call do not say)
             texts, owner = [], []
             for at, found in enumerate(hits["ids"]):
@@ -685,6 +719,9 @@ class Pipeline:
             text = read["answers"][0]["text"] if read["answerable"] else NO_ANSWER_FOUND
         else:
             text = await self._generate(question, hits["ids"], multimodal)
+        cited = None
+        if citations is not None:
+            cited = await self.embedder.attribute_answer(text, texts, owner=owner, **citations)
         ranked = self._sources(hits)
         for on, column, key in ((rerank, "rerank_scores", "rerank_score"), (hybrid, "hybrid_scores", "hybrid_score"),
                                 (mmr, "mmr_scores", "mmr_score"), (late, "late_scores", "late_score"),
@@ -709,6 +746,11 @@ class Pipeline:
         if read is not None:
             for src, found in zip(ranked, read["answer_spans"]):
                 src["answer_spans"] = [{key: span[key] for key in SPAN_KEYS} for span in found]
+        if cited is not None:
+            for at, src in enumerate(ranked):
+                src["cited_by"] = [claim for claim, entry in enumerate(cited["citations"])
+                                   if any(found["source"] == at for found in entry["sources"])]
+                src["support"] = cited["support"][at] if at < len(cited["support"]) else 0.0
         if group_by_document:
             at = 0
             for document_rank, group in enumerate(hits["groups"], 1):
@@ -717,6 +759,8 @@ class Pipeline:
                     src["document_rank"] = document_rank
                 at += len(group["ids"])
         made = {key: hits[key] for key in ("corrections", "phrases") if key in hits}
+        if cited is not None:
+            made.update(citations=cited["citations"], groundedness=cited["groundedness"])
         if read is not None:
             return {"answer": text, "sources": ranked, "answerable": read["answerable"],
                     "answers": [{key: answer[key] for key in ANSWER_KEYS} for answer in read["answers"]], **made}
@@ -752,6 +796,24 @@ class Pipeline:
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
         return {"total": hits["total"], "truncated": hits["truncated"], "hits": self._sources(hits),
                 "facets": hits["facets"]}
+
+    async def attribute(self, answer: str, passages: Optional[List[str]], ids: Optional[List[str]],
+                        threshold: Optional[float], max_citations: Optional[int]) -> dict:
+        """POST /attribute: EmbeddingManager.attribute_answer of `answer` against `passages`, or against the raw text
+        passages of the stored `ids` (source i is ids[i]); no retrieval and no generator call"""
+        self._need(CITATION_NEEDS)
+        owner = None
+        if ids is not None:
+            passages, owner = [], []
+            for at, found in enumerate(ids):
+                for passage in (await self.retriever.retrieve_raw_documents([found]))[self.CONTEXT_KINDS[0]]:
+                    passages.append(passage)
+                    owner.append(at)
+        try:
+            return await self.embedder.attribute_answer(answer, passages, owner=owner, threshold=threshold,
+                                                        max_citations=max_citations)
+        except ValueError as e:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
 
     async def health(self) -> dict:
         parts = {"llm_adapter": await self.llm.health_check(),
@@ -933,6 +995,19 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
                 raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
                                     detail="`reader_answer` and `extractive_answer` both replace the generator's "
                                            "answer: send one of them")
+        if (request.citation_threshold is not None or request.max_citations is not None) and not request.citations:
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                detail="`citation_threshold` and `max_citations` belong to answer citations: send them "
+                                       "with `citations`")
+        cite = None
+        if request.citations:
+            from .attribution import citation_parameters
+
+            pipe._need(CITATION_NEEDS)
+            try:      # a setting changed out of range after start-up
+                cite = citation_parameters(request.citation_threshold, request.max_citations)
+            except ValueError as e:
+                raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
         if request.filter is not None:
             try:
                 _, timed = check_filter(request.filter)
@@ -1028,9 +1103,10 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
                                     **({} if window is None else {"passage_tokens": window}),
                                     **({} if not request.extractive_answer else {"extractive": True}),
                                     **({} if not (request.reader or request.reader_answer) else
-                                       {"reader": "answer" if request.reader_answer else "spans"}))
+                                       {"reader": "answer" if request.reader_answer else "spans"}),
+                                    **({} if cite is None else {"citations": cite}))
         except ValueError as e:
-            if recommend is None:
+            if recommend is None and cite is None:
                 raise
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))   # an id no stored item has
         if out is None:
@@ -1066,6 +1142,17 @@ def create_app(embedder: Optional[Any] = None, retriever: Optional[Any] = None, 
         except ValueError as e:
             raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST, detail=str(e))
         return {"chunks": chunks, "chunker": "semantic", "processing_time": time.time() - t0}
+
+    @app.post("/attribute")
+    @_as_http_500
+    async def attribute_answer(request: AttributeRequest):
+        t0 = time.time()
+        if (request.passages is None) == (request.ids is None):
+            raise HTTPException(status_code=status.HTTP_400_BAD_REQUEST,
+                                detail="Send the evidence as `passages` or as stored `ids`, one of the two")
+        out = await pipe.attribute(request.answer, request.passages, request.ids, request.citation_threshold,
+                                   request.max_citations)
+        return {**out, "processing_time": time.time() - t0}
 
     @app.post("/explore")
     @_as_http_500
